@@ -32,9 +32,20 @@ Workloads (BASELINE.json):
              (idx0, idx1, d0, d1)).  Weak scaling: per-GPU work is fixed, the global query set
              grows with N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline`
-and `cpu_baseline` objects, for every N.  The CPU baseline leg is the only place the oracle is
-used (its output also checks the GPU result on the sample's first queries).
+Prints ONE JSON line on rank 0 (contract in the task statement) carrying a `roofline` object,
+read from the library's kernel timers during the timed steps.  A plain run does nothing else:
+set-up, warm-up, the timed steps, --dump-outputs if given, the line.
+
+  --full               also the CPU baseline (`cpu_baseline`; the only place the oracle is used, its
+                       output also checks the GPU result on the sample's first queries:
+                       `verified_vs_oracle`) and, for N > 1, the exchange timed on its own
+                       (`gather_ms_per_step` in --mode ranks) and the `gather_consistent` checks;
+                       without it those keys are null / absent.
+  --dump-outputs DIR   after the timed steps, writes what the last step handed its caller (rank 0's
+                       gathered result for N > 1) as DIR/idx.npy and DIR/dist.npy, float64 [rows, 2]
+                       (-1 = no neighbour).  Above 64 MB in all, a fixed seeded sample of rows is
+                       written instead, with its row numbers in DIR/rows.npy.  The inputs are seeded,
+                       so two builds run with the same arguments can be compared output for output.
 
 SPECTAVI_BENCH_REHEARSE=1 (one-GPU box): every rank shares cuda:0, the exchange runs over gloo
 on host copies (ranks) / peer copies (inlib); exercises the launcher, sharding, gather and
@@ -77,13 +88,21 @@ def parse_args(argv=None):
     ap.add_argument("--yrows", type=int, default=None,
                     help="query rows PER GPU; default 1,000,000 at --gpus 1, 500,000 otherwise")
     ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline + oracle check and (N > 1) the separate exchange timing and "
+                         "gather consistency checks; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target wall time of the CPU baseline sample, split over the thread counts (0 disables it)")
+                    help="--full: target wall time of the CPU baseline sample, split over the thread counts "
+                         "(0 disables it)")
     ap.add_argument("--verify", type=int, default=64,
-                    help="queries of the CPU-baseline sample also compared with the GPU result (0 = none)")
+                    help="--full: queries of the CPU-baseline sample also compared with the GPU result (0 = none)")
     a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.xrows is None:
         a.xrows = 1_000_000 if a.gpus == 1 else 4_000_000
     if a.yrows is None:
@@ -293,6 +312,28 @@ def synthetic(torch, dev, args, rank):
     return x, y
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor [rows, k], same rows) as
+    path/<name>.npy in float64, exact for the int64 indices (-1 = no neighbour) and int32 / float32
+    distances.  Above DUMP_MAX_BYTES the same fixed, seeded sample of rows (sorted) is taken from
+    every array and its row numbers are written as path/rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(8 * (a.numel() // max(a.shape[0], 1)) for a in arrays.values())
+    keep = None
+    if rows * row_bytes > DUMP_MAX_BYTES:
+        n = (DUMP_MAX_BYTES - 4096 * (len(arrays) + 1)) // (row_bytes + 8)
+        keep = np.sort(np.random.default_rng(0x5eed).choice(rows, n, replace=False))
+        np.save(os.path.join(path, "rows.npy"), keep.astype(np.float64))
+    for name, a in arrays.items():
+        a = a.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), (a if keep is None else a[keep]).astype(np.float64))
+
+
 def line_of(args, world, value, elapsed, roofline, cpu, verified, mode, extra):
     par = ("query-shard x%d, database replicated, RCCL gather of 16 B records" % world) + (
         " (one process per GPU, torch.distributed)" if mode == "ranks" else
@@ -377,9 +418,9 @@ def run_rank(args):
     _, merge_ms = spv.profile_read("l1k2_merge")
 
     # the exchange step on its own ("report its time as a separate line"): K packs +
-    # gathers of the last result, outside the timed region
+    # gathers of the last result, outside the timed region (--full)
     gather_s = 0.0
-    if world > 1:
+    if world > 1 and args.full:
         fence()
         g0 = time.perf_counter()
         for _ in range(args.steps):
@@ -394,8 +435,15 @@ def run_rank(args):
 
     value = float(args.xrows) * args.yrows * world * args.steps / elapsed
     if rank == 0:
+        if args.dump_outputs:
+            if world > 1:
+                from spectavi_amd.sharded import unpack_records
+                gi, gd = unpack_records(torch.cat(gather_bufs))
+            else:
+                gi, gd = idx, d
+            dump_outputs(args.dump_outputs, {"idx": gi, "dist": gd})
         extra = {}
-        if world > 1:
+        if world > 1 and args.full:
             extra["gather_ms_per_step"] = gather_s / args.steps * 1e3  # pack + RCCL gather alone, max over ranks
             # shard 0 of the gathered records must be rank 0's own result
             i0, d0 = gather_bufs[0][:, 0:2].to(dev), gather_bufs[0][:, 2:4].to(dev)
@@ -403,7 +451,7 @@ def run_rank(args):
         if rehearse:
             extra["rehearsal"] = True
         cpu = verified = None
-        if args.cpu_seconds > 0:  # rank 0's host cores, for every N; the other ranks wait at the barrier below
+        if args.full and args.cpu_seconds > 0:  # rank 0's host cores, for every N; the other ranks wait at the barrier below
             nv = min(args.verify, args.yrows)
             cpu, verified = cpu_baseline(x.cpu().numpy(), y.cpu().numpy(), args.cpu_seconds,
                                          idx[:nv].cpu().numpy() if nv else None,
@@ -479,20 +527,23 @@ def run_inlib(args):
     wl, widen_ms = spv.profile_read("gather_widen")
 
     value = float(args.xrows) * args.yrows * world * args.steps / elapsed
-    # every shard of the gathered result against that GPU's own un-gathered result
-    consistent = True
-    for r, dev in enumerate(devs):
-        ir, dr = spv.l1k2(xs[r], ys[r])
-        lo = r * args.yrows
-        consistent = consistent and bool(torch.equal(ir.to(idx.device), idx[lo:lo + args.yrows]) and
-                                         torch.equal(dr.to(d.device), d[lo:lo + args.yrows]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"idx": idx, "dist": d})
     extra = {"gather_ms_per_step": (gather_ms / max(gl, 1)) + (widen_ms / max(wl, 1)),
-             "gather_transport": "ncclGather (ncclCommInitAll clique)" if transport == "rccl" else "hipMemcpyPeerAsync",
-             "gather_consistent": consistent}
+             "gather_transport": "ncclGather (ncclCommInitAll clique)" if transport == "rccl" else "hipMemcpyPeerAsync"}
+    if args.full:
+        # every shard of the gathered result against that GPU's own un-gathered result
+        consistent = True
+        for r, dev in enumerate(devs):
+            ir, dr = spv.l1k2(xs[r], ys[r])
+            lo = r * args.yrows
+            consistent = consistent and bool(torch.equal(ir.to(idx.device), idx[lo:lo + args.yrows]) and
+                                             torch.equal(dr.to(d.device), d[lo:lo + args.yrows]))
+        extra["gather_consistent"] = consistent
     if rehearse:
         extra["rehearsal"] = True
     cpu = verified = None
-    if args.cpu_seconds > 0:
+    if args.full and args.cpu_seconds > 0:
         nv = min(args.verify, args.yrows)
         cpu, verified = cpu_baseline(xs[0].cpu().numpy(), ys[0].cpu().numpy(), args.cpu_seconds,
                                      idx[:nv].cpu().numpy() if nv else None, d[:nv].cpu().numpy() if nv else None, nv)

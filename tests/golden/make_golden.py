@@ -10,7 +10,10 @@ fixture stores the numpy result next to the oracle result when the case is
 small enough for numpy.
 
 Run from the repo root:  python tests/golden/make_golden.py
+(with SPECTAVI_REFERENCE_TREE=<reference checkout> also reference_frontend_signatures.json)
 """
+import ast
+import json
 import os
 import sys
 
@@ -32,6 +35,34 @@ def l1k2_case(name, x, y):
     nidx, ndist = o.numpy_l1_top2(x, y)
     assert np.array_equal(idx, nidx) and np.array_equal(dist, ndist), name
     np.savez_compressed(os.path.join(OUT, name), x=x, y=y, idx=idx, dist=dist)
+
+
+def frontend_signatures(src_dir):
+    """Parameter names and defaults of the reference front-end's hot-path functions and the lengths
+    of its ctypes argtypes lists, read from spectavi/feature.py and spectavi/mvg.py as text (ast):
+    nothing is imported or executed.  tests/test_abi.py holds spectavi_amd's front-end to them."""
+    wanted = {"feature": (["nn_bruteforcel1k2", "nn_cascading_hash", "normalize_to_ubyte_and_multiple_16_dim"],
+                          ["_nn_bruteforcel1k2", "_nn_cascading_hash"]),
+              "mvg": (["dlt_triangulate", "dlt_reprojection_error", "hnormalize", "ransac_fitter",
+                       "seven_point_algorithm"],
+                      ["_dlt_triangulate", "_dlt_reprojection_error", "_ransac_fitter", "_seven_point_algorithm"])}
+    doc = {"functions": {}, "argtypes_len": {}}
+    for mod, (funs, clibs) in wanted.items():
+        tree = ast.parse(open(os.path.join(src_dir, mod + ".py")).read())
+        defs = {n.name: n for n in tree.body if isinstance(n, ast.FunctionDef)}
+        doc["functions"][mod] = {f: {"params": [a.arg for a in defs[f].args.args],
+                                     "defaults": [ast.literal_eval(d) for d in defs[f].args.defaults]} for f in funs}
+        lens = {}
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Attribute):
+                t = node.targets[0]
+                if t.attr == "argtypes" and isinstance(t.value, ast.Name) and t.value.id in clibs:
+                    lens[t.value.id] = len(node.value.elts)
+        assert sorted(lens) == sorted(clibs), (mod, lens)
+        doc["argtypes_len"][mod] = {c: lens[c] for c in clibs}
+    with open(os.path.join(OUT, "reference_frontend_signatures.json"), "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 def main():
@@ -102,6 +133,8 @@ def main():
     if os.path.exists(ref_table):
         np.savez_compressed(os.path.join(OUT, "sift_sur_ogre_table.npz"),
                             table=np.loadtxt(ref_table).astype(np.float32))
+    if os.environ.get("SPECTAVI_REFERENCE_TREE"):
+        frontend_signatures(os.path.join(os.environ["SPECTAVI_REFERENCE_TREE"], "spectavi"))
     print("golden fixtures written to", OUT)
 
 

@@ -110,53 +110,34 @@ def test_no_gpu_is_a_loud_error():
 
 
 def test_frontend_signatures_match_reference_source():
-    """Where the reference tree is mounted (the build container; not the GPU box), check that the
-    hot-path front-end functions keep the reference's parameter names and defaults and that the
-    ctypes argtypes lists have the same length and scalar/pointer pattern.  Source is parsed as
-    text (ast), nothing is imported or executed from the reference."""
-    import ast
+    """The hot-path front-end functions keep the reference's parameter names and defaults, and the
+    ctypes argtypes lists have the reference's lengths.  The reference's side is stored in
+    tests/golden/reference_frontend_signatures.json (tests/golden/make_golden.py: its source parsed
+    as text with ast; nothing imported or executed from it)."""
     import inspect
-    ref_dir = "/root/reference/spectavi"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("reference tree not present")
+    import json
     from spectavi_amd import feature, mvg
 
-    def ref_functions(path):
-        tree = ast.parse(open(path).read())
-        out = {}
-        for node in tree.body:
-            if isinstance(node, ast.FunctionDef):
-                names = [a.arg for a in node.args.args]
-                defaults = [ast.literal_eval(d) for d in node.args.defaults]
-                out[node.name] = (names, defaults)
-        return tree, out
-
-    def ref_argtypes_len(tree, var):
-        for node in ast.walk(tree):
-            if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Attribute):
-                t = node.targets[0]
-                if t.attr == "argtypes" and isinstance(t.value, ast.Name) and t.value.id == var:
-                    return len(node.value.elts)
-        return None
-
-    ftree, ffun = ref_functions(os.path.join(ref_dir, "feature.py"))
-    mtree, mfun = ref_functions(os.path.join(ref_dir, "mvg.py"))
-    for mod, funs, names in ((feature, ffun, ["nn_bruteforcel1k2", "nn_cascading_hash",
-                                              "normalize_to_ubyte_and_multiple_16_dim"]),
-                             (mvg, mfun, ["dlt_triangulate", "dlt_reprojection_error", "hnormalize",
-                                          "ransac_fitter", "seven_point_algorithm"])):
+    with open(os.path.join(ROOT, "tests", "golden", "reference_frontend_signatures.json")) as f:
+        ref = json.load(f)
+    funs, argl = ref["functions"], ref["argtypes_len"]
+    for mod, names in ((feature, ["nn_bruteforcel1k2", "nn_cascading_hash",
+                                  "normalize_to_ubyte_and_multiple_16_dim"]),
+                       (mvg, ["dlt_triangulate", "dlt_reprojection_error", "hnormalize",
+                              "ransac_fitter", "seven_point_algorithm"])):
+        mfun = funs[mod.__name__.rsplit(".", 1)[-1]]
         for name in names:
             sig = inspect.signature(getattr(mod, name))
             ours = list(sig.parameters)
             our_defaults = [p.default for p in sig.parameters.values() if p.default is not inspect._empty]
-            assert ours == funs[name][0], name
-            assert our_defaults == funs[name][1], name
-    assert len(feature._nn_bruteforcel1k2.argtypes) == ref_argtypes_len(ftree, "_nn_bruteforcel1k2") == 8
-    assert len(feature._nn_cascading_hash.argtypes) == ref_argtypes_len(ftree, "_nn_cascading_hash") == 11
-    assert len(mvg._dlt_triangulate.argtypes) == ref_argtypes_len(mtree, "_dlt_triangulate") == 6
-    assert len(mvg._dlt_reprojection_error.argtypes) == ref_argtypes_len(mtree, "_dlt_reprojection_error") == 6
-    assert len(mvg._ransac_fitter.argtypes) == ref_argtypes_len(mtree, "_ransac_fitter") == 14
-    assert len(mvg._seven_point_algorithm.argtypes) == ref_argtypes_len(mtree, "_seven_point_algorithm") == 4
+            assert ours == mfun[name]["params"], name
+            assert our_defaults == mfun[name]["defaults"], name
+    assert len(feature._nn_bruteforcel1k2.argtypes) == argl["feature"]["_nn_bruteforcel1k2"] == 8
+    assert len(feature._nn_cascading_hash.argtypes) == argl["feature"]["_nn_cascading_hash"] == 11
+    assert len(mvg._dlt_triangulate.argtypes) == argl["mvg"]["_dlt_triangulate"] == 6
+    assert len(mvg._dlt_reprojection_error.argtypes) == argl["mvg"]["_dlt_reprojection_error"] == 6
+    assert len(mvg._ransac_fitter.argtypes) == argl["mvg"]["_ransac_fitter"] == 14
+    assert len(mvg._seven_point_algorithm.argtypes) == argl["mvg"]["_seven_point_algorithm"] == 4
 
 
 def test_only_the_declared_api_is_exported():

@@ -102,3 +102,41 @@ def test_host_cpu_reports_model_and_counts():
     model, physical, logical = bench.host_cpu()
     assert isinstance(model, str) and model and logical == os.cpu_count()
     assert physical is None or 1 <= physical <= logical
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    a = bench.parse_args(["--steps", "3", "--warmup", "1"])
+    assert a.steps == 3 and a.warmup == 1 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_exact_and_sampled_deterministically(tmp_path):
+    """--dump-outputs: float64 arrays that hold the indices (-1 = no neighbour) and distances exactly;
+    above the size cap the same seeded rows of every array, their row numbers in rows.npy."""
+    import numpy as np
+    import torch
+    idx = torch.arange(200, dtype=torch.int64).reshape(100, 2)
+    idx[7, 1] = -1
+    dist = torch.arange(200, dtype=torch.int32).reshape(100, 2) * 163
+    bench.dump_outputs(str(tmp_path / "a"), {"idx": idx, "dist": dist})
+    assert sorted(os.listdir(tmp_path / "a")) == ["dist.npy", "idx.npy"]
+    got = np.load(tmp_path / "a" / "idx.npy")
+    assert got.dtype == np.float64 and got[7, 1] == -1 and np.array_equal(got, idx.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "dist.npy"), dist.numpy())
+
+    old = bench.DUMP_MAX_BYTES
+    bench.DUMP_MAX_BYTES = 20000
+    try:
+        for sub in ("b", "c"):
+            bench.dump_outputs(str(tmp_path / sub), {"idx": idx.repeat(10, 1), "dist": dist.repeat(10, 1)})
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    rows = np.load(tmp_path / "b" / "rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 20000
+    assert np.array_equal(np.load(tmp_path / "b" / "idx.npy"), idx.repeat(10, 1).numpy()[rows])
+    for f in ("rows.npy", "idx.npy", "dist.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
