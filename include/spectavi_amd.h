@@ -314,6 +314,12 @@ int spv_dlt_reprojection_error(const double *P0, const double *P1, int npt, cons
 
 /* Scratch bytes needed by spv_l1k2_device for this shape. */
 size_t spv_l1k2_workspace_bytes(int xrows, int yrows, int dim);
+/* The launch plan spv_l1k2_device follows for this shape (on one device; the host-pointer entry
+ * points shard the queries over the devices first): out = {kernel row width in bytes, queries per
+ * lane, database slices, rows per slice, 1 if the wide-row kernel runs else 0}.  The
+ * SPECTAVI_L1K2_Q / SPECTAVI_L1K2_BLOCKS overrides are applied.  Host only, touches no device.
+ * SPV_ERR_INVALID (out untouched) for a shape the kernels do not take. */
+int spv_l1k2_plan(int xrows, int yrows, int dim, int out[5]);
 /* d_x uint8[xrows,dim], d_y uint8[yrows,dim] (16-byte aligned bases),
  * d_idx uint64[yrows,2], d_dist int32[yrows,2], d_ws >= workspace bytes. */
 int spv_l1k2_device(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,

@@ -1893,6 +1893,21 @@ size_t spv_l1k2_workspace_bytes(int xrows, int yrows, int dim) {
   return p.dim_pad < 0 ? 0 : p.total_bytes;
 }
 
+int spv_l1k2_plan(int xrows, int yrows, int dim, int out[5]) {
+  clear_error();
+  if (!out) return set_error(SPV_ERR_INVALID, "null output");
+  if (dim <= 0 || dim % 16 != 0 || xrows < 0 || yrows < 0)
+    return set_error(SPV_ERR_INVALID, "bad shape (xrows=%d, yrows=%d, dim=%d)", xrows, yrows, dim);
+  const L1K2Plan p = l1k2_plan(xrows, yrows, dim);
+  if (p.dim_pad < 0) return set_error(SPV_ERR_INVALID, "dim=%d is not supported by the L1 kernels", dim);
+  out[0] = p.dim_pad;
+  out[1] = p.q;
+  out[2] = p.slices;
+  out[3] = p.slice_rows;
+  out[4] = p.dim_pad > 256 ? 1 : 0;  // l1k2_run: widths above 256 take l1k2_wide_kernel
+  return SPV_OK;
+}
+
 int spv_l1k2_device(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,
                     uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, void *stream) {
   clear_error();

@@ -16,6 +16,8 @@ _vp = ct.c_void_p
 
 clib.spv_l1k2_workspace_bytes.restype = ct.c_size_t
 clib.spv_l1k2_workspace_bytes.argtypes = [ct.c_int, ct.c_int, ct.c_int]
+clib.spv_l1k2_plan.restype = ct.c_int
+clib.spv_l1k2_plan.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.POINTER(ct.c_int)]
 clib.spv_l1k2_device.restype = ct.c_int
 clib.spv_l1k2_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
 clib.spv_cascade_workspace_bytes.restype = ct.c_size_t
@@ -101,6 +103,14 @@ def l1k2(x, y, workspace=None):
         check(clib.spv_l1k2_device(x.data_ptr(), y.data_ptr(), xrows, yrows, dim, idx.data_ptr(),
                                    dist.data_ptr(), ws.data_ptr(), ws.numel(), stream))
     return idx, dist
+
+
+def l1k2_plan(xrows, yrows, dim):
+    """The launch plan l1k2() follows for this shape (spv_l1k2_plan; host only, no device touched):
+    dict of dim_pad (kernel row width), q (queries per lane), slices, slice_rows, wide (bool)."""
+    out = (ct.c_int * 5)()
+    check(clib.spv_l1k2_plan(xrows, yrows, dim, out))
+    return dict(dim_pad=out[0], q=out[1], slices=out[2], slice_rows=out[3], wide=bool(out[4]))
 
 
 def shard_bounds(total, shards):

@@ -245,3 +245,46 @@ def test_ransac_fit_argument_checks_without_gpu():
     assert call(9, 10) == SPV_ERR_INVALID        # fewer than 10 correspondences (the reference's constructor throws)
     assert call(12, -1) == SPV_ERR_INVALID
     assert call(12, 800000000) == SPV_ERR_INVALID
+
+
+def test_l1k2_variant_cases_reach_every_instantiation():
+    """spv_l1k2_plan (host only) on the case table of tests/test_l1k2_variants_gpu.py: every case
+    gets the (width, queries per lane) it is written for, and together the cases reach exactly the
+    instantiations l1k2_run launches (INSTANTIATED in tests/l1k2_variant_cases.py, kept beside the
+    `switch (p.dim_pad)` of l1k2_run) and all three merge forms.  A retuned plan or a new width that
+    leaves a kernel without a case fails here, without a GPU."""
+    from spectavi_amd import device
+    from tests import l1k2_variant_cases as lc
+    reached, merges = set(), set()
+    for case in lc.CASES:
+        xrows, yrows, dim = case[:3]
+        plan = device.l1k2_plan(xrows, yrows, dim)
+        key = lc.plan_key(plan)
+        assert key[:2] == case[5], (lc.case_id(case), plan)
+        assert xrows % plan["slice_rows"] != 0, ("the last slice must be ragged", lc.case_id(case), plan)
+        if key[1] > 1:
+            assert yrows % (256 * key[1]) == 1, ("one live query in the last block", lc.case_id(case))
+        reached.add(key)
+        merges.add(lc.merge_form(plan))
+    assert reached == lc.INSTANTIATED
+    assert merges == lc.MERGE_FORMS
+
+
+def test_l1k2_plan_rejects_bad_shapes():
+    from spectavi_amd import _lib, device
+    for args in ((10, 10, 24), (10, 10, 0), (-1, 10, 16), (10, 10, 2064)):
+        with pytest.raises(_lib.SpectaviError):
+            device.l1k2_plan(*args)
+    assert device.l1k2_plan(0, 1, 2048) == dict(dim_pad=2048, q=1, slices=1, slice_rows=64, wide=True)
+
+
+def test_cascade_variant_cases_reach_every_projection_form():
+    """The case table of tests/test_cascade_variants_gpu.py holds one case per query-side projection
+    instantiation the default selection can pick (by the restatement of that selection in
+    tests/cascade_variant_cases.py; a kernel trace checks the library itself:
+    tools/kernel_coverage.py)."""
+    from tests import cascade_variant_cases as cc
+    targets = [cc.projection_kernels(*c)[1] for c in cc.CASES]
+    assert set(targets) == cc.REACHABLE_QUERY_FORMS and len(targets) == len(set(targets))
+    for dim, m, n, g in cc.CASES:
+        assert dim % 16 == 0 and 1 <= m <= 31 and n >= 1 and 0 <= g <= min(m, 16)

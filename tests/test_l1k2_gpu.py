@@ -89,18 +89,23 @@ def test_errors_are_reported_not_thrown():
         _raw(np.zeros((4, 2064), np.uint8), np.zeros((4, 2064), np.uint8))
 
 
-def test_device_path_and_variants(oracle, monkeypatch):
-    """spv_l1k2_device on resident tensors; every queries-per-lane variant gives the same bits."""
+def test_device_path_and_variants(oracle):
+    """spv_l1k2_device on resident tensors; each queries-per-lane count, as the library's plan picks
+    it from the shape, gives the oracle's bits.  (The SPECTAVI_L1K2_Q override is read once per
+    process: tests/test_knobs_gpu.py runs it in child processes; tests/test_l1k2_variants_gpu.py
+    covers every width at every count.)"""
     import torch
     from spectavi_amd import device
-    x = uniform_u8(5, 3000, 128)
-    y = uniform_u8(6, 2500, 128)
-    oidx, odist = oracle.nn_bruteforcel1k2(x, y, nthreads=8)
-    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-    idx, dist = device.l1k2(xd, yd)
-    torch.cuda.synchronize()
-    assert np.array_equal(idx.cpu().numpy().view(np.uint64), oidx)
-    assert np.array_equal(dist.cpu().numpy(), odist)
+    for m, n, dim, q in ((3000, 2500, 128, 1), (16384 + 37, 2049, 128, 2), (65536 + 27, 1025, 64, 4)):
+        assert device.l1k2_plan(m, n, dim)["q"] == q
+        x = uniform_u8(5, m, dim)
+        y = uniform_u8(6, n, dim)
+        oidx, odist = oracle.nn_bruteforcel1k2(x, y, nthreads=8)
+        xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+        idx, dist = device.l1k2(xd, yd)
+        torch.cuda.synchronize()
+        assert np.array_equal(idx.cpu().numpy().view(np.uint64), oidx), (m, n, dim, q)
+        assert np.array_equal(dist.cpu().numpy(), odist), (m, n, dim, q)
 
 
 def test_full_size_properties_256k(oracle):
