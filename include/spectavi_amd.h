@@ -106,8 +106,8 @@ void spv_release_cached_memory(void);
 const char *spv_version(void);
 
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
- * "l1k2_tile", "l1k2_merge", "cascade_project", "cascade_buckets",
- * "cascade_probe_refine", "dlt") are bracketed by hipEvents recorded on the
+ * "l1k2_tile", "l1k2_merge", "bruteforce", "bruteforce_merge", "cascade_project",
+ * "cascade_buckets", "cascade_probe_refine", "dlt") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
  * last reset. */
@@ -116,7 +116,9 @@ void spv_profile_reset(void);
 int spv_profile_read(const char *kernel, long long *launches, double *total_ms);
 /* Diagnostic: sustained issue rate of one VALU instruction with register
  * operands only (op: 0 v_sad_hi_u8, 1 v_sad_u8, 2 v_sad_u16, 3 v_xor+v_add,
- * 4 v_fma_f32, 5 v_dot4_u32_u8, 6 v_med3_u32) and the shader clock held. */
+ * 4 v_fma_f32, 5 v_dot4_u32_u8, 6 v_med3_u32, 7 v_sub_f32, 8 v_pk_add_f32, 9 v_pk_mul_f32,
+ * 10 the correctly rounded sqrtf sequence) and the shader clock held.  A packed instruction
+ * counts as one op (two results); op 10 counts one sequence per op. */
 int spv_microbench_valu(int op, int blocks, int iters, double *lane_ops_per_s, double *clock_ghz);
 /* Diagnostic: memory ceilings.  mode 0 = 16-byte-per-lane streaming copy of table_bytes
  * (bytes read + written per second); mode 1 = random 128-byte row gathers, 8 lanes per row,
@@ -140,6 +142,33 @@ int spv_microbench_memory(int mode, size_t table_bytes, double *bytes_per_s);
  * reference uses it as the OpenMP team size, src/BruteForceNnL1K2.h:92). */
 void nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
                        int nthreads, NdArray *outidx, NdArray *outdist);
+
+/* Exact p-norm k-nearest-neighbour of every query row y against every database row x.
+ * Replaces reference src/Spectavi.cpp:258-282 (BruteForceNn::find_neighbours, src/BruteForceNn.h).
+ *   x: float32 (nn_bruteforce) or int32 (nn_bruteforcei) [xrows, dim], y: same type [yrows, dim];
+ *   outidx: callee-allocated size_t[yrows,k] (col 0 = nearest), outdist: float / int [yrows,k].
+ * Distance of (y_i, x_j): s = 0; for c = 0..dim-1 in order: s = s + t_c, every operation rounded on
+ * its own (no FMA, no reassociation), with d = float(x - y) (int rows: float(int32(x - y))) and
+ *   p == 1: t = |d|   p == 2: t = d*d   p == 0.5: t = sqrtf(|d|) (correctly rounded)
+ *   other p: t = float(pow((double)|d|, (double)p))
+ * where p is the float argument widened to double; int rows truncate every t to int and sum in
+ * int32.  For p in {1, 2, 0.5} the distances are bit-identical to that arithmetic; for other p the
+ * device pow may differ from glibc's by an ulp of the double (int rows: a term whose pow lands an
+ * ulp below an integer truncates one lower, so a distance may be up to dim units off).  The int domain is: no int32 overflow
+ * in x - y, t or s; outside it, and for NaN / inf inputs, the result is unspecified (no fault).
+ * Result per query: the k smallest (dist, idx) pairs in lexicographic order, ascending -- what the
+ * reference's strict-< scan in ascending idx yields where it is defined (it is not on a tie at the
+ * k-th place, src/BruteForceNn.h:93-116).  Missing neighbours (xrows < k) fill the end of the row
+ * with idx (size_t)-1 and dist +inf (float) / INT_MAX (int); the reference leaves them unwritten.
+ * `mu` is accepted and ignored: the result is always exact (with mu <= 0 the reference's prune is
+ * exact too; with mu > 0 it is approximate and scan-order dependent).
+ * Limits: 1 <= k <= 64, 1 <= dim <= 2048 (any dim), p finite and > 0, xrows, yrows >= 0; outside
+ * them SPV_ERR_INVALID and the outputs are not allocated.  One device: the first one selected by
+ * spv_set_device / spv_set_devices (sharding over the device list is not implemented). */
+void nn_bruteforce(const float *x, const float *y, int xrows, int yrows, int dim, int k, float p, float mu,
+                   NdArray *outidx, NdArray *outdist);
+void nn_bruteforcei(const int *x, const int *y, int xrows, int yrows, int dim, int k, float p, float mu,
+                    NdArray *outidx, NdArray *outdist);
 
 /* Cascade-hash candidate prefilter + L1 refine.  Replaces reference
  * src/Spectavi.cpp:321-336 (CascadingHashNn, src/CascadingHashNn.h:86-245).
@@ -206,6 +235,11 @@ void ransac_fitter(const double *x0, const double *x1, int npt, double required_
 /* idx: uint64[yrows,2], dist: int32[yrows,2]. */
 int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
                           uint64_t *idx, int32_t *dist);
+
+/* nn_bruteforce (is_int = 0: float32 rows, float32 dist) / nn_bruteforcei (is_int = 1: int32 rows,
+ * int32 dist) with caller-allocated idx uint64[yrows,k], dist [yrows,k]. */
+int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
+                      uint64_t *idx, void *dist);
 
 /* As nn_cascading_hash but with explicit hyperplanes: dict is
  * float32[n, dim, m] (table-major, then dim, then bit: the fill order of
@@ -356,6 +390,17 @@ int spv_dlt_gathered_device(int ndev, const int *devices, const double *P0, cons
                             double *d_dst, int want_error, int transport);
 /* First row of shard r of `total` rows over `shards` contiguous balanced shards (r = shards: total). */
 long long spv_shard_lo(long long total, int shards, int r);
+
+/* Exact p-norm k-NN with everything resident: d_x, d_y float32 or int32 [rows, dim] (4-byte
+ * aligned), d_idx uint64[yrows,k], d_dist float32 / int32 [yrows,k], contract as nn_bruteforce.
+ * slices = 0: the automatic plan, which needs spv_bruteforce_workspace_bytes(xrows, yrows, dim, k)
+ * bytes of d_ws (8-byte aligned).  slices > 0 forces that many database slices (fewer if some would
+ * be empty; at most 65535) and needs max(that, yrows * slices * k * 8) bytes.  The result does not
+ * depend on the slice count.  Kernel names for spv_profile_read: "bruteforce", "bruteforce_merge". */
+size_t spv_bruteforce_workspace_bytes(int xrows, int yrows, int dim, int k);
+int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrows, int yrows, int dim, int k,
+                          float p, int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes,
+                          void *stream);
 
 /* Scratch bytes needed by spv_cascade_device. */
 size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g);

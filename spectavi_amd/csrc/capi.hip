@@ -754,6 +754,32 @@ int host_l1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
   });
 }
 
+// Exact p-norm k-NN through host pointers, on the first selected device (no sharding).
+int host_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
+                    uint64_t *idx, void *dist) {
+  SPV_TRY(bruteforce_check(xrows, yrows, dim, k, p));
+  if (yrows == 0) return SPV_OK;
+  if (!y || !idx || !dist || (xrows > 0 && !x)) return set_error(SPV_ERR_INVALID, "null pointer");
+  SPV_TRY(ensure_device());
+  int dev = 0;
+  SPV_HIP_CHECK(hipGetDevice(&dev));
+  const size_t xb = (size_t)xrows * dim * 4, yb = (size_t)yrows * dim * 4;
+  const size_t ib = (size_t)yrows * k * sizeof(uint64_t), db = (size_t)yrows * k * 4;
+  const size_t wsb = bruteforce_plan(xrows, yrows, k, 0).part_bytes;
+  DevBuf dx, dy, di, dd, ws;
+  SPV_TRY(dx.alloc(xb));
+  SPV_TRY(dy.alloc(yb));
+  SPV_TRY(di.alloc(ib));
+  SPV_TRY(dd.alloc(db));
+  SPV_TRY(ws.alloc(wsb));
+  hipStream_t st = hipStreamPerThread;
+  if (xb) SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, xb, hipMemcpyHostToDevice, st));
+  SPV_HIP_CHECK(hipMemcpyAsync(dy.p, y, yb, hipMemcpyHostToDevice, st));
+  SPV_TRY(bruteforce_run(dx.p, dy.p, is_int, xrows, yrows, dim, k, p, 0, di.as<uint64_t>(), dd.p, ws.p, wsb, st));
+  SPV_HIP_CHECK(hipMemcpyAsync(dist, dd.p, db, hipMemcpyDeviceToHost, st));
+  return download(dev, idx, di.p, ib, st);
+}
+
 int check_cascade_args(int xrows, int yrows, int dim, int m, int n, int g) {
   if (xrows < 0 || yrows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
   if (dim <= 0 || dim % 16 != 0)
@@ -1603,6 +1629,29 @@ void nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows,
   });
 }
 
+static void nn_bruteforce_ref(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k,
+                              float p, float mu, NdArray *outidx, NdArray *outdist) {
+  (void)mu;  // the result is always exact (include/spectavi_amd.h)
+  clear_error();
+  if (bruteforce_check(xrows, yrows, dim, k, p) != SPV_OK) return;
+  (void)host_guard([&] {
+    SPV_TRY(alloc_out(outidx, (size_t)yrows, (size_t)k, (int)sizeof(size_t)));
+    SPV_TRY(alloc_out(outdist, (size_t)yrows, (size_t)k, 4));
+    return host_bruteforce(x, y, is_int, xrows, yrows, dim, k, p, static_cast<uint64_t *>(outidx->m_data),
+                           outdist->m_data);
+  });
+}
+
+void nn_bruteforce(const float *x, const float *y, int xrows, int yrows, int dim, int k, float p, float mu,
+                   NdArray *outidx, NdArray *outdist) {
+  nn_bruteforce_ref(x, y, 0, xrows, yrows, dim, k, p, mu, outidx, outdist);
+}
+
+void nn_bruteforcei(const int *x, const int *y, int xrows, int yrows, int dim, int k, float p, float mu,
+                    NdArray *outidx, NdArray *outdist) {
+  nn_bruteforce_ref(x, y, 1, xrows, yrows, dim, k, p, mu, outidx, outdist);
+}
+
 void nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int dim, int k,
                        int hash_bit_rate, int num_hash_tables, int num_candidate_neighbours,
                        NdArray *outidx, NdArray *outdist) {
@@ -1651,6 +1700,12 @@ int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yro
                           uint64_t *idx, int32_t *dist) {
   clear_error();
   return host_guard([&] { return host_l1k2(x, y, xrows, yrows, dim, idx, dist); });
+}
+
+int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
+                      uint64_t *idx, void *dist) {
+  clear_error();
+  return host_guard([&] { return host_bruteforce(x, y, is_int, xrows, yrows, dim, k, p, idx, dist); });
 }
 
 int spv_nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int dim, int m,
@@ -1913,6 +1968,24 @@ int spv_l1k2_device(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows
   clear_error();
   return guard([&] { return l1k2_run(d_x, d_y, xrows, yrows, dim, d_idx, d_dist, d_ws, ws_bytes,
                   static_cast<hipStream_t>(stream)); });
+}
+
+size_t spv_bruteforce_workspace_bytes(int xrows, int yrows, int dim, int k) {
+  if (bruteforce_check(xrows, yrows, dim, k, 1.f) != SPV_OK) {
+    clear_error();
+    return 0;
+  }
+  return bruteforce_plan(xrows, yrows, k, 0).part_bytes;
+}
+
+int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrows, int yrows, int dim, int k,
+                          float p, int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes,
+                          void *stream) {
+  clear_error();
+  return guard([&] {
+    return bruteforce_run(d_x, d_y, is_int, xrows, yrows, dim, k, p, slices, d_idx, d_dist, d_ws, ws_bytes,
+                          static_cast<hipStream_t>(stream));
+  });
 }
 
 size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g) {

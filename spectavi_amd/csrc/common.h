@@ -66,6 +66,21 @@ L1K2Plan l1k2_plan(int xrows, int yrows, int dim);
 int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,
              uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
 
+// ---- exact p-norm k-NN (bruteforce.hip) ---------------------------------------------
+struct BruteForcePlan {
+  int qblocks;       // query blocks of 256
+  int slice_rows;    // database rows per slice
+  int slices;        // database slices
+  size_t part_bytes; // per-slice top-k keys (the whole workspace)
+};
+int bruteforce_p_kind(double p);  // 0: p = 1, 1: p = 2, 2: p = 0.5, 3: any other p
+// SPV_ERR_INVALID (message set) outside the limits of include/spectavi_amd.h; touches no device
+int bruteforce_check(int xrows, int yrows, int dim, int k, float p);
+// slices > 0 forces that many database slices (fewer if some would be empty)
+BruteForcePlan bruteforce_plan(int xrows, int yrows, int k, int slices);
+int bruteforce_run(const void *d_x, const void *d_y, int is_int, int xrows, int yrows, int dim, int k, float p,
+                   int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
 // ---- cascade hash (cascade.hip) -----------------------------------------------------
 size_t cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g);
 int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int dim, int m, int n,

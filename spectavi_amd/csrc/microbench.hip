@@ -9,7 +9,8 @@
 namespace spv {
 namespace {
 
-enum Op { OP_SAD_HI = 0, OP_SAD = 1, OP_SAD_U16 = 2, OP_ADD = 3, OP_FMA = 4, OP_DOT4 = 5, OP_MED3 = 6 };
+enum Op { OP_SAD_HI = 0, OP_SAD = 1, OP_SAD_U16 = 2, OP_ADD = 3, OP_FMA = 4, OP_DOT4 = 5, OP_MED3 = 6, OP_SUB_F32 = 7,
+          OP_PK_ADD = 8, OP_PK_MUL = 9, OP_SQRT = 10 };
 
 template <int OP>
 __device__ __forceinline__ uint32_t apply(uint32_t q, uint32_t x, uint32_t a) {
@@ -19,6 +20,10 @@ __device__ __forceinline__ uint32_t apply(uint32_t q, uint32_t x, uint32_t a) {
   if (OP == OP_ADD) return a + (q ^ x);  // v_xor + v_add (2 full-rate ops)
   if (OP == OP_FMA) return __float_as_uint(__builtin_fmaf(__uint_as_float(q), __uint_as_float(x), __uint_as_float(a)));
   if (OP == OP_DOT4) return __builtin_amdgcn_udot4(q, x, a, false);
+  if (OP == OP_SUB_F32) return __float_as_uint(__uint_as_float(a) - __uint_as_float(q));
+  // the sqrtf of bruteforce.hip's p = 0.5 term (v_sqrt_f32 + the correctly-rounding fix-up); the
+  // operand is kept finite and non-negative by clearing the sign and top exponent bit
+  if (OP == OP_SQRT) return __float_as_uint(sqrtf(__uint_as_float((a ^ q) & 0x3FFFFFFFu)));
   return max(min(q, a), min(max(q, a), x));  // v_med3_u32
 }
 
@@ -56,21 +61,64 @@ __global__ __launch_bounds__(256) void rate_kernel(uint32_t *out, unsigned long 
   }
 }
 
+// Packed f32 (v_pk_add_f32 / v_pk_mul_f32): 8 float2 accumulators, the same 64 instructions per
+// iteration and per lane as rate_kernel (each instruction produces two results).
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+template <int OP>
+__global__ __launch_bounds__(256) void pk_rate_kernel(uint32_t *out, unsigned long long *clk, int iters,
+                                                      uint32_t seed) {
+  constexpr int ACCS = 8;
+  f2 a[ACCS], q[8];
+#pragma unroll
+  for (int i = 0; i < ACCS; ++i) a[i] = f2{1.0f + threadIdx.x * 1e-3f, 1.0f + i * 1e-3f};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) q[i] = f2{(seed & 0xFF) * 1e-9f + i * 1e-9f, 1e-9f * (i + 1)};
+  if (OP == OP_PK_MUL)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[i] += f2{1.0f, 1.0f};  // factors near one keep the products finite
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+#pragma unroll
+      for (int i = 0; i < ACCS; ++i) a[i] = OP == OP_PK_MUL ? a[i] * q[(r + i) & 7] : a[i] + q[(r + i) & 7];
+    }
+    asm volatile("" : "+v"(q[it & 7]));  // keep the operands opaque so nothing is hoisted
+  }
+  const unsigned long long c1 = __builtin_amdgcn_s_memtime();
+  const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < ACCS; ++i) s += a[i].x + a[i].y;
+  out[blockIdx.x * blockDim.x + threadIdx.x] = __float_as_uint(s);
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    clk[0] = c1 - c0;
+    clk[1] = r1 - r0;
+  }
+}
+
 template <int OP>
 void launch(int blocks, uint32_t *out, unsigned long long *clk, int iters) {
-  hipLaunchKernelGGL((rate_kernel<OP>), dim3(blocks), dim3(256), 0, nullptr, out, clk, iters, 12345u);
+  if constexpr (OP == OP_PK_ADD || OP == OP_PK_MUL)
+    hipLaunchKernelGGL((pk_rate_kernel<OP>), dim3(blocks), dim3(256), 0, nullptr, out, clk, iters, 12345u);
+  else
+    hipLaunchKernelGGL((rate_kernel<OP>), dim3(blocks), dim3(256), 0, nullptr, out, clk, iters, 12345u);
 }
 
 }  // namespace
 }  // namespace spv
 
 // op: 0 v_sad_hi_u8, 1 v_sad_u8, 2 v_sad_u16, 3 v_xor+v_add (counted as 1), 4 v_fma_f32,
-// 5 v_dot4_u32_u8, 6 v_med3_u32.  Each lane executes iters*64 ops.
+// 5 v_dot4_u32_u8, 6 v_med3_u32, 7 v_sub_f32, 8 v_pk_add_f32, 9 v_pk_mul_f32 (one packed
+// instruction = one op), 10 v_xor + v_and + the sqrtf sequence (counted as 1).  Each lane executes
+// iters*64 ops.
 extern "C" int spv_microbench_valu(int op, int blocks, int iters, double *lane_ops_per_s,
                                    double *clock_ghz) {
   using namespace spv;
   clear_error();
-  if (blocks <= 0 || iters <= 0 || !lane_ops_per_s || !clock_ghz || op < 0 || op > 6)
+  if (blocks <= 0 || iters <= 0 || !lane_ops_per_s || !clock_ghz || op < 0 || op > 10)
     return set_error(SPV_ERR_INVALID, "bad args");
   int s = ensure_device();
   if (s != SPV_OK) return s;
@@ -90,7 +138,11 @@ extern "C" int spv_microbench_valu(int op, int blocks, int iters, double *lane_o
       case 3: launch<OP_ADD>(blocks, out, clk, iters); break;
       case 4: launch<OP_FMA>(blocks, out, clk, iters); break;
       case 5: launch<OP_DOT4>(blocks, out, clk, iters); break;
-      default: launch<OP_MED3>(blocks, out, clk, iters); break;
+      case 6: launch<OP_MED3>(blocks, out, clk, iters); break;
+      case 7: launch<OP_SUB_F32>(blocks, out, clk, iters); break;
+      case 8: launch<OP_PK_ADD>(blocks, out, clk, iters); break;
+      case 9: launch<OP_PK_MUL>(blocks, out, clk, iters); break;
+      default: launch<OP_SQRT>(blocks, out, clk, iters); break;
     }
   }
   SPV_HIP_CHECK(hipEventRecord(e1, nullptr));

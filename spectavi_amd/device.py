@@ -105,6 +105,42 @@ def l1k2(x, y, workspace=None):
     return idx, dist
 
 
+clib.spv_bruteforce_workspace_bytes.restype = ct.c_size_t
+clib.spv_bruteforce_workspace_bytes.argtypes = [ct.c_int] * 4
+clib.spv_bruteforce_device.restype = ct.c_int
+clib.spv_bruteforce_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_float,
+                                       ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
+
+
+def bruteforce(x, y, k=2, p=2.0, workspace=None, slices=0):
+    """Exact p-norm k-NN on device (the contract of feature.nn_bruteforce): x [M,D], y [N,D] both
+    float32 or both int32 CUDA tensors.  Returns (idx int64 [N,k] -- the ABI's size_t bits, -1 = no
+    neighbour --, dist float32 / int32 [N,k]).  `slices` > 0 forces that many database slices (the
+    result does not depend on it).  Asynchronous on the current stream."""
+    from spectavi_amd.feature import check_bruteforce_args
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.int32):
+        raise TypeError("x must be a float32 or int32 tensor")
+    _need(x, x.dtype, "x")
+    _need(y, x.dtype, "y")
+    check_bruteforce_args(tuple(x.shape), tuple(y.shape), k, p)
+    if int(slices) < 0:
+        raise ValueError("slices must be >= 0")
+    k, slices = int(k), int(slices)
+    xrows, dim = x.shape
+    yrows = y.shape[0]
+    idx = torch.empty((yrows, k), dtype=torch.int64, device=y.device)
+    dist = torch.empty((yrows, k), dtype=x.dtype, device=y.device)
+    nbytes = clib.spv_bruteforce_workspace_bytes(xrows, yrows, dim, k)
+    if slices > 0:
+        nbytes = max(nbytes, yrows * slices * k * 8)
+    with _on_device_of(x, y) as stream:
+        ws = (workspace or _default_ws).get(nbytes, y.device)
+        check(clib.spv_bruteforce_device(x.data_ptr(), y.data_ptr(), int(x.dtype == torch.int32), xrows, yrows, dim,
+                                         k, float(p), slices, idx.data_ptr(), dist.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), stream))
+    return idx, dist
+
+
 def l1k2_plan(xrows, yrows, dim):
     """The launch plan l1k2() follows for this shape (spv_l1k2_plan; host only, no device touched):
     dict of dim_pad (kernel row width), q (queries per lane), slices, slice_rows, wide (bool)."""

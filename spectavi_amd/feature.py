@@ -58,6 +58,96 @@ def nn_bruteforcel1k2(x, y, nthreads=1):
 
 
 # ==================================================================================
+# brute-force p-norm k-NN     (reference spectavi/feature.py:204-289)
+# ==================================================================================
+_nn_bruteforce = clib.nn_bruteforce
+_nn_bruteforce.restype = None
+_nn_bruteforce.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
+                           ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
+                           ct.c_int,
+                           ct.c_int,
+                           ct.c_int,
+                           ct.c_int,
+                           ct.c_float,
+                           ct.c_float,
+                           ct.POINTER(NdArray),
+                           ct.POINTER(NdArray), ]
+
+_nn_bruteforcei = clib.nn_bruteforcei
+_nn_bruteforcei.restype = None
+_nn_bruteforcei.argtypes = [ndpointer(ct.c_int, flags="C_CONTIGUOUS"),
+                            ndpointer(ct.c_int, flags="C_CONTIGUOUS"),
+                            ct.c_int,
+                            ct.c_int,
+                            ct.c_int,
+                            ct.c_int,
+                            ct.c_float,
+                            ct.c_float,
+                            ct.POINTER(NdArray),
+                            ct.POINTER(NdArray), ]
+
+BRUTEFORCE_MAX_K = 64
+BRUTEFORCE_MAX_DIM = 2048
+
+
+def check_bruteforce_args(xshape, yshape, k, p):
+    """The limits of nn_bruteforce (include/spectavi_amd.h) as ValueError, before any device work."""
+    if len(xshape) != 2 or len(yshape) != 2:
+        raise ValueError("x and y must be 2-D")
+    if xshape[1] != yshape[1]:
+        raise ValueError("x and y must have the same number of columns (%d != %d)" % (xshape[1], yshape[1]))
+    if not 1 <= xshape[1] <= BRUTEFORCE_MAX_DIM:
+        raise ValueError("dim=%d outside [1, %d]" % (xshape[1], BRUTEFORCE_MAX_DIM))
+    if int(k) != k or not 1 <= k <= BRUTEFORCE_MAX_K:
+        raise ValueError("k=%r outside [1, %d]" % (k, BRUTEFORCE_MAX_K))
+    pf = np.float32(p)  # what the library receives (a C float)
+    if not (np.isfinite(pf) and pf > 0):
+        raise ValueError("p=%r: a finite p > 0 is required" % (p,))
+
+
+def nn_bruteforce(x, y, p=.5, mu=0., k=2, use_int=False):
+    """
+    Exact k nearest neighbours of every row of `y` (queries) among the rows of `x`
+    (database) under the p-norm distance sum_c |x_c - y_c|^p (no p-th root), on the GPU.
+
+    The distance of each pair is the sequential, unfused float32 sum over the columns of
+    |d|, d*d, sqrtf(|d|) (p = 1, 2, 0.5; bit-exact) or float(pow(|d|, p)) (other p); with
+    `use_int` the rows are ``np.round(100 * x).astype('int32')`` and every term is truncated
+    to int and summed in int32 (reference spectavi/feature.py:204-289).  Ties are broken by
+    the lower database index.  `mu` is accepted and ignored: the result is always exact.
+
+    Returns
+    -------
+    nn_idx : uint64 ndarray [yrows, k]   index into `x`, nearest first
+    nn_dist : float32 (int32 with `use_int`) ndarray [yrows, k], ascending
+    With fewer than k database rows the missing columns hold idx 2**64-1 and dist
+    +inf (INT_MAX with `use_int`).
+
+    Raises ValueError for k outside [1, 64], dim outside [1, 2048], mismatched
+    column counts and p that is not finite and > 0.
+    """
+    x = np.asarray(x)
+    y = np.asarray(y)
+    check_bruteforce_args(x.shape, y.shape, k, p)
+    k = int(k)
+    xrows, dim = x.shape
+    yrows = y.shape[0]
+    nn_idx = NdArray(dtype='uint64')
+    if not use_int:
+        nn_dist = NdArray(dtype='float32')
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.float32)
+        _nn_bruteforce(x, y, xrows, yrows, dim, k, p, mu, ct.byref(nn_idx), ct.byref(nn_dist))
+    else:
+        nn_dist = NdArray(dtype='int32')
+        xi = np.ascontiguousarray(np.round(100 * x).astype('int32'))
+        yi = np.ascontiguousarray(np.round(100 * y).astype('int32'))
+        _nn_bruteforcei(xi, yi, xrows, yrows, dim, k, p, mu, ct.byref(nn_idx), ct.byref(nn_dist))
+    check()
+    return nn_idx.asarray(), nn_dist.asarray()
+
+
+# ==================================================================================
 # cascading hash              (reference spectavi/feature.py:346-376)
 # ==================================================================================
 _nn_cascading_hash = clib.nn_cascading_hash

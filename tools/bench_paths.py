@@ -312,6 +312,66 @@ def next_rows(steps, warmup):
                           "config": {"workload": "%d x 132 float32" % rows}, "dtype": "f32", "data": "synthetic"}), flush=True)
 
 
+# VALU instructions per pair-element of the tile kernel's 32-column body (bf_tile_kernel, gfx950
+# disassembly: v_pk_* count one instruction for two rows) and the microbench op (tools/microbench.py)
+# whose measured rate prices them; s_nop hazards and the per-row-group work are not counted.
+BF_ISSUE = {("f32", 2.0): (1.5, "v_pk_add_f32/v_pk_mul_f32", 8), ("f32", 1.0): (2.0, "v_pk_add_f32 + 2 v_and_b32", 8),
+            ("f32", 0.5): (None, "sqrtf sequence", 10), ("i32", 1.0): (None, "scalar", 7)}
+
+
+def bruteforce_rows(steps, warmup):
+    """Exact p-norm k-NN (device.bruteforce), inputs resident: the 131072^2 x 128 rows and the
+    reference test's 1000 x 1000 x 132 call."""
+    from spectavi_amd._lib import clib
+    import ctypes as ct
+    clib.spv_microbench_valu.restype = ct.c_int
+    clib.spv_microbench_valu.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double)]
+    rates = {}
+    for op in (7, 8, 10):
+        r, c = ct.c_double(0), ct.c_double(0)
+        clib.spv_microbench_valu(op, 4096, 20000, ct.byref(r), ct.byref(c))
+        rates[op] = r.value
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(0xbf)
+    rows, dim = 131072, 128
+    xf = torch.randn((rows, dim), device=dev, generator=g)
+    yf = torch.randn((rows, dim), device=dev, generator=g)
+    xi = torch.randint(-100, 100, (rows, dim), dtype=torch.int32, device=dev, generator=g)
+    yi = torch.randint(-100, 100, (rows, dim), dtype=torch.int32, device=dev, generator=g)
+    for dt_name, p, k in (("f32", 2.0, 2), ("f32", 1.0, 2), ("f32", 0.5, 2), ("i32", 1.0, 2), ("f32", 2.0, 16)):
+        x, y = (xf, yf) if dt_name == "f32" else (xi, yi)
+        _, dt = timed(lambda: spv.bruteforce(x, y, k=k, p=p), steps, warmup)
+        n, ms = spv.profile_read("bruteforce")
+        nm, msm = spv.profile_read("bruteforce_merge")
+        ks = ms / max(n, 1) / 1e3
+        pairs = float(rows) * rows
+        rec = {"metric": "exact p-norm k-NN, pairs/s (%s p=%g k=%d)" % (dt_name, p, k), "value": pairs / dt,
+               "unit": "pairs/s", "ms_per_step": dt * 1e3, "kernel_ms": ks * 1e3, "merge_ms": msm / max(nm, 1),
+               "kernel_pairs_per_s": pairs / ks, "config": {"workload": "%d x %d, D=%d" % (rows, rows, dim)},
+               "dtype": dt_name, "data": "synthetic"}
+        per, what, op = BF_ISSUE.get((dt_name, p), (None, None, None))
+        if per is not None and k <= 2:
+            bound = rates[op] / (per * dim)  # pairs/s if the body's VALU instructions issued at the measured rate
+            rec["issue_bound"] = {"instr_per_pair_element": per, "instructions": what, "rate_op": op,
+                                  "measured_lane_instr_per_s": rates[op], "bound_pairs_per_s": bound,
+                                  "frac": pairs / ks / bound}
+        print(json.dumps(rec), flush=True)
+    print(json.dumps({"metric": "microbench rates (lane-instructions/s)", "v_sub_f32": rates[7],
+                      "v_pk_add_f32": rates[8], "sqrtf_sequence": rates[10]}), flush=True)
+    # the reference test's shape through the host-pointer entry point (numpy in / out), latency
+    rng = np.random.default_rng(67)
+    xh = rng.standard_normal((1000, 132)).astype(np.float32)
+    yh = rng.standard_normal((1000, 132)).astype(np.float32)
+    feature.nn_bruteforce(xh, yh, p=2, k=2)
+    t0 = time.perf_counter()
+    for _ in range(20):
+        feature.nn_bruteforce(xh, yh, p=2, k=2)
+    dt = (time.perf_counter() - t0) / 20
+    print(json.dumps({"metric": "nn_bruteforce host-pointer call latency", "value": dt * 1e3, "unit": "ms",
+                      "ms_per_step": dt * 1e3, "config": {"workload": "1000 x 1000, D=132, p=2, k=2, numpy in/out"},
+                      "dtype": "f32", "data": "synthetic"}), flush=True)
+
+
 def ransac_fit():
     """The RANSAC loop itself (seven-point solve + candidate processing + best-model rule) through the
     host-pointer entry: all tries evaluated (requirement out of reach) for the rate, then the time to
@@ -353,7 +413,7 @@ if __name__ == "__main__":
     ap.add_argument("--npt", type=int, default=10_000_000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit (default all)")
+    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit,bf (default all)")
     a = ap.parse_args()
     want = set(filter(None, a.only.split(",")))
     if not want or "cascade" in want:
@@ -369,3 +429,5 @@ if __name__ == "__main__":
         end_to_end()
     if not want or "fit" in want:
         ransac_fit()
+    if not want or "bf" in want:
+        bruteforce_rows(a.steps, a.warmup)

@@ -8,7 +8,8 @@ from spectavi_amd._lib import clib, check  # noqa: E402
 
 clib.spv_microbench_valu.restype = ct.c_int
 clib.spv_microbench_valu.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double)]
-NAMES = ["v_sad_hi_u8", "v_sad_u8", "v_sad_u16", "v_xor+v_add (2 ops)", "v_fma_f32", "v_dot4_u32_u8", "v_med3_u32"]
+NAMES = ["v_sad_hi_u8", "v_sad_u8", "v_sad_u16", "v_xor+v_add (2 ops)", "v_fma_f32", "v_dot4_u32_u8", "v_med3_u32",
+         "v_sub_f32", "v_pk_add_f32", "v_pk_mul_f32", "xor+and+sqrtf seq"]
 for op, name in enumerate(NAMES):
     for blocks in (256, 1024, 4096):
         r, c = ct.c_double(0), ct.c_double(0)
