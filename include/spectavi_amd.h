@@ -197,7 +197,12 @@ void dlt_triangulate(const double *P0, const double *P1, int npt, const double *
 
 /* Reprojection error of the triangulated point, ||hn(P0 X)-hn(x)|| + ||hn(P1 X)-hn(xp)||.
  * Replaces reference src/Spectavi.cpp:54-68 (src/DltTriangulator.h:67-74).
- * dst: caller double[npt]. */
+ * dst: caller double[npt].  +inf and NaN come out exactly where the reference's IEEE arithmetic
+ * gives them for the same X (+inf where a squared residual overflows; NaN for w = 0 with x = 0,
+ * nan observations, ...), so `err > thr` rejects them.  Both results (here and dlt_triangulate)
+ * are the same bits after a row of x or xp is multiplied by +-2^k (whenever the scaled row is
+ * exact: |w| up to 2^1023 and subnormal entries included) and after both cameras are multiplied
+ * by the same 2^k (|k| <= 200), and do not depend on the point's position in the batch. */
 void dlt_reprojection_error(const double *P0, const double *P1, int npt, const double *x,
                             const double *xp, double *dst);
 

@@ -161,14 +161,31 @@ inline bool null_gs_inverse_iteration(const double (&A0)[4][4], double (&xv)[4])
   return true;
 }
 
+// the kernel's rcp_hom2: the reciprocal of w for the perspective division (a / w, b / w) = (a r, b r).
+// Outside |w| in [2^-1020, 2^1020] a, b and w are first brought to |w| in [0.5, 1) by one exact power
+// of two (0, inf and nan w are left as they are), so the quotients do not change when the row is
+// rescaled by a power of two that leaves it exact.  a and b are returned scaled.
+inline double rcp_hom(double &a, double &b, double w) {
+  const double aw = std::fabs(w);
+  if (!(aw >= std::ldexp(1.0, -1020) && aw <= std::ldexp(1.0, 1020)) && std::isfinite(w) && w != 0.0) {
+    int ex = 0;
+    std::frexp(w, &ex);
+    a = std::ldexp(a, -ex);
+    b = std::ldexp(b, -ex);
+    w = std::ldexp(w, -ex);
+  }
+  return 1.0 / w;
+}
+
 // fast = true: method 2 with method 1 as fallback (dlt_triangulate / dlt_reprojection_error and,
 // since round 2, RANSAC scoring: the kernel defers its slow lanes to a second pass, the result per
 // (hypothesis, point) pair is this function's); fast = false: method 1 only.
 inline void dlt_solve(const double *P0, const double *P1, const double *x, const double *xp,
                       Solve &out, bool fast = true) {
-  const double ix = 1.0 / x[2], iy = 1.0 / xp[2];  // one reciprocal per view, as the kernel
-  const double u = x[0] * ix, v = x[1] * ix;
-  const double up = xp[0] * iy, vp = xp[1] * iy;
+  double x0 = x[0], x1 = x[1], y0 = xp[0], y1 = xp[1];
+  const double ix = rcp_hom(x0, x1, x[2]), iy = rcp_hom(y0, y1, xp[2]);  // one reciprocal per view, as the kernel
+  const double u = x0 * ix, v = x1 * ix;
+  const double up = y0 * iy, vp = y1 * iy;
   double A[4][4];
   for (int c = 0; c < 4; ++c) {
     A[0][c] = std::fma(u, P0[8 + c], -P0[0 + c]);

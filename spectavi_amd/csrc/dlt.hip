@@ -66,11 +66,42 @@ __device__ __forceinline__ double rsqrt_nr2(double x) {
   t = __builtin_fma(-(x * q), q, 1.0);
   return __builtin_fma(0.5 * q, t, q);
 }
-// sqrt(s) for s >= 0 as s * rsqrt(s); zero and the range whose reciprocal root would overflow or
-// lose bits take the IEEE instruction sequence (exact zeros occur: noise-free points reproject exactly)
+// sqrt(s) for s >= 0 as s * rsqrt(s); zero, +inf, nan and the ranges whose reciprocal root would
+// overflow or lose bits take the IEEE instruction sequence (exact zeros occur: noise-free points
+// reproject exactly; a squared residual that overflows must stay +inf, where v_rsq_f64(inf) = 0 and
+// the Newton step would make it inf * 0 = nan)
 __device__ __forceinline__ double sqrt_fast(double s) {
-  if (!(s >= 0x1p-900)) return sqrt(s);
+  if (!(s >= 0x1p-900 && s <= 0x1p900)) return sqrt(s);
   return s * rsqrt_nr2(s);
+}
+
+// The perspective division (a / w, b / w) as a * r, b * r with r = rcp_nr2(w) + 2 Newton steps.
+// Where |w| is outside [2^-1020, 2^1020] (1 / w subnormal or overflowing, or w itself subnormal --
+// what v_rcp_f64 does there is not relied on), a, b and w are first brought to |w| in [0.5, 1) by one
+// exact power of two; 0, inf and nan w are left as they are (frexp exponent 0) and keep IEEE's
+// answers.  So the quotients are the same bits after the row (a, b, w) is rescaled by any power of
+// two that leaves it exact.  a and b are returned scaled.  Both views of a point go through one
+// range test: the rescaling is a branch that almost no wave takes, and in range rcp_nr2 needs no
+// guard for 0 / inf.
+__device__ __forceinline__ bool rcp_in_range(double w) {
+  const double aw = fabs(w);
+  return aw >= 0x1p-1020 && aw <= 0x1p1020;
+}
+__device__ __forceinline__ double rcp_hom_slow(double &a, double &b, double w) {
+  const int ex = -__builtin_amdgcn_frexp_exp(w);
+  a = __builtin_amdgcn_ldexp(a, ex);
+  b = __builtin_amdgcn_ldexp(b, ex);
+  return rcp_nr2_ieee(__builtin_amdgcn_ldexp(w, ex));
+}
+__device__ __forceinline__ void rcp_hom2(double &a0, double &b0, double w0, double &a1, double &b1, double w1,
+                                         double &r0, double &r1) {
+  if (__builtin_expect(rcp_in_range(w0) && rcp_in_range(w1), 1)) {
+    r0 = rcp_nr2(w0);
+    r1 = rcp_nr2(w1);
+  } else {
+    r0 = rcp_hom_slow(a0, b0, w0);
+    r1 = rcp_hom_slow(a1, b1, w1);
+  }
 }
 
 // ---- null vector, method 1: one-sided (Hestenes) Jacobi, always converges ----------------
@@ -257,7 +288,8 @@ __device__ __forceinline__ bool null_gs_inverse_iteration(const double (&A0)[4][
 __device__ __forceinline__ void dlt_matrix(const Cameras &cam, double x0, double x1, double x2, double y0,
                                            double y1, double y2, double (&A)[4][4], double &u, double &v,
                                            double &up, double &vp) {
-  const double ix = rcp_nr2_ieee(x2), iy = rcp_nr2_ieee(y2);  // one reciprocal per view; x / 0 stays +-inf or nan
+  double ix, iy;  // one reciprocal per view; x / 0 stays +-inf or nan
+  rcp_hom2(x0, x1, x2, y0, y1, y2, ix, iy);
   u = x0 * ix;
   v = x1 * ix;
   up = y0 * iy;
@@ -316,6 +348,8 @@ __device__ __forceinline__ double reprojection_error(const Cameras &cam, const d
   }
   z0 = r0[2];
   z1 = r1[2];
+  // (the depths need no range test: |P X [2]| >= 2^1020 takes cameras near the top of the range, and a
+  // subnormal depth's reciprocal overflows or its quotients do; 0 and inf keep IEEE's answers)
   const double i0 = rcp_nr2_ieee(r0[2]), i1 = rcp_nr2_ieee(r1[2]);
   const double e0x = __builtin_fma(r0[0], i0, -u), e0y = __builtin_fma(r0[1], i0, -v);
   const double e1x = __builtin_fma(r1[0], i1, -up), e1y = __builtin_fma(r1[1], i1, -vp);

@@ -156,13 +156,24 @@ def check_against_oracle(X, oX, P0, P1, x, xp, what="X"):
     return worst
 
 
+def _same_classes(a, b, what):
+    """nan, +inf and -inf in exactly the same places (the sign of an infinity included)."""
+    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
+    assert a.shape == b.shape, what
+    for name, f in (("nan", np.isnan), ("+inf", np.isposinf), ("-inf", np.isneginf)):
+        bad = np.flatnonzero(f(a) != f(b))
+        assert bad.size == 0, "%s: %s entries differ from the mirror's at %d places, first %d: %r vs %r" % (
+            what, name, bad.size, bad[0], a[bad[0]], b[bad[0]])
+
+
 def check_against_mirror(X, mX, P0, P1, x, xp, E=None, mE=None, what="X"):
     """The HIP path against the host mirror of its own operation sequence (oracle_dlt_mirror.cpp).
     Until round 3 the two were bit-identical; since the kernel takes its reciprocals and reciprocal
     square roots from v_rcp_f64 / v_rsq_f64 + two Newton steps (< 1 ulp from the mirror's exact
     1/x, 1/sqrt(x)) they agree to a few ulps times the conditioning of the point -- a determinism
     aid (no lane- or shape-dependent path, inf/nan in the same rows), not a parity statement:
-      * the rows with a non-finite entry coincide;
+      * the rows with a non-finite entry coincide, and so does every entry's class (finite, nan,
+        +inf, -inf) in X and, on every row, in the reprojection errors;
       * |X - mX| <= 1e-13 + 32 eps sigma1 / (sigma3 - sigma4) on the finite, well-separated rows
         (the verdict's "<= 1e-13 relative" with the same conditioning term as check_against_oracle);
       * reprojection errors within 1e-9 relative + a conditioning- and depth-scaled absolute term.
@@ -170,6 +181,9 @@ def check_against_mirror(X, mX, P0, P1, x, xp, E=None, mE=None, what="X"):
     X, mX = np.asarray(X, np.float64), np.asarray(mX, np.float64)
     badX, badM = ~np.isfinite(X).all(axis=1), ~np.isfinite(mX).all(axis=1)
     assert np.array_equal(badX, badM), "%s: non-finite rows differ from the mirror's (%d vs %d)" % (what, badX.sum(), badM.sum())
+    _same_classes(X, mX, what + " (X)")
+    if E is not None:
+        _same_classes(E, mE, what + " (reprojection error)")
     A, obs, _ = dlt_matrices(P0, P1, x, xp, return_formation_error=True)
     S, _, ok = lapack_svd(A)
     ok &= ~badX
