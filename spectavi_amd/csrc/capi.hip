@@ -4,27 +4,20 @@
 // call the same device-pointer runners (l1k2_run / cascade_run / dlt_run) the
 // section-3 symbols expose.  No compute happens on the host and there is no
 // CPU fallback: every path ends in a HIP kernel launch or in an error status.
+// The transfer machinery is in host_io.hip, device selection and the gathered
+// multi-device forms in shard.hip.
 
 #include "common.h"
+#include "host_io.h"
 #include "records.h"
+#include "shard.h"
 
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
-#include <condition_variable>
-#include <exception>
-#include <initializer_list>
 #include <map>
-#include <memory>
-#include <new>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <utility>
 #include <random>
-#include <vector>
 
 namespace spv {
 
@@ -32,12 +25,9 @@ namespace {
 thread_local int g_status = SPV_OK;
 thread_local char g_message[512] = "";
 
-std::mutex g_cfg_mutex;
-int g_device = -1;  // -1: not chosen yet
-std::vector<int> g_devices;  // empty: not chosen yet
+std::mutex g_seed_mutex;
 bool g_seed_fixed = false;
 uint32_t g_seed = 0;
-int g_gather_mode = -1;  // -1: SPECTAVI_GATHER, else automatic; SPV_GATHER_DIRECT / SPV_GATHER_RCCL
 }  // namespace
 
 int set_error(int status, const char *fmt, ...) {
@@ -52,22 +42,6 @@ int set_error(int status, const char *fmt, ...) {
 void clear_error() {
   g_status = SPV_OK;
   g_message[0] = '\0';
-}
-
-// No C++ exception may cross the extern "C" boundary (the reference's own symbols let them
-// escape into libffi and abort the process, src/BruteForceNnL1K2.h:75,79): every entry point
-// runs its body through this.
-template <typename Fn>
-static int guard(Fn fn) {
-  try {
-    return fn();
-  } catch (const std::bad_alloc &) {
-    return set_error(SPV_ERR_NOMEM, "host allocation failed");
-  } catch (const std::exception &e) {
-    return set_error(SPV_ERR_INTERNAL, "unexpected C++ exception: %s", e.what());
-  } catch (...) {
-    return set_error(SPV_ERR_INTERNAL, "unexpected C++ exception");
-  }
 }
 
 // ---- optional kernel timing ----------------------------------------------------------
@@ -153,101 +127,18 @@ static int host_guard(Fn fn) {
   return guard(fn);
 }
 
-static int use_device(int dev) {
-  int count = 0;
-  hipError_t e = hipGetDeviceCount(&count);
-  if (e != hipSuccess || count <= 0)
-    return set_error(SPV_ERR_HIP, "no HIP device available (%s); libspectavi has no CPU fallback",
-                     e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-  if (dev < 0 || dev >= count)
-    return set_error(SPV_ERR_HIP, "device %d requested but only %d devices are visible", dev, count);
-  SPV_HIP_CHECK(hipSetDevice(dev));
-  return SPV_OK;
+// The prologue of every exported entry point: a fresh status, then the body under guard() (api) or,
+// when the body may switch the current device, host_guard() (host_api).
+template <typename Fn>
+static int api(Fn fn) {
+  clear_error();
+  return guard(fn);
 }
-
-// Devices the host-pointer entry points shard over.  One entry unless
-// spv_set_devices() / SPECTAVI_DEVICES ("0,1,2,3" or "all") asked for more.
-static std::vector<int> device_list() {
-  std::lock_guard<std::mutex> lk(g_cfg_mutex);
-  if (g_devices.empty()) {
-    const char *e = getenv("SPECTAVI_DEVICES");
-    if (e && *e) {
-      if (!strcmp(e, "all")) {
-        int count = 0;
-        if (hipGetDeviceCount(&count) == hipSuccess)
-          for (int d = 0; d < count; ++d) g_devices.push_back(d);
-      } else {
-        for (const char *c = e; *c;) {
-          char *end = nullptr;
-          const long v = strtol(c, &end, 10);
-          if (end == c) break;
-          g_devices.push_back((int)v);
-          c = (*end == ',') ? end + 1 : end;
-        }
-      }
-    }
-    if (g_devices.empty()) {
-      if (g_device < 0) {
-        const char *d = getenv("SPECTAVI_DEVICE");
-        g_device = (d && *d) ? atoi(d) : 0;
-      }
-      g_devices.push_back(g_device);
-    }
-  }
-  return g_devices;
+template <typename Fn>
+static int host_api(Fn fn) {
+  clear_error();
+  return host_guard(fn);
 }
-
-// How the shards of a host-pointer call reach the caller's arrays: each shard copied straight
-// into its slice (direct), or gathered on the first listed GPU over RCCL and copied from there
-// (north_star's "RCCL gather of (idx0, idx1, d0, d1)").  spv_set_gather_mode / SPECTAVI_GATHER
-// choose; left alone, RCCL is used exactly when more than one distinct device is configured.
-// Automatic mode only: can a clique over exactly these devices be built?  (librccl opened,
-// ncclCommInitAll done; both cached, a refusal too, so a box without a usable RCCL pays once.)
-static bool rccl_clique_usable(const std::vector<int> &devs) {
-  static std::mutex mu;
-  static std::map<std::vector<int>, bool> known;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = known.find(devs);
-  if (it != known.end()) return it->second;
-  bool ok;
-  {
-    std::lock_guard<std::mutex> glk(gather_mutex());
-    GatherCtx *ctx = nullptr;
-    ok = gather_ctx_get(devs, true, &ctx) == SPV_OK;
-  }
-  if (!ok) {
-    fprintf(stderr, "libspectavi: RCCL gather unavailable (%s); sharding with direct copies instead\n", g_message);
-    clear_error();
-  }
-  known[devs] = ok;
-  return ok;
-}
-
-static int gather_transport(const std::vector<int> &devs, long long total = -1) {
-  int mode;
-  {
-    std::lock_guard<std::mutex> lk(g_cfg_mutex);
-    mode = g_gather_mode;
-  }
-  if (mode < 0) {
-    const char *e = getenv("SPECTAVI_GATHER");
-    if (e && !strcmp(e, "rccl")) mode = SPV_GATHER_RCCL;
-    if (e && !strcmp(e, "direct")) mode = SPV_GATHER_DIRECT;
-    if (e && !strcmp(e, "copy")) mode = SPV_GATHER_PEERCOPY;
-  }
-  if (mode >= 0) return mode;  // asked for by name: a failure of that transport is the caller's error
-  if (devs.size() < 2) return SPV_GATHER_DIRECT;
-  for (size_t a = 0; a < devs.size(); ++a)
-    for (size_t b = a + 1; b < devs.size(); ++b)
-      if (devs[a] == devs[b]) return SPV_GATHER_DIRECT;  // a clique needs distinct devices
-  // the clique a call of `total` rows would use (run_gathered lists no more ranks than rows)
-  const size_t G = total < 0 ? devs.size() : (size_t)std::min<long long>((long long)devs.size(), std::max<long long>(total, 1));
-  if (!rccl_clique_usable(std::vector<int>(devs.begin(), devs.begin() + G))) return SPV_GATHER_DIRECT;
-  return SPV_GATHER_RCCL;
-}
-static bool use_rccl_gather(const std::vector<int> &devs, long long total) { return gather_transport(devs, total) != SPV_GATHER_DIRECT; }
-
-int ensure_device() { return use_device(device_list()[0]); }
 
 int device_cu_count() {
   static std::atomic<int> cache[64];  // per device, 0 = not asked yet
@@ -261,493 +152,90 @@ int device_cu_count() {
   return cus;
 }
 
-// Splits [0, total) into contiguous balanced shards, one per configured device, and runs
-// fn(device, lo, hi) on a host thread per shard (every row of the hot path is independent:
-// the reference parallelises the same loop with OpenMP, src/BruteForceNnL1K2.h:92).  Each
-// shard writes straight into its slice of the caller's output, so no gather is needed
-// inside one process.
-template <typename Fn>
-static int run_sharded(long long total, Fn fn) {
-  const std::vector<int> devs = device_list();
-  const int G = (int)std::min<long long>((long long)devs.size(), std::max<long long>(total, 1));
-  if (G <= 1) return fn(devs[0], 0LL, total);
-  std::vector<int> status(G, SPV_OK);
-  std::vector<std::string> message(G);
-  std::vector<std::thread> threads;
-  const long long base = total / G, extra = total % G;
-  threads.reserve(G);
-  for (int r = 0; r < G; ++r) {
-    const long long lo = r * base + std::min<long long>(r, extra);
-    const long long hi = lo + base + (r < extra ? 1 : 0);
-    auto shard = [&, r, lo, hi] {
-      status[r] = guard([&] {
-        const int st = fn(devs[r], lo, hi);
-        if (st != SPV_OK) message[r] = g_message;
-        return st;
-      });
-    };
-    // a thread that cannot be started (std::system_error) must not unwind through joinable
-    // threads (std::terminate): run that shard on this thread instead
-    try {
-      threads.emplace_back(shard);
-    } catch (...) {
-      shard();
-    }
-  }
-  for (auto &t : threads) t.join();
-  for (int r = 0; r < G; ++r)
-    if (status[r] != SPV_OK)
-      return set_error(status[r], "device %d: %s", devs[r], message[r].c_str());
+// ---- argument rules -------------------------------------------------------------------
+// The row width of the L1 and cascade paths.  *_ok: the rule alone, which the workspace-size queries
+// use without touching the thread's last error; check_*: the rule with its message.
+static bool dim_ok(int dim) { return dim > 0 && dim % 16 == 0; }
+static bool l1k2_shape_ok(int xrows, int yrows, int dim) { return xrows >= 0 && yrows >= 0 && dim_ok(dim); }
+// (g up to m: the size query has never applied check_cascade_args' g <= 16)
+static bool cascade_shape_ok(int xrows, int yrows, int dim, int m, int n, int g) {
+  return l1k2_shape_ok(xrows, yrows, dim) && m >= 1 && m <= 31 && n >= 1 && g >= 0 && g <= m;
+}
+
+static int check_dim(int dim) {
+  if (!dim_ok(dim))
+    return set_error(SPV_ERR_INVALID, "Input matrix inner dimensions must be 16-byte aligned (dim=%d).", dim);
+  return SPV_OK;
+}
+
+static int check_l1k2_args(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
+                           const uint64_t *idx, const int32_t *dist) {
+  if (xrows < 0 || yrows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
+  SPV_TRY(check_dim(dim));
+  if (yrows > 0 && (!y || !idx || !dist || (xrows > 0 && !x))) return set_error(SPV_ERR_INVALID, "null pointer");
+  return SPV_OK;
+}
+
+static int check_cascade_args(int xrows, int yrows, int dim, int m, int n, int g) {
+  if (xrows < 0 || yrows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
+  SPV_TRY(check_dim(dim));
+  if (m < 1 || m > 31) return set_error(SPV_ERR_INVALID, "hash_bit_rate m=%d must be in [1,31]", m);
+  if (n < 1) return set_error(SPV_ERR_INVALID, "num_hash_tables n=%d must be >= 1", n);
+  if (g < 0 || g > m || g > 16)
+    return set_error(SPV_ERR_INVALID, "num_candidate_neighbours g=%d must be in [0,min(m,16)]", g);
+  return SPV_OK;
+}
+
+static int check_gathered_devices(int ndev, const int *devices, int transport) {
+  if (ndev < 1 || ndev > 64 || !devices) return set_error(SPV_ERR_INVALID, "bad device list");
+  if (transport != SPV_GATHER_RCCL && transport != SPV_GATHER_PEERCOPY)
+    return set_error(SPV_ERR_INVALID, "transport must be SPV_GATHER_RCCL or SPV_GATHER_PEERCOPY");
   return SPV_OK;
 }
 
 namespace {
 
-// Per-device cache of freed device buffers for the host-pointer paths: repeated calls
-// (a front-end matching image pairs, RANSAC-style loops over dlt_triangulate) would
-// otherwise pay five hipMalloc/hipFree pairs each.  Grow-only up to kPoolCapBytes per
-// device; spv_release_cached_memory() empties it.  A buffer goes back to the pool only after
-// the owning thread's stream has drained (DevBuf's destructor synchronises it: a no-op on the
-// normal path, which has already synchronised, and the safety net on error paths), so a
-// later owner on another stream never sees work in flight.
-class DevicePool {
- public:
-  static constexpr size_t kPoolCapBytes = (size_t)4 << 30;
-  void *acquire(int dev, size_t bytes, size_t *got) {
-    std::lock_guard<std::mutex> lk(mu_);
-    auto &fl = free_[dev];
-    size_t best = fl.size();
-    for (size_t i = 0; i < fl.size(); ++i)
-      if (fl[i].second >= bytes && fl[i].second <= 2 * bytes + 4096 &&
-          (best == fl.size() || fl[i].second < fl[best].second))
-        best = i;
-    if (best == fl.size()) return nullptr;
-    void *p = fl[best].first;
-    *got = fl[best].second;
-    held_[dev] -= fl[best].second;
-    fl.erase(fl.begin() + best);
-    return p;
-  }
-  void release(int dev, void *p, size_t bytes) {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      if (held_[dev] + bytes <= kPoolCapBytes) {
-        free_[dev].emplace_back(p, bytes);
-        held_[dev] += bytes;
-        return;
-      }
-    }
-    (void)hipFree(p);
-  }
-  void clear() {
-    std::lock_guard<std::mutex> lk(mu_);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto &kv : free_) {
-      (void)hipSetDevice(kv.first);
-      for (auto &b : kv.second) (void)hipFree(b.first);
-      kv.second.clear();
-    }
-    held_.clear();
-    (void)hipSetDevice(cur);
-  }
-
- private:
-  std::mutex mu_;
-  std::map<int, std::vector<std::pair<void *, size_t>>> free_;
-  std::map<int, size_t> held_;
-};
-DevicePool g_pool;
-
-// RAII device buffer for the host-pointer paths (allocated on the current device).
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  int dev = 0;
-  ~DevBuf() {
-    if (!p) return;
-    (void)hipStreamSynchronize(hipStreamPerThread);
-    g_pool.release(dev, p, cap);
-  }
-  int alloc(size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    (void)hipGetDevice(&dev);
-    p = g_pool.acquire(dev, bytes, &cap);
-    if (p) return SPV_OK;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      // the cache may be what is exhausting the device: drop it and retry once
-      g_pool.clear();
-      e = hipMalloc(&p, bytes);
-    }
-    if (e != hipSuccess) {
-      p = nullptr;
-      return set_error(SPV_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    }
-    cap = bytes;
-    return SPV_OK;
-  }
-  template <typename T>
-  T *as() {
-    return static_cast<T *>(p);
-  }
-};
-
-// A caller's fresh result array (np.empty) has no pages yet: the device-to-host copy then
-// runs at the page-fault rate (~11 GB/s measured) instead of the link rate.  Large outputs are
-// therefore touched -- one byte per page, from a few threads -- while the inputs travel and the
-// kernels run; the contents of an output buffer are undefined before the call returns, so
-// writing to it early is allowed.  Skipped when the output overlaps an input.
-class HostPrefault {
- public:
-  // Pages are touched in 2 MB blocks dealt round-robin to the threads (block j belongs to thread
-  // j % T), so the front of the array is ready first and wait_range() can release a consumer
-  // that only needs a prefix while the rest is still being touched.
-  static constexpr size_t kBlock = (size_t)2 << 20;
-  HostPrefault(void *dst, size_t bytes, std::initializer_list<std::pair<const void *, size_t>> inputs) {
-    constexpr size_t kMin = (size_t)16 << 20, kPage = 4096;
-    if (!dst || bytes < kMin) return;
-    const char *lo = static_cast<const char *>(dst), *hi = lo + bytes;
-    for (const auto &in : inputs) {
-      const char *a = static_cast<const char *>(in.first);
-      if (a && a < hi && a + in.second > lo) return;
-    }
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int T = (int)std::min<size_t>(std::min<unsigned>(8u, hw), bytes / kMin + 1);
-    const size_t nblocks = (bytes + kBlock - 1) / kBlock;
-    done_.reset(new std::atomic<size_t>[T]);
-    for (int i = 0; i < T; ++i) done_[i].store(0, std::memory_order_relaxed);
-    nthreads_ = T;
-    try {
-      for (int i = 0; i < T; ++i)
-        threads_.emplace_back([=] {
-          volatile char *p = static_cast<volatile char *>(dst);
-          size_t mine = 0;
-          for (size_t b = (size_t)i; b < nblocks; b += (size_t)T) {
-            for (size_t off = b * kBlock; off < std::min(bytes, (b + 1) * kBlock); off += kPage) p[off] = 0;
-            done_[i].store(++mine, std::memory_order_release);
-          }
-          done_[i].store(SIZE_MAX, std::memory_order_release);
-        });
-    } catch (...) {  // could not start a thread: the copy simply faults the pages itself
-    }
-    // a thread that never started owns blocks nobody touches: they count as done (the copy into
-    // them then faults the pages itself, which is only slower)
-    for (int i = (int)threads_.size(); i < T; ++i) done_[i].store(SIZE_MAX, std::memory_order_release);
-  }
-  // Returns once no prefault store can land in [off, off + len) any more: a consumer must call
-  // this (or wait()) before it writes real data there -- a late `p[off] = 0` would otherwise
-  // overwrite one byte per page of the result.
-  void wait_range(size_t off, size_t len) {
-    if (nthreads_ == 0 || len == 0) return;
-    const size_t b0 = off / kBlock, b1 = (off + len - 1) / kBlock;
-    for (size_t b = b0; b <= b1; ++b) {
-      const int owner = (int)(b % (size_t)nthreads_);
-      const size_t need = b / (size_t)nthreads_ + 1;  // blocks the owner must have finished
-      while (done_[owner].load(std::memory_order_acquire) < need) std::this_thread::yield();
-    }
-  }
-  void wait() {
-    for (auto &t : threads_)
-      if (t.joinable()) t.join();
-    threads_.clear();
-  }
-  ~HostPrefault() { wait(); }
-
- private:
-  std::vector<std::thread> threads_;
-  std::unique_ptr<std::atomic<size_t>[]> done_;
-  int nthreads_ = 0;
-};
-
-// ---- results back to pageable host memory ------------------------------------------------
-// A device-to-host copy into a caller's ordinary (pageable) array runs at ~16 GB/s: the runtime
-// stages it through pinned memory and copies out of the staging buffer with one host thread.  For
-// large results the library does that staging itself with several threads: each worker owns a slice
-// of every chunk, two pinned bounce buffers and its own stream; it waits for the chunk's producer
-// event on the device side, copies device -> pinned at the link rate, and copies pinned -> the
-// caller's array while its next slice is already in flight.  Chunks become available as the caller
-// announces them (ready()), so a chunked computation overlaps its uploads and kernels with the
-// download of the chunks before.
-class PinnedPool {
- public:
-  static constexpr size_t kCapBytes = (size_t)256 << 20;  // kept for reuse; more is handed back
-  void *acquire(size_t bytes) {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      for (size_t i = 0; i < free_.size(); ++i)
-        if (free_[i].second >= bytes && free_[i].second <= 2 * bytes + 4096) {
-          void *p = free_[i].first;
-          held_ -= free_[i].second;
-          free_.erase(free_.begin() + i);
-          return p;
-        }
-    }
-    void *p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(mu_);
-    cap_[p] = bytes;
-    return p;
-  }
-  void release(void *p) {
-    if (!p) return;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      const size_t bytes = cap_[p];
-      if (held_ + bytes <= kCapBytes) {
-        free_.emplace_back(p, bytes);
-        held_ += bytes;
-        return;
-      }
-      cap_.erase(p);
-    }
-    (void)hipHostFree(p);
-  }
-  void clear() {
-    std::lock_guard<std::mutex> lk(mu_);
-    for (auto &b : free_) {
-      cap_.erase(b.first);
-      (void)hipHostFree(b.first);
-    }
-    free_.clear();
-    held_ = 0;
-  }
-
- private:
-  std::mutex mu_;
-  std::vector<std::pair<void *, size_t>> free_;
-  std::map<void *, size_t> cap_;
-  size_t held_ = 0;
-};
-PinnedPool g_pinned;
-
-class D2HPipeline {
- public:
-  static constexpr size_t kMinBytes = (size_t)16 << 20;  // below this a plain copy is as good
-  D2HPipeline(int dev, const void *d_src, void *h_dst, size_t bytes, size_t chunk_bytes)
-      : dev_(dev), src_(static_cast<const char *>(d_src)), dst_(static_cast<char *>(h_dst)), bytes_(bytes),
-        chunk_(std::max<size_t>(chunk_bytes, 1)), nchunks_((int)((bytes + chunk_ - 1) / chunk_)),
-        events_(nchunks_, nullptr) {
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    workers_ = (int)std::min<size_t>(std::min<unsigned>(6u, hw), std::max<size_t>(1, std::min(chunk_, bytes) >> 20));
-    piece_ = round_up((std::min(chunk_, bytes) + workers_ - 1) / workers_, 4096);
-    try {
-      for (int t = 0; t < workers_; ++t) threads_.emplace_back([this, t] { work(t); });
-    } catch (...) {  // fewer workers than planned: the missing slices are copied by finish()
-    }
-    started_ = (int)threads_.size();
-  }
-  // The caller's array is still being pre-touched by `touch`: every slice waits for its own pages
-  // before the pinned -> caller copy (call before the first ready(); touch must outlive finish()).
-  void set_prefault(HostPrefault *touch) { prefault_ = touch; }
-  // chunk k (bytes [k * chunk, (k+1) * chunk) of the source) is final once `ev` has passed;
-  // chunks must be announced in order.  ev must outlive finish().
-  void ready(int k, hipEvent_t ev) {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      events_[k] = ev;
-      ready_ = k + 1;
-    }
-    cv_.notify_all();
-  }
-  void abort() {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      aborted_ = true;
-    }
-    cv_.notify_all();
-  }
-  int finish() {
-    for (auto &t : threads_)
-      if (t.joinable()) t.join();
-    threads_.clear();
-    if (aborted_) return SPV_OK;  // the caller reports its own error
-    if (status_.load() != SPV_OK) return set_error(status_.load(), "%s", message_.c_str());
-    for (int t = started_; t < workers_; ++t) work(t);  // slices of workers that never started
-    if (status_.load() != SPV_OK) return set_error(status_.load(), "%s", message_.c_str());
-    return SPV_OK;
-  }
-  ~D2HPipeline() {
-    abort();
-    for (auto &t : threads_)
-      if (t.joinable()) t.join();
-  }
-
- private:
-  void fail(int st, const char *what, hipError_t e) {
-    std::lock_guard<std::mutex> lk(mu_);
-    if (status_.load() == SPV_OK) {
-      message_ = std::string(what) + ": " + hipGetErrorString(e);
-      status_.store(st);
-    }
-  }
-  void work(int t) {
-    if (hipSetDevice(dev_) != hipSuccess) return fail(SPV_ERR_HIP, "hipSetDevice", hipGetLastError());
-    char *pin[2] = {static_cast<char *>(g_pinned.acquire(piece_)), static_cast<char *>(g_pinned.acquire(piece_))};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    hipStream_t st = hipStreamPerThread;
-    bool ok = pin[0] && pin[1];
-    if (!ok) fail(SPV_ERR_NOMEM, "hipHostMalloc", hipErrorOutOfMemory);
-    for (int i = 0; ok && i < 2; ++i)
-      if (hipEventCreateWithFlags(&done[i], hipEventDisableTiming) != hipSuccess) {
-        ok = false;
-        fail(SPV_ERR_HIP, "hipEventCreate", hipGetLastError());
-      }
-    size_t prev_off = 0, prev_len = 0;
-    int prev_slot = -1;
-    auto drain = [&] {  // the slice whose download is in flight: pinned -> the caller's array
-      if (prev_slot < 0) return;
-      const hipError_t e = hipEventSynchronize(done[prev_slot]);
-      if (e != hipSuccess) {
-        ok = false;
-        fail(SPV_ERR_HIP, "device-to-host copy", e);
-      } else {
-        if (prefault_) prefault_->wait_range(prev_off, prev_len);
-        memcpy(dst_ + prev_off, pin[prev_slot], prev_len);
-      }
-      prev_slot = -1;
-    };
-    for (int k = 0; ok && k < nchunks_; ++k) {
-      hipEvent_t ev;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return ready_ > k || aborted_; });
-        if (aborted_) {
-          ok = false;
-          break;
-        }
-        ev = events_[k];
-      }
-      const size_t c0 = (size_t)k * chunk_, c1 = std::min(bytes_, c0 + chunk_);
-      const size_t off = c0 + (size_t)t * piece_;
-      if (off >= c1) {
-        continue;  // this chunk is shorter than t slices
-      }
-      const size_t len = std::min(piece_, c1 - off);
-      const int slot = k & 1;
-      if (prev_slot == slot) drain();  // (a skipped chunk in between) never overwrite an undrained buffer
-      if (!ok) break;
-      hipError_t e = ev ? hipStreamWaitEvent(st, ev, 0) : hipSuccess;
-      if (e == hipSuccess) e = hipMemcpyAsync(pin[slot], src_ + off, len, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipEventRecord(done[slot], st);
-      if (e != hipSuccess) {
-        ok = false;
-        fail(SPV_ERR_HIP, "device-to-host copy", e);
-        break;
-      }
-      drain();  // the previous slice, while this one travels
-      prev_off = off;
-      prev_len = len;
-      prev_slot = slot;
-    }
-    if (ok) drain();
-    (void)hipStreamSynchronize(st);
-    for (int i = 0; i < 2; ++i) {
-      if (done[i]) (void)hipEventDestroy(done[i]);
-      g_pinned.release(pin[i]);
-    }
-  }
-
-  int dev_;
-  const char *src_;
-  char *dst_;
-  size_t bytes_, chunk_;
-  int nchunks_;
-  std::vector<hipEvent_t> events_;
-  int workers_ = 1, started_ = 0;
-  size_t piece_ = 0;
-  HostPrefault *prefault_ = nullptr;
-  std::vector<std::thread> threads_;
-  std::mutex mu_;
-  std::condition_variable cv_;
-  int ready_ = 0;
-  bool aborted_ = false;
-  std::atomic<int> status_{SPV_OK};
-  std::string message_;
-};
-
-// An event recorded on `st` now, destroyed with the holder.
-struct ScopedEvent {
-  hipEvent_t ev = nullptr;
-  int record(hipStream_t st) {
-    SPV_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    SPV_HIP_CHECK(hipEventRecord(ev, st));
-    return SPV_OK;
-  }
-  ~ScopedEvent() {
-    if (ev) (void)hipEventDestroy(ev);
-  }
-};
-
-// Device result -> caller's array: through the threaded pinned pipeline when large, else one copy.
-// `st` is the stream the producing kernels were enqueued on; returns after the data has arrived.
-int download(int dev, void *h_dst, const void *d_src, size_t bytes, hipStream_t st) {
-  if (bytes < D2HPipeline::kMinBytes) {
-    SPV_HIP_CHECK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, st));
-    SPV_HIP_CHECK(hipStreamSynchronize(st));
-    return SPV_OK;
-  }
-  ScopedEvent produced;
-  SPV_TRY(produced.record(st));
-  const size_t chunk = (size_t)8 << 20;
-  D2HPipeline pipe(dev, d_src, h_dst, bytes, chunk);
-  const int n = (int)((bytes + chunk - 1) / chunk);
-  for (int k = 0; k < n; ++k) pipe.ready(k, produced.ev);
-  const int status = pipe.finish();
-  SPV_HIP_CHECK(hipStreamSynchronize(st));
-  return status;
+// ---- single-device host-pointer bodies ---------------------------------------------------
+// Their prologue: makes `dev` current and names the stream their work is queued on.
+int host_begin(int dev, hipStream_t *st) {
+  *st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
+  return use_device(dev);
 }
 
-int check_l1k2_args(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim, const uint64_t *idx,
-                    const int32_t *dist) {
-  if (xrows < 0 || yrows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
-  if (dim <= 0 || dim % 16 != 0)
-    return set_error(SPV_ERR_INVALID,
-                     "Input matrix inner dimensions must be 16-byte aligned (dim=%d).", dim);
-  if (yrows > 0 && (!y || !idx || !dist || (xrows > 0 && !x))) return set_error(SPV_ERR_INVALID, "null pointer");
-  return SPV_OK;
-}
-
+// The L1, cascade and DLT bodies are bound by the PCIe link: the result arrays
+// start pre-faulting first, every buffer is allocated before the first copy is queued, and the
+// pre-faulting has ended before the first device-to-host copy.
 int host_l1k2_one(int dev, const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
                   uint64_t *idx, int32_t *dist) {
   SPV_TRY(check_l1k2_args(x, y, xrows, yrows, dim, idx, dist));
   if (yrows == 0) return SPV_OK;
-  SPV_TRY(use_device(dev));
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
   const size_t xb = (size_t)xrows * dim, yb = (size_t)yrows * dim;
+  const size_t ib = (size_t)yrows * 2 * sizeof(uint64_t), db = (size_t)yrows * 2 * sizeof(int32_t);
   const size_t wsb = spv_l1k2_workspace_bytes(xrows, yrows, dim);
-  HostPrefault touch_idx(idx, (size_t)yrows * 2 * sizeof(uint64_t), {{x, xb}, {y, yb}});
-  HostPrefault touch_dist(dist, (size_t)yrows * 2 * sizeof(int32_t), {{x, xb}, {y, yb}});
+  HostPrefault touch_idx(idx, ib, {{x, xb}, {y, yb}});
+  HostPrefault touch_dist(dist, db, {{x, xb}, {y, yb}});
   DevBuf dx, dy, di, dd, ws;
-  SPV_TRY(dx.alloc(xb));
-  SPV_TRY(dy.alloc(yb));
-  SPV_TRY(di.alloc((size_t)yrows * 2 * sizeof(uint64_t)));
-  SPV_TRY(dd.alloc((size_t)yrows * 2 * sizeof(int32_t)));
-  SPV_TRY(ws.alloc(wsb));
-  hipStream_t st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
-  if (xb) SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, xb, hipMemcpyHostToDevice, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dy.p, y, yb, hipMemcpyHostToDevice, st));
+  SPV_TRY(alloc_all({{&dx, xb}, {&dy, yb}, {&di, ib}, {&dd, db}, {&ws, wsb}}));
+  SPV_TRY(dx.copy_in(x, xb, st));
+  SPV_TRY(dy.copy_in(y, yb, st));
   SPV_TRY(l1k2_run(dx.as<uint8_t>(), dy.as<uint8_t>(), xrows, yrows, dim, di.as<uint64_t>(),
                    dd.as<int32_t>(), ws.p, wsb, st));
   touch_idx.wait();
   touch_dist.wait();
-  SPV_HIP_CHECK(hipMemcpyAsync(dist, dd.p, (size_t)yrows * 2 * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, st));
-  return download(dev, idx, di.p, (size_t)yrows * 2 * sizeof(uint64_t), st);
+  SPV_TRY(dd.copy_out(dist, db, st));
+  return download(dev, idx, di.p, ib, st);
 }
-
-int host_l1k2_gathered(const std::vector<int> &devs, const uint8_t *x, const uint8_t *y, int xrows, int yrows,
-                       int dim, uint64_t *idx, int32_t *dist);
-int host_cascade_gathered(const std::vector<int> &devs, const float *x, const float *y, int xrows, int yrows,
-                          int dim, int m, int n, int g, const float *dict, uint64_t *idx, float *dist,
-                          int32_t *ncand);
-int host_dlt_gathered(const std::vector<int> &devs, const double *P0, const double *P1, int npt, const double *x,
-                      const double *xp, double *dst, bool want_error);
 
 int host_l1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim, uint64_t *idx,
               int32_t *dist) {
   if (yrows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
   const std::vector<int> devs = device_list();
-  if (yrows > 0 && use_rccl_gather(devs, yrows)) return host_l1k2_gathered(devs, x, y, xrows, yrows, dim, idx, dist);
+  if (yrows > 0 && gather_transport(devs, yrows) != SPV_GATHER_DIRECT) {
+    SPV_TRY(check_l1k2_args(x, y, xrows, yrows, dim, idx, dist));
+    return l1k2_gathered(devs, {x, nullptr}, {y, nullptr}, xrows, yrows, dim, idx, dist, SPV_GATHER_AUTO);
+  }
   return run_sharded(yrows, [&](int dev, long long lo, long long hi) {
     return host_l1k2_one(dev, x, y ? y + (size_t)lo * dim : y, xrows, (int)(hi - lo), dim,
                          idx ? idx + 2 * lo : idx, dist ? dist + 2 * lo : dist);
@@ -760,36 +248,18 @@ int host_bruteforce(const void *x, const void *y, int is_int, int xrows, int yro
   SPV_TRY(bruteforce_check(xrows, yrows, dim, k, p));
   if (yrows == 0) return SPV_OK;
   if (!y || !idx || !dist || (xrows > 0 && !x)) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(ensure_device());
-  int dev = 0;
-  SPV_HIP_CHECK(hipGetDevice(&dev));
-  const size_t xb = (size_t)xrows * dim * 4, yb = (size_t)yrows * dim * 4;
+  const int dev = device_list()[0];
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
   const size_t ib = (size_t)yrows * k * sizeof(uint64_t), db = (size_t)yrows * k * 4;
   const size_t wsb = bruteforce_plan(xrows, yrows, k, 0).part_bytes;
   DevBuf dx, dy, di, dd, ws;
-  SPV_TRY(dx.alloc(xb));
-  SPV_TRY(dy.alloc(yb));
-  SPV_TRY(di.alloc(ib));
-  SPV_TRY(dd.alloc(db));
-  SPV_TRY(ws.alloc(wsb));
-  hipStream_t st = hipStreamPerThread;
-  if (xb) SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, xb, hipMemcpyHostToDevice, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dy.p, y, yb, hipMemcpyHostToDevice, st));
+  SPV_TRY(dx.upload(x, (size_t)xrows * dim * 4, st));
+  SPV_TRY(dy.upload(y, (size_t)yrows * dim * 4, st));
+  SPV_TRY(alloc_all({{&di, ib}, {&dd, db}, {&ws, wsb}}));
   SPV_TRY(bruteforce_run(dx.p, dy.p, is_int, xrows, yrows, dim, k, p, 0, di.as<uint64_t>(), dd.p, ws.p, wsb, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dist, dd.p, db, hipMemcpyDeviceToHost, st));
+  SPV_TRY(dd.copy_out(dist, db, st));
   return download(dev, idx, di.p, ib, st);
-}
-
-int check_cascade_args(int xrows, int yrows, int dim, int m, int n, int g) {
-  if (xrows < 0 || yrows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
-  if (dim <= 0 || dim % 16 != 0)
-    return set_error(SPV_ERR_INVALID,
-                     "Input matrix inner dimensions must be 16-byte aligned (dim=%d).", dim);
-  if (m < 1 || m > 31) return set_error(SPV_ERR_INVALID, "hash_bit_rate m=%d must be in [1,31]", m);
-  if (n < 1) return set_error(SPV_ERR_INVALID, "num_hash_tables n=%d must be >= 1", n);
-  if (g < 0 || g > m || g > 16)
-    return set_error(SPV_ERR_INVALID, "num_candidate_neighbours g=%d must be in [0,min(m,16)]", g);
-  return SPV_OK;
 }
 
 int host_cascade_one(int dev, const float *x, const float *y, int xrows, int yrows, int dim, int m,
@@ -798,40 +268,36 @@ int host_cascade_one(int dev, const float *x, const float *y, int xrows, int yro
   if (yrows == 0) return SPV_OK;
   if (!y || !idx || !dist || !dict || (xrows > 0 && !x))
     return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(use_device(dev));
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
   const size_t xb = (size_t)xrows * dim * sizeof(float), yb = (size_t)yrows * dim * sizeof(float);
   const size_t db = (size_t)n * dim * m * sizeof(float);
+  const size_t ib = (size_t)yrows * 2 * sizeof(uint64_t), sb = (size_t)yrows * 2 * sizeof(float);
+  const size_t nb = (size_t)yrows * sizeof(int32_t);
   const size_t wsb = cascade_workspace_bytes(xrows, yrows, dim, m, n, g);
-  HostPrefault touch_idx(idx, (size_t)yrows * 2 * sizeof(uint64_t), {{x, xb}, {y, yb}});
+  HostPrefault touch_idx(idx, ib, {{x, xb}, {y, yb}});
   DevBuf dx, dy, dd, di, dds, dn, ws;
-  SPV_TRY(dx.alloc(xb));
-  SPV_TRY(dy.alloc(yb));
-  SPV_TRY(dd.alloc(db));
-  SPV_TRY(di.alloc((size_t)yrows * 2 * sizeof(uint64_t)));
-  SPV_TRY(dds.alloc((size_t)yrows * 2 * sizeof(float)));
-  SPV_TRY(dn.alloc((size_t)yrows * sizeof(int32_t)));
-  SPV_TRY(ws.alloc(wsb));
-  hipStream_t st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
-  if (xb) SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, xb, hipMemcpyHostToDevice, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dy.p, y, yb, hipMemcpyHostToDevice, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dd.p, dict, db, hipMemcpyHostToDevice, st));
+  SPV_TRY(alloc_all({{&dx, xb}, {&dy, yb}, {&dd, db}, {&di, ib}, {&dds, sb}, {&dn, nb}, {&ws, wsb}}));
+  SPV_TRY(dx.copy_in(x, xb, st));
+  SPV_TRY(dy.copy_in(y, yb, st));
+  SPV_TRY(dd.copy_in(dict, db, st));
   SPV_TRY(cascade_run(dx.as<float>(), dy.as<float>(), xrows, yrows, dim, m, n, g, dd.as<float>(),
                       di.as<uint64_t>(), dds.as<float>(), dn.as<int32_t>(), ws.p, wsb, st));
   touch_idx.wait();
-  SPV_HIP_CHECK(hipMemcpyAsync(dist, dds.p, (size_t)yrows * 2 * sizeof(float),
-                               hipMemcpyDeviceToHost, st));
-  if (ncand)
-    SPV_HIP_CHECK(hipMemcpyAsync(ncand, dn.p, (size_t)yrows * sizeof(int32_t),
-                                 hipMemcpyDeviceToHost, st));
-  return download(dev, idx, di.p, (size_t)yrows * 2 * sizeof(uint64_t), st);
+  SPV_TRY(dds.copy_out(dist, sb, st));
+  if (ncand) SPV_TRY(dn.copy_out(ncand, nb, st));
+  return download(dev, idx, di.p, ib, st);
 }
 
 int host_cascade(const float *x, const float *y, int xrows, int yrows, int dim, int m, int n,
                  int g, const float *dict, uint64_t *idx, float *dist, int32_t *ncand) {
   SPV_TRY(check_cascade_args(xrows, yrows, dim, m, n, g));
   const std::vector<int> devs = device_list();
-  if (yrows > 0 && use_rccl_gather(devs, yrows))
-    return host_cascade_gathered(devs, x, y, xrows, yrows, dim, m, n, g, dict, idx, dist, ncand);
+  if (yrows > 0 && gather_transport(devs, yrows) != SPV_GATHER_DIRECT) {
+    if (!y || !idx || !dist || !dict || (xrows > 0 && !x)) return set_error(SPV_ERR_INVALID, "null pointer");
+    return cascade_gathered(devs, {x, nullptr}, {y, nullptr}, {dict, nullptr}, xrows, yrows, dim, m, n, g, idx, dist,
+                            ncand, SPV_GATHER_AUTO);
+  }
   return run_sharded(yrows, [&](int dev, long long lo, long long hi) {
     return host_cascade_one(dev, x, y ? y + (size_t)lo * dim : y, xrows, (int)(hi - lo), dim, m, n, g,
                             dict, idx ? idx + 2 * lo : idx, dist ? dist + 2 * lo : dist,
@@ -844,22 +310,20 @@ int host_dlt_one(int dev, const double *P0, const double *P1, int npt, const dou
   if (npt < 0) return set_error(SPV_ERR_INVALID, "negative point count");
   if (npt == 0) return SPV_OK;
   if (!P0 || !P1 || !x || !xp || !dst) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(use_device(dev));
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
   const size_t row = (want_error ? 1 : 4) * sizeof(double);
   const size_t ib = (size_t)npt * 3 * sizeof(double);
   const size_t ob = (size_t)npt * row;
   DevBuf dx, dxp, dd;
-  SPV_TRY(dx.alloc(ib));
-  SPV_TRY(dxp.alloc(ib));
-  SPV_TRY(dd.alloc(ob));
-  hipStream_t st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
+  SPV_TRY(alloc_all({{&dx, ib}, {&dxp, ib}, {&dd, ob}}));
   if (ob < D2HPipeline::kMinBytes) {
     HostPrefault touch(dst, ob, {{x, ib}, {xp, ib}});
-    SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, ib, hipMemcpyHostToDevice, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dxp.p, xp, ib, hipMemcpyHostToDevice, st));
+    SPV_TRY(dx.copy_in(x, ib, st));
+    SPV_TRY(dxp.copy_in(xp, ib, st));
     SPV_TRY(dlt_run(P0, P1, npt, dx.as<double>(), dxp.as<double>(), dd.as<double>(), want_error, st));
     touch.wait();
-    SPV_HIP_CHECK(hipMemcpyAsync(dst, dd.p, ob, hipMemcpyDeviceToHost, st));
+    SPV_TRY(dd.copy_out(dst, ob, st));
     SPV_HIP_CHECK(hipStreamSynchronize(st));
     return SPV_OK;
   }
@@ -904,7 +368,10 @@ int host_dlt(const double *P0, const double *P1, int npt, const double *x, const
   if (npt < 0) return set_error(SPV_ERR_INVALID, "negative point count");
   const int cols = want_error ? 1 : 4;
   const std::vector<int> devs = device_list();
-  if (npt > 0 && use_rccl_gather(devs, npt)) return host_dlt_gathered(devs, P0, P1, npt, x, xp, dst, want_error);
+  if (npt > 0 && gather_transport(devs, npt) != SPV_GATHER_DIRECT) {
+    if (!P0 || !P1 || !x || !xp || !dst) return set_error(SPV_ERR_INVALID, "null pointer");
+    return dlt_gathered(devs, P0, P1, {x, nullptr}, {xp, nullptr}, npt, dst, want_error, SPV_GATHER_AUTO);
+  }
   return run_sharded(npt, [&](int dev, long long lo, long long hi) {
     return host_dlt_one(dev, P0, P1, (int)(hi - lo), x ? x + 3 * lo : x, xp ? xp + 3 * lo : xp,
                         dst ? dst + cols * lo : dst, want_error);
@@ -916,27 +383,21 @@ int host_dlt_score(const double *P0, const double *P1s, int nhyp, int npt, const
   if (npt < 0 || nhyp < 0) return set_error(SPV_ERR_INVALID, "negative count");
   if (nhyp == 0) return SPV_OK;
   if (!P0 || !P1s || !counts || (npt > 0 && (!x || !xp))) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(ensure_device());
-  const size_t ib = (size_t)npt * 3 * sizeof(double);
-  DevBuf dx, dxp, dp, dc, dm, ws;
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t ib = (size_t)npt * 3 * sizeof(double), cb = (size_t)nhyp * sizeof(int32_t);
   const size_t wsb = dlt_score_workspace_bytes(nhyp, npt);
-  SPV_TRY(dx.alloc(ib));
-  SPV_TRY(dxp.alloc(ib));
-  SPV_TRY(dp.alloc((size_t)nhyp * 12 * sizeof(double)));
-  SPV_TRY(dc.alloc((size_t)nhyp * sizeof(int32_t)));
+  DevBuf dx, dxp, dp, dc, dm, ws;
+  SPV_TRY(dx.upload(x, ib, st));
+  SPV_TRY(dxp.upload(xp, ib, st));
+  SPV_TRY(dp.upload(P1s, (size_t)nhyp * 12 * sizeof(double), st));
+  SPV_TRY(dc.alloc(cb));
   if (mask) SPV_TRY(dm.alloc((size_t)nhyp * npt));
   SPV_TRY(ws.alloc(wsb));
-  hipStream_t st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
-  if (ib) {
-    SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, ib, hipMemcpyHostToDevice, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dxp.p, xp, ib, hipMemcpyHostToDevice, st));
-  }
-  SPV_HIP_CHECK(hipMemcpyAsync(dp.p, P1s, (size_t)nhyp * 12 * sizeof(double), hipMemcpyHostToDevice, st));
   SPV_TRY(dlt_score_run(P0, dp.as<double>(), nhyp, npt, dx.as<double>(), dxp.as<double>(), max_error,
                         dc.as<int>(), mask ? dm.as<unsigned char>() : nullptr, ws.p, wsb, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(counts, dc.p, (size_t)nhyp * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (mask && npt > 0)
-    SPV_HIP_CHECK(hipMemcpyAsync(mask, dm.p, (size_t)nhyp * npt, hipMemcpyDeviceToHost, st));
+  SPV_TRY(dc.copy_out(counts, cb, st));
+  if (mask) SPV_TRY(dm.copy_out(mask, (size_t)nhyp * npt, st));
   SPV_HIP_CHECK(hipStreamSynchronize(st));
   return SPV_OK;
 }
@@ -949,7 +410,8 @@ int host_ransac_process(const double *Fs, int nF, const double *x0, const double
   if (nF == 0) return SPV_OK;
   if (npt == 0) return set_error(SPV_ERR_INVALID, "no correspondences");
   if (!Fs || !x0 || !x1 || !success || !inlier_count || !best_cam) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(ensure_device());
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
   // candidates per launch: the scoring grid takes 65535 hypotheses (4 per candidate) and the
   // per-camera masks are kept under 1 GiB
   int chunk = 16383;
@@ -957,37 +419,30 @@ int host_ransac_process(const double *Fs, int nF, const double *x0, const double
   chunk = std::min(chunk, nF);
   const size_t ib = (size_t)npt * 3 * sizeof(double);
   const size_t wsb = ransac_workspace_bytes(chunk, npt, mask != nullptr);
+  const size_t c4 = (size_t)chunk * sizeof(int32_t), c8 = (size_t)chunk * sizeof(double);
   DevBuf dx, dxp, dF, ds, dc, db, dP, dr, dE, d4, dm, ws;
-  SPV_TRY(dx.alloc(ib));
-  SPV_TRY(dxp.alloc(ib));
-  SPV_TRY(dF.alloc((size_t)chunk * 9 * sizeof(double)));
-  SPV_TRY(ds.alloc((size_t)chunk * sizeof(int32_t)));
-  SPV_TRY(dc.alloc((size_t)chunk * sizeof(int32_t)));
-  SPV_TRY(db.alloc((size_t)chunk * sizeof(int32_t)));
-  SPV_TRY(dP.alloc((size_t)chunk * 12 * sizeof(double)));
-  SPV_TRY(dr.alloc((size_t)chunk * sizeof(double)));
-  SPV_TRY(dE.alloc((size_t)chunk * 9 * sizeof(double)));
-  SPV_TRY(d4.alloc((size_t)chunk * 4 * sizeof(int32_t)));
+  SPV_TRY(alloc_all({{&dx, ib}, {&dxp, ib}, {&dF, 9 * c8}, {&ds, c4}, {&dc, c4}, {&db, c4}, {&dP, 12 * c8},
+                     {&dr, c8}, {&dE, 9 * c8}, {&d4, 4 * c4}}));
   if (mask) SPV_TRY(dm.alloc((size_t)chunk * npt));
   SPV_TRY(ws.alloc(wsb));
-  hipStream_t st = hipStreamPerThread;
-  SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x0, ib, hipMemcpyHostToDevice, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dxp.p, x1, ib, hipMemcpyHostToDevice, st));
+  SPV_TRY(dx.copy_in(x0, ib, st));
+  SPV_TRY(dxp.copy_in(x1, ib, st));
   for (int f0 = 0; f0 < nF; f0 += chunk) {
     const int nf = std::min(chunk, nF - f0);
-    SPV_HIP_CHECK(hipMemcpyAsync(dF.p, Fs + (size_t)f0 * 9, (size_t)nf * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+    const size_t n4 = (size_t)nf * sizeof(int32_t), n8 = (size_t)nf * sizeof(double);
+    SPV_TRY(dF.copy_in(Fs + (size_t)f0 * 9, 9 * n8, st));
     SPV_TRY(ransac_process_run(dF.as<double>(), nf, npt, dx.as<double>(), dxp.as<double>(), ratio_allowed,
                                required_percent, max_error, find_best, ds.as<int>(), dc.as<int>(), db.as<int>(),
                                dP.as<double>(), dr.as<double>(), dE.as<double>(), d4.as<int>(),
                                mask ? dm.as<unsigned char>() : nullptr, ws.p, wsb, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(success + f0, ds.p, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(inlier_count + f0, dc.p, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(best_cam + f0, db.p, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (best_P) SPV_HIP_CHECK(hipMemcpyAsync(best_P + (size_t)f0 * 12, dP.p, (size_t)nf * 12 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (ratio) SPV_HIP_CHECK(hipMemcpyAsync(ratio + f0, dr.p, (size_t)nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (E) SPV_HIP_CHECK(hipMemcpyAsync(E + (size_t)f0 * 9, dE.p, (size_t)nf * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (counts4) SPV_HIP_CHECK(hipMemcpyAsync(counts4 + (size_t)f0 * 4, d4.p, (size_t)nf * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (mask) SPV_HIP_CHECK(hipMemcpyAsync(mask + (size_t)f0 * npt, dm.p, (size_t)nf * npt, hipMemcpyDeviceToHost, st));
+    SPV_TRY(ds.copy_out(success + f0, n4, st));
+    SPV_TRY(dc.copy_out(inlier_count + f0, n4, st));
+    SPV_TRY(db.copy_out(best_cam + f0, n4, st));
+    if (best_P) SPV_TRY(dP.copy_out(best_P + (size_t)f0 * 12, 12 * n8, st));
+    if (ratio) SPV_TRY(dr.copy_out(ratio + f0, n8, st));
+    if (E) SPV_TRY(dE.copy_out(E + (size_t)f0 * 9, 9 * n8, st));
+    if (counts4) SPV_TRY(d4.copy_out(counts4 + (size_t)f0 * 4, 4 * n4, st));
+    if (mask) SPV_TRY(dm.copy_out(mask + (size_t)f0 * npt, (size_t)nf * npt, st));
     SPV_HIP_CHECK(hipStreamSynchronize(st));  // the staging buffers are reused by the next chunk
   }
   return SPV_OK;
@@ -998,22 +453,20 @@ int host_seven_point(const double *x, const double *xp, int n, int32_t *nroot, d
   if (n < 0) return set_error(SPV_ERR_INVALID, "negative count");
   if (n == 0) return SPV_OK;
   if (!x || !xp || !nroot || !Fs) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(ensure_device());
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t ib = (size_t)n * 14 * sizeof(double), fb = (size_t)n * 27 * sizeof(double);
+  const size_t nb = (size_t)n * sizeof(int32_t), bb = (size_t)n * 18 * sizeof(double);
   DevBuf dx, dxp, dF, dn, db;
-  const size_t ib = (size_t)n * 14 * sizeof(double);
-  SPV_TRY(dx.alloc(ib));
-  SPV_TRY(dxp.alloc(ib));
-  SPV_TRY(dF.alloc((size_t)n * 27 * sizeof(double)));
-  SPV_TRY(dn.alloc((size_t)n * sizeof(int32_t)));
-  if (basis) SPV_TRY(db.alloc((size_t)n * 18 * sizeof(double)));
-  hipStream_t st = hipStreamPerThread;
-  SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, ib, hipMemcpyHostToDevice, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dxp.p, xp, ib, hipMemcpyHostToDevice, st));
+  SPV_TRY(dx.upload(x, ib, st));
+  SPV_TRY(dxp.upload(xp, ib, st));
+  SPV_TRY(alloc_all({{&dF, fb}, {&dn, nb}}));
+  if (basis) SPV_TRY(db.alloc(bb));
   SPV_TRY(seven_point_run(dx.as<double>(), dxp.as<double>(), n, dF.as<double>(), dn.as<int>(),
                           basis ? db.as<double>() : nullptr, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(Fs, dF.p, (size_t)n * 27 * sizeof(double), hipMemcpyDeviceToHost, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(nroot, dn.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (basis) SPV_HIP_CHECK(hipMemcpyAsync(basis, db.p, (size_t)n * 18 * sizeof(double), hipMemcpyDeviceToHost, st));
+  SPV_TRY(dF.copy_out(Fs, fb, st));
+  SPV_TRY(dn.copy_out(nroot, nb, st));
+  if (basis) SPV_TRY(db.copy_out(basis, bb, st));
   SPV_HIP_CHECK(hipStreamSynchronize(st));
   return SPV_OK;
 }
@@ -1066,10 +519,8 @@ int host_ransac_fit(const double *x0, const double *x1, int npt, double required
   SPV_TRY(ws.alloc(wsb));
   const double *d_x0 = x0, *d_x1 = x1;
   if (!inputs_on_device) {
-    SPV_TRY(dx.alloc(ib));
-    SPV_TRY(dxp.alloc(ib));
-    SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x0, ib, hipMemcpyHostToDevice, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dxp.p, x1, ib, hipMemcpyHostToDevice, st));
+    SPV_TRY(dx.upload(x0, ib, st));
+    SPV_TRY(dxp.upload(x1, ib, st));
     d_x0 = dx.as<double>();
     d_x1 = dxp.as<double>();
   }
@@ -1111,20 +562,16 @@ int host_ratio(const uint64_t *idx, const void *dist, int dist_is_float, int yro
   *count = 0;
   if (yrows == 0) return SPV_OK;
   if (!idx || !dist || !matches) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(ensure_device());
-  DevBuf di, dd, dm, dc, ws;
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
   const size_t wsb = ratio_workspace_bytes(yrows);
-  SPV_TRY(di.alloc((size_t)yrows * 2 * sizeof(uint64_t)));
-  SPV_TRY(dd.alloc((size_t)yrows * 2 * 4));
-  SPV_TRY(dm.alloc((size_t)yrows * 2 * sizeof(int32_t)));
-  SPV_TRY(dc.alloc(sizeof(int32_t)));
-  SPV_TRY(ws.alloc(wsb));
-  hipStream_t st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
-  SPV_HIP_CHECK(hipMemcpyAsync(di.p, idx, (size_t)yrows * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(dd.p, dist, (size_t)yrows * 2 * 4, hipMemcpyHostToDevice, st));
+  DevBuf di, dd, dm, dc, ws;
+  SPV_TRY(di.upload(idx, (size_t)yrows * 2 * sizeof(uint64_t), st));
+  SPV_TRY(dd.upload(dist, (size_t)yrows * 2 * 4, st));
+  SPV_TRY(alloc_all({{&dm, (size_t)yrows * 2 * sizeof(int32_t)}, {&dc, sizeof(int32_t)}, {&ws, wsb}}));
   SPV_TRY(ratio_run(di.as<uint64_t>(), dd.p, dist_is_float, yrows, min_ratio, dm.as<int>(), dc.as<int>(),
                     ws.p, wsb, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(count, dc.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  SPV_TRY(dc.copy_out(count, sizeof(int32_t), st));
   SPV_HIP_CHECK(hipStreamSynchronize(st));
   if (*count > 0)
     SPV_HIP_CHECK(hipMemcpy(matches, dm.p, (size_t)*count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1135,16 +582,15 @@ int host_sift_split(const float *table, int rows, float *geom, uint8_t *desc) {
   if (rows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
   if (rows == 0) return SPV_OK;
   if (!table || !geom || !desc) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(ensure_device());
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t gb = (size_t)rows * 4 * sizeof(float), db = (size_t)rows * 128;
   DevBuf dt, dg, dd;
-  SPV_TRY(dt.alloc((size_t)rows * 132 * sizeof(float)));
-  SPV_TRY(dg.alloc((size_t)rows * 4 * sizeof(float)));
-  SPV_TRY(dd.alloc((size_t)rows * 128));
-  hipStream_t st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
-  SPV_HIP_CHECK(hipMemcpyAsync(dt.p, table, (size_t)rows * 132 * sizeof(float), hipMemcpyHostToDevice, st));
+  SPV_TRY(dt.upload(table, (size_t)rows * 132 * sizeof(float), st));
+  SPV_TRY(alloc_all({{&dg, gb}, {&dd, db}}));
   SPV_TRY(sift_split_run(dt.as<float>(), rows, dg.as<float>(), dd.as<uint8_t>(), st));
-  SPV_HIP_CHECK(hipMemcpyAsync(geom, dg.p, (size_t)rows * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-  SPV_HIP_CHECK(hipMemcpyAsync(desc, dd.p, (size_t)rows * 128, hipMemcpyDeviceToHost, st));
+  SPV_TRY(dg.copy_out(geom, gb, st));
+  SPV_TRY(dd.copy_out(desc, db, st));
   SPV_HIP_CHECK(hipStreamSynchronize(st));
   return SPV_OK;
 }
@@ -1155,315 +601,21 @@ int host_normalize(const float *x, int rows, int dim, float *out_f32, uint8_t *o
   if (dim == 1 && rows > 1)
     return set_error(SPV_ERR_INVALID, "normalisation of a single-column table is not supported (dim=1)");
   if (!x || (!out_f32 && !out_u8)) return set_error(SPV_ERR_INVALID, "null pointer");
-  SPV_TRY(ensure_device());
-  const int dim16 = (dim + 15) / 16 * 16;
-  DevBuf dx, df, du, ws;
-  SPV_TRY(dx.alloc((size_t)rows * dim * sizeof(float)));
-  if (out_f32) SPV_TRY(df.alloc((size_t)rows * dim16 * sizeof(float)));
-  if (out_u8) SPV_TRY(du.alloc((size_t)rows * dim16));
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t ub = (size_t)rows * ((dim + 15) / 16 * 16), fb = ub * sizeof(float);
   const size_t wsb = normalize_workspace_bytes_rows(rows, dim);
+  DevBuf dx, df, du, ws;
+  SPV_TRY(dx.upload(x, (size_t)rows * dim * sizeof(float), st));
+  if (out_f32) SPV_TRY(df.alloc(fb));
+  if (out_u8) SPV_TRY(du.alloc(ub));
   SPV_TRY(ws.alloc(wsb));
-  hipStream_t st = hipStreamPerThread;  // concurrent callers (ctypes drops the GIL) do not serialise on the null stream
-  SPV_HIP_CHECK(hipMemcpyAsync(dx.p, x, (size_t)rows * dim * sizeof(float), hipMemcpyHostToDevice, st));
   SPV_TRY(normalize_run(dx.as<float>(), rows, dim, out_f32 ? df.as<float>() : nullptr,
                         out_u8 ? du.as<unsigned char>() : nullptr, ws.p, wsb, st));
-  if (out_f32)
-    SPV_HIP_CHECK(hipMemcpyAsync(out_f32, df.p, (size_t)rows * dim16 * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (out_u8) SPV_HIP_CHECK(hipMemcpyAsync(out_u8, du.p, (size_t)rows * dim16, hipMemcpyDeviceToHost, st));
+  if (out_f32) SPV_TRY(df.copy_out(out_f32, fb, st));
+  if (out_u8) SPV_TRY(du.copy_out(out_u8, ub, st));
   SPV_HIP_CHECK(hipStreamSynchronize(st));
   return SPV_OK;
-}
-
-// ---- RCCL-gathered sharding -----------------------------------------------------------
-// Device buffers of one shard (or of the root), alive until every stream of the call has drained.
-struct BufList {
-  std::vector<std::unique_ptr<DevBuf>> v;
-  int add(size_t bytes, DevBuf **out) {
-    v.emplace_back(new DevBuf);
-    *out = v.back().get();
-    return (*out)->alloc(bytes);
-  }
-};
-
-// total rows over the listed devices: rank r runs `produce` on a host thread of its own (device
-// devs[r] current, work enqueued on the clique's stream r) and leaves its rows, row_bytes[k] each,
-// in K send buffers of max_cnt rows; the calling thread then gathers each of the K buffers on rank 0
-// with one ncclGather per rank (gather.hip) and runs `consume` on the root: recv[k] holds
-// [G][max_cnt] rows in rank order.  Everything is synchronised before the buffers are released.
-template <typename Produce, typename Consume>
-int run_gathered(const std::vector<int> &all_devs, long long total, const std::vector<size_t> &row_bytes,
-                 Produce produce, Consume consume, int transport = SPV_GATHER_AUTO) {
-  const int G = (int)std::min<long long>((long long)all_devs.size(), std::max<long long>(total, 1));
-  const std::vector<int> devs(all_devs.begin(), all_devs.begin() + G);
-  const size_t K = row_bytes.size();
-  // (decided before the clique lock is taken: the automatic rule may itself build a clique under it)
-  const bool want_rccl = (transport == SPV_GATHER_AUTO ? gather_transport(all_devs, total) : transport) == SPV_GATHER_RCCL;
-  std::lock_guard<std::mutex> lk(gather_mutex());  // one clique user at a time
-  for (int d : devs) SPV_TRY(use_device(d));         // fail early on a bad device number
-  GatherCtx *ctx = nullptr;
-  SPV_TRY(gather_ctx_get(devs, want_rccl, &ctx));
-  const long long max_cnt = shard_lo(total, G, 1);   // = size of shard 0, the largest
-  std::vector<BufList> bufs(G + 1);                  // [G] = the root's receive / staging buffers
-  std::vector<std::vector<const void *>> send(K, std::vector<const void *>(G, nullptr));
-  std::vector<int> status(G, SPV_OK);
-  std::vector<std::string> message(G);
-  {
-    std::vector<std::thread> threads;
-    threads.reserve(G);
-    for (int r = 0; r < G; ++r) {
-      auto shard = [&, r] {
-        status[r] = guard([&] {
-          int st = use_device(devs[r]);
-          if (st == SPV_OK) {
-            std::vector<const void *> mine(K, nullptr);
-            st = produce(r, shard_lo(total, G, r), shard_lo(total, G, r + 1), max_cnt, gather_stream(ctx, r),
-                         bufs[r], mine);
-            for (size_t k = 0; k < K; ++k) send[k][r] = mine[k];
-          }
-          if (st != SPV_OK) message[r] = g_message;
-          return st;
-        });
-      };
-      try {
-        threads.emplace_back(shard);
-      } catch (...) {
-        shard();
-      }
-    }
-    for (auto &t : threads) t.join();
-  }
-  int st = SPV_OK;
-  for (int r = 0; r < G && st == SPV_OK; ++r)
-    if (status[r] != SPV_OK) st = set_error(status[r], "device %d: %s", devs[r], message[r].c_str());
-  std::vector<const void *> recv(K, nullptr);
-  if (st == SPV_OK) st = use_device(devs[0]);
-  for (size_t k = 0; k < K && st == SPV_OK; ++k) {
-    DevBuf *rb = nullptr;
-    st = bufs[G].add((size_t)G * max_cnt * row_bytes[k], &rb);
-    if (st == SPV_OK) {
-      recv[k] = rb->p;
-      st = gather_bytes_run(ctx, send[k], rb->p, (size_t)max_cnt * row_bytes[k]);
-    }
-  }
-  if (st == SPV_OK) st = use_device(devs[0]);
-  if (st == SPV_OK) st = consume(recv, G, max_cnt, gather_stream(ctx, 0), bufs[G]);
-  // drain every rank's stream before its buffers go back to the pool, error or not
-  for (int r = 0; r < G; ++r)
-    if (hipSetDevice(devs[r]) == hipSuccess) {
-      const hipError_t e = hipStreamSynchronize(gather_stream(ctx, r));
-      if (e != hipSuccess && st == SPV_OK)
-        st = set_error(SPV_ERR_HIP, "device %d: %s", devs[r], hipGetErrorString(e));
-    }
-  return st;
-}
-
-int host_l1k2_gathered(const std::vector<int> &devs, const uint8_t *x, const uint8_t *y, int xrows, int yrows,
-                       int dim, uint64_t *idx, int32_t *dist) {
-  SPV_TRY(check_l1k2_args(x, y, xrows, yrows, dim, idx, dist));
-  const size_t xb = (size_t)xrows * dim;
-  HostPrefault touch_idx(idx, (size_t)yrows * 2 * sizeof(uint64_t), {{x, xb}, {y, (size_t)yrows * dim}});
-  auto produce = [&](int, long long lo, long long hi, long long max_cnt, hipStream_t st, BufList &b,
-                     std::vector<const void *> &send) {
-    const int cnt = (int)(hi - lo);
-    const size_t wsb = spv_l1k2_workspace_bytes(xrows, cnt, dim);
-    DevBuf *dx, *dy, *di, *dd, *ws, *rec;
-    SPV_TRY(b.add(xb, &dx));
-    SPV_TRY(b.add((size_t)cnt * dim, &dy));
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(uint64_t), &di));
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(int32_t), &dd));
-    SPV_TRY(b.add(wsb, &ws));
-    SPV_TRY(b.add((size_t)max_cnt * sizeof(Record), &rec));
-    if (xb) SPV_HIP_CHECK(hipMemcpyAsync(dx->p, x, xb, hipMemcpyHostToDevice, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dy->p, y + (size_t)lo * dim, (size_t)cnt * dim, hipMemcpyHostToDevice, st));
-    SPV_TRY(l1k2_run(dx->as<uint8_t>(), dy->as<uint8_t>(), xrows, cnt, dim, di->as<uint64_t>(), dd->as<int32_t>(),
-                     ws->p, wsb, st));
-    SPV_TRY(gather_pack_run(di->as<uint64_t>(), dd->p, cnt, rec->p, st));
-    send[0] = rec->p;
-    return SPV_OK;
-  };
-  auto consume = [&](const std::vector<const void *> &recv, int G, long long max_cnt, hipStream_t st, BufList &b) {
-    DevBuf *di, *dd;
-    SPV_TRY(b.add((size_t)yrows * 2 * sizeof(uint64_t), &di));
-    SPV_TRY(b.add((size_t)yrows * 2 * sizeof(int32_t), &dd));
-    SPV_TRY(gather_widen_run(recv[0], yrows, G, max_cnt, di->as<uint64_t>(), dd->p, st));
-    touch_idx.wait();
-    SPV_HIP_CHECK(hipMemcpyAsync(idx, di->p, (size_t)yrows * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dist, dd->p, (size_t)yrows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    return SPV_OK;
-  };
-  return run_gathered(devs, yrows, {sizeof(Record)}, produce, consume);
-}
-
-// The same exchange with everything resident: device devs[r] already holds a replica of the database
-// (d_x[r]) and its contiguous balanced query shard (d_y[r]); the widened result lands in d_idx /
-// d_dist on devs[0].  Scratch comes from the per-device buffer cache, so repeated calls allocate
-// nothing.  Returns after every rank's stream has drained.
-int device_l1k2_gathered(const std::vector<int> &devs, const uint8_t *const *d_x, const uint8_t *const *d_y,
-                         int xrows, long long yrows, int dim, uint64_t *d_idx, int32_t *d_dist, int transport) {
-  auto produce = [&](int r, long long lo, long long hi, long long max_cnt, hipStream_t st, BufList &b,
-                     std::vector<const void *> &send) {
-    const int cnt = (int)(hi - lo);
-    const size_t wsb = spv_l1k2_workspace_bytes(xrows, cnt, dim);
-    DevBuf *di, *dd, *ws, *rec;
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(uint64_t), &di));
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(int32_t), &dd));
-    SPV_TRY(b.add(wsb, &ws));
-    SPV_TRY(b.add((size_t)max_cnt * sizeof(Record), &rec));
-    SPV_TRY(l1k2_run(d_x[r], d_y[r], xrows, cnt, dim, di->as<uint64_t>(), dd->as<int32_t>(), ws->p, wsb, st));
-    SPV_TRY(gather_pack_run(di->as<uint64_t>(), dd->p, cnt, rec->p, st));
-    send[0] = rec->p;
-    return SPV_OK;
-  };
-  auto consume = [&](const std::vector<const void *> &recv, int G, long long max_cnt, hipStream_t st, BufList &) {
-    return gather_widen_run(recv[0], yrows, G, max_cnt, d_idx, d_dist, st);
-  };
-  return run_gathered(devs, yrows, {sizeof(Record)}, produce, consume, transport);
-}
-
-// Cascade hash and DLT with everything resident, the same way: per-device replicas of the database
-// and of the hyperplanes (every rank rebuilds identical codes and bucket tables), query / point shards
-// per device, results gathered and (cascade) widened on devs[0].
-int device_cascade_gathered(const std::vector<int> &devs, const float *const *d_x, const float *const *d_y,
-                            int xrows, long long yrows, int dim, int m, int n, int g, const float *const *d_dict,
-                            uint64_t *d_idx, float *d_dist, int32_t *d_ncand, int transport) {
-  auto produce = [&](int r, long long lo, long long hi, long long max_cnt, hipStream_t st, BufList &b,
-                     std::vector<const void *> &send) {
-    const int cnt = (int)(hi - lo);
-    const size_t wsb = cascade_workspace_bytes(xrows, cnt, dim, m, n, g);
-    DevBuf *di, *dds, *dn, *ws, *rec;
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(uint64_t), &di));
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(float), &dds));
-    SPV_TRY(b.add((size_t)max_cnt * sizeof(int32_t), &dn));
-    SPV_TRY(b.add(wsb, &ws));
-    SPV_TRY(b.add((size_t)max_cnt * sizeof(Record), &rec));
-    SPV_TRY(cascade_run(d_x[r], d_y[r], xrows, cnt, dim, m, n, g, d_dict[r], di->as<uint64_t>(), dds->as<float>(),
-                        d_ncand ? dn->as<int32_t>() : nullptr, ws->p, wsb, st));
-    SPV_TRY(gather_pack_run(di->as<uint64_t>(), dds->p, cnt, rec->p, st));  // float32 distances as their bits
-    send[0] = rec->p;
-    if (d_ncand) send[1] = dn->p;
-    return SPV_OK;
-  };
-  auto consume = [&](const std::vector<const void *> &recv, int G, long long max_cnt, hipStream_t st, BufList &) {
-    SPV_TRY(gather_widen_run(recv[0], yrows, G, max_cnt, d_idx, d_dist, st));
-    if (d_ncand)
-      for (int r = 0; r < G; ++r) {  // the shards' segments to their slices of the root's array
-        const long long lo = shard_lo(yrows, G, r), hi = shard_lo(yrows, G, r + 1);
-        SPV_HIP_CHECK(hipMemcpyAsync(d_ncand + lo, static_cast<const int32_t *>(recv[1]) + (size_t)r * max_cnt,
-                                     (size_t)(hi - lo) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-      }
-    return SPV_OK;
-  };
-  std::vector<size_t> rows = {sizeof(Record)};
-  if (d_ncand) rows.push_back(sizeof(int32_t));
-  return run_gathered(devs, yrows, rows, produce, consume, transport);
-}
-
-int device_dlt_gathered(const std::vector<int> &devs, const double *P0, const double *P1, long long npt,
-                        const double *const *d_x, const double *const *d_xp, double *d_dst, bool want_error,
-                        int transport) {
-  const size_t row = (want_error ? 1 : 4) * sizeof(double);
-  auto produce = [&](int r, long long lo, long long hi, long long max_cnt, hipStream_t st, BufList &b,
-                     std::vector<const void *> &send) {
-    DevBuf *dd;
-    SPV_TRY(b.add((size_t)max_cnt * row, &dd));
-    SPV_TRY(dlt_run(P0, P1, hi - lo, d_x[r], d_xp[r], dd->as<double>(), want_error, st));
-    send[0] = dd->p;
-    return SPV_OK;
-  };
-  auto consume = [&](const std::vector<const void *> &recv, int G, long long max_cnt, hipStream_t st, BufList &) {
-    for (int r = 0; r < G; ++r) {  // rows are already in the ABI layout: shard segments to their slices
-      const long long lo = shard_lo(npt, G, r), hi = shard_lo(npt, G, r + 1);
-      SPV_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(d_dst) + (size_t)lo * row,
-                                   static_cast<const char *>(recv[0]) + (size_t)r * max_cnt * row,
-                                   (size_t)(hi - lo) * row, hipMemcpyDeviceToDevice, st));
-    }
-    return SPV_OK;
-  };
-  return run_gathered(devs, npt, {row}, produce, consume, transport);
-}
-
-int host_cascade_gathered(const std::vector<int> &devs, const float *x, const float *y, int xrows, int yrows,
-                          int dim, int m, int n, int g, const float *dict, uint64_t *idx, float *dist,
-                          int32_t *ncand) {
-  if (!y || !idx || !dist || !dict || (xrows > 0 && !x)) return set_error(SPV_ERR_INVALID, "null pointer");
-  const size_t xb = (size_t)xrows * dim * sizeof(float);
-  const size_t db = (size_t)n * dim * m * sizeof(float);
-  HostPrefault touch_idx(idx, (size_t)yrows * 2 * sizeof(uint64_t), {{x, xb}, {y, (size_t)yrows * dim * sizeof(float)}});
-  auto produce = [&](int, long long lo, long long hi, long long max_cnt, hipStream_t st, BufList &b,
-                     std::vector<const void *> &send) {
-    const int cnt = (int)(hi - lo);
-    const size_t yb = (size_t)cnt * dim * sizeof(float);
-    const size_t wsb = cascade_workspace_bytes(xrows, cnt, dim, m, n, g);
-    DevBuf *dx, *dy, *dd, *di, *dds, *dn, *ws, *rec;
-    SPV_TRY(b.add(xb, &dx));
-    SPV_TRY(b.add(yb, &dy));
-    SPV_TRY(b.add(db, &dd));
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(uint64_t), &di));
-    SPV_TRY(b.add((size_t)cnt * 2 * sizeof(float), &dds));
-    SPV_TRY(b.add((size_t)max_cnt * sizeof(int32_t), &dn));
-    SPV_TRY(b.add(wsb, &ws));
-    SPV_TRY(b.add((size_t)max_cnt * sizeof(Record), &rec));
-    if (xb) SPV_HIP_CHECK(hipMemcpyAsync(dx->p, x, xb, hipMemcpyHostToDevice, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dy->p, y + (size_t)lo * dim, yb, hipMemcpyHostToDevice, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dd->p, dict, db, hipMemcpyHostToDevice, st));
-    SPV_TRY(cascade_run(dx->as<float>(), dy->as<float>(), xrows, cnt, dim, m, n, g, dd->as<float>(),
-                        di->as<uint64_t>(), dds->as<float>(), ncand ? dn->as<int32_t>() : nullptr, ws->p, wsb, st));
-    SPV_TRY(gather_pack_run(di->as<uint64_t>(), dds->p, cnt, rec->p, st));  // float32 distances as their bits
-    send[0] = rec->p;
-    if (ncand) send[1] = dn->p;
-    return SPV_OK;
-  };
-  auto consume = [&](const std::vector<const void *> &recv, int G, long long max_cnt, hipStream_t st, BufList &b) {
-    DevBuf *di, *dd;
-    SPV_TRY(b.add((size_t)yrows * 2 * sizeof(uint64_t), &di));
-    SPV_TRY(b.add((size_t)yrows * 2 * sizeof(float), &dd));
-    SPV_TRY(gather_widen_run(recv[0], yrows, G, max_cnt, di->as<uint64_t>(), dd->p, st));
-    touch_idx.wait();
-    SPV_HIP_CHECK(hipMemcpyAsync(idx, di->p, (size_t)yrows * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dist, dd->p, (size_t)yrows * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (ncand)
-      for (int r = 0; r < G; ++r) {  // 4 bytes per query: the shards' segments straight to their slices
-        const long long lo = shard_lo(yrows, G, r), hi = shard_lo(yrows, G, r + 1);
-        SPV_HIP_CHECK(hipMemcpyAsync(ncand + lo, static_cast<const int32_t *>(recv[1]) + (size_t)r * max_cnt,
-                                     (size_t)(hi - lo) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      }
-    return SPV_OK;
-  };
-  std::vector<size_t> rows = {sizeof(Record)};
-  if (ncand) rows.push_back(sizeof(int32_t));
-  return run_gathered(devs, yrows, rows, produce, consume);
-}
-
-int host_dlt_gathered(const std::vector<int> &devs, const double *P0, const double *P1, int npt, const double *x,
-                      const double *xp, double *dst, bool want_error) {
-  if (!P0 || !P1 || !x || !xp || !dst) return set_error(SPV_ERR_INVALID, "null pointer");
-  const size_t row = (want_error ? 1 : 4) * sizeof(double);
-  HostPrefault touch(dst, (size_t)npt * row, {{x, (size_t)npt * 24}, {xp, (size_t)npt * 24}});
-  auto produce = [&](int, long long lo, long long hi, long long max_cnt, hipStream_t st, BufList &b,
-                     std::vector<const void *> &send) {
-    const long long cnt = hi - lo;
-    const size_t ib = (size_t)cnt * 3 * sizeof(double);
-    DevBuf *dx, *dxp, *dd;
-    SPV_TRY(b.add(ib, &dx));
-    SPV_TRY(b.add(ib, &dxp));
-    SPV_TRY(b.add((size_t)max_cnt * row, &dd));
-    SPV_HIP_CHECK(hipMemcpyAsync(dx->p, x + 3 * lo, ib, hipMemcpyHostToDevice, st));
-    SPV_HIP_CHECK(hipMemcpyAsync(dxp->p, xp + 3 * lo, ib, hipMemcpyHostToDevice, st));
-    SPV_TRY(dlt_run(P0, P1, cnt, dx->as<double>(), dxp->as<double>(), dd->as<double>(), want_error, st));
-    send[0] = dd->p;
-    return SPV_OK;
-  };
-  auto consume = [&](const std::vector<const void *> &recv, int G, long long max_cnt, hipStream_t st, BufList &) {
-    touch.wait();
-    for (int r = 0; r < G; ++r) {  // rows are already in the ABI layout: shard segments to their slices
-      const long long lo = shard_lo(npt, G, r), hi = shard_lo(npt, G, r + 1);
-      SPV_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(dst) + (size_t)lo * row,
-                                   static_cast<const char *>(recv[0]) + (size_t)r * max_cnt * row,
-                                   (size_t)(hi - lo) * row, hipMemcpyDeviceToHost, st));
-    }
-    return SPV_OK;
-  };
-  return run_gathered(devs, npt, {row}, produce, consume);
 }
 
 // Hyperplanes as the reference draws them (src/CascadingHashNn.h:86-100):
@@ -1547,22 +699,13 @@ int spv_device_count(void) {
   if (hipGetDeviceCount(&c) != hipSuccess) return 0;
   return c;
 }
-int spv_set_device(int device) {
-  clear_error();
-  if (device < 0) return set_error(SPV_ERR_INVALID, "device %d", device);
-  std::lock_guard<std::mutex> lk(g_cfg_mutex);
-  g_device = device;
-  g_devices.assign(1, device);
-  return SPV_OK;
-}
+int spv_set_device(int device) { return spv_set_devices(&device, 1); }
 int spv_set_devices(const int *devices, int count) {
   clear_error();
   if (count < 1 || !devices) return set_error(SPV_ERR_INVALID, "need at least one device");
   for (int i = 0; i < count; ++i)
     if (devices[i] < 0) return set_error(SPV_ERR_INVALID, "device %d", devices[i]);
-  std::lock_guard<std::mutex> lk(g_cfg_mutex);
-  g_devices.assign(devices, devices + count);
-  g_device = devices[0];
+  set_device_list(devices, count);
   return SPV_OK;
 }
 
@@ -1570,15 +713,11 @@ int spv_set_gather_mode(int mode) {
   clear_error();
   if (mode != SPV_GATHER_AUTO && mode != SPV_GATHER_DIRECT && mode != SPV_GATHER_RCCL && mode != SPV_GATHER_PEERCOPY)
     return set_error(SPV_ERR_INVALID, "gather mode %d", mode);
-  std::lock_guard<std::mutex> lk(g_cfg_mutex);
-  g_gather_mode = mode;
+  set_gather_mode(mode);
   return SPV_OK;
 }
 
-void spv_release_cached_memory(void) {
-  g_pool.clear();
-  g_pinned.clear();
-}
+void spv_release_cached_memory(void) { release_transfer_caches(); }
 
 void spv_profile_enable(int on) {
   g_prof_on.store(on != 0);
@@ -1666,7 +805,7 @@ void nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int
     SPV_TRY(alloc_out(outdist, (size_t)yrows, 2, (int)sizeof(float)));
     uint32_t seed;
     {
-      std::lock_guard<std::mutex> lk(g_cfg_mutex);
+      std::lock_guard<std::mutex> lk(g_seed_mutex);
       const char *e = getenv("SPECTAVI_HASH_SEED");
       if (g_seed_fixed)
         seed = g_seed;
@@ -1685,34 +824,29 @@ void nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int
 
 void dlt_triangulate(const double *P0, const double *P1, int npt, const double *x,
                      const double *xp, double *dst) {
-  clear_error();
-  (void)host_guard([&] { return host_dlt(P0, P1, npt, x, xp, dst, false); });
+  (void)host_api([&] { return host_dlt(P0, P1, npt, x, xp, dst, false); });
 }
 
 void dlt_reprojection_error(const double *P0, const double *P1, int npt, const double *x,
                             const double *xp, double *dst) {
-  clear_error();
-  (void)host_guard([&] { return host_dlt(P0, P1, npt, x, xp, dst, true); });
+  (void)host_api([&] { return host_dlt(P0, P1, npt, x, xp, dst, true); });
 }
 
 // ---- host-pointer status variants ---------------------------------------------------
 int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
                           uint64_t *idx, int32_t *dist) {
-  clear_error();
-  return host_guard([&] { return host_l1k2(x, y, xrows, yrows, dim, idx, dist); });
+  return host_api([&] { return host_l1k2(x, y, xrows, yrows, dim, idx, dist); });
 }
 
 int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                       uint64_t *idx, void *dist) {
-  clear_error();
-  return host_guard([&] { return host_bruteforce(x, y, is_int, xrows, yrows, dim, k, p, idx, dist); });
+  return host_api([&] { return host_bruteforce(x, y, is_int, xrows, yrows, dim, k, p, idx, dist); });
 }
 
 int spv_nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int dim, int m,
                           int n, int g, const float *dict, uint64_t *idx, float *dist,
                           int32_t *ncand) {
-  clear_error();
-  return host_guard([&] { return host_cascade(x, y, xrows, yrows, dim, m, n, g, dict, idx, dist, ncand); });
+  return host_api([&] { return host_cascade(x, y, xrows, yrows, dim, m, n, g, dict, idx, dist, ncand); });
 }
 
 int spv_generate_hash_dict(uint32_t seed, int dim, int m, int n, float *dict) {
@@ -1723,19 +857,17 @@ int spv_generate_hash_dict(uint32_t seed, int dim, int m, int n, float *dict) {
 }
 
 void spv_set_hash_seed(uint32_t seed, int use_fixed) {
-  std::lock_guard<std::mutex> lk(g_cfg_mutex);
+  std::lock_guard<std::mutex> lk(g_seed_mutex);
   g_seed = seed;
   g_seed_fixed = use_fixed != 0;
 }
 
 int spv_dlt_triangulate(const double *P0, const double *P1, int npt, const double *x,
                         const double *xp, double *dst) {
-  clear_error();
-  return host_guard([&] { return host_dlt(P0, P1, npt, x, xp, dst, false); });
+  return host_api([&] { return host_dlt(P0, P1, npt, x, xp, dst, false); });
 }
 int spv_normalize(const float *x, int rows, int dim, float *out_f32, uint8_t *out_u8) {
-  clear_error();
-  return host_guard([&] { return host_normalize(x, rows, dim, out_f32, out_u8); });
+  return host_api([&] { return host_normalize(x, rows, dim, out_f32, out_u8); });
 }
 size_t spv_normalize_workspace_bytes(int dim) { return dim <= 0 ? 0 : normalize_workspace_bytes(dim); }
 size_t spv_normalize_workspace_bytes_rows(int rows, int dim) {
@@ -1743,64 +875,54 @@ size_t spv_normalize_workspace_bytes_rows(int rows, int dim) {
 }
 int spv_normalize_device(const float *d_x, int rows, int dim, float *d_out_f32, uint8_t *d_out_u8,
                          void *d_ws, size_t ws_bytes, void *stream) {
-  clear_error();
-  return guard([&] { return normalize_run(d_x, rows, dim, d_out_f32, d_out_u8, d_ws, ws_bytes, static_cast<hipStream_t>(stream)); });
+  return api([&] { return normalize_run(d_x, rows, dim, d_out_f32, d_out_u8, d_ws, ws_bytes, static_cast<hipStream_t>(stream)); });
 }
 int spv_sift_split(const float *table, int rows, float *geom, uint8_t *desc) {
-  clear_error();
-  return host_guard([&] { return host_sift_split(table, rows, geom, desc); });
+  return host_api([&] { return host_sift_split(table, rows, geom, desc); });
 }
 int spv_sift_split_device(const float *d_table, int rows, float *d_geom, uint8_t *d_desc,
                           void *stream) {
-  clear_error();
-  return guard([&] { return sift_split_run(d_table, rows, d_geom, d_desc, static_cast<hipStream_t>(stream)); });
+  return api([&] { return sift_split_run(d_table, rows, d_geom, d_desc, static_cast<hipStream_t>(stream)); });
 }
 int spv_gather_match_coords_device(const float *d_geom_x, const float *d_geom_y,
                                    const int32_t *d_matches, const int32_t *d_count, int capacity,
                                    double *d_x0, double *d_x1, void *stream) {
-  clear_error();
-  return guard([&] { return gather_match_coords_run(d_geom_x, d_geom_y, d_matches, d_count, capacity, d_x0, d_x1,
-                                 static_cast<hipStream_t>(stream)); });
+  return api([&] { return gather_match_coords_run(d_geom_x, d_geom_y, d_matches, d_count, capacity, d_x0, d_x1,
+                                                  static_cast<hipStream_t>(stream)); });
 }
 int spv_ratio_test(const uint64_t *idx, const void *dist, int dist_is_float, int yrows,
                    double min_ratio, int32_t *matches, int32_t *count) {
-  clear_error();
-  return host_guard([&] { return host_ratio(idx, dist, dist_is_float, yrows, min_ratio, matches, count); });
+  return host_api([&] { return host_ratio(idx, dist, dist_is_float, yrows, min_ratio, matches, count); });
 }
 size_t spv_ratio_test_workspace_bytes(int yrows) { return yrows < 0 ? 0 : ratio_workspace_bytes(yrows); }
 int spv_ratio_test_device(const uint64_t *d_idx, const void *d_dist, int dist_is_float, int yrows,
                           double min_ratio, int32_t *d_matches, int32_t *d_count, void *d_ws,
                           size_t ws_bytes, void *stream) {
-  clear_error();
-  return guard([&] { return ratio_run(d_idx, d_dist, dist_is_float, yrows, min_ratio, d_matches, d_count, d_ws, ws_bytes,
-                   static_cast<hipStream_t>(stream)); });
+  return api([&] { return ratio_run(d_idx, d_dist, dist_is_float, yrows, min_ratio, d_matches, d_count, d_ws, ws_bytes,
+                                    static_cast<hipStream_t>(stream)); });
 }
 int spv_dlt_score_hypotheses(const double *P0, const double *P1s, int nhyp, int npt,
                              const double *x, const double *xp, double max_error,
                              int32_t *counts, uint8_t *mask) {
-  clear_error();
-  return host_guard([&] { return host_dlt_score(P0, P1s, nhyp, npt, x, xp, max_error, counts, mask); });
+  return host_api([&] { return host_dlt_score(P0, P1s, nhyp, npt, x, xp, max_error, counts, mask); });
 }
 int spv_ransac_process_candidates(const double *Fs, int nF, const double *x0, const double *x1, int npt,
                                   double singular_value_ratio_allowed, double required_percent_inliers,
                                   double reprojection_error_allowed, int find_best_even_in_failure,
                                   int32_t *success, int32_t *inlier_count, int32_t *best_camera, double *best_P,
                                   double *gate_ratio, double *E, int32_t *counts4, uint8_t *inlier_mask) {
-  clear_error();
-  return host_guard([&] {
+  return host_api([&] {
     return host_ransac_process(Fs, nF, x0, x1, npt, singular_value_ratio_allowed, required_percent_inliers,
                                reprojection_error_allowed, find_best_even_in_failure, success, inlier_count,
                                best_camera, best_P, gate_ratio, E, counts4, inlier_mask);
   });
 }
 int spv_seven_point(const double *x, const double *xp, int n, int32_t *nroot, double *Fs, double *basis) {
-  clear_error();
-  return host_guard([&] { return host_seven_point(x, xp, n, nroot, Fs, basis); });
+  return host_api([&] { return host_seven_point(x, xp, n, nroot, Fs, basis); });
 }
 int spv_seven_point_device(const double *d_x, const double *d_xp, int n, double *d_Fs, int32_t *d_nroot,
                            double *d_basis, void *stream) {
-  clear_error();
-  return guard([&] { return seven_point_run(d_x, d_xp, n, d_Fs, d_nroot, d_basis, static_cast<hipStream_t>(stream)); });
+  return api([&] { return seven_point_run(d_x, d_xp, n, d_Fs, d_nroot, d_basis, static_cast<hipStream_t>(stream)); });
 }
 int spv_ransac_sample(unsigned long long seed, int npt, int ntries, int32_t *samples) {
   clear_error();
@@ -1815,8 +937,7 @@ int spv_ransac_fit(const double *x0, const double *x1, int npt, double required_
                    double singular_value_ratio_allowed, unsigned long long seed, int32_t *success,
                    double *essential, double *camera, double *inlier_percent, int32_t *inlier_idx,
                    int32_t *n_inliers, int32_t *best_try, int32_t *best_root, int32_t *tries_run) {
-  clear_error();
-  return host_guard([&] {
+  return host_api([&] {
     return host_ransac_fit(x0, x1, npt, required_percent_inliers, reprojection_error_allowed, maximum_tries,
                            find_best_even_in_failure, singular_value_ratio_allowed, nullptr, seed, success, essential,
                            camera, inlier_percent, inlier_idx, n_inliers, best_try, best_root, tries_run);
@@ -1828,8 +949,7 @@ int spv_ransac_fit_device(const double *d_x0, const double *d_x1, int npt, doubl
                           int32_t *success, double *essential, double *camera, double *inlier_percent,
                           int32_t *inlier_idx, int32_t *n_inliers, int32_t *best_try, int32_t *best_root,
                           int32_t *tries_run, void *stream) {
-  clear_error();
-  return guard([&] {
+  return api([&] {
     return host_ransac_fit(d_x0, d_x1, npt, required_percent_inliers, reprojection_error_allowed, maximum_tries,
                            find_best_even_in_failure, singular_value_ratio_allowed, samples, seed, success, essential,
                            camera, inlier_percent, inlier_idx, n_inliers, best_try, best_root, tries_run, true,
@@ -1910,8 +1030,7 @@ int spv_ransac_process_candidates_device(const double *d_Fs, int nF, long long n
                                          int32_t *d_best_camera, double *d_best_P, double *d_gate_ratio, double *d_E,
                                          int32_t *d_counts4, uint8_t *d_inlier_mask, void *d_ws, size_t ws_bytes,
                                          void *stream) {
-  clear_error();
-  return guard([&] {
+  return api([&] {
     return ransac_process_run(d_Fs, nF, npt, d_x0, d_x1, singular_value_ratio_allowed, required_percent_inliers,
                               reprojection_error_allowed, find_best_even_in_failure, d_success, d_inlier_count,
                               d_best_camera, d_best_P, d_gate_ratio, d_E, d_counts4, d_inlier_mask, d_ws, ws_bytes,
@@ -1922,28 +1041,25 @@ int spv_dlt_score_hypotheses_device(const double *P0, const double *d_P1s, int n
                                     long long npt, const double *d_x, const double *d_xp,
                                     double max_error, int32_t *d_counts, uint8_t *d_mask,
                                     void *stream) {
-  clear_error();
-  return guard([&] { return dlt_score_run(P0, d_P1s, nhyp, npt, d_x, d_xp, max_error, d_counts, d_mask, nullptr, 0,
-                       static_cast<hipStream_t>(stream)); });
+  return api([&] { return dlt_score_run(P0, d_P1s, nhyp, npt, d_x, d_xp, max_error, d_counts, d_mask, nullptr, 0,
+                                        static_cast<hipStream_t>(stream)); });
 }
 size_t spv_dlt_score_workspace_bytes(int nhyp, long long npt) { return dlt_score_workspace_bytes(nhyp, npt); }
 int spv_dlt_score_hypotheses_device_ws(const double *P0, const double *d_P1s, int nhyp, long long npt,
                                        const double *d_x, const double *d_xp, double max_error,
                                        int32_t *d_counts, uint8_t *d_mask, void *d_ws, size_t ws_bytes,
                                        void *stream) {
-  clear_error();
-  return guard([&] { return dlt_score_run(P0, d_P1s, nhyp, npt, d_x, d_xp, max_error, d_counts, d_mask, d_ws,
-                       ws_bytes, static_cast<hipStream_t>(stream)); });
+  return api([&] { return dlt_score_run(P0, d_P1s, nhyp, npt, d_x, d_xp, max_error, d_counts, d_mask, d_ws,
+                                        ws_bytes, static_cast<hipStream_t>(stream)); });
 }
 int spv_dlt_reprojection_error(const double *P0, const double *P1, int npt, const double *x,
                                const double *xp, double *dst) {
-  clear_error();
-  return host_guard([&] { return host_dlt(P0, P1, npt, x, xp, dst, true); });
+  return host_api([&] { return host_dlt(P0, P1, npt, x, xp, dst, true); });
 }
 
 // ---- device-pointer variants --------------------------------------------------------
 size_t spv_l1k2_workspace_bytes(int xrows, int yrows, int dim) {
-  if (dim <= 0 || dim % 16 != 0 || xrows < 0 || yrows < 0) return 0;
+  if (!l1k2_shape_ok(xrows, yrows, dim)) return 0;
   const L1K2Plan p = l1k2_plan(xrows, yrows, dim);
   return p.dim_pad < 0 ? 0 : p.total_bytes;
 }
@@ -1951,7 +1067,7 @@ size_t spv_l1k2_workspace_bytes(int xrows, int yrows, int dim) {
 int spv_l1k2_plan(int xrows, int yrows, int dim, int out[5]) {
   clear_error();
   if (!out) return set_error(SPV_ERR_INVALID, "null output");
-  if (dim <= 0 || dim % 16 != 0 || xrows < 0 || yrows < 0)
+  if (!l1k2_shape_ok(xrows, yrows, dim))
     return set_error(SPV_ERR_INVALID, "bad shape (xrows=%d, yrows=%d, dim=%d)", xrows, yrows, dim);
   const L1K2Plan p = l1k2_plan(xrows, yrows, dim);
   if (p.dim_pad < 0) return set_error(SPV_ERR_INVALID, "dim=%d is not supported by the L1 kernels", dim);
@@ -1965,9 +1081,8 @@ int spv_l1k2_plan(int xrows, int yrows, int dim, int out[5]) {
 
 int spv_l1k2_device(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,
                     uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, void *stream) {
-  clear_error();
-  return guard([&] { return l1k2_run(d_x, d_y, xrows, yrows, dim, d_idx, d_dist, d_ws, ws_bytes,
-                  static_cast<hipStream_t>(stream)); });
+  return api([&] { return l1k2_run(d_x, d_y, xrows, yrows, dim, d_idx, d_dist, d_ws, ws_bytes,
+                                   static_cast<hipStream_t>(stream)); });
 }
 
 size_t spv_bruteforce_workspace_bytes(int xrows, int yrows, int dim, int k) {
@@ -1981,35 +1096,28 @@ size_t spv_bruteforce_workspace_bytes(int xrows, int yrows, int dim, int k) {
 int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrows, int yrows, int dim, int k,
                           float p, int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes,
                           void *stream) {
-  clear_error();
-  return guard([&] {
+  return api([&] {
     return bruteforce_run(d_x, d_y, is_int, xrows, yrows, dim, k, p, slices, d_idx, d_dist, d_ws, ws_bytes,
                           static_cast<hipStream_t>(stream));
   });
 }
 
 size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g) {
-  if (dim <= 0 || dim % 16 != 0 || m < 1 || m > 31 || n < 1 || g < 0 || g > m || xrows < 0 ||
-      yrows < 0)
-    return 0;
+  if (!cascade_shape_ok(xrows, yrows, dim, m, n, g)) return 0;
   return cascade_workspace_bytes(xrows, yrows, dim, m, n, g);
 }
 
 int spv_l1k2_gathered_device(int ndev, const int *devices, const uint8_t *const *d_x, const uint8_t *const *d_y,
                              int xrows, long long yrows_total, int dim, uint64_t *d_idx, int32_t *d_dist,
                              int transport) {
-  clear_error();
-  return host_guard([&] {
-    if (ndev < 1 || ndev > 64 || !devices || !d_x || !d_y) return set_error(SPV_ERR_INVALID, "bad device list");
-    if (transport != SPV_GATHER_RCCL && transport != SPV_GATHER_PEERCOPY)
-      return set_error(SPV_ERR_INVALID, "transport must be SPV_GATHER_RCCL or SPV_GATHER_PEERCOPY");
+  return host_api([&] {
+    if (!d_x || !d_y) return set_error(SPV_ERR_INVALID, "bad device list");
+    SPV_TRY(check_gathered_devices(ndev, devices, transport));
     if (xrows < 0 || yrows_total < 0 || yrows_total > (long long)INT32_MAX * ndev)
       return set_error(SPV_ERR_INVALID, "bad row count");
-    if (dim <= 0 || dim % 16 != 0)
-      return set_error(SPV_ERR_INVALID, "Input matrix inner dimensions must be 16-byte aligned (dim=%d).", dim);
-    if (yrows_total == 0) return (int)SPV_OK;
+    SPV_TRY(check_dim(dim));
+    if (yrows_total == 0) return SPV_OK;
     if (!d_idx || !d_dist) return set_error(SPV_ERR_INVALID, "null pointer");
-    const std::vector<int> devs(devices, devices + ndev);
     const int G = (int)std::min<long long>(ndev, yrows_total);
     for (int r = 0; r < G; ++r) {
       if (!d_y[r] || (xrows > 0 && !d_x[r])) return set_error(SPV_ERR_INVALID, "null pointer (rank %d)", r);
@@ -2017,51 +1125,43 @@ int spv_l1k2_gathered_device(int ndev, const int *devices, const uint8_t *const 
         return set_error(SPV_ERR_INVALID, "device pointers must be 16-byte aligned (rank %d)", r);
     }
     if (((uintptr_t)d_idx | (uintptr_t)d_dist) & 15) return set_error(SPV_ERR_INVALID, "device pointers must be 16-byte aligned");
-    return device_l1k2_gathered(devs, d_x, d_y, xrows, yrows_total, dim, d_idx, d_dist, transport);
+    return l1k2_gathered(std::vector<int>(devices, devices + ndev), {nullptr, d_x}, {nullptr, d_y}, xrows, yrows_total,
+                         dim, d_idx, d_dist, transport);
   });
-}
-
-static int check_gathered_devices(int ndev, const int *devices, int transport) {
-  if (ndev < 1 || ndev > 64 || !devices) return set_error(SPV_ERR_INVALID, "bad device list");
-  if (transport != SPV_GATHER_RCCL && transport != SPV_GATHER_PEERCOPY)
-    return set_error(SPV_ERR_INVALID, "transport must be SPV_GATHER_RCCL or SPV_GATHER_PEERCOPY");
-  return SPV_OK;
 }
 
 int spv_cascade_gathered_device(int ndev, const int *devices, const float *const *d_x, const float *const *d_y,
                                 int xrows, long long yrows_total, int dim, int m, int n, int g,
                                 const float *const *d_dict, uint64_t *d_idx, float *d_dist, int32_t *d_ncand,
                                 int transport) {
-  clear_error();
-  return host_guard([&] {
+  return host_api([&] {
     SPV_TRY(check_gathered_devices(ndev, devices, transport));
     if (!d_x || !d_y || !d_dict) return set_error(SPV_ERR_INVALID, "null pointer");
     if (yrows_total < 0 || yrows_total > (long long)INT32_MAX * ndev) return set_error(SPV_ERR_INVALID, "bad row count");
     SPV_TRY(check_cascade_args(xrows, 0, dim, m, n, g));
-    if (yrows_total == 0) return (int)SPV_OK;
+    if (yrows_total == 0) return SPV_OK;
     if (!d_idx || !d_dist) return set_error(SPV_ERR_INVALID, "null pointer");
     const int G = (int)std::min<long long>(ndev, yrows_total);
     for (int r = 0; r < G; ++r)
       if (!d_y[r] || !d_dict[r] || (xrows > 0 && !d_x[r])) return set_error(SPV_ERR_INVALID, "null pointer (rank %d)", r);
-    return device_cascade_gathered(std::vector<int>(devices, devices + ndev), d_x, d_y, xrows, yrows_total, dim, m, n, g,
-                                   d_dict, d_idx, d_dist, d_ncand, transport);
+    return cascade_gathered(std::vector<int>(devices, devices + ndev), {nullptr, d_x}, {nullptr, d_y}, {nullptr, d_dict},
+                            xrows, yrows_total, dim, m, n, g, d_idx, d_dist, d_ncand, transport);
   });
 }
 
 int spv_dlt_gathered_device(int ndev, const int *devices, const double *P0, const double *P1, long long npt_total,
                             const double *const *d_x, const double *const *d_xp, double *d_dst, int want_error,
                             int transport) {
-  clear_error();
-  return host_guard([&] {
+  return host_api([&] {
     SPV_TRY(check_gathered_devices(ndev, devices, transport));
     if (npt_total < 0) return set_error(SPV_ERR_INVALID, "negative point count");
-    if (npt_total == 0) return (int)SPV_OK;
+    if (npt_total == 0) return SPV_OK;
     if (!P0 || !P1 || !d_x || !d_xp || !d_dst) return set_error(SPV_ERR_INVALID, "null pointer");
     const int G = (int)std::min<long long>(ndev, npt_total);
     for (int r = 0; r < G; ++r)
       if (!d_x[r] || !d_xp[r]) return set_error(SPV_ERR_INVALID, "null pointer (rank %d)", r);
-    return device_dlt_gathered(std::vector<int>(devices, devices + ndev), P0, P1, npt_total, d_x, d_xp, d_dst,
-                               want_error != 0, transport);
+    return dlt_gathered(std::vector<int>(devices, devices + ndev), P0, P1, {nullptr, d_x}, {nullptr, d_xp}, npt_total,
+                        d_dst, want_error != 0, transport);
   });
 }
 
@@ -2074,10 +1174,8 @@ long long spv_shard_lo(long long total, int shards, int r) {
 int spv_cascade_device(const float *d_x, const float *d_y, int xrows, int yrows, int dim, int m,
                        int n, int g, const float *d_dict, uint64_t *d_idx, float *d_dist,
                        int32_t *d_ncand, void *d_ws, size_t ws_bytes, void *stream) {
-  clear_error();
-  return guard([&] {
-    int s = check_cascade_args(xrows, yrows, dim, m, n, g);
-    if (s != SPV_OK) return s;
+  return api([&] {
+    SPV_TRY(check_cascade_args(xrows, yrows, dim, m, n, g));
     return cascade_run(d_x, d_y, xrows, yrows, dim, m, n, g, d_dict, d_idx, d_dist, d_ncand, d_ws,
                        ws_bytes, static_cast<hipStream_t>(stream));
   });
@@ -2086,14 +1184,12 @@ int spv_cascade_device(const float *d_x, const float *d_y, int xrows, int yrows,
 int spv_dlt_triangulate_device(const double *P0, const double *P1, long long npt,
                                const double *d_x, const double *d_xp, double *d_dst,
                                void *stream) {
-  clear_error();
-  return guard([&] { return dlt_run(P0, P1, npt, d_x, d_xp, d_dst, false, static_cast<hipStream_t>(stream)); });
+  return api([&] { return dlt_run(P0, P1, npt, d_x, d_xp, d_dst, false, static_cast<hipStream_t>(stream)); });
 }
 int spv_dlt_reprojection_error_device(const double *P0, const double *P1, long long npt,
                                       const double *d_x, const double *d_xp, double *d_dst,
                                       void *stream) {
-  clear_error();
-  return guard([&] { return dlt_run(P0, P1, npt, d_x, d_xp, d_dst, true, static_cast<hipStream_t>(stream)); });
+  return api([&] { return dlt_run(P0, P1, npt, d_x, d_xp, d_dst, true, static_cast<hipStream_t>(stream)); });
 }
 
 }  // extern "C"

@@ -6,8 +6,10 @@
 #include <stddef.h>
 
 #include <algorithm>
+#include <exception>
 #include <functional>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "../../include/spectavi_amd.h"
@@ -33,6 +35,22 @@ void clear_error();
     int _s = (expr);             \
     if (_s != SPV_OK) return _s; \
   } while (0)
+
+// No C++ exception may cross the extern "C" boundary (the reference's own symbols let them
+// escape into libffi and abort the process, src/BruteForceNnL1K2.h:75,79): every entry point,
+// and every host thread a call runs a shard on, runs its body through this.
+template <typename Fn>
+int guard(Fn fn) {
+  try {
+    return fn();
+  } catch (const std::bad_alloc &) {
+    return set_error(SPV_ERR_NOMEM, "host allocation failed");
+  } catch (const std::exception &e) {
+    return set_error(SPV_ERR_INTERNAL, "unexpected C++ exception: %s", e.what());
+  } catch (...) {
+    return set_error(SPV_ERR_INTERNAL, "unexpected C++ exception");
+  }
+}
 
 // Selects the process-wide device for host-pointer entry points on this thread.
 int ensure_device();

@@ -1,5 +1,5 @@
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from spectavi_amd import feature, mvg
 rng = np.random.default_rng(0)
 for n in (1000, 10000, 50000):
