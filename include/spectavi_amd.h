@@ -107,7 +107,7 @@ const char *spv_version(void);
 
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
  * "l1k2_tile", "l1k2_merge", "bruteforce", "bruteforce_merge", "cascade_project",
- * "cascade_buckets", "cascade_probe_refine", "dlt") are bracketed by hipEvents recorded on the
+ * "cascade_buckets", "cascade_probe_refine", "dlt", "rectify") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
  * last reset. */
@@ -233,6 +233,33 @@ void ransac_fitter(const double *x0, const double *x1, int npt, double required_
                    double singular_value_ratio_allowed, bool progressbar, bool *success, NdArray *essential,
                    NdArray *camera, double *inlier_percent, NdArray *inlier_idx);
 
+/* Epipolar-line rectification of an image pair.  Replaces reference src/Spectavi.cpp:89-119
+ * (Rectifier::resample, src/Camera.h:61-445).
+ *   P0, P1: double[3,4]; im0, im1: double[hgt, wid, nchan] (nchan = 1: [hgt, wid]).
+ *   rectified0/1: callee-allocated double[output_rows, output_cols] (nchan = 1) or
+ *   [output_rows, output_cols, nchan]; rectified_idx0/1: int32[output_rows, output_cols].
+ * Contract (IEEE double, every operation rounded on its own, sums left to right as written):
+ *   F = [P1 C]x P1 P0^T (P0 P0^T)^-1, C the unit null vector of P0, computed once on the host
+ *   (spv_rectify_fundamental; its bits are not part of the contract).
+ *   Shape (spv_rectify_shape): C = wid*nchan, output_cols = int(sf*C/nchan),
+ *   extra_rows = int(max(hgt, C)/2.), output_rows = hgt + 2*extra_rows, rnx = int(sf*wid).
+ *   Row r, v = r - extra_rows, x_i = 0. + i*delta with delta = (wid-1)/(rnx-1), i < min(rnx, output_cols):
+ *     image 0: l_j = (F[0][j]*0. + F[1][j]*v) + F[2][j], y_i = ((-l_2) - (l_0*x_i)) / l_1;
+ *     image 1: the same with m_j = (F[j][0]*x_0 + F[j][1]*y_0) + F[j][2], (x_0, y_0) image 0's
+ *     first sample of the row.
+ *   A sample is valid iff x > -1 && x < wid && y > -1 && y < hgt (NaN: invalid); then
+ *   value = im[(int)y, (int)x, :] copied bit for bit and idx = (int)y*wid + (int)x; otherwise
+ *   value 0.0 and idx -1.  Columns [rnx, output_cols) are 0 / -1; samples i >= output_cols are
+ *   dropped (the reference writes them past the row).  The reference's column alignment is a no-op
+ *   (every shift is 0) and is not reproduced.
+ * Defined where the reference is not: a singular P0 P0^T or a non-finite F (F all NaN) and cameras
+ * sharing a centre (F = 0) leave every sample invalid.  Rejected with SPV_ERR_INVALID (outputs not
+ * allocated): non-finite or non-positive sf, wid, hgt or nchan < 1, hgt*wid or wid*nchan >= 2^31,
+ * rnx < 1 or output_cols < 1, output_rows >= 2^31.  One device: the first one selected. */
+void image_pair_rectification(const double *P0, const double *P1, const double *im0, const double *im1, int wid,
+                              int hgt, int nchan, double sampling_factor, NdArray *rectified0, NdArray *rectified1,
+                              NdArray *rectified_idx0, NdArray *rectified_idx1);
+
 /* ------------------------------------------------------------------------ */
 /* 2. Host-pointer variants: caller-allocated outputs, int status            */
 /* ------------------------------------------------------------------------ */
@@ -340,6 +367,13 @@ int spv_ransac_fit_device(const double *d_x0, const double *d_x1, int npt, doubl
                           int32_t *inlier_idx, int32_t *n_inliers, int32_t *best_try, int32_t *best_root,
                           int32_t *tries_run, void *stream);
 
+/* The output shape of image_pair_rectification: out = {output_rows, output_cols, rnx}.  Host only;
+ * SPV_ERR_INVALID (out untouched) for the arguments image_pair_rectification rejects. */
+int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]);
+/* The fundamental matrix image_pair_rectification resamples with, F double[3,3] row-major (all NaN
+ * for a singular P0 P0^T, zero for cameras sharing a centre).  Host only. */
+int spv_rectify_fundamental(const double *P0, const double *P1, double *F);
+
 int spv_dlt_triangulate(const double *P0, const double *P1, int npt, const double *x,
                         const double *xp, double *dst);
 int spv_dlt_reprojection_error(const double *P0, const double *P1, int npt, const double *x,
@@ -406,6 +440,16 @@ size_t spv_bruteforce_workspace_bytes(int xrows, int yrows, int dim, int k);
 int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrows, int yrows, int dim, int k,
                           float p, int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes,
                           void *stream);
+
+/* image_pair_rectification with everything resident and F given (a HOST pointer, 9 doubles, from
+ * spv_rectify_fundamental): dtype SPV_RECTIFY_F64 (d_im0, d_im1, d_r0, d_r1 double, 8-byte aligned)
+ * or SPV_RECTIFY_U8 (uint8_t: 8-bit images, values copied as bytes); d_ri0, d_ri1 int32.  Output
+ * shapes from spv_rectify_shape; every element of the four outputs is written.  Asynchronous, no
+ * host synchronisation.  Kernel name for spv_profile_read: "rectify". */
+#define SPV_RECTIFY_F64 0
+#define SPV_RECTIFY_U8 1
+int spv_rectify_device(const double *F, const void *d_im0, const void *d_im1, int dtype, int wid, int hgt, int nchan,
+                       double sf, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, void *stream);
 
 /* Scratch bytes needed by spv_cascade_device. */
 size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g);

@@ -262,6 +262,32 @@ int host_bruteforce(const void *x, const void *y, int is_int, int xrows, int yro
   return download(dev, idx, di.p, ib, st);
 }
 
+// Rectification through host pointers, on the first selected device: both images up, one kernel,
+// the four outputs back.  r0 / r1 double[rows, cols, nchan], ri0 / ri1 int32[rows, cols].
+int host_rectify(const double *P0, const double *P1, const double *im0, const double *im1, int wid, int hgt,
+                 int nchan, double sf, double *r0, double *r1, int32_t *ri0, int32_t *ri1) {
+  int shape[3];
+  SPV_TRY(rectify_shape(wid, hgt, nchan, sf, shape));
+  if (!P0 || !P1 || !im0 || !im1 || !r0 || !r1 || !ri0 || !ri1) return set_error(SPV_ERR_INVALID, "null pointer");
+  double F[9];
+  rectify_fundamental(P0, P1, F);
+  const int dev = device_list()[0];
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
+  const size_t ib = (size_t)hgt * wid * nchan * sizeof(double);
+  const size_t ob = (size_t)shape[0] * shape[1], vb = ob * nchan * sizeof(double), xb = ob * sizeof(int32_t);
+  DevBuf di0, di1, dr0, dr1, dx0, dx1;
+  SPV_TRY(alloc_all({{&di0, ib}, {&di1, ib}, {&dr0, vb}, {&dr1, vb}, {&dx0, xb}, {&dx1, xb}}));
+  SPV_TRY(di0.copy_in(im0, ib, st));
+  SPV_TRY(di1.copy_in(im1, ib, st));
+  SPV_TRY(rectify_run(F, di0.p, di1.p, SPV_RECTIFY_F64, wid, hgt, nchan, sf, dr0.p, dr1.p, dx0.as<int32_t>(),
+                      dx1.as<int32_t>(), st));
+  SPV_TRY(dx0.copy_out(ri0, xb, st));
+  SPV_TRY(dx1.copy_out(ri1, xb, st));
+  SPV_TRY(download(dev, r0, dr0.p, vb, st));
+  return download(dev, r1, dr1.p, vb, st);
+}
+
 int host_cascade_one(int dev, const float *x, const float *y, int xrows, int yrows, int dim, int m,
                      int n, int g, const float *dict, uint64_t *idx, float *dist, int32_t *ncand) {
   SPV_TRY(check_cascade_args(xrows, yrows, dim, m, n, g));
@@ -636,7 +662,7 @@ void fill_hash_dict(uint32_t seed, int dim, int m, int n, float *dict) {
 #if !defined(SPECTAVI_EXTERNAL_NDARRAY) && !defined(SPV_NDARRAY_ITEMSIZE)
 #define SPV_NDARRAY_ITEMSIZE(arr) ((arr)->m_itemsize)
 #endif
-int alloc_out(NdArray *arr, size_t rows, size_t cols, int itemsize) {
+int alloc_out(NdArray *arr, size_t rows, size_t cols, int itemsize, size_t depth = 0) {
   if (!arr) return set_error(SPV_ERR_INVALID, "null NdArray");
 #ifdef SPV_NDARRAY_ITEMSIZE
   if ((int)SPV_NDARRAY_ITEMSIZE(arr) != itemsize)
@@ -644,7 +670,8 @@ int alloc_out(NdArray *arr, size_t rows, size_t cols, int itemsize) {
 #else
   (void)itemsize;
 #endif
-  ndarray_set_size(arr, rows, cols);
+  if (depth) ndarray_set_size3(arr, rows, cols, depth);
+  else ndarray_set_size(arr, rows, cols);
   ndarray_alloc(arr);
   if (!arr->m_data) return set_error(SPV_ERR_NOMEM, "ndarray_alloc failed");
   return SPV_OK;
@@ -830,6 +857,24 @@ void dlt_triangulate(const double *P0, const double *P1, int npt, const double *
 void dlt_reprojection_error(const double *P0, const double *P1, int npt, const double *x,
                             const double *xp, double *dst) {
   (void)host_api([&] { return host_dlt(P0, P1, npt, x, xp, dst, true); });
+}
+
+void image_pair_rectification(const double *P0, const double *P1, const double *im0, const double *im1, int wid,
+                              int hgt, int nchan, double sampling_factor, NdArray *rectified0, NdArray *rectified1,
+                              NdArray *rectified_idx0, NdArray *rectified_idx1) {
+  clear_error();
+  int shape[3];
+  if (rectify_shape(wid, hgt, nchan, sampling_factor, shape) != SPV_OK) return;
+  (void)host_guard([&] {
+    const size_t rows = (size_t)shape[0], cols = (size_t)shape[1], depth = nchan > 1 ? (size_t)nchan : 0;
+    SPV_TRY(alloc_out(rectified0, rows, cols, (int)sizeof(double), depth));
+    SPV_TRY(alloc_out(rectified1, rows, cols, (int)sizeof(double), depth));
+    SPV_TRY(alloc_out(rectified_idx0, rows, cols, (int)sizeof(int32_t)));
+    SPV_TRY(alloc_out(rectified_idx1, rows, cols, (int)sizeof(int32_t)));
+    return host_rectify(P0, P1, im0, im1, wid, hgt, nchan, sampling_factor,
+                        static_cast<double *>(rectified0->m_data), static_cast<double *>(rectified1->m_data),
+                        static_cast<int32_t *>(rectified_idx0->m_data), static_cast<int32_t *>(rectified_idx1->m_data));
+  });
 }
 
 // ---- host-pointer status variants ---------------------------------------------------
@@ -1052,6 +1097,21 @@ int spv_dlt_score_hypotheses_device_ws(const double *P0, const double *d_P1s, in
   return api([&] { return dlt_score_run(P0, d_P1s, nhyp, npt, d_x, d_xp, max_error, d_counts, d_mask, d_ws,
                                         ws_bytes, static_cast<hipStream_t>(stream)); });
 }
+int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]) {
+  return api([&] {
+    if (!out) return set_error(SPV_ERR_INVALID, "null output");
+    return rectify_shape(wid, hgt, nchan, sf, out);
+  });
+}
+
+int spv_rectify_fundamental(const double *P0, const double *P1, double *F) {
+  return api([&] {
+    if (!P0 || !P1 || !F) return set_error(SPV_ERR_INVALID, "null pointer");
+    rectify_fundamental(P0, P1, F);
+    return SPV_OK;
+  });
+}
+
 int spv_dlt_reprojection_error(const double *P0, const double *P1, int npt, const double *x,
                                const double *xp, double *dst) {
   return host_api([&] { return host_dlt(P0, P1, npt, x, xp, dst, true); });
@@ -1099,6 +1159,14 @@ int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrow
   return api([&] {
     return bruteforce_run(d_x, d_y, is_int, xrows, yrows, dim, k, p, slices, d_idx, d_dist, d_ws, ws_bytes,
                           static_cast<hipStream_t>(stream));
+  });
+}
+
+int spv_rectify_device(const double *F, const void *d_im0, const void *d_im1, int dtype, int wid, int hgt, int nchan,
+                       double sf, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, void *stream) {
+  return api([&] {
+    return rectify_run(F, d_im0, d_im1, dtype, wid, hgt, nchan, sf, d_r0, d_r1, d_ri0, d_ri1,
+                       static_cast<hipStream_t>(stream));
   });
 }
 

@@ -109,6 +109,13 @@ int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int di
 int dlt_run(const double *P0, const double *P1, long long npt, const double *d_x,
             const double *d_xp, double *d_dst, bool want_error, hipStream_t stream);
 
+// ---- epipolar rectification (rectify.hip) --------------------------------------------
+// out = {output_rows, output_cols, rnx}; SPV_ERR_INVALID (message set) outside the header's limits
+int rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]);
+void rectify_fundamental(const double *P0, const double *P1, double *F);  // host only
+int rectify_run(const double *F, const void *d_im0, const void *d_im1, int dtype, int wid, int hgt, int nchan,
+                double sf, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, hipStream_t stream);
+
 // ---- ratio test + compaction (match.hip) ---------------------------------------------
 size_t ratio_workspace_bytes(int yrows);
 int ratio_run(const uint64_t *d_idx, const void *d_dist, int dist_is_float, int yrows,

@@ -535,3 +535,37 @@ def seven_point(x, xp, want_basis=False):
         check(clib.spv_seven_point_device(x.data_ptr(), xp.data_ptr(), n, Fs.data_ptr(), nroot.data_ptr(),
                                           basis.data_ptr() if want_basis else None, stream))
     return (nroot, Fs, basis) if want_basis else (nroot, Fs)
+
+
+clib.spv_rectify_device.restype = ct.c_int
+clib.spv_rectify_device.argtypes = [_f64p, _vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_double,
+                                    _vp, _vp, _vp, _vp, _vp]
+_RECTIFY_DTYPE = {torch.float64: 0, torch.uint8: 1}  # SPV_RECTIFY_F64, SPV_RECTIFY_U8
+
+
+def image_pair_rectification(P0, P1, im0, im1, sampling_factor=1.2):
+    """mvg.image_pair_rectification with the images resident in HBM: im0, im1 CUDA tensors of one
+    shape, [hgt, wid] or [hgt, wid, nchan], both float64 or both uint8 (values are copied, never
+    computed, so 8-bit images stay 8-bit).  P0, P1 float64 [3,4] on the host.  Returns the uncropped
+    (r0, r1 [rows, cols] or [rows, cols, nchan] of the images' dtype, ri0, ri1 int32 [rows, cols]).
+    Asynchronous on the current stream."""
+    from spectavi_amd import mvg
+    if not isinstance(im0, torch.Tensor) or im0.dtype not in _RECTIFY_DTYPE:
+        raise TypeError("im0 must be a float64 or uint8 tensor")
+    _need(im0, im0.dtype, "im0")
+    _need(im1, im0.dtype, "im1")
+    if im0.shape != im1.shape:
+        raise TypeError("Input images must have same size.")
+    hgt, wid, nchan = mvg.image_dims(tuple(im0.shape))
+    F = mvg.rectification_fundamental(P0, P1).reshape(-1)
+    rows, cols, _ = mvg.rectification_shape(wid, hgt, nchan, sampling_factor)
+    vshape = (rows, cols) if nchan == 1 else (rows, cols, nchan)
+    r0 = torch.empty(vshape, dtype=im0.dtype, device=im0.device)
+    r1 = torch.empty(vshape, dtype=im0.dtype, device=im0.device)
+    ri0 = torch.empty((rows, cols), dtype=torch.int32, device=im0.device)
+    ri1 = torch.empty((rows, cols), dtype=torch.int32, device=im0.device)
+    with _on_device_of(im0, im1) as stream:
+        check(clib.spv_rectify_device(F, im0.data_ptr(), im1.data_ptr(), _RECTIFY_DTYPE[im0.dtype], wid, hgt, nchan,
+                                      float(sampling_factor), r0.data_ptr(), r1.data_ptr(), ri0.data_ptr(),
+                                      ri1.data_ptr(), stream))
+    return r0, r1, ri0, ri1

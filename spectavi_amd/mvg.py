@@ -3,8 +3,8 @@
 ====================
 Multi-view-geometry front-end: the batched DLT triangulator of the reference's
 ``spectavi.mvg`` (reference spectavi/mvg.py:259-306) and its callers, the seven-point
-algorithm and the RANSAC fitter (reference spectavi/mvg.py:112-248), bound to the
-gfx950 build of ``libspectavi.so``.
+algorithm and the RANSAC fitter (reference spectavi/mvg.py:112-248), and the image-pair
+rectification (reference spectavi/mvg.py:47-106), bound to the gfx950 build of ``libspectavi.so``.
 """
 import ctypes as ct
 
@@ -358,3 +358,87 @@ def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.
             'camera': P.reshape(3, 4) if found else None, 'inlier_percent': float(pct.value),
             'inlier_idx': idx[:n.value].copy(), 'best_try': bt.value, 'best_root': br.value,
             'tries_run': ran.value}
+
+
+# ==================================================================================
+# image_pair_rectification (reference spectavi/mvg.py:47-106)
+# ==================================================================================
+_image_pair_rectification = clib.image_pair_rectification
+_image_pair_rectification.restype = None
+_image_pair_rectification.argtypes = [_f64, _f64, _f64, _f64, ct.c_int, ct.c_int, ct.c_int, ct.c_double,
+                                      ct.POINTER(NdArray), ct.POINTER(NdArray), ct.POINTER(NdArray),
+                                      ct.POINTER(NdArray)]
+_spv_rectify_fundamental = clib.spv_rectify_fundamental
+_spv_rectify_fundamental.restype = ct.c_int
+_spv_rectify_fundamental.argtypes = [_f64, _f64, _f64]
+_spv_rectify_shape = clib.spv_rectify_shape
+_spv_rectify_shape.restype = ct.c_int
+_spv_rectify_shape.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_double, _i32]
+
+
+def _cameras(P0, P1):
+    P0 = np.ascontiguousarray(P0, dtype=np.float64)
+    P1 = np.ascontiguousarray(P1, dtype=np.float64)
+    if not (P0.shape == (3, 4) and P1.shape == (3, 4)):
+        raise TypeError('P0,P1 must be camera matrices.')
+    return P0, P1
+
+
+def rectification_fundamental(P0, P1):
+    """The fundamental matrix float64 [3,3] that `image_pair_rectification` resamples along:
+    [P1 C]x P1 P0^T (P0 P0^T)^-1 with C the unit null vector of P0.  All NaN when P0 P0^T is
+    singular, zero when the two camera centres coincide (every sample is then invalid)."""
+    P0, P1 = _cameras(P0, P1)
+    F = np.zeros(9)
+    check(_spv_rectify_fundamental(P0, P1, F))
+    return F.reshape(3, 3)
+
+
+def rectification_shape(wid, hgt, nchan, sampling_factor):
+    """(output_rows, output_cols, rnx) of a rectification, as include/spectavi_amd.h states them."""
+    out = np.zeros(3, np.int32)
+    check(_spv_rectify_shape(int(wid), int(hgt), int(nchan), float(sampling_factor), out))
+    return tuple(int(v) for v in out)
+
+
+def image_dims(shape):
+    """(hgt, wid, nchan) of an image shape [hgt, wid] or [hgt, wid, nchan]."""
+    if len(shape) == 2:
+        return shape[0], shape[1], 1
+    if len(shape) == 3:
+        return shape
+    raise TypeError('Images must be [hgt, wid] or [hgt, wid, nchan].')
+
+
+def image_pair_rectification(P0, P1, im0, im1, sampling_factor=1.2, crop_invalid=True):
+    """
+    Rectify an image pair given their two camera matrices (reference spectavi/mvg.py:47-106; the
+    contract is stated with image_pair_rectification in include/spectavi_amd.h).
+
+    P0, P1 : float64 [3,4] camera matrices.  im0, im1 : images of the same shape, [hgt, wid] or
+    [hgt, wid, nchan] (taken as float64).  Every output row resamples im0 along an epipolar line
+    and im1 along its corresponding line, `sampling_factor` samples per input column.
+    Returns (r0, r1, ri0, ri1): the rectified images float64 [rows, cols] (or [rows, cols, nchan])
+    and the flat source pixel index (y * wid + x) of every sample, int32 [rows, cols], -1 (value 0)
+    where a sample falls outside its image.  With `crop_invalid` all four are cropped to the
+    bounding box of the samples valid in either image; ValueError if there are none.
+    """
+    if np.any(np.shape(im0) != np.shape(im1)):
+        raise TypeError("Input images must have same size.")
+    P0, P1 = _cameras(P0, P1)
+    im0 = np.ascontiguousarray(im0, dtype=np.float64)
+    im1 = np.ascontiguousarray(im1, dtype=np.float64)
+    hgt, wid, nchan = image_dims(im0.shape)
+    r0, r1 = NdArray(), NdArray()
+    ri0, ri1 = NdArray(dtype='int32'), NdArray(dtype='int32')
+    _image_pair_rectification(P0, P1, im0, im1, wid, hgt, nchan, float(sampling_factor),
+                              ct.byref(r0), ct.byref(r1), ct.byref(ri0), ct.byref(ri1))
+    check()
+    r0, r1, ri0, ri1 = r0.asarray(), r1.asarray(), ri0.asarray(), ri1.asarray()
+    if crop_invalid:
+        y, x = np.where((ri0 != -1) | (ri1 != -1))
+        if y.size == 0:
+            raise ValueError("No valid rectified sample: nothing to crop to.")
+        ys, xs = slice(y.min(), y.max() + 1), slice(x.min(), x.max() + 1)
+        r0, r1, ri0, ri1 = r0[ys, xs, ...], r1[ys, xs, ...], ri0[ys, xs], ri1[ys, xs]
+    return r0, r1, ri0, ri1

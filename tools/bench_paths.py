@@ -372,6 +372,39 @@ def bruteforce_rows(steps, warmup):
                       "dtype": "f32", "data": "synthetic"}), flush=True)
 
 
+def rectify_rows(steps, warmup):
+    """image_pair_rectification with resident images (device.image_pair_rectification): 1920 x 1080,
+    sf = 1.2, gray and 3-channel, float64 and uint8.  Bytes moved = the four outputs written once plus
+    the valid samples' pixels read; the fraction is of spv_microbench_memory's streaming-copy rate."""
+    import ctypes as ct
+    from spectavi_amd._lib import clib, check
+    from tests.test_rectify_gpu import image, pair
+    clib.spv_microbench_memory.restype = ct.c_int
+    clib.spv_microbench_memory.argtypes = [ct.c_int, ct.c_size_t, ct.POINTER(ct.c_double)]
+    stream = ct.c_double(0)
+    check(clib.spv_microbench_memory(0, 1 << 30, ct.byref(stream)))
+    rng = np.random.default_rng(1080)
+    hgt, wid, sf = 1080, 1920, 1.2
+    P0, P1 = pair(rng, hgt, wid)
+    for nchan in (1, 3):
+        for dt in (np.float64, np.uint8):
+            im0, im1 = (torch.from_numpy(image(rng, hgt, wid, nchan, dt, specials=False)).cuda() for _ in range(2))
+            out, dt_call = timed(lambda: spv.image_pair_rectification(P0, P1, im0, im1, sf), steps, warmup)
+            n, ms = spv.profile_read("rectify")
+            ks = ms / max(n, 1) / 1e3
+            rows, cols = out[2].shape
+            item = np.dtype(dt).itemsize
+            nvalid = int((out[2] >= 0).sum() + (out[3] >= 0).sum())
+            moved = 2 * rows * cols * (nchan * item + 4) + nvalid * nchan * item
+            print(json.dumps({"metric": "image_pair_rectification kernel, bytes moved / s (%s, nchan=%d)" % (
+                np.dtype(dt).name, nchan), "value": moved / ks, "unit": "B/s", "kernel_ms": ks * 1e3,
+                "ms_per_call": dt_call * 1e3, "bytes_moved": moved, "output_shape": [rows, cols, nchan],
+                "valid_fraction": nvalid / (2.0 * rows * cols), "stream_copy_B_per_s": stream.value,
+                "frac_of_stream": moved / ks / stream.value,
+                "config": {"workload": "%d x %d, sf=%g, stereo pair, images resident" % (wid, hgt, sf)},
+                "dtype": np.dtype(dt).name, "data": "synthetic"}), flush=True)
+
+
 def ransac_fit():
     """The RANSAC loop itself (seven-point solve + candidate processing + best-model rule) through the
     host-pointer entry: all tries evaluated (requirement out of reach) for the rate, then the time to
@@ -413,7 +446,7 @@ if __name__ == "__main__":
     ap.add_argument("--npt", type=int, default=10_000_000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit,bf (default all)")
+    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit,bf,rectify (default all)")
     a = ap.parse_args()
     want = set(filter(None, a.only.split(",")))
     if not want or "cascade" in want:
@@ -431,3 +464,5 @@ if __name__ == "__main__":
         ransac_fit()
     if not want or "bf" in want:
         bruteforce_rows(a.steps, a.warmup)
+    if not want or "rectify" in want:
+        rectify_rows(a.steps, a.warmup)
