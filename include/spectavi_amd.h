@@ -51,6 +51,7 @@ extern "C" {
 #define SPV_ERR_HIP 2     /* HIP runtime / no device / launch failure */
 #define SPV_ERR_NOMEM 3   /* host or device allocation failed */
 #define SPV_ERR_INTERNAL 4 /* a C++ exception was caught at the boundary (never propagated) */
+#define SPV_ERR_OVERFLOW 5 /* a caller-sized output was too small (the true count is still reported) */
 
 /* Status of the last call made by this thread through any entry point below
  * (the void reference-compatible symbols report errors only this way). */
@@ -260,6 +261,54 @@ void image_pair_rectification(const double *P0, const double *P1, const double *
                               int hgt, int nchan, double sampling_factor, NdArray *rectified0, NdArray *rectified1,
                               NdArray *rectified_idx0, NdArray *rectified_idx1);
 
+/* SIFT keypoints and descriptors of a grayscale image.  Replaces reference src/Spectavi.cpp:130-215
+ * (SiftFilter::filter, src/Sift.h:49-129): vlfeat vl_sift_* with every setting at its default,
+ * O = max(floor(log2(min(w, h))) - omin - 3, 1), S = 3, omin = -1, peak_thresh = 0,
+ * edge_thresh = 10, magnif = 3, norm_thresh = 0.
+ *   im: float32[hgt, wid]; out: callee-allocated float32[nkp, 132].  Row: x, y, sigma, angle in
+ *   input pixels, then 128 values (uint8) min(512 d, 255).  The clamp is vlfeat's command-line
+ *   tool's; the reference's unclamped (vl_uint8) cast is undefined above 255.
+ *   Row order is vlfeat's: octave by octave; within an octave the DoG scan order (s, then y, then
+ *   x) of the candidates that survive refinement; per keypoint up to four orientations in
+ *   histogram-bin order.
+ * Contract (IEEE float / double as vlfeat computes them, no contraction; k = 2^(1/3),
+ * sigma0 = 1.6 k, dsigma0 = sigma0 sqrt(1 - 1/k^2); f() rounds to float):
+ *   Scale space.  Octave -1: upsample along x then y (out[2i] = a[i], out[2i+1] = (a[i]+a[i+1])*0.5f,
+ *   the last two samples a[n-1]), then smooth by sqrt(sa^2 - sb^2), sa = sigma0 k^-1, sb = 1.
+ *   Level s = 0..4 is level s-1 smoothed by dsigma0 k^s.  Octave o >= 0: level -1 is [::2, ::2]
+ *   of level 2 of octave o-1, cropped to (hgt >> o, wid >> o).  Smoothing by sigma: W =
+ *   max(ceil(4 sigma), 1), tap j = f(exp(-0.5 (double) f(d d))), d = f(f(j - W) / f(sigma)),
+ *   divided by their float sum; vertical pass then horizontal pass, each acc += in[clamp(p)] * tap
+ *   in float over p ascending.  Taps are computed on the host with the C library's exp.
+ *   Detection.  D[s] = L[s+1] - L[s]; a candidate at s in {0,1,2}, 1 <= x <= w-2, 1 <= y <= h-2
+ *   is v >= 0 and strictly above its 26 neighbours, or v <= 0 and strictly below.  Refinement:
+ *   vlfeat's five Newton steps in double (Gauss elimination with partial pivoting, pivot below
+ *   (double) 1e-10f gives b = 0), moves of one pixel where |b| > 0.6; kept if |val| > 0,
+ *   0 <= score < 12.1, every |b| < 1.5, the refined x, y inside the octave and -1 <= s + b2 <= 4.
+ *   Stored x = f(xn 2^o), y = f(yn 2^o), sigma = f(sigma0 2^(sn/3) 2^o); these floats feed the
+ *   orientation and the descriptor.
+ *   Gradients, orientation histogram (36 bins, bilinear, in double, six [1 1 1]/3 passes, peaks
+ *   above 0.8 max, at most four) and descriptor (4x4x8 bins, index (by+2)*32 + (bx+2)*8 + bt,
+ *   window offsets max(-W, 1-xi) .. min(W, w-xi-2)) follow vlfeat's fast_sqrt, fast_atan2,
+ *   mod_2pi and 257-entry fast_expn table (the C library's exp) bit for bit; every bin is a float
+ *   (orientation: double) sum over the window in raster order; the norm is a float sum of squares
+ *   in index order, divided by fast_sqrt(norm) + FLT_EPSILON, clamped at 0.2f, normalised again.
+ *   sin and cos of the angle and pow in sigma are the device's; a last-bit difference from the
+ *   C library's can move a value by one float ulp.
+ * Every row's descriptor follows the window rule above, for keypoints on the octave's border too
+ * (where the reference may leave its descriptor buffer unwritten).
+ * Rejected with SPV_ERR_INVALID: wid or hgt < 1 or > 8192.  A constant image gives 0 rows.  One
+ * device: the first one selected. */
+void sift_filter(const float *im, int wid, int hgt, NdArray *out);
+
+/* Batch form (reference src/Spectavi.cpp:160-215): images and callee-allocated outputs are
+ * registered, then processed one after another on the device.  nthread is accepted and ignored.
+ * The registered image buffers must stay alive until sift_filter_batch_process returns. */
+void *sift_filter_batch_create(void);
+void sift_filter_batch_register_image(void *sfb, const float *im, int wid, int hgt, NdArray *out);
+void sift_filter_batch_process(void *sfb, int nthread);
+void sift_filter_batch_destroy(void *sfb);
+
 /* ------------------------------------------------------------------------ */
 /* 2. Host-pointer variants: caller-allocated outputs, int status            */
 /* ------------------------------------------------------------------------ */
@@ -450,6 +499,28 @@ int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrow
 #define SPV_RECTIFY_U8 1
 int spv_rectify_device(const double *F, const void *d_im0, const void *d_im1, int dtype, int wid, int hgt, int nchan,
                        double sf, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, void *stream);
+
+/* sift_filter with a status.  out: float32 NdArray, allocated by the callee. */
+int spv_sift_filter(const float *im, int wid, int hgt, NdArray *out);
+/* sift_filter into a caller-allocated float32[capacity, 132] table.  *count receives the true
+ * number of rows; when it exceeds capacity the first capacity rows are written and the call
+ * returns SPV_ERR_OVERFLOW. */
+int spv_sift_table(const float *im, int wid, int hgt, float *table, int capacity, int32_t *count);
+
+/* Rows of the first table that sift_filter, spv_sift_filter and the batch form allocate before they
+ * know the count (0: the default, max(1024, min(wid*hgt/16, 2^20))).  A longer result runs the
+ * pipeline a second time into an exact table; the results are the same either way. */
+int spv_sift_set_first_capacity(int rows);
+
+/* Scratch bytes needed by spv_sift_device (0 for a size sift_filter rejects). */
+size_t spv_sift_workspace_bytes(int wid, int hgt);
+/* sift_filter with everything resident: d_im float32[hgt, wid], d_table float32[capacity, 132],
+ * d_count int32[1].  Rows [0, min(*d_count, capacity)) are written and *d_count receives the true
+ * row count (a count above capacity means overflow).  Asynchronous on `stream`: keypoint counts
+ * stay on the device, the host never waits.  Kernel names for spv_profile_read: "sift_pyramid",
+ * "sift_detect", "sift_describe". */
+int spv_sift_device(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_bytes, float *d_table, int capacity,
+                    int32_t *d_count, void *stream);
 
 /* Scratch bytes needed by spv_cascade_device. */
 size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g);

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <map>
 #include <random>
+#include <string>
 
 namespace spv {
 
@@ -287,6 +288,62 @@ int host_rectify(const double *P0, const double *P1, const double *im0, const do
   SPV_TRY(download(dev, r0, dr0.p, vb, st));
   return download(dev, r1, dr1.p, vb, st);
 }
+
+int alloc_out(NdArray *arr, size_t rows, size_t cols, int itemsize, size_t depth);
+
+// First table size of the host forms that size the table to the result (0: the default guess).
+std::atomic<int> g_sift_first_rows{0};
+
+// SIFT through host pointers, on the first selected device.  With `out` the table is sized to the
+// true count: when the first guess is short, the pipeline runs again into a second, exact buffer (the
+// first one goes back to the pool when the call ends).  Otherwise `table` holds `capacity` rows and a
+// longer result is SPV_ERR_OVERFLOW with the true count in *count.
+int host_sift(const float *im, int wid, int hgt, NdArray *out, float *table, int capacity, int32_t *count) {
+  SPV_TRY(sift_check(wid, hgt));
+  if (!im || (!out && (!count || (capacity > 0 && !table)))) return set_error(SPV_ERR_INVALID, "null pointer");
+  if (capacity < 0) return set_error(SPV_ERR_INVALID, "negative capacity");
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t wsb = sift_workspace_bytes(wid, hgt);
+  const int first = g_sift_first_rows.load();
+  int cap = !out ? capacity
+                 : first > 0 ? first : std::max(1024, (int)std::min<long long>((long long)wid * hgt / 16, 1 << 20));
+  DevBuf dim, ws, dt, dt_exact, dc;
+  SPV_TRY(dim.upload(im, (size_t)wid * hgt * sizeof(float), st));
+  SPV_TRY(alloc_all({{&ws, wsb}, {&dc, sizeof(int32_t)}, {&dt, (size_t)std::max(cap, 1) * 132 * sizeof(float)}}));
+  DevBuf *tab = &dt;
+  int32_t n = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    SPV_TRY(sift_run(dim.as<float>(), wid, hgt, ws.p, wsb, tab->as<float>(), cap, dc.as<int>(), st));
+    SPV_TRY(dc.copy_out(&n, sizeof(n), st));
+    SPV_HIP_CHECK(hipStreamSynchronize(st));
+    if (!out || n <= cap) break;
+    cap = n;
+    SPV_TRY(dt_exact.alloc((size_t)cap * 132 * sizeof(float)));
+    tab = &dt_exact;
+  }
+  const int rows = std::min(n, cap);
+  if (out) {
+    SPV_TRY(alloc_out(out, (size_t)n, 132, (int)sizeof(float), 0));
+    table = static_cast<float *>(out->m_data);
+  } else {
+    *count = n;
+  }
+  SPV_TRY(tab->copy_out(table, (size_t)rows * 132 * sizeof(float), st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  if (!out && n > capacity)
+    return set_error(SPV_ERR_OVERFLOW, "sift: %d rows do not fit a table of %d", (int)n, capacity);
+  return SPV_OK;
+}
+
+struct SiftBatch {
+  struct Item {
+    const float *im;
+    int wid, hgt;
+    NdArray *out;
+  };
+  std::vector<Item> items;
+};
 
 int host_cascade_one(int dev, const float *x, const float *y, int xrows, int yrows, int dim, int m,
                      int n, int g, const float *dict, uint64_t *idx, float *dist, int32_t *ncand) {
@@ -877,6 +934,48 @@ void image_pair_rectification(const double *P0, const double *P1, const double *
   });
 }
 
+void sift_filter(const float *im, int wid, int hgt, NdArray *out) {
+  (void)host_api([&] {
+    if (!out) return set_error(SPV_ERR_INVALID, "null NdArray");
+    return host_sift(im, wid, hgt, out, nullptr, 0, nullptr);
+  });
+}
+
+void *sift_filter_batch_create(void) {
+  clear_error();
+  return new (std::nothrow) SiftBatch();
+}
+
+void sift_filter_batch_register_image(void *sfb, const float *im, int wid, int hgt, NdArray *out) {
+  (void)api([&] {
+    if (!sfb) return set_error(SPV_ERR_INVALID, "null batch");
+    static_cast<SiftBatch *>(sfb)->items.push_back({im, wid, hgt, out});
+    return SPV_OK;
+  });
+}
+
+// nthread is accepted and ignored: the images run one after another on the device.  Every image is
+// processed; the status is the first failure's.
+void sift_filter_batch_process(void *sfb, int nthread) {
+  (void)nthread;
+  (void)host_api([&] {
+    if (!sfb) return set_error(SPV_ERR_INVALID, "null batch");
+    int first = SPV_OK;
+    std::string msg;
+    for (const SiftBatch::Item &it : static_cast<SiftBatch *>(sfb)->items) {
+      const int s = it.out ? host_sift(it.im, it.wid, it.hgt, it.out, nullptr, 0, nullptr)
+                           : set_error(SPV_ERR_INVALID, "null NdArray");
+      if (s != SPV_OK && first == SPV_OK) {
+        first = s;
+        msg = spv_last_error();
+      }
+    }
+    return first == SPV_OK ? SPV_OK : set_error(first, "%s", msg.c_str());
+  });
+}
+
+void sift_filter_batch_destroy(void *sfb) { delete static_cast<SiftBatch *>(sfb); }
+
 // ---- host-pointer status variants ---------------------------------------------------
 int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
                           uint64_t *idx, int32_t *dist) {
@@ -1117,6 +1216,25 @@ int spv_dlt_reprojection_error(const double *P0, const double *P1, int npt, cons
   return host_api([&] { return host_dlt(P0, P1, npt, x, xp, dst, true); });
 }
 
+int spv_sift_filter(const float *im, int wid, int hgt, NdArray *out) {
+  return host_api([&] {
+    if (!out) return set_error(SPV_ERR_INVALID, "null NdArray");
+    return host_sift(im, wid, hgt, out, nullptr, 0, nullptr);
+  });
+}
+
+int spv_sift_set_first_capacity(int rows) {
+  return api([&] {
+    if (rows < 0) return set_error(SPV_ERR_INVALID, "negative row count");
+    g_sift_first_rows.store(rows);
+    return SPV_OK;
+  });
+}
+
+int spv_sift_table(const float *im, int wid, int hgt, float *table, int capacity, int32_t *count) {
+  return host_api([&] { return host_sift(im, wid, hgt, nullptr, table, capacity, count); });
+}
+
 // ---- device-pointer variants --------------------------------------------------------
 size_t spv_l1k2_workspace_bytes(int xrows, int yrows, int dim) {
   if (!l1k2_shape_ok(xrows, yrows, dim)) return 0;
@@ -1167,6 +1285,21 @@ int spv_rectify_device(const double *F, const void *d_im0, const void *d_im1, in
   return api([&] {
     return rectify_run(F, d_im0, d_im1, dtype, wid, hgt, nchan, sf, d_r0, d_r1, d_ri0, d_ri1,
                        static_cast<hipStream_t>(stream));
+  });
+}
+
+size_t spv_sift_workspace_bytes(int wid, int hgt) {
+  if (sift_check(wid, hgt) != SPV_OK) {
+    clear_error();
+    return 0;
+  }
+  return sift_workspace_bytes(wid, hgt);
+}
+
+int spv_sift_device(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_bytes, float *d_table, int capacity,
+                    int32_t *d_count, void *stream) {
+  return api([&] {
+    return sift_run(d_im, wid, hgt, d_ws, ws_bytes, d_table, capacity, d_count, static_cast<hipStream_t>(stream));
   });
 }
 

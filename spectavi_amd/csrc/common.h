@@ -116,6 +116,16 @@ void rectify_fundamental(const double *P0, const double *P1, double *F);  // hos
 int rectify_run(const double *F, const void *d_im0, const void *d_im1, int dtype, int wid, int hgt, int nchan,
                 double sf, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, hipStream_t stream);
 
+// ---- vlfeat-exact SIFT (sift.hip) ----------------------------------------------------
+constexpr int kSiftMaxSide = 8192;  // candidates pack x, y of octave -1 in 15 bits each; counts stay below 2^31
+int sift_check(int wid, int hgt);   // SPV_ERR_INVALID (message set) outside the header's limits
+int sift_noctaves(int wid, int hgt);
+size_t sift_workspace_bytes(int wid, int hgt);
+// Writes rows [0, min(count, capacity)) of d_table float32[capacity,132] and the true row count to
+// *d_count; asynchronous on `stream`.
+int sift_run(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_bytes, float *d_table, int capacity,
+             int *d_count, hipStream_t stream);
+
 // ---- ratio test + compaction (match.hip) ---------------------------------------------
 size_t ratio_workspace_bytes(int yrows);
 int ratio_run(const uint64_t *d_idx, const void *d_dist, int dist_is_float, int yrows,

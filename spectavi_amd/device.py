@@ -569,3 +569,48 @@ def image_pair_rectification(P0, P1, im0, im1, sampling_factor=1.2):
                                       float(sampling_factor), r0.data_ptr(), r1.data_ptr(), ri0.data_ptr(),
                                       ri1.data_ptr(), stream))
     return r0, r1, ri0, ri1
+
+
+clib.spv_sift_workspace_bytes.restype = ct.c_size_t
+clib.spv_sift_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
+clib.spv_sift_device.restype = ct.c_int
+clib.spv_sift_device.argtypes = [_vp, ct.c_int, ct.c_int, _vp, ct.c_size_t, _vp, ct.c_int, _vp, _vp]
+
+
+def sift_into(im, table, count, workspace=None):
+    """vlfeat-exact SIFT of im (float32 [H, W] CUDA tensor) into table (float32 [capacity, 132]): rows
+    [0, min(n, capacity)) are written and count (int32 [1]) receives the true row count n.
+    Asynchronous on the current stream; nothing is synchronised."""
+    _need(im, torch.float32, "im")
+    _need(table, torch.float32, "table")
+    _need(count, torch.int32, "count")
+    if im.dim() != 2:
+        raise TypeError("Only 2d images are supported.")
+    if table.dim() != 2 or table.shape[1] != 132 or count.numel() < 1:
+        raise ValueError("table must be [capacity, 132] and count hold one int32")
+    hgt, wid = im.shape
+    nbytes = clib.spv_sift_workspace_bytes(wid, hgt)
+    with _on_device_of(im, table, count) as stream:
+        ws = (workspace or _default_ws).get(nbytes, im.device)
+        check(clib.spv_sift_device(im.data_ptr(), wid, hgt, ws.data_ptr(), ws.numel(), table.data_ptr(),
+                                   table.shape[0], count.data_ptr(), stream))
+
+
+def sift(im_tensor, workspace=None):
+    """vlfeat-exact SIFT on device: im_tensor float32 [H, W] (CUDA).  Returns the float32 [nkp, 132]
+    table (x, y, sigma, angle, 128 descriptor values), which split_sift_table and normalize accept.
+    Reads the row count back once (a second pass when the first table guess is short)."""
+    if not isinstance(im_tensor, torch.Tensor) or im_tensor.dim() != 2:
+        raise TypeError("Only 2d images are supported.")
+    im = im_tensor.to(torch.float32).contiguous()
+    hgt, wid = im.shape
+    count = torch.zeros(1, dtype=torch.int32, device=im.device)
+    cap = max(1024, min(wid * hgt // 16, 1 << 20))
+    for _ in range(2):
+        table = torch.empty((cap, 132), dtype=torch.float32, device=im.device)
+        sift_into(im, table, count, workspace)
+        n = int(count.item())
+        if n <= cap:
+            return table[:n]
+        cap = n
+    raise AssertionError("unreachable: the second pass is sized to the true count")

@@ -356,3 +356,137 @@ def normalize_to_ubyte_and_multiple_16_dim_gpu(x, want_ubyte=False):
     u8 = np.empty((rows, dim16), np.uint8) if want_ubyte else None
     check(_spv_normalize(x, rows, dim, out.ctypes.data, u8.ctypes.data if want_ubyte else None))
     return (out, u8) if want_ubyte else out
+
+
+# ==================================================================================
+# SIFT                        (reference spectavi/feature.py:17-148)
+# ==================================================================================
+_sift_filter = clib.sift_filter
+_sift_filter.restype = None
+_sift_filter.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
+                         ct.c_int,
+                         ct.c_int,
+                         ct.POINTER(NdArray), ]
+
+_sift_filter_batch_create = clib.sift_filter_batch_create
+_sift_filter_batch_create.restype = ct.c_void_p
+_sift_filter_batch_create.argtypes = []
+
+_sift_filter_batch_destroy = clib.sift_filter_batch_destroy
+_sift_filter_batch_destroy.restype = None
+_sift_filter_batch_destroy.argtypes = [ct.c_void_p]
+
+_sift_filter_batch_register_image = clib.sift_filter_batch_register_image
+_sift_filter_batch_register_image.restype = None
+_sift_filter_batch_register_image.argtypes = [ct.c_void_p,
+                                              ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
+                                              ct.c_int,
+                                              ct.c_int,
+                                              ct.POINTER(NdArray), ]
+
+_sift_filter_batch_process = clib.sift_filter_batch_process
+_sift_filter_batch_process.restype = None
+_sift_filter_batch_process.argtypes = [ct.c_void_p, ct.c_int]
+
+_spv_sift_table = clib.spv_sift_table
+_spv_sift_table.restype = ct.c_int
+_spv_sift_table.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
+                            ct.c_int,
+                            ct.c_int,
+                            ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
+                            ct.c_int,
+                            ct.POINTER(ct.c_int32), ]
+
+
+def _gray(im):
+    if len(np.shape(im)) != 2:
+        raise TypeError("Only 2d images are supported.")
+    return np.ascontiguousarray(im, dtype=np.float32)
+
+
+def sift_filter(im):
+    """
+    SIFT keypoints and descriptors of a grayscale image `im` (2-d): vlfeat with default settings
+    (include/spectavi_amd.h, sift_filter).
+
+    Returns
+    -------
+    kps : float32 ndarray [nkp, 132]
+        x, y, sigma, angle, then 128 descriptor values (uint8 stored as float).
+    """
+    im = _gray(im)
+    hgt, wid = im.shape
+    ret = NdArray(dtype='float32')
+    _sift_filter(im, wid, hgt, ret)
+    check()
+    return ret.asarray()
+
+
+def sift_table(im, capacity):
+    """sift_filter into a table of `capacity` rows: (table float32 [capacity, 132], true row count).
+    A result longer than `capacity` raises SpectaviError (SPV_ERR_OVERFLOW) naming the true count."""
+    im = _gray(im)
+    hgt, wid = im.shape
+    table = np.zeros((max(int(capacity), 0), 132), np.float32)
+    count = ct.c_int32(0)
+    check(_spv_sift_table(im, wid, hgt, table, int(capacity), ct.byref(count)))
+    return table, int(count.value)
+
+
+def sift_filter_batch(ims, nthread=8):
+    """
+    sift_filter of every image of the list `ims`, processed on the GPU one after another.
+    `nthread` is accepted for the reference's signature and ignored.
+
+    Returns
+    -------
+    kps : list of float32 ndarrays [nkp, 132], one per image.
+    """
+    ims = [_gray(im) for im in ims]
+    nims = len(ims)
+    nthread = int(np.min([nims, nthread])) if nims else 0
+    sfb = _sift_filter_batch_create()
+    if not sfb:
+        raise MemoryError("sift_filter_batch_create failed")
+    rets = [NdArray(dtype='float32') for _ in range(nims)]
+    try:
+        for im, ret in zip(ims, rets):
+            hgt, wid = im.shape
+            _sift_filter_batch_register_image(sfb, im, wid, hgt, ret)
+            check()
+        _sift_filter_batch_process(sfb, nthread)
+        check()
+    finally:
+        _sift_filter_batch_destroy(sfb)
+    return [ret.asarray() for ret in rets]
+
+
+def sift_filter_striped(im, nthread=8, buffer_size=20):
+    """
+    SIFT of one image cut into `nthread` horizontal stripes with `buffer_size` rows of overlap, the
+    reference's stitching (reference spectavi/feature.py:96-148): each stripe's keypoints are shifted
+    back by the stripe's first buffered row and kept when iy_start < y < iy_end.  Boundary effects
+    make the result close to, but usually not equal to, sift_filter's.
+    """
+    if len(np.shape(im)) != 2:
+        raise TypeError("Only 2d images are supported.")
+    hgt, _ = im.shape
+    split_hgt = int(np.ceil(hgt / float(nthread)))
+    bboxes = list()
+    ims = list()
+    for iy in range(0, hgt, split_hgt):
+        iy_start = iy
+        iy_end = min([iy + split_hgt, hgt])
+        bf_start = max([iy_start - buffer_size, 0])
+        bf_end = min([iy_end + buffer_size + 1, hgt])
+        bboxes.append([iy_start, iy_end, bf_start])
+        ims.append(im[bf_start:bf_end])
+    sifts = sift_filter_batch(ims, nthread=nthread)
+    ret_sift = list()
+    for bb, sift in zip(bboxes, sifts):
+        iy_start, iy_end, bf_start = bb
+        sy = sift[:, 1]
+        sy += bf_start
+        idx = (sy > iy_start) & (sy < iy_end)
+        ret_sift.append(sift[idx])
+    return np.vstack(ret_sift)

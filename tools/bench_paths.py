@@ -405,6 +405,50 @@ def rectify_rows(steps, warmup):
                 "dtype": np.dtype(dt).name, "data": "synthetic"}), flush=True)
 
 
+def sift_rows(steps, warmup):
+    """SIFT with the image resident (device.sift_into, table preallocated): 640 x 480, 1920 x 1080 and
+    3840 x 2160 smoothed-noise images.  Device time per image split by the library's hipEvent brackets:
+    sift_pyramid (upsample / downsample + 12 smoothing passes per octave), sift_detect (extrema,
+    scans, refinement, compaction) and sift_describe (gradients, orientation, descriptors).  The
+    pyramid's bound is its minimum traffic (each pass reads and writes every pixel of its octave once,
+    4 bytes each way) at spv_microbench_memory's streaming-copy rate; the oracle's CPU time is for the
+    numpy restatement at 640 x 480."""
+    import ctypes as ct
+    from spectavi_amd._lib import clib, check
+    from tests import sift_oracle as so
+    from tests.sift_cases import smooth_random
+    clib.spv_microbench_memory.restype = ct.c_int
+    clib.spv_microbench_memory.argtypes = [ct.c_int, ct.c_size_t, ct.POINTER(ct.c_double)]
+    stream = ct.c_double(0)
+    check(clib.spv_microbench_memory(0, 1 << 30, ct.byref(stream)))
+    t0 = time.perf_counter()
+    so.sift(smooth_random(11, 480, 640))
+    oracle_s = time.perf_counter() - t0
+    for wid, hgt in ((640, 480), (1920, 1080), (3840, 2160)):
+        im = torch.from_numpy(smooth_random(11, hgt, wid)).cuda()
+        table = torch.empty((1 << 20, 132), dtype=torch.float32, device="cuda")
+        count = torch.zeros(1, dtype=torch.int32, device="cuda")
+        _, dt_call = timed(lambda: spv.sift_into(im, table, count), steps, warmup)
+        parts = {}
+        for k in ("sift_pyramid", "sift_detect", "sift_describe"):
+            n, ms = spv.profile_read(k)
+            parts[k] = ms / steps
+        nrow = int(count.item())
+        O = so.noctaves(wid, hgt)
+        area = sum((2 * wid * 2 * hgt) if o < 0 else (wid >> o) * (hgt >> o) for o in range(-1, -1 + O))
+        passes_bytes = 8.0 * (10 * area + 2 * 4 * wid * hgt) + 4 * wid * hgt + 16 * wid * hgt
+        bound_ms = passes_bytes / stream.value * 1e3
+        print(json.dumps({"metric": "sift_filter device time per image (%d x %d)" % (wid, hgt),
+                          "value": sum(parts.values()), "unit": "ms", "pyramid_ms": parts["sift_pyramid"],
+                          "detect_ms": parts["sift_detect"], "describe_ms": parts["sift_describe"],
+                          "ms_per_call": dt_call * 1e3, "rows": nrow, "octaves": O,
+                          "pyramid_min_bytes": passes_bytes, "pyramid_bound_ms": bound_ms,
+                          "pyramid_frac_of_bound": bound_ms / parts["sift_pyramid"],
+                          "stream_copy_B_per_s": stream.value, "oracle_cpu_s_640x480": oracle_s,
+                          "config": {"workload": "%d x %d smoothed noise, image resident" % (wid, hgt)},
+                          "dtype": "f32", "data": "synthetic"}), flush=True)
+
+
 def ransac_fit():
     """The RANSAC loop itself (seven-point solve + candidate processing + best-model rule) through the
     host-pointer entry: all tries evaluated (requirement out of reach) for the rate, then the time to
@@ -446,7 +490,7 @@ if __name__ == "__main__":
     ap.add_argument("--npt", type=int, default=10_000_000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit,bf,rectify (default all)")
+    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit,bf,rectify,sift (default all)")
     a = ap.parse_args()
     want = set(filter(None, a.only.split(",")))
     if not want or "cascade" in want:
@@ -466,3 +510,5 @@ if __name__ == "__main__":
         bruteforce_rows(a.steps, a.warmup)
     if not want or "rectify" in want:
         rectify_rows(a.steps, a.warmup)
+    if not want or "sift" in want:
+        sift_rows(a.steps, a.warmup)
