@@ -91,6 +91,25 @@ int spv_set_devices(const int *devices, int count);
 #define SPV_GATHER_RCCL 1
 #define SPV_GATHER_PEERCOPY 2
 int spv_set_gather_mode(int mode);
+/* L1 2-NN at dim 128: whether spv_l1k2_device and everything built on it rule most pairs out with an
+ * exact integer lower bound on the matrix cores (l1k2_prune.hip) before the exact distances.  AUTO (the
+ * default, also SPECTAVI_L1K2_PRUNE=auto): where the plan's database slices are at least 32768 rows long
+ * (from about 512k x 512k rows on; 1M x 1M and 4M x 500k qualify, 256k x 256k does not); ON (=1): wherever the path
+ * exists, i.e. dim 128 and at least 32 database rows; OFF (=0): never.  Results are bit-identical
+ * either way, and neither spv_l1k2_plan nor spv_l1k2_workspace_bytes depends on it. */
+#define SPV_L1K2_PRUNE_AUTO (-1)
+#define SPV_L1K2_PRUNE_OFF 0
+#define SPV_L1K2_PRUNE_ON 1
+int spv_l1k2_set_prune(int mode);
+/* The mode in force (the setter's last value, else SPECTAVI_L1K2_PRUNE, else AUTO). */
+int spv_l1k2_get_prune(void);
+/* Which path the calling thread's last spv_l1k2_device call took: out = {pairs put to the bound,
+ * pairs that survived it, pairs evaluated by waves that gave the bound up}; all zero if the tile
+ * kernels ran.  Waits for that launch; the workspace it was given must still be allocated. */
+int spv_l1k2_prune_stats(unsigned long long out[3]);
+/* The bound's table (host only, no GPU involved): phi = the four int8 features of every byte value,
+ * and integers p, m with p |a-b| >= m - phi(a).phi(b) for all bytes a, b, m being the largest such. */
+int spv_l1k2_bound_table(int8_t phi[256][4], int *p, int *m);
 /* Host statement of the 16-byte record format (no GPU involved), for callers that run their own
  * collective on raw records.  pack: idx uint64[n,2] ((size_t)-1 = no neighbour), dist32 = int32 or
  * float32 [n,2] -> rec int32[n,4] = (idx0, idx1, d0 bits, d1 bits), -1 = no neighbour.
@@ -434,7 +453,10 @@ int spv_dlt_reprojection_error(const double *P0, const double *P1, int npt, cons
 /*    Buffers must belong to the calling thread's current HIP device.         */
 /* ------------------------------------------------------------------------ */
 
-/* Scratch bytes needed by spv_l1k2_device for this shape. */
+/* Scratch bytes needed by spv_l1k2_device for this shape.  At dim 128 with at least 32 database rows this
+ * includes 512 bytes per database row and per query row for the int8 features of the bound path
+ * (spv_l1k2_set_prune), whether or not the path is switched on: the size depends on the shape alone.
+ * That is about five times the input (1.0 GB more at 1M x 1M). */
 size_t spv_l1k2_workspace_bytes(int xrows, int yrows, int dim);
 /* The launch plan spv_l1k2_device follows for this shape (on one device; the host-pointer entry
  * points shard the queries over the devices first): out = {kernel row width in bytes, queries per

@@ -801,6 +801,33 @@ int spv_set_gather_mode(int mode) {
   return SPV_OK;
 }
 
+int spv_l1k2_set_prune(int mode) {
+  clear_error();
+  if (mode != SPV_L1K2_PRUNE_AUTO && mode != SPV_L1K2_PRUNE_OFF && mode != SPV_L1K2_PRUNE_ON)
+    return set_error(SPV_ERR_INVALID, "prune mode %d", mode);
+  l1k2_set_prune(mode);
+  return SPV_OK;
+}
+
+int spv_l1k2_get_prune(void) { return l1k2_get_prune(); }
+
+int spv_l1k2_prune_stats(unsigned long long out[3]) {
+  clear_error();
+  if (!out) return set_error(SPV_ERR_INVALID, "null output");
+  return guard([&] { return l1k2_prune_last_stats(out); });
+}
+
+int spv_l1k2_bound_table(int8_t phi[256][4], int *p, int *m) {
+  clear_error();
+  if (!phi || !p || !m) return set_error(SPV_ERR_INVALID, "null output");
+  const L1K2Bound &b = l1k2_bound();
+  for (int a = 0; a < 256; ++a)
+    for (int f = 0; f < 4; ++f) phi[a][f] = b.phi[a][f];
+  *p = b.p;
+  *m = b.m;
+  return b.ok ? SPV_OK : set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
+}
+
 void spv_release_cached_memory(void) { release_transfer_caches(); }
 
 void spv_profile_enable(int on) {

@@ -78,11 +78,33 @@ struct L1K2Plan {
   int qblocks;     // query blocks
   size_t pad_x_bytes, pad_y_bytes;  // padded copies (0 when dim == dim_pad)
   size_t part_bytes;                // partial top-2 keys
+  size_t feat_x_bytes, feat_y_bytes, thr_bytes;  // l1k2_prune.hip: int8 features and shared thresholds (dim 128 only)
   size_t total_bytes;
 };
 L1K2Plan l1k2_plan(int xrows, int yrows, int dim);
 int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,
              uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- matrix-core lower bound for the L1 2-NN at dim 128 (l1k2_prune.hip) -------------
+struct L1K2Bound {
+  int8_t phi[256][4];  // features of a byte value
+  int p, m;            // p |a-b| >= m - phi(a).phi(b) for all bytes a, b
+  bool ok;             // the table passed its exhaustive check
+};
+const L1K2Bound &l1k2_bound();                               // host only, built once
+int l1k2_set_prune(int mode);                                // -1 auto, 0 never, 1 wherever possible; returns the mode before
+int l1k2_get_prune();
+void l1k2_prune_forget();                                    // l1k2_run took the tile kernels
+// {pairs bounded, survivors, pairs of the exact fallback} of the calling thread's last l1k2_run (zeros: tile kernels);
+// waits for that launch; its workspace must still be allocated
+int l1k2_prune_last_stats(unsigned long long out[3]);
+bool l1k2_prune_selected(int xrows, int yrows, int dim, int slice_rows);  // does l1k2_run take the bound path now
+void l1k2_prune_bytes(int xrows, int yrows, int dim, int slices, size_t *fx_bytes, size_t *fy_bytes, size_t *thr_bytes);
+// features, thresholds and the bound-and-survivor kernel; writes the partial keys l1k2_merge_kernel reads
+// *work_out: {count, -, (query block of 256, slice) ...} of the workgroups that gave the bound up and whose
+// partial keys l1k2_run has yet to compute with the tile kernel; *groups_out: how many there can be
+int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *d_extra,
+                   uint64_t *part, const uint32_t **work_out, int *groups_out, hipStream_t stream);
 
 // ---- exact p-norm k-NN (bruteforce.hip) ---------------------------------------------
 struct BruteForcePlan {

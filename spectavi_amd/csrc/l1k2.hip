@@ -32,9 +32,11 @@
 // (size_t idx[N,2], int dist[N,2]; sentinels INT_MAX / (size_t)-1 as
 // src/BruteForceNnL1K2.h:100-103).
 //
-// Roofline: sum-of-abs-diff is not a contraction (no MFMA); the bound is the issue
-// rate of v_sad_hi_u8 -- one wave64 instruction per 4 cycles per SIMD, measured -- at
-// 32 lane-ops per 128-D pair.  The kernel runs at 0.90 of that peak.  See DESIGN.md.
+// Roofline: sum-of-abs-diff is not a contraction; the bound of these kernels is the issue rate of
+// v_sad_hi_u8 -- one wave64 instruction per 4 cycles per SIMD, measured -- at 32 lane-ops per 128-D pair.
+// The kernel runs at 0.90 of that peak.  At dim 128 and large shapes l1k2_run instead takes
+// l1k2_prune.hip, which rules most pairs out with an exact int8 matrix-core lower bound and pays the
+// SADs for the survivors only; everything else runs here.  See DESIGN.md 4.1.
 
 #include "common.h"
 
@@ -140,20 +142,36 @@ __device__ __forceinline__ uint64_t widen_key(uint32_t k, uint32_t slice_base) {
 // Tile kernel.  grid = (query blocks, slices); block = 256 threads = 4 waves.
 // Thread t of query block qb owns queries qb*256*Q + q*256 + t, q = 0..Q-1.
 // ---------------------------------------------------------------------------------
-template <int D4, int Q>
+// With a work list (l1k2_prune.hip: {count, -, (query block, slice) ...}) blocks kWorkSub e .. kWorkSub e + 7 compute
+// entry e instead, an eighth of the slice each (the bound path's slices are long and few: whole slices would
+// leave the chip a third empty in the last round), and merge their keys into the entry's partial pair, which
+// the workgroup that listed it has set to "none", by the two-minimum protocol of l1k2_prune.hip.
+constexpr int kWorkSub = 8;
+template <int D4, int Q, int kThreads = spv::kThreads>
 __global__ __launch_bounds__(kThreads, 3) void l1k2_tile_kernel(
     const uint4 *__restrict__ x, const uint4 *__restrict__ y, int M, int N, int slice_rows,
-    int S, uint64_t *__restrict__ part) {
+    int S, uint64_t *part, const uint32_t *__restrict__ work = nullptr) {
   constexpr int V4 = D4 / 4;                                   // 16-byte vectors per row
   constexpr int TILE_V4 = kTileRows * V4;                      // vectors per tile
   constexpr int NL = (TILE_V4 + kThreads - 1) / kThreads;      // staging loads per thread
   __shared__ uint4 tile[2][TILE_V4];
 
   const int t = threadIdx.x;
-  const int qb = blockIdx.x;
-  const int s = blockIdx.y;
-  const int row_begin = s * slice_rows;
-  const int row_end = min(M, row_begin + slice_rows);
+  int qb = blockIdx.x;
+  int s = blockIdx.y;
+  if (work) {
+    const uint32_t e = blockIdx.x / kWorkSub;
+    if (e >= work[0]) return;
+    qb = (int)work[2 + 2 * e];
+    s = (int)work[3 + 2 * e];
+  }
+  int row_begin = s * slice_rows;
+  int row_end = min(M, row_begin + slice_rows);
+  if (work) {
+    const int sub = ((slice_rows + kWorkSub - 1) / kWorkSub + kTileRows - 1) / kTileRows * kTileRows;
+    row_begin += (int)(blockIdx.x % kWorkSub) * sub;
+    row_end = min(row_end, row_begin + sub);
+  }
 
   // ---- this lane's queries -> registers
   uint32_t qreg[Q][D4];
@@ -261,8 +279,21 @@ __global__ __launch_bounds__(kThreads, 3) void l1k2_tile_kernel(
   for (int q = 0; q < Q; ++q) {
     if (qi[q] < N) {
       uint64_t *dst = part + ((size_t)qi[q] * S + s) * 2;
-      dst[0] = widen_key(k1[q], (uint32_t)row_begin);
-      dst[1] = widen_key(k2[q], (uint32_t)row_begin);
+      const uint64_t a1 = widen_key(k1[q], (uint32_t)row_begin), a2 = widen_key(k2[q], (uint32_t)row_begin);
+      if (work) {
+        unsigned long long *d = reinterpret_cast<unsigned long long *>(dst);
+        if (a1 != kKey64None) {
+          const unsigned long long old = atomicMin(&d[0], (unsigned long long)a1);
+          atomicMin(&d[1], old > a1 ? old : (unsigned long long)a1);
+        }
+        if (a2 != kKey64None) {
+          const unsigned long long old = atomicMin(&d[0], (unsigned long long)a2);
+          atomicMin(&d[1], old > a2 ? old : (unsigned long long)a2);
+        }
+      } else {
+        dst[0] = a1;
+        dst[1] = a2;
+      }
     }
   }
 }
@@ -547,7 +578,9 @@ L1K2Plan l1k2_plan(int xrows, int yrows, int dim) {
     p.pad_y_bytes = round_up((size_t)yrows * p.dim_pad, 256);
   }
   p.part_bytes = round_up((size_t)std::max(yrows, 1) * p.slices * 2 * sizeof(uint64_t), 256);
-  p.total_bytes = p.pad_x_bytes + p.pad_y_bytes + p.part_bytes;
+  // scratch of the bound path: a function of the shape alone, whether or not the path is switched on
+  l1k2_prune_bytes(xrows, yrows, dim, p.slices, &p.feat_x_bytes, &p.feat_y_bytes, &p.thr_bytes);
+  p.total_bytes = p.pad_x_bytes + p.pad_y_bytes + p.part_bytes + p.feat_x_bytes + p.feat_y_bytes + p.thr_bytes;
   return p;
 }
 
@@ -592,6 +625,19 @@ int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int d
 
   {
     ProfScope prof("l1k2_tile", stream);
+  l1k2_prune_forget();
+  if (l1k2_prune_selected(xrows, yrows, dim, p.slice_rows)) {
+    // dim 128, large shapes: matrix-core lower bound, exact SADs for the survivors only (l1k2_prune.hip)
+    const uint32_t *work = nullptr;
+    int groups = 0;
+    SPV_TRY(l1k2_prune_run(kx, ky, xrows, yrows, p, ws + p.pad_x_bytes + p.pad_y_bytes + p.part_bytes, part, &work,
+                           &groups, stream));
+    // the (query block, slice) groups on which the bound did not pay: exactly, two queries per lane in blocks of
+    // 128 lanes = the 256 queries of a group, eight blocks per group; blocks beyond the list's length leave at once
+    hipLaunchKernelGGL((l1k2_tile_kernel<32, 2, 128>), dim3((unsigned)groups * kWorkSub), dim3(128), 0, stream,
+                       reinterpret_cast<const uint4 *>(kx), reinterpret_cast<const uint4 *>(ky), xrows, yrows,
+                       p.slice_rows, p.slices, part, work);
+  } else
   switch (p.dim_pad) {
     case 32: launch_tile_q<8>(kx, ky, xrows, yrows, p, part, stream); break;
     case 48: launch_tile_q<12>(kx, ky, xrows, yrows, p, part, stream); break;

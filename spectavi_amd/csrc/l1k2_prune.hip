@@ -1,0 +1,526 @@
+// l1k2_prune.hip -- L1 2-NN at dim 128: most pairs are ruled out by an exact integer lower bound
+// computed on the matrix cores, and only the survivors pay for the 32 v_sad_u8 of the exact distance.
+// Results are bit-identical to l1k2_tile_kernel (l1k2.hip); l1k2_run chooses between the two.
+//
+// The bound.  |a - b| on bytes has a rank-4 minorant: with the harmonics k = 1, 3 of its cosine series,
+//     phi(a) = ( r(127 cos(pi a/255)), r(127 sin(pi a/255)), r(127 cos(3 pi a/255)/3), r(127 sin(3 pi a/255)/3) )
+// as int8 (r = round to nearest), G(a,b) = phi(a).phi(b), an integer slope p and
+//     m = min over all 65536 byte pairs of ( p |a-b| + G(a,b) ),
+// it holds by construction, in integers, that  p |a-b| >= m - G(a,b),  hence for 128-byte rows
+//     p L1(x,y) >= 128 m - sum_d G(x_d, y_d).
+// The sum is an int8 GEMM of depth 512 accumulated exactly in int32 (v_mfma_i32_32x32x32_i8).  If thr is
+// any value >= the query's final second-best distance, a pair with 128 m - sum > p thr (strictly) cannot
+// enter the result.  p and m are derived from the finished integer table on the host (l1k2_bound) and
+// the inequality is asserted over all byte pairs before the path is ever taken.
+//
+// The kernel.  grid = (blocks of 256 queries, database slices); 4 waves, each owning 64 queries whose
+// 512 feature bytes stay in VGPRs as the B operand (2 column blocks x 16 k-steps x 4 dwords).  Database
+// feature tiles (32 rows x 512 B) stream through LDS, double buffered, one barrier per tile, as the byte
+// tiles of l1k2_tile_kernel do.  Per tile and wave: 32 MFMAs, then one compare per accumulator register
+// against the lane's threshold 128 m - p thr (the C layout puts one query on each lane) folded into one bit
+// mask per lane, and the surviving (query, row) pairs are appended to the wave's queue in LDS, one per lane and
+// round.  Whenever 64 are queued, and at the end of the tile, the wave evaluates them exactly, one pair per
+// lane, both rows read from LDS (the workgroup's 256 query rows and the tile's 32 database rows are kept
+// there as they are, beside the features; from global memory the same reads bound the kernel at the
+// vector cache).  A key dist<<32 | row that beats the query's current second best enters its top-2 in LDS
+// with two 64-bit atomic minima: old = min(k1, key); min(k2, max(old, key)).  Every key but the final
+// minimum is displaced exactly once, so k2 ends as the second smallest under any interleaving.
+//
+// Thresholds are shared between workgroups through thr[query] in the workspace (initialised to
+// 0xFFFFFFFF): a workgroup reads it every fourth tile and lowers it with atomicMin when its own second best
+// improves.  Every value ever stored is the second best over a subset of the database, hence >= the
+// final one: WHICH pairs are skipped depends on timing, the result never does.
+//
+// Fallback.  Every wave keeps a running survivor share.  When it exceeds the measured break-even (16 %; 3/4
+// in a workgroup's first tiles; see l1k2_prune_selected) the wave raises a flag, and at the tile's barrier
+// the whole workgroup publishes the thresholds it has, sets its partial keys to "none", puts its (query
+// block, slice) on a work list and leaves.  l1k2_run then launches l1k2_tile_kernel<32, 2, 128> over that
+// list: the parent's exact kernel, 256 queries per block, eight blocks per listed slice merging their keys
+// with the two-minimum protocol.  An in-kernel exact loop (one query per lane, scalar-fed rows) ran at half
+// the tile kernel's rate on ordinary data and was dropped.
+//
+// Register budget: 252 of the 256 VGPRs that two waves per SIMD allow (128 of them the B operand), no
+// scratch; LDS 79880 of the 81920 bytes that two workgroups per CU allow.  Any added live value spills or
+// halves the occupancy: check the ISA after every change.
+#include "common.h"
+
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+namespace spv {
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kQPerWave = 64;                 // two MFMA column blocks of 32
+constexpr int kQPerBlock = kWaves * kQPerWave;
+constexpr int kTileRows = 32;                 // MFMA rows
+constexpr int kFeatV4 = 32;                   // 512 feature bytes per row = 32 x 16 B
+constexpr int kLdsRowV4 = kFeatV4 + 1;        // +16 B: the 32 rows of a k-step fall on distinct banks
+constexpr int kQueue = 128;                   // < 64 queued, then <= 64 appended in one round
+constexpr int kSkipTilesAlone = 3;            // tiles left out of the running share while a workgroup has no thresholds at all
+constexpr int kWarmTilesShared = 8;           // ... at the break-even share, with thresholds inherited from other slices
+constexpr int kWarmTilesAlone = 256;          // ... and without: its own thresholds take thousands of rows to settle
+constexpr int kShareUnit = 1024;              // the break-even survivor share is passed in 1/1024
+constexpr int kBreakEvenShare = 164;          // 16 %, see l1k2_prune_selected and profiles/r07_prune_breakeven.jsonl
+constexpr uint32_t kMaxDist = 128 * 255;
+constexpr int kStatSlots = 16;                // survivor counters, spread to keep the atomics apart
+constexpr int kStatWords = kStatSlots * 4 * 2;
+
+struct FeatTable { uint32_t w[256]; };        // phi(a) packed little-endian, one dword per byte value
+
+__global__ __launch_bounds__(kThreads) void l1k2_feature_kernel(const uint32_t *__restrict__ src,
+                                                                uint4 *__restrict__ dst, size_t words,
+                                                                FeatTable tab) {
+  __shared__ uint32_t t[256];
+  t[threadIdx.x] = tab.w[threadIdx.x];
+  __syncthreads();
+  for (size_t e = blockIdx.x * (size_t)kThreads + threadIdx.x; e < words; e += (size_t)gridDim.x * kThreads) {
+    const uint32_t v = src[e];
+    dst[e] = make_uint4(t[v & 255], t[(v >> 8) & 255], t[(v >> 16) & 255], t[v >> 24]);
+  }
+}
+
+// thresholds "none yet"; the counters and the work-list length behind them zero
+__global__ __launch_bounds__(kThreads) void l1k2_thr_init_kernel(uint32_t *thr, size_t nthr, size_t n) {
+  for (size_t e = blockIdx.x * (size_t)kThreads + threadIdx.x; e < n; e += (size_t)gridDim.x * kThreads)
+    thr[e] = e < nthr ? 0xFFFFFFFFu : 0u;
+}
+
+// LDS accesses of one wave are executed in order; this keeps the compiler from moving them
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
+    const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
+    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, uint32_t *thr,
+    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part) {
+  __shared__ uint4 ftile[2][kTileRows * kLdsRowV4];
+  __shared__ unsigned long long k1s[kQPerBlock], k2s[kQPerBlock];
+  __shared__ uint4 qraw[kQPerBlock * 8];            // the workgroup's query rows as they are
+  __shared__ uint4 xraw[2][kTileRows * 8];          // the tile's database rows as they are
+  __shared__ uint16_t queue[kWaves][kQueue];        // survivors: query of the wave << 5 | row of the tile
+  __shared__ int bail[2];                           // set in tile tl & 1: the workgroup gives the bound up
+  // 79880 bytes in all: two workgroups per CU
+
+  const int t = threadIdx.x;
+  const int w = t >> 6, lane = t & 63, c = lane & 31, g = lane >> 5;
+  const int s = blockIdx.y;
+  const int row_begin = s * slice_rows;
+  const int row_end = min(M, row_begin + slice_rows);
+  const int qbase = blockIdx.x * kQPerBlock + w * kQPerWave;  // this wave's first query
+  const int qslot = w * kQPerWave;                            // and its first top-2 slot
+
+  k1s[t] = ~0ull;
+  k2s[t] = ~0ull;
+  if (t < 2) bail[t] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int e = t + i * kThreads;
+    qraw[e] = y[(size_t)min((int)blockIdx.x * kQPerBlock + (e >> 3), N - 1) * 8 + (e & 7)];
+  }
+
+  // ---- staging of the database feature tiles
+  uint4 stage[4], stage_raw;
+  auto stage_load = [&](int row0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = t + i * kThreads;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (row0 + (e >> 5) < row_end) v = fx[(size_t)row0 * kFeatV4 + e];
+      stage[i] = v;
+    }
+    stage_raw = make_uint4(0, 0, 0, 0);
+    if (row0 + (t >> 3) < row_end) stage_raw = x[(size_t)row0 * 8 + t];
+  };
+  auto stage_store = [&](uint4 *dst, uint4 *dst_raw) {
+    dst_raw[t] = stage_raw;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = t + i * kThreads;
+      dst[(e >> 5) * kLdsRowV4 + (e & 31)] = stage[i];
+    }
+  };
+
+  // ---- exact evaluation of the newest n <= 64 queued pairs of the current tile, one per lane.  Both rows
+  // come from LDS in 16-byte pieces, each lane starting at a piece of its own so that the 64 rows,
+  // which all begin on bank 0, are not read through the same four banks.
+  int cnt = 0;  // wave-uniform
+  auto drain = [&](int n, const uint4 *xr, uint32_t row0) {
+    wave_lds_fence();
+    const int base = cnt - n;
+    if (lane < n) {
+      const uint32_t e = queue[w][base + lane];
+      const int q6 = e >> 5, i = e & 31;
+      const uint4 *qa = qraw + (qslot + q6) * 8, *xa = xr + i * 8;
+      const unsigned long long k2now = k2s[qslot + q6];
+      uint32_t d = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int j = (k + lane) & 7;
+        const uint4 a = qa[j], b = xa[j];
+        d = __builtin_amdgcn_sad_u8(a.x, b.x, d);
+        d = __builtin_amdgcn_sad_u8(a.y, b.y, d);
+        d = __builtin_amdgcn_sad_u8(a.z, b.z, d);
+        d = __builtin_amdgcn_sad_u8(a.w, b.w, d);
+      }
+      // a key that does not beat the query's second best of this moment never will (k2 only falls):
+      // nearly all survivors end here, and the two dependent atomics are left to the few that matter
+      const unsigned long long key = ((unsigned long long)d << 32) | (row0 + i);
+      if (key < k2now) {
+        const unsigned long long old = atomicMin(&k1s[qslot + q6], key);
+        atomicMin(&k2s[qslot + q6], old > key ? old : key);
+      }
+    }
+    cnt = base;
+    wave_lds_fence();
+  };
+
+  // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b].  seen[b] is the
+  // smallest shared threshold read so far.
+  int tq[2];
+  uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+  auto refresh = [&](bool shared) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const uint32_t loc = (uint32_t)(k2s[qslot + 32 * b + c] >> 32);
+      const int qi = qbase + 32 * b + c;
+      if (shared && qi < N) {
+        const uint32_t glob = __hip_atomic_load(&thr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (loc < glob && g == 0) atomicMin(&thr[qi], loc);
+        seen[b] = min(seen[b], glob);
+      }
+      // thr = "none yet" keeps every pair: sum >= 128 m - p 32640 always
+      tq[b] = m128 - p * (int)min(min(loc, seen[b]), kMaxDist);
+    }
+  };
+
+  const int ntiles = (row_end - row_begin + kTileRows - 1) / kTileRows;
+  if (ntiles > 0) {
+    stage_load(row_begin);
+    stage_store(ftile[0], xraw[0]);
+  }
+  __syncthreads();
+
+  unsigned long long n_bound = 0, n_surv = 0;  // wave-uniform statistics
+  bool gave_up = false;                        // workgroup-uniform
+  int warm = kWarmTilesAlone, skip_tiles = kSkipTilesAlone;
+  int recent = 0;  // survivors of the last tiles, each tile weighing 7/8 of the one after it: 8 x the running share
+  int tl = 0;
+  {
+    // ---- this wave's queries as the B operand
+    v4i bq[2][16];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const uint4 *f = fy + (size_t)min(qbase + 32 * b + c, N - 1) * kFeatV4;
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + g]);
+    }
+
+    for (; tl < ntiles; ++tl) {
+      const int row0 = row_begin + tl * kTileRows;
+      const bool has_next = tl + 1 < ntiles;
+      if (has_next) stage_load(row0 + kTileRows);
+      const int nrows = min(kTileRows, row_end - row0);
+      const uint4 *buf = ftile[tl & 1];
+      refresh((tl & 3) == 0);  // the shared thresholds move slowly: every fourth tile is enough
+      if (tl == 0 && __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
+        warm = kWarmTilesShared;
+        skip_tiles = 0;
+      }
+
+      v16i acc[2];
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[0][v] = acc[1][v] = 0;
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) {
+        const v4i a = __builtin_bit_cast(v4i, buf[c * kLdsRowV4 + 2 * ks + g]);
+        acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[0][ks], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[1][ks], acc[1], 0, 0, 0);
+      }
+
+      // One bit per accumulator register: bit 31 - n of `skip` says that pair n = 16 b + v of this lane is
+      // ruled out (sum < threshold; the difference cannot overflow).  Register v of a lane is row
+      // 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are zero padding and
+      // must never be taken for neighbours.
+      uint32_t skip = 0;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) skip = __builtin_amdgcn_alignbit(skip, (uint32_t)(acc[b][v] - tq[b]), 31);
+      }
+      uint32_t live = ~skip;
+      if (nrows < kTileRows) {
+        uint32_t valid = 0;
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if (8 * (v >> 2) + 4 * g + (v & 3) < nrows) valid |= 0x80008000u >> v;
+        live &= valid;
+      }
+      // compaction: every round each lane with survivors left appends its first one to the wave's queue
+      int tile_surv = 0;
+      for (;;) {
+        const bool has = live != 0;
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(has);
+        if (mask == 0ull) break;
+        const int n = __clz(live | 1u);
+        const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (has) {
+          queue[w][pos] = (uint16_t)(((32 * (n >> 4) + c) << 5) | (8 * ((n >> 2) & 3) + 4 * g + (n & 3)));
+          live &= ~(0x80000000u >> n);
+        }
+        const int add = __popcll(mask);
+        cnt += add;
+        tile_surv += add;
+        if (cnt >= 64) drain(64, xraw[tl & 1], (uint32_t)row0);
+      }
+      // the tile's raw rows are overwritten during the next tile: nothing stays queued
+      if (cnt > 0) drain(cnt, xraw[tl & 1], (uint32_t)row0);
+      n_bound += (unsigned long long)nrows * kQPerWave;
+      n_surv += tile_surv;
+
+      // Above the break-even share a survivor pass costs more than the exact loop saves.  A wave that
+      // sees that raises the flag of this tile; after the barrier the whole workgroup reads the same flag
+      // (the next tile uses the other one, and a flag is never lowered), puts itself on the work list of
+      // l1k2_tile_kernel, which then computes this (query block, slice) from scratch, and leaves.
+      recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
+      const int limit = tl >= warm ? max_share : tl > skip_tiles ? kShareUnit * 3 / 4 : kShareUnit;
+      if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
+      if (has_next) stage_store(ftile[(tl + 1) & 1], xraw[(tl + 1) & 1]);
+      __syncthreads();
+      if (bail[tl & 1]) {
+        gave_up = true;
+        break;
+      }
+    }
+  }
+  if (gave_up) {
+    // what this workgroup has found still bounds its queries' second best from above: hand it on;
+    // the exact kernel merges into the partial pair, which starts as "none"
+    const int qo = blockIdx.x * kQPerBlock + t;
+    if (qo < N) {
+      const uint32_t loc = (uint32_t)(k2s[t] >> 32);
+      if (loc < __hip_atomic_load(&thr[qo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qo], loc);
+      uint64_t *dst = part + ((size_t)qo * S + s) * 2;
+      dst[0] = ~0ull;
+      dst[1] = ~0ull;
+    }
+    if (t == 0) {
+      const uint32_t slot = atomicAdd(&work[0], 1u);
+      work[2 + 2 * slot] = blockIdx.x;
+      work[3 + 2 * slot] = blockIdx.y;
+    }
+    if (lane == 0) {
+      unsigned long long *st = stats + ((blockIdx.x + w) % kStatSlots) * 4;
+      atomicAdd(&st[0], n_bound);
+      atomicAdd(&st[1], n_surv);
+      atomicAdd(&st[2], (unsigned long long)(row_end - row_begin) * kQPerWave);
+    }
+    return;
+  }
+  __syncthreads();
+
+  const int qi = blockIdx.x * kQPerBlock + t;
+  if (qi < N) {
+    const unsigned long long a1 = k1s[t], a2 = k2s[t];
+    uint64_t *dst = part + ((size_t)qi * S + s) * 2;
+    dst[0] = a1;
+    dst[1] = a2;
+    const uint32_t loc = (uint32_t)(a2 >> 32);
+    if (loc < __hip_atomic_load(&thr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qi], loc);
+  }
+  if (lane == 0) {
+    unsigned long long *st = stats + ((blockIdx.x + w) % kStatSlots) * 4;
+    atomicAdd(&st[0], n_bound);
+    atomicAdd(&st[1], n_surv);
+  }
+}
+
+std::atomic<int> g_prune_mode{-2};  // -2: SPECTAVI_L1K2_PRUNE not read yet; -1 auto, 0 off, 1 forced
+
+int prune_mode() {
+  int mode = g_prune_mode.load();
+  if (mode == -2) {
+    const char *v = getenv("SPECTAVI_L1K2_PRUNE");
+    mode = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
+    int expected = -2;
+    if (!g_prune_mode.compare_exchange_strong(expected, mode)) mode = expected;
+  }
+  return mode;
+}
+
+L1K2Bound make_bound() {
+  L1K2Bound b{};
+  const double pi = 3.14159265358979323846;
+  for (int a = 0; a < 256; ++a) {
+    b.phi[a][0] = (int8_t)std::nearbyint(127.0 * std::cos(pi * a / 255.0));
+    b.phi[a][1] = (int8_t)std::nearbyint(127.0 * std::sin(pi * a / 255.0));
+    b.phi[a][2] = (int8_t)std::nearbyint(127.0 * std::cos(3.0 * pi * a / 255.0) / 3.0);
+    b.phi[a][3] = (int8_t)std::nearbyint(127.0 * std::sin(3.0 * pi * a / 255.0) / 3.0);
+  }
+  static int G[256][256];
+  long long sumG = 0;
+  for (int a = 0; a < 256; ++a)
+    for (int c = 0; c < 256; ++c) {
+      int g = 0;
+      for (int f = 0; f < 4; ++f) g += (int)b.phi[a][f] * (int)b.phi[c][f];
+      G[a][c] = g;
+      sumG += g;
+    }
+  // the slope whose bound is largest on average over all byte pairs: mean of (m_p - G) / p
+  double best = -1e300;
+  for (int p = 100; p < 260; ++p) {
+    int m = 0x7FFFFFFF;
+    for (int a = 0; a < 256; ++a)
+      for (int c = 0; c < 256; ++c) m = std::min(m, p * std::abs(a - c) + G[a][c]);
+    const double mean = (65536.0 * m - (double)sumG) / p;
+    if (mean > best) {
+      best = mean;
+      b.p = p;
+      b.m = m;
+    }
+  }
+  // the path is refused unless the inequality holds on every byte pair and nothing can overflow
+  b.ok = true;
+  for (int a = 0; a < 256; ++a)
+    for (int c = 0; c < 256; ++c)
+      if ((long long)b.p * std::abs(a - c) < (long long)b.m - G[a][c] || std::abs(G[a][c]) >= (1 << 24) / 128 * 128)
+        b.ok = false;
+  if ((long long)b.p * kMaxDist + 128ll * std::abs(b.m) >= 0x7FFFFFFFll) b.ok = false;
+  return b;
+}
+
+}  // namespace
+
+const L1K2Bound &l1k2_bound() {
+  static const L1K2Bound b = make_bound();
+  return b;
+}
+
+int l1k2_set_prune(int mode) {
+  const int before = prune_mode();
+  g_prune_mode.store(mode);
+  return before;
+}
+int l1k2_get_prune() { return prune_mode(); }
+
+namespace {
+// where the counters of the calling thread's last l1k2_run lie (null: it took the tile kernels)
+thread_local unsigned long long *t_last_stats = nullptr;
+thread_local hipStream_t t_last_stream = nullptr;
+}  // namespace
+
+void l1k2_prune_forget() { t_last_stats = nullptr; }
+
+int l1k2_prune_last_stats(unsigned long long out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!t_last_stats) return SPV_OK;
+  unsigned long long raw[kStatSlots * 4];
+  SPV_HIP_CHECK(hipStreamSynchronize(t_last_stream));
+  SPV_HIP_CHECK(hipMemcpy(raw, t_last_stats, sizeof raw, hipMemcpyDeviceToHost));
+  for (int i = 0; i < kStatSlots; ++i)
+    for (int k = 0; k < 3; ++k) out[k] += raw[4 * i + k];
+  return SPV_OK;
+}
+
+// When `auto` takes the path (tools/l1k2_prune_sweep.py, tools/l1k2_prune_breakeven.py; profiles/r07_*):
+//  * The gain comes with the number of database slices that hand thresholds on: 0.95x at 128k x 128k,
+//    1.16x at 256k x 256k, 1.35x at 512k x 512k, 1.44x at 1M x 1M on uniform bytes.
+//  * What the path costs when the bound does not pay is the tiles a workgroup spends finding that out, at up
+//    to 4.3x the exact cost per pair (all pairs surviving), before it hands its slice to the tile kernel.
+//    With the plan's 8192-row slices at 256k x 256k that was +16 %; it is bounded by 8 of a slice's tiles,
+//    so `auto` asks for slices of at least 1024 tiles (the plan gives them from about 512k x 512k on).
+//  * Break-even: with the fallback off the path ties with the tile kernel at an average survivor share of
+//    about 9 % (uniform bytes in [0, 224): 11.8 %, 72.5 ms against 61.7 ms; [0, 256): 5.7 %, 54 ms) and a
+//    workgroup of the early slices sees about twice the average.  A workgroup hands over when its running
+//    share exceeds 16 % (kBreakEvenShare; judged from its 8th tile on with inherited thresholds, from its 256th
+//    without, while its own thresholds settle), or 3/4 right after its first tiles.
+constexpr int kPruneMinX = 262144, kPruneMinSlice = 32768;
+
+bool l1k2_prune_possible(int xrows, int yrows, int dim) { return dim == 128 && xrows >= kTileRows && yrows >= 1; }
+
+bool l1k2_prune_selected(int xrows, int yrows, int dim, int slice_rows) {
+  if (!l1k2_prune_possible(xrows, yrows, dim) || !l1k2_bound().ok) return false;
+  const int mode = prune_mode();
+  if (mode == 0) return false;
+  if (mode == 1) return true;
+  return xrows >= kPruneMinX && slice_rows >= kPruneMinSlice;
+}
+
+void l1k2_prune_bytes(int xrows, int yrows, int dim, int slices, size_t *fx_bytes, size_t *fy_bytes, size_t *thr_bytes) {
+  *fx_bytes = *fy_bytes = *thr_bytes = 0;
+  if (!l1k2_prune_possible(xrows, yrows, dim)) return;
+  *fx_bytes = round_up((size_t)xrows * 512, 256);
+  *fy_bytes = round_up((size_t)yrows * 512, 256);
+  // thresholds, the counters, the work list of the workgroups that gave up (its length, then one
+  // (query block, slice) pair for each workgroup there can be)
+  const size_t groups = (size_t)((yrows + kQPerBlock - 1) / kQPerBlock) * slices;
+  *thr_bytes = round_up((((size_t)yrows + 1) / 2 * 2 + kStatWords + 2 + 2 * groups) * 4, 256);
+}
+
+int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *d_extra,
+                   uint64_t *part, const uint32_t **work_out, int *groups_out, hipStream_t stream) {
+  const L1K2Bound &b = l1k2_bound();
+  if (!b.ok) return set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
+  size_t fxb, fyb, thb;
+  l1k2_prune_bytes(xrows, yrows, 128, p.slices, &fxb, &fyb, &thb);
+  uint4 *fx = reinterpret_cast<uint4 *>(d_extra);
+  uint4 *fy = reinterpret_cast<uint4 *>(d_extra + fxb);
+  uint32_t *thr = reinterpret_cast<uint32_t *>(d_extra + fxb + fyb);
+  const size_t nthr = ((size_t)yrows + 1) / 2 * 2;
+  unsigned long long *stats = reinterpret_cast<unsigned long long *>(thr + nthr);
+  uint32_t *work = thr + nthr + kStatWords;
+
+  static const FeatTable tab = [&] {
+    FeatTable t;
+    for (int a = 0; a < 256; ++a)
+      t.w[a] = (uint32_t)(uint8_t)b.phi[a][0] | (uint32_t)(uint8_t)b.phi[a][1] << 8 | (uint32_t)(uint8_t)b.phi[a][2] << 16 |
+               (uint32_t)(uint8_t)b.phi[a][3] << 24;
+    return t;
+  }();
+  // Survivor share (in 1/1024 of a tile's pairs) above which a wave finishes its slice exactly.
+  // SPECTAVI_L1K2_PRUNE_SHARE overrides it for measurements (tools/l1k2_prune_breakeven.py): 0 = every
+  // wave leaves the bound after the warm-up tiles, 1024 = never.
+  static const int max_share = [] {
+    const char *v = getenv("SPECTAVI_L1K2_PRUNE_SHARE");
+    return (v && *v) ? std::max(0, std::min(kShareUnit, atoi(v))) : kBreakEvenShare;
+  }();
+  const size_t xw = (size_t)xrows * 32, yw = (size_t)yrows * 32;
+  auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + kThreads - 1) / kThreads, 8192)); };
+  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
+                     xw, tab);
+  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(yw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_y), fy,
+                     yw, tab);
+  hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(nthr + kStatWords + 2), dim3(kThreads), 0, stream, thr, nthr,
+                     nthr + kStatWords + 2);
+  const dim3 grid((unsigned)((yrows + kQPerBlock - 1) / kQPerBlock), (unsigned)p.slices);
+  hipLaunchKernelGGL(l1k2_prune_kernel, grid, dim3(kThreads), 0, stream, reinterpret_cast<const uint4 *>(d_x),
+                     reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, 128 * b.m, b.p,
+                     max_share, thr, stats, work, part);
+  SPV_HIP_CHECK(hipGetLastError());
+  *work_out = work;
+  *groups_out = (int)(grid.x * grid.y);
+  t_last_stats = stats;
+  t_last_stream = stream;
+  static const bool print_stats = [] {
+    const char *v = getenv("SPECTAVI_L1K2_PRUNE_STATS");
+    return v && v[0] == '1';
+  }();
+  if (print_stats) {  // debugging aid: synchronises
+    unsigned long long h[3];
+    SPV_TRY(l1k2_prune_last_stats(h));
+    fprintf(stderr, "l1k2_prune %d x %d: bounded %llu pairs, %llu survived (%.4f), %llu evaluated by the exact fallback\n",
+            xrows, yrows, h[0], h[1], h[0] ? (double)h[1] / (double)h[0] : 0.0, h[2]);
+  }
+  return SPV_OK;
+}
+
+}  // namespace spv

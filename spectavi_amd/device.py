@@ -141,6 +141,42 @@ def bruteforce(x, y, k=2, p=2.0, workspace=None, slices=0):
     return idx, dist
 
 
+clib.spv_l1k2_set_prune.restype = ct.c_int
+clib.spv_l1k2_set_prune.argtypes = [ct.c_int]
+
+
+def l1k2_set_prune(mode):
+    """Whether l1k2() at dim 128 rules pairs out with the matrix-core lower bound first
+    (spv_l1k2_set_prune): "auto" (shapes whose database slices are at least 32768 rows long, the default), 1 / True (wherever the path exists),
+    0 / False (never).  The results do not depend on it."""
+    if isinstance(mode, str):
+        mode = {"auto": -1}.get(mode)
+    if isinstance(mode, bool):
+        mode = int(mode)
+    if not isinstance(mode, int) or mode not in (-1, 0, 1):
+        raise ValueError("prune mode must be 'auto', 0 or 1")
+    check(clib.spv_l1k2_set_prune(mode))
+
+
+clib.spv_l1k2_get_prune.restype = ct.c_int
+clib.spv_l1k2_get_prune.argtypes = []
+clib.spv_l1k2_prune_stats.restype = ct.c_int
+clib.spv_l1k2_prune_stats.argtypes = [ct.POINTER(ct.c_ulonglong)]
+
+
+def l1k2_get_prune():
+    """The prune mode in force: -1 (auto), 0 or 1."""
+    return int(clib.spv_l1k2_get_prune())
+
+
+def l1k2_prune_stats():
+    """(pairs put to the bound, survivors, pairs of the exact fallback) of this thread's last l1k2()
+    call; all zero if it ran the tile kernels.  Synchronises with that call."""
+    out = (ct.c_ulonglong * 3)()
+    check(clib.spv_l1k2_prune_stats(out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def l1k2_plan(xrows, yrows, dim):
     """The launch plan l1k2() follows for this shape (spv_l1k2_plan; host only, no device touched):
     dict of dim_pad (kernel row width), q (queries per lane), slices, slice_rows, wide (bool)."""
