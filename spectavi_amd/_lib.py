@@ -8,6 +8,8 @@ SpectaviError from the first call.
 import ctypes as ct
 import os
 
+from spectavi_amd._proto import PROTOTYPES
+
 _PKG_DIR = os.path.dirname(os.path.realpath(__file__))
 lib_path = os.path.join(_PKG_DIR, "libspectavi.so")
 
@@ -46,18 +48,11 @@ clib = ct.cdll.LoadLibrary(lib_path)
 
 SPV_OK, SPV_ERR_INVALID, SPV_ERR_HIP, SPV_ERR_NOMEM, SPV_ERR_INTERNAL = 0, 1, 2, 3, 4
 
-clib.spv_last_status.restype = ct.c_int
-clib.spv_last_status.argtypes = []
-clib.spv_last_error.restype = ct.c_char_p
-clib.spv_last_error.argtypes = []
-clib.spv_version.restype = ct.c_char_p
-clib.spv_version.argtypes = []
-clib.spv_device_count.restype = ct.c_int
-clib.spv_device_count.argtypes = []
-clib.spv_set_device.restype = ct.c_int
-clib.spv_set_device.argtypes = [ct.c_int]
-clib.spv_set_hash_seed.restype = None
-clib.spv_set_hash_seed.argtypes = [ct.c_uint32, ct.c_int]
+# every prototype of the C-ABI, once (spectavi_amd/_proto.py); nothing else declares one
+for _name, (_restype, _argtypes) in PROTOTYPES.items():
+    _fn = getattr(clib, _name)
+    _fn.restype = _restype
+    _fn.argtypes = _argtypes
 
 
 class SpectaviError(RuntimeError):
@@ -88,8 +83,6 @@ def set_devices(devices):
     """Shard the host-array entry points (feature.*, mvg.*) over these GPUs of the node."""
     devices = [int(d) for d in devices]
     arr = (ct.c_int * len(devices))(*devices)
-    clib.spv_set_devices.restype = ct.c_int
-    clib.spv_set_devices.argtypes = [ct.POINTER(ct.c_int), ct.c_int]
     check(clib.spv_set_devices(arr, len(devices)))
 
 
@@ -109,6 +102,4 @@ def set_gather_mode(mode):
     on the first listed GPU, inside libspectavi.so), "copy" (the same records and root layout moved by peer copies, no RCCL), "direct" (each shard copied to its slice), or
     "auto" (SPECTAVI_GATHER if set, else RCCL when more than one distinct device is listed)."""
     mode = {"auto": GATHER_AUTO, "direct": GATHER_DIRECT, "rccl": GATHER_RCCL, "copy": GATHER_PEERCOPY}.get(mode, mode)
-    clib.spv_set_gather_mode.restype = ct.c_int
-    clib.spv_set_gather_mode.argtypes = [ct.c_int]
     check(clib.spv_set_gather_mode(int(mode)))

@@ -12,31 +12,6 @@ import torch
 
 from spectavi_amd._lib import clib, check
 
-_vp = ct.c_void_p
-
-clib.spv_l1k2_workspace_bytes.restype = ct.c_size_t
-clib.spv_l1k2_workspace_bytes.argtypes = [ct.c_int, ct.c_int, ct.c_int]
-clib.spv_l1k2_plan.restype = ct.c_int
-clib.spv_l1k2_plan.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.POINTER(ct.c_int)]
-clib.spv_l1k2_device.restype = ct.c_int
-clib.spv_l1k2_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
-clib.spv_cascade_workspace_bytes.restype = ct.c_size_t
-clib.spv_cascade_workspace_bytes.argtypes = [ct.c_int] * 6
-clib.spv_cascade_device.restype = ct.c_int
-clib.spv_cascade_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
-                                    _vp, _vp, _vp, _vp, _vp, ct.c_size_t, _vp]
-_f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
-clib.spv_dlt_triangulate_device.restype = ct.c_int
-clib.spv_dlt_triangulate_device.argtypes = [_f64p, _f64p, ct.c_longlong, _vp, _vp, _vp, _vp]
-clib.spv_dlt_reprojection_error_device.restype = ct.c_int
-clib.spv_dlt_reprojection_error_device.argtypes = [_f64p, _f64p, ct.c_longlong, _vp, _vp, _vp, _vp]
-clib.spv_profile_enable.restype = None
-clib.spv_profile_enable.argtypes = [ct.c_int]
-clib.spv_profile_read.restype = ct.c_int
-clib.spv_profile_read.argtypes = [ct.c_char_p, ct.POINTER(ct.c_longlong), ct.POINTER(ct.c_double)]
-clib.spv_profile_reset.restype = None
-clib.spv_profile_reset.argtypes = []
-
 
 def _stream(dev=None):
     return ct.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -105,13 +80,6 @@ def l1k2(x, y, workspace=None):
     return idx, dist
 
 
-clib.spv_bruteforce_workspace_bytes.restype = ct.c_size_t
-clib.spv_bruteforce_workspace_bytes.argtypes = [ct.c_int] * 4
-clib.spv_bruteforce_device.restype = ct.c_int
-clib.spv_bruteforce_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_float,
-                                       ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
-
-
 def bruteforce(x, y, k=2, p=2.0, workspace=None, slices=0):
     """Exact p-norm k-NN on device (the contract of feature.nn_bruteforce): x [M,D], y [N,D] both
     float32 or both int32 CUDA tensors.  Returns (idx int64 [N,k] -- the ABI's size_t bits, -1 = no
@@ -141,10 +109,6 @@ def bruteforce(x, y, k=2, p=2.0, workspace=None, slices=0):
     return idx, dist
 
 
-clib.spv_l1k2_set_prune.restype = ct.c_int
-clib.spv_l1k2_set_prune.argtypes = [ct.c_int]
-
-
 def l1k2_set_prune(mode):
     """Whether l1k2() at dim 128 rules pairs out with the matrix-core lower bound first
     (spv_l1k2_set_prune): "auto" (shapes whose database slices are at least 32768 rows long, the default), 1 / True (wherever the path exists),
@@ -156,12 +120,6 @@ def l1k2_set_prune(mode):
     if not isinstance(mode, int) or mode not in (-1, 0, 1):
         raise ValueError("prune mode must be 'auto', 0 or 1")
     check(clib.spv_l1k2_set_prune(mode))
-
-
-clib.spv_l1k2_get_prune.restype = ct.c_int
-clib.spv_l1k2_get_prune.argtypes = []
-clib.spv_l1k2_prune_stats.restype = ct.c_int
-clib.spv_l1k2_prune_stats.argtypes = [ct.POINTER(ct.c_ulonglong)]
 
 
 def l1k2_get_prune():
@@ -187,8 +145,6 @@ def l1k2_plan(xrows, yrows, dim):
 
 def shard_bounds(total, shards):
     """[lo_0, lo_1, ..., total]: the contiguous balanced shards the library itself uses."""
-    clib.spv_shard_lo.restype = ct.c_longlong
-    clib.spv_shard_lo.argtypes = [ct.c_longlong, ct.c_int, ct.c_int]
     return [int(clib.spv_shard_lo(int(total), int(shards), r)) for r in range(int(shards) + 1)]
 
 
@@ -221,9 +177,6 @@ def l1k2_gathered(xs, ys, transport="rccl"):
     py = (ct.c_void_p * G)(*[y.data_ptr() for y in ys])
     for y in ys:
         torch.cuda.synchronize(y.device)  # the library runs on streams of its own
-    clib.spv_l1k2_gathered_device.restype = ct.c_int
-    clib.spv_l1k2_gathered_device.argtypes = [ct.c_int, ct.POINTER(ct.c_int), ct.POINTER(ct.c_void_p),
-                                              ct.POINTER(ct.c_void_p), ct.c_int, ct.c_longlong, ct.c_int, _vp, _vp, ct.c_int]
     mode = {"rccl": 1, "copy": 2}[transport]
     check(clib.spv_l1k2_gathered_device(G, devs, px, py, xrows, total, dim, idx.data_ptr(), dist.data_ptr(), mode))
     return idx, dist
@@ -259,10 +212,6 @@ def cascade_gathered(xs, ys, dicts, g=2, transport="rccl", want_ncand=False):
     ncand = torch.empty((total,), dtype=torch.int32, device=root) if want_ncand else None
     devs = (ct.c_int * G)(*[y.device.index for y in ys])
     vp = ct.c_void_p * G
-    clib.spv_cascade_gathered_device.restype = ct.c_int
-    clib.spv_cascade_gathered_device.argtypes = [ct.c_int, ct.POINTER(ct.c_int), ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p),
-                                                 ct.c_int, ct.c_longlong, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
-                                                 ct.POINTER(ct.c_void_p), _vp, _vp, _vp, ct.c_int]
     check(clib.spv_cascade_gathered_device(G, devs, vp(*[x.data_ptr() for x in xs]), vp(*[y.data_ptr() for y in ys]), xrows,
                                            total, dim, m, n, g, vp(*[d.data_ptr() for d in dicts]), idx.data_ptr(),
                                            dist.data_ptr(), ncand.data_ptr() if want_ncand else None,
@@ -286,9 +235,6 @@ def dlt_gathered(P0, P1, xs, xps, want_error=False, transport="rccl"):
     out = torch.empty((total, 1 if want_error else 4), dtype=torch.float64, device=xs[0].device)
     devs = (ct.c_int * G)(*[x.device.index for x in xs])
     vp = ct.c_void_p * G
-    clib.spv_dlt_gathered_device.restype = ct.c_int
-    clib.spv_dlt_gathered_device.argtypes = [ct.c_int, ct.POINTER(ct.c_int), _f64p, _f64p, ct.c_longlong,
-                                             ct.POINTER(ct.c_void_p), ct.POINTER(ct.c_void_p), _vp, ct.c_int, ct.c_int]
     check(clib.spv_dlt_gathered_device(G, devs, np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64), total,
                                        vp(*[x.data_ptr() for x in xs]), vp(*[xp.data_ptr() for xp in xps]), out.data_ptr(),
                                        int(bool(want_error)), {"rccl": 1, "copy": 2}[transport]))
@@ -340,20 +286,6 @@ def dlt_reprojection_error(P0, P1, x, xp):
     return _dlt(clib.spv_dlt_reprojection_error_device, P0, P1, x, xp, 1)
 
 
-clib.spv_ratio_test_workspace_bytes.restype = ct.c_size_t
-clib.spv_ratio_test_workspace_bytes.argtypes = [ct.c_int]
-clib.spv_ratio_test_device.restype = ct.c_int
-clib.spv_ratio_test_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_double, _vp, _vp, _vp, ct.c_size_t, _vp]
-clib.spv_dlt_score_hypotheses_device.restype = ct.c_int
-clib.spv_dlt_score_hypotheses_device.argtypes = [_f64p, _vp, ct.c_int, ct.c_longlong, _vp, _vp, ct.c_double,
-                                                 _vp, _vp, _vp]
-clib.spv_dlt_score_workspace_bytes.restype = ct.c_size_t
-clib.spv_dlt_score_workspace_bytes.argtypes = [ct.c_int, ct.c_longlong]
-clib.spv_dlt_score_hypotheses_device_ws.restype = ct.c_int
-clib.spv_dlt_score_hypotheses_device_ws.argtypes = [_f64p, _vp, ct.c_int, ct.c_longlong, _vp, _vp, ct.c_double,
-                                                    _vp, _vp, _vp, ct.c_size_t, _vp]
-
-
 def ratio_test(idx, dist, min_ratio, workspace=None):
     """Ratio test + ordered compaction on device.  idx int64 [N,2], dist int32/float32 [N,2]
     (outputs of l1k2 / cascade).  Returns (matches int32 [N,2] capacity, count int32 [1]);
@@ -392,12 +324,6 @@ def dlt_score_hypotheses(P0, P1s, x, xp, max_error, want_mask=False, workspace=N
                                                       mask.data_ptr() if want_mask else None, ws.data_ptr(),
                                                       ws.numel(), stream))
     return (counts, mask) if want_mask else counts
-
-
-clib.spv_sift_split_device.restype = ct.c_int
-clib.spv_sift_split_device.argtypes = [_vp, ct.c_int, _vp, _vp, _vp]
-clib.spv_gather_match_coords_device.restype = ct.c_int
-clib.spv_gather_match_coords_device.argtypes = [_vp, _vp, _vp, _vp, ct.c_int, _vp, _vp, _vp]
 
 
 def split_sift_table(table):
@@ -445,14 +371,6 @@ def profile_read(name):
     return int(n.value), float(ms.value)
 
 
-clib.spv_ransac_workspace_bytes.restype = ct.c_size_t
-clib.spv_ransac_workspace_bytes.argtypes = [ct.c_int, ct.c_longlong, ct.c_int]
-clib.spv_ransac_process_candidates_device.restype = ct.c_int
-clib.spv_ransac_process_candidates_device.argtypes = [_vp, ct.c_int, ct.c_longlong, _vp, _vp, ct.c_double, ct.c_double,
-                                                      ct.c_double, ct.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                      _vp, ct.c_size_t, _vp]
-
-
 def ransac_process_candidates(Fs, x0, x1, singular_value_ratio_allowed=3e-2, required_percent_inliers=.9,
                               reprojection_error_allowed=.5, find_best_even_in_failure=True, want_mask=False,
                               workspace=None):
@@ -488,14 +406,6 @@ def ransac_process_candidates(Fs, x0, x1, singular_value_ratio_allowed=3e-2, req
     return out
 
 
-_i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
-clib.spv_ransac_fit_device.restype = ct.c_int
-clib.spv_ransac_fit_device.argtypes = [_vp, _vp, ct.c_int, ct.c_double, ct.c_double, ct.c_int, ct.c_int, ct.c_double,
-                                       ct.c_ulonglong, _vp, ct.POINTER(ct.c_int32), _f64p, _f64p,
-                                       ct.POINTER(ct.c_double), _i32p, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32),
-                                       ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32), _vp]
-
-
 def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.5, maximum_tries=500,
                find_best_even_in_failure=True, singular_value_ratio_allowed=3e-2, seed=0, samples=None):
     """`mvg.ransac_fit` with the correspondences resident in HBM (reference RansacFitter::fit_essential,
@@ -528,12 +438,6 @@ def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.
             'inlier_idx': idx[:n.value].copy(), 'best_try': bt.value, 'best_root': br.value, 'tries_run': ran.value}
 
 
-clib.spv_normalize_workspace_bytes_rows.restype = ct.c_size_t
-clib.spv_normalize_workspace_bytes_rows.argtypes = [ct.c_int, ct.c_int]
-clib.spv_normalize_device.restype = ct.c_int
-clib.spv_normalize_device.argtypes = [_vp, ct.c_int, ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
-
-
 def normalize(x, want_float=True, want_ubyte=False, workspace=None):
     """`normalize_to_ubyte_and_multiple_16_dim` (reference spectavi/feature.py:384-407) on a CUDA float32
     [rows, dim] table, bit-identical to the numpy function: returns the float32 [rows, dim16] table
@@ -550,10 +454,6 @@ def normalize(x, want_float=True, want_ubyte=False, workspace=None):
     if want_float and want_ubyte:
         return out, u8
     return out if want_float else u8
-
-
-clib.spv_seven_point_device.restype = ct.c_int
-clib.spv_seven_point_device.argtypes = [_vp, _vp, ct.c_int, _vp, _vp, _vp, _vp]
 
 
 def seven_point(x, xp, want_basis=False):
@@ -573,9 +473,6 @@ def seven_point(x, xp, want_basis=False):
     return (nroot, Fs, basis) if want_basis else (nroot, Fs)
 
 
-clib.spv_rectify_device.restype = ct.c_int
-clib.spv_rectify_device.argtypes = [_f64p, _vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_double,
-                                    _vp, _vp, _vp, _vp, _vp]
 _RECTIFY_DTYPE = {torch.float64: 0, torch.uint8: 1}  # SPV_RECTIFY_F64, SPV_RECTIFY_U8
 
 
@@ -605,12 +502,6 @@ def image_pair_rectification(P0, P1, im0, im1, sampling_factor=1.2):
                                       float(sampling_factor), r0.data_ptr(), r1.data_ptr(), ri0.data_ptr(),
                                       ri1.data_ptr(), stream))
     return r0, r1, ri0, ri1
-
-
-clib.spv_sift_workspace_bytes.restype = ct.c_size_t
-clib.spv_sift_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
-clib.spv_sift_device.restype = ct.c_int
-clib.spv_sift_device.argtypes = [_vp, ct.c_int, ct.c_int, _vp, ct.c_size_t, _vp, ct.c_int, _vp, _vp]
 
 
 def sift_into(im, table, count, workspace=None):

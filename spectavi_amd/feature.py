@@ -9,7 +9,6 @@ bound with ctypes to the gfx950 build of ``libspectavi.so``.
 import ctypes as ct
 
 import numpy as np
-from numpy.ctypeslib import ndpointer
 
 from spectavi_amd._lib import clib, check
 from spectavi_amd.ndarray import NdArray
@@ -18,15 +17,6 @@ from spectavi_amd.ndarray import NdArray
 # brute-force L1, k = 2       (reference spectavi/feature.py:234-243)
 # ==================================================================================
 _nn_bruteforcel1k2 = clib.nn_bruteforcel1k2
-_nn_bruteforcel1k2.restype = None
-_nn_bruteforcel1k2.argtypes = [ndpointer(ct.c_ubyte, flags="C_CONTIGUOUS"),
-                               ndpointer(ct.c_ubyte, flags="C_CONTIGUOUS"),
-                               ct.c_int,
-                               ct.c_int,
-                               ct.c_int,
-                               ct.c_int,
-                               ct.POINTER(NdArray),
-                               ct.POINTER(NdArray), ]
 
 
 def nn_bruteforcel1k2(x, y, nthreads=1):
@@ -61,30 +51,7 @@ def nn_bruteforcel1k2(x, y, nthreads=1):
 # brute-force p-norm k-NN     (reference spectavi/feature.py:204-289)
 # ==================================================================================
 _nn_bruteforce = clib.nn_bruteforce
-_nn_bruteforce.restype = None
-_nn_bruteforce.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                           ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                           ct.c_int,
-                           ct.c_int,
-                           ct.c_int,
-                           ct.c_int,
-                           ct.c_float,
-                           ct.c_float,
-                           ct.POINTER(NdArray),
-                           ct.POINTER(NdArray), ]
-
 _nn_bruteforcei = clib.nn_bruteforcei
-_nn_bruteforcei.restype = None
-_nn_bruteforcei.argtypes = [ndpointer(ct.c_int, flags="C_CONTIGUOUS"),
-                            ndpointer(ct.c_int, flags="C_CONTIGUOUS"),
-                            ct.c_int,
-                            ct.c_int,
-                            ct.c_int,
-                            ct.c_int,
-                            ct.c_float,
-                            ct.c_float,
-                            ct.POINTER(NdArray),
-                            ct.POINTER(NdArray), ]
 
 BRUTEFORCE_MAX_K = 64
 BRUTEFORCE_MAX_DIM = 2048
@@ -151,33 +118,8 @@ def nn_bruteforce(x, y, p=.5, mu=0., k=2, use_int=False):
 # cascading hash              (reference spectavi/feature.py:346-376)
 # ==================================================================================
 _nn_cascading_hash = clib.nn_cascading_hash
-_nn_cascading_hash.restype = None
-_nn_cascading_hash.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                               ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                               ct.c_int,
-                               ct.c_int,
-                               ct.c_int,
-                               ct.c_int,
-                               ct.c_int,
-                               ct.c_int,
-                               ct.c_int,
-                               ct.POINTER(NdArray),
-                               ct.POINTER(NdArray), ]
-
 _spv_nn_cascading_hash = clib.spv_nn_cascading_hash
-_spv_nn_cascading_hash.restype = ct.c_int
-_spv_nn_cascading_hash.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                                   ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                                   ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
-                                   ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                                   ndpointer(ct.c_uint64, flags="C_CONTIGUOUS"),
-                                   ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                                   ct.c_void_p]
-
 _spv_generate_hash_dict = clib.spv_generate_hash_dict
-_spv_generate_hash_dict.restype = ct.c_int
-_spv_generate_hash_dict.argtypes = [ct.c_uint32, ct.c_int, ct.c_int, ct.c_int,
-                                    ndpointer(ct.c_float, flags="C_CONTIGUOUS")]
 
 
 def auto_hash_bit_rate(xrows, yrows):
@@ -283,10 +225,6 @@ def normalize_to_ubyte_and_multiple_16_dim(x, dtype='float32'):
 # ratio test + match compaction (reference example/ex01_essential_estimation.py:102-106)
 # ==================================================================================
 _spv_ratio_test = clib.spv_ratio_test
-_spv_ratio_test.restype = ct.c_int
-_spv_ratio_test.argtypes = [ndpointer(ct.c_uint64, flags="C_CONTIGUOUS"), ct.c_void_p, ct.c_int, ct.c_int,
-                            ct.c_double, ndpointer(ct.c_int32, flags="C_CONTIGUOUS"),
-                            ct.POINTER(ct.c_int32)]
 
 
 def ratio_test_matches(nn_idx, nn_dist, min_ratio):
@@ -315,10 +253,6 @@ def ratio_test_matches(nn_idx, nn_dist, min_ratio):
 # SIFT table adapter (reference src/Sift.h:13,115-123: rows of 132 floats)
 # ==================================================================================
 _spv_sift_split = clib.spv_sift_split
-_spv_sift_split.restype = ct.c_int
-_spv_sift_split.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"), ct.c_int,
-                            ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                            ndpointer(ct.c_ubyte, flags="C_CONTIGUOUS")]
 
 
 def split_sift_table(table):
@@ -339,9 +273,6 @@ def split_sift_table(table):
 # normalisation on device (same result as normalize_to_ubyte_and_multiple_16_dim above)
 # ==================================================================================
 _spv_normalize = clib.spv_normalize
-_spv_normalize.restype = ct.c_int
-_spv_normalize.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"), ct.c_int, ct.c_int, ct.c_void_p,
-                           ct.c_void_p]
 
 
 def normalize_to_ubyte_and_multiple_16_dim_gpu(x, want_ubyte=False):
@@ -362,40 +293,11 @@ def normalize_to_ubyte_and_multiple_16_dim_gpu(x, want_ubyte=False):
 # SIFT                        (reference spectavi/feature.py:17-148)
 # ==================================================================================
 _sift_filter = clib.sift_filter
-_sift_filter.restype = None
-_sift_filter.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                         ct.c_int,
-                         ct.c_int,
-                         ct.POINTER(NdArray), ]
-
 _sift_filter_batch_create = clib.sift_filter_batch_create
-_sift_filter_batch_create.restype = ct.c_void_p
-_sift_filter_batch_create.argtypes = []
-
 _sift_filter_batch_destroy = clib.sift_filter_batch_destroy
-_sift_filter_batch_destroy.restype = None
-_sift_filter_batch_destroy.argtypes = [ct.c_void_p]
-
 _sift_filter_batch_register_image = clib.sift_filter_batch_register_image
-_sift_filter_batch_register_image.restype = None
-_sift_filter_batch_register_image.argtypes = [ct.c_void_p,
-                                              ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                                              ct.c_int,
-                                              ct.c_int,
-                                              ct.POINTER(NdArray), ]
-
 _sift_filter_batch_process = clib.sift_filter_batch_process
-_sift_filter_batch_process.restype = None
-_sift_filter_batch_process.argtypes = [ct.c_void_p, ct.c_int]
-
 _spv_sift_table = clib.spv_sift_table
-_spv_sift_table.restype = ct.c_int
-_spv_sift_table.argtypes = [ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                            ct.c_int,
-                            ct.c_int,
-                            ndpointer(ct.c_float, flags="C_CONTIGUOUS"),
-                            ct.c_int,
-                            ct.POINTER(ct.c_int32), ]
 
 
 def _gray(im):

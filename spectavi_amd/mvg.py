@@ -9,7 +9,6 @@ rectification (reference spectavi/mvg.py:47-106), bound to the gfx950 build of `
 import ctypes as ct
 
 import numpy as np
-from numpy.ctypeslib import ndpointer
 
 from spectavi_amd._lib import clib, check
 from spectavi_amd.ndarray import NdArray
@@ -21,17 +20,7 @@ def hnormalize(x):
 
 
 _dlt_triangulate = clib.dlt_triangulate
-_dlt_triangulate.restype = None
-_dlt_triangulate.argtypes = [ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                             ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                             ct.c_int,
-                             ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                             ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                             ndpointer(ct.c_double, flags="C_CONTIGUOUS"), ]
-
 _dlt_reprojection_error = clib.dlt_reprojection_error
-_dlt_reprojection_error.restype = None
-_dlt_reprojection_error.argtypes = list(_dlt_triangulate.argtypes)
 
 
 def dlt_triangulate(P0, P1, x, xp, ret_error=False):
@@ -74,15 +63,6 @@ def dlt_reprojection_error(P0, P1, x, xp):
 # RANSAC hypothesis scoring (the inner loops of reference src/RansacFitter.h:59-95)
 # ==================================================================================
 _spv_dlt_score_hypotheses = clib.spv_dlt_score_hypotheses
-_spv_dlt_score_hypotheses.restype = ct.c_int
-_spv_dlt_score_hypotheses.argtypes = [ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                                      ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                                      ct.c_int, ct.c_int,
-                                      ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                                      ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                                      ct.c_double,
-                                      ndpointer(ct.c_int32, flags="C_CONTIGUOUS"),
-                                      ct.c_void_p]
 
 
 def dlt_score_hypotheses(P0, P1s, x, xp, max_error, return_mask=False):
@@ -117,11 +97,6 @@ def dlt_score_hypotheses(P0, P1s, x, xp, max_error, return_mask=False):
 # RANSAC candidate processing (reference src/RansacFitter.h:42-95 + src/Camera.h:31-46)
 # ==================================================================================
 _spv_ransac_process = clib.spv_ransac_process_candidates
-_spv_ransac_process.restype = ct.c_int
-_f64 = ndpointer(ct.c_double, flags="C_CONTIGUOUS")
-_i32 = ndpointer(ct.c_int32, flags="C_CONTIGUOUS")
-_spv_ransac_process.argtypes = [_f64, ct.c_int, _f64, _f64, ct.c_int, ct.c_double, ct.c_double, ct.c_double, ct.c_int,
-                                _i32, _i32, _i32, _f64, _f64, _f64, _i32, ct.c_void_p]
 
 
 def process_fundamental_matrices(Fs, x0, x1, options={'required_percent_inliers': .9,
@@ -179,11 +154,6 @@ def process_fundamental_matrices(Fs, x0, x1, options={'required_percent_inliers'
 # seven_point_algorithm / ransac_fitter (reference spectavi/mvg.py:112-248)
 # ==================================================================================
 _seven_point_algorithm = clib.seven_point_algorithm
-_seven_point_algorithm.restype = None
-_seven_point_algorithm.argtypes = [ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                                   ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                                   ct.POINTER(ct.c_int),
-                                   ndpointer(ct.c_double, flags="C_CONTIGUOUS")]
 
 
 def seven_point_algorithm(x, xp):
@@ -208,8 +178,6 @@ def seven_point_algorithm(x, xp):
 
 
 _spv_seven_point = clib.spv_seven_point
-_spv_seven_point.restype = ct.c_int
-_spv_seven_point.argtypes = [_f64, _f64, ct.c_int, _i32, _f64, ct.c_void_p]
 
 
 def seven_point_batch(x, xp, return_basis=False):
@@ -233,21 +201,6 @@ def seven_point_batch(x, xp, return_basis=False):
 
 
 _ransac_fitter = clib.ransac_fitter
-_ransac_fitter.restype = None
-_ransac_fitter.argtypes = [ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                           ndpointer(ct.c_double, flags="C_CONTIGUOUS"),
-                           ct.c_int,
-                           ct.c_double,
-                           ct.c_double,
-                           ct.c_int,
-                           ct.c_bool,
-                           ct.c_double,
-                           ct.c_bool,
-                           ct.POINTER(ct.c_bool),
-                           ct.POINTER(NdArray),
-                           ct.POINTER(NdArray),
-                           ct.POINTER(ct.c_double),
-                           ct.POINTER(NdArray), ]
 
 
 def ransac_fitter(x0, x1, options={'required_percent_inliers': .9,
@@ -298,8 +251,6 @@ def ransac_fitter(x0, x1, options={'required_percent_inliers': .9,
 
 
 _spv_ransac_sample = clib.spv_ransac_sample
-_spv_ransac_sample.restype = ct.c_int
-_spv_ransac_sample.argtypes = [ct.c_ulonglong, ct.c_int, ct.c_int, _i32]
 
 
 def ransac_sample(seed, npt, ntries):
@@ -310,16 +261,8 @@ def ransac_sample(seed, npt, ntries):
     return samples
 
 
-_fit_out = [ct.POINTER(ct.c_int32), _f64, _f64, ct.POINTER(ct.c_double), _i32, ct.POINTER(ct.c_int32),
-            ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int32)]
 _spv_ransac_fit = clib.spv_ransac_fit
-_spv_ransac_fit.restype = ct.c_int
-_spv_ransac_fit.argtypes = [_f64, _f64, ct.c_int, ct.c_double, ct.c_double, ct.c_int, ct.c_int, ct.c_double,
-                            ct.c_ulonglong] + _fit_out
 _spv_ransac_fit_samples = clib.spv_ransac_fit_samples
-_spv_ransac_fit_samples.restype = ct.c_int
-_spv_ransac_fit_samples.argtypes = [_f64, _f64, ct.c_int, ct.c_double, ct.c_double, _i32, ct.c_int, ct.c_int,
-                                    ct.c_double] + _fit_out
 
 
 def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.5, maximum_tries=500,
@@ -364,16 +307,8 @@ def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.
 # image_pair_rectification (reference spectavi/mvg.py:47-106)
 # ==================================================================================
 _image_pair_rectification = clib.image_pair_rectification
-_image_pair_rectification.restype = None
-_image_pair_rectification.argtypes = [_f64, _f64, _f64, _f64, ct.c_int, ct.c_int, ct.c_int, ct.c_double,
-                                      ct.POINTER(NdArray), ct.POINTER(NdArray), ct.POINTER(NdArray),
-                                      ct.POINTER(NdArray)]
 _spv_rectify_fundamental = clib.spv_rectify_fundamental
-_spv_rectify_fundamental.restype = ct.c_int
-_spv_rectify_fundamental.argtypes = [_f64, _f64, _f64]
 _spv_rectify_shape = clib.spv_rectify_shape
-_spv_rectify_shape.restype = ct.c_int
-_spv_rectify_shape.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_double, _i32]
 
 
 def _cameras(P0, P1):

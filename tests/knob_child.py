@@ -66,11 +66,6 @@ def run_cascade(cases, oracle):
 
 def run_l1k2(q, oracle):
     from spectavi_amd._lib import clib, check
-    clib.spv_l1k2_plan.restype = ct.c_int
-    clib.spv_l1k2_plan.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.POINTER(ct.c_int)]
-    clib.spv_nn_bruteforcel1k2.restype = ct.c_int
-    clib.spv_nn_bruteforcel1k2.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int,
-                                           ct.c_void_p, ct.c_void_p]
     for dim in L1K2_DIMS:
         for yrows in L1K2_YROWS:
             xrows = 700 + yrows % 7

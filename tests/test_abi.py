@@ -9,15 +9,118 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+SCALARS = {"int": ct.c_int, "int32_t": ct.c_int32, "uint32_t": ct.c_uint32, "long long": ct.c_longlong,
+           "unsigned long long": ct.c_ulonglong, "size_t": ct.c_size_t, "float": ct.c_float, "double": ct.c_double,
+           "bool": ct.c_bool}
+POINTEES = dict(SCALARS, int8_t=ct.c_int8, uint8_t=ct.c_uint8, uint64_t=ct.c_uint64)
+C_CONTIGUOUS = 0x1   # NPY_ARRAY_C_CONTIGUOUS, as numpy.ctypeslib.ndpointer keeps it in _flags_
 
-def declared_symbols():
-    names = set()
+
+def c_type(text, named):
+    """A return type or a parameter as the headers spell them -> (base type, pointer depth):
+    'const double *P0' -> ('double', 1), 'int out[5]' -> ('int', 1), 'const float *const *d_x' -> ('float', 2)."""
+    text, dims = re.subn(r"\[\d+\]", "", text)
+    words = [w for w in text.replace("*", " ").split() if w != "const"]
+    base = " ".join(words[:-1] if named else words)
+    assert base in POINTEES or base in ("void", "char", "NdArray"), "unknown C type in %r" % text
+    return base, text.count("*") + (1 if dims else 0)
+
+
+def declared_prototypes():
+    """{name: ((base, depth) of the return type, [(base, depth) of every parameter])} of every function
+    the two headers declare.  Understands the spellings they use and fails on any other."""
+    protos = {}
     for hdr in ("spectavi_amd.h", "NdArray.h"):
         text = open(os.path.join(ROOT, "include", hdr)).read()
         text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        for m in re.finditer(r"^\s*(?:const\s+)?(?:void|int|size_t|char|long long)\s*\*?\s*(\w+)\s*\(", text, flags=re.M):
-            names.add(m.group(1))
-    return sorted(names)
+        assert "//" not in text and "\\\n" not in text
+        text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+        text = re.sub(r"typedef struct NdArray \{.*?\} NdArray;", "", text, flags=re.S)
+        text = text.replace('extern "C" {', "")
+        for decl in text.split(";"):
+            decl = " ".join(decl.split())
+            if decl in ("", "}"):   # "}" closes extern "C"
+                continue
+            m = re.fullmatch(r"(.*?)(\w+) ?\((.*)\)", decl)
+            assert m and m.group(2) not in protos, "cannot parse %r" % decl
+            params = [] if m.group(3) == "void" else [c_type(a, True) for a in m.group(3).split(",")]
+            protos[m.group(2)] = (c_type(m.group(1), False), params)
+    return protos
+
+
+def declared_symbols():
+    return sorted(declared_prototypes())
+
+
+def accepts(ctype, base, depth):
+    """Whether a ctypes restype / argtypes entry can stand for the C type (base, depth)."""
+    from spectavi_amd.ndarray import NdArray
+    if depth == 0:
+        return ctype is (None if base == "void" else SCALARS[base])
+    if depth == 2:
+        return ctype is ct.POINTER(ct.c_void_p)
+    if base in ("void", "char", "NdArray"):
+        return ctype is {"void": ct.c_void_p, "char": ct.c_char_p, "NdArray": ct.POINTER(NdArray)}[base]
+    if ctype is ct.c_void_p or ctype is ct.POINTER(POINTEES[base]):
+        return True
+    return (hasattr(ctype, "_dtype_") and ctype._dtype_ == np.dtype(POINTEES[base])   # an ndpointer class
+            and bool((ctype._flags_ or 0) & C_CONTIGUOUS))
+
+
+def mismatches(proto, decl):
+    """What is wrong with the ctypes prototype (restype, [argtypes]) of a function declared as decl."""
+    (restype, argtypes), (ret, params) = proto, decl
+    if len(argtypes) != len(params):
+        return ["%d arguments, the header has %d" % (len(argtypes), len(params))]
+    bad = [] if accepts(restype, *ret) else ["restype %r for %s" % (restype, ret)]
+    return bad + ["slot %d: %r for %s" % (k, a, c) for k, (a, c) in enumerate(zip(argtypes, params))
+                  if not accepts(a, *c)]
+
+
+def test_prototype_table_names_every_declared_function():
+    from spectavi_amd._proto import PROTOTYPES
+    assert set(PROTOTYPES) == set(declared_prototypes()), set(PROTOTYPES) ^ set(declared_prototypes())
+
+
+def test_prototype_table_agrees_with_the_headers():
+    """Every restype and every argtypes slot of spectavi_amd/_proto.py against include/*.h."""
+    from spectavi_amd._proto import PROTOTYPES
+    decls = declared_prototypes()
+    wrong = {n: mismatches(PROTOTYPES[n], d) for n, d in decls.items() if mismatches(PROTOTYPES[n], d)}
+    assert not wrong, wrong
+
+
+def test_prototype_check_refuses_wrong_prototypes():
+    from numpy.ctypeslib import ndpointer
+    i, f64a = ct.c_int, ndpointer(np.float64, flags="C_CONTIGUOUS")
+    decls = declared_prototypes()
+    for name, proto in (
+            ("spv_set_device", (i, [])),                                        # one argument too few
+            ("spv_shard_lo", (ct.c_longlong, [i, i, i])),                       # c_int for a long long
+            ("spv_l1k2_workspace_bytes", (i, [i, i, i])),                       # c_int for a size_t return
+            ("spv_rectify_shape", (i, [i, i, i, ct.c_float, ct.POINTER(i)])),   # c_float for a double
+            ("spv_rectify_fundamental", (i, [ndpointer(np.float32, flags="C_CONTIGUOUS"), f64a, f64a])),
+            ("spv_rectify_fundamental", (i, [ndpointer(np.float64), f64a, f64a])),   # contiguity not required
+            ("spv_profile_enable", (None, [ct.c_void_p])),                      # c_void_p for an int
+            ("spv_last_error", (ct.c_void_p, [])),                              # not a string
+            ("spv_l1k2_gathered_device", (i, [i, ct.POINTER(i)] + [ct.c_void_p] * 2 + [i, ct.c_longlong, i]
+                                          + [ct.c_void_p] * 2 + [i]))):         # c_void_p for a T *const *
+        assert mismatches(proto, decls[name]), name
+
+
+def test_library_carries_the_table_after_importing_the_loader_alone():
+    """In a fresh process, so that nothing imported earlier in this session can have typed clib."""
+    import subprocess
+    import sys
+    code = ("import sys; from spectavi_amd._lib import clib; from spectavi_amd._proto import PROTOTYPES\n"
+            "assert not {'torch', 'spectavi_amd.feature', 'spectavi_amd.mvg', 'spectavi_amd.device'} & set(sys.modules)\n"
+            "for n, (r, a) in PROTOTYPES.items():\n"
+            "    fn = getattr(clib, n)\n"
+            "    assert fn.restype is r and len(fn.argtypes) == len(a) and all(x is y for x, y in zip(fn.argtypes, a)), n\n"
+            "print('typed', len(PROTOTYPES))")
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("typed"), r.stdout + r.stderr
 
 
 def test_library_exports_every_declared_symbol():
@@ -35,9 +138,6 @@ def test_ndarray_struct_matches_header():
     from spectavi_amd.ndarray import NdArray
     assert ct.sizeof(NdArray) == 8 + 4 * 8 + 4 + 4
     a = NdArray(dtype='int32')
-    clib.ndarray_set_size.argtypes = [ct.POINTER(NdArray), ct.c_size_t, ct.c_size_t]
-    clib.ndarray_alloc.argtypes = [ct.POINTER(NdArray)]
-    clib.ndarray_alloc.restype = ct.c_int
     clib.ndarray_set_size(ct.byref(a), 3, 2)
     assert clib.ndarray_alloc(ct.byref(a)) == 0
     ct.memmove(a.m_data, (ct.c_int32 * 6)(1, 2, 3, 4, 5, 6), 24)
@@ -157,10 +257,6 @@ def test_record_pack_and_widen_arithmetic():
     back to their rows.  Host functions only; no GPU involved."""
     from spectavi_amd._lib import clib, SPV_ERR_INVALID
     u64p, i32p = ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_int32)
-    clib.spv_records_pack.restype = ct.c_int
-    clib.spv_records_pack.argtypes = [u64p, ct.c_void_p, ct.c_longlong, i32p]
-    clib.spv_records_unpack.restype = ct.c_int
-    clib.spv_records_unpack.argtypes = [i32p, ct.c_longlong, ct.c_int, ct.c_longlong, u64p, ct.c_void_p]
     rng = np.random.default_rng(9)
     none = np.iinfo(np.uint64).max
     for total, G in ((1, 1), (7, 1), (7, 3), (8, 8), (1001, 3), (1000, 8), (5, 4), (64, 7)):
@@ -209,8 +305,6 @@ def test_record_pack_and_widen_arithmetic():
 
 def test_gather_mode_api_without_gpu():
     from spectavi_amd._lib import clib, SPV_ERR_INVALID
-    clib.spv_set_gather_mode.restype = ct.c_int
-    clib.spv_set_gather_mode.argtypes = [ct.c_int]
     assert clib.spv_set_gather_mode(7) == SPV_ERR_INVALID
     for mode in (1, 0, -1):
         assert clib.spv_set_gather_mode(mode) == 0

@@ -51,9 +51,6 @@ def test_c_abi_refuses_bad_arguments_without_a_device():
     without a GPU; the workspace query answers 0 for a refused shape."""
     from spectavi_amd._lib import clib, SPV_ERR_INVALID
     f = clib.spv_nn_bruteforce
-    f.restype = ct.c_int
-    f.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_float,
-                  ct.c_void_p, ct.c_void_p]
     x = np.zeros((4, 8), np.float32)
     idx = np.zeros((4, 64), np.uint64)
     dist = np.zeros((4, 64), np.float32)
@@ -67,8 +64,6 @@ def test_c_abi_refuses_bad_arguments_without_a_device():
     # yrows = 0 is a valid empty call: nothing to compute, no device needed
     assert f(None, None, 0, 0, 0, 8, 2, 2.0, None, None) == 0
     ws = clib.spv_bruteforce_workspace_bytes
-    ws.restype = ct.c_size_t
-    ws.argtypes = [ct.c_int] * 4
     assert ws(100, 100, 8, 0) == 0 and ws(100, 100, 2049, 2) == 0
     assert ws(100, 100, 8, 2) >= 100 * 2 * 8
 

@@ -181,7 +181,7 @@ def test_device_path_and_plan_independence(is_int):
 
 def test_bad_arguments_through_the_c_abi():
     import torch
-    from spectavi_amd import device, feature  # noqa: F401  (device declares the argtypes)
+    from spectavi_amd import feature
     from spectavi_amd._lib import clib, SPV_ERR_INVALID
     from spectavi_amd.ndarray import NdArray
     x = np.zeros((8, 4), np.float32)

@@ -10,8 +10,6 @@ def _table():
     from spectavi_amd._lib import clib
     phi = np.zeros((256, 4), np.int8)
     p, m = ct.c_int(0), ct.c_int(0)
-    clib.spv_l1k2_bound_table.restype = ct.c_int
-    clib.spv_l1k2_bound_table.argtypes = [ct.c_void_p, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int)]
     assert clib.spv_l1k2_bound_table(phi.ctypes.data, ct.byref(p), ct.byref(m)) == 0
     return phi.astype(np.int64), int(p.value), int(m.value)
 

@@ -13,15 +13,11 @@ I32MAX = np.iinfo(np.int32).max
 
 def _raw(x, y):
     """spv_nn_bruteforcel1k2: host pointers, caller-allocated outputs."""
-    import ctypes as ct
     from spectavi_amd._lib import clib, check
     x = np.ascontiguousarray(x)
     y = np.ascontiguousarray(y)
     idx = np.empty((y.shape[0], 2), np.uint64)
     dist = np.empty((y.shape[0], 2), np.int32)
-    clib.spv_nn_bruteforcel1k2.restype = ct.c_int
-    clib.spv_nn_bruteforcel1k2.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int,
-                                           ct.c_void_p, ct.c_void_p]
     check(clib.spv_nn_bruteforcel1k2(x.ctypes.data, y.ctypes.data, x.shape[0], y.shape[0], y.shape[1],
                                      idx.ctypes.data, dist.ctypes.data))
     return idx, dist
@@ -156,7 +152,6 @@ def test_randomized_shapes(oracle):
 
 def test_repeated_calls_reuse_cached_buffers(oracle):
     """The host path caches device buffers between calls; results must not depend on it."""
-    import ctypes as ct
     from spectavi_amd._lib import clib
     rng = np.random.default_rng(5)
     for k in range(6):
@@ -167,15 +162,12 @@ def test_repeated_calls_reuse_cached_buffers(oracle):
         oidx, odist = oracle.nn_bruteforcel1k2(x, y, nthreads=8)
         assert np.array_equal(idx, oidx) and np.array_equal(dist, odist)
         if k == 3:
-            clib.spv_release_cached_memory.restype = None
             clib.spv_release_cached_memory()
 
 
 def test_workspace_too_small_is_an_error():
     import torch
-    import ctypes as ct
     from spectavi_amd._lib import clib, SPV_ERR_INVALID
-    from spectavi_amd import device  # noqa: F401  (declares argtypes)
     x = torch.zeros((1000, 128), dtype=torch.uint8, device="cuda")
     idx = torch.empty((1000, 2), dtype=torch.int64, device="cuda")
     dist = torch.empty((1000, 2), dtype=torch.int32, device="cuda")

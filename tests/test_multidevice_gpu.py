@@ -205,7 +205,6 @@ def test_misaligned_device_pointers_are_rejected():
     off a 16-byte boundary must come back as SPV_ERR_INVALID, not as a fault."""
     import torch
     from spectavi_amd._lib import clib, SPV_ERR_INVALID
-    from spectavi_amd import device  # noqa: F401  (declares argtypes)
     buf = torch.zeros(1000 * 128 + 64, dtype=torch.uint8, device="cuda")
     x = buf[:1000 * 128]
     idx = torch.empty((1000, 2), dtype=torch.int64, device="cuda")

@@ -121,7 +121,8 @@ def test_invalid_arguments():
     assert clib.spv_last_status() == SPV_ERR_INVALID and not r0.m_data and not ri1.m_data
     with pytest.raises(SpectaviError):
         mvg.image_pair_rectification(P, P, im, im, sampling_factor=0.1)
-    # the device form checks its arguments before any launch (a private function object: clib[name])
+    # the device form checks its arguments before any launch.  A private function object (clib[name]):
+    # the shared prototype takes F as a float64 array, here F and the images are raw addresses and NULL
     dev = clib["spv_rectify_device"]
     dev.restype = ct.c_int
     dev.argtypes = [ct.c_void_p] * 3 + [ct.c_int] * 4 + [ct.c_double] + [ct.c_void_p] * 5

@@ -150,26 +150,14 @@ def test_bad_sizes_raise(feature):
         feature.sift_filter(np.zeros((9000, 1), np.float32))
     out = feature.NdArray(dtype="float32")
     f = clib.spv_sift_filter
-    f.restype = ct.c_int
-    f.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(feature.NdArray)]
     im = np.zeros((4, 4), np.float32)
     assert f(im.ctypes.data, 4, -4, ct.byref(out)) == 1
     assert f(None, 4, 4, ct.byref(out)) == 1
 
 
-def _clib():
-    import ctypes as ct
-    from spectavi_amd._lib import clib
-    clib.spv_sift_set_first_capacity.restype = ct.c_int
-    clib.spv_sift_set_first_capacity.argtypes = [ct.c_int]
-    clib.spv_release_cached_memory.restype = None
-    clib.spv_release_cached_memory.argtypes = []
-    return clib
-
-
 def test_second_pass_gives_the_same_bits(feature):
     """A first table guess below the true count runs the pipeline again into an exact table."""
-    clib = _clib()
+    from spectavi_amd._lib import clib
     im, _ = sur_ogre()
     want, n = feature.sift_table(im, 4096)
     assert n == 1168
@@ -188,7 +176,7 @@ def test_second_pass_releases_the_first_table(feature):
     """The short first table (here 14 000 rows, 7.4 MB) goes back to the pool: after the pool is
     emptied, three calls leave the device's free memory where one call left it."""
     import torch
-    clib = _clib()
+    from spectavi_amd._lib import clib
     im = smooth_random(1, 480, 641)
     try:
         assert clib.spv_sift_set_first_capacity(14000) == 0

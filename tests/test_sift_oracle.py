@@ -3,8 +3,6 @@
 The oracle is anchored to vlfeat: on the reference's test image it reproduces vlfeat's recorded table
 (tests/golden/sift_sur_ogre_table.npz) row for row, the reference's own allclose on the frames
 (reference test/test_feature.py:33-47) and every descriptor value equal."""
-import ctypes as ct
-
 import numpy as np
 import pytest
 
@@ -78,7 +76,6 @@ def test_sift_filter_rejects_non_2d():
 def test_sift_workspace_bytes_rules():
     from spectavi_amd._lib import clib
     f = clib.spv_sift_workspace_bytes
-    f.restype, f.argtypes = ct.c_size_t, [ct.c_int, ct.c_int]
     assert f(0, 10) == 0 and f(10, -1) == 0 and f(8193, 10) == 0
     assert f(310, 233) > 4 * 620 * 466 * 6
     assert f(8192, 8192) > 0

@@ -281,14 +281,7 @@ def next_rows(steps, warmup):
                                    "unit": "GB/s", "frac": nbytes / (ms / max(n, 1) * 1e-3) / 1e9 / HBM_PEAK,
                                    "algorithmic": "672 B per row"},
                       "config": {"workload": "%d x 132 float32" % rows}, "dtype": "f32->u8", "data": "synthetic"}), flush=True)
-    clib.spv_normalize_workspace_bytes.restype = ct.c_size_t
-    clib.spv_normalize_workspace_bytes.argtypes = [ct.c_int]
-    clib.spv_normalize_device.restype = ct.c_int
-    clib.spv_normalize_device.argtypes = [ct.c_void_p, ct.c_int, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p,
-                                          ct.c_size_t, ct.c_void_p]
     out = torch.empty((rows, 144), dtype=torch.float32, device=dev)
-    clib.spv_normalize_workspace_bytes_rows.restype = ct.c_size_t
-    clib.spv_normalize_workspace_bytes_rows.argtypes = [ct.c_int, ct.c_int]
     ws_walk = torch.empty(clib.spv_normalize_workspace_bytes(132), dtype=torch.uint8, device=dev)
     ws_fold = torch.empty(clib.spv_normalize_workspace_bytes_rows(rows, 132), dtype=torch.uint8, device=dev)
     # the same rows as a real SIFT table has them: sub-pixel x, y, scale, angle in (-pi, pi], 128 descriptor values
@@ -324,8 +317,6 @@ def bruteforce_rows(steps, warmup):
     reference test's 1000 x 1000 x 132 call."""
     from spectavi_amd._lib import clib
     import ctypes as ct
-    clib.spv_microbench_valu.restype = ct.c_int
-    clib.spv_microbench_valu.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double)]
     rates = {}
     for op in (7, 8, 10):
         r, c = ct.c_double(0), ct.c_double(0)
@@ -379,8 +370,6 @@ def rectify_rows(steps, warmup):
     import ctypes as ct
     from spectavi_amd._lib import clib, check
     from tests.test_rectify_gpu import image, pair
-    clib.spv_microbench_memory.restype = ct.c_int
-    clib.spv_microbench_memory.argtypes = [ct.c_int, ct.c_size_t, ct.POINTER(ct.c_double)]
     stream = ct.c_double(0)
     check(clib.spv_microbench_memory(0, 1 << 30, ct.byref(stream)))
     rng = np.random.default_rng(1080)
@@ -417,8 +406,6 @@ def sift_rows(steps, warmup):
     from spectavi_amd._lib import clib, check
     from tests import sift_oracle as so
     from tests.sift_cases import smooth_random
-    clib.spv_microbench_memory.restype = ct.c_int
-    clib.spv_microbench_memory.argtypes = [ct.c_int, ct.c_size_t, ct.POINTER(ct.c_double)]
     stream = ct.c_double(0)
     check(clib.spv_microbench_memory(0, 1 << 30, ct.byref(stream)))
     t0 = time.perf_counter()
