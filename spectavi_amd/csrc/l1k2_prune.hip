@@ -27,9 +27,16 @@
 // minimum is displaced exactly once, so k2 ends as the second smallest under any interleaving.
 //
 // Thresholds are shared between workgroups through thr[query] in the workspace (initialised to
-// 0xFFFFFFFF): a workgroup reads it every fourth tile and lowers it with atomicMin when its own second best
-// improves.  Every value ever stored is the second best over a subset of the database, hence >= the
-// final one: WHICH pairs are skipped depends on timing, the result never does.
+// 0xFFFFFFFF): a workgroup reads it every fourth tile, one tile before it uses the value, and lowers it with
+// atomicMin when its own second best improves.  Every value ever stored is the second best over a subset
+// of the database, hence >= the final one: WHICH pairs are skipped depends on timing, the result never does.
+//
+// Waits.  No tile waits for global memory except at the one vmcnt(0) before stage_store, a whole tile after
+// the loads it covers were issued: the B operand is waited for once, before the loop (else the compiler
+// guards each of the 32 MFMAs of every tile with a vmcnt wait, the last of them on the next tile's
+// prefetch), and the threshold loads ride behind the stage loads of the tile before.  The A operand is read
+// from LDS two k-steps ahead of its MFMAs (three 4-register buffers, lgkmcnt(1) between the pairs), and the
+// survivor pass requests its 16 row pieces in two batches of eight.
 //
 // Fallback.  Every wave keeps a running survivor share.  When it exceeds the measured break-even (16 %; 3/4
 // in a workgroup's first tiles; see l1k2_prune_selected) the wave raises a flag, and at the tile's barrier
@@ -39,9 +46,11 @@
 // with the two-minimum protocol.  An in-kernel exact loop (one query per lane, scalar-fed rows) ran at half
 // the tile kernel's rate on ordinary data and was dropped.
 //
-// Register budget: 252 of the 256 VGPRs that two waves per SIMD allow (128 of them the B operand), no
-// scratch; LDS 79880 of the 81920 bytes that two workgroups per CU allow.  Any added live value spills or
-// halves the occupancy: check the ISA after every change.
+// Register budget: all 256 VGPRs that two waves per SIMD allow (128 of them the B operand, 12 the A
+// buffers, 20 the staged tile), no scratch; LDS 79880 of the 81920 bytes that two workgroups per CU allow.
+// Any added live value spills (all 16 survivor pieces in flight at once: 10-15 spilled registers): the ISA
+// is checked after every change by tests/test_l1k2_prune_isa.py (registers, spills, scratch, LDS, and no
+// vmcnt wait between the first and the last MFMA of a tile).
 #include "common.h"
 
 #include <atomic>
@@ -71,6 +80,7 @@ constexpr int kBreakEvenShare = 164;          // 16 %, see l1k2_prune_selected a
 constexpr uint32_t kMaxDist = 128 * 255;
 constexpr int kStatSlots = 16;                // survivor counters, spread to keep the atomics apart
 constexpr int kStatWords = kStatSlots * 4 * 2;
+constexpr int kWaitVm0 = 0x0F70;              // s_waitcnt vmcnt(0), the other counters left alone
 
 struct FeatTable { uint32_t w[256]; };        // phi(a) packed little-endian, one dword per byte value
 
@@ -162,14 +172,26 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       const uint4 *qa = qraw + (qslot + q6) * 8, *xa = xr + i * 8;
       const unsigned long long k2now = k2s[qslot + q6];
       uint32_t d = 0;
+      // The 16 pieces are requested in two batches of eight, each in flight as a whole before its first
+      // use (the accumulators and the A buffers are dead here): two LDS round trips for the rows, not five.
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int j = (k + lane) & 7;
-        const uint4 a = qa[j], b = xa[j];
-        d = __builtin_amdgcn_sad_u8(a.x, b.x, d);
-        d = __builtin_amdgcn_sad_u8(a.y, b.y, d);
-        d = __builtin_amdgcn_sad_u8(a.z, b.z, d);
-        d = __builtin_amdgcn_sad_u8(a.w, b.w, d);
+      for (int h = 0; h < 2; ++h) {
+        uint4 a[4], b[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int j = (4 * h + k + lane) & 7;
+          a[k] = qa[j];
+          b[k] = xa[j];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          d = __builtin_amdgcn_sad_u8(a[k].x, b[k].x, d);
+          d = __builtin_amdgcn_sad_u8(a[k].y, b[k].y, d);
+          d = __builtin_amdgcn_sad_u8(a[k].z, b[k].z, d);
+          d = __builtin_amdgcn_sad_u8(a[k].w, b[k].w, d);
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
       // a key that does not beat the query's second best of this moment never will (k2 only falls):
       // nearly all survivors end here, and the two dependent atomics are left to the few that matter
@@ -184,21 +206,32 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
   };
 
   // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b].  seen[b] is the
-  // smallest shared threshold read so far.
+  // shared threshold read last.  Only atomicMin ever writes thr[], so a later read is never above an earlier
+  // one and simply replaces it (and any value ever read there is a valid bound).  The two loads are issued
+  // a tile ahead of the refresh that uses them, behind that tile's stage loads, and have landed by the
+  // vmcnt(0) before its stage_store: no tile waits for them.  Lanes past the last query read the last
+  // query's threshold, whose features they also carry.
   int tq[2];
   uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+  auto thr_load = [&]() {
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+      seen[b] = __hip_atomic_load(&thr[min(qbase + 32 * b + c, N - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
   auto refresh = [&](bool shared) {
+    uint32_t loc[2];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      const uint32_t loc = (uint32_t)(k2s[qslot + 32 * b + c] >> 32);
-      const int qi = qbase + 32 * b + c;
-      if (shared && qi < N) {
-        const uint32_t glob = __hip_atomic_load(&thr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (loc < glob && g == 0) atomicMin(&thr[qi], loc);
-        seen[b] = min(seen[b], glob);
-      }
+      loc[b] = (uint32_t)(k2s[qslot + 32 * b + c] >> 32);
       // thr = "none yet" keeps every pair: sum >= 128 m - p 32640 always
-      tq[b] = m128 - p * (int)min(min(loc, seen[b]), kMaxDist);
+      tq[b] = m128 - p * (int)min(min(loc[b], seen[b]), kMaxDist);
+    }
+    if (shared && g == 0) {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int qi = qbase + 32 * b + c;
+        if (qi < N && loc[b] < seen[b]) atomicMin(&thr[qi], loc[b]);
+      }
     }
   };
 
@@ -223,27 +256,40 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + g]);
     }
+    thr_load();
+    // The B operand is complete before the loop is entered.  Without this wait the compiler, which cannot
+    // prove on the back edge that these loads have landed, guards every MFMA of every tile with a vmcnt
+    // wait, and the last of them wait for the prefetch of the next tile.
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
 
     for (; tl < ntiles; ++tl) {
       const int row0 = row_begin + tl * kTileRows;
       const bool has_next = tl + 1 < ntiles;
       if (has_next) stage_load(row0 + kTileRows);
+      const bool shared = (tl & 3) == 0;  // the shared thresholds move slowly: every fourth tile is enough
       const int nrows = min(kTileRows, row_end - row0);
       const uint4 *buf = ftile[tl & 1];
-      refresh((tl & 3) == 0);  // the shared thresholds move slowly: every fourth tile is enough
+      refresh(shared);
       if (tl == 0 && __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
         warm = kWarmTilesShared;
         skip_tiles = 0;
       }
+      if ((tl & 3) == 3) thr_load();  // for the next tile; they land behind this tile's work
 
       v16i acc[2];
 #pragma unroll
       for (int v = 0; v < 16; ++v) acc[0][v] = acc[1][v] = 0;
+      // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair
+      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, buf[c * kLdsRowV4 + 2 * ks + g]); };
+      v4i a3[3];
+      a3[0] = lda(0);
+      a3[1] = lda(1);
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
-        const v4i a = __builtin_bit_cast(v4i, buf[c * kLdsRowV4 + 2 * ks + g]);
-        acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[0][ks], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[1][ks], acc[1], 0, 0, 0);
+        if (ks + 2 < 16) a3[(ks + 2) % 3] = lda(ks + 2);
+        acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[0][ks], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[1][ks], acc[1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
       }
 
       // One bit per accumulator register: bit 31 - n of `skip` says that pair n = 16 b + v of this lane is
@@ -443,6 +489,9 @@ int l1k2_prune_last_stats(unsigned long long out[3]) {
 //    workgroup of the early slices sees about twice the average.  A workgroup hands over when its running
 //    share exceeds 16 % (kBreakEvenShare; judged from its 8th tile on with inherited thresholds, from its 256th
 //    without, while its own thresholds settle), or 3/4 right after its first tiles.
+//    Since the waits were taken out of the kernel the tie is at about 11 % (47.0 / 63.8 ms at shares 5.7 / 11.7 %
+//    against 62.0 ms, profiles/r08_prune_breakeven_knobs.jsonl); the rule was left as it is, its cost on inputs
+//    that do not pay has not grown (profiles/r08_prune_breakeven.jsonl).
 constexpr int kPruneMinX = 262144, kPruneMinSlice = 32768;
 
 bool l1k2_prune_possible(int xrows, int yrows, int dim) { return dim == 128 && xrows >= kTileRows && yrows >= 1; }
