@@ -403,17 +403,136 @@ def fuzz_pipeline(seed, budget, only_case=None):
     return n
 
 
+def sift_image(rng, h, w):
+    """One random h x w image of a class of tests/sift_cases.py, scaled by 1/255, 1 or 257 and sometimes
+    shifted below zero: (image float32, description)."""
+    from tests import sift_cases as sc
+    kind = int(rng.integers(0, 9))
+    seed = int(rng.integers(0, 1 << 30))
+    if kind == 0:
+        im, what = sc.smooth_random(seed, h, w, passes=int(rng.integers(0, 4))), "smooth"
+    elif kind == 1:
+        im, what = sc.white_noise(seed, h, w), "u8-noise"
+    elif kind == 2:
+        im, what = sc.white_noise(seed, h, w, binary=True), "binary-noise"
+    elif kind == 3:
+        im, what = sc.grey_levels(sc.smooth_random(seed, h, w), int(rng.choice([2, 4, 8]))), "grey-levels"
+    elif kind == 4:
+        im, what = sc.stretch_clip(sc.smooth_random(seed, h, w, passes=1)), "stretch-clip"
+    elif kind == 5:
+        im, what = sc.checkerboard(h, w, int(rng.choice([2, 3, 8, 13]))), "checkerboard"
+    elif kind == 6:
+        im, what = sc.edge_and_corner(h, w), "edge-corner"
+    elif kind == 7:
+        y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+        im = np.zeros((h, w))
+        for _ in range(int(rng.integers(1, 6))):
+            cx, cy, sg = rng.uniform(0, w), rng.uniform(0, h), float(np.exp(rng.uniform(np.log(1.0), np.log(10.0))))
+            im += rng.choice([-200.0, 200.0]) * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * sg * sg))
+        im, what = (im + 128).astype(np.float32), "blobs"
+    else:
+        src = sc.castle("01") if rng.random() < 0.5 else sc.sur_ogre()[0]   # a crop of a photograph, tiled if short
+        y0, x0 = int(rng.integers(0, src.shape[0])), int(rng.integers(0, src.shape[1]))
+        im = np.take(np.take(src, (y0 + np.arange(h)) % src.shape[0], 0), (x0 + np.arange(w)) % src.shape[1], 1)
+        what = "photo"
+    scale = [np.float32(1) / np.float32(255), np.float32(1), np.float32(257)][int(rng.integers(0, 3))]
+    offset = np.float32(rng.choice([0, 0, -128, -255]))
+    im = np.ascontiguousarray((im.astype(np.float32) + offset) * scale, np.float32)
+    return im, "%s %dx%d scale=%g offset=%g" % (what, h, w, scale, offset)
+
+
+def sift_case(seed, n):
+    """Case n of the SIFT fuzz: (rng, images, description); the first image is the case's own, the others
+    (small) fill a batch."""
+    rng = np.random.default_rng([seed, 9, n])
+
+    def side(hi):
+        return int(np.exp(rng.uniform(0, np.log(hi + 1))))   # log-uniform in 1..hi
+    if rng.random() < 0.15:    # thin: one side up to the limit of 8192, the other at most 16
+        long_, short = (8192 if rng.random() < 0.3 else min(side(8192) + 200, 8192)), int(rng.integers(1, 17))
+        h, w = (short, long_) if rng.random() < 0.5 else (long_, short)
+    else:
+        h, w = side(200), side(200)
+    im, what = sift_image(rng, h, w)
+    ims = [im] + [sift_image(rng, side(60), side(60))[0] for _ in range(int(rng.integers(0, 5)))]
+    return rng, ims, what
+
+
+def fuzz_sift(seed, budget, only_case=None):
+    """sift_filter, device.sift, sift_filter_batch and sift_table (a capacity above, at and below the true
+    count), sometimes with a first table guess below the count, bit for bit against tests/sift_oracle.py."""
+    import torch
+    from spectavi_amd import device
+    from spectavi_amd._lib import SpectaviError, clib
+    from tests import sift_oracle as so
+    t0, n = time.time(), 0 if only_case is None else only_case
+    while time.time() - t0 < budget:
+        rng, ims, what = sift_case(seed, n)
+        entry = ("filter", "device", "batch", "table")[int(rng.integers(0, 4))]
+        want = so.sift(ims[0])
+        rows = len(want)
+        first = int(rng.integers(1, rows + 1)) if rows and rng.random() < 0.3 else 0   # a short first table
+        bad = None
+        try:
+            if first and clib.spv_sift_set_first_capacity(first) != 0:
+                raise SystemExit("SIFT case=%d: spv_sift_set_first_capacity(%d) failed" % (n, first))
+            if entry == "filter":
+                got = [feature.sift_filter(ims[0])]
+            elif entry == "device":
+                got = [device.sift(torch.from_numpy(ims[0]).cuda()).cpu().numpy()]
+            elif entry == "batch":
+                nthread = int(rng.integers(1, 9))                # also more threads than images
+                entry = "batch of %d nthread=%d" % (len(ims), nthread)
+                got = feature.sift_filter_batch(ims, nthread=nthread)
+                if len(got) != len(ims):
+                    bad = "%d tables for %d images" % (len(got), len(ims))
+            else:
+                got = []
+                for cap in (rows + int(rng.integers(1, 50)), rows):
+                    table, cnt = feature.sift_table(ims[0], cap)
+                    if cnt != rows or table.shape != (cap, 132) or table[rows:].any():
+                        bad = "capacity %d: count %d, table %s" % (cap, cnt, table.shape)
+                    got.append(table[:rows])
+                if rows:
+                    cap = int(rng.integers(0, rows))
+                    try:
+                        feature.sift_table(ims[0], cap)
+                        bad = "capacity %d below the count raised nothing" % cap
+                    except SpectaviError as e:
+                        if e.status != 5 or str(rows) not in str(e):    # SPV_ERR_OVERFLOW, naming the true count
+                            bad = "capacity %d below the count: %s" % (cap, e)
+        finally:
+            clib.spv_sift_set_first_capacity(0)
+        wants = [want] * len(got) if entry in ("filter", "device", "table") else [want] + [so.sift(im) for im in ims[1:]]
+        for i, (g, wnt) in enumerate(zip(got, wants)):
+            if bad:
+                break
+            if g.dtype != np.float32 or g.shape != wnt.shape:
+                bad = "image %d: table %s %s, oracle %s" % (i, g.shape, g.dtype, wnt.shape)
+            elif g.tobytes() != wnt.tobytes():
+                r = np.flatnonzero((g.view(np.int32) != wnt.view(np.int32)).any(1))
+                c = np.flatnonzero(g[r[0]].view(np.int32) != wnt[r[0]].view(np.int32))
+                bad = "image %d: %d of %d rows differ, first row %d columns %s: gpu %s oracle %s" % (
+                    i, len(r), len(wnt), r[0], c[:6], g[r[0], c[:6]], wnt[r[0], c[:6]])
+        if bad:
+            raise SystemExit("SIFT MISMATCH seed=%d case=%d %s entry=%s first_capacity=%d: %s" % (seed, n, what, entry, first, bad))
+        n += 1
+        if only_case is not None:
+            break
+    return n
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60.0, help="budget per path")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--only", default="", help="comma list of l1k2,cascade,dlt,ratio,score,normalize,seven_point,ransac_fit,pipeline")
+    ap.add_argument("--only", default="", help="comma list of l1k2,cascade,dlt,ratio,score,normalize,seven_point,ransac_fit,pipeline,sift")
     ap.add_argument("--case", type=int, default=None, help="re-run one case number of the --only path")
     a = ap.parse_args()
     want = set(filter(None, a.only.split(",")))
     for name, fn in (("l1k2", fuzz_l1k2), ("cascade", fuzz_cascade), ("dlt", fuzz_dlt), ("ratio", fuzz_ratio),
                      ("score", fuzz_score), ("normalize", fuzz_normalize), ("seven_point", fuzz_seven_point),
-                     ("ransac_fit", fuzz_ransac_fit), ("pipeline", fuzz_pipeline)):
+                     ("ransac_fit", fuzz_ransac_fit), ("pipeline", fuzz_pipeline), ("sift", fuzz_sift)):
         if want and name not in want:
             continue
         cases = fn(a.seed, a.seconds, a.case)

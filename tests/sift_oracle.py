@@ -108,10 +108,13 @@ def extrema(D):
     return s, y + 1, x + 1
 
 
-def refine(D, s, x, y, w, h):
-    """vlfeat's refinement of one candidate: None or (xn, yn, sn, integer s)."""
+def refine(D, s, x, y, w, h, report=None):
+    """vlfeat's refinement of one candidate: None or (xn, yn, sn, integer s).  `report` (a dict) receives
+    what happened: moved (the sample point left the candidate's pixel), and for a rejected candidate
+    which tests it failed: value, edge (the score), offset, bounds."""
     b = [0.0, 0.0, 0.0]
     dx = dy = 0
+    x0, y0 = x, y
     for _ in range(5):
         x += dx
         y += dy
@@ -164,6 +167,10 @@ def refine(D, s, x, y, w, h):
     xn, yn, sn = x + b[0], y + b[1], s + b[2]
     good = (abs(val) > 0 and score < 12.1 and score >= 0 and abs(b[0]) < 1.5 and abs(b[1]) < 1.5
             and abs(b[2]) < 1.5 and 0 <= xn <= w - 1 and 0 <= yn <= h - 1 and -1 <= sn <= S + 1)
+    if report is not None:
+        report.update(moved=(x, y) != (x0, y0), value=not abs(val) > 0, edge=not (score < 12.1 and score >= 0),
+                      offset=not (abs(b[0]) < 1.5 and abs(b[1]) < 1.5 and abs(b[2]) < 1.5),
+                      bounds=not (0 <= xn <= w - 1 and 0 <= yn <= h - 1 and -1 <= sn <= S + 1))
     return (xn, yn, sn, s) if good else None
 
 
@@ -205,8 +212,8 @@ def mod2pi(x):
     return x
 
 
-def gradient(L):
-    """(mod, ang) float32 [h, w] of one level."""
+def gradient_xy(L):
+    """(gx, gy) float32 [h, w] of one level: central differences, one-sided at the border."""
     gx = np.empty_like(L)
     gy = np.empty_like(L)
     gx[:, 1:-1] = F32(0.5) * (L[:, 2:] - L[:, :-2])
@@ -215,6 +222,12 @@ def gradient(L):
     gy[1:-1] = F32(0.5) * (L[2:] - L[:-2])
     gy[0] = L[1] - L[0]
     gy[-1] = L[-1] - L[-2]
+    return gx, gy
+
+
+def gradient(L):
+    """(mod, ang) float32 [h, w] of one level."""
+    gx, gy = gradient_xy(L)
     mod = fast_sqrt(gx * gx + gy * gy)
     ang = mod2pi((fast_atan2(gy, gx).astype(np.float64) + 2 * math.pi).astype(np.float32))
     return mod, ang.reshape(L.shape)

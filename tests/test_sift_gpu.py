@@ -96,19 +96,29 @@ def test_device_table_feeds_split_and_normalize():
 
 
 def test_striped_follows_reference_stitching(feature):
-    im = smooth_random(7, 200, 150)
-    nthread, buf = 4, 20
-    got = feature.sift_filter_striped(im, nthread=nthread, buffer_size=buf)
-    split = int(np.ceil(200 / float(nthread)))
-    parts = []
-    for iy in range(0, 200, split):
-        lo, hi = iy, min(iy + split, 200)
-        b0, b1 = max(lo - buf, 0), min(hi + buf + 1, 200)
-        t = so.sift(im[b0:b1])
-        t[:, 1] += b0
-        parts.append(t[(t[:, 1] > lo) & (t[:, 1] < hi)])
-    want = np.vstack(parts)
-    assert_tables_match(got, want, "striped")
+    """(height, nthread, buffer_size): the reference's defaults at a small size, no overlap at all, a height
+    that nthread does not divide (a short last stripe), and more threads than rows (one-row stripes)."""
+    for hgt, nthread, buf in ((200, 4, 20), (200, 4, 0), (203, 4, 20), (12, 16, 20), (12, 16, 0)):
+        im = smooth_random(7, hgt, 150)
+        got = feature.sift_filter_striped(im, nthread=nthread, buffer_size=buf)
+        split = int(np.ceil(hgt / float(nthread)))
+        parts, seen = [], {}
+        for iy in range(0, hgt, split):
+            lo, hi = iy, min(iy + split, hgt)
+            b0, b1 = max(lo - buf, 0), min(hi + buf + 1, hgt)
+            if (b0, b1) not in seen:
+                seen[(b0, b1)] = so.sift(im[b0:b1])
+            t = seen[(b0, b1)].copy()
+            t[:, 1] += b0
+            parts.append(t[(t[:, 1] > lo) & (t[:, 1] < hi)])
+        want = np.vstack(parts)
+        assert len(parts) == min(nthread, hgt) and (len(want) > 0) == (not (hgt == 12 and buf == 0))  # two-row stripes: no rows
+        assert_tables_match(got, want, "striped %d rows, nthread %d, buffer %d" % (hgt, nthread, buf))
+
+
+def test_batch_of_no_images(feature):
+    assert feature.sift_filter_batch([]) == [] and feature.sift_filter_batch([], nthread=3) == []
+    assert [t.shape for t in feature.sift_filter_batch([np.full((9, 9), 1, np.float32)], nthread=8)] == [(0, 132)]
 
 
 def test_overflow_reports_true_count(feature):
