@@ -546,6 +546,21 @@ int spv_sift_device(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_b
 
 /* Scratch bytes needed by spv_cascade_device. */
 size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g);
+/* The launch plan spv_cascade_device follows for this shape under the SPECTAVI_CASCADE_* environment
+ * of the moment (MFMA, MFMA4, GROUP, QHIST = 0 switch a form off, SORT = 0 / 1 forces the sorted probe
+ * off / on, RU = 2 selects probe_refine_kernel<1, 2>; all are read on every call).  Host only, touches no device.  out =
+ *   [0]      projection family: 0 project_kernel, 1 project_mfma_kernel, 2 project_mfma4_kernel
+ *   [1], [2] the family's two template parameters: (MC, NT), (CT, FULL) or (CT, NG)
+ *   [3]      GMAX of the query-side projection (the database side always has 1)
+ *   [4]      probe: 0 probe_refine_kernel, 1 probe_table_kernel
+ *   [5], [6] its CPL and RU
+ *   [7]      its WPE                 (0 for probe_refine_kernel)
+ *   [8], [9] its SHIFT and FULL      (0 for probe_refine_kernel)
+ *   [10]     1 if the probe walks the queries sorted by each table's sign code
+ *   [11]     1 if the query histogram is fused into the projection
+ * SPV_ERR_INVALID (out untouched) outside the limits of spv_cascade_device: dim a positive multiple of
+ * 16 up to 2048, m in [1,31], n >= 1, g in [0, min(m,16)], row counts >= 0. */
+int spv_cascade_plan(int xrows, int yrows, int dim, int m, int n, int g, int out[12]);
 /* d_x,d_y float32[rows,dim]; d_dict float32[n,dim,m]; outputs as in section 2
  * (d_ncand may be NULL). */
 int spv_cascade_device(const float *d_x, const float *d_y, int xrows, int yrows, int dim,

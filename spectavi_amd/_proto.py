@@ -107,6 +107,7 @@ PROTOTYPES = {
     "spv_sift_workspace_bytes": (sz, [i, i]),
     "spv_sift_device": (i, [vp, i, i, vp, sz, vp, i, vp, vp]),
     "spv_cascade_workspace_bytes": (sz, [i] * 6),
+    "spv_cascade_plan": (i, [i] * 6 + [pi]),
     "spv_cascade_device": (i, [vp, vp] + [i] * 6 + [vp] * 5 + [sz, vp]),
     "spv_dlt_triangulate_device": (i, _dlt_device),
     "spv_dlt_reprojection_error_device": (i, _dlt_device),

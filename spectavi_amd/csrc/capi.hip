@@ -1335,6 +1335,19 @@ size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, 
   return cascade_workspace_bytes(xrows, yrows, dim, m, n, g);
 }
 
+int spv_cascade_plan(int xrows, int yrows, int dim, int m, int n, int g, int out[12]) {
+  clear_error();
+  if (!out) return set_error(SPV_ERR_INVALID, "null output");
+  SPV_TRY(check_cascade_args(xrows, yrows, dim, m, n, g));
+  if (dim > kCascadeMaxDim)
+    return set_error(SPV_ERR_INVALID, "dim=%d > %d is not supported by the cascade refine kernel", dim, kCascadeMaxDim);
+  const CascadePlan p = cascade_plan(xrows, yrows, dim, m, n, g);
+  const int v[12] = {p.family, p.pa,    p.pb,   p.gmax_q, p.use_group, p.cpl,
+                     p.ru,     p.wpe,   p.shift, p.full,  p.sorted,    p.qhist_fused};
+  std::copy(v, v + 12, out);
+  return SPV_OK;
+}
+
 int spv_l1k2_gathered_device(int ndev, const int *devices, const uint8_t *const *d_x, const uint8_t *const *d_y,
                              int xrows, long long yrows_total, int dim, uint64_t *d_idx, int32_t *d_dist,
                              int transport) {

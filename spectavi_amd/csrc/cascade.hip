@@ -32,6 +32,10 @@
 //                     kernel 6 does not apply -- full-code check (m > 22) or rows wider
 //                     than 256 bytes (up to 2048)
 //
+// Which instantiation of 2, 3, 6 and 7 runs for a shape is decided in one host function,
+// cascade_plan (after the kernels), from the shape and the SPECTAVI_CASCADE_MFMA / MFMA4 / GROUP /
+// QHIST / SORT / RU environment; cascade_run launches what the plan names and spv_cascade_plan exports it.
+//
 // Candidate semantics (closed form of filter_potential_neighbours, :208-227):
 // database row k is a candidate of query i iff for some table j
 //   ((code_j(x_k) ^ sign_j(y_i)) & ~mask_j(y_i)) == 0.
@@ -87,7 +91,7 @@ constexpr int kProjChunk = 16;               // dims staged per step (dim % 16 =
 constexpr int kProjXStride = kProjChunk * 4 + 16;  // bytes per row in LDS: 80 -> conflict-free b128 reads
 
 // NT tables are accumulated per pass over the rows (NT*R*MC accumulators per lane); NT = 2 (the
-// default for n >= 2, see launch_project) reads the float32 rows from HBM exactly once.
+// choice whenever MC <= 24, see cascade_plan) reads the float32 rows from HBM exactly once.
 template <int MC, int NT, bool IS_QUERY, int GMAX>
 __global__ __launch_bounds__(kThreads) void project_kernel(
     const float *__restrict__ rows, int nrows, int dim, int m, int n, int g,
@@ -1301,176 +1305,195 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE, W
   }
 }
 
-struct CascadeLayout {
-  int mc, hb;
-  size_t off_dictp, off_dictm, off_ux, off_uy, off_xcodes, off_ysign, off_ymask, off_bstart,
-      off_order, off_ranks, off_segsum, off_qbstart, off_qorder, off_qranks, off_partial, off_pvisited, total;
+// ---------------------------------------------------------------------------------
+// Host side: the plan -- every choice between kernels, made once from the shape and the knobs -- and
+// the launches it names
+// ---------------------------------------------------------------------------------
+
+// The SPECTAVI_CASCADE_* environment, read on every call (tests switch SORT inside one process).
+// MFMA=0, MFMA4=0, GROUP=0 and QHIST=0 turn a form off where the shape would take it (A/B runs; each
+// forces a form that other shapes select anyway); SORT=0 / 1 forces the sorted probe off / on; RU=2
+// halves the rows in flight of the wave-per-query probe at rows of up to 128 bytes.
+struct CascadeKnobs {
+  bool mfma, mfma4, group, qhist, ru2;
+  int sort;  // -1: by size
 };
 
-CascadeLayout cascade_layout(int xrows, int yrows, int dim, int m, int n) {
-  CascadeLayout L{};
-  L.mc = (m + 3) / 4 * 4;  // accumulators per table: multiples of 4 (one ds_read_b128 each)
-  L.hb = bucket_bits(m);
-  const size_t nb1 = ((size_t)1 << L.hb) + 1;
+CascadeKnobs cascade_knobs() {
+  auto first = [](const char *name) {
+    const char *e = getenv(name);
+    return e ? e[0] : '\0';
+  };
+  const char sort = first("SPECTAVI_CASCADE_SORT");
+  return {first("SPECTAVI_CASCADE_MFMA") != '0', first("SPECTAVI_CASCADE_MFMA4") != '0',
+          first("SPECTAVI_CASCADE_GROUP") != '0', first("SPECTAVI_CASCADE_QHIST") != '0',
+          first("SPECTAVI_CASCADE_RU") == '2', sort == '0' || sort == '1' ? sort - '0' : -1};
+}
+
+}  // namespace
+
+CascadePlan cascade_plan(int xrows, int yrows, int dim, int m, int n, int g) {
+  const CascadeKnobs K = cascade_knobs();
+  CascadePlan P{};
+  P.mc = (m + 3) / 4 * 4;  // accumulators per table: multiples of 4 (one ds_read_b128 each)
+  P.hb = bucket_bits(m);
+  const size_t nb1 = ((size_t)1 << P.hb) + 1;
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
     off += round_up(std::max<size_t>(bytes, 16), 256);
     return o;
   };
-  L.off_dictp = take((size_t)n * dim * L.mc * sizeof(float));
-  L.off_dictm = take((size_t)(dim + 16) * 64 * sizeof(float));  // MFMA layout, at most 64 columns, rows padded to a multiple of 32
-  L.off_ux = take((size_t)xrows * dim);
-  L.off_uy = take((size_t)yrows * dim);
-  L.off_xcodes = take((size_t)n * xrows * sizeof(uint32_t));
-  L.off_ysign = take((size_t)n * yrows * sizeof(uint32_t));
-  L.off_ymask = take((size_t)n * yrows * sizeof(uint32_t));
-  L.off_bstart = take((size_t)2 * n * nb1 * sizeof(uint32_t));  // [n] database tables, then [n] query tables (one scan)
-  L.off_order = take((size_t)n * xrows * sizeof(uint32_t));
-  L.off_ranks = take((size_t)n * xrows * sizeof(uint32_t));
-  L.off_segsum = take((size_t)2 * n * ((nb1 + kScanSeg - 1) / kScanSeg) * sizeof(uint32_t));
+  P.off_dictp = take((size_t)n * dim * P.mc * sizeof(float));
+  P.off_dictm = take((size_t)(dim + 16) * 64 * sizeof(float));  // MFMA layout, at most 64 columns, rows padded to a multiple of 32
+  P.off_ux = take((size_t)xrows * dim);
+  P.off_uy = take((size_t)yrows * dim);
+  P.off_xcodes = take((size_t)n * xrows * sizeof(uint32_t));
+  P.off_ysign = take((size_t)n * yrows * sizeof(uint32_t));
+  P.off_ymask = take((size_t)n * yrows * sizeof(uint32_t));
+  P.off_bstart = take((size_t)2 * n * nb1 * sizeof(uint32_t));  // [n] database tables, then [n] query tables (one scan)
+  P.off_order = take((size_t)n * xrows * sizeof(uint32_t));
+  P.off_ranks = take((size_t)n * xrows * sizeof(uint32_t));
+  P.off_segsum = take((size_t)2 * n * ((nb1 + kScanSeg - 1) / kScanSeg) * sizeof(uint32_t));
   // the probe's per-table query order (counting sort of the queries by sign code) and what a
   // query carries from one table's pass to the next
-  L.off_qbstart = L.off_bstart + (size_t)n * nb1 * sizeof(uint32_t);
-  L.off_qorder = take((size_t)n * yrows * sizeof(uint32_t));
-  L.off_qranks = take((size_t)n * yrows * sizeof(uint32_t));
-  L.off_partial = take((size_t)yrows * 2 * sizeof(uint64_t));
-  L.off_pvisited = take((size_t)yrows * sizeof(int32_t));
-  L.total = off;
-  return L;
-}
+  P.off_qbstart = P.off_bstart + (size_t)n * nb1 * sizeof(uint32_t);
+  P.off_qorder = take((size_t)n * yrows * sizeof(uint32_t));
+  P.off_qranks = take((size_t)n * yrows * sizeof(uint32_t));
+  P.off_partial = take((size_t)yrows * 2 * sizeof(uint64_t));
+  P.off_pvisited = take((size_t)yrows * sizeof(int32_t));
+  P.total = off;
 
-template <bool IS_QUERY>
-void launch_project(int mc, int g, const float *rows, int nrows, int dim, int m, int n,
-                    const float *dictp, uint32_t *codes, uint32_t *masks, uint8_t *img,
-                    uint32_t *counts, uint32_t *ranks, uint32_t hbmask, int nb, hipStream_t stream) {
-  if (nrows <= 0) return;
-  const dim3 grid((nrows + kProjTile - 1) / kProjTile), block(kThreads);
-  constexpr int G1 = IS_QUERY ? 4 : 1, G2 = IS_QUERY ? 16 : 1;
-  // two tables per pass while the accumulators fit (MC <= 24), else one
-#define SPV_LAUNCH_PROJECT(MCV, NTV)                                                           \
-  if (g <= G1)                                                                                  \
-    hipLaunchKernelGGL((project_kernel<MCV, NTV, IS_QUERY, G1>), grid, block, 0, stream, rows,  \
-                       nrows, dim, m, n, g, dictp, codes, masks, img, counts, ranks, hbmask, nb); \
-  else                                                                                          \
-    hipLaunchKernelGGL((project_kernel<MCV, NTV, IS_QUERY, G2>), grid, block, 0, stream, rows,  \
-                       nrows, dim, m, n, g, dictp, codes, masks, img, counts, ranks, hbmask, nb);
-  // two tables per pass while 2 x 2 x MC accumulators fit the register budget (MC <= 24)
-  // Two tables per pass (rows read from HBM once) with one row per lane: 0.47 ms for 1M + 1M rows;
-  // measured alternatives: one table per pass 0.54 ms; two rows per lane 0.58 (one table) / 0.65
-  // (two tables) -- its 77 KB of LDS per workgroup halve the occupancy.
-  // SPECTAVI_CASCADE_NT=1 selects one table per pass.
-  static const bool nt1_env = [] {
-    const char *e = getenv("SPECTAVI_CASCADE_NT");
-    return e && e[0] == '1';
-  }();
-  const bool two = n >= 2 && !nt1_env;
-#define SPV_PROJECT_CASE(MCV)                                             \
-  case MCV:                                                               \
-    if (two && MCV <= 24) {                                               \
-      SPV_LAUNCH_PROJECT(MCV, (MCV <= 24 ? 2 : 1))                        \
-    } else {                                                              \
-      SPV_LAUNCH_PROJECT(MCV, 1)                                          \
-    }                                                                     \
-    break;
-  switch (mc) {
-    SPV_PROJECT_CASE(4)
-    SPV_PROJECT_CASE(8)
-    SPV_PROJECT_CASE(12)
-    SPV_PROJECT_CASE(16)
-    SPV_PROJECT_CASE(20)
-    SPV_PROJECT_CASE(24)
-    SPV_PROJECT_CASE(28)
-    default:
-      SPV_LAUNCH_PROJECT(32, 1)
-      break;
+  // Projection: on the matrix cores when the n*m hyperplanes fit 64 columns, else on the VALU.
+  const long long nm = (long long)n * m;
+  const bool on_mfma = K.mfma && nm <= 64;
+  const bool whole_chunks = dim % kMfmaChunk == 0;
+  const int left = (int)(nm % 16);
+  if (on_mfma && K.mfma4 && whole_chunks && dim <= 512 && left >= 1 && left <= 8) {
+    // 1..8 columns beyond whole 16-column tiles (the default 2 x 17): left-over columns on 4x4x1 MFMAs
+    P.family = 2;
+    P.pa = (int)(nm / 16);
+    P.pb = (left + 3) / 4;
+    P.gmax_q = g <= 2 ? 2 : 16;
+  } else if (on_mfma) {
+    P.family = 1;
+    P.pa = (int)((nm + 15) / 16);
+    P.pb = whole_chunks;
+    P.gmax_q = g <= 2 ? 2 : g <= 4 ? 4 : 16;
+  } else {
+    // Two tables per pass (rows read from HBM once, an odd last pass included) while 2 x MC
+    // accumulators fit the register budget (MC <= 24), with one row per lane: 0.47 ms for 1M + 1M
+    // rows; measured alternatives: one table per pass 0.54 ms; two rows per lane 0.58 (one table) /
+    // 0.65 (two tables) -- its 77 KB of LDS per workgroup halve the occupancy.
+    P.family = 0;
+    P.pa = P.mc;
+    P.pb = P.mc <= 24 ? 2 : 1;
+    P.gmax_q = g <= 4 ? 4 : 16;
   }
-#undef SPV_PROJECT_CASE
-#undef SPV_LAUNCH_PROJECT
-}
+  P.proj_rows = P.family == 0 ? kProjTile : kThreads;
 
-// Matrix-core projection: applies when the n*m hyperplanes fit 64 columns.
-inline bool project_mfma_applies(int m, int n) {
-  static const bool off = [] {
-    const char *e = getenv("SPECTAVI_CASCADE_MFMA");
-    return e && e[0] == '0';
-  }();
-  return !off && (long long)n * m <= 64;
-}
-
-template <bool IS_QUERY>
-void launch_project_mfma(int g, const float *rows, int nrows, int dim, int m, int n, const float *dictm,
-                         uint32_t *codes, uint32_t *masks, uint8_t *img, uint32_t *counts,
-                         uint32_t *ranks, uint32_t hbmask, int nb, hipStream_t stream) {
-  if (nrows <= 0) return;
-  const int ct = (n * m + 15) / 16;
-  const dim3 grid((nrows + kThreads - 1) / kThreads), block(kThreads);
-  constexpr int G0 = IS_QUERY ? 2 : 1, G1 = IS_QUERY ? 4 : 1, G2 = IS_QUERY ? 16 : 1;
-  const bool full = dim % kMfmaChunk == 0;
-  // 1..8 columns beyond whole 16-column tiles (the default 2 x 17): left-over columns on 4x4x1 MFMAs
-  {
-    const int nm = n * m, ctm = nm / 16, left = nm % 16, ng = (left + 3) / 4;
-    static const bool off4 = [] {
-      const char *e = getenv("SPECTAVI_CASCADE_MFMA4");
-      return e && e[0] == '0';
-    }();
-    if (!off4 && full && dim <= 512 && left >= 1 && left <= 8) {
-#define SPV_LAUNCH_M4(CTV, NGV)                                                                        \
-  if (g <= G0)                                                                                         \
-    hipLaunchKernelGGL((project_mfma4_kernel<CTV, NGV, IS_QUERY, G0>), grid, block,                    \
-                       (size_t)(NGV) * dim * 16, stream, rows,                                         \
-                       nrows, dim, m, n, g, dictm, codes, masks, img, counts, ranks, hbmask, nb);      \
-  else                                                                                                 \
-    hipLaunchKernelGGL((project_mfma4_kernel<CTV, NGV, IS_QUERY, G2>), grid, block,                    \
-                       (size_t)(NGV) * dim * 16, stream, rows,                                         \
-                       nrows, dim, m, n, g, dictm, codes, masks, img, counts, ranks, hbmask, nb)
-      switch (ctm * 2 + (ng - 1)) {
-        case 0: SPV_LAUNCH_M4(0, 1); break;
-        case 1: SPV_LAUNCH_M4(0, 2); break;
-        case 2: SPV_LAUNCH_M4(1, 1); break;
-        case 3: SPV_LAUNCH_M4(1, 2); break;
-        case 4: SPV_LAUNCH_M4(2, 1); break;
-        case 5: SPV_LAUNCH_M4(2, 2); break;
-        case 6: SPV_LAUNCH_M4(3, 1); break;
-        default: SPV_LAUNCH_M4(3, 2); break;
-      }
-#undef SPV_LAUNCH_M4
-      return;
+  // Probe: the group-per-query kernel unless the full-code check is needed (m > bucket bits) or rows
+  // are wider than 256 bytes; otherwise the wave-per-query kernel.  The group kernel walks the
+  // queries table by table in the order of that table's sign code when the input is large enough for
+  // the order to matter (the per-table counting sorts and passes cost a dozen small launches).
+  const int cpl = (dim / 16 + 7) / 8;
+  P.use_group = K.group && m <= P.hb && cpl <= 2;
+  P.sorted = P.use_group && xrows > 0 && (K.sort >= 0 ? K.sort == 1 : (n <= 8 && (long long)yrows >= 65536));
+  // query histogram + ranks: fused into the matrix-core projection's epilogue (+0.05 ms on the query
+  // pass at 1M rows: every wave ends on the round trip of its returning atomics) or, with QHIST=0
+  // and always on the VALU path, a kernel of their own after it (+0.10 ms)
+  P.qhist_fused = P.sorted && K.qhist && P.family != 0;
+  if (P.use_group) {
+    while ((1 << P.dshift) < dim) ++P.dshift;
+    P.nblk = (yrows + kThreads / 8 - 1) / (kThreads / 8);
+    P.per_xcd = P.sorted ? (P.nblk + 7) / 8 : 0;
+    P.probe_grid = P.sorted ? 8 * P.per_xcd : P.nblk;
+    if (cpl == 1) {
+      // rows of up to 128 bytes: eight rows in flight per group, lane s owning candidate s after the
+      // transposing reduce (69 VGPRs, seven waves per SIMD): 0.90 ms per 1M queries against 0.98 for
+      // four rows in flight with every lane reducing every candidate (59 VGPRs, eight waves;
+      // profiles/r03_cascade_variants.txt has the earlier builds)
+      P.cpl = 1, P.ru = 8, P.wpe = 7;
+      // row offsets by shift: dim 16, 32, 64 and SIFT's 128 (FULL: the benchmark's shape), unless
+      // the image has 4 GiB or more; by multiplication at dim 48, 80, 96, 112
+      P.shift = (1 << P.dshift) == dim && (unsigned long long)xrows * (unsigned)dim < (1ull << 32);
+      P.full = P.shift && dim == 128;
+    } else {
+      P.cpl = 2, P.ru = 4, P.wpe = 6;  // dim 144 .. 256 (80 VGPRs)
     }
+  } else {
+    P.probe_grid = (yrows + kThreads / 64 - 1) / (kThreads / 64);
+    // rows up to 128, 256, 512, 1024 and 2048 bytes, the widest the L1 kernels take as well
+    P.cpl = cpl <= 2 ? cpl : cpl <= 4 ? 4 : cpl <= 8 ? 8 : 16;
+    // RU=2 at rows of up to 128 bytes: 1.16 ms against 1.32 for 1M x 1M, m = 24 on uniform rows (1.1
+    // candidates per query; RU 8 took 1.94 and is gone): profiles/r10_cascade_ru_ab.txt
+    P.ru = P.cpl == 1 && K.ru2 ? 2 : P.cpl <= 2 ? 4 : P.cpl == 4 ? 2 : 1;
   }
-#define SPV_LAUNCH_ONE(CTV, GV, FULLV)                                                               \
-  hipLaunchKernelGGL((project_mfma_kernel<CTV, IS_QUERY, GV, FULLV>), grid, block, 0, stream, rows,  \
-                     nrows, dim, m, n, g, dictm, codes, masks, img, counts, ranks, hbmask, nb)
-#define SPV_LAUNCH_MFMA(CTV)                                                                         \
-  case CTV:                                                                                          \
-    if (g <= G0) {                                                                                   \
-      if (full) SPV_LAUNCH_ONE(CTV, G0, true);                                                       \
-      else SPV_LAUNCH_ONE(CTV, G0, false);                                                           \
-    } else if (g <= G1) {                                                                            \
-      if (full) SPV_LAUNCH_ONE(CTV, G1, true);                                                       \
-      else SPV_LAUNCH_ONE(CTV, G1, false);                                                           \
-    } else {                                                                                         \
-      if (full) SPV_LAUNCH_ONE(CTV, G2, true);                                                       \
-      else SPV_LAUNCH_ONE(CTV, G2, false);                                                           \
-    }                                                                                                \
-    break;
-  switch (ct) {
-    SPV_LAUNCH_MFMA(1)
-    SPV_LAUNCH_MFMA(2)
-    SPV_LAUNCH_MFMA(3)
-    default:
-      SPV_LAUNCH_MFMA(4)
+  return P;
+}
+
+size_t cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g) {
+  return cascade_plan(xrows, yrows, dim, m, n, g).total;
+}
+
+namespace {
+
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals v, if there is one.
+template <int... Vs, typename F>
+void pick(int v, F f) {
+  ((v == Vs ? f(std::integral_constant<int, Vs>{}) : void()), ...);
+}
+
+// pick over a projection family's query-side GMAX values QGs; the database side has GMAX 1 alone.
+template <bool IS_QUERY, int... QGs, typename F>
+void pick_gmax(int gmax_q, F f) {
+  if constexpr (IS_QUERY) pick<QGs...>(gmax_q, f);
+  else f(std::integral_constant<int, 1>{});
+}
+
+// The plan's projection over the database rows or the query rows.  False if the plan names no
+// instantiation.
+template <bool IS_QUERY>
+bool launch_project(const CascadePlan &P, const float *rows, int nrows, int dim, int m, int n, int g,
+                    const float *dict, uint32_t *codes, uint32_t *masks, uint8_t *img, uint32_t *counts,
+                    uint32_t *ranks, uint32_t hbmask, int nb, hipStream_t stream) {
+  if (nrows <= 0) return true;
+  const dim3 grid((nrows + P.proj_rows - 1) / P.proj_rows), block(kThreads);
+  bool launched = false;
+  auto go = [&](auto kernel, size_t lds) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, rows, nrows, dim, m, n, g, dict, codes, masks, img,
+                       counts, ranks, hbmask, nb);
+    launched = true;
+  };
+  if (P.family == 0) {
+    pick<4, 8, 12, 16, 20, 24, 28, 32>(P.pa, [&](auto MC) {
+      constexpr int mc = decltype(MC)::value;
+      pick_gmax<IS_QUERY, 4, 16>(P.gmax_q, [&](auto G) {
+        go(project_kernel<mc, (mc <= 24 ? 2 : 1), IS_QUERY, decltype(G)::value>, 0);
+      });
+    });
+  } else if (P.family == 1) {
+    pick<1, 2, 3, 4>(P.pa, [&](auto CT) {
+      pick_gmax<IS_QUERY, 2, 4, 16>(P.gmax_q, [&](auto G) {
+        constexpr int ct = decltype(CT)::value, gmax = decltype(G)::value;
+        if (P.pb) go(project_mfma_kernel<ct, IS_QUERY, gmax, true>, 0);
+        else go(project_mfma_kernel<ct, IS_QUERY, gmax, false>, 0);
+      });
+    });
+  } else {
+    pick<0, 1, 2, 3>(P.pa, [&](auto CT) {
+      pick<1, 2>(P.pb, [&](auto NG) {
+        pick_gmax<IS_QUERY, 2, 16>(P.gmax_q, [&](auto G) {
+          constexpr int ng = decltype(NG)::value;  // the left-over hyperplanes' LDS table [dim/4][4][4] per group
+          go(project_mfma4_kernel<decltype(CT)::value, ng, IS_QUERY, decltype(G)::value>, (size_t)ng * dim * 16);
+        });
+      });
+    });
   }
-#undef SPV_LAUNCH_ONE
-#undef SPV_LAUNCH_MFMA
+  return launched;
 }
 
 }  // namespace
-
-size_t cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g) {
-  (void)g;
-  return cascade_layout(xrows, yrows, dim, m, n).total;
-}
 
 int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int dim, int m, int n,
                 int g, const float *d_dict, uint64_t *d_idx, float *d_dist, int32_t *d_ncand,
@@ -1480,10 +1503,9 @@ int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int di
     return set_error(SPV_ERR_INVALID, "null device pointer");
   if (g > 16) return set_error(SPV_ERR_INVALID, "num_candidate_neighbours g=%d > 16", g);
   // before anything is enqueued: rows wider than the refine kernels take, misaligned bases
-  const int cpl = (dim / 16 + 7) / 8;
-  if (cpl > 16)
-    return set_error(SPV_ERR_INVALID, "dim=%d > 2048 is not supported by the cascade refine kernel",
-                     dim);
+  if (dim > kCascadeMaxDim)
+    return set_error(SPV_ERR_INVALID, "dim=%d > %d is not supported by the cascade refine kernel", dim,
+                     kCascadeMaxDim);
   if ((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_y) |
        reinterpret_cast<uintptr_t>(d_dict) | reinterpret_cast<uintptr_t>(d_ws)) & 15)
     return set_error(SPV_ERR_INVALID, "device pointers must be 16-byte aligned (x %p, y %p, dict %p, ws %p)",
@@ -1491,76 +1513,42 @@ int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int di
   if ((reinterpret_cast<uintptr_t>(d_idx) & 7) || (reinterpret_cast<uintptr_t>(d_dist) & 3) ||
       (reinterpret_cast<uintptr_t>(d_ncand) & 3))
     return set_error(SPV_ERR_INVALID, "output pointers must be aligned to their element size");
-  const CascadeLayout L = cascade_layout(xrows, yrows, dim, m, n);
-  if (!d_ws || ws_bytes < L.total)
-    return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, L.total);
+  const CascadePlan P = cascade_plan(xrows, yrows, dim, m, n, g);
+  if (!d_ws || ws_bytes < P.total)
+    return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, P.total);
   uint8_t *ws = static_cast<uint8_t *>(d_ws);
-  float *dictp = reinterpret_cast<float *>(ws + L.off_dictp);
-  uint8_t *ux = ws + L.off_ux;
-  uint8_t *uy = ws + L.off_uy;
-  uint32_t *xcodes = reinterpret_cast<uint32_t *>(ws + L.off_xcodes);
-  uint32_t *ysign = reinterpret_cast<uint32_t *>(ws + L.off_ysign);
-  uint32_t *ymask = reinterpret_cast<uint32_t *>(ws + L.off_ymask);
-  uint32_t *bstart = reinterpret_cast<uint32_t *>(ws + L.off_bstart);
-  uint32_t *order = reinterpret_cast<uint32_t *>(ws + L.off_order);
-  uint32_t *ranks = reinterpret_cast<uint32_t *>(ws + L.off_ranks);
-  const int nb = 1 << L.hb;
+  uint8_t *ux = ws + P.off_ux;
+  uint8_t *uy = ws + P.off_uy;
+  uint32_t *xcodes = reinterpret_cast<uint32_t *>(ws + P.off_xcodes);
+  uint32_t *ysign = reinterpret_cast<uint32_t *>(ws + P.off_ysign);
+  uint32_t *ymask = reinterpret_cast<uint32_t *>(ws + P.off_ymask);
+  uint32_t *bstart = reinterpret_cast<uint32_t *>(ws + P.off_bstart);
+  uint32_t *order = reinterpret_cast<uint32_t *>(ws + P.off_order);
+  uint32_t *ranks = reinterpret_cast<uint32_t *>(ws + P.off_ranks);
+  uint32_t *qbstart = reinterpret_cast<uint32_t *>(ws + P.off_qbstart);
+  uint32_t *qorder = reinterpret_cast<uint32_t *>(ws + P.off_qorder);
+  uint32_t *qranks = reinterpret_cast<uint32_t *>(ws + P.off_qranks);
+  const int nb = 1 << P.hb;
   const uint32_t hbmask = (uint32_t)nb - 1;
 
-  // The probe walks the queries table by table in the order of that table's sign code when the
-  // group kernel applies and the input is large enough for the order to matter (the per-table
-  // counting sorts and passes cost a dozen small launches); SPECTAVI_CASCADE_SORT=0 / 1 force it
-  // off / on (A/B runs, and the fuzz run covers both forms: same results).
-  const int sort_env = [] {  // read per call: tests switch it inside one process
-    const char *e = getenv("SPECTAVI_CASCADE_SORT");
-    return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
-  }();
-  static const bool group_env = [] {
-    const char *e = getenv("SPECTAVI_CASCADE_GROUP");
-    return !(e && e[0] == '0');
-  }();
-  const bool use_group = group_env && m <= L.hb && cpl <= 2;
-  const bool sorted = use_group && xrows > 0 &&
-                      (sort_env >= 0 ? sort_env == 1 : (n <= 8 && (long long)yrows >= 65536));
-  uint32_t *qbstart = reinterpret_cast<uint32_t *>(ws + L.off_qbstart);
-  uint32_t *qorder = reinterpret_cast<uint32_t *>(ws + L.off_qorder);
-  uint32_t *qranks = reinterpret_cast<uint32_t *>(ws + L.off_qranks);
-
-  SPV_HIP_CHECK(hipMemsetAsync(bstart, 0, (size_t)(sorted ? 2 : 1) * n * (nb + 1) * sizeof(uint32_t), stream));
-  // query histogram + ranks: fused into the matrix-core projection's epilogue (+0.05 ms on the query
-  // pass at 1M rows: every wave ends on the round trip of its returning atomics) or, with
-  // SPECTAVI_CASCADE_QHIST=0 and always on the VALU path, a kernel of their own after it (+0.10 ms)
-  static const bool qhist_fused = [] {
-    const char *e = getenv("SPECTAVI_CASCADE_QHIST");
-    return !(e && e[0] == '0');
-  }();
-  uint32_t *qcounts = sorted && qhist_fused ? qbstart : nullptr;
-  uint32_t *qrk = sorted && qhist_fused ? qranks : nullptr;
+  SPV_HIP_CHECK(hipMemsetAsync(bstart, 0, (size_t)(P.sorted ? 2 : 1) * n * (nb + 1) * sizeof(uint32_t), stream));
   {
   ProfScope prof("cascade_project", stream);
-  if (project_mfma_applies(m, n)) {
-    float *dictm = reinterpret_cast<float *>(ws + L.off_dictm);
-    const int nc = (n * m + 15) / 16 * 16;
-    hipLaunchKernelGGL(repack_dict_mfma_kernel, dim3(64), dim3(kThreads), 0, stream, d_dict, dictm, n, dim,
-                       m, nc);
-    launch_project_mfma<false>(0, d_x, xrows, dim, m, n, dictm, xcodes, nullptr, ux, bstart, ranks, hbmask,
-                               nb, stream);
-    launch_project_mfma<true>(g, d_y, yrows, dim, m, n, dictm, ysign, ymask, uy, qcounts, qrk, hbmask,
-                              nb, stream);
-    if (sorted && !qhist_fused)
-      hipLaunchKernelGGL(query_rank_kernel, dim3(1024), dim3(256), 0, stream, ysign, yrows, n, hbmask, nb, qbstart,
-                         qranks);
-  } else {
-    hipLaunchKernelGGL(repack_dict_kernel, dim3(64), dim3(kThreads), 0, stream, d_dict, dictp, n, dim,
-                       m, L.mc);
-    launch_project<false>(L.mc, 0, d_x, xrows, dim, m, n, dictp, xcodes, nullptr, ux, bstart, ranks, hbmask,
-                          nb, stream);
-    launch_project<true>(L.mc, g, d_y, yrows, dim, m, n, dictp, ysign, ymask, uy, nullptr, nullptr, hbmask,
-                         nb, stream);
-    if (sorted)
-      hipLaunchKernelGGL(query_rank_kernel, dim3(1024), dim3(256), 0, stream, ysign, yrows, n, hbmask, nb, qbstart,
-                         qranks);
-  }
+  float *dict = reinterpret_cast<float *>(ws + (P.family == 0 ? P.off_dictp : P.off_dictm));
+  if (P.family == 0)
+    hipLaunchKernelGGL(repack_dict_kernel, dim3(64), dim3(kThreads), 0, stream, d_dict, dict, n, dim, m, P.mc);
+  else
+    hipLaunchKernelGGL(repack_dict_mfma_kernel, dim3(64), dim3(kThreads), 0, stream, d_dict, dict, n, dim, m,
+                       (n * m + 15) / 16 * 16);
+  if (!launch_project<false>(P, d_x, xrows, dim, m, n, 0, dict, xcodes, nullptr, ux, bstart, ranks, hbmask, nb,
+                             stream) ||
+      !launch_project<true>(P, d_y, yrows, dim, m, n, g, dict, ysign, ymask, uy, P.qhist_fused ? qbstart : nullptr,
+                            P.qhist_fused ? qranks : nullptr, hbmask, nb, stream))
+    return set_error(SPV_ERR_INTERNAL, "cascade plan names no projection kernel (family %d <%d, %d>, GMAX %d)",
+                     P.family, P.pa, P.pb, P.gmax_q);
+  if (P.sorted && !P.qhist_fused)
+    hipLaunchKernelGGL(query_rank_kernel, dim3(1024), dim3(256), 0, stream, ysign, yrows, n, hbmask, nb, qbstart,
+                       qranks);
   }
   SPV_HIP_CHECK(hipGetLastError());
 
@@ -1569,8 +1557,8 @@ int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int di
   {
     // database and (sorted probe) query histograms sit back to back: one scan over 2n "tables"
     const int nseg = (nb + 1 + kScanSeg - 1) / kScanSeg;
-    const int ntab = sorted ? 2 * n : n;
-    uint32_t *segsum = reinterpret_cast<uint32_t *>(ws + L.off_segsum);
+    const int ntab = P.sorted ? 2 * n : n;
+    uint32_t *segsum = reinterpret_cast<uint32_t *>(ws + P.off_segsum);
     hipLaunchKernelGGL(bucket_segsum_kernel, dim3(nseg, ntab), dim3(256), 0, stream, bstart, nb, nseg, segsum);
     hipLaunchKernelGGL(bucket_segscan_kernel, dim3(ntab), dim3(1024), 0, stream, segsum, nseg);
     hipLaunchKernelGGL(bucket_scan_kernel, dim3(nseg, ntab), dim3(1024), 0, stream, bstart, nb, nseg, segsum);
@@ -1578,98 +1566,44 @@ int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int di
   if (xrows > 0)
     hipLaunchKernelGGL(bucket_fill_kernel, dim3(2048), dim3(kThreads), 0, stream, xcodes, ranks, xrows, n,
                        hbmask, nb, bstart, order);
-  if (sorted)  // the queries' own order, per table, by sign code
+  if (P.sorted)  // the queries' own order, per table, by sign code
     hipLaunchKernelGGL(bucket_fill_kernel, dim3(2048), dim3(kThreads), 0, stream, ysign, qranks, yrows, n,
                        hbmask, nb, qbstart, qorder);
   }
   SPV_HIP_CHECK(hipGetLastError());
 
-  const dim3 grid((yrows + kThreads / 64 - 1) / (kThreads / 64)), block(kThreads);
   ProfScope prof_probe("cascade_probe_refine", stream);
-  // group-per-query kernel unless the full-code check is needed (m > bucket bits) or rows
-  // are wider than 256 bytes; otherwise the wave-per-query kernel
-  if (use_group) {
-    const int nblk = (yrows + kThreads / 8 - 1) / (kThreads / 8);
-    uint64_t *partial = reinterpret_cast<uint64_t *>(ws + L.off_partial);
-    int32_t *pvisited = reinterpret_cast<int32_t *>(ws + L.off_pvisited);
-    const int per_xcd = sorted ? (nblk + 7) / 8 : 0;
-    const dim3 ggrid(sorted ? 8 * per_xcd : nblk);
-    {
-      int dshift = 0;
-      while ((1 << dshift) < dim) ++dshift;
-      const bool shift = (1 << dshift) == dim && (unsigned long long)xrows * (unsigned)dim < (1ull << 32);
-      const int nb1 = nb + 1;
-      for (int ps = 0; ps < n; ++ps) {
-        const uint32_t *qo = sorted ? qorder + (size_t)ps * yrows : nullptr;
-#define SPV_RU(...) SPV_RU_(__VA_ARGS__ __VA_OPT__(,) 4)
-#define SPV_RU_(A, ...) A
-#define SPV_LAUNCH_LEAN(C, W, S, F, ...)                                                                              \
-  hipLaunchKernelGGL((probe_table_kernel<C, SPV_RU(__VA_ARGS__), W, S, F>), ggrid, block, 0, stream, ux, uy, xrows, yrows, dim, dshift, \
-                     g, L.hb, ysign + (size_t)ps * yrows, ymask + (size_t)ps * yrows, bstart + (size_t)ps * nb1,   \
-                     order + (size_t)ps * xrows, qo, nblk, per_xcd, partial, pvisited, ps == 0, ps == n - 1,       \
-                     d_idx, d_dist, d_ncand)
-        if (cpl == 1) {
-          // waves per SIMD: 59 VGPRs and 18 KB of LDS per workgroup = eight waves.  (A first build
-          // wanted 88 VGPRs -- the list fill's unrolled lane constants, see the kernel -- and measured
-          // 1.11 ms per 1M queries at five unspilled waves, 1.21-1.24 spilling at 6-8:
-          // profiles/r03_cascade_variants.txt)
-          // rows of up to 128 bytes: eight rows in flight per group, lane s owning candidate s after the
-          // transposing reduce (69 VGPRs, seven waves): 0.90 ms per 1M queries against 0.98 for four rows
-          // in flight with every lane reducing every candidate (59 VGPRs, eight waves);
-          // SPECTAVI_CASCADE_RU8=0 selects the latter (A/B runs)
-          const bool ru4_env = [] {  // read per call: the tests run both forms in one process
-            const char *e = getenv("SPECTAVI_CASCADE_RU8");
-            return e && e[0] == '0';
-          }();
-          if (ru4_env) {
-            if (shift && dim == 128)
-              SPV_LAUNCH_LEAN(1, 8, true, true);
-            else if (shift)
-              SPV_LAUNCH_LEAN(1, 8, true, false);
-            else
-              SPV_LAUNCH_LEAN(1, 8, false, false);
-          } else if (shift && dim == 128)
-            SPV_LAUNCH_LEAN(1, 7, true, true, 8);     // SIFT-128, the benchmark's shape
-          else if (shift)
-            SPV_LAUNCH_LEAN(1, 7, true, false, 8);    // dim 16, 32, 64
-          else
-            SPV_LAUNCH_LEAN(1, 7, false, false, 8);   // dim 48, 80, 96, 112, or an image of 4 GiB and more
-        } else {
-          SPV_LAUNCH_LEAN(2, 6, false, false);     // dim 144 .. 256 (80 VGPRs)
-        }
-#undef SPV_LAUNCH_LEAN
-#undef SPV_RU
-      }
-      SPV_HIP_CHECK(hipGetLastError());
-      return SPV_OK;
+  const dim3 grid(P.probe_grid), block(kThreads);
+  if (P.use_group) {
+    uint64_t *partial = reinterpret_cast<uint64_t *>(ws + P.off_partial);
+    int32_t *pvisited = reinterpret_cast<int32_t *>(ws + P.off_pvisited);
+    auto go = [&](auto kernel) {  // one pass per table, the two smallest keys carried from pass to pass
+      for (int ps = 0; ps < n; ++ps)
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, ux, uy, xrows, yrows, dim, P.dshift, g, P.hb,
+                           ysign + (size_t)ps * yrows, ymask + (size_t)ps * yrows, bstart + (size_t)ps * (nb + 1),
+                           order + (size_t)ps * xrows, P.sorted ? qorder + (size_t)ps * yrows : nullptr, P.nblk,
+                           P.per_xcd, partial, pvisited, ps == 0, ps == n - 1, d_idx, d_dist, d_ncand);
+    };
+    if (P.cpl == 2) go(probe_table_kernel<2, 4, 6, false, false>);
+    else if (P.full) go(probe_table_kernel<1, 8, 7, true, true>);
+    else if (P.shift) go(probe_table_kernel<1, 8, 7, true, false>);
+    else go(probe_table_kernel<1, 8, 7, false, false>);
+  } else {
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, stream, ux, uy, xrows, yrows, dim, m, n, g, P.hb, xcodes, ysign,
+                         ymask, bstart, order, d_idx, d_dist, d_ncand);
+    };
+    switch (P.cpl) {
+      case 1:
+        if (P.ru == 2) go(probe_refine_kernel<1, 2>);
+        else go(probe_refine_kernel<1, 4>);
+        break;
+      case 2: go(probe_refine_kernel<2, 4>); break;
+      case 4: go(probe_refine_kernel<4, 2>); break;
+      case 8: go(probe_refine_kernel<8, 1>); break;
+      default: go(probe_refine_kernel<16, 1>); break;
     }
   }
-  const dim3 pgrid(grid.x);
-#define SPV_LAUNCH_PROBE(C, U)                                                                       \
-  hipLaunchKernelGGL((probe_refine_kernel<C, U>), pgrid, block, 0, stream, ux, uy, xrows, yrows, dim, \
-                     m, n, g, L.hb, xcodes, ysign, ymask, bstart, order, d_idx, d_dist,             \
-                     d_ncand)
-  static const int ru_env = [] {
-    const char *e = getenv("SPECTAVI_CASCADE_RU");
-    return e ? atoi(e) : 0;
-  }();
-  if (cpl == 1) {
-    if (ru_env == 2)
-      SPV_LAUNCH_PROBE(1, 2);
-    else if (ru_env == 8)
-      SPV_LAUNCH_PROBE(1, 8);
-    else
-      SPV_LAUNCH_PROBE(1, 4);
-  } else if (cpl == 2) {
-    SPV_LAUNCH_PROBE(2, 4);
-  } else if (cpl <= 4) {
-    SPV_LAUNCH_PROBE(4, 2);
-  } else if (cpl <= 8) {
-    SPV_LAUNCH_PROBE(8, 1);   // rows up to 1024 bytes
-  } else {
-    SPV_LAUNCH_PROBE(16, 1);  // rows up to 2048 bytes, the widest the L1 kernels take as well
-  }
-#undef SPV_LAUNCH_PROBE
   SPV_HIP_CHECK(hipGetLastError());
   return SPV_OK;
 }

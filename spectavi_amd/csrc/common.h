@@ -122,6 +122,27 @@ int bruteforce_run(const void *d_x, const void *d_y, int is_int, int xrows, int 
                    int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
 
 // ---- cascade hash (cascade.hip) -----------------------------------------------------
+constexpr int kCascadeMaxDim = 2048;  // the widest row the refine kernels take
+// Everything cascade_run decides for a shape under the SPECTAVI_CASCADE_* knobs of the moment.
+struct CascadePlan {
+  // workspace layout
+  int mc, hb;  // accumulators per table of the VALU projection (m rounded up to 4); bucket bits
+  size_t off_dictp, off_dictm, off_ux, off_uy, off_xcodes, off_ysign, off_ymask, off_bstart,
+      off_order, off_ranks, off_segsum, off_qbstart, off_qorder, off_qranks, off_partial, off_pvisited, total;
+  // projection: 0 project_kernel<MC, NT>, 1 project_mfma_kernel<CT, FULL>, 2 project_mfma4_kernel<CT, NG>
+  int family, pa, pb;
+  int gmax_q;          // GMAX of the query side (the database side is always 1)
+  int proj_rows;       // rows per workgroup of that kernel
+  bool use_group;      // probe_table_kernel (one 8-lane group per query), else probe_refine_kernel
+  bool sorted;         // the group probe walks the queries in the order of each table's sign code
+  bool qhist_fused;    // sorted: query histogram + ranks in the projection's epilogue, else query_rank_kernel
+  int cpl, ru, wpe;    // the probe's template parameters (wpe, shift, full: probe_table_kernel only)
+  bool shift, full;
+  int dshift;          // ceil(log2(dim))
+  int nblk, per_xcd;   // group probe: query blocks, blocks per XCD range (0: unsorted)
+  unsigned probe_grid;
+};
+CascadePlan cascade_plan(int xrows, int yrows, int dim, int m, int n, int g);  // host only
 size_t cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g);
 int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int dim, int m, int n,
                 int g, const float *d_dict, uint64_t *d_idx, float *d_dist, int32_t *d_ncand,

@@ -143,6 +143,26 @@ def l1k2_plan(xrows, yrows, dim):
     return dict(dim_pad=out[0], q=out[1], slices=out[2], slice_rows=out[3], wide=bool(out[4]))
 
 
+def cascade_plan(xrows, yrows, dim, m, n, g):
+    """The launch plan cascade() follows for this shape under the SPECTAVI_CASCADE_* environment of the
+    moment (spv_cascade_plan; host only, no device touched): dict of family, pa, pb, gmax_q, probe_kind,
+    cpl, ru, wpe, shift, full, sorted, qhist_fused as the header lists them, and the instantiations
+    project_db, project_query and probe spelled as tools/kernel_coverage.py --list prints them."""
+    out = (ct.c_int * 12)()
+    check(clib.spv_cascade_plan(xrows, yrows, dim, m, n, g, out))
+    p = dict(zip(("family", "pa", "pb", "gmax_q", "probe_kind", "cpl", "ru", "wpe"), out[:8]))
+    p.update(zip(("shift", "full", "sorted", "qhist_fused"), map(bool, out[8:])))
+    tf = ("false", "true")
+    name = ("project_kernel", "project_mfma_kernel", "project_mfma4_kernel")[p["family"]]
+    for key, query, gmax in (("project_db", 0, 1), ("project_query", 1, p["gmax_q"])):
+        # project_mfma_kernel<CT, IS_QUERY, GMAX, FULL>; the other two <.., .., IS_QUERY, GMAX>
+        args = (p["pa"], tf[query], gmax, tf[p["pb"]]) if p["family"] == 1 else (p["pa"], p["pb"], tf[query], gmax)
+        p[key] = "%s<%s>" % (name, ", ".join(map(str, args)))
+    p["probe"] = ("probe_table_kernel<%d, %d, %d, %s, %s>" % (p["cpl"], p["ru"], p["wpe"], tf[p["shift"]], tf[p["full"]])
+                  if p["probe_kind"] else "probe_refine_kernel<%d, %d>" % (p["cpl"], p["ru"]))
+    return p
+
+
 def shard_bounds(total, shards):
     """[lo_0, lo_1, ..., total]: the contiguous balanced shards the library itself uses."""
     return [int(clib.spv_shard_lo(int(total), int(shards), r)) for r in range(int(shards) + 1)]

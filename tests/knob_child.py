@@ -1,7 +1,8 @@
 """Child process of tests/test_knobs_gpu.py: runs a short fixed case list against the oracle under
-one of the library's static A/B knobs (SPECTAVI_* variables read once per process, so they cannot
-be switched inside the pytest process).  The parent puts the knob in this process's environment;
-argv[1] names the setting.  Exits 1 on the first mismatch, printing the case.
+one of the library's A/B knobs (SPECTAVI_* variables; SPECTAVI_L1K2_Q is read once per process, so
+it cannot be switched inside the pytest process).  The parent puts the knob in this process's
+environment; argv[1] names the setting.  Before each case the child asks the library's plan
+whether the knob took effect.  Exits 1 on the first mismatch, printing the case.
 
     python tests/knob_child.py <setting>"""
 import ctypes as ct
@@ -14,33 +15,32 @@ if ROOT not in sys.path:
 
 import numpy as np  # noqa: E402
 
-# setting -> (the environment the parent sets, cases).  Cascade cases are (dim, m, n, g); the comment
-# names what the knob makes the library launch.
+# setting -> (the environment the parent sets, kind, cases).  Cascade cases are (dim, m, n, g); the comment
+# names what the knob makes the library launch, PLAN_WANTS what the child asserts of device.cascade_plan.
 SETTINGS = {
-    # VALU projection for n*m <= 64: project_kernel<MC, 1, ..> (n = 1) and <MC, 2, ..>
+    # VALU projection for n*m <= 64: project_kernel<MC, 2, ..>, at n = 1 too (one odd pass)
     "mfma0": ({"SPECTAVI_CASCADE_MFMA": "0"}, "cascade",
               [(128, 2, 1, 1), (128, 8, 1, 2), (64, 12, 1, 5), (144, 16, 1, 3), (128, 20, 1, 6),
                (96, 24, 1, 4), (128, 17, 2, 2), (32, 6, 2, 2)]),
     # left-over columns on the 16-column MFMA tiles instead of 4x4x1: project_mfma_kernel
     "mfma4_0": ({"SPECTAVI_CASCADE_MFMA4": "0"}, "cascade",
                 [(128, 9, 2, 2), (64, 6, 1, 3), (256, 11, 2, 4), (128, 17, 2, 2), (512, 13, 3, 2)]),
-    # one table per pass: project_kernel<MC <= 24, 1, ..>
-    "nt1": ({"SPECTAVI_CASCADE_NT": "1"}, "cascade",
-            [(128, 4, 17, 2), (128, 8, 16, 5), (64, 12, 6, 3), (128, 16, 5, 9), (48, 20, 4, 4), (128, 24, 3, 6)]),
     # wave-per-query probe_refine_kernel<1, 4> / <2, 4> where the group kernel would run
     "group0": ({"SPECTAVI_CASCADE_GROUP": "0"}, "cascade",
                [(16, 4, 2, 2), (48, 9, 2, 3), (128, 8, 2, 2), (144, 8, 4, 3), (256, 10, 2, 4), (128, 17, 2, 2)]),
     # sorted probe with the query histogram in a kernel of its own (query_rank_kernel)
     "qhist0": ({"SPECTAVI_CASCADE_QHIST": "0", "SPECTAVI_CASCADE_SORT": "1"}, "cascade",
                [(128, 10, 2, 2), (128, 17, 2, 2), (64, 6, 1, 3), (144, 8, 4, 3), (32, 16, 2, 1)]),
-    # rows per round of the wave-per-query refine (m > bucket bits, rows <= 128 bytes)
+    # two rows per round of the wave-per-query refine (m > bucket bits, rows <= 128 bytes): probe_refine_kernel<1, 2>
     "ru2": ({"SPECTAVI_CASCADE_RU": "2"}, "cascade", [(128, 25, 2, 3), (64, 23, 2, 2), (32, 30, 2, 5), (96, 24, 1, 4)]),
-    "ru8": ({"SPECTAVI_CASCADE_RU": "8"}, "cascade", [(128, 25, 2, 3), (64, 23, 2, 2), (32, 30, 2, 5), (96, 24, 1, 4)]),
     # queries per lane forced (clamped to what the width allows), small ragged shapes
     "l1k2_q1": ({"SPECTAVI_L1K2_Q": "1"}, "l1k2", 1),
     "l1k2_q2": ({"SPECTAVI_L1K2_Q": "2"}, "l1k2", 2),
     "l1k2_q4": ({"SPECTAVI_L1K2_Q": "4"}, "l1k2", 4),
 }
+
+PLAN_WANTS = {"mfma0": {"family": 0}, "mfma4_0": {"family": 1}, "group0": {"probe_kind": 0},
+              "qhist0": {"sorted": True, "qhist_fused": False}, "ru2": {"probe_kind": 0, "cpl": 1, "ru": 2}}
 
 L1K2_DIMS = (16, 48, 64, 128, 144, 256, 400)
 L1K2_YROWS = (1, 257, 1025)
@@ -51,11 +51,14 @@ def _fail(what):
     sys.exit(1)
 
 
-def run_cascade(cases, oracle):
-    from spectavi_amd import feature
+def run_cascade(cases, wants, oracle):
+    from spectavi_amd import device, feature
     from tests.cascade_variant_cases import cascade_data
     for dim, m, n, g in cases:
         x, y, d = cascade_data(dim, m, n, g, xrows=2000, yrows=700)
+        plan = device.cascade_plan(len(x), len(y), dim, m, n, g)
+        if any(plan[k] != v for k, v in wants.items()):
+            _fail("cascade plan dim=%d m=%d n=%d g=%d: %r, the knob wants %r" % (dim, m, n, g, plan, wants))
         idx, dist, ncand = feature.nn_cascading_hash_with_dict(x, y, d, g=g, return_ncand=True)
         oidx, odist, oncand, _ = oracle.nn_cascading_hash(x, y, m, n, g, d)
         for name, a, b in (("ncand", ncand, oncand), ("dist", dist, odist), ("idx", idx, oidx)):
@@ -97,7 +100,7 @@ def main(setting):
     from oracle import oracle
     oracle.lib()
     if kind == "cascade":
-        run_cascade(cases, oracle)
+        run_cascade(cases, PLAN_WANTS[setting], oracle)
     else:
         run_l1k2(cases, oracle)
     print("all ok: %s" % setting, flush=True)

@@ -373,12 +373,78 @@ def test_l1k2_plan_rejects_bad_shapes():
 
 
 def test_cascade_variant_cases_reach_every_projection_form():
-    """The case table of tests/test_cascade_variants_gpu.py holds one case per query-side projection
-    instantiation the default selection can pick (by the restatement of that selection in
-    tests/cascade_variant_cases.py; a kernel trace checks the library itself:
-    tools/kernel_coverage.py)."""
+    """spv_cascade_plan (host only) on the case table of tests/test_cascade_variants_gpu.py, at that
+    test's own row counts: every case gets the query-side projection instantiation it is written
+    for, and together the cases reach every form the default selection can pick
+    (REACHABLE_QUERY_FORMS in tests/cascade_variant_cases.py), each once.  A retuned threshold in
+    cascade_plan that leaves a kernel without a case fails here, without a GPU."""
+    from spectavi_amd import device
     from tests import cascade_variant_cases as cc
-    targets = [cc.projection_kernels(*c)[1] for c in cc.CASES]
-    assert set(targets) == cc.REACHABLE_QUERY_FORMS and len(targets) == len(set(targets))
-    for dim, m, n, g in cc.CASES:
+    for case in cc.CASES:
+        dim, m, n, g, target = case
         assert dim % 16 == 0 and 1 <= m <= 31 and n >= 1 and 0 <= g <= min(m, 16)
+        plan = device.cascade_plan(3000, 1100, dim, m, n, g)
+        assert plan["project_query"] == target, (cc.case_id(case), plan)
+        assert plan["project_db"] == cc.database_form(target), (cc.case_id(case), plan)
+    targets = [c[4] for c in cc.CASES]
+    assert set(targets) == cc.REACHABLE_QUERY_FORMS and len(targets) == len(set(targets))
+
+
+def test_cascade_plan_names_only_shipped_kernels(monkeypatch):
+    """spv_cascade_plan over a grid of shapes: every kernel it names is in the static sets of
+    tests/cascade_variant_cases.py (the instantiations cascade.hip ships), and the probes named are
+    all of PROBE_FORMS but the one only SPECTAVI_CASCADE_RU=2 selects -- probe_table_kernel<1, 8, 7, false, false>, which also serves power-of-two
+    widths over images of 4 GiB and more, is reached at the widths that are no power of two; the
+    4 GiB rule itself is asked for directly.  Bad shapes are SPV_ERR_INVALID."""
+    from spectavi_amd import _lib, device
+    from tests import cascade_variant_cases as cc
+    for k in ("MFMA", "MFMA4", "GROUP", "QHIST", "SORT", "RU"):
+        monkeypatch.delenv("SPECTAVI_CASCADE_" + k, raising=False)
+    probes, queries = set(), set()
+    for dim in list(range(16, 257, 16)) + [512, 1024, 2048]:
+        for m in range(1, 32):
+            for n in (1, 2, 3, 4, 9, 17):
+                for g in sorted({0, 2, 4, 5, min(m, 16)}):
+                    if g > m:
+                        continue
+                    for xrows, yrows in ((0, 1), (3000, 1100), (70000, 70000)):
+                        plan = device.cascade_plan(xrows, yrows, dim, m, n, g)
+                        assert plan["project_query"] in cc.REACHABLE_QUERY_FORMS, plan
+                        assert plan["project_db"] == cc.database_form(plan["project_query"]), plan
+                        assert plan["probe"] in cc.PROBE_FORMS, plan
+                        assert plan["probe_kind"] == plan["probe"].startswith("probe_table"), plan
+                        assert plan["sorted"] == (plan["probe"].startswith("probe_table") and n <= 8 and yrows >= 65536), plan
+                        assert plan["qhist_fused"] == (plan["sorted"] and plan["family"] != 0), plan
+                        probes.add(plan["probe"])
+                        queries.add(plan["project_query"])
+    assert probes == cc.PROBE_FORMS - cc.KNOB_PROBE_FORMS
+    monkeypatch.setenv("SPECTAVI_CASCADE_RU", "2")
+    assert {device.cascade_plan(3000, 1100, dim, 25, 2, 3)["probe"] for dim in (16, 128, 144)} == \
+        cc.KNOB_PROBE_FORMS | {"probe_refine_kernel<2, 4>"}
+    monkeypatch.delenv("SPECTAVI_CASCADE_RU")
+    assert queries == cc.REACHABLE_QUERY_FORMS
+    assert device.cascade_plan((1 << 25) - 1, 1, 128, 8, 2, 2)["probe"] == "probe_table_kernel<1, 8, 7, true, true>"
+    assert device.cascade_plan(1 << 25, 1, 128, 8, 2, 2)["probe"] == "probe_table_kernel<1, 8, 7, false, false>"
+    out = (ct.c_int * 12)(*([-7] * 12))
+    for dim, m, n, g in ((24, 8, 2, 2), (128, 0, 2, 0), (128, 32, 2, 2), (128, 4, 2, 5), (128, 20, 2, 17), (2064, 8, 2, 2)):
+        assert _lib.clib.spv_cascade_plan(3000, 1100, dim, m, n, g, out) == _lib.SPV_ERR_INVALID, (dim, m, n, g)
+        assert _lib.clib.spv_last_error(), (dim, m, n, g)
+        assert list(out) == [-7] * 12
+        with pytest.raises(_lib.SpectaviError):
+            device.cascade_plan(3000, 1100, dim, m, n, g)
+
+
+def test_cascade_knob_settings_change_the_plan(monkeypatch):
+    """What the children of tests/test_knobs_gpu.py assert before each case, without a GPU: under each
+    cascade setting of tests/knob_child.py the plan of every case shows the form the knob forces."""
+    from spectavi_amd import device
+    from tests.knob_child import PLAN_WANTS, SETTINGS
+    assert set(PLAN_WANTS) == {s for s, (_, kind, _) in SETTINGS.items() if kind == "cascade"}
+    for setting, wants in PLAN_WANTS.items():
+        for k in ("MFMA", "MFMA4", "GROUP", "QHIST", "SORT", "RU"):
+            monkeypatch.delenv("SPECTAVI_CASCADE_" + k, raising=False)
+        for k, v in SETTINGS[setting][0].items():
+            monkeypatch.setenv(k, v)
+        for dim, m, n, g in SETTINGS[setting][2]:
+            plan = device.cascade_plan(2000, 700, dim, m, n, g)
+            assert {k: plan[k] for k in wants} == wants, (setting, dim, m, n, g, plan)

@@ -1,12 +1,13 @@
 """GPU parity of every projection kernel instantiation the cascade's default selection can pick
-(launch_project / launch_project_mfma in spectavi_amd/csrc/cascade.hip), one (dim, m, n, g) per
-query-side instantiation -- the database side of the same case runs the matching <.., false, 1>
-form -- plus the probe forms that only the per-call SPECTAVI_CASCADE_RU8 switch reaches at widths
-that are not a power of two.  Candidate counts, indices and distances bit-exact vs the oracle."""
+(cascade_plan in spectavi_amd/csrc/cascade.hip), one (dim, m, n, g) per query-side instantiation --
+the database side of the same case runs the matching <.., false, 1> form -- plus the non-shift
+probe form at widths that are not a power of two.  Each test first asks the library's own plan
+that it launches what the case is written for.  Candidate counts, indices and distances bit-exact
+vs the oracle."""
 import numpy as np
 import pytest
 
-from tests.cascade_variant_cases import CASES, cascade_data, projection_kernels
+from tests.cascade_variant_cases import CASES, cascade_data, case_id
 
 pytestmark = pytest.mark.gpu
 
@@ -20,22 +21,24 @@ def _check(oracle, x, y, d, m, n, g):
     assert np.array_equal(idx, oidx)
 
 
-@pytest.mark.parametrize("dim,m,n,g", CASES, ids=["%s-%dd-m%dn%dg%d" % ((projection_kernels(*c)[1],) + c)
-                                                  for c in CASES])
-def test_projection_variant_matches_oracle(oracle, dim, m, n, g):
+@pytest.mark.parametrize("dim,m,n,g,target", CASES, ids=[case_id(c) for c in CASES])
+def test_projection_variant_matches_oracle(oracle, dim, m, n, g, target):
+    from spectavi_amd import device
     x, y, d = cascade_data(dim, m, n, g)
+    assert device.cascade_plan(len(x), len(y), dim, m, n, g)["project_query"] == target
     _check(oracle, x, y, d, m, n, g)
 
 
 @pytest.mark.parametrize("dim", [48, 80, 96, 112])
 def test_probe_forms_at_non_power_of_two_widths(oracle, monkeypatch, dim):
-    """Rows of at most 128 bytes whose width is not a power of two take the non-shift probe forms:
-    probe_table_kernel<1, 8, 7, false, false> by default and <1, 4, 8, false, false> with
-    SPECTAVI_CASCADE_RU8=0 (read per call), each in the one-pass and the sorted (per-table) form."""
+    """Rows of at most 128 bytes whose width is not a power of two take the non-shift probe form,
+    probe_table_kernel<1, 8, 7, false, false>, in the one-pass and the sorted (per-table) form
+    (SPECTAVI_CASCADE_SORT, read per call)."""
+    from spectavi_amd import device
     m, n, g = 9, 2, 3
     x, y, d = cascade_data(dim, m, n, g)
     for sort in ("0", "1"):
         monkeypatch.setenv("SPECTAVI_CASCADE_SORT", sort)
-        for ru8 in ("1", "0"):
-            monkeypatch.setenv("SPECTAVI_CASCADE_RU8", ru8)
-            _check(oracle, x, y, d, m, n, g)
+        plan = device.cascade_plan(len(x), len(y), dim, m, n, g)
+        assert plan["probe"] == "probe_table_kernel<1, 8, 7, false, false>" and plan["sorted"] == (sort == "1")
+        _check(oracle, x, y, d, m, n, g)

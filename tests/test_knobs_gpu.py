@@ -1,6 +1,7 @@
-"""The library's static A/B knobs (SPECTAVI_CASCADE_MFMA / MFMA4 / NT / GROUP / QHIST / RU,
-SPECTAVI_L1K2_Q) are read once per process, so each setting runs in a fresh child process
-(tests/knob_child.py) with only that knob added to its environment, against the oracle."""
+"""The library's A/B knobs (SPECTAVI_CASCADE_MFMA / MFMA4 / GROUP / QHIST / RU, SPECTAVI_L1K2_Q): each
+setting runs in a fresh child process (tests/knob_child.py) with only that knob added to its
+environment -- SPECTAVI_L1K2_Q is read once per process -- and the child checks, through the
+library's plan, that the knob changed the launch before it compares against the oracle."""
 import os
 import subprocess
 import sys

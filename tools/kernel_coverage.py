@@ -37,10 +37,10 @@ NOTES = {
         "probe_table_kernel<1, 8, 7, false, false> also serves the non-shift probe of power-of-two widths "
         "for images of 4 GiB and more (xrows * dim >= 2^32); that path is not exercised by any test "
         "(the instantiation itself runs at dims 48..112).",
-        "project_kernel<4, 1|2, true, 16> can never be selected: G = 16 needs g > 4, and g <= m <= 4 at MC 4.",
-        "project_kernel<MC <= 24, 1, ..> (m*n > 64) and project_kernel at m*n <= 64 are reached only with "
-        "SPECTAVI_CASCADE_NT=1 / SPECTAVI_CASCADE_MFMA=0, probe_refine_kernel<1, 2> / <1, 8> only with "
-        "SPECTAVI_CASCADE_RU=2 / 8: tests/test_knobs_gpu.py runs them in child processes.",
+        "project_kernel<4, 2, true, 16> can never be selected: G = 16 needs g > 4, and g <= m <= 4 at MC 4.",
+        "probe_refine_kernel<1, 2> is reached only with SPECTAVI_CASCADE_RU=2 (tests/test_knobs_gpu.py runs it in a "
+        "child process); every other instantiation is one the default selection takes for some shape "
+        "(spv_cascade_plan says which; tests/test_abi.py sweeps it without a GPU).",
     ],
 }
 
