@@ -176,6 +176,8 @@ void nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows,
  * device pow may differ from glibc's by an ulp of the double (int rows: a term whose pow lands an
  * ulp below an integer truncates one lower, so a distance may be up to dim units off).  The int domain is: no int32 overflow
  * in x - y, t or s; outside it, and for NaN / inf inputs, the result is unspecified (no fault).
+ * Finite inputs are always specified: float32 subnormals are kept (in x - y, t and s), and a distance
+ * that overflows to +inf belongs to a real neighbour, which sorts by idx ahead of the missing ones.
  * Result per query: the k smallest (dist, idx) pairs in lexicographic order, ascending -- what the
  * reference's strict-< scan in ascending idx yields where it is defined (it is not on a tie at the
  * k-th place, src/BruteForceNn.h:93-116).  Missing neighbours (xrows < k) fill the end of the row

@@ -359,8 +359,10 @@ int bruteforce_run(const void *d_x, const void *d_y, int is_int, int xrows, int 
     return set_error(SPV_ERR_INVALID, "idx and the workspace must be 8-byte aligned");
   const BruteForcePlan pl = bruteforce_plan(xrows, yrows, k, slices);
   if (pl.slices > 65535) return set_error(SPV_ERR_INVALID, "slices=%d > 65535", pl.slices);
-  if (!d_ws || ws_bytes < pl.part_bytes)
-    return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, pl.part_bytes);
+  // what the kernels touch, and what the header asks of a caller who forces the slice count (the plan's
+  // part_bytes, which spv_bruteforce_workspace_bytes reports, is that rounded up to 256)
+  const size_t need = (size_t)yrows * pl.slices * k * sizeof(uint64_t);
+  if (!d_ws || ws_bytes < need) return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, need);
   uint64_t *part = static_cast<uint64_t *>(d_ws);
   const double pd = (double)p;
   {

@@ -49,7 +49,8 @@ def distances(x, y, p, is_int=False):
             diff = (x[None, :, c].astype(np.int64) - y[:, None, c].astype(np.int64)).astype(np.int32)
             d = diff.astype(np.float32)
         else:
-            d = x[None, :, c].astype(np.float32) - y[:, None, c].astype(np.float32)
+            with np.errstate(over="ignore"):   # finite x - y may overflow to +-inf: inside the contract
+                d = x[None, :, c].astype(np.float32) - y[:, None, c].astype(np.float32)
         with np.errstate(over="ignore", invalid="ignore"):
             out = out + term(d, p, is_int)
     return out

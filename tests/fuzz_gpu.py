@@ -522,17 +522,109 @@ def fuzz_sift(seed, budget, only_case=None):
     return n
 
 
+def bruteforce_case(seed, n):
+    """Case n of the exact k-NN fuzz, reproducible on its own: (x, y, p, k, entry, slices, description).  The
+    values come from a class of tests/bruteforce_value_cases.py, randn or small ints (a three-letter alphabet
+    half of the time: ties); int draws are scaled into the contract's domain (no int32 overflow)."""
+    from tests import bruteforce_value_cases as vc
+    rng = np.random.default_rng([seed, 10, n])
+    is_int = bool(rng.integers(0, 2))
+    p = float(rng.choice([1.0, 2.0, 0.5]))
+    k = int(rng.choice([1, 2, 3, 8, 9, 64, rng.integers(1, 65), rng.integers(1, 65)]))
+    dim = int(rng.choice([1, 3, 4, 31, 32, 33, 255, 256, 257, rng.integers(1, 301), rng.integers(1, 301), rng.integers(1, 301)]))
+    xrows = int(rng.choice([0, 1, k - 1, k, 31, 32, 33, rng.integers(0, 601), rng.integers(0, 601), rng.integers(0, 601)]))
+    yrows = int(rng.choice([0, 1, 255, 256, 257, rng.integers(0, 301), rng.integers(0, 301), rng.integers(0, 301)]))
+    if is_int:
+        cls = str(rng.choice(["i_big", "i_big", "small", "alphabet"]))
+        # the widest span whose worst pair stays inside int32: dim terms of t(2 * span)
+        top = {1.0: (2 ** 31 - 1) // (2 * dim), 2.0: int(np.sqrt((2 ** 31 - 1) / dim)) // 2, 0.5: 2 ** 29}[p]
+        span = max(2, int(top * float(rng.choice([1.0, 0.5, 1.0 / 64]))))
+        for _ in range(8):   # float32 rounds |d| and d * d up as well as down: check, and redraw narrower
+            if cls == "i_big":
+                a = rng.integers(-span, span, (xrows + yrows, dim))
+            else:
+                a = rng.integers(-50, 50, (xrows + yrows, dim)) if cls == "small" else rng.integers(0, 3, (xrows + yrows, dim))
+            a = a.astype(np.int32)
+            if vc.int_domain_bound_ok(a, a[:0], p):
+                break
+            span = max(2, span // 2)
+        else:
+            raise SystemExit("BRUTEFORCE seed=%d case=%d: no int draw inside the domain at dim=%d p=%g" % (seed, n, dim, p))
+        what = "%s(span %d)" % (cls, span) if cls == "i_big" else cls
+    else:
+        cls = str(rng.choice(["huge", "max", "subn", "under", "mixed", "offset", "zeros", "randn", "randn"]))
+        a = vc.randn(rng, xrows + yrows, dim) if cls == "randn" else vc.BY_NAME[cls].gen(rng, xrows + yrows, dim)
+        what = cls
+    x, y = np.ascontiguousarray(a[:xrows]), np.ascontiguousarray(a[xrows:])
+    if xrows and yrows and rng.random() < 0.3:   # exact duplicates of database rows: distance 0, and ties
+        m = min(yrows, 8)
+        y[:m] = x[rng.integers(0, xrows, m)]
+    entry = ("host", "device", "frontend")[int(rng.integers(0, 3))]
+    slices = int(rng.choice([0, 1, 2, 3, 7, 64])) if entry == "device" else 0
+    desc = "%s %s xrows=%d yrows=%d dim=%d k=%d p=%g entry=%s slices=%d" % (
+        "int32" if is_int else "float32", what, xrows, yrows, dim, k, p, entry, slices)
+    return x, y, p, k, entry, slices, desc
+
+
+def fuzz_bruteforce(seed, budget, only_case=None):
+    """nn_bruteforce / nn_bruteforcei through spv_nn_bruteforce, device.bruteforce (forced slice counts) and
+    feature.nn_bruteforce (with and without use_int), p in {1, 2, 0.5}: indices and distance bits equal to
+    tests/bruteforce_oracle.py."""
+    import ctypes as ct
+    import torch
+    from spectavi_amd import device
+    from tests import bruteforce_oracle as bo
+    t0, n = time.time(), 0 if only_case is None else only_case
+    while time.time() - t0 < budget:
+        x, y, p, k, entry, slices, desc = bruteforce_case(seed, n)
+        is_int = x.dtype == np.int32
+        if entry == "host":
+            oi = feature.NdArray(dtype="uint64")
+            od = feature.NdArray(dtype="int32" if is_int else "float32")
+            fn = feature._nn_bruteforcei if is_int else feature._nn_bruteforce
+            fn(x, y, x.shape[0], y.shape[0], x.shape[1], k, p, 0.0, ct.byref(oi), ct.byref(od))
+            feature.check()
+            gi, gd = oi.asarray(), od.asarray()
+        elif entry == "device":
+            ti, td = device.bruteforce(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), k=k, p=p, slices=slices)
+            torch.cuda.synchronize()
+            gi, gd = ti.cpu().numpy().view(np.uint64), td.cpu().numpy()
+        elif is_int:   # the front-end makes the int rows itself: hand it the floats that round to them
+            xf, yf = x.astype(np.float64) / 100, y.astype(np.float64) / 100
+            if not (np.array_equal(np.round(100 * xf).astype("int32"), x) and np.array_equal(np.round(100 * yf).astype("int32"), y)):
+                raise SystemExit("BRUTEFORCE seed=%d case=%d %s: the int rows do not survive / 100" % (seed, n, desc))
+            gi, gd = feature.nn_bruteforce(xf, yf, p=p, k=k, use_int=True)
+        else:
+            gi, gd = feature.nn_bruteforce(x, y, p=p, k=k)
+        wi, wd = bo.nn_bruteforce(x, y, p, k, is_int)
+        bad = None
+        if gi.dtype != np.uint64 or gd.dtype != wd.dtype or gi.shape != wi.shape or gd.shape != wd.shape:
+            bad = "idx %s %s dist %s %s, oracle %s %s" % (gi.shape, gi.dtype, gd.shape, gd.dtype, wd.shape, wd.dtype)
+        else:
+            r = np.flatnonzero((gi != wi).any(1) | (gd.view(np.uint32) != wd.view(np.uint32)).any(1))
+            if r.size:
+                bad = "%d of %d queries differ, first %d: gpu idx %s dist %s, oracle idx %s dist %s" % (
+                    r.size, len(wi), r[0], gi[r[0]], gd[r[0]], wi[r[0]], wd[r[0]])
+        if bad:
+            raise SystemExit("BRUTEFORCE MISMATCH seed=%d case=%d %s: %s" % (seed, n, desc, bad))
+        n += 1
+        if only_case is not None:
+            break
+    return n
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60.0, help="budget per path")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--only", default="", help="comma list of l1k2,cascade,dlt,ratio,score,normalize,seven_point,ransac_fit,pipeline,sift")
+    ap.add_argument("--only", default="", help="comma list of l1k2,cascade,dlt,ratio,score,normalize,seven_point,ransac_fit,pipeline,sift,bruteforce")
     ap.add_argument("--case", type=int, default=None, help="re-run one case number of the --only path")
     a = ap.parse_args()
     want = set(filter(None, a.only.split(",")))
     for name, fn in (("l1k2", fuzz_l1k2), ("cascade", fuzz_cascade), ("dlt", fuzz_dlt), ("ratio", fuzz_ratio),
                      ("score", fuzz_score), ("normalize", fuzz_normalize), ("seven_point", fuzz_seven_point),
-                     ("ransac_fit", fuzz_ransac_fit), ("pipeline", fuzz_pipeline), ("sift", fuzz_sift)):
+                     ("ransac_fit", fuzz_ransac_fit), ("pipeline", fuzz_pipeline), ("sift", fuzz_sift),
+                     ("bruteforce", fuzz_bruteforce)):
         if want and name not in want:
             continue
         cases = fn(a.seed, a.seconds, a.case)

@@ -19,7 +19,7 @@ def fz(oracle):
 
 
 @pytest.mark.parametrize("path,seconds", [("l1k2", 4), ("cascade", 6), ("dlt", 3), ("ratio", 2), ("score", 2),
-                                          ("normalize", 3), ("sift", 8)])
+                                          ("normalize", 3), ("sift", 8), ("bruteforce", 4)])
 def test_random_cases_match_oracle(fz, path, seconds):
     fn = getattr(fz, "fuzz_" + path)
     try:
