@@ -338,7 +338,7 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       // (the next tile uses the other one, and a flag is never lowered), puts itself on the work list of
       // l1k2_tile_kernel, which then computes this (query block, slice) from scratch, and leaves.
       recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
-      const int limit = tl >= warm ? max_share : tl > skip_tiles ? kShareUnit * 3 / 4 : kShareUnit;
+      const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
       if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
       if (has_next) stage_store(ftile[(tl + 1) & 1], xraw[(tl + 1) & 1]);
       __syncthreads();
@@ -537,7 +537,9 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   }();
   // Survivor share (in 1/1024 of a tile's pairs) above which a wave finishes its slice exactly.
   // SPECTAVI_L1K2_PRUNE_SHARE overrides it for measurements (tools/l1k2_prune_breakeven.py): 0 = every
-  // wave leaves the bound after the warm-up tiles, 1024 = never.
+  // wave leaves the bound after the warm-up tiles, 1024 = never.  The 3/4 rule of the first tiles yields to a
+  // larger value, so that 1024 really means never: before, a workgroup whose pairs all survived still left
+  // at its tile 4 and "fallback disabled" measured the exact kernel (profiles/r12_l1k2_prune_shapes.txt).
   static const int max_share = [] {
     const char *v = getenv("SPECTAVI_L1K2_PRUNE_SHARE");
     return (v && *v) ? std::max(0, std::min(kShareUnit, atoi(v))) : kBreakEvenShare;

@@ -2,7 +2,16 @@
 the plain tile kernel (0), against the CPU oracle and each other, bit for bit: more than two database
 slices' worth of rows with a ragged tail, a query count that fills no whole block, and the inputs on
 which a pruning kernel goes wrong (ties, the extreme distances, nothing to prune, duplicates in
-different slices, real descriptors, a database shorter than a slice)."""
+different slices, real descriptors, a database shorter than a slice).
+
+What these shapes reach, read against l1k2_plan(): with 8193 queries and the default 16384 wanted blocks
+the 131109 rows fall into 683 slices of 192 rows, six 32-row tiles of the bound kernel each, the last
+slice 165 rows (six tiles, 5 live rows in the last); "short" into 64-row slices of two tiles and a last
+slice of one tile with 21 rows; "oneslice" is a single slice of two tiles, the second with 8 rows.  The
+children with SPECTAVI_L1K2_BLOCKS=64 add four slices of 1026 tiles (the last 1020, again 5 live rows).
+All of it with one query count, whose last block holds one live query.  The slice lengths in between, every ragged count, the query tails at
+the edges of the MFMA column blocks, the hand-over placed on purpose and the keep rule at equality are
+the business of tests/test_l1k2_prune_shapes_gpu.py and its case table tests/l1k2_prune_cases.py."""
 import os
 import subprocess
 import sys
