@@ -1280,7 +1280,7 @@ int spv_l1k2_plan(int xrows, int yrows, int dim, int out[5]) {
   out[1] = p.q;
   out[2] = p.slices;
   out[3] = p.slice_rows;
-  out[4] = p.dim_pad > 256 ? 1 : 0;  // l1k2_run: widths above 256 take l1k2_wide_kernel
+  out[4] = p.path == kL1K2Wide ? 1 : 0;
   return SPV_OK;
 }
 

@@ -69,19 +69,45 @@ struct ProfScope {
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// ---- L1 2-NN (l1k2.hip) -------------------------------------------------------------
+// ---- L1 2-NN (l1k2.hip, l1k2_prune.hip) ---------------------------------------------
+// The SPECTAVI_L1K2_* variables, read once per process.
+struct L1K2Knobs {
+  int q;             // SPECTAVI_L1K2_Q: queries per lane (1, 2 or 4; anything else: the plan's own choice)
+  int blocks;        // SPECTAVI_L1K2_BLOCKS: workgroups the slicing aims for
+  int prune;         // SPECTAVI_L1K2_PRUNE: the prune mode a process starts with (-1 auto, 0 never, 1 wherever possible)
+  int prune_share;   // SPECTAVI_L1K2_PRUNE_SHARE: hand-over share in 1/1024 (-1: the measured break-even)
+  bool prune_stats;  // SPECTAVI_L1K2_PRUNE_STATS=1: the bound path prints its counters (synchronises)
+};
+const L1K2Knobs &l1k2_knobs();
+
+enum L1K2Path {
+  kL1K2Tile,   // l1k2_tile_kernel<dim_pad / 4, q>
+  kL1K2Wide,   // l1k2_wide_kernel<q>: widths above 256
+  kL1K2Bound,  // l1k2_prune.hip, then l1k2_tile_kernel<32, 2, 128> over its work list: dim 128, where the prune mode says so
+};
+// Everything l1k2_run launches for a shape under the knobs and the prune mode of the moment.  The workspace
+// layout and all that spv_l1k2_plan reports are a function of the shape and the knobs alone: the prune mode
+// only turns kL1K2Tile into kL1K2Bound.
 struct L1K2Plan {
-  int dim_pad;     // kernel row width in bytes (>= dim, zero padded)
+  int dim_pad;     // kernel row width in bytes (>= dim, zero padded); < 0: no kernel takes this width
   int q;           // queries per lane
   int slice_rows;  // database rows per slice (<= 65536)
   int slices;      // number of database slices
   int qblocks;     // query blocks
-  size_t pad_x_bytes, pad_y_bytes;  // padded copies (0 when dim == dim_pad)
-  size_t part_bytes;                // partial top-2 keys
-  size_t feat_x_bytes, feat_y_bytes, thr_bytes;  // l1k2_prune.hip: int8 features and shared thresholds (dim 128 only)
-  size_t total_bytes;
+  bool padded;     // pad_rows_kernel copies both sides to dim_pad first
+  L1K2Path path;
+  int merge_lanes;       // l1k2_merge_kernel<1 | 8 | 64>: lanes per query
+  dim3 grid;             // tile kernel: (query blocks, slices); wide kernel: one XCD-padded row of both
+  size_t wide_lds;       // wide kernel: dynamic LDS bytes
+  dim3 bound_grid;       // l1k2_prune_kernel: (blocks of 256 queries, slices)
+  unsigned work_grid;    // tile kernel over the bound path's work list: kWorkSub blocks for every workgroup there
+  unsigned merge_grid;
+  // workspace: byte offsets, in this order.  Padded copies (empty unless `padded`), partial top-2 keys, then the
+  // bound path's scratch (empty unless dim 128 with >= 32 database rows): int8 features, shared thresholds, counters,
+  // work list {count, -, (query block of 256, slice) ...} of the workgroups that gave the bound up.
+  size_t off_pad_x, off_pad_y, off_part, off_feat_x, off_feat_y, off_thr, off_stats, off_work, total_bytes;
 };
-L1K2Plan l1k2_plan(int xrows, int yrows, int dim);
+L1K2Plan l1k2_plan(int xrows, int yrows, int dim);  // host only
 int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,
              uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
 
@@ -94,17 +120,18 @@ struct L1K2Bound {
 const L1K2Bound &l1k2_bound();                               // host only, built once
 int l1k2_set_prune(int mode);                                // -1 auto, 0 never, 1 wherever possible; returns the mode before
 int l1k2_get_prune();
-void l1k2_prune_forget();                                    // l1k2_run took the tile kernels
+// The bound path's part of a plan whose slicing is done: its scratch from byte `base` of the workspace on, and
+// path / bound_grid where the prune mode takes the path for this shape.  Returns the end of the scratch.
+size_t l1k2_prune_plan(int xrows, int yrows, int dim, size_t base, L1K2Plan *p);
+// features, thresholds and the bound-and-survivor kernel; writes the partial keys l1k2_merge_kernel reads, but
+// for the workgroups on the work list, whose keys l1k2_run has yet to compute with the tile kernel
+int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *ws,
+                   hipStream_t stream);
+// l1k2_run notes where the counters of the calling thread's run lie, or null: it took the tile kernels
+void l1k2_prune_note_run(const void *d_stats, hipStream_t stream);
 // {pairs bounded, survivors, pairs of the exact fallback} of the calling thread's last l1k2_run (zeros: tile kernels);
 // waits for that launch; its workspace must still be allocated
 int l1k2_prune_last_stats(unsigned long long out[3]);
-bool l1k2_prune_selected(int xrows, int yrows, int dim, int slice_rows);  // does l1k2_run take the bound path now
-void l1k2_prune_bytes(int xrows, int yrows, int dim, int slices, size_t *fx_bytes, size_t *fy_bytes, size_t *thr_bytes);
-// features, thresholds and the bound-and-survivor kernel; writes the partial keys l1k2_merge_kernel reads
-// *work_out: {count, -, (query block of 256, slice) ...} of the workgroups that gave the bound up and whose
-// partial keys l1k2_run has yet to compute with the tile kernel; *groups_out: how many there can be
-int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *d_extra,
-                   uint64_t *part, const uint32_t **work_out, int *groups_out, hipStream_t stream);
 
 // ---- exact p-norm k-NN (bruteforce.hip) ---------------------------------------------
 struct BruteForcePlan {

@@ -42,6 +42,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace spv {
 namespace {
@@ -68,41 +69,10 @@ __device__ __forceinline__ void lds_row(uint4 (&dst)[V4], const uint4 *row) {
   for (int c = 0; c < V4; ++c) dst[c] = row[c];
 }
 
-template <int D4, int Q>
-__device__ __forceinline__ void row_update(const uint32_t (&qreg)[Q][D4], const uint4 (&xr)[D4 / 4],
-                                           uint32_t j, uint32_t (&k1)[Q], uint32_t (&k2)[Q]) {
-  // Q independent accumulator chains, interleaved so consecutive v_sad_hi_u8
-  // never depend on each other.
-  uint32_t acc[Q];
-#pragma unroll
-  for (int q = 0; q < Q; ++q) acc[q] = j;
-#pragma unroll
-  for (int c = 0; c < D4 / 4; ++c) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = sad_hi(qreg[q][4 * c + 0], xr[c].x, acc[q]);
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = sad_hi(qreg[q][4 * c + 1], xr[c].y, acc[q]);
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = sad_hi(qreg[q][4 * c + 2], xr[c].z, acc[q]);
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = sad_hi(qreg[q][4 * c + 3], xr[c].w, acc[q]);
-  }
-  // Lazy top-2: a new key enters only if it beats the current second best of
-  // its query.  After the first few hundred rows of a slice that is rare, so the
-  // common case is Q compares and one wave-uniform branch instead of Q x
-  // (v_min + v_med3).  Result-identical to the eager update.
-  bool any = false;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) any |= acc[q] < k2[q];
-  if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q) top2_insert(k1[q], k2[q], acc[q]);
-  }
-}
-
-// Chunked-row form for wide descriptors: the row is consumed as NCH chunks of CH4 = D4/NCH
-// dwords (two for dim 192, four for dim 256) so that only one chunk-sized buffer pair is live
-// next to the 2 x D4 query registers (two queries per lane keep the LDS broadcast amortised)
+// One chunk of a row, C of NCH (CH4 = D4 / NCH dwords), into the Q accumulators: Q independent chains,
+// interleaved so consecutive v_sad_hi_u8 never depend on each other.  Narrow rows are one chunk; wide
+// descriptors are consumed in chunks (two for dim 192, four for dim 256) so that only one chunk-sized buffer
+// pair is live next to the 2 x D4 query registers (two queries per lane keep the LDS broadcast amortised)
 // and the kernel keeps three waves per SIMD.
 template <int D4, int Q, int NCH, int C>
 __device__ __forceinline__ void chunk_accumulate(const uint32_t (&qreg)[Q][D4],
@@ -121,6 +91,9 @@ __device__ __forceinline__ void chunk_accumulate(const uint32_t (&qreg)[Q][D4],
   }
 }
 
+// Lazy top-2: a new key enters only if it beats the current second best of its query.  After the first few
+// hundred rows of a slice that is rare, so the common case is Q compares and one wave-uniform branch instead
+// of Q x (v_min + v_med3).  Result-identical to the eager update.
 template <int Q>
 __device__ __forceinline__ void lazy_top2(const uint32_t (&acc)[Q], uint32_t (&k1)[Q], uint32_t (&k2)[Q]) {
   bool any = false;
@@ -132,10 +105,29 @@ __device__ __forceinline__ void lazy_top2(const uint32_t (&acc)[Q], uint32_t (&k
   }
 }
 
+// One whole row xr with tile-local index j against the lane's Q queries.
+template <int D4, int Q>
+__device__ __forceinline__ void row_update(const uint32_t (&qreg)[Q][D4], const uint4 (&xr)[D4 / 4],
+                                           uint32_t j, uint32_t (&k1)[Q], uint32_t (&k2)[Q]) {
+  uint32_t acc[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) acc[q] = j;
+  chunk_accumulate<D4, Q, 1, 0>(qreg, xr, acc);
+  lazy_top2<Q>(acc, k1, k2);
+}
+
 // Partial-key layout: part[(query * S + slice) * 2 + {0,1}], key = dist<<32 | global idx.
 __device__ __forceinline__ uint64_t widen_key(uint32_t k, uint32_t slice_base) {
   if (k == kKeyNone) return kKey64None;
   return ((uint64_t)(k >> 16) << 32) | (uint64_t)(slice_base + (k & 0xFFFFu));
+}
+
+// The two-minimum protocol of l1k2_prune.hip on a partial pair in memory: old = min(k1, key);
+// min(k2, max(old, key)).  "None" never enters.
+__device__ __forceinline__ void top2_atomic_insert(unsigned long long *k1, unsigned long long *k2, uint64_t key) {
+  if (key == kKey64None) return;
+  const unsigned long long old = atomicMin(k1, (unsigned long long)key);
+  atomicMin(k2, old > key ? old : (unsigned long long)key);
 }
 
 // ---------------------------------------------------------------------------------
@@ -147,13 +139,13 @@ __device__ __forceinline__ uint64_t widen_key(uint32_t k, uint32_t slice_base) {
 // leave the chip a third empty in the last round), and merge their keys into the entry's partial pair, which
 // the workgroup that listed it has set to "none", by the two-minimum protocol of l1k2_prune.hip.
 constexpr int kWorkSub = 8;
-template <int D4, int Q, int kThreads = spv::kThreads>
-__global__ __launch_bounds__(kThreads, 3) void l1k2_tile_kernel(
+template <int D4, int Q, int THREADS = kThreads>
+__global__ __launch_bounds__(THREADS, 3) void l1k2_tile_kernel(
     const uint4 *__restrict__ x, const uint4 *__restrict__ y, int M, int N, int slice_rows,
     int S, uint64_t *part, const uint32_t *__restrict__ work = nullptr) {
   constexpr int V4 = D4 / 4;                                   // 16-byte vectors per row
   constexpr int TILE_V4 = kTileRows * V4;                      // vectors per tile
-  constexpr int NL = (TILE_V4 + kThreads - 1) / kThreads;      // staging loads per thread
+  constexpr int NL = (TILE_V4 + THREADS - 1) / THREADS;      // staging loads per thread
   __shared__ uint4 tile[2][TILE_V4];
 
   const int t = threadIdx.x;
@@ -178,7 +170,7 @@ __global__ __launch_bounds__(kThreads, 3) void l1k2_tile_kernel(
   int qi[Q];
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
-    qi[q] = qb * (kThreads * Q) + q * kThreads + t;
+    qi[q] = qb * (THREADS * Q) + q * THREADS + t;
     const int src = min(qi[q], N - 1);
     const uint4 *yr = y + (size_t)src * V4;
 #pragma unroll
@@ -199,7 +191,7 @@ __global__ __launch_bounds__(kThreads, 3) void l1k2_tile_kernel(
   auto stage_load = [&](int row0) {
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
-      const int e = t + i * kThreads;
+      const int e = t + i * THREADS;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (e < TILE_V4 && row0 + e / V4 < row_end) v = x[(size_t)row0 * V4 + e];
       stage[i] = v;
@@ -208,7 +200,7 @@ __global__ __launch_bounds__(kThreads, 3) void l1k2_tile_kernel(
   auto stage_store = [&](uint4 *dst) {
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
-      const int e = t + i * kThreads;
+      const int e = t + i * THREADS;
       if (e < TILE_V4) dst[e] = stage[i];
     }
   };
@@ -282,14 +274,8 @@ __global__ __launch_bounds__(kThreads, 3) void l1k2_tile_kernel(
       const uint64_t a1 = widen_key(k1[q], (uint32_t)row_begin), a2 = widen_key(k2[q], (uint32_t)row_begin);
       if (work) {
         unsigned long long *d = reinterpret_cast<unsigned long long *>(dst);
-        if (a1 != kKey64None) {
-          const unsigned long long old = atomicMin(&d[0], (unsigned long long)a1);
-          atomicMin(&d[1], old > a1 ? old : (unsigned long long)a1);
-        }
-        if (a2 != kKey64None) {
-          const unsigned long long old = atomicMin(&d[0], (unsigned long long)a2);
-          atomicMin(&d[1], old > a2 ? old : (unsigned long long)a2);
-        }
+        top2_atomic_insert(&d[0], &d[1], a1);
+        top2_atomic_insert(&d[0], &d[1], a2);
       } else {
         dst[0] = a1;
         dst[1] = a2;
@@ -391,7 +377,7 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_wide_kernel(const uint4 *__r
       }
     }
     // ragged end of the row (dim is a multiple of 16, not of 128): one 16-byte group at a time, same
-    // roles -- round 3; before, such rows were zero padded to whole chunks (dim 272 paid for 384)
+    // roles; zero padded to whole chunks instead, dim 272 paid for 384
     for (int v4 = V4full; v4 < V4; ++v4) {
       uint4 qw[Q];
 #pragma unroll
@@ -495,62 +481,95 @@ __global__ __launch_bounds__(kThreads) void pad_rows_kernel(const uint8_t *__res
   }
 }
 
-// Tuning knobs (read once): SPECTAVI_L1K2_Q / SPECTAVI_L1K2_BLOCKS override the plan
-// (tools/l1k2_sweep.py).
-static int env_int(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
+// Small compile-time tables of template arguments.  pick: f(std::integral_constant<int, V>{}), a launch that
+// returns true, for the V among Vs that equals v; false if there is none.  first_at_least: the first V >= v
+// (Vs ascending), else 0.
+template <int... Vs> struct Ints {};
+template <int... Vs, typename F>
+bool pick(Ints<Vs...>, int v, F f) {
+  return (... || (v == Vs && f(std::integral_constant<int, Vs>{})));
+}
+template <int... Vs>
+int first_at_least(Ints<Vs...>, int v) {
+  int r = 0;
+  ((r == 0 && v <= Vs ? r = Vs : 0), ...);
+  return r;
 }
 
-template <int D4, int Q>
-void launch_tile(const uint8_t *x, const uint8_t *y, int M, int N, const L1K2Plan &p,
-                 uint64_t *part, hipStream_t stream) {
-  dim3 grid(p.qblocks, p.slices);
-  hipLaunchKernelGGL((l1k2_tile_kernel<D4, Q>), grid, dim3(kThreads), 0, stream,
-                     reinterpret_cast<const uint4 *>(x), reinterpret_cast<const uint4 *>(y), M, N,
-                     p.slice_rows, p.slices, part);
-}
-
-template <int D4>
-void launch_tile_q(const uint8_t *x, const uint8_t *y, int M, int N, const L1K2Plan &p,
-                   uint64_t *part, hipStream_t stream) {
-  constexpr int QMAX = D4 <= 16 ? 4 : 2;
-  if (p.q >= 4 && QMAX >= 4)
-    launch_tile<D4, (QMAX >= 4 ? 4 : 1)>(x, y, M, N, p, part, stream);
-  else if (p.q >= 2 && QMAX >= 2)
-    launch_tile<D4, (QMAX >= 2 ? 2 : 1)>(x, y, M, N, p, part, stream);
-  else
-    launch_tile<D4, 1>(x, y, M, N, p, part, stream);
-}
+// Row widths in bytes with a tile-kernel instantiation; other dims up to 256 are zero-padded to the next one.
+// (They are better off so than in the wide kernel unpadded: measured 0.55-0.80 of the SAD peak on the true
+// width against 0.51-0.64, dims 48..240, when only {64, 128, 144, 192, 256} existed.)
+using TileWidths = Ints<32, 48, 64, 80, 96, 112, 128, 144, 160, 192, 256>;
 
 // Queries per lane.  Measured on MI355X at 256k x 256k, D=128 (tools/l1k2_sweep.py): Q=2
 // (154 VGPRs, 3 waves/SIMD) beats Q=4 (224 VGPRs, 2 waves/SIMD) by ~3 % and Q=1 by ~15 %.
 // Wide rows (192 / 256) also take Q=2: with one query per lane the broadcast LDS reads, not
 // the SADs, bound the kernel (0.66 of the SAD peak measured at Q=1).
-int max_q_for(int dim_pad) { return dim_pad <= 64 ? 4 : 2; }
+constexpr int max_q_for(int dim_pad) { return dim_pad <= 64 ? 4 : 2; }
+
+struct Operands {  // what every main kernel takes
+  const uint4 *x, *y;
+  int M, N;
+  uint64_t *part;
+  hipStream_t stream;
+};
+
+template <int D4, int Q>
+bool launch_tile(const Operands &o, const L1K2Plan &p) {
+  hipLaunchKernelGGL((l1k2_tile_kernel<D4, Q>), p.grid, dim3(kThreads), 0, o.stream, o.x, o.y, o.M, o.N, p.slice_rows,
+                     p.slices, o.part);
+  return true;
+}
+
+// The instantiation of the plan's q; 4 exists where max_q_for allows it.  (The kernels are emitted in the
+// order of these lists, which is the order they have always had in the code object.)
+template <int D4>
+bool launch_tile_q(const Operands &o, const L1K2Plan &p) {
+  auto go = [&](auto Q) { return launch_tile<D4, decltype(Q)::value>(o, p); };
+  if constexpr (max_q_for(4 * D4) >= 4) return pick(Ints<4, 2, 1>{}, p.q, go);
+  else return pick(Ints<1, 2>{}, p.q, go);
+}
+
+template <int Q>
+bool launch_wide(const Operands &o, const L1K2Plan &p) {
+  hipLaunchKernelGGL((l1k2_wide_kernel<Q>), p.grid, dim3(kThreads), p.wide_lds, o.stream, o.x, o.y, o.M, o.N,
+                     p.dim_pad / 4, p.slice_rows, p.slices, o.part);
+  return true;
+}
 
 }  // namespace
 
-// Kernel row widths that are instantiated; other dims are zero-padded up.
-static int pick_dim_pad(int dim) {
-  static const int kDims[] = {32, 48, 64, 80, 96, 112, 128, 144, 160, 192, 256};
-  // (widths below 256 that are not instantiated are better off padded to the next one than in the wide
-  // kernel unpadded: measured 0.55-0.80 of the SAD peak on the true width against 0.51-0.64, dims 48..240,
-  // when only {64, 128, 144, 192, 256} existed)
-  for (int d : kDims)
-    if (dim <= d) return d;
-  return dim <= kMaxGenericDim ? dim : -1;  // wide-row kernel: any multiple of 16 bytes (whole 128-byte chunks + a ragged end)
+const L1K2Knobs &l1k2_knobs() {
+  static const L1K2Knobs knobs = [] {
+    auto num = [](const char *name, int dflt) {
+      const char *v = getenv(name);
+      return (v && *v) ? atoi(v) : dflt;
+    };
+    L1K2Knobs k;
+    k.q = num("SPECTAVI_L1K2_Q", 0);  // the two tuning knobs of tools/l1k2_sweep.py
+    k.blocks = std::max(1, num("SPECTAVI_L1K2_BLOCKS", 16384));
+    const char *v = getenv("SPECTAVI_L1K2_PRUNE");
+    k.prune = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
+    v = getenv("SPECTAVI_L1K2_PRUNE_SHARE");
+    k.prune_share = (v && *v) ? std::max(0, atoi(v)) : -1;
+    v = getenv("SPECTAVI_L1K2_PRUNE_STATS");
+    k.prune_stats = v && v[0] == '1';
+    return k;
+  }();
+  return knobs;
 }
 
 L1K2Plan l1k2_plan(int xrows, int yrows, int dim) {
   L1K2Plan p{};
-  p.dim_pad = pick_dim_pad(dim);
+  p.dim_pad = first_at_least(TileWidths{}, dim);
+  // above the tile widths the wide kernel takes any multiple of 16 bytes (whole 128-byte chunks + a ragged end)
+  const bool wide = p.dim_pad == 0;
+  if (wide) p.dim_pad = dim <= kMaxGenericDim ? dim : -1;
   if (p.dim_pad < 0 || xrows < 0 || yrows < 0) return p;
-  const bool wide = p.dim_pad > 256;
+  p.padded = p.dim_pad != dim;
+  p.path = wide ? kL1K2Wide : kL1K2Tile;
   const int qmax = wide ? 2 : max_q_for(p.dim_pad);
   const int qlanes = kThreads;  // queries per workgroup per unit of q
-  // queries per lane: as many as registers allow once there are enough queries
-  // to keep >= 512 workgroups of 256 lanes busy without it
   // as many queries per lane as registers allow, unless that leaves too few workgroups
   // (query blocks x possible database slices) to fill the chip
   int q = qmax;
@@ -560,27 +579,31 @@ L1K2Plan l1k2_plan(int xrows, int yrows, int dim) {
     if (qb * smax >= 1024) break;
     q /= 2;
   }
-  static const int q_env = env_int("SPECTAVI_L1K2_Q", 0);
-  if (q_env == 1 || q_env == 2 || q_env == 4) q = std::min(q_env, qmax);
+  const L1K2Knobs &knobs = l1k2_knobs();
+  if (knobs.q == 1 || knobs.q == 2 || knobs.q == 4) q = std::min(knobs.q, qmax);
   p.q = q;
   p.qblocks = std::max(1, (yrows + qlanes * q - 1) / (qlanes * q));
   // database slices: enough workgroups to fill 256 CUs x 2 several times over,
   // each slice a multiple of the tile and <= 65536 rows (16-bit local index)
-  static const int want_blocks = std::max(1, env_int("SPECTAVI_L1K2_BLOCKS", 16384));
-  int s_target = std::max(1, (want_blocks + p.qblocks - 1) / p.qblocks);
+  int s_target = std::max(1, (knobs.blocks + p.qblocks - 1) / p.qblocks);
   long long rows = (xrows + s_target - 1) / s_target;
   rows = (rows + kTileRows - 1) / kTileRows * kTileRows;
   rows = std::min<long long>(std::max<long long>(rows, kTileRows), 65536);
   p.slice_rows = (int)rows;
   p.slices = std::max(1, (int)((xrows + rows - 1) / rows));
-  if (p.dim_pad != dim) {
-    p.pad_x_bytes = round_up((size_t)xrows * p.dim_pad, 256);
-    p.pad_y_bytes = round_up((size_t)yrows * p.dim_pad, 256);
-  }
-  p.part_bytes = round_up((size_t)std::max(yrows, 1) * p.slices * 2 * sizeof(uint64_t), 256);
-  // scratch of the bound path: a function of the shape alone, whether or not the path is switched on
-  l1k2_prune_bytes(xrows, yrows, dim, p.slices, &p.feat_x_bytes, &p.feat_y_bytes, &p.thr_bytes);
-  p.total_bytes = p.pad_x_bytes + p.pad_y_bytes + p.part_bytes + p.feat_x_bytes + p.feat_y_bytes + p.thr_bytes;
+  // the wide kernel decodes its XCD-aware row of blocks itself: query blocks padded to a multiple of 8
+  p.grid = wide ? dim3((unsigned)((p.qblocks + 7) / 8 * 8 * p.slices)) : dim3(p.qblocks, p.slices);
+  p.wide_lds = wide ? (size_t)kWideRows * p.dim_pad : 0;
+  p.merge_lanes = p.slices <= 4 ? 1 : p.slices <= 32 ? 8 : 64;
+  p.merge_grid = (unsigned)(((long long)yrows * p.merge_lanes + kThreads - 1) / kThreads);
+
+  p.off_pad_y = p.padded ? round_up((size_t)xrows * p.dim_pad, 256) : 0;
+  p.off_part = p.off_pad_y + (p.padded ? round_up((size_t)yrows * p.dim_pad, 256) : 0);
+  p.off_feat_x = p.off_part + round_up((size_t)std::max(yrows, 1) * p.slices * 2 * sizeof(uint64_t), 256);
+  p.total_bytes = l1k2_prune_plan(xrows, yrows, dim, p.off_feat_x, &p);
+  // two queries per lane in blocks of 128 lanes = the 256 queries of a bound workgroup, kWorkSub blocks for each;
+  // blocks beyond the list's length leave at once
+  if (p.path == kL1K2Bound) p.work_grid = p.bound_grid.x * p.bound_grid.y * kWorkSub;
   return p;
 }
 
@@ -610,9 +633,8 @@ int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int d
 
   uint8_t *ws = static_cast<uint8_t *>(d_ws);
   const uint8_t *kx = d_x, *ky = d_y;
-  if (p.dim_pad != dim) {
-    uint8_t *px = ws;
-    uint8_t *py = ws + p.pad_x_bytes;
+  if (p.padded) {
+    uint8_t *px = ws + p.off_pad_x, *py = ws + p.off_pad_y;
     if (xrows > 0)
       hipLaunchKernelGGL(pad_rows_kernel, dim3(2048), dim3(kThreads), 0, stream, d_x, px,
                          (size_t)xrows, dim, p.dim_pad);
@@ -621,68 +643,33 @@ int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int d
     kx = px;
     ky = py;
   }
-  uint64_t *part = reinterpret_cast<uint64_t *>(ws + p.pad_x_bytes + p.pad_y_bytes);
-
+  const Operands o{reinterpret_cast<const uint4 *>(kx), reinterpret_cast<const uint4 *>(ky), xrows, yrows,
+                   reinterpret_cast<uint64_t *>(ws + p.off_part), stream};
+  l1k2_prune_note_run(p.path == kL1K2Bound ? ws + p.off_stats : nullptr, stream);
   {
     ProfScope prof("l1k2_tile", stream);
-  l1k2_prune_forget();
-  if (l1k2_prune_selected(xrows, yrows, dim, p.slice_rows)) {
-    // dim 128, large shapes: matrix-core lower bound, exact SADs for the survivors only (l1k2_prune.hip)
-    const uint32_t *work = nullptr;
-    int groups = 0;
-    SPV_TRY(l1k2_prune_run(kx, ky, xrows, yrows, p, ws + p.pad_x_bytes + p.pad_y_bytes + p.part_bytes, part, &work,
-                           &groups, stream));
-    // the (query block, slice) groups on which the bound did not pay: exactly, two queries per lane in blocks of
-    // 128 lanes = the 256 queries of a group, eight blocks per group; blocks beyond the list's length leave at once
-    hipLaunchKernelGGL((l1k2_tile_kernel<32, 2, 128>), dim3((unsigned)groups * kWorkSub), dim3(128), 0, stream,
-                       reinterpret_cast<const uint4 *>(kx), reinterpret_cast<const uint4 *>(ky), xrows, yrows,
-                       p.slice_rows, p.slices, part, work);
-  } else
-  switch (p.dim_pad) {
-    case 32: launch_tile_q<8>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 48: launch_tile_q<12>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 64: launch_tile_q<16>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 80: launch_tile_q<20>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 96: launch_tile_q<24>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 112: launch_tile_q<28>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 128: launch_tile_q<32>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 144: launch_tile_q<36>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 160: launch_tile_q<40>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 192: launch_tile_q<48>(kx, ky, xrows, yrows, p, part, stream); break;
-    case 256: launch_tile_q<64>(kx, ky, xrows, yrows, p, part, stream); break;
-    default: {
-      if (p.dim_pad <= 256 || p.dim_pad > kMaxGenericDim || p.dim_pad % 16)
-        return set_error(SPV_ERR_INVALID, "internal: bad dim_pad %d", p.dim_pad);
-      const size_t lds = (size_t)kWideRows * p.dim_pad;
-      const dim3 grid((unsigned)((p.qblocks + 7) / 8 * 8 * p.slices));  // decoded XCD-aware in the kernel
-      if (p.q >= 2)
-        hipLaunchKernelGGL((l1k2_wide_kernel<2>), grid, dim3(kThreads), lds, stream,
-                           reinterpret_cast<const uint4 *>(kx), reinterpret_cast<const uint4 *>(ky), xrows, yrows,
-                           p.dim_pad / 4, p.slice_rows, p.slices, part);
-      else
-        hipLaunchKernelGGL((l1k2_wide_kernel<1>), grid, dim3(kThreads), lds, stream,
-                           reinterpret_cast<const uint4 *>(kx), reinterpret_cast<const uint4 *>(ky), xrows, yrows,
-                           p.dim_pad / 4, p.slice_rows, p.slices, part);
+    bool launched = true;
+    if (p.path == kL1K2Bound) {
+      // dim 128, large shapes: matrix-core lower bound, exact SADs for the survivors only (l1k2_prune.hip), then
+      // exactly the (query block, slice) groups on which the bound did not pay
+      SPV_TRY(l1k2_prune_run(kx, ky, xrows, yrows, p, ws, stream));
+      hipLaunchKernelGGL((l1k2_tile_kernel<32, 2, 128>), dim3(p.work_grid), dim3(128), 0, stream, o.x, o.y, xrows, yrows,
+                         p.slice_rows, p.slices, o.part, reinterpret_cast<const uint32_t *>(ws + p.off_work));
+    } else if (p.path == kL1K2Tile) {
+      launched = pick(TileWidths{}, p.dim_pad, [&](auto W) { return launch_tile_q<decltype(W)::value / 4>(o, p); });
+    } else {
+      launched = pick(Ints<2, 1>{}, p.q, [&](auto Q) { return launch_wide<decltype(Q)::value>(o, p); });
     }
-  }
+    if (!launched) return set_error(SPV_ERR_INVALID, "internal: no kernel for dim_pad %d, q %d", p.dim_pad, p.q);
   }
   SPV_HIP_CHECK(hipGetLastError());
 
   ProfScope prof_merge("l1k2_merge", stream);
-
-  if (p.slices <= 4) {
-    const int blocks = (yrows + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL((l1k2_merge_kernel<1>), dim3(blocks), dim3(kThreads), 0, stream, part, yrows,
-                       p.slices, d_idx, d_dist);
-  } else if (p.slices <= 32) {
-    const int blocks = (int)(((long long)yrows * 8 + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL((l1k2_merge_kernel<8>), dim3(blocks), dim3(kThreads), 0, stream, part, yrows,
-                       p.slices, d_idx, d_dist);
-  } else {
-    const int blocks = (int)(((long long)yrows * 64 + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL((l1k2_merge_kernel<64>), dim3(blocks), dim3(kThreads), 0, stream, part,
+  pick(Ints<1, 8, 64>{}, p.merge_lanes, [&](auto L) {
+    hipLaunchKernelGGL((l1k2_merge_kernel<decltype(L)::value>), dim3(p.merge_grid), dim3(kThreads), 0, stream, o.part,
                        yrows, p.slices, d_idx, d_dist);
-  }
+    return true;
+  });
   SPV_HIP_CHECK(hipGetLastError());
   return SPV_OK;
 }

@@ -39,7 +39,7 @@
 // survivor pass requests its 16 row pieces in two batches of eight.
 //
 // Fallback.  Every wave keeps a running survivor share.  When it exceeds the measured break-even (16 %; 3/4
-// in a workgroup's first tiles; see l1k2_prune_selected) the wave raises a flag, and at the tile's barrier
+// in a workgroup's first tiles; see l1k2_prune_plan) the wave raises a flag, and at the tile's barrier
 // the whole workgroup publishes the thresholds it has, sets its partial keys to "none", puts its (query
 // block, slice) on a work list and leaves.  l1k2_run then launches l1k2_tile_kernel<32, 2, 128> over that
 // list: the parent's exact kernel, 256 queries per block, eight blocks per listed slice merging their keys
@@ -76,7 +76,7 @@ constexpr int kSkipTilesAlone = 3;            // tiles left out of the running s
 constexpr int kWarmTilesShared = 8;           // ... at the break-even share, with thresholds inherited from other slices
 constexpr int kWarmTilesAlone = 256;          // ... and without: its own thresholds take thousands of rows to settle
 constexpr int kShareUnit = 1024;              // the break-even survivor share is passed in 1/1024
-constexpr int kBreakEvenShare = 164;          // 16 %, see l1k2_prune_selected and profiles/r07_prune_breakeven.jsonl
+constexpr int kBreakEvenShare = 164;          // 16 %, see l1k2_prune_plan and profiles/r07_prune_breakeven.jsonl
 constexpr uint32_t kMaxDist = 128 * 255;
 constexpr int kStatSlots = 16;                // survivor counters, spread to keep the atomics apart
 constexpr int kStatWords = kStatSlots * 4 * 2;
@@ -390,16 +390,9 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
   }
 }
 
-std::atomic<int> g_prune_mode{-2};  // -2: SPECTAVI_L1K2_PRUNE not read yet; -1 auto, 0 off, 1 forced
-
-int prune_mode() {
-  int mode = g_prune_mode.load();
-  if (mode == -2) {
-    const char *v = getenv("SPECTAVI_L1K2_PRUNE");
-    mode = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
-    int expected = -2;
-    if (!g_prune_mode.compare_exchange_strong(expected, mode)) mode = expected;
-  }
+// -1 auto, 0 off, 1 forced: SPECTAVI_L1K2_PRUNE until l1k2_set_prune is called
+std::atomic<int> &prune_mode() {
+  static std::atomic<int> mode{l1k2_knobs().prune};
   return mode;
 }
 
@@ -451,31 +444,32 @@ const L1K2Bound &l1k2_bound() {
   return b;
 }
 
-int l1k2_set_prune(int mode) {
-  const int before = prune_mode();
-  g_prune_mode.store(mode);
-  return before;
-}
-int l1k2_get_prune() { return prune_mode(); }
+int l1k2_set_prune(int mode) { return prune_mode().exchange(mode); }
+int l1k2_get_prune() { return prune_mode().load(); }
 
 namespace {
 // where the counters of the calling thread's last l1k2_run lie (null: it took the tile kernels)
-thread_local unsigned long long *t_last_stats = nullptr;
+thread_local const unsigned long long *t_last_stats = nullptr;
 thread_local hipStream_t t_last_stream = nullptr;
-}  // namespace
 
-void l1k2_prune_forget() { t_last_stats = nullptr; }
-
-int l1k2_prune_last_stats(unsigned long long out[3]) {
+int read_stats(const unsigned long long *d_stats, hipStream_t stream, unsigned long long out[3]) {
   out[0] = out[1] = out[2] = 0;
-  if (!t_last_stats) return SPV_OK;
+  if (!d_stats) return SPV_OK;
   unsigned long long raw[kStatSlots * 4];
-  SPV_HIP_CHECK(hipStreamSynchronize(t_last_stream));
-  SPV_HIP_CHECK(hipMemcpy(raw, t_last_stats, sizeof raw, hipMemcpyDeviceToHost));
+  SPV_HIP_CHECK(hipStreamSynchronize(stream));
+  SPV_HIP_CHECK(hipMemcpy(raw, d_stats, sizeof raw, hipMemcpyDeviceToHost));
   for (int i = 0; i < kStatSlots; ++i)
     for (int k = 0; k < 3; ++k) out[k] += raw[4 * i + k];
   return SPV_OK;
 }
+}  // namespace
+
+void l1k2_prune_note_run(const void *d_stats, hipStream_t stream) {
+  t_last_stats = static_cast<const unsigned long long *>(d_stats);
+  t_last_stream = stream;
+}
+
+int l1k2_prune_last_stats(unsigned long long out[3]) { return read_stats(t_last_stats, t_last_stream, out); }
 
 // When `auto` takes the path (tools/l1k2_prune_sweep.py, tools/l1k2_prune_breakeven.py; profiles/r07_*):
 //  * The gain comes with the number of database slices that hand thresholds on: 0.95x at 128k x 128k,
@@ -494,39 +488,37 @@ int l1k2_prune_last_stats(unsigned long long out[3]) {
 //    that do not pay has not grown (profiles/r08_prune_breakeven.jsonl).
 constexpr int kPruneMinX = 262144, kPruneMinSlice = 32768;
 
-bool l1k2_prune_possible(int xrows, int yrows, int dim) { return dim == 128 && xrows >= kTileRows && yrows >= 1; }
-
-bool l1k2_prune_selected(int xrows, int yrows, int dim, int slice_rows) {
-  if (!l1k2_prune_possible(xrows, yrows, dim) || !l1k2_bound().ok) return false;
-  const int mode = prune_mode();
-  if (mode == 0) return false;
-  if (mode == 1) return true;
-  return xrows >= kPruneMinX && slice_rows >= kPruneMinSlice;
+size_t l1k2_prune_plan(int xrows, int yrows, int dim, size_t base, L1K2Plan *p) {
+  p->off_feat_x = p->off_feat_y = p->off_thr = p->off_stats = p->off_work = base;
+  if (dim != 128 || xrows < kTileRows || yrows < 1) return base;  // no such path, no scratch
+  // The scratch is a function of the shape alone, whether or not the path is switched on: the features, then
+  // one block of dwords: thresholds (an even number: the counters are 64-bit), the counters, the work list
+  // (its length, then one (query block, slice) pair for each workgroup there can be).
+  const unsigned qgroups = (unsigned)((yrows + kQPerBlock - 1) / kQPerBlock);
+  const size_t nthr = ((size_t)yrows + 1) / 2 * 2;
+  p->off_feat_y = base + round_up((size_t)xrows * 512, 256);
+  p->off_thr = p->off_feat_y + round_up((size_t)yrows * 512, 256);
+  p->off_stats = p->off_thr + nthr * 4;
+  p->off_work = p->off_stats + kStatWords * 4;
+  const int mode = l1k2_get_prune();
+  const bool wanted = mode == 1 || (mode != 0 && xrows >= kPruneMinX && p->slice_rows >= kPruneMinSlice);
+  if (wanted && l1k2_bound().ok) {
+    p->path = kL1K2Bound;
+    p->bound_grid = dim3(qgroups, (unsigned)p->slices);
+  }
+  return p->off_thr + round_up((nthr + kStatWords + 2 + 2 * (size_t)qgroups * p->slices) * 4, 256);
 }
 
-void l1k2_prune_bytes(int xrows, int yrows, int dim, int slices, size_t *fx_bytes, size_t *fy_bytes, size_t *thr_bytes) {
-  *fx_bytes = *fy_bytes = *thr_bytes = 0;
-  if (!l1k2_prune_possible(xrows, yrows, dim)) return;
-  *fx_bytes = round_up((size_t)xrows * 512, 256);
-  *fy_bytes = round_up((size_t)yrows * 512, 256);
-  // thresholds, the counters, the work list of the workgroups that gave up (its length, then one
-  // (query block, slice) pair for each workgroup there can be)
-  const size_t groups = (size_t)((yrows + kQPerBlock - 1) / kQPerBlock) * slices;
-  *thr_bytes = round_up((((size_t)yrows + 1) / 2 * 2 + kStatWords + 2 + 2 * groups) * 4, 256);
-}
-
-int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *d_extra,
-                   uint64_t *part, const uint32_t **work_out, int *groups_out, hipStream_t stream) {
+int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *ws,
+                   hipStream_t stream) {
   const L1K2Bound &b = l1k2_bound();
   if (!b.ok) return set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
-  size_t fxb, fyb, thb;
-  l1k2_prune_bytes(xrows, yrows, 128, p.slices, &fxb, &fyb, &thb);
-  uint4 *fx = reinterpret_cast<uint4 *>(d_extra);
-  uint4 *fy = reinterpret_cast<uint4 *>(d_extra + fxb);
-  uint32_t *thr = reinterpret_cast<uint32_t *>(d_extra + fxb + fyb);
-  const size_t nthr = ((size_t)yrows + 1) / 2 * 2;
-  unsigned long long *stats = reinterpret_cast<unsigned long long *>(thr + nthr);
-  uint32_t *work = thr + nthr + kStatWords;
+  uint4 *fx = reinterpret_cast<uint4 *>(ws + p.off_feat_x);
+  uint4 *fy = reinterpret_cast<uint4 *>(ws + p.off_feat_y);
+  uint32_t *thr = reinterpret_cast<uint32_t *>(ws + p.off_thr);
+  unsigned long long *stats = reinterpret_cast<unsigned long long *>(ws + p.off_stats);
+  uint32_t *work = reinterpret_cast<uint32_t *>(ws + p.off_work);
+  const size_t nthr = (p.off_stats - p.off_thr) / 4;
 
   static const FeatTable tab = [&] {
     FeatTable t;
@@ -540,10 +532,8 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   // wave leaves the bound after the warm-up tiles, 1024 = never.  The 3/4 rule of the first tiles yields to a
   // larger value, so that 1024 really means never: before, a workgroup whose pairs all survived still left
   // at its tile 4 and "fallback disabled" measured the exact kernel (profiles/r12_l1k2_prune_shapes.txt).
-  static const int max_share = [] {
-    const char *v = getenv("SPECTAVI_L1K2_PRUNE_SHARE");
-    return (v && *v) ? std::max(0, std::min(kShareUnit, atoi(v))) : kBreakEvenShare;
-  }();
+  const int share = l1k2_knobs().prune_share;
+  const int max_share = share < 0 ? kBreakEvenShare : std::min(kShareUnit, share);
   const size_t xw = (size_t)xrows * 32, yw = (size_t)yrows * 32;
   auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + kThreads - 1) / kThreads, 8192)); };
   hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
@@ -552,22 +542,13 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
                      yw, tab);
   hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(nthr + kStatWords + 2), dim3(kThreads), 0, stream, thr, nthr,
                      nthr + kStatWords + 2);
-  const dim3 grid((unsigned)((yrows + kQPerBlock - 1) / kQPerBlock), (unsigned)p.slices);
-  hipLaunchKernelGGL(l1k2_prune_kernel, grid, dim3(kThreads), 0, stream, reinterpret_cast<const uint4 *>(d_x),
+  hipLaunchKernelGGL(l1k2_prune_kernel, p.bound_grid, dim3(kThreads), 0, stream, reinterpret_cast<const uint4 *>(d_x),
                      reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, 128 * b.m, b.p,
-                     max_share, thr, stats, work, part);
+                     max_share, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part));
   SPV_HIP_CHECK(hipGetLastError());
-  *work_out = work;
-  *groups_out = (int)(grid.x * grid.y);
-  t_last_stats = stats;
-  t_last_stream = stream;
-  static const bool print_stats = [] {
-    const char *v = getenv("SPECTAVI_L1K2_PRUNE_STATS");
-    return v && v[0] == '1';
-  }();
-  if (print_stats) {  // debugging aid: synchronises
+  if (l1k2_knobs().prune_stats) {  // debugging aid: synchronises
     unsigned long long h[3];
-    SPV_TRY(l1k2_prune_last_stats(h));
+    SPV_TRY(read_stats(stats, stream, h));
     fprintf(stderr, "l1k2_prune %d x %d: bounded %llu pairs, %llu survived (%.4f), %llu evaluated by the exact fallback\n",
             xrows, yrows, h[0], h[1], h[0] ? (double)h[1] / (double)h[0] : 0.0, h[2]);
   }

@@ -10,10 +10,11 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-# The instantiations l1k2_run launches (spectavi_amd/csrc/l1k2.hip): the `switch (p.dim_pad)` in
-# l1k2_run picks the row width, launch_tile_q picks Q in {1, 2, 4} for D4 <= 16 and {1, 2} above
-# (dim_pad = 4 * D4); widths above 256 go to l1k2_wide_kernel<1> / <2>; the merge kernel takes 1
-# lane per query for <= 4 slices, 8 for <= 32, 64 beyond.  As (dim_pad, q, wide) and merge forms:
+# The instantiations l1k2_run launches (spectavi_amd/csrc/l1k2.hip), all named by l1k2_plan: the
+# row width is one of the table `TileWidths`, launch_tile_q picks Q in {1, 2, 4} for D4 <= 16 and
+# {1, 2} above (dim_pad = 4 * D4, max_q_for); widths above 256 go to l1k2_wide_kernel<1> / <2>; the
+# merge kernel takes the plan's merge_lanes: 1 lane per query for <= 4 slices, 8 for <= 32, 64 beyond
+# (merge_form below restates it: spv_l1k2_plan does not report it).  As (dim_pad, q, wide) and merge forms:
 TILE_WIDTHS = (32, 48, 64, 80, 96, 112, 128, 144, 160, 192, 256)
 INSTANTIATED = ({(w, q, False) for w in TILE_WIDTHS for q in ((1, 2, 4) if w <= 64 else (1, 2))}
                 | {("wide", 1, True), ("wide", 2, True)})

@@ -345,7 +345,7 @@ def test_l1k2_variant_cases_reach_every_instantiation():
     """spv_l1k2_plan (host only) on the case table of tests/test_l1k2_variants_gpu.py: every case
     gets the (width, queries per lane) it is written for, and together the cases reach exactly the
     instantiations l1k2_run launches (INSTANTIATED in tests/l1k2_variant_cases.py, kept beside the
-    `switch (p.dim_pad)` of l1k2_run) and all three merge forms.  A retuned plan or a new width that
+    table `TileWidths` of l1k2.hip) and all three merge forms.  A retuned plan or a new width that
     leaves a kernel without a case fails here, without a GPU."""
     from spectavi_amd import device
     from tests import l1k2_variant_cases as lc
