@@ -126,7 +126,8 @@ void spv_release_cached_memory(void);
 const char *spv_version(void);
 
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
- * "l1k2_tile", "l1k2_merge", "bruteforce", "bruteforce_merge", "cascade_project",
+ * "l1k2_tile", "l1k2_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
+ * "ann_merge", "ann_rerank", "cascade_project",
  * "cascade_buckets", "cascade_probe_refine", "dlt", "rectify") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
@@ -191,6 +192,50 @@ void nn_bruteforce(const float *x, const float *y, int xrows, int yrows, int dim
                    NdArray *outidx, NdArray *outdist);
 void nn_bruteforcei(const int *x, const int *y, int xrows, int yrows, int dim, int k, float p, float mu,
                     NdArray *outidx, NdArray *outdist);
+
+/* Approximate L2 k-nearest-neighbour of every query row y against every database row x, indices only.
+ * Takes the place of reference src/Spectavi.cpp:230-241 (src/Hnswlib.h); there is no HNSW graph here: every
+ * pair is scored coarsely on the bf16 matrix cores, the ncand best rows of each query are kept, and
+ * those are re-ranked exactly.  ann_hnswlib uses the default ncand; spv_ann_l2 (section 2) takes
+ * ncand and also returns the distances.
+ *   x: float32[xrows, dim] database, y: float32[yrows, dim] queries;
+ *   out: callee-allocated size_t[yrows,k] (col 0 = nearest).
+ * Limits: 1 <= dim <= 2048, 1 <= k <= 64, xrows, yrows >= 0; ncand = 0 means max(16, 4k), otherwise
+ * k <= ncand <= 256; outside them SPV_ERR_INVALID and the outputs are not allocated.  One device: the
+ * first one selected by spv_set_device / spv_set_devices, as for nn_bruteforce.
+ * 1. Centring: m_c = rintf(mean of column c of x), the mean from a fixed-order reduction (double sums of
+ *    1024-row chunks, added in chunk order; no float atomics; a mean that is not finite counts as 0);
+ *    x' = bf16(x - m), y' = bf16(y - m), each rounded to nearest even.  L2 is translation invariant;
+ *    centring removes the cancellation bf16 cannot carry, and an integer m keeps integer data integer.
+ * 2. Coarse score: s(i,j) = n_j - 2 (y'_i . x'_j), n_j = sum_c x'_jc^2 (fp32, column order).  The products
+ *    run on the bf16 MFMA with fp32 accumulation in one fixed K order: the bits of s(i,j) depend on the
+ *    pair alone, not on tile position, slice count or launch shape; the zero padding of dim (to a
+ *    multiple of 32) and of edge tiles is exact.
+ * 3. Candidates: per query the ncand smallest keys (s, idx) in lexicographic order, s as the
+ *    order-preserving integer image of the float.  If xrows <= ncand every row is a candidate.
+ * 4. Re-rank: the exact distance of every candidate from the original float32 rows in nn_bruteforce's
+ *    p = 2 arithmetic (d = x - y, t = d*d, s = s + t in column order, each operation rounded on its
+ *    own); the result is the k smallest (dist, idx) pairs, ascending.  Missing neighbours are
+ *    ((size_t)-1, +inf).
+ * Consequences: every returned distance is exact; the result is a function of (x, y, k, ncand) only;
+ * candidate sets are nested in ncand, so a larger ncand never gives a larger j-th distance.  Exact
+ * domain: when all values of both sides are integers inside one window [a, a+255], and dim <= 128 (or,
+ * more generally, every partial sum of products stays below 2^24), steps 1-2 introduce no rounding, s
+ * orders the pairs exactly as the true distance does, and the result equals nn_bruteforce(p = 2) bit
+ * for bit, even at ncand = k.  With NaN or inf inputs, or scores that overflow, a pair may be missed;
+ * the distances that are returned are still exact, and nothing ever faults. */
+void ann_hnswlib(const float *x, const float *y, int xrows, int yrows, int dim, int k, NdArray *out);
+
+/* The reference's k-medians exports (src/Spectavi.cpp:300-319), so that its front-end binds against this
+ * library alone.  nn_kmedians returns the EXACT L1 k-NN -- nn_bruteforce with p = 1, same outputs and
+ * limits -- which is the quantity the reference's randomly seeded cluster filter approximates
+ * (src/KMedians.h:260-295); nmx, nmy and c (its cluster counts) are accepted and ignored.  kmedians
+ * validates its arguments (x non-NULL, xrows >= 0, dim >= 1, k >= 1: SPV_ERR_INVALID otherwise) and
+ * returns: the reference computes a clustering there and discards it.  There is no k-medians
+ * clustering in this library. */
+void nn_kmedians(const float *x, const float *y, int xrows, int yrows, int dim, int nmx, int nmy, int c, int k,
+                 NdArray *outidx, NdArray *outdist);
+void kmedians(const float *x, int xrows, int dim, int k);
 
 /* Cascade-hash candidate prefilter + L1 refine.  Replaces reference
  * src/Spectavi.cpp:321-336 (CascadingHashNn, src/CascadingHashNn.h:86-245).
@@ -342,6 +387,11 @@ int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yro
  * int32 dist) with caller-allocated idx uint64[yrows,k], dist [yrows,k]. */
 int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                       uint64_t *idx, void *dist);
+
+/* ann_hnswlib with the candidate count as an argument (0: the default) and the distances: idx
+ * uint64[yrows,k], dist float32[yrows,k] or NULL. */
+int spv_ann_l2(const float *x, const float *y, int xrows, int yrows, int dim, int k, int ncand, uint64_t *idx,
+               float *dist);
 
 /* As nn_cascading_hash but with explicit hyperplanes: dict is
  * float32[n, dim, m] (table-major, then dim, then bit: the fill order of
@@ -513,6 +563,23 @@ size_t spv_bruteforce_workspace_bytes(int xrows, int yrows, int dim, int k);
 int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrows, int yrows, int dim, int k,
                           float p, int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes,
                           void *stream);
+
+/* Approximate L2 k-NN on device pointers: d_x float32[xrows,dim], d_y float32[yrows,dim] (4-byte aligned;
+ * 16-byte aligned rows let the re-rank load 16 bytes at a time), d_idx uint64[yrows,k], d_dist
+ * float32[yrows,k], contract as ann_hnswlib.  slices = 0: the automatic plan, which needs
+ * spv_ann_l2_workspace_bytes(xrows, yrows, dim, k, ncand) bytes of 256-byte aligned workspace (0 for an
+ * invalid shape); slices > 0 forces that many database slices (fewer if some would be empty) and needs
+ * at most yrows * slices * (8 * buffer length + 4) + 512 bytes more.  The result does not depend on the
+ * slice count.  spv_ann_l2_plan is host-only and touches no device: out = {padded K, query tile, row
+ * tile, slices, rows per slice, ncand in force, keys in the survivor buffer of a (query, slice), MFMA
+ * shape (32: 32x32x16, 16: 16x16x32)}; outside the limits SPV_ERR_INVALID and out is untouched.
+ * The plan always takes the 32x32x16 shape; SPECTAVI_ANN_MFMA=16 in the environment selects the other for
+ * measurements (off the exact domain its K order, hence a score's last bit, may differ).
+ * Kernel names for spv_profile_read: "ann_prep", "ann_coarse", "ann_merge", "ann_rerank". */
+size_t spv_ann_l2_workspace_bytes(int xrows, int yrows, int dim, int k, int ncand);
+int spv_ann_l2_plan(int xrows, int yrows, int dim, int k, int ncand, int slices, int out[8]);
+int spv_ann_l2_device(const float *d_x, const float *d_y, int xrows, int yrows, int dim, int k, int ncand, int slices,
+                      uint64_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, void *stream);
 
 /* image_pair_rectification with everything resident and F given (a HOST pointer, 9 doubles, from
  * spv_rectify_fundamental): dtype SPV_RECTIFY_F64 (d_im0, d_im1, d_r0, d_r1 double, 8-byte aligned)

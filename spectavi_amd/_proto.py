@@ -58,6 +58,9 @@ PROTOTYPES = {
     "nn_bruteforcel1k2": (None, [u8a, u8a, i, i, i, i, nd, nd]),
     "nn_bruteforce": (None, [f32a, f32a] + _knn),
     "nn_bruteforcei": (None, [i32a, i32a] + _knn),
+    "ann_hnswlib": (None, [f32a, f32a, i, i, i, i, nd]),
+    "nn_kmedians": (None, [f32a, f32a] + [i] * 7 + [nd, nd]),
+    "kmedians": (None, [f32a, i, i, i]),
     "nn_cascading_hash": (None, [f32a, f32a] + [i] * 7 + [nd, nd]),
     "dlt_triangulate": (None, _dlt),
     "dlt_reprojection_error": (None, _dlt),
@@ -72,6 +75,7 @@ PROTOTYPES = {
     # ---- 2. host-pointer variants
     "spv_nn_bruteforcel1k2": (i, [vp, vp, i, i, i, vp, vp]),
     "spv_nn_bruteforce": (i, [vp, vp, i, i, i, i, i, f, vp, vp]),
+    "spv_ann_l2": (i, [vp, vp, i, i, i, i, i, vp, vp]),
     "spv_nn_cascading_hash": (i, [f32a, f32a] + [i] * 6 + [f32a, u64a, f32a, vp]),
     "spv_generate_hash_dict": (i, [u32, i, i, i, f32a]),
     "spv_set_hash_seed": (None, [u32, i]),
@@ -100,6 +104,9 @@ PROTOTYPES = {
     "spv_shard_lo": (ll, [ll, i, i]),
     "spv_bruteforce_workspace_bytes": (sz, [i] * 4),
     "spv_bruteforce_device": (i, [vp, vp, i, i, i, i, i, f, i, vp, vp, vp, sz, vp]),
+    "spv_ann_l2_workspace_bytes": (sz, [i] * 5),
+    "spv_ann_l2_plan": (i, [i] * 6 + [pi]),
+    "spv_ann_l2_device": (i, [vp, vp] + [i] * 6 + [vp] * 3 + [sz, vp]),
     "spv_rectify_device": (i, [f64a, vp, vp, i, i, i, i, d, vp, vp, vp, vp, vp]),
     "spv_sift_filter": (i, [vp, i, i, nd]),
     "spv_sift_table": (i, [f32a, i, i, f32a, i, pi32]),

@@ -263,6 +263,27 @@ int host_bruteforce(const void *x, const void *y, int is_int, int xrows, int yro
   return download(dev, idx, di.p, ib, st);
 }
 
+// Approximate L2 k-NN through host pointers, on the first selected device (no sharding).  dist may be NULL.
+int host_ann(const float *x, const float *y, int xrows, int yrows, int dim, int k, int ncand, uint64_t *idx,
+             float *dist) {
+  SPV_TRY(ann_check(xrows, yrows, dim, k, ncand));
+  if (yrows == 0) return SPV_OK;
+  if (!y || !idx || (xrows > 0 && !x)) return set_error(SPV_ERR_INVALID, "null pointer");
+  const int dev = device_list()[0];
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
+  const size_t ib = (size_t)yrows * k * sizeof(uint64_t), db = (size_t)yrows * k * 4;
+  const size_t wsb = std::max<size_t>(ann_plan(xrows, yrows, dim, k, ncand, 0).total_bytes, 256);
+  DevBuf dx, dy, di, dd, ws;
+  SPV_TRY(dx.upload(x, (size_t)xrows * dim * 4, st));
+  SPV_TRY(dy.upload(y, (size_t)yrows * dim * 4, st));
+  SPV_TRY(alloc_all({{&di, ib}, {&dd, db}, {&ws, wsb}}));
+  SPV_TRY(ann_run(dx.as<float>(), dy.as<float>(), xrows, yrows, dim, k, ncand, 0, di.as<uint64_t>(), dd.as<float>(),
+                  ws.p, wsb, st));
+  if (dist) SPV_TRY(dd.copy_out(dist, db, st));
+  return download(dev, idx, di.p, ib, st);
+}
+
 // Rectification through host pointers, on the first selected device: both images up, one kernel,
 // the four outputs back.  r0 / r1 double[rows, cols, nchan], ri0 / ri1 int32[rows, cols].
 int host_rectify(const double *P0, const double *P1, const double *im0, const double *im1, int wid, int hgt,
@@ -902,6 +923,26 @@ void nn_bruteforcei(const int *x, const int *y, int xrows, int yrows, int dim, i
   nn_bruteforce_ref(x, y, 1, xrows, yrows, dim, k, p, mu, outidx, outdist);
 }
 
+void ann_hnswlib(const float *x, const float *y, int xrows, int yrows, int dim, int k, NdArray *out) {
+  clear_error();
+  if (ann_check(xrows, yrows, dim, k, 0) != SPV_OK) return;
+  (void)host_guard([&] {
+    SPV_TRY(alloc_out(out, (size_t)yrows, (size_t)k, (int)sizeof(size_t)));
+    return host_ann(x, y, xrows, yrows, dim, k, 0, static_cast<uint64_t *>(out->m_data), nullptr);
+  });
+}
+
+void nn_kmedians(const float *x, const float *y, int xrows, int yrows, int dim, int nmx, int nmy, int c, int k,
+                 NdArray *outidx, NdArray *outdist) {
+  (void)nmx, (void)nmy, (void)c;  // cluster counts of the reference's filter; the result here is exact
+  nn_bruteforce_ref(x, y, 0, xrows, yrows, dim, k, 1.f, 0.f, outidx, outdist);
+}
+
+void kmedians(const float *x, int xrows, int dim, int k) {
+  clear_error();
+  if (!x || xrows < 0 || dim < 1 || k < 1) set_error(SPV_ERR_INVALID, "kmedians: bad arguments");
+}
+
 void nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int dim, int k,
                        int hash_bit_rate, int num_hash_tables, int num_candidate_neighbours,
                        NdArray *outidx, NdArray *outdist) {
@@ -1012,6 +1053,11 @@ int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yro
 int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                       uint64_t *idx, void *dist) {
   return host_api([&] { return host_bruteforce(x, y, is_int, xrows, yrows, dim, k, p, idx, dist); });
+}
+
+int spv_ann_l2(const float *x, const float *y, int xrows, int yrows, int dim, int k, int ncand, uint64_t *idx,
+               float *dist) {
+  return host_api([&] { return host_ann(x, y, xrows, yrows, dim, k, ncand, idx, dist); });
 }
 
 int spv_nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int dim, int m,
@@ -1304,6 +1350,39 @@ int spv_bruteforce_device(const void *d_x, const void *d_y, int is_int, int xrow
   return api([&] {
     return bruteforce_run(d_x, d_y, is_int, xrows, yrows, dim, k, p, slices, d_idx, d_dist, d_ws, ws_bytes,
                           static_cast<hipStream_t>(stream));
+  });
+}
+
+size_t spv_ann_l2_workspace_bytes(int xrows, int yrows, int dim, int k, int ncand) {
+  if (ann_check(xrows, yrows, dim, k, ncand) != SPV_OK) {
+    clear_error();
+    return 0;
+  }
+  return ann_plan(xrows, yrows, dim, k, ncand, 0).total_bytes;
+}
+
+int spv_ann_l2_plan(int xrows, int yrows, int dim, int k, int ncand, int slices, int out[8]) {
+  clear_error();
+  if (!out) return set_error(SPV_ERR_INVALID, "null output");
+  SPV_TRY(ann_check(xrows, yrows, dim, k, ncand));
+  if (slices < 0) return set_error(SPV_ERR_INVALID, "slices=%d", slices);
+  const AnnPlan p = ann_plan(xrows, yrows, dim, k, ncand, slices);
+  out[0] = p.kpad;
+  out[1] = p.qtile;
+  out[2] = p.rtile;
+  out[3] = p.slices;
+  out[4] = p.slice_rows;
+  out[5] = p.ncand;
+  out[6] = p.buflen;
+  out[7] = p.mfma;
+  return SPV_OK;
+}
+
+int spv_ann_l2_device(const float *d_x, const float *d_y, int xrows, int yrows, int dim, int k, int ncand, int slices,
+                      uint64_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, void *stream) {
+  return api([&] {
+    return ann_run(d_x, d_y, xrows, yrows, dim, k, ncand, slices, d_idx, d_dist, d_ws, ws_bytes,
+                   static_cast<hipStream_t>(stream));
   });
 }
 

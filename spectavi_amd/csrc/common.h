@@ -148,6 +148,30 @@ BruteForcePlan bruteforce_plan(int xrows, int yrows, int k, int slices);
 int bruteforce_run(const void *d_x, const void *d_y, int is_int, int xrows, int yrows, int dim, int k, float p,
                    int slices, uint64_t *d_idx, void *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
 
+// ---- approximate L2 k-NN: bf16 matrix-core score, exact re-rank (ann.hip) -------------
+// Everything ann_run launches for a shape.
+struct AnnPlan {
+  int kpad;        // row width of the bf16 images (dim rounded up to 32)
+  int qtile;       // queries per workgroup of the coarse kernel
+  int rtile;       // database rows per tile
+  int slices;      // database slices
+  int slice_rows;  // database rows per slice
+  int ncand;       // candidates per query in force
+  int buflen;      // keys in the survivor buffer of one (query, slice)
+  int mfma;        // 32: mfma_f32_32x32x16_bf16, 16: mfma_f32_16x16x32_bf16 (SPECTAVI_ANN_MFMA, for measurements)
+  bool all_rows;   // xrows <= ncand: every row is a candidate, only the re-rank runs
+  int qblocks;     // query blocks
+  int chunks;      // partial column sums
+  // workspace: byte offsets, in this order
+  size_t off_part, off_mean, off_xb, off_yb, off_norm, off_cand, off_cnt, off_buf, total_bytes;
+};
+// SPV_ERR_INVALID (message set) outside the limits of include/spectavi_amd.h; touches no device
+int ann_check(int xrows, int yrows, int dim, int k, int ncand);
+// slices > 0 forces that many database slices (fewer if some would be empty); host only
+AnnPlan ann_plan(int xrows, int yrows, int dim, int k, int ncand, int slices);
+int ann_run(const float *d_x, const float *d_y, int xrows, int yrows, int dim, int k, int ncand, int slices,
+            uint64_t *d_idx, float *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
 // ---- cascade hash (cascade.hip) -----------------------------------------------------
 constexpr int kCascadeMaxDim = 2048;  // the widest row the refine kernels take
 // Everything cascade_run decides for a shape under the SPECTAVI_CASCADE_* knobs of the moment.

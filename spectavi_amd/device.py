@@ -109,6 +109,41 @@ def bruteforce(x, y, k=2, p=2.0, workspace=None, slices=0):
     return idx, dist
 
 
+def ann_l2_plan(xrows, yrows, dim, k=2, ncand=0, slices=0):
+    """The launch plan ann_l2() follows for this shape (spv_ann_l2_plan; host only, no device touched):
+    dict of kpad (padded row width), qtile, rtile (queries per workgroup, database rows per tile), slices,
+    slice_rows, ncand (in force), buflen (keys in the survivor buffer of a query and slice), mfma (32 or 16)."""
+    out = (ct.c_int * 8)()
+    check(clib.spv_ann_l2_plan(xrows, yrows, dim, k, ncand, slices, out))
+    return dict(zip(("kpad", "qtile", "rtile", "slices", "slice_rows", "ncand", "buflen", "mfma"), out))
+
+
+def ann_l2(x, y, k=2, ncand=0, workspace=None, slices=0):
+    """Approximate L2 k-NN on device (the contract of feature.ann_l2): x [M,D], y [N,D] float32 CUDA
+    tensors.  Returns (idx int64 [N,k] -- the ABI's size_t bits, -1 = no neighbour --, dist float32 [N,k],
+    exact).  `slices` > 0 forces that many database slices (the result does not depend on it).
+    Asynchronous on the current stream."""
+    from spectavi_amd.feature import check_ann_args
+    _need(x, torch.float32, "x")
+    _need(y, torch.float32, "y")
+    check_ann_args(tuple(x.shape), tuple(y.shape), k, ncand)
+    if int(slices) < 0:
+        raise ValueError("slices must be >= 0")
+    k, ncand, slices = int(k), int(ncand), int(slices)
+    xrows, dim = x.shape
+    yrows = y.shape[0]
+    idx = torch.empty((yrows, k), dtype=torch.int64, device=y.device)
+    dist = torch.empty((yrows, k), dtype=torch.float32, device=y.device)
+    nbytes = clib.spv_ann_l2_workspace_bytes(xrows, yrows, dim, k, ncand)
+    if slices > 0:
+        nbytes += yrows * slices * (8 * ann_l2_plan(xrows, yrows, dim, k, ncand)["buflen"] + 4) + 512
+    with _on_device_of(x, y) as stream:
+        ws = (workspace or _default_ws).get(nbytes, y.device)
+        check(clib.spv_ann_l2_device(x.data_ptr(), y.data_ptr(), xrows, yrows, dim, k, ncand, slices, idx.data_ptr(),
+                                     dist.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+    return idx, dist
+
+
 def l1k2_set_prune(mode):
     """Whether l1k2() at dim 128 rules pairs out with the matrix-core lower bound first
     (spv_l1k2_set_prune): "auto" (shapes whose database slices are at least 32768 rows long, the default), 1 / True (wherever the path exists),

@@ -115,6 +115,109 @@ def nn_bruteforce(x, y, p=.5, mu=0., k=2, use_int=False):
 
 
 # ==================================================================================
+# approximate L2 k-NN         (reference spectavi/feature.py:161-199)
+# ==================================================================================
+_ann_hnswlib = clib.ann_hnswlib
+_spv_ann_l2 = clib.spv_ann_l2
+
+ANN_MAX_NCAND = 256
+
+
+def check_ann_args(xshape, yshape, k, ncand=0):
+    """The limits of ann_hnswlib / spv_ann_l2 (include/spectavi_amd.h) as ValueError, before any device work."""
+    if len(xshape) != 2 or len(yshape) != 2:
+        raise ValueError("x and y must be 2-D")
+    if xshape[1] != yshape[1]:
+        raise ValueError("x and y must have the same number of columns (%d != %d)" % (xshape[1], yshape[1]))
+    if not 1 <= xshape[1] <= BRUTEFORCE_MAX_DIM:
+        raise ValueError("dim=%d outside [1, %d]" % (xshape[1], BRUTEFORCE_MAX_DIM))
+    if int(k) != k or not 1 <= k <= BRUTEFORCE_MAX_K:
+        raise ValueError("k=%r outside [1, %d]" % (k, BRUTEFORCE_MAX_K))
+    if int(ncand) != ncand or (ncand != 0 and not k <= ncand <= ANN_MAX_NCAND):
+        raise ValueError("ncand=%r outside [k=%d, %d] (0: the default max(16, 4k))" % (ncand, k, ANN_MAX_NCAND))
+
+
+def ann_hnswlib(x, y, k=2):
+    """
+    Approximate L2 k nearest neighbours of every row of `y` (queries) among the rows of `x`
+    (database), indices only: the reference's call (spectavi/feature.py:172-199), answered by a
+    coarse score of every pair on the bf16 matrix cores and an exact re-rank of the best
+    max(16, 4k) rows of each query (include/spectavi_amd.h, ann_hnswlib).  `ann_l2` also takes
+    the candidate count and returns the distances.
+
+    Returns
+    -------
+    nn_idx : uint64 ndarray [yrows, k]   index into `x`, nearest first; 2**64-1 where `x` has
+    fewer than k rows.
+    """
+    x = np.asarray(x)
+    y = np.asarray(y)
+    check_ann_args(x.shape, y.shape, k)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    xrows, dim = x.shape
+    yrows = y.shape[0]
+    ann_ret = NdArray(dtype='uint64')
+    _ann_hnswlib(x, y, xrows, yrows, dim, int(k), ct.byref(ann_ret))
+    check()
+    return ann_ret.asarray()
+
+
+def ann_l2(x, y, k=2, ncand=0, return_dist=False):
+    """
+    `ann_hnswlib` with `ncand` candidates per query (0: max(16, 4k); otherwise k <= ncand <= 256)
+    and, with `return_dist`, the distances: float32 [yrows, k], the exact sequential unfused
+    sum of (x - y)**2 of every returned pair, ascending; +inf where a neighbour is missing.
+    The result is a function of (x, y, k, ncand) alone; a larger `ncand` never gives a larger
+    j-th distance; on integer rows inside one window of 256 values and dim <= 128 it equals
+    ``nn_bruteforce(x, y, p=2, k=k)`` bit for bit.
+    """
+    x = np.asarray(x)
+    y = np.asarray(y)
+    check_ann_args(x.shape, y.shape, k, ncand)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    xrows, dim = x.shape
+    yrows = y.shape[0]
+    idx = np.empty((yrows, int(k)), np.uint64)
+    dist = np.empty((yrows, int(k)), np.float32) if return_dist else None
+    check(_spv_ann_l2(x.ctypes.data, y.ctypes.data, xrows, yrows, dim, int(k), int(ncand), idx.ctypes.data,
+                      dist.ctypes.data if return_dist else None))
+    return (idx, dist) if return_dist else idx
+
+
+# ==================================================================================
+# k-medians exports           (reference spectavi/feature.py:313-337)
+# ==================================================================================
+_nn_kmedians = clib.nn_kmedians
+
+
+def nn_kmedians(x, y, k, c=5):
+    """
+    The reference's k-medians matcher (spectavi/feature.py:328-337), answered exactly: the L1
+    k nearest neighbours, ``nn_bruteforce(x, y, p=1., k=k)``, which is what the reference's randomly
+    seeded cluster filter approximates.  `c` only sets the cluster counts the library ignores.
+
+    Returns (uint64 [yrows, k], float32 [yrows, k]).
+    """
+    x = np.asarray(x)
+    y = np.asarray(y)
+    check_bruteforce_args(x.shape, y.shape, k, 1.)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    xrows, dim = x.shape
+    yrows, ydim = y.shape
+    nmx = int(np.round(np.sqrt(xrows / c) * c))
+    nmy = int(np.round(np.sqrt(yrows / c) * c))
+    assert ydim == dim
+    nn_idx = NdArray(dtype='uint64')
+    nn_dist = NdArray(dtype='float32')
+    _nn_kmedians(x, y, xrows, yrows, dim, nmx, nmy, c, int(k), ct.byref(nn_idx), ct.byref(nn_dist))
+    check()
+    return nn_idx.asarray(), nn_dist.asarray()
+
+
+# ==================================================================================
 # cascading hash              (reference spectavi/feature.py:346-376)
 # ==================================================================================
 _nn_cascading_hash = clib.nn_cascading_hash

@@ -363,6 +363,53 @@ def bruteforce_rows(steps, warmup):
                       "dtype": "f32", "data": "synthetic"}), flush=True)
 
 
+BF16_MFMA_PEAK = 2.5e15  # dense bf16 MFMA, FLOP/s (MI355X spec)
+
+
+def ann_rows(steps, warmup):
+    """Approximate L2 k-NN (device.ann_l2) against the exact p = 2 route (device.bruteforce) at the
+    bruteforce row's shape, 131072^2 x 128, k = 2, inputs resident: the two calls alternate in one
+    process, every step timed by device events; kernel times from the library's own brackets."""
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(0xbf)
+    rows, dim, k = 131072, 128, 2
+    x = torch.randn((rows, dim), device=dev, generator=g)
+    y = torch.randn((rows, dim), device=dev, generator=g)
+    plan = spv.ann_l2_plan(rows, rows, dim, k)
+    calls = {"ann_l2": lambda: spv.ann_l2(x, y, k=k), "nn_bruteforce": lambda: spv.bruteforce(x, y, k=k, p=2.0)}
+    for _ in range(max(warmup, 1)):
+        for fn in calls.values():
+            fn()
+    torch.cuda.synchronize()
+    names = ("ann_prep", "ann_coarse", "ann_merge", "ann_rerank")
+    spv.profile_reset()
+    times = {n: [] for n in calls}
+    for _ in range(max(steps, 3)):
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            spv.profile_enable(name == "ann_l2")
+            e0.record()
+            out = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1))
+    spv.profile_enable(False)
+    kern = {n: spv.profile_read(n)[1] / max(spv.profile_read(n)[0], 1) for n in names}
+    ai, _ = calls["ann_l2"]()
+    bi, _ = calls["nn_bruteforce"]()
+    differ = int((ai != bi).sum().item())
+    pairs = float(rows) * rows
+    share = 2.0 * plan["kpad"] * pairs / (kern["ann_coarse"] * 1e-3) / BF16_MFMA_PEAK
+    ann, bf = times["ann_l2"], times["nn_bruteforce"]
+    print(json.dumps({
+        "metric": "approximate L2 k-NN vs exact p=2 k-NN, pairs/s (f32 k=%d)" % k, "value": pairs / (np.mean(ann) * 1e-3),
+        "unit": "pairs/s", "ann_ms": ann, "bruteforce_ms": bf, "ratio": float(np.mean(bf) / np.mean(ann)),
+        "every_ann_step_faster": bool(max(ann) < min(bf)), "kernel_ms": kern, "plan": plan,
+        "coarse_share_of_bf16_mfma_peak": share, "coarse_mfma_bound": bool(share > 0.5),
+        "positions_differing_from_exact": differ, "positions": int(ai.numel()),
+        "config": {"workload": "%d x %d, D=%d" % (rows, rows, dim)}, "dtype": "f32", "data": "synthetic"}), flush=True)
+
+
 def rectify_rows(steps, warmup):
     """image_pair_rectification with resident images (device.image_pair_rectification): 1920 x 1080,
     sf = 1.2, gray and 3-channel, float64 and uint8.  Bytes moved = the four outputs written once plus
@@ -477,7 +524,7 @@ if __name__ == "__main__":
     ap.add_argument("--npt", type=int, default=10_000_000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit,bf,rectify,sift (default all)")
+    ap.add_argument("--only", default="", help="comma list of: cascade,dlt,next,shapes,e2e,fit,bf,ann,rectify,sift (default all)")
     a = ap.parse_args()
     want = set(filter(None, a.only.split(",")))
     if not want or "cascade" in want:
@@ -495,6 +542,8 @@ if __name__ == "__main__":
         ransac_fit()
     if not want or "bf" in want:
         bruteforce_rows(a.steps, a.warmup)
+    if not want or "ann" in want:
+        ann_rows(a.steps, a.warmup)
     if not want or "rectify" in want:
         rectify_rows(a.steps, a.warmup)
     if not want or "sift" in want:
