@@ -15,8 +15,9 @@
 //
 // The kernel.  grid = (blocks of 256 queries, database slices); 4 waves, each owning 64 queries whose
 // 512 feature bytes stay in VGPRs as the B operand (2 column blocks x 16 k-steps x 4 dwords).  Database
-// feature tiles (32 rows x 512 B) stream through LDS, double buffered, one barrier per tile, as the byte
-// tiles of l1k2_tile_kernel do.  Per tile and wave: 32 MFMAs, then one compare per accumulator register
+// feature tiles (32 rows x 512 B) stream through LDS, double buffered, one barrier per tile, loaded from
+// global memory straight into LDS (global_load_lds_dwordx4; see stage_issue).  Per tile and wave: 32 MFMAs,
+// then one compare per accumulator register
 // against the lane's threshold 128 m - p thr (the C layout puts one query on each lane) folded into one bit
 // mask per lane, and the surviving (query, row) pairs are appended to the wave's queue in LDS, one per lane and
 // round.  Whenever 64 are queued, and at the end of the tile, the wave evaluates them exactly, one pair per
@@ -31,12 +32,13 @@
 // atomicMin when its own second best improves.  Every value ever stored is the second best over a subset
 // of the database, hence >= the final one: WHICH pairs are skipped depends on timing, the result never does.
 //
-// Waits.  No tile waits for global memory except at the one vmcnt(0) before stage_store, a whole tile after
-// the loads it covers were issued: the B operand is waited for once, before the loop (else the compiler
-// guards each of the 32 MFMAs of every tile with a vmcnt wait, the last of them on the next tile's
-// prefetch), and the threshold loads ride behind the stage loads of the tile before.  The A operand is read
-// from LDS two k-steps ahead of its MFMAs (three 4-register buffers, lgkmcnt(1) between the pairs), and the
-// survivor pass requests its 16 row pieces in two batches of eight.
+// Waits.  No tile waits for global memory except at the one explicit vmcnt(0) before its barrier, a whole tile
+// after the loads it covers were issued at the tile's top; that wait is also the only thing that makes the
+// next tile visible in LDS.  The B operand is waited for once, before the loop (else the compiler guards each
+// of the 32 MFMAs of every tile with a vmcnt wait), and the threshold loads ride behind the stage loads of the
+// tile before.  The A operand is read from LDS two k-steps ahead of its MFMAs (three 4-register buffers,
+// lgkmcnt(1) between the pairs), and the survivor pass requests all 16 pieces of its two rows at once: one
+// LDS round trip per drain.
 //
 // Fallback.  Every wave keeps a running survivor share.  When it exceeds the measured break-even (16 %; 3/4
 // in a workgroup's first tiles; see l1k2_prune_plan) the wave raises a flag, and at the tile's barrier
@@ -47,16 +49,18 @@
 // the tile kernel's rate on ordinary data and was dropped.
 //
 // Register budget: all 256 VGPRs that two waves per SIMD allow (128 of them the B operand, 12 the A
-// buffers, 20 the staged tile), no scratch; LDS 79880 of the 81920 bytes that two workgroups per CU allow.
-// Any added live value spills (all 16 survivor pieces in flight at once: 10-15 spilled registers): the ISA
-// is checked after every change by tests/test_l1k2_prune_isa.py (registers, spills, scratch, LDS, and no
-// vmcnt wait between the first and the last MFMA of a tile).
+// buffers; no register carries the staged tile, which is what lets the 64 of a drain's 16 pieces fit), no
+// scratch; LDS 78856 of the 81920 bytes that two workgroups per CU allow.  The ISA is checked after every
+// change by tests/test_l1k2_prune_isa.py (registers, spills, scratch, LDS, and no vmcnt wait between the
+// first and the last MFMA of a tile) and tests/test_l1k2_prune_staging_isa.py (the loads to LDS, no vmcnt wait
+// between them and the tile's MFMAs, counted lgkmcnt waits among the MFMAs).
 #include "common.h"
 
 #include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 namespace spv {
 namespace {
@@ -70,8 +74,11 @@ constexpr int kQPerWave = 64;                 // two MFMA column blocks of 32
 constexpr int kQPerBlock = kWaves * kQPerWave;
 constexpr int kTileRows = 32;                 // MFMA rows
 constexpr int kFeatV4 = 32;                   // 512 feature bytes per row = 32 x 16 B
-constexpr int kLdsRowV4 = kFeatV4 + 1;        // +16 B: the 32 rows of a k-step fall on distinct banks
+constexpr int kLdsRowV4 = kFeatV4;            // no pad: a wave's direct-to-LDS load lands 64 x 16 B in a row
 constexpr int kQueue = 128;                   // < 64 queued, then <= 64 appended in one round
+constexpr int kDrainBatch = 8;                // 16-byte pieces of each of a survivor's two rows requested at once
+constexpr int kFtileV4 = kTileRows * kLdsRowV4;
+constexpr int kXrawV4 = kTileRows * 8;
 constexpr int kSkipTilesAlone = 3;            // tiles left out of the running share while a workgroup has no thresholds at all
 constexpr int kWarmTilesShared = 8;           // ... at the break-even share, with thresholds inherited from other slices
 constexpr int kWarmTilesAlone = 256;          // ... and without: its own thresholds take thousands of rows to settle
@@ -81,6 +88,27 @@ constexpr uint32_t kMaxDist = 128 * 255;
 constexpr int kStatSlots = 16;                // survivor counters, spread to keep the atomics apart
 constexpr int kStatWords = kStatSlots * 4 * 2;
 constexpr int kWaitVm0 = 0x0F70;              // s_waitcnt vmcnt(0), the other counters left alone
+
+// Phase stamps (-DSPV_L1K2_PHASE_STAMPS, never in the shipped library): every wave sums the shader cycles of each
+// phase of its tiles in scalar registers and lane 0 stores the sums once, when the wave ends; l1k2_prune_run
+// prints their totals.  Such a build is for attribution only and is never the one that is timed: a stamp waits
+// for lgkmcnt(0) and pins the schedule around it.
+enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPhLoop, kPhases };
+#ifdef SPV_L1K2_PHASE_STAMPS
+#define SPV_STAMP_PARAM , unsigned long long *stamps_out
+#define SPV_STAMP_ARG , d_stamps
+__device__ __forceinline__ unsigned long long stamp() {
+  unsigned long long v;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return v;
+}
+#else
+#define SPV_STAMP_PARAM
+#define SPV_STAMP_ARG
+__device__ __forceinline__ unsigned long long stamp() { return 0; }
+#endif
 
 struct FeatTable { uint32_t w[256]; };        // phi(a) packed little-endian, one dword per byte value
 
@@ -111,14 +139,15 @@ __device__ __forceinline__ void wave_lds_fence() {
 __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
     const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
     const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, uint32_t *thr,
-    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part) {
-  __shared__ uint4 ftile[2][kTileRows * kLdsRowV4];
+    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
+  // 512-byte alignment: the A-operand read folds its swizzle into the address with one XOR
+  __shared__ __attribute__((aligned(512))) uint4 ftile[2][kFtileV4];
   __shared__ unsigned long long k1s[kQPerBlock], k2s[kQPerBlock];
   __shared__ uint4 qraw[kQPerBlock * 8];            // the workgroup's query rows as they are
-  __shared__ uint4 xraw[2][kTileRows * 8];          // the tile's database rows as they are
+  __shared__ uint4 xraw[2][kXrawV4];                // the tile's database rows as they are
   __shared__ uint16_t queue[kWaves][kQueue];        // survivors: query of the wave << 5 | row of the tile
   __shared__ int bail[2];                           // set in tile tl & 1: the workgroup gives the bound up
-  // 79880 bytes in all: two workgroups per CU
+  // 78856 bytes in all: two workgroups per CU
 
   const int t = threadIdx.x;
   const int w = t >> 6, lane = t & 63, c = lane & 31, g = lane >> 5;
@@ -137,32 +166,51 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
     qraw[e] = y[(size_t)min((int)blockIdx.x * kQPerBlock + (e >> 3), N - 1) * 8 + (e & 7)];
   }
 
-  // ---- staging of the database feature tiles
-  uint4 stage[4], stage_raw;
-  auto stage_load = [&](int row0) {
+  // ---- staging of the database tiles, from global memory straight into LDS (global_load_lds_dwordx4): no
+  // registers carry the tile and no ds_write stores it.  A wave's instruction lands its 64 x 16 B one after the
+  // other from the base in M0, so the LDS image is lane-linear and unpadded, and the swizzle that keeps the
+  // A-operand reads off each other's banks is made on the source side: the lane that lands on piece j of row r
+  // fetches piece j ^ (r & 15), and piece q of row r is read back from slot q ^ (r & 15).  EXEC must be full at
+  // these loads, so rows past the end of a ragged last tile are not predicated off but clamped to the last
+  // row: the tile then holds copies of it, which the `valid` mask keeps out of the queue.
+  // The loads are one asm statement, not __builtin_amdgcn_global_load_lds: the compiler, knowing of a load to
+  // LDS in flight, waits for vmcnt(0) before the first LDS read that may alias it (the A operand of this very
+  // tile, in the other buffer) and at every workgroup fence (each drain), and turns every counted lgkmcnt wait
+  // of the MFMA run into lgkmcnt(0).  Unknown to it, they count on vmcnt only, behind its own loads at most,
+  // which can only make one of its waits longer; nothing but the s_waitcnt vmcnt(0) ahead of the tile's
+  // barrier makes the data visible.  M0 is the compiler's: it is put back in the same statement.
+  typedef __attribute__((address_space(3))) void *lds_ptr;
+  const uint32_t lds_f = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&ftile[0][w * 64]));
+  const uint32_t lds_r = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&xraw[0][w * 64]));
+  auto stage_issue = [&](int row0, int b) {
+    const uint4 *src[5];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int e = t + i * kThreads;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (row0 + (e >> 5) < row_end) v = fx[(size_t)row0 * kFeatV4 + e];
-      stage[i] = v;
+      const int e = t + i * kThreads, r = e >> 5;
+      src[i] = fx + (size_t)min(row0 + r, row_end - 1) * kFeatV4 + ((e & 31) ^ (r & 15));
     }
-    stage_raw = make_uint4(0, 0, 0, 0);
-    if (row0 + (t >> 3) < row_end) stage_raw = x[(size_t)row0 * 8 + t];
-  };
-  auto stage_store = [&](uint4 *dst, uint4 *dst_raw) {
-    dst_raw[t] = stage_raw;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = t + i * kThreads;
-      dst[(e >> 5) * kLdsRowV4 + (e & 31)] = stage[i];
-    }
+    src[4] = x + (size_t)min(row0 + (t >> 3), row_end - 1) * 8 + (t & 7);
+    const uint32_t f0 = lds_f + b * (kFtileV4 * 16), r0 = lds_r + b * (kXrawV4 * 16);
+    uint32_t m0_kept;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
+        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
+        "s_mov_b32 m0, %9\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off\n\t"
+        "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(m0_kept)
+        : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]), "v"(src[4]), "s"(f0), "s"(f0 + 4096u), "s"(f0 + 8192u),
+          "s"(f0 + 12288u), "s"(r0)
+        : "memory");
   };
 
   // ---- exact evaluation of the newest n <= 64 queued pairs of the current tile, one per lane.  Both rows
   // come from LDS in 16-byte pieces, each lane starting at a piece of its own so that the 64 rows,
   // which all begin on bank 0, are not read through the same four banks.
   int cnt = 0;  // wave-uniform
+  unsigned long long ph[kPhases] = {};  // wave-uniform cycle sums, all zero and dead without the stamps
   auto drain = [&](int n, const uint4 *xr, uint32_t row0) {
     wave_lds_fence();
     const int base = cnt - n;
@@ -172,20 +220,20 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       const uint4 *qa = qraw + (qslot + q6) * 8, *xa = xr + i * 8;
       const unsigned long long k2now = k2s[qslot + q6];
       uint32_t d = 0;
-      // The 16 pieces are requested in two batches of eight, each in flight as a whole before its first
-      // use (the accumulators and the A buffers are dead here): two LDS round trips for the rows, not five.
+      // All 16 pieces are in flight before the first is used (the accumulators and the A buffers are dead
+      // here, and no register holds a staged tile): one LDS round trip for the rows.
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        uint4 a[4], b[4];
+      for (int h = 0; h < 8 / kDrainBatch; ++h) {
+        uint4 a[kDrainBatch], b[kDrainBatch];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int j = (4 * h + k + lane) & 7;
+        for (int k = 0; k < kDrainBatch; ++k) {
+          const int j = (kDrainBatch * h + k + lane) & 7;
           a[k] = qa[j];
           b[k] = xa[j];
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < kDrainBatch; ++k) {
           d = __builtin_amdgcn_sad_u8(a[k].x, b[k].x, d);
           d = __builtin_amdgcn_sad_u8(a[k].y, b[k].y, d);
           d = __builtin_amdgcn_sad_u8(a[k].z, b[k].z, d);
@@ -209,7 +257,7 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
   // shared threshold read last.  Only atomicMin ever writes thr[], so a later read is never above an earlier
   // one and simply replaces it (and any value ever read there is a valid bound).  The two loads are issued
   // a tile ahead of the refresh that uses them, behind that tile's stage loads, and have landed by the
-  // vmcnt(0) before its stage_store: no tile waits for them.  Lanes past the last query read the last
+  // vmcnt(0) before its barrier: no tile waits for them.  Lanes past the last query read the last
   // query's threshold, whose features they also carry.
   int tq[2];
   uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
@@ -237,8 +285,8 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
 
   const int ntiles = (row_end - row_begin + kTileRows - 1) / kTileRows;
   if (ntiles > 0) {
-    stage_load(row_begin);
-    stage_store(ftile[0], xraw[0]);
+    stage_issue(row_begin, 0);
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
   }
   __syncthreads();
 
@@ -263,12 +311,16 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
     __builtin_amdgcn_s_waitcnt(kWaitVm0);
 
     for (; tl < ntiles; ++tl) {
+      const unsigned long long t_top = stamp();
+      const unsigned long long drained = ph[kPhDrain];
       const int row0 = row_begin + tl * kTileRows;
       const bool has_next = tl + 1 < ntiles;
-      if (has_next) stage_load(row0 + kTileRows);
+      // every wave passed the barrier of tile tl - 1 after its last read of these buffers
+      if (has_next) stage_issue(row0 + kTileRows, (tl + 1) & 1);
       const bool shared = (tl & 3) == 0;  // the shared thresholds move slowly: every fourth tile is enough
       const int nrows = min(kTileRows, row_end - row0);
-      const uint4 *buf = ftile[tl & 1];
+      // this lane's A-operand slot at k-step 0 in this tile's buffer: row c, piece g ^ (c & 15)
+      const int a0 = (tl & 1) * kFtileV4 + c * kLdsRowV4 + (g ^ (c & 15));
       refresh(shared);
       if (tl == 0 && __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
         warm = kWarmTilesShared;
@@ -279,11 +331,15 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       v16i acc[2];
 #pragma unroll
       for (int v = 0; v < 16; ++v) acc[0][v] = acc[1][v] = 0;
-      // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair
-      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, buf[c * kLdsRowV4 + 2 * ks + g]); };
+      // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair.  Each
+      // ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same of the upper half) holds 16
+      // distinct c mod 16 at one g, hence 16 distinct 16-byte slots of the 256-byte bank row: no conflict.
+      // Piece (2 ks + g) ^ (c & 15) = (g ^ (c & 15)) ^ 2 ks; the row and the buffer lie above those bits.
+      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, ftile[0][a0 ^ (2 * ks)]); };
       v4i a3[3];
       a3[0] = lda(0);
       a3[1] = lda(1);
+      const unsigned long long t_mfma = stamp();
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
         if (ks + 2 < 16) a3[(ks + 2) % 3] = lda(ks + 2);
@@ -294,8 +350,9 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
 
       // One bit per accumulator register: bit 31 - n of `skip` says that pair n = 16 b + v of this lane is
       // ruled out (sum < threshold; the difference cannot overflow).  Register v of a lane is row
-      // 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are zero padding and
-      // must never be taken for neighbours.
+      // 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are copies of the
+      // slice's last row and must never be taken for neighbours.
+      const unsigned long long t_cmp = stamp();
       uint32_t skip = 0;
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
@@ -326,10 +383,18 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
         const int add = __popcll(mask);
         cnt += add;
         tile_surv += add;
-        if (cnt >= 64) drain(64, xraw[tl & 1], (uint32_t)row0);
+        if (cnt >= 64) {
+          const unsigned long long d0 = stamp();
+          drain(64, xraw[tl & 1], (uint32_t)row0);
+          ph[kPhDrain] += stamp() - d0;
+        }
       }
       // the tile's raw rows are overwritten during the next tile: nothing stays queued
-      if (cnt > 0) drain(cnt, xraw[tl & 1], (uint32_t)row0);
+      if (cnt > 0) {
+        const unsigned long long d0 = stamp();
+        drain(cnt, xraw[tl & 1], (uint32_t)row0);
+        ph[kPhDrain] += stamp() - d0;
+      }
       n_bound += (unsigned long long)nrows * kQPerWave;
       n_surv += tile_surv;
 
@@ -340,14 +405,32 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
       const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
       if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
-      if (has_next) stage_store(ftile[(tl + 1) & 1], xraw[(tl + 1) & 1]);
+      const unsigned long long t_wait = stamp();
+      // the next tile and the thresholds have landed: a whole tile after their loads were issued
+      __builtin_amdgcn_s_waitcnt(kWaitVm0);
+      const unsigned long long t_bar = stamp();
       __syncthreads();
+      const unsigned long long t_end = stamp();
+      ph[kPhStage] += t_mfma - t_top;
+      ph[kPhMfma] += t_cmp - t_mfma;
+      ph[kPhCompact] += (t_wait - t_cmp) - (ph[kPhDrain] - drained);
+      ph[kPhVmWait] += t_bar - t_wait;
+      ph[kPhBarrier] += t_end - t_bar;
+      ph[kPhLoop] += t_end - t_top;
       if (bail[tl & 1]) {
         gave_up = true;
         break;
       }
     }
   }
+#ifdef SPV_L1K2_PHASE_STAMPS
+  if (lane == 0) {
+    unsigned long long *out = stamps_out + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kWaves + w) * (kPhases + 1);
+#pragma unroll
+    for (int k = 0; k < kPhases; ++k) out[k] = ph[k];
+    out[kPhases] = (unsigned long long)(tl + (gave_up ? 1 : 0));  // tiles this wave ran
+  }
+#endif
   if (gave_up) {
     // what this workgroup has found still bounds its queries' second best from above: hand it on;
     // the exact kernel merges into the partial pair, which starts as "none"
@@ -542,10 +625,33 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
                      yw, tab);
   hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(nthr + kStatWords + 2), dim3(kThreads), 0, stream, thr, nthr,
                      nthr + kStatWords + 2);
+#ifdef SPV_L1K2_PHASE_STAMPS
+  const size_t nstamp = (size_t)p.bound_grid.x * p.bound_grid.y * kWaves * (kPhases + 1);
+  unsigned long long *d_stamps = nullptr;
+  SPV_HIP_CHECK(hipMalloc(&d_stamps, nstamp * 8));
+  SPV_HIP_CHECK(hipMemsetAsync(d_stamps, 0, nstamp * 8, stream));
+#endif
   hipLaunchKernelGGL(l1k2_prune_kernel, p.bound_grid, dim3(kThreads), 0, stream, reinterpret_cast<const uint4 *>(d_x),
                      reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, 128 * b.m, b.p,
-                     max_share, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part));
+                     max_share, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part) SPV_STAMP_ARG);
   SPV_HIP_CHECK(hipGetLastError());
+#ifdef SPV_L1K2_PHASE_STAMPS
+  {
+    static const char *const names[kPhases] = {"stage issue + refresh", "MFMA run", "compare + compaction", "drains",
+                                               "vmcnt(0) wait", "barrier wait", "whole tile"};
+    std::vector<unsigned long long> h(nstamp);
+    SPV_HIP_CHECK(hipStreamSynchronize(stream));
+    SPV_HIP_CHECK(hipMemcpy(h.data(), d_stamps, nstamp * 8, hipMemcpyDeviceToHost));
+    SPV_HIP_CHECK(hipFree(d_stamps));
+    unsigned long long sum[kPhases + 1] = {};
+    for (size_t i = 0; i < nstamp; ++i) sum[i % (kPhases + 1)] += h[i];
+    const double tiles = (double)std::max(1ull, sum[kPhases]);
+    fprintf(stderr, "l1k2_prune phase stamps, %d x %d: %llu wave-tiles\n", xrows, yrows, sum[kPhases]);
+    for (int k = 0; k < kPhases; ++k)
+      fprintf(stderr, "  %-24s %14llu cycles  %8.1f per wave-tile  %5.1f %%\n", names[k], sum[k], sum[k] / tiles,
+              100.0 * sum[k] / (double)std::max(1ull, sum[kPhLoop]));
+  }
+#endif
   if (l1k2_knobs().prune_stats) {  // debugging aid: synchronises
     unsigned long long h[3];
     SPV_TRY(read_stats(stats, stream, h));
