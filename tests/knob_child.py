@@ -1,6 +1,6 @@
 """Child process of tests/test_knobs_gpu.py: runs a short fixed case list against the oracle under
-one of the library's A/B knobs (SPECTAVI_* variables; SPECTAVI_L1K2_Q is read once per process, so
-it cannot be switched inside the pytest process).  The parent puts the knob in this process's
+one of the library's A/B knobs (SPECTAVI_* variables; SPECTAVI_L1K2_Q and SPECTAVI_ANN_MFMA are read once
+per process, so they cannot be switched inside the pytest process).  The parent puts the knob in this process's
 environment; argv[1] names the setting.  Before each case the child asks the library's plan
 whether the knob took effect.  Exits 1 on the first mismatch, printing the case.
 
@@ -37,6 +37,8 @@ SETTINGS = {
     "l1k2_q1": ({"SPECTAVI_L1K2_Q": "1"}, "l1k2", 1),
     "l1k2_q2": ({"SPECTAVI_L1K2_Q": "2"}, "l1k2", 2),
     "l1k2_q4": ({"SPECTAVI_L1K2_Q": "4"}, "l1k2", 4),
+    # the 16x16x32 bf16 MFMA in the coarse stage of ann_l2: ann_coarse_kernel<16, KG>, every KG
+    "ann_mfma16": ({"SPECTAVI_ANN_MFMA": "16"}, "ann", 16),
 }
 
 PLAN_WANTS = {"mfma0": {"family": 0}, "mfma4_0": {"family": 1}, "group0": {"probe_kind": 0},
@@ -44,6 +46,9 @@ PLAN_WANTS = {"mfma0": {"family": 0}, "mfma4_0": {"family": 1}, "group0": {"prob
 
 L1K2_DIMS = (16, 48, 64, 128, 144, 256, 400)
 L1K2_YROWS = (1, 257, 1025)
+ANN_SLICES = (0, 3)
+ANN_LARGE_PAIRS = ((64, 64), (8, 161), (64, 256))
+ANN_MODEL_NCAND = (4, 64)
 
 
 def _fail(what):
@@ -92,11 +97,34 @@ def run_l1k2(q, oracle):
             print("ok l1k2 %dx%dx%d q=%d" % (xrows, yrows, dim, plan[1]), flush=True)
 
 
+def run_ann(mfma):
+    """The variant cases of tests/ann_cases.py on the other MFMA shape; every check asserts first that the
+    plan names that shape."""
+    from tests import ann_cases as ac
+    try:
+        for dim in ac.COARSE_CASES:
+            for slices in ANN_SLICES:
+                ac.check_coarse_case(dim, slices, mfma)
+                print("ok ann coarse dim=%d slices=%d" % (dim, slices), flush=True)
+        for dim in ac.LARGE_DIMS:
+            for k, ncand in ANN_LARGE_PAIRS:
+                ac.check_large_case(dim, k, ncand, mfma)
+                print("ok ann large dim=%d k=%d ncand=%d" % (dim, k, ncand), flush=True)
+        for ncand in ANN_MODEL_NCAND:
+            print("ok " + ac.check_model_case("randn", ncand, mfma), flush=True)
+    except AssertionError as e:
+        _fail("ann mfma=%d: %s" % (mfma, e))
+
+
 def main(setting):
     env, kind, cases = SETTINGS[setting]
     for k, v in env.items():
         if os.environ.get(k) != v:
             _fail("the parent must set %s=%s for setting %s" % (k, v, setting))
+    if kind == "ann":
+        run_ann(cases)
+        print("all ok: %s" % setting, flush=True)
+        return
     from oracle import oracle
     oracle.lib()
     if kind == "cascade":

@@ -20,7 +20,7 @@ def test_static_knobs_in_child_processes():
     """One child per setting, one at a time.  A child that fails, dies on a signal or overruns its
     time limit fails the test with its output, and no further child is started."""
     base = {k: v for k, v in os.environ.items()
-            if not k.startswith(("SPECTAVI_CASCADE_", "SPECTAVI_L1K2_"))}
+            if not k.startswith(("SPECTAVI_CASCADE_", "SPECTAVI_L1K2_", "SPECTAVI_ANN_"))}
     cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [CHILD]
     for setting, (knobs, _, _) in SETTINGS.items():
         env = dict(base, **knobs)

@@ -42,6 +42,11 @@ NOTES = {
         "child process); every other instantiation is one the default selection takes for some shape "
         "(spv_cascade_plan says which; tests/test_abi.py sweeps it without a GPU).",
     ],
+    "ann.hip": [
+        "ann_coarse_kernel<16, *> is reached only with SPECTAVI_ANN_MFMA=16, which is read once per process: "
+        "tests/test_knobs_gpu.py runs the five widths in a child process (setting ann_mfma16) whose plan "
+        "assertion names the shape; they show here only if the trace followed that child.",
+    ],
 }
 
 
