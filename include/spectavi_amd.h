@@ -110,6 +110,19 @@ int spv_l1k2_prune_stats(unsigned long long out[3]);
 /* The bound's table (host only, no GPU involved): phi = the four int8 features of every byte value,
  * and integers p, m with p |a-b| >= m - phi(a).phi(b) for all bytes a, b, m being the largest such. */
 int spv_l1k2_bound_table(int8_t phi[256][4], int *p, int *m);
+/* Which table the bound runs with.  RECIPE: harmonics 1 and 3 of the cosine series of |a - b|, what
+ * spv_l1k2_bound_table returns.  TUNED: the table tools/l1k2_bound_tune.py optimised for the mean bound, which lets
+ * about a tenth as many pairs through on uniform bytes; p and m are derived from it at load under the same exhaustive
+ * check, and if it ever failed that check the recipe would run in its place.  DEFAULT (also SPECTAVI_L1K2_BOUND unset):
+ * TUNED where prune mode AUTO takes the path, RECIPE under prune mode ON.  Results are bit-identical either way. */
+#define SPV_L1K2_BOUND_DEFAULT (-1)
+#define SPV_L1K2_BOUND_RECIPE 0
+#define SPV_L1K2_BOUND_TUNED 1
+int spv_l1k2_set_bound(int which);
+/* The setting in force (the setter's last value, else SPECTAVI_L1K2_BOUND = 0 | 1, else DEFAULT). */
+int spv_l1k2_get_bound(void);
+/* spv_l1k2_bound_table for either table (which = RECIPE or TUNED). */
+int spv_l1k2_bound_table_of(int which, int8_t phi[256][4], int *p, int *m);
 /* Host statement of the 16-byte record format (no GPU involved), for callers that run their own
  * collective on raw records.  pack: idx uint64[n,2] ((size_t)-1 = no neighbour), dist32 = int32 or
  * float32 [n,2] -> rec int32[n,4] = (idx0, idx1, d0 bits, d1 bits), -1 = no neighbour.

@@ -849,6 +849,28 @@ int spv_l1k2_bound_table(int8_t phi[256][4], int *p, int *m) {
   return b.ok ? SPV_OK : set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
 }
 
+int spv_l1k2_set_bound(int which) {
+  clear_error();
+  if (which != SPV_L1K2_BOUND_DEFAULT && which != SPV_L1K2_BOUND_RECIPE && which != SPV_L1K2_BOUND_TUNED)
+    return set_error(SPV_ERR_INVALID, "bound table %d", which);
+  l1k2_set_bound(which);
+  return SPV_OK;
+}
+
+int spv_l1k2_get_bound(void) { return l1k2_get_bound(); }
+
+int spv_l1k2_bound_table_of(int which, int8_t phi[256][4], int *p, int *m) {
+  clear_error();
+  if (!phi || !p || !m) return set_error(SPV_ERR_INVALID, "null output");
+  if (which != SPV_L1K2_BOUND_RECIPE && which != SPV_L1K2_BOUND_TUNED) return set_error(SPV_ERR_INVALID, "bound table %d", which);
+  const L1K2Bound &b = l1k2_bound_of(which);
+  for (int a = 0; a < 256; ++a)
+    for (int f = 0; f < 4; ++f) phi[a][f] = b.phi[a][f];
+  *p = b.p;
+  *m = b.m;
+  return b.ok ? SPV_OK : set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
+}
+
 void spv_release_cached_memory(void) { release_transfer_caches(); }
 
 void spv_profile_enable(int on) {

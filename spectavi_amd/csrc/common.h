@@ -76,7 +76,9 @@ struct L1K2Knobs {
   int blocks;        // SPECTAVI_L1K2_BLOCKS: workgroups the slicing aims for
   int prune;         // SPECTAVI_L1K2_PRUNE: the prune mode a process starts with (-1 auto, 0 never, 1 wherever possible)
   int prune_share;   // SPECTAVI_L1K2_PRUNE_SHARE: hand-over share in 1/1024 (-1: the measured break-even)
+  int prune_octet;   // SPECTAVI_L1K2_PRUNE_OCTET: most pairs a survivor pass takes eight lanes per pair for (-1: the measured crossover; 0: never)
   bool prune_stats;  // SPECTAVI_L1K2_PRUNE_STATS=1: the bound path prints its counters (synchronises)
+  int bound;         // SPECTAVI_L1K2_BOUND: the bound table a process starts with (-1 default, 0 recipe, 1 tuned)
 };
 const L1K2Knobs &l1k2_knobs();
 
@@ -100,6 +102,7 @@ struct L1K2Plan {
   dim3 grid;             // tile kernel: (query blocks, slices); wide kernel: one XCD-padded row of both
   size_t wide_lds;       // wide kernel: dynamic LDS bytes
   dim3 bound_grid;       // l1k2_prune_kernel: (blocks of 256 queries, slices)
+  int bound;             // ... and the table it runs with (kL1K2BoundRecipe / kL1K2BoundTuned)
   unsigned work_grid;    // tile kernel over the bound path's work list: kWorkSub blocks for every workgroup there
   unsigned merge_grid;
   // workspace: byte offsets, in this order.  Padded copies (empty unless `padded`), partial top-2 keys, then the
@@ -117,7 +120,11 @@ struct L1K2Bound {
   int p, m;            // p |a-b| >= m - phi(a).phi(b) for all bytes a, b
   bool ok;             // the table passed its exhaustive check
 };
-const L1K2Bound &l1k2_bound();                               // host only, built once
+enum { kL1K2BoundRecipe = 0, kL1K2BoundTuned = 1 };           // the cosine recipe; the optimised table of l1k2_bound_tuned.h
+const L1K2Bound &l1k2_bound();                               // the recipe; host only, built once
+const L1K2Bound &l1k2_bound_of(int which);                   // either table, each built once; a tuned table that fails its check is the recipe
+int l1k2_set_bound(int which);                               // -1 default (tuned under prune mode auto, the recipe under mode 1), 0, 1; returns the setting before
+int l1k2_get_bound();
 int l1k2_set_prune(int mode);                                // -1 auto, 0 never, 1 wherever possible; returns the mode before
 int l1k2_get_prune();
 // The bound path's part of a plan whose slicing is done: its scratch from byte `base` of the workspace on, and

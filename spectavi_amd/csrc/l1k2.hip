@@ -552,8 +552,12 @@ const L1K2Knobs &l1k2_knobs() {
     k.prune = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
     v = getenv("SPECTAVI_L1K2_PRUNE_SHARE");
     k.prune_share = (v && *v) ? std::max(0, atoi(v)) : -1;
+    v = getenv("SPECTAVI_L1K2_PRUNE_OCTET");
+    k.prune_octet = (v && *v) ? std::max(0, atoi(v)) : -1;
     v = getenv("SPECTAVI_L1K2_PRUNE_STATS");
     k.prune_stats = v && v[0] == '1';
+    v = getenv("SPECTAVI_L1K2_BOUND");
+    k.bound = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
     return k;
   }();
   return knobs;

@@ -20,10 +20,12 @@
 // then one compare per accumulator register
 // against the lane's threshold 128 m - p thr (the C layout puts one query on each lane) folded into one bit
 // mask per lane, and the surviving (query, row) pairs are appended to the wave's queue in LDS, one per lane and
-// round.  Whenever 64 are queued, and at the end of the tile, the wave evaluates them exactly, one pair per
-// lane, both rows read from LDS (the workgroup's 256 query rows and the tile's 32 database rows are kept
-// there as they are, beside the features; from global memory the same reads bound the kernel at the
-// vector cache).  A key dist<<32 | row that beats the query's current second best enters its top-2 in LDS
+// round.  Whenever 64 are queued, and at the end of the tile, the wave evaluates them exactly, both rows read
+// from LDS (the workgroup's 256 query rows and the tile's 32 database rows are kept there as they are, beside
+// the features; from global memory the same reads bound the kernel at the vector cache): one pair per lane
+// (drain: 16 reads and 32 v_sad_u8 whatever the count), or, for the handful of pairs that a tile leaves once
+// thresholds have settled, eight lanes per pair and eight pairs per round (drain_octets: two reads, four
+// v_sad_u8 and three DPP adds per round), up to kOctetPairs pairs.  A key dist<<32 | row that beats the query's current second best enters its top-2 in LDS
 // with two 64-bit atomic minima: old = min(k1, key); min(k2, max(old, key)).  Every key but the final
 // minimum is displaced exactly once, so k2 ends as the second smallest under any interleaving.
 //
@@ -55,6 +57,7 @@
 // first and the last MFMA of a tile) and tests/test_l1k2_prune_staging_isa.py (the loads to LDS, no vmcnt wait
 // between them and the tile's MFMAs, counted lgkmcnt waits among the MFMAs).
 #include "common.h"
+#include "l1k2_bound_tuned.h"
 
 #include <atomic>
 #include <cmath>
@@ -77,6 +80,7 @@ constexpr int kFeatV4 = 32;                   // 512 feature bytes per row = 32 
 constexpr int kLdsRowV4 = kFeatV4;            // no pad: a wave's direct-to-LDS load lands 64 x 16 B in a row
 constexpr int kQueue = 128;                   // < 64 queued, then <= 64 appended in one round
 constexpr int kDrainBatch = 8;                // 16-byte pieces of each of a survivor's two rows requested at once
+constexpr int kOctetPairs = 24;               // up to here the end-of-tile drain takes eight lanes per pair (drain_octets), see l1k2_prune_run
 constexpr int kFtileV4 = kTileRows * kLdsRowV4;
 constexpr int kXrawV4 = kTileRows * 8;
 constexpr int kSkipTilesAlone = 3;            // tiles left out of the running share while a workgroup has no thresholds at all
@@ -138,7 +142,7 @@ __device__ __forceinline__ void wave_lds_fence() {
 
 __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
     const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
-    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, uint32_t *thr,
+    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
     unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
   // 512-byte alignment: the A-operand read folds its swizzle into the address with one XOR
   __shared__ __attribute__((aligned(512))) uint4 ftile[2][kFtileV4];
@@ -245,6 +249,42 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       // nearly all survivors end here, and the two dependent atomics are left to the few that matter
       const unsigned long long key = ((unsigned long long)d << 32) | (row0 + i);
       if (key < k2now) {
+        const unsigned long long old = atomicMin(&k1s[qslot + q6], key);
+        atomicMin(&k2s[qslot + q6], old > key ? old : key);
+      }
+    }
+    cnt = base;
+    wave_lds_fence();
+  };
+
+  // ---- the same for few pairs, eight lanes per pair and eight pairs per round: a tile of the benchmark leaves a
+  // handful of survivors, and one pair per lane pays 16 reads and 32 v_sad_u8 for them as for 64.  Lane 8 o + j
+  // holds piece j of octet o's two rows (one ds_read_b128 each), four v_sad_u8 and three DPP adds give every lane
+  // of the octet the distance, and the octet's first lane does the key compare and the two minima.  All lanes stay
+  // active (octets past the last pair repeat it and store nothing): the DPP adds read their neighbours.
+  // Bank conflicts: a ds_read_b128 lane group ({0-3, 12-15, 20-27} and so on) holds pieces 0-3 of two octets and
+  // pieces 4-7 of two others; rows are 128 B and the bank row 256 B, so the two octets that share their pieces
+  // collide exactly when their rows have the same parity.  Two pairs with rows of one parity cover each slot
+  // twice whatever the map, so 2-way is the floor there; no group ever takes more than two cycles.
+  auto drain_octets = [&](int n, const uint4 *xr, uint32_t row0) {
+    wave_lds_fence();
+    const int base = cnt - n;
+    const int oct = lane >> 3, piece = lane & 7;
+    for (int r = 0; r < n; r += 8) {
+      const int j = r + oct;
+      const uint32_t e = queue[w][base + min(j, n - 1)];
+      const int q6 = e >> 5, i = e & 31;
+      const uint4 a = qraw[(qslot + q6) * 8 + piece], b = xr[i * 8 + piece];
+      const unsigned long long k2now = k2s[qslot + q6];
+      uint32_t d = __builtin_amdgcn_sad_u8(a.x, b.x, 0u);
+      d = __builtin_amdgcn_sad_u8(a.y, b.y, d);
+      d = __builtin_amdgcn_sad_u8(a.z, b.z, d);
+      d = __builtin_amdgcn_sad_u8(a.w, b.w, d);
+      d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+      d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+      d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x141, 0xF, 0xF, false);  // row_half_mirror: the other quad
+      const unsigned long long key = ((unsigned long long)d << 32) | (row0 + i);
+      if (piece == 0 && j < n && key < k2now) {
         const unsigned long long old = atomicMin(&k1s[qslot + q6], key);
         atomicMin(&k2s[qslot + q6], old > key ? old : key);
       }
@@ -392,7 +432,10 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       // the tile's raw rows are overwritten during the next tile: nothing stays queued
       if (cnt > 0) {
         const unsigned long long d0 = stamp();
-        drain(cnt, xraw[tl & 1], (uint32_t)row0);
+        if (cnt <= octet_max)
+          drain_octets(cnt, xraw[tl & 1], (uint32_t)row0);
+        else
+          drain(cnt, xraw[tl & 1], (uint32_t)row0);
         ph[kPhDrain] += stamp() - d0;
       }
       n_bound += (unsigned long long)nrows * kQPerWave;
@@ -479,16 +522,20 @@ std::atomic<int> &prune_mode() {
   return mode;
 }
 
-L1K2Bound make_bound() {
+// -1 default, 0 recipe, 1 tuned: SPECTAVI_L1K2_BOUND until l1k2_set_bound is called
+std::atomic<int> &bound_choice() {
+  static std::atomic<int> which{l1k2_knobs().bound};
+  return which;
+}
+
+// p, m and the verdict for a finished int8 table, p swept over [p_lo, p_hi).  Nothing about a table is trusted:
+// whatever produced it, the path runs only if the inequality holds on every byte pair and nothing can overflow.
+L1K2Bound make_bound(const int8_t phi[256][4], int p_lo, int p_hi) {
   L1K2Bound b{};
-  const double pi = 3.14159265358979323846;
-  for (int a = 0; a < 256; ++a) {
-    b.phi[a][0] = (int8_t)std::nearbyint(127.0 * std::cos(pi * a / 255.0));
-    b.phi[a][1] = (int8_t)std::nearbyint(127.0 * std::sin(pi * a / 255.0));
-    b.phi[a][2] = (int8_t)std::nearbyint(127.0 * std::cos(3.0 * pi * a / 255.0) / 3.0);
-    b.phi[a][3] = (int8_t)std::nearbyint(127.0 * std::sin(3.0 * pi * a / 255.0) / 3.0);
-  }
-  static int G[256][256];
+  for (int a = 0; a < 256; ++a)
+    for (int f = 0; f < 4; ++f) b.phi[a][f] = phi[a][f];
+  std::vector<int> Gv(256 * 256);
+  int(*G)[256] = reinterpret_cast<int(*)[256]>(Gv.data());
   long long sumG = 0;
   for (int a = 0; a < 256; ++a)
     for (int c = 0; c < 256; ++c) {
@@ -499,7 +546,7 @@ L1K2Bound make_bound() {
     }
   // the slope whose bound is largest on average over all byte pairs: mean of (m_p - G) / p
   double best = -1e300;
-  for (int p = 100; p < 260; ++p) {
+  for (int p = p_lo; p < p_hi; ++p) {
     int m = 0x7FFFFFFF;
     for (int a = 0; a < 256; ++a)
       for (int c = 0; c < 256; ++c) m = std::min(m, p * std::abs(a - c) + G[a][c]);
@@ -520,15 +567,45 @@ L1K2Bound make_bound() {
   return b;
 }
 
+L1K2Bound make_recipe() {
+  int8_t phi[256][4];
+  const double pi = 3.14159265358979323846;
+  for (int a = 0; a < 256; ++a) {
+    phi[a][0] = (int8_t)std::nearbyint(127.0 * std::cos(pi * a / 255.0));
+    phi[a][1] = (int8_t)std::nearbyint(127.0 * std::sin(pi * a / 255.0));
+    phi[a][2] = (int8_t)std::nearbyint(127.0 * std::cos(3.0 * pi * a / 255.0) / 3.0);
+    phi[a][3] = (int8_t)std::nearbyint(127.0 * std::sin(3.0 * pi * a / 255.0) / 3.0);
+  }
+  return make_bound(phi, 100, 260);
+}
+
+FeatTable feat_table(const L1K2Bound &b) {
+  FeatTable t;
+  for (int a = 0; a < 256; ++a)
+    t.w[a] = (uint32_t)(uint8_t)b.phi[a][0] | (uint32_t)(uint8_t)b.phi[a][1] << 8 | (uint32_t)(uint8_t)b.phi[a][2] << 16 |
+             (uint32_t)(uint8_t)b.phi[a][3] << 24;
+  return t;
+}
+
 }  // namespace
 
 const L1K2Bound &l1k2_bound() {
-  static const L1K2Bound b = make_bound();
+  static const L1K2Bound b = make_recipe();
   return b;
+}
+
+// The tuned table (tools/l1k2_bound_tune.py) lets about a tenth of the recipe's pairs through on uniform bytes.
+// Its sweep of p is wider than the recipe's, whose range the recipe's tests pin.
+const L1K2Bound &l1k2_bound_of(int which) {
+  if (which != kL1K2BoundTuned) return l1k2_bound();
+  static const L1K2Bound tuned = make_bound(kL1K2BoundTunedPhi, 64, 400);
+  return tuned.ok ? tuned : l1k2_bound();
 }
 
 int l1k2_set_prune(int mode) { return prune_mode().exchange(mode); }
 int l1k2_get_prune() { return prune_mode().load(); }
+int l1k2_set_bound(int which) { return bound_choice().exchange(which); }
+int l1k2_get_bound() { return bound_choice().load(); }
 
 namespace {
 // where the counters of the calling thread's last l1k2_run lie (null: it took the tile kernels)
@@ -585,7 +662,12 @@ size_t l1k2_prune_plan(int xrows, int yrows, int dim, size_t base, L1K2Plan *p) 
   p->off_work = p->off_stats + kStatWords * 4;
   const int mode = l1k2_get_prune();
   const bool wanted = mode == 1 || (mode != 0 && xrows >= kPruneMinX && p->slice_rows >= kPruneMinSlice);
-  if (wanted && l1k2_bound().ok) {
+  // The table: as set, else the tuned one where `auto` takes the path and the recipe where the path is forced
+  // (mode 1 is what the case tables of the tests run, with survivor counts worked out from the recipe).
+  const int which = l1k2_get_bound();
+  p->bound = which >= 0 ? which : mode == 1 ? kL1K2BoundRecipe : kL1K2BoundTuned;
+  if (p->bound == kL1K2BoundTuned && &l1k2_bound_of(kL1K2BoundTuned) == &l1k2_bound()) p->bound = kL1K2BoundRecipe;
+  if (wanted && l1k2_bound_of(p->bound).ok) {
     p->path = kL1K2Bound;
     p->bound_grid = dim3(qgroups, (unsigned)p->slices);
   }
@@ -594,7 +676,7 @@ size_t l1k2_prune_plan(int xrows, int yrows, int dim, size_t base, L1K2Plan *p) 
 
 int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *ws,
                    hipStream_t stream) {
-  const L1K2Bound &b = l1k2_bound();
+  const L1K2Bound &b = l1k2_bound_of(p.bound);
   if (!b.ok) return set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
   uint4 *fx = reinterpret_cast<uint4 *>(ws + p.off_feat_x);
   uint4 *fy = reinterpret_cast<uint4 *>(ws + p.off_feat_y);
@@ -603,13 +685,8 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   uint32_t *work = reinterpret_cast<uint32_t *>(ws + p.off_work);
   const size_t nthr = (p.off_stats - p.off_thr) / 4;
 
-  static const FeatTable tab = [&] {
-    FeatTable t;
-    for (int a = 0; a < 256; ++a)
-      t.w[a] = (uint32_t)(uint8_t)b.phi[a][0] | (uint32_t)(uint8_t)b.phi[a][1] << 8 | (uint32_t)(uint8_t)b.phi[a][2] << 16 |
-               (uint32_t)(uint8_t)b.phi[a][3] << 24;
-    return t;
-  }();
+  static const FeatTable tabs[2] = {feat_table(l1k2_bound_of(kL1K2BoundRecipe)), feat_table(l1k2_bound_of(kL1K2BoundTuned))};
+  const FeatTable &tab = tabs[p.bound == kL1K2BoundTuned];
   // Survivor share (in 1/1024 of a tile's pairs) above which a wave finishes its slice exactly.
   // SPECTAVI_L1K2_PRUNE_SHARE overrides it for measurements (tools/l1k2_prune_breakeven.py): 0 = every
   // wave leaves the bound after the warm-up tiles, 1024 = never.  The 3/4 rule of the first tiles yields to a
@@ -617,6 +694,14 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   // at its tile 4 and "fallback disabled" measured the exact kernel (profiles/r12_l1k2_prune_shapes.txt).
   const int share = l1k2_knobs().prune_share;
   const int max_share = share < 0 ? kBreakEvenShare : std::min(kShareUnit, share);
+  // Most pairs for which the end-of-tile survivor pass takes eight lanes per pair; SPECTAVI_L1K2_PRUNE_OCTET overrides it
+  // for measurements (0 = always one pair per lane, 64 = always octets).  24 is the value that was timed at 1M x 1M (four
+  // pairs per wave and tile on average, where it beats the band).  With the hand-over off at 256k x 256k, 12 and 22
+  // survivors per wave and tile on average, 0 / 8 / 16 / 24 / 32 / 64 gave 33.7 / 33.5 / 33.9 / 34.2 / 34.3 / 34.5 ms and
+  // 34.7 / - / 34.9 / - / 36.5 / 37.3 ms (profiles/r16_prune_octet_crossover.jsonl): the rounds wait for each other, the
+  // crossover lies between 8 and 16 pairs, and 8 is the value to time next at 1M x 1M.
+  const int octet = l1k2_knobs().prune_octet;
+  const int octet_max = octet < 0 ? kOctetPairs : std::min(64, octet);
   const size_t xw = (size_t)xrows * 32, yw = (size_t)yrows * 32;
   auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + kThreads - 1) / kThreads, 8192)); };
   hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
@@ -633,7 +718,7 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
 #endif
   hipLaunchKernelGGL(l1k2_prune_kernel, p.bound_grid, dim3(kThreads), 0, stream, reinterpret_cast<const uint4 *>(d_x),
                      reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, 128 * b.m, b.p,
-                     max_share, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part) SPV_STAMP_ARG);
+                     max_share, octet_max, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part) SPV_STAMP_ARG);
   SPV_HIP_CHECK(hipGetLastError());
 #ifdef SPV_L1K2_PHASE_STAMPS
   {

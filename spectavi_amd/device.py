@@ -162,6 +162,32 @@ def l1k2_get_prune():
     return int(clib.spv_l1k2_get_prune())
 
 
+def l1k2_set_bound(which):
+    """Which table the matrix-core lower bound of l1k2() runs with (spv_l1k2_set_bound): "default" (the tuned
+    table where prune mode "auto" takes the path, the recipe under prune mode 1), 0 / "recipe", 1 / "tuned".
+    The results do not depend on it."""
+    if isinstance(which, str):
+        which = {"default": -1, "recipe": 0, "tuned": 1}.get(which)
+    if isinstance(which, bool) or not isinstance(which, int) or which not in (-1, 0, 1):
+        raise ValueError("bound table must be 'default', 'recipe' (0) or 'tuned' (1)")
+    check(clib.spv_l1k2_set_bound(which))
+
+
+def l1k2_get_bound():
+    """The bound table setting in force: -1 (default), 0 (recipe) or 1 (tuned)."""
+    return int(clib.spv_l1k2_get_bound())
+
+
+def l1k2_bound_table(which=0):
+    """(phi int64 [256, 4], p, m) of the recipe (0) or the tuned (1) table (spv_l1k2_bound_table_of; host only):
+    p |a - b| >= m - phi[a] . phi[b] for all bytes a, b."""
+    import numpy as np
+    phi = np.zeros((256, 4), np.int8)
+    p, m = ct.c_int(0), ct.c_int(0)
+    check(clib.spv_l1k2_bound_table_of(int(which), phi.ctypes.data, ct.byref(p), ct.byref(m)))
+    return phi.astype(np.int64), int(p.value), int(m.value)
+
+
 def l1k2_prune_stats():
     """(pairs put to the bound, survivors, pairs of the exact fallback) of this thread's last l1k2()
     call; all zero if it ran the tile kernels.  Synchronises with that call."""
