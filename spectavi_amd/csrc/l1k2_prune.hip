@@ -16,16 +16,17 @@
 // The kernel.  grid = (blocks of 256 queries, database slices); 4 waves, each owning 64 queries whose
 // 512 feature bytes stay in VGPRs as the B operand (2 column blocks x 16 k-steps x 4 dwords).  Database
 // feature tiles (32 rows x 512 B) stream through LDS, double buffered, one barrier per tile, loaded from
-// global memory straight into LDS (global_load_lds_dwordx4; see stage_issue).  Per tile and wave: 32 MFMAs,
-// then one compare per accumulator register
-// against the lane's threshold 128 m - p thr (the C layout puts one query on each lane) folded into one bit
+// global memory straight into LDS (global_load_lds_dwordx4; see stage_issue), each load addressed by a scalar
+// base that moves on by one tile per iteration plus a tile-invariant lane offset.  Per tile and wave: 32 MFMAs
+// whose accumulators start at minus the lane's threshold 128 m - p thr (the C layout puts one query on each
+// lane), so that the sign bit of each accumulator register says "ruled out"; the 32 signs are folded into one bit
 // mask per lane, and the surviving (query, row) pairs are appended to the wave's queue in LDS, one per lane and
 // round.  Whenever 64 are queued, and at the end of the tile, the wave evaluates them exactly, both rows read
 // from LDS (the workgroup's 256 query rows and the tile's 32 database rows are kept there as they are, beside
 // the features; from global memory the same reads bound the kernel at the vector cache): one pair per lane
-// (drain: 16 reads and 32 v_sad_u8 whatever the count), or, for the handful of pairs that a tile leaves once
-// thresholds have settled, eight lanes per pair and eight pairs per round (drain_octets: two reads, four
-// v_sad_u8 and three DPP adds per round), up to kOctetPairs pairs.  A key dist<<32 | row that beats the query's current second best enters its top-2 in LDS
+// (drain: 16 reads and 32 v_sad_u8 whatever the count), or, up to kOctetPairs pairs, eight lanes per pair and
+// eight pairs per round (drain_octets: two reads, four v_sad_u8 and three DPP adds per round).
+// A key dist<<32 | row that beats the query's current second best enters its top-2 in LDS
 // with two 64-bit atomic minima: old = min(k1, key); min(k2, max(old, key)).  Every key but the final
 // minimum is displaced exactly once, so k2 ends as the second smallest under any interleaving.
 //
@@ -39,8 +40,10 @@
 // next tile visible in LDS.  The B operand is waited for once, before the loop (else the compiler guards each
 // of the 32 MFMAs of every tile with a vmcnt wait), and the threshold loads ride behind the stage loads of the
 // tile before.  The A operand is read from LDS two k-steps ahead of its MFMAs (three 4-register buffers,
-// lgkmcnt(1) between the pairs), and the survivor pass requests all 16 pieces of its two rows at once: one
-// LDS round trip per drain.
+// lgkmcnt(1) between the pairs), its first two reads being the tile's first instructions, ahead of the stage
+// issue and the thresholds; the survivor pass requests all 16 pieces of its two rows at once: one LDS round trip
+// per drain.  The workgroup's bail flag is read right behind the tile's
+// barrier and looked at behind the next tile's threshold reads, with which it arrives: no round trip of its own.
 //
 // Fallback.  Every wave keeps a running survivor share.  When it exceeds the measured break-even (16 %; 3/4
 // in a workgroup's first tiles; see l1k2_prune_plan) the wave raises a flag, and at the tile's barrier
@@ -51,11 +54,13 @@
 // the tile kernel's rate on ordinary data and was dropped.
 //
 // Register budget: all 256 VGPRs that two waves per SIMD allow (128 of them the B operand, 12 the A
-// buffers; no register carries the staged tile, which is what lets the 64 of a drain's 16 pieces fit), no
-// scratch; LDS 78856 of the 81920 bytes that two workgroups per CU allow.  The ISA is checked after every
-// change by tests/test_l1k2_prune_isa.py (registers, spills, scratch, LDS, and no vmcnt wait between the
-// first and the last MFMA of a tile) and tests/test_l1k2_prune_staging_isa.py (the loads to LDS, no vmcnt wait
-// between them and the tile's MFMAs, counted lgkmcnt waits among the MFMAs).
+// buffers, 5 the lane offsets of the stage loads and 10 what a ragged tile makes them from again, where 10 held
+// the five 64-bit addresses; no register carries the staged tile, which is what lets the 64 of a drain's 16
+// pieces fit), no scratch; LDS 78856 of the 81920 bytes that two workgroups per CU allow.  The ISA is checked
+// after every change by tests/test_l1k2_prune_isa.py (registers, spills, scratch, LDS, and no vmcnt wait between
+// the first and the last MFMA of a tile), tests/test_l1k2_prune_staging_isa.py (the loads to LDS, no vmcnt wait
+// between them and the tile's MFMAs, counted lgkmcnt waits among the MFMAs) and
+// tests/test_l1k2_prune_chain_isa.py (the scalar-base form of the loads, the vector instructions at a tile's top).
 #include "common.h"
 #include "l1k2_bound_tuned.h"
 
@@ -80,7 +85,7 @@ constexpr int kFeatV4 = 32;                   // 512 feature bytes per row = 32 
 constexpr int kLdsRowV4 = kFeatV4;            // no pad: a wave's direct-to-LDS load lands 64 x 16 B in a row
 constexpr int kQueue = 128;                   // < 64 queued, then <= 64 appended in one round
 constexpr int kDrainBatch = 8;                // 16-byte pieces of each of a survivor's two rows requested at once
-constexpr int kOctetPairs = 24;               // up to here the end-of-tile drain takes eight lanes per pair (drain_octets), see l1k2_prune_run
+constexpr int kOctetPairs = 8;                // up to here the end-of-tile drain takes eight lanes per pair (drain_octets), see l1k2_prune_run
 constexpr int kFtileV4 = kTileRows * kLdsRowV4;
 constexpr int kXrawV4 = kTileRows * 8;
 constexpr int kSkipTilesAlone = 3;            // tiles left out of the running share while a workgroup has no thresholds at all
@@ -186,27 +191,38 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
   typedef __attribute__((address_space(3))) void *lds_ptr;
   const uint32_t lds_f = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&ftile[0][w * 64]));
   const uint32_t lds_r = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&xraw[0][w * 64]));
-  auto stage_issue = [&](int row0, int b) {
-    const uint4 *src[5];
+  // Addresses.  The tile's first feature row and first raw row are two wave-uniform 64-bit pointers, which the
+  // scalar unit advances by one tile per iteration (at 4M rows the feature offset passes 2^31), and each load
+  // adds the lane's byte offset within the tile (global_load_lds_dwordx4 vOff, s[base:base+1]).  The five
+  // offsets are the same for every full tile and stay in five registers; only a ragged tile, the last of a
+  // slice, computes them again with the row clamp, under a wave-uniform branch around that arithmetic alone
+  // (no full tile follows a ragged one, so they are overwritten in place).
+  uint32_t voff[5];
+  auto lane_offsets = [&](int nrows) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = t + i * kThreads, r = e >> 5;
-      src[i] = fx + (size_t)min(row0 + r, row_end - 1) * kFeatV4 + ((e & 31) ^ (r & 15));
+      voff[i] = (uint32_t)(min(r, nrows - 1) * kFeatV4 + ((e & 31) ^ (r & 15))) * 16u;
     }
-    src[4] = x + (size_t)min(row0 + (t >> 3), row_end - 1) * 8 + (t & 7);
+    voff[4] = (uint32_t)(min(t >> 3, nrows - 1) * 8 + (t & 7)) * 16u;
+  };
+  lane_offsets(kTileRows);
+  auto stage_issue = [&](const uint4 *ftile0, const uint4 *xtile0, int nrows, int b) {
+    if (__builtin_expect(nrows < kTileRows, 0)) lane_offsets(nrows);
     const uint32_t f0 = lds_f + b * (kFtileV4 * 16), r0 = lds_r + b * (kXrawV4 * 16);
     uint32_t m0_kept;
+    // s_nop 2: with the two s_mov ahead of it, five states between whatever wrote a base register and its first use
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
-        "s_mov_b32 m0, %9\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off\n\t"
-        "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, off\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %11\n\t"
+        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %11\n\t"
+        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %11\n\t"
+        "s_mov_b32 m0, %9\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %11\n\t"
+        "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %12\n\t"
         "s_mov_b32 m0, %0"
         : "=&s"(m0_kept)
-        : "v"(src[0]), "v"(src[1]), "v"(src[2]), "v"(src[3]), "v"(src[4]), "s"(f0), "s"(f0 + 4096u), "s"(f0 + 8192u),
-          "s"(f0 + 12288u), "s"(r0)
+        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "s"(f0), "s"(f0 + 4096u), "s"(f0 + 8192u),
+          "s"(f0 + 12288u), "s"(r0), "s"(ftile0), "s"(xtile0)
         : "memory");
   };
 
@@ -293,13 +309,14 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
     wave_lds_fence();
   };
 
-  // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b].  seen[b] is the
+  // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b] = 128 m - p thr; what is
+  // kept is ntq[b] = -tq[b], the value that the tile's accumulators start from.  seen[b] is the
   // shared threshold read last.  Only atomicMin ever writes thr[], so a later read is never above an earlier
   // one and simply replaces it (and any value ever read there is a valid bound).  The two loads are issued
   // a tile ahead of the refresh that uses them, behind that tile's stage loads, and have landed by the
   // vmcnt(0) before its barrier: no tile waits for them.  Lanes past the last query read the last
   // query's threshold, whose features they also carry.
-  int tq[2];
+  int ntq[2];
   uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
   auto thr_load = [&]() {
 #pragma unroll
@@ -312,7 +329,7 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
     for (int b = 0; b < 2; ++b) {
       loc[b] = (uint32_t)(k2s[qslot + 32 * b + c] >> 32);
       // thr = "none yet" keeps every pair: sum >= 128 m - p 32640 always
-      tq[b] = m128 - p * (int)min(min(loc[b], seen[b]), kMaxDist);
+      ntq[b] = p * (int)min(min(loc[b], seen[b]), kMaxDist) - m128;
     }
     if (shared && g == 0) {
 #pragma unroll
@@ -325,16 +342,23 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
 
   const int ntiles = (row_end - row_begin + kTileRows - 1) / kTileRows;
   if (ntiles > 0) {
-    stage_issue(row_begin, 0);
+    stage_issue(fx + (size_t)row_begin * kFeatV4, x + (size_t)row_begin * 8, min(kTileRows, row_end - row_begin), 0);
     __builtin_amdgcn_s_waitcnt(kWaitVm0);
   }
   __syncthreads();
+  // the tile that the loop stages next
+  const uint4 *fnext = fx + ((size_t)row_begin + kTileRows) * kFeatV4, *xnext = x + ((size_t)row_begin + kTileRows) * 8;
 
   unsigned long long n_bound = 0, n_surv = 0;  // wave-uniform statistics
   bool gave_up = false;                        // workgroup-uniform
   int warm = kWarmTilesAlone, skip_tiles = kSkipTilesAlone;
   int recent = 0;  // survivors of the last tiles, each tile weighing 7/8 of the one after it: 8 x the running share
   int tl = 0;
+  // bail[] of the tile before, read right behind its barrier.  The index carries a zero that the compiler cannot
+  // see through: a value it knows to be wave-uniform is moved to a scalar register where it is loaded, which
+  // waits for it there; this one stays in its vector register until the tile's top asks for it.
+  int bailed = 0, zero_v = 0;
+  asm volatile("" : "+v"(zero_v));
   {
     // ---- this wave's queries as the B operand
     v4i bq[2][16];
@@ -355,30 +379,49 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       const unsigned long long drained = ph[kPhDrain];
       const int row0 = row_begin + tl * kTileRows;
       const bool has_next = tl + 1 < ntiles;
-      // every wave passed the barrier of tile tl - 1 after its last read of these buffers
-      if (has_next) stage_issue(row0 + kTileRows, (tl + 1) & 1);
-      const bool shared = (tl & 3) == 0;  // the shared thresholds move slowly: every fourth tile is enough
-      const int nrows = min(kTileRows, row_end - row0);
       // this lane's A-operand slot at k-step 0 in this tile's buffer: row c, piece g ^ (c & 15)
       const int a0 = (tl & 1) * kFtileV4 + c * kLdsRowV4 + (g ^ (c & 15));
+      // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair.  Each
+      // ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same of the upper half) holds 16
+      // distinct c mod 16 at one g, hence 16 distinct 16-byte slots of the 256-byte bank row: no conflict.
+      // Piece (2 ks + g) ^ (c & 15) = (g ^ (c & 15)) ^ 2 ks; the row and the buffer lie above those bits.
+      // The first two reads are the tile's first instructions: the stage issue and the thresholds run in their
+      // latency (the memory clobber of the loads keeps them ahead).
+      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, ftile[0][a0 ^ (2 * ks)]); };
+      v4i a3[3];
+      a3[0] = lda(0);
+      a3[1] = lda(1);
+      // every wave passed the barrier of tile tl - 1 after its last read of these buffers
+      if (has_next) {
+        stage_issue(fnext, xnext, min(kTileRows, row_end - row0 - kTileRows), (tl + 1) & 1);
+        fnext += kFtileV4;
+        xnext += kXrawV4;
+      }
+      const bool shared = (tl & 3) == 0;  // the shared thresholds move slowly: every fourth tile is enough
+      const int nrows = min(kTileRows, row_end - row0);
       refresh(shared);
       if (tl == 0 && __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
         warm = kWarmTilesShared;
         skip_tiles = 0;
       }
       if ((tl & 3) == 3) thr_load();  // for the next tile; they land behind this tile's work
+      // The workgroup leaves after the tile whose flag was raised, before it bounds a pair of this one.  The loads
+      // and the thresholds just issued are harmless: every published value is a valid bound, the exit path
+      // publishes anyway, and it waits for the loads.  The flag arrived with the k2s[] that the thresholds were
+      // made from; pinning them here keeps that one wait ahead of the branch (sunk below it, the reads would be
+      // pending on the way out of the loop and the compiler would wait for them at every tile's top).
+      asm volatile("" ::"v"(ntq[0]), "v"(ntq[1]));
+      if (__builtin_amdgcn_readfirstlane(bailed)) break;
 
+      // The accumulators start at minus the lane's threshold, so that a register ends as sum - threshold and its
+      // sign bit says "ruled out" (the difference cannot overflow: make_bound).  The 32 moves stand where the
+      // wave waits for its first A reads anyway, and take a subtraction per register out of the compare.
       v16i acc[2];
 #pragma unroll
-      for (int v = 0; v < 16; ++v) acc[0][v] = acc[1][v] = 0;
-      // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair.  Each
-      // ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same of the upper half) holds 16
-      // distinct c mod 16 at one g, hence 16 distinct 16-byte slots of the 256-byte bank row: no conflict.
-      // Piece (2 ks + g) ^ (c & 15) = (g ^ (c & 15)) ^ 2 ks; the row and the buffer lie above those bits.
-      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, ftile[0][a0 ^ (2 * ks)]); };
-      v4i a3[3];
-      a3[0] = lda(0);
-      a3[1] = lda(1);
+      for (int b = 0; b < 2; ++b) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[b][v] = ntq[b];
+      }
       const unsigned long long t_mfma = stamp();
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
@@ -389,7 +432,7 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       }
 
       // One bit per accumulator register: bit 31 - n of `skip` says that pair n = 16 b + v of this lane is
-      // ruled out (sum < threshold; the difference cannot overflow).  Register v of a lane is row
+      // ruled out (sum < threshold: the register's sign).  Register v of a lane is row
       // 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are copies of the
       // slice's last row and must never be taken for neighbours.
       const unsigned long long t_cmp = stamp();
@@ -397,7 +440,7 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
 #pragma unroll
-        for (int v = 0; v < 16; ++v) skip = __builtin_amdgcn_alignbit(skip, (uint32_t)(acc[b][v] - tq[b]), 31);
+        for (int v = 0; v < 16; ++v) skip = __builtin_amdgcn_alignbit(skip, (uint32_t)acc[b][v], 31);
       }
       uint32_t live = ~skip;
       if (nrows < kTileRows) {
@@ -460,18 +503,19 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       ph[kPhVmWait] += t_bar - t_wait;
       ph[kPhBarrier] += t_end - t_bar;
       ph[kPhLoop] += t_end - t_top;
-      if (bail[tl & 1]) {
-        gave_up = true;
-        break;
-      }
+      // The flag is asked for here and looked at behind the next tile's first LDS wait: no round trip of its own.
+      bailed = bail[(tl & 1) + zero_v];
     }
+    gave_up = __builtin_amdgcn_readfirstlane(bailed) != 0;  // whether it was seen at a tile's top or the slice ended with it
   }
+  // a wave must not end with a load into its workgroup's LDS in flight
+  if (gave_up) __builtin_amdgcn_s_waitcnt(kWaitVm0);
 #ifdef SPV_L1K2_PHASE_STAMPS
   if (lane == 0) {
     unsigned long long *out = stamps_out + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kWaves + w) * (kPhases + 1);
 #pragma unroll
     for (int k = 0; k < kPhases; ++k) out[k] = ph[k];
-    out[kPhases] = (unsigned long long)(tl + (gave_up ? 1 : 0));  // tiles this wave ran
+    out[kPhases] = (unsigned long long)tl;  // tiles this wave ran
   }
 #endif
   if (gave_up) {
@@ -695,11 +739,11 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   const int share = l1k2_knobs().prune_share;
   const int max_share = share < 0 ? kBreakEvenShare : std::min(kShareUnit, share);
   // Most pairs for which the end-of-tile survivor pass takes eight lanes per pair; SPECTAVI_L1K2_PRUNE_OCTET overrides it
-  // for measurements (0 = always one pair per lane, 64 = always octets).  24 is the value that was timed at 1M x 1M (four
-  // pairs per wave and tile on average, where it beats the band).  With the hand-over off at 256k x 256k, 12 and 22
-  // survivors per wave and tile on average, 0 / 8 / 16 / 24 / 32 / 64 gave 33.7 / 33.5 / 33.9 / 34.2 / 34.3 / 34.5 ms and
-  // 34.7 / - / 34.9 / - / 36.5 / 37.3 ms (profiles/r16_prune_octet_crossover.jsonl): the rounds wait for each other, the
-  // crossover lies between 8 and 16 pairs, and 8 is the value to time next at 1M x 1M.
+  // for measurements (0 = always one pair per lane, 64 = always octets).  One round of eight pairs: with the hand-over off
+  // at 256k x 256k, 12 and 22 survivors per wave and tile on average, 0 / 8 / 16 / 24 / 32 / 64 gave 33.7 / 33.5 / 33.9 /
+  // 34.2 / 34.3 / 34.5 ms and 34.7 / - / 34.9 / - / 36.5 / 37.3 ms (profiles/r16_prune_octet_crossover.jsonl): the rounds
+  // wait for each other.  At 1M x 1M (four pairs per wave and tile on average) 8, 16 and 24 were timed against each other
+  // on one build: DESIGN.md 4.1, "The wave's chain per tile", has the three numbers.
   const int octet = l1k2_knobs().prune_octet;
   const int octet_max = octet < 0 ? kOctetPairs : std::min(64, octet);
   const size_t xw = (size_t)xrows * 32, yw = (size_t)yrows * 32;
