@@ -673,13 +673,37 @@ static int fold_chunks(int rows) { return (rows + kFoldChunk - 1) / kFoldChunk; 
 // workspace that lets normalize_run fold the column sums (tables of at least kFoldMinRows rows)
 constexpr int kFoldMinRows = 64 * kFoldChunk;  // below this the launches and the always-walked first chunks (the sum
                                                // doubles through a binade per chunk at first) cost more than walking
+// The statistics, then the fold's buffers: stated once, the size query walks them from a null base.
+static size_t fold_layout(void *base, int rows, int dim, FoldBufs *fb, int **colserial) {
+  WsWalk w(base);
+  w.reserve(normalize_workspace_bytes(dim));
+  if (rows < kFoldMinRows) return w.end();
+  const int nblk = (dim + kFoldCols - 1) / kFoldCols;
+  const size_t n = (size_t)fold_chunks(rows) * dim;
+  fb->nchunks = fold_chunks(rows);
+  fb->csum = w.take<double>(n * sizeof(double));
+  fb->cpmin = w.take<double>(n * sizeof(double));
+  fb->cpmax = w.take<double>(n * sizeof(double));
+  fb->cvmax = w.take<float>(n * sizeof(float));
+  fb->cvmin = w.take<float>(n * sizeof(float));
+  fb->cfinite = w.take<int>(n * sizeof(int));
+  fb->eguess = w.take<int>(n * sizeof(int));
+  fb->d0 = w.take<int>(n * sizeof(int));
+  fb->d1 = w.take<int>(n * sizeof(int));
+  fb->tlo = w.take<int>(n * sizeof(int));
+  fb->thi = w.take<int>(n * sizeof(int));
+  fb->qq = w.take<int>(n * sizeof(int));
+  fb->colvmax = w.take<float>((size_t)dim * sizeof(float));
+  fb->colvmin = w.take<float>((size_t)dim * sizeof(float));
+  fb->blockserial = w.take<int>((size_t)nblk * sizeof(int));
+  *colserial = w.take<int>((size_t)dim * sizeof(int));
+  return w.end();
+}
+
 size_t normalize_workspace_bytes_rows(int rows, int dim) {
-  size_t b = normalize_workspace_bytes(dim);
-  if (rows < kFoldMinRows) return b;
-  const size_t n = (size_t)fold_chunks(rows) * std::max(dim, 1);
-  b += 3 * round_up(n * sizeof(double), 256) + 9 * round_up(n * sizeof(int), 256);
-  b += 3 * round_up((size_t)dim * sizeof(float), 256) + round_up((size_t)((dim + kFoldCols - 1) / kFoldCols) * sizeof(int), 256);
-  return b;
+  FoldBufs fb;
+  int *colserial;
+  return fold_layout(nullptr, rows, dim, &fb, &colserial);
 }
 
 int normalize_run(const float *d_x, int rows, int dim, float *d_out_f32, unsigned char *d_out_u8,
@@ -701,33 +725,10 @@ int normalize_run(const float *d_x, int rows, int dim, float *d_out_f32, unsigne
     return e && *e == '1';
   }();
   const int *only_blocks = nullptr;
-  if (!serial_only && rows >= kFoldMinRows && ws_bytes >= normalize_workspace_bytes_rows(rows, dim)) {
-    const int nch = fold_chunks(rows);
-    const size_t n = (size_t)nch * dim;
-    unsigned char *p = static_cast<unsigned char *>(d_ws) + normalize_workspace_bytes(dim);
-    auto take = [&](size_t bytes) {
-      unsigned char *q = p;
-      p += round_up(bytes, 256);
-      return q;
-    };
-    FoldBufs fb;
-    fb.csum = reinterpret_cast<double *>(take(n * sizeof(double)));
-    fb.cpmin = reinterpret_cast<double *>(take(n * sizeof(double)));
-    fb.cpmax = reinterpret_cast<double *>(take(n * sizeof(double)));
-    fb.cvmax = reinterpret_cast<float *>(take(n * sizeof(float)));
-    fb.cvmin = reinterpret_cast<float *>(take(n * sizeof(float)));
-    fb.cfinite = reinterpret_cast<int *>(take(n * sizeof(int)));
-    fb.eguess = reinterpret_cast<int *>(take(n * sizeof(int)));
-    fb.d0 = reinterpret_cast<int *>(take(n * sizeof(int)));
-    fb.d1 = reinterpret_cast<int *>(take(n * sizeof(int)));
-    fb.tlo = reinterpret_cast<int *>(take(n * sizeof(int)));
-    fb.thi = reinterpret_cast<int *>(take(n * sizeof(int)));
-    fb.qq = reinterpret_cast<int *>(take(n * sizeof(int)));
-    fb.colvmax = reinterpret_cast<float *>(take((size_t)dim * sizeof(float)));
-    fb.colvmin = reinterpret_cast<float *>(take((size_t)dim * sizeof(float)));
-    fb.blockserial = reinterpret_cast<int *>(take((size_t)nblk * sizeof(int)));
-    int *colserial = reinterpret_cast<int *>(take((size_t)dim * sizeof(int)));
-    fb.nchunks = nch;
+  FoldBufs fb;
+  int *colserial;
+  if (!serial_only && rows >= kFoldMinRows && ws_bytes >= fold_layout(d_ws, rows, dim, &fb, &colserial)) {
+    const int nch = fb.nchunks;
     const dim3 grid((unsigned)nblk, (unsigned)nch);
     hipLaunchKernelGGL(colsum_stats_kernel, grid, dim3(kFoldThreads), 0, stream, d_x, rows, dim, fb);
     hipLaunchKernelGGL(colsum_plan_kernel, dim3(dim), dim3(64), 0, stream, nch, dim, fb, colserial);

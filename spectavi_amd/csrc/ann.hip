@@ -491,21 +491,16 @@ AnnPlan ann_plan(int xrows, int yrows, int dim, int k, int ncand, int slices) {
   p.slices = std::max(1, (int)(((long long)xrows + p.slice_rows - 1) / p.slice_rows));
   p.chunks = std::max(1, (xrows + kMeanChunk - 1) / kMeanChunk);
   const size_t xr = (size_t)std::max(xrows, 1), yr = (size_t)std::max(yrows, 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += round_up(bytes, 256);
-    return at;
-  };
-  p.off_part = take((size_t)p.chunks * dim * sizeof(double));
-  p.off_mean = take((size_t)p.kpad * sizeof(float));
-  p.off_xb = take(xr * p.kpad * 2);
-  p.off_yb = take(yr * p.kpad * 2);
-  p.off_norm = take(xr * sizeof(float));
-  p.off_cand = take(yr * p.ncand * sizeof(uint32_t));
-  p.off_cnt = take(yr * p.slices * sizeof(int));
-  p.off_buf = take(yr * p.slices * p.buflen * sizeof(uint64_t));
-  p.total_bytes = p.all_rows ? 0 : off;
+  WsWalk w;
+  p.off_part = w.reserve((size_t)p.chunks * dim * sizeof(double));
+  p.off_mean = w.reserve((size_t)p.kpad * sizeof(float));
+  p.off_xb = w.reserve(xr * p.kpad * 2);
+  p.off_yb = w.reserve(yr * p.kpad * 2);
+  p.off_norm = w.reserve(xr * sizeof(float));
+  p.off_cand = w.reserve(yr * p.ncand * sizeof(uint32_t));
+  p.off_cnt = w.reserve(yr * p.slices * sizeof(int));
+  p.off_buf = w.reserve(yr * p.slices * p.buflen * sizeof(uint64_t));
+  p.total_bytes = p.all_rows ? 0 : w.end();
   return p;
 }
 
@@ -554,24 +549,13 @@ int ann_run(const float *d_x, const float *d_y, int xrows, int yrows, int dim, i
       ProfScope prof("ann_coarse", stream);
       const dim3 grid(p.qblocks, p.slices);
       const int kg = p.kpad <= kKC ? p.kpad / 32 : 0;
-#define SPV_ANN_COARSE(SHAPE, KG)                                                                               \
-  hipLaunchKernelGGL((ann_coarse_kernel<SHAPE, KG>), grid, dim3(kThreads), 0, stream, xb, yb, norm, xrows, yrows, \
-                     p.kpad, p.slice_rows, p.slices, p.ncand, p.buflen, buf, cnt)
-#define SPV_ANN_COARSE_KG(SHAPE)                \
-  switch (kg) {                                 \
-    case 1: SPV_ANN_COARSE(SHAPE, 1); break;    \
-    case 2: SPV_ANN_COARSE(SHAPE, 2); break;    \
-    case 3: SPV_ANN_COARSE(SHAPE, 3); break;    \
-    case 4: SPV_ANN_COARSE(SHAPE, 4); break;    \
-    default: SPV_ANN_COARSE(SHAPE, 0); break;   \
-  }
-      if (p.mfma == 32) {
-        SPV_ANN_COARSE_KG(32)
-      } else {
-        SPV_ANN_COARSE_KG(16)
-      }
-#undef SPV_ANN_COARSE_KG
-#undef SPV_ANN_COARSE
+      pick(Ints<32, 16>{}, p.mfma, [&](auto SHAPE) {
+        return pick(Ints<1, 2, 3, 4, 0>{}, kg, [&](auto KG) {
+          hipLaunchKernelGGL((ann_coarse_kernel<decltype(SHAPE)::value, decltype(KG)::value>), grid, dim3(kThreads), 0,
+                             stream, xb, yb, norm, xrows, yrows, p.kpad, p.slice_rows, p.slices, p.ncand, p.buflen, buf, cnt);
+          return true;
+        });
+      });
     }
     SPV_HIP_CHECK(hipGetLastError());
     {

@@ -35,6 +35,7 @@
 // No MFMA: ||x||^2 + ||y||^2 - 2 x.y does not reproduce the sequential unfused sum.
 
 #include "common.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <cmath>
@@ -229,12 +230,6 @@ __global__ __launch_bounds__(kThreads) void bf_tile_kernel(const uint32_t *__res
 // the S x k partial keys, then k rounds of a wave-wide minimum: the lane holding it pops.
 // Writes idx uint64[N,k] ((size_t)-1 = none) and 32-bit dist[N,k] (+inf / INT_MAX = none).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, mask, 64);
-  const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), mask, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 template <int KB>
 __global__ __launch_bounds__(kThreads) void bf_merge_kernel(const uint64_t *__restrict__ part, int N, int S,
                                                             int k, uint32_t none_dist,
@@ -284,33 +279,20 @@ __global__ __launch_bounds__(kThreads) void bf_merge_kernel(const uint64_t *__re
 // ---- launch ---------------------------------------------------------------------------------
 int k_bucket(int k) { return k <= 2 ? 2 : k <= 8 ? 8 : 64; }
 
-template <bool INT, int PK, int KB>
+using KBuckets = Ints<2, 8, 64>;
+
+// the tile kernel of the plan's p kind and k bucket
+template <bool INT>
 void launch_tile(const void *x, const void *y, int M, int N, int dim, const BruteForcePlan &pl, int k, double p,
                  uint64_t *part, hipStream_t stream) {
-  hipLaunchKernelGGL((bf_tile_kernel<INT, PK, KB>), dim3(pl.qblocks, pl.slices), dim3(kThreads), 0, stream,
-                     static_cast<const uint32_t *>(x), static_cast<const uint32_t *>(y), M, N, dim, pl.slice_rows,
-                     pl.slices, k, p, part);
-}
-
-template <bool INT, int PK>
-void launch_tile_k(const void *x, const void *y, int M, int N, int dim, const BruteForcePlan &pl, int k,
-                   double p, uint64_t *part, hipStream_t stream) {
-  switch (k_bucket(k)) {
-    case 2: launch_tile<INT, PK, 2>(x, y, M, N, dim, pl, k, p, part, stream); break;
-    case 8: launch_tile<INT, PK, 8>(x, y, M, N, dim, pl, k, p, part, stream); break;
-    default: launch_tile<INT, PK, 64>(x, y, M, N, dim, pl, k, p, part, stream); break;
-  }
-}
-
-template <bool INT>
-void launch_tile_p(const void *x, const void *y, int M, int N, int dim, const BruteForcePlan &pl, int k,
-                   double p, uint64_t *part, hipStream_t stream) {
-  switch (bruteforce_p_kind(p)) {
-    case P_ONE: launch_tile_k<INT, P_ONE>(x, y, M, N, dim, pl, k, p, part, stream); break;
-    case P_TWO: launch_tile_k<INT, P_TWO>(x, y, M, N, dim, pl, k, p, part, stream); break;
-    case P_HALF: launch_tile_k<INT, P_HALF>(x, y, M, N, dim, pl, k, p, part, stream); break;
-    default: launch_tile_k<INT, P_GEN>(x, y, M, N, dim, pl, k, p, part, stream); break;
-  }
+  pick(Ints<P_ONE, P_TWO, P_HALF, P_GEN>{}, bruteforce_p_kind(p), [&](auto PK) {
+    return pick(KBuckets{}, k_bucket(k), [&](auto KB) {
+      hipLaunchKernelGGL((bf_tile_kernel<INT, decltype(PK)::value, decltype(KB)::value>), dim3(pl.qblocks, pl.slices),
+                         dim3(kThreads), 0, stream, static_cast<const uint32_t *>(x), static_cast<const uint32_t *>(y), M,
+                         N, dim, pl.slice_rows, pl.slices, k, p, part);
+      return true;
+    });
+  });
 }
 
 }  // namespace
@@ -359,16 +341,16 @@ int bruteforce_run(const void *d_x, const void *d_y, int is_int, int xrows, int 
     return set_error(SPV_ERR_INVALID, "idx and the workspace must be 8-byte aligned");
   const BruteForcePlan pl = bruteforce_plan(xrows, yrows, k, slices);
   if (pl.slices > 65535) return set_error(SPV_ERR_INVALID, "slices=%d > 65535", pl.slices);
-  // what the kernels touch, and what the header asks of a caller who forces the slice count (the plan's
-  // part_bytes, which spv_bruteforce_workspace_bytes reports, is that rounded up to 256)
-  const size_t need = (size_t)yrows * pl.slices * k * sizeof(uint64_t);
+  // the plan's part_bytes, which spv_bruteforce_workspace_bytes reports; of a caller who forces the slice count
+  // the header asks what the kernels touch (part_bytes is that rounded up to 256)
+  const size_t need = slices > 0 ? (size_t)yrows * pl.slices * k * sizeof(uint64_t) : pl.part_bytes;
   if (!d_ws || ws_bytes < need) return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, need);
   uint64_t *part = static_cast<uint64_t *>(d_ws);
   const double pd = (double)p;
   {
     ProfScope prof("bruteforce", stream);
-    if (is_int) launch_tile_p<true>(d_x, d_y, xrows, yrows, dim, pl, k, pd, part, stream);
-    else launch_tile_p<false>(d_x, d_y, xrows, yrows, dim, pl, k, pd, part, stream);
+    if (is_int) launch_tile<true>(d_x, d_y, xrows, yrows, dim, pl, k, pd, part, stream);
+    else launch_tile<false>(d_x, d_y, xrows, yrows, dim, pl, k, pd, part, stream);
   }
   SPV_HIP_CHECK(hipGetLastError());
   {
@@ -376,14 +358,11 @@ int bruteforce_run(const void *d_x, const void *d_y, int is_int, int xrows, int 
     const unsigned blocks = (unsigned)(((long long)yrows * 64 + kThreads - 1) / kThreads);
     const uint32_t none = is_int ? 0x7FFFFFFFu : 0x7F800000u;  // INT_MAX / +inf
     uint32_t *dist = static_cast<uint32_t *>(d_dist);
-    switch (k_bucket(k)) {
-      case 2: hipLaunchKernelGGL((bf_merge_kernel<2>), dim3(blocks), dim3(kThreads), 0, stream, part, yrows,
-                                 pl.slices, k, none, d_idx, dist); break;
-      case 8: hipLaunchKernelGGL((bf_merge_kernel<8>), dim3(blocks), dim3(kThreads), 0, stream, part, yrows,
-                                 pl.slices, k, none, d_idx, dist); break;
-      default: hipLaunchKernelGGL((bf_merge_kernel<64>), dim3(blocks), dim3(kThreads), 0, stream, part, yrows,
-                                  pl.slices, k, none, d_idx, dist); break;
-    }
+    pick(KBuckets{}, k_bucket(k), [&](auto KB) {
+      hipLaunchKernelGGL((bf_merge_kernel<decltype(KB)::value>), dim3(blocks), dim3(kThreads), 0, stream, part, yrows,
+                         pl.slices, k, none, d_idx, dist);
+      return true;
+    });
   }
   SPV_HIP_CHECK(hipGetLastError());
   return SPV_OK;

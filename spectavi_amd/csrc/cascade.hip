@@ -44,6 +44,7 @@
 // smallest (dist, idx) pairs of the candidate set, lexicographic.
 
 #include "common.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -697,31 +698,7 @@ __global__ __launch_bounds__(256) void bucket_segsum_kernel(const uint32_t *__re
 
 // in-place exclusive scan of segsum[j][0..nseg) (nseg <= 4097 for 2^22 buckets)
 __global__ __launch_bounds__(1024) void bucket_segscan_kernel(uint32_t *__restrict__ segsum, int nseg) {
-  __shared__ uint32_t wsum[16];
-  __shared__ uint32_t carry;
-  uint32_t *c = segsum + (size_t)blockIdx.x * nseg;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nseg; base += 1024) {
-    const int e = base + t;
-    const uint32_t v = e < nseg ? c[e] : 0u;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int k = 0; k < w; ++k) woff += wsum[k];
-    const uint32_t excl = carry + woff + incl - v;
-    if (e < nseg) c[e] = excl;
-    __syncthreads();
-    if (t == 1023) carry = excl + v;
-    __syncthreads();
-  }
+  block_scan_inplace(segsum + (size_t)blockIdx.x * nseg, nseg);
 }
 
 __global__ __launch_bounds__(1024) void bucket_scan_kernel(uint32_t *__restrict__ counts, int nb,
@@ -730,20 +707,9 @@ __global__ __launch_bounds__(1024) void bucket_scan_kernel(uint32_t *__restrict_
   __shared__ uint32_t wsum[16];
   const int j = blockIdx.y, seg = blockIdx.x;
   uint32_t *c = counts + (size_t)j * (nb + 1);
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int e = seg * kScanSeg + t;
+  const int e = seg * kScanSeg + threadIdx.x;
   const uint32_t v = e <= nb ? c[e] : 0u;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wsum[w] = incl;
-  __syncthreads();
-  uint32_t woff = segoff[(size_t)j * nseg + seg];
-  for (int k = 0; k < w; ++k) woff += wsum[k];
-  const uint32_t excl = woff + incl - v;
+  const uint32_t excl = block_scan_excl(v, wsum) + segoff[(size_t)j * nseg + seg];
   if (e <= nb) c[e] = excl;
 }
 
@@ -796,12 +762,6 @@ __device__ __forceinline__ void top2_insert_distinct(uint64_t &k1, uint64_t &k2,
   } else if (k < k2) {
     k2 = k;
   }
-}
-
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, mask, 64);
-  const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), mask, 64);
-  return ((uint64_t)hi << 32) | lo;
 }
 
 // two smallest DISTINCT keys of {a1,a2,b1,b2}
@@ -923,12 +883,7 @@ __global__ __launch_bounds__(kThreads) void probe_refine_kernel(
     }
     // exclusive offsets of the buckets in the list: scan over the first lane of each probe
     const uint32_t mylen = psub == 0 ? len : 0u;
-    uint32_t incl = mylen;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += o;
-    }
+    const uint32_t incl = wave_scan_incl(mylen, lane);
     const uint32_t total = __shfl(incl, 63, 64);
     if (!check_code && total <= (uint32_t)kListCap) {
       // fast path: the lanes of a probe copy its bucket into the shared list
@@ -971,8 +926,8 @@ __global__ __launch_bounds__(kThreads) void probe_refine_kernel(
   // argmin-2 butterfly over the 8 lane groups (keys are uniform inside a group)
 #pragma unroll
   for (int msk = 8; msk < 64; msk <<= 1) {
-    const uint64_t b1 = shfl_xor64(k1, msk);
-    const uint64_t b2 = shfl_xor64(k2, msk);
+    const uint64_t b1 = shfl_xor_u64(k1, msk);
+    const uint64_t b2 = shfl_xor_u64(k2, msk);
     merge_distinct(k1, k2, b1, b2);
   }
   if (lane == 0) {
@@ -1338,31 +1293,26 @@ CascadePlan cascade_plan(int xrows, int yrows, int dim, int m, int n, int g) {
   P.mc = (m + 3) / 4 * 4;  // accumulators per table: multiples of 4 (one ds_read_b128 each)
   P.hb = bucket_bits(m);
   const size_t nb1 = ((size_t)1 << P.hb) + 1;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += round_up(std::max<size_t>(bytes, 16), 256);
-    return o;
-  };
-  P.off_dictp = take((size_t)n * dim * P.mc * sizeof(float));
-  P.off_dictm = take((size_t)(dim + 16) * 64 * sizeof(float));  // MFMA layout, at most 64 columns, rows padded to a multiple of 32
-  P.off_ux = take((size_t)xrows * dim);
-  P.off_uy = take((size_t)yrows * dim);
-  P.off_xcodes = take((size_t)n * xrows * sizeof(uint32_t));
-  P.off_ysign = take((size_t)n * yrows * sizeof(uint32_t));
-  P.off_ymask = take((size_t)n * yrows * sizeof(uint32_t));
-  P.off_bstart = take((size_t)2 * n * nb1 * sizeof(uint32_t));  // [n] database tables, then [n] query tables (one scan)
-  P.off_order = take((size_t)n * xrows * sizeof(uint32_t));
-  P.off_ranks = take((size_t)n * xrows * sizeof(uint32_t));
-  P.off_segsum = take((size_t)2 * n * ((nb1 + kScanSeg - 1) / kScanSeg) * sizeof(uint32_t));
+  WsWalk w(nullptr, 16);  // no piece shorter than 16 bytes
+  P.off_dictp = w.reserve((size_t)n * dim * P.mc * sizeof(float));
+  P.off_dictm = w.reserve((size_t)(dim + 16) * 64 * sizeof(float));  // MFMA layout, at most 64 columns, rows padded to a multiple of 32
+  P.off_ux = w.reserve((size_t)xrows * dim);
+  P.off_uy = w.reserve((size_t)yrows * dim);
+  P.off_xcodes = w.reserve((size_t)n * xrows * sizeof(uint32_t));
+  P.off_ysign = w.reserve((size_t)n * yrows * sizeof(uint32_t));
+  P.off_ymask = w.reserve((size_t)n * yrows * sizeof(uint32_t));
+  P.off_bstart = w.reserve((size_t)2 * n * nb1 * sizeof(uint32_t));  // [n] database tables, then [n] query tables (one scan)
+  P.off_order = w.reserve((size_t)n * xrows * sizeof(uint32_t));
+  P.off_ranks = w.reserve((size_t)n * xrows * sizeof(uint32_t));
+  P.off_segsum = w.reserve((size_t)2 * n * ((nb1 + kScanSeg - 1) / kScanSeg) * sizeof(uint32_t));
   // the probe's per-table query order (counting sort of the queries by sign code) and what a
   // query carries from one table's pass to the next
   P.off_qbstart = P.off_bstart + (size_t)n * nb1 * sizeof(uint32_t);
-  P.off_qorder = take((size_t)n * yrows * sizeof(uint32_t));
-  P.off_qranks = take((size_t)n * yrows * sizeof(uint32_t));
-  P.off_partial = take((size_t)yrows * 2 * sizeof(uint64_t));
-  P.off_pvisited = take((size_t)yrows * sizeof(int32_t));
-  P.total = off;
+  P.off_qorder = w.reserve((size_t)n * yrows * sizeof(uint32_t));
+  P.off_qranks = w.reserve((size_t)n * yrows * sizeof(uint32_t));
+  P.off_partial = w.reserve((size_t)yrows * 2 * sizeof(uint64_t));
+  P.off_pvisited = w.reserve((size_t)yrows * sizeof(int32_t));
+  P.total = w.end();
 
   // Projection: on the matrix cores when the n*m hyperplanes fit 64 columns, else on the VALU.
   const long long nm = (long long)n * m;
@@ -1438,59 +1388,46 @@ size_t cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int 
 
 namespace {
 
-// f(std::integral_constant<int, V>{}) for the V among Vs that equals v, if there is one.
-template <int... Vs, typename F>
-void pick(int v, F f) {
-  ((v == Vs ? f(std::integral_constant<int, Vs>{}) : void()), ...);
-}
-
-// pick over a projection family's query-side GMAX values QGs; the database side has GMAX 1 alone.
-template <bool IS_QUERY, int... QGs, typename F>
-void pick_gmax(int gmax_q, F f) {
-  if constexpr (IS_QUERY) pick<QGs...>(gmax_q, f);
-  else f(std::integral_constant<int, 1>{});
-}
+// A projection family's GMAX values: QGs on the query side; the database side has GMAX 1 alone.
+template <bool IS_QUERY, int... QGs>
+using GMaxes = std::conditional_t<IS_QUERY, Ints<QGs...>, Ints<1>>;
 
 // The plan's projection over the database rows or the query rows.  False if the plan names no
-// instantiation.
+// instantiation.  (The lists descend: the order these kernels have always had in the code object.)
 template <bool IS_QUERY>
 bool launch_project(const CascadePlan &P, const float *rows, int nrows, int dim, int m, int n, int g,
                     const float *dict, uint32_t *codes, uint32_t *masks, uint8_t *img, uint32_t *counts,
                     uint32_t *ranks, uint32_t hbmask, int nb, hipStream_t stream) {
   if (nrows <= 0) return true;
   const dim3 grid((nrows + P.proj_rows - 1) / P.proj_rows), block(kThreads);
-  bool launched = false;
+  const int gmax = IS_QUERY ? P.gmax_q : 1;
   auto go = [&](auto kernel, size_t lds) {
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, rows, nrows, dim, m, n, g, dict, codes, masks, img,
                        counts, ranks, hbmask, nb);
-    launched = true;
+    return true;
   };
-  if (P.family == 0) {
-    pick<4, 8, 12, 16, 20, 24, 28, 32>(P.pa, [&](auto MC) {
+  if (P.family == 0)
+    return pick(Ints<32, 28, 24, 20, 16, 12, 8, 4>{}, P.pa, [&](auto MC) {
       constexpr int mc = decltype(MC)::value;
-      pick_gmax<IS_QUERY, 4, 16>(P.gmax_q, [&](auto G) {
-        go(project_kernel<mc, (mc <= 24 ? 2 : 1), IS_QUERY, decltype(G)::value>, 0);
+      return pick(GMaxes<IS_QUERY, 16, 4>{}, gmax, [&](auto G) {
+        return go(project_kernel<mc, (mc <= 24 ? 2 : 1), IS_QUERY, decltype(G)::value>, 0);
       });
     });
-  } else if (P.family == 1) {
-    pick<1, 2, 3, 4>(P.pa, [&](auto CT) {
-      pick_gmax<IS_QUERY, 2, 4, 16>(P.gmax_q, [&](auto G) {
-        constexpr int ct = decltype(CT)::value, gmax = decltype(G)::value;
-        if (P.pb) go(project_mfma_kernel<ct, IS_QUERY, gmax, true>, 0);
-        else go(project_mfma_kernel<ct, IS_QUERY, gmax, false>, 0);
+  if (P.family == 1)
+    return pick(Ints<4, 3, 2, 1>{}, P.pa, [&](auto CT) {
+      return pick(GMaxes<IS_QUERY, 16, 4, 2>{}, gmax, [&](auto G) {
+        constexpr int ct = decltype(CT)::value, gm = decltype(G)::value;
+        return P.pb ? go(project_mfma_kernel<ct, IS_QUERY, gm, true>, 0) : go(project_mfma_kernel<ct, IS_QUERY, gm, false>, 0);
       });
     });
-  } else {
-    pick<0, 1, 2, 3>(P.pa, [&](auto CT) {
-      pick<1, 2>(P.pb, [&](auto NG) {
-        pick_gmax<IS_QUERY, 2, 16>(P.gmax_q, [&](auto G) {
-          constexpr int ng = decltype(NG)::value;  // the left-over hyperplanes' LDS table [dim/4][4][4] per group
-          go(project_mfma4_kernel<decltype(CT)::value, ng, IS_QUERY, decltype(G)::value>, (size_t)ng * dim * 16);
-        });
+  return pick(Ints<3, 2, 1, 0>{}, P.pa, [&](auto CT) {
+    return pick(Ints<2, 1>{}, P.pb, [&](auto NG) {
+      return pick(GMaxes<IS_QUERY, 16, 2>{}, gmax, [&](auto G) {
+        constexpr int ng = decltype(NG)::value;  // the left-over hyperplanes' LDS table [dim/4][4][4] per group
+        return go(project_mfma4_kernel<decltype(CT)::value, ng, IS_QUERY, decltype(G)::value>, (size_t)ng * dim * 16);
       });
     });
-  }
-  return launched;
+  });
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 #include <functional>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/spectavi_amd.h"
@@ -69,6 +70,45 @@ struct ProfScope {
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// A workspace layout is stated once, as a function of the shape that takes its pieces from a WsWalk one after
+// another.  The size query walks it from a null base and reports end(); the run walks it from the caller's buffer,
+// gets its pointers and holds the same end() against the bytes it was given.  A piece starts on a multiple of 256
+// bytes from the base and takes at least min_piece bytes.
+struct WsWalk {
+  explicit WsWalk(void *base = nullptr, size_t min_piece = 0) : base_(static_cast<unsigned char *>(base)), min_(min_piece) {}
+  size_t reserve(size_t bytes) {  // the offset of the next piece
+    const size_t at = end_;
+    end_ += round_up(std::max(bytes, min_), 256);
+    return at;
+  }
+  template <typename T = unsigned char>
+  T *take(size_t bytes) {  // the next piece itself; null on a walk without a base
+    const size_t at = reserve(bytes);
+    return base_ ? reinterpret_cast<T *>(base_ + at) : nullptr;
+  }
+  size_t end() const { return end_; }
+
+ private:
+  unsigned char *base_;
+  size_t min_, end_ = 0;
+};
+
+// Small compile-time tables of template arguments.  pick: f(std::integral_constant<int, V>{}), a launch that
+// returns true, for the first V among Vs that equals v; false if there is none.  first_at_least: the first V >= v
+// (Vs ascending), else 0.  hipcc emits kernel instantiations in the order the host code first names them: pick is
+// a left fold, and the lists name their values in the order the code objects have always had.
+template <int... Vs> struct Ints {};
+template <int... Vs, typename F>
+bool pick(Ints<Vs...>, int v, F f) {
+  return (... || (v == Vs && f(std::integral_constant<int, Vs>{})));
+}
+template <int... Vs>
+int first_at_least(Ints<Vs...>, int v) {
+  int r = 0;
+  ((r == 0 && v <= Vs ? r = Vs : 0), ...);
+  return r;
+}
+
 // ---- L1 2-NN (l1k2.hip, l1k2_prune.hip) ---------------------------------------------
 // The SPECTAVI_L1K2_* variables, read once per process.
 struct L1K2Knobs {
@@ -105,6 +145,8 @@ struct L1K2Plan {
   int bound;             // ... and the table it runs with (kL1K2BoundRecipe / kL1K2BoundTuned)
   unsigned work_grid;    // tile kernel over the bound path's work list: kWorkSub blocks for every workgroup there
   unsigned merge_grid;
+  size_t thr_words;      // bound path: shared thresholds (an even number: the counters behind them are 64-bit)
+  size_t init_words;     // ... and the dwords l1k2_thr_init_kernel sets: thresholds, counters, the work list's header
   // workspace: byte offsets, in this order.  Padded copies (empty unless `padded`), partial top-2 keys, then the
   // bound path's scratch (empty unless dim 128 with >= 32 database rows): int8 features, shared thresholds, counters,
   // work list {count, -, (query block of 256, slice) ...} of the workgroups that gave the bound up.
@@ -127,9 +169,9 @@ int l1k2_set_bound(int which);                               // -1 default (tune
 int l1k2_get_bound();
 int l1k2_set_prune(int mode);                                // -1 auto, 0 never, 1 wherever possible; returns the mode before
 int l1k2_get_prune();
-// The bound path's part of a plan whose slicing is done: its scratch from byte `base` of the workspace on, and
-// path / bound_grid where the prune mode takes the path for this shape.  Returns the end of the scratch.
-size_t l1k2_prune_plan(int xrows, int yrows, int dim, size_t base, L1K2Plan *p);
+// The bound path's part of a plan whose slicing is done: its scratch, the next pieces of the plan's walk, and
+// path / bound_grid where the prune mode takes the path for this shape.
+void l1k2_prune_plan(int xrows, int yrows, int dim, WsWalk *w, L1K2Plan *p);
 // features, thresholds and the bound-and-survivor kernel; writes the partial keys l1k2_merge_kernel reads, but
 // for the workgroups on the work list, whose keys l1k2_run has yet to compute with the tile kernel
 int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *ws,

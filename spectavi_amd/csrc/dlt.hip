@@ -858,15 +858,29 @@ __global__ __launch_bounds__(kDltThreads) void best_mask_kernel(const unsigned c
 
 }  // namespace
 
-size_t ransac_workspace_bytes(int nF, long long npt, bool want_mask) {
-  size_t b = round_up((size_t)nF * 48 * sizeof(double), 256);      // cameras
-  b += round_up((size_t)nF * 4 * sizeof(int), 256);                 // inlier counts
-  b += round_up((size_t)nF * sizeof(int), 256);                     // gate flags
-  b += round_up(((size_t)nF + 1) * sizeof(int), 256);               // the candidates that passed the gate + their count
-  if (want_mask) b += round_up((size_t)nF * 4 * (size_t)npt, 256);  // per-camera inlier masks
-  b += dlt_score_workspace_bytes(4 * nF, npt);                      // the scorer's work list
+// The workspace of ransac_process_run, stated once: the size query walks it from a null base.
+struct RansacBufs {
+  double *cams;
+  int *counts, *gated, *nlive;  // nlive: [0] = count, [1..] = the ids of the candidates that passed the gate
+  unsigned char *mask4;         // per-camera inlier masks (null: no mask wanted)
+  void *score_ws;               // the scorer's work list
+  size_t score_bytes, end;
+};
+static RansacBufs ransac_layout(void *base, int nF, long long npt, bool want_mask) {
+  WsWalk w(base);
+  RansacBufs b{};
+  b.cams = w.take<double>((size_t)nF * 48 * sizeof(double));
+  b.counts = w.take<int>((size_t)nF * 4 * sizeof(int));
+  b.gated = w.take<int>((size_t)nF * sizeof(int));
+  b.nlive = w.take<int>(((size_t)nF + 1) * sizeof(int));
+  if (want_mask) b.mask4 = w.take((size_t)nF * 4 * (size_t)npt);
+  b.score_bytes = dlt_score_workspace_bytes(4 * nF, npt);
+  b.score_ws = w.take(b.score_bytes);
+  b.end = w.end();
   return b;
 }
+
+size_t ransac_workspace_bytes(int nF, long long npt, bool want_mask) { return ransac_layout(nullptr, nF, npt, want_mask).end; }
 
 int ransac_process_run(const double *d_Fs, int nF, long long npt, const double *d_x0, const double *d_x1,
                        double ratio_allowed, double required_percent, double max_error, int find_best,
@@ -879,40 +893,28 @@ int ransac_process_run(const double *d_Fs, int nF, long long npt, const double *
     return set_error(SPV_ERR_INVALID, "null device pointer");
   if (nF > 16383) return set_error(SPV_ERR_INVALID, "more than 16383 candidates per call");
   if (npt == 0) return set_error(SPV_ERR_INVALID, "no correspondences");
-  const size_t need = ransac_workspace_bytes(nF, npt, d_mask != nullptr);
-  if (!d_ws || ws_bytes < need) return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, need);
-  unsigned char *ws = static_cast<unsigned char *>(d_ws);
-  double *cams = reinterpret_cast<double *>(ws);
-  ws += round_up((size_t)nF * 48 * sizeof(double), 256);
-  int *counts = reinterpret_cast<int *>(ws);
-  ws += round_up((size_t)nF * 4 * sizeof(int), 256);
-  int *gated = reinterpret_cast<int *>(ws);
-  ws += round_up((size_t)nF * sizeof(int), 256);
-  int *nlive = reinterpret_cast<int *>(ws);  // [0] = count, [1..] = candidate ids
-  int *live = nlive + 1;
-  ws += round_up(((size_t)nF + 1) * sizeof(int), 256);
-  unsigned char *mask4 = d_mask ? ws : nullptr;
-  if (d_mask) ws += round_up((size_t)nF * 4 * (size_t)npt, 256);
-  const size_t score_ws = dlt_score_workspace_bytes(4 * nF, npt);
+  const RansacBufs b = ransac_layout(d_ws, nF, npt, d_mask != nullptr);
+  if (!d_ws || ws_bytes < b.end) return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, b.end);
+  int *live = b.nlive + 1;
   const int fblocks = (nF + kDltThreads - 1) / kDltThreads;
-  SPV_HIP_CHECK(hipMemsetAsync(nlive, 0, sizeof(int), stream));
+  SPV_HIP_CHECK(hipMemsetAsync(b.nlive, 0, sizeof(int), stream));
   {
     ProfScope prof("ransac_cameras", stream);
     hipLaunchKernelGGL(essential_cameras_kernel, dim3(fblocks), dim3(kDltThreads), 0, stream, d_Fs, nF,
-                       ratio_allowed, cams, d_ratio, d_E, gated, live, nlive);
+                       ratio_allowed, b.cams, d_ratio, d_E, b.gated, live, b.nlive);
     SPV_HIP_CHECK(hipGetLastError());
   }
   const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};  // Camera(): Identity(3,4), src/Camera.h:27
   // a mask row of a gated camera is never looked at (best_mask_kernel only reads the best camera's)
-  SPV_TRY(dlt_score_run(P0, cams, 4 * nF, npt, d_x0, d_x1, max_error, counts, mask4, ws, score_ws, stream, live, nlive,
-                        score_rows_cap));
-  hipLaunchKernelGGL(select_camera_kernel, dim3(fblocks), dim3(kDltThreads), 0, stream, counts, gated, cams, nF, npt,
-                     required_percent, find_best, d_success, d_inlier_count, d_best_cam, d_best_P, d_counts4);
+  SPV_TRY(dlt_score_run(P0, b.cams, 4 * nF, npt, d_x0, d_x1, max_error, b.counts, b.mask4, b.score_ws, b.score_bytes,
+                        stream, live, b.nlive, score_rows_cap));
+  hipLaunchKernelGGL(select_camera_kernel, dim3(fblocks), dim3(kDltThreads), 0, stream, b.counts, b.gated, b.cams, nF,
+                     npt, required_percent, find_best, d_success, d_inlier_count, d_best_cam, d_best_P, d_counts4);
   SPV_HIP_CHECK(hipGetLastError());
   if (d_mask) {
     const unsigned mb = (unsigned)std::min<long long>((npt + kDltThreads - 1) / kDltThreads, 1024);
-    hipLaunchKernelGGL(best_mask_kernel, dim3(mb, (unsigned)nF), dim3(kDltThreads), 0, stream, mask4, d_best_cam, npt,
-                       d_mask);
+    hipLaunchKernelGGL(best_mask_kernel, dim3(mb, (unsigned)nF), dim3(kDltThreads), 0, stream, b.mask4, d_best_cam,
+                       npt, d_mask);
     SPV_HIP_CHECK(hipGetLastError());
   }
   return SPV_OK;

@@ -39,6 +39,7 @@
 // SADs for the survivors only; everything else runs here.  See DESIGN.md 4.1.
 
 #include "common.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -432,12 +433,6 @@ __device__ __forceinline__ void merge_pair(uint64_t &a1, uint64_t &a2, uint64_t 
   a2 = hi < m2 ? hi : m2;
 }
 
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, mask, 64);
-  const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), mask, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 template <int LPQ>
 __global__ __launch_bounds__(kThreads) void l1k2_merge_kernel(const uint64_t *__restrict__ part,
                                                               int N, int S,
@@ -479,21 +474,6 @@ __global__ __launch_bounds__(kThreads) void pad_rows_kernel(const uint8_t *__res
     if (c < dim) v = *reinterpret_cast<const uint32_t *>(src + r * dim + c);  // dim % 16 == 0
     reinterpret_cast<uint32_t *>(dst)[e] = v;
   }
-}
-
-// Small compile-time tables of template arguments.  pick: f(std::integral_constant<int, V>{}), a launch that
-// returns true, for the V among Vs that equals v; false if there is none.  first_at_least: the first V >= v
-// (Vs ascending), else 0.
-template <int... Vs> struct Ints {};
-template <int... Vs, typename F>
-bool pick(Ints<Vs...>, int v, F f) {
-  return (... || (v == Vs && f(std::integral_constant<int, Vs>{})));
-}
-template <int... Vs>
-int first_at_least(Ints<Vs...>, int v) {
-  int r = 0;
-  ((r == 0 && v <= Vs ? r = Vs : 0), ...);
-  return r;
 }
 
 // Row widths in bytes with a tile-kernel instantiation; other dims up to 256 are zero-padded to the next one.
@@ -601,10 +581,12 @@ L1K2Plan l1k2_plan(int xrows, int yrows, int dim) {
   p.merge_lanes = p.slices <= 4 ? 1 : p.slices <= 32 ? 8 : 64;
   p.merge_grid = (unsigned)(((long long)yrows * p.merge_lanes + kThreads - 1) / kThreads);
 
-  p.off_pad_y = p.padded ? round_up((size_t)xrows * p.dim_pad, 256) : 0;
-  p.off_part = p.off_pad_y + (p.padded ? round_up((size_t)yrows * p.dim_pad, 256) : 0);
-  p.off_feat_x = p.off_part + round_up((size_t)std::max(yrows, 1) * p.slices * 2 * sizeof(uint64_t), 256);
-  p.total_bytes = l1k2_prune_plan(xrows, yrows, dim, p.off_feat_x, &p);
+  WsWalk w;
+  p.off_pad_x = w.reserve(p.padded ? (size_t)xrows * p.dim_pad : 0);
+  p.off_pad_y = w.reserve(p.padded ? (size_t)yrows * p.dim_pad : 0);
+  p.off_part = w.reserve((size_t)std::max(yrows, 1) * p.slices * 2 * sizeof(uint64_t));
+  l1k2_prune_plan(xrows, yrows, dim, &w, &p);
+  p.total_bytes = w.end();
   // two queries per lane in blocks of 128 lanes = the 256 queries of a bound workgroup, kWorkSub blocks for each;
   // blocks beyond the list's length leave at once
   if (p.path == kL1K2Bound) p.work_grid = p.bound_grid.x * p.bound_grid.y * kWorkSub;

@@ -692,17 +692,19 @@ int l1k2_prune_last_stats(unsigned long long out[3]) { return read_stats(t_last_
 //    that do not pay has not grown (profiles/r08_prune_breakeven.jsonl).
 constexpr int kPruneMinX = 262144, kPruneMinSlice = 32768;
 
-size_t l1k2_prune_plan(int xrows, int yrows, int dim, size_t base, L1K2Plan *p) {
-  p->off_feat_x = p->off_feat_y = p->off_thr = p->off_stats = p->off_work = base;
-  if (dim != 128 || xrows < kTileRows || yrows < 1) return base;  // no such path, no scratch
+void l1k2_prune_plan(int xrows, int yrows, int dim, WsWalk *w, L1K2Plan *p) {
+  p->off_feat_x = p->off_feat_y = p->off_thr = p->off_stats = p->off_work = w->end();
+  if (dim != 128 || xrows < kTileRows || yrows < 1) return;  // no such path, no scratch
   // The scratch is a function of the shape alone, whether or not the path is switched on: the features, then
   // one block of dwords: thresholds (an even number: the counters are 64-bit), the counters, the work list
   // (its length, then one (query block, slice) pair for each workgroup there can be).
   const unsigned qgroups = (unsigned)((yrows + kQPerBlock - 1) / kQPerBlock);
-  const size_t nthr = ((size_t)yrows + 1) / 2 * 2;
-  p->off_feat_y = base + round_up((size_t)xrows * 512, 256);
-  p->off_thr = p->off_feat_y + round_up((size_t)yrows * 512, 256);
-  p->off_stats = p->off_thr + nthr * 4;
+  p->thr_words = ((size_t)yrows + 1) / 2 * 2;
+  p->init_words = p->thr_words + kStatWords + 2;
+  p->off_feat_x = w->reserve((size_t)xrows * 512);
+  p->off_feat_y = w->reserve((size_t)yrows * 512);
+  p->off_thr = w->reserve((p->init_words + 2 * (size_t)qgroups * p->slices) * 4);
+  p->off_stats = p->off_thr + p->thr_words * 4;
   p->off_work = p->off_stats + kStatWords * 4;
   const int mode = l1k2_get_prune();
   const bool wanted = mode == 1 || (mode != 0 && xrows >= kPruneMinX && p->slice_rows >= kPruneMinSlice);
@@ -715,7 +717,6 @@ size_t l1k2_prune_plan(int xrows, int yrows, int dim, size_t base, L1K2Plan *p) 
     p->path = kL1K2Bound;
     p->bound_grid = dim3(qgroups, (unsigned)p->slices);
   }
-  return p->off_thr + round_up((nthr + kStatWords + 2 + 2 * (size_t)qgroups * p->slices) * 4, 256);
 }
 
 int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, const L1K2Plan &p, uint8_t *ws,
@@ -727,7 +728,6 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   uint32_t *thr = reinterpret_cast<uint32_t *>(ws + p.off_thr);
   unsigned long long *stats = reinterpret_cast<unsigned long long *>(ws + p.off_stats);
   uint32_t *work = reinterpret_cast<uint32_t *>(ws + p.off_work);
-  const size_t nthr = (p.off_stats - p.off_thr) / 4;
 
   static const FeatTable tabs[2] = {feat_table(l1k2_bound_of(kL1K2BoundRecipe)), feat_table(l1k2_bound_of(kL1K2BoundTuned))};
   const FeatTable &tab = tabs[p.bound == kL1K2BoundTuned];
@@ -752,8 +752,8 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
                      xw, tab);
   hipLaunchKernelGGL(l1k2_feature_kernel, blocks(yw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_y), fy,
                      yw, tab);
-  hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(nthr + kStatWords + 2), dim3(kThreads), 0, stream, thr, nthr,
-                     nthr + kStatWords + 2);
+  hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(p.init_words), dim3(kThreads), 0, stream, thr, p.thr_words,
+                     p.init_words);
 #ifdef SPV_L1K2_PHASE_STAMPS
   const size_t nstamp = (size_t)p.bound_grid.x * p.bound_grid.y * kWaves * (kPhases + 1);
   unsigned long long *d_stamps = nullptr;

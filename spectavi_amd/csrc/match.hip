@@ -16,6 +16,7 @@
 // lane), an exclusive scan of the block counts (one workgroup), an ordered scatter.
 
 #include "common.h"
+#include "device_util.h"
 
 namespace spv {
 namespace {
@@ -64,33 +65,10 @@ __global__ __launch_bounds__(kThreads) void ratio_count_kernel(const uint64_t *_
 // in-place exclusive scan of counts[0..n); counts[n] and *total receive the sum
 __global__ __launch_bounds__(1024) void block_scan_kernel(int *__restrict__ counts, int n,
                                                           int *__restrict__ total) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int e = base + t;
-    const int v = e < n ? counts[e] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int k = 0; k < w; ++k) woff += wsum[k];
-    const int excl = carry + woff + incl - v;
-    if (e < n) counts[e] = excl;
-    __syncthreads();
-    if (t == 1023) carry = excl + v;
-    __syncthreads();
-  }
-  if (t == 0) {
-    counts[n] = carry;
-    *total = carry;
+  const int sum = block_scan_inplace(counts, n);
+  if (threadIdx.x == 0) {
+    counts[n] = sum;
+    *total = sum;
   }
 }
 

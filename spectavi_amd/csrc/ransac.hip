@@ -354,8 +354,6 @@ int seven_point_run(const double *d_x, const double *d_xp, int n, double *d_Fs, 
   return SPV_OK;
 }
 
-size_t ransac_fit_state_bytes() { return round_up(sizeof(FitState), 256); }
-
 // Tries per batch: three candidates each, at most 16383 candidates per ransac_process_run, and about
 // 2e9 (camera, correspondence) solves so that one batch stays in the tens of milliseconds.
 int ransac_fit_batch_limit(long long npt) {
@@ -363,57 +361,43 @@ int ransac_fit_batch_limit(long long npt) {
   return (int)std::max<long long>(1, std::min<long long>(16383 / 3, by_work));
 }
 
-size_t ransac_fit_workspace_bytes(int batch, long long npt) {
-  const int nc = 3 * batch;
-  size_t b = ransac_fit_state_bytes();
-  b += round_up((size_t)batch * 7 * sizeof(int), 256);      // samples
-  b += round_up((size_t)nc * 9 * sizeof(double), 256);      // candidate F
-  b += 3 * round_up((size_t)nc * sizeof(int), 256);         // ok, inlier count, best camera
-  b += round_up((size_t)nc * 12 * sizeof(double), 256);     // best camera matrices
-  b += round_up((size_t)npt, 256);                          // the winner's inlier mask
-  b += ransac_workspace_bytes(nc, npt, false);
-  b += ransac_workspace_bytes(1, npt, true);
-  return b;
-}
-
 namespace {
+// The workspace of ransac_fit_run, stated once: the size query walks it from a null base.
 struct FitBuffers {
   FitState *state;
   int *samples;
-  double *Fs;
+  double *Fs;  // candidate F
   int *ok, *count, *best_cam;
   double *best_P;
-  unsigned char *mask;
+  unsigned char *mask;  // the winner's inlier mask
   void *ws;
   size_t ws_bytes;
   void *ws1;
-  size_t ws1_bytes;
+  size_t ws1_bytes, end;
 };
 
 FitBuffers carve(void *d_ws, int batch, long long npt) {
   const int nc = 3 * batch;
-  unsigned char *p = static_cast<unsigned char *>(d_ws);
+  WsWalk w(d_ws);
   FitBuffers b;
-  auto take = [&](size_t bytes) {
-    unsigned char *q = p;
-    p += round_up(bytes, 256);
-    return q;
-  };
-  b.state = reinterpret_cast<FitState *>(take(sizeof(FitState)));
-  b.samples = reinterpret_cast<int *>(take((size_t)batch * 7 * sizeof(int)));
-  b.Fs = reinterpret_cast<double *>(take((size_t)nc * 9 * sizeof(double)));
-  b.ok = reinterpret_cast<int *>(take((size_t)nc * sizeof(int)));
-  b.count = reinterpret_cast<int *>(take((size_t)nc * sizeof(int)));
-  b.best_cam = reinterpret_cast<int *>(take((size_t)nc * sizeof(int)));
-  b.best_P = reinterpret_cast<double *>(take((size_t)nc * 12 * sizeof(double)));
-  b.mask = take((size_t)npt);
+  b.state = w.take<FitState>(sizeof(FitState));
+  b.samples = w.take<int>((size_t)batch * 7 * sizeof(int));
+  b.Fs = w.take<double>((size_t)nc * 9 * sizeof(double));
+  b.ok = w.take<int>((size_t)nc * sizeof(int));
+  b.count = w.take<int>((size_t)nc * sizeof(int));
+  b.best_cam = w.take<int>((size_t)nc * sizeof(int));
+  b.best_P = w.take<double>((size_t)nc * 12 * sizeof(double));
+  b.mask = w.take((size_t)npt);
   b.ws_bytes = ransac_workspace_bytes(nc, npt, false);
-  b.ws = take(b.ws_bytes);
+  b.ws = w.take(b.ws_bytes);
   b.ws1_bytes = ransac_workspace_bytes(1, npt, true);
-  b.ws1 = take(b.ws1_bytes);
+  b.ws1 = w.take(b.ws1_bytes);
+  b.end = w.end();
   return b;
 }
 }  // namespace
+
+size_t ransac_fit_workspace_bytes(int batch, long long npt) { return carve(nullptr, batch, npt).end; }
 
 // d_x0, d_x1: double[npt,3] on the device.  next_samples(first_try, n, dst) fills the 7-subsets of
 // tries [first_try, first_try + n) into host memory.  Host outputs: *success, essential double[9],
@@ -427,9 +411,8 @@ int ransac_fit_run(const double *d_x0, const double *d_x1, long long npt, double
   if (npt < 1 || max_tries < 0) return set_error(SPV_ERR_INVALID, "bad count");
   if (!d_x0 || !d_x1) return set_error(SPV_ERR_INVALID, "null device pointer");
   if (batch < 1 || batch > 16383 / 3) return set_error(SPV_ERR_INVALID, "batch %d", batch);
-  if (!d_ws || ws_bytes < ransac_fit_workspace_bytes(batch, npt))
-    return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, ransac_fit_workspace_bytes(batch, npt));
   const FitBuffers b = carve(d_ws, batch, npt);
+  if (!d_ws || ws_bytes < b.end) return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, b.end);
   SPV_HIP_CHECK(hipMemsetAsync(b.state, 0, sizeof(FitState), stream));
   // two host buffers: the subsets of the next batch are drawn while the device works on this one
   std::vector<int> host_a((size_t)batch * 7), host_b((size_t)batch * 7);

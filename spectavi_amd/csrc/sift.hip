@@ -667,32 +667,21 @@ SiftLayout sift_layout(int wid, int hgt) {
   SiftLayout l{};
   l.N = (size_t)(2 * wid) * (size_t)(2 * hgt);
   const size_t rows = 3 * (size_t)(2 * hgt);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = round_up(off + bytes, 256);
-    return o;
-  };
-  l.o_ctr = take(C_COUNT * sizeof(int));
-  l.o_L = take(6 * l.N * sizeof(float));
-  size_t det = 0;  // offsets of the detection lists inside the scratch region (cand at 0)
-  auto sub = [&](size_t bytes) {
-    const size_t o = det;
-    det = round_up(det + bytes, 256);
-    return o;
-  };
-  sub(l.N * sizeof(uint32_t));
-  l.o_cflag = sub(l.N * sizeof(int));
-  l.o_coff = sub(l.N * sizeof(int));
-  l.o_crec = sub(l.N * sizeof(KeyRec));
-  l.o_scratch = take(std::max({det, 6 * l.N * sizeof(float), l.N * sizeof(float)}));
-  l.o_rowcnt = take(rows * sizeof(int));
-  l.o_rowoff = take(rows * sizeof(int));
-  l.o_kp = take(l.N * sizeof(KeyRec));
-  l.o_ang = take(l.N * 4 * sizeof(double));
-  l.o_nang = take(l.N * sizeof(int));
-  l.o_row = take(l.N * sizeof(int));
-  l.total = off;
+  WsWalk w, det;  // det: the detection lists inside the scratch region (cand at 0)
+  l.o_ctr = w.reserve(C_COUNT * sizeof(int));
+  l.o_L = w.reserve(6 * l.N * sizeof(float));
+  det.reserve(l.N * sizeof(uint32_t));
+  l.o_cflag = det.reserve(l.N * sizeof(int));
+  l.o_coff = det.reserve(l.N * sizeof(int));
+  l.o_crec = det.reserve(l.N * sizeof(KeyRec));
+  l.o_scratch = w.reserve(std::max({det.end(), 6 * l.N * sizeof(float), l.N * sizeof(float)}));
+  l.o_rowcnt = w.reserve(rows * sizeof(int));
+  l.o_rowoff = w.reserve(rows * sizeof(int));
+  l.o_kp = w.reserve(l.N * sizeof(KeyRec));
+  l.o_ang = w.reserve(l.N * 4 * sizeof(double));
+  l.o_nang = w.reserve(l.N * sizeof(int));
+  l.o_row = w.reserve(l.N * sizeof(int));
+  l.total = w.end();
   return l;
 }
 
