@@ -121,6 +121,21 @@ int spv_l1k2_bound_table(int8_t phi[256][4], int *p, int *m);
 int spv_l1k2_set_bound(int which);
 /* The setting in force (the setter's last value, else SPECTAVI_L1K2_BOUND = 0 | 1, else DEFAULT). */
 int spv_l1k2_get_bound(void);
+/* Which form of the bound kernel runs where the bound path is taken.  NARROW: 256 queries per workgroup over 32-row
+ * database tiles, two workgroups per CU.  WIDE: 512 queries over 64-row tiles, one workgroup per CU, which pays what a
+ * tile costs whatever survives half as often.  DEFAULT (also SPECTAVI_L1K2_PRUNE_FORM unset): WIDE where prune mode
+ * AUTO takes the path and there are at least 1024 such workgroups (1M x 1M and 4M x 500k qualify), else NARROW; always
+ * NARROW under prune mode ON.  Results are bit-identical either way, and neither spv_l1k2_plan nor
+ * spv_l1k2_workspace_bytes depends on it. */
+#define SPV_L1K2_PRUNE_FORM_DEFAULT (-1)
+#define SPV_L1K2_PRUNE_FORM_NARROW 0
+#define SPV_L1K2_PRUNE_FORM_WIDE 1
+int spv_l1k2_set_prune_form(int form);
+/* The setting in force (the setter's last value, else SPECTAVI_L1K2_PRUNE_FORM = 0 | 1, else DEFAULT). */
+int spv_l1k2_get_prune_form(void);
+/* The form that spv_l1k2_device would run for this shape under the settings in force (host only, no GPU involved):
+ * NARROW or WIDE, or -1 where it would not take the bound path at all. */
+int spv_l1k2_prune_form_of(int xrows, int yrows, int dim);
 /* spv_l1k2_bound_table for either table (which = RECIPE or TUNED). */
 int spv_l1k2_bound_table_of(int which, int8_t phi[256][4], int *p, int *m);
 /* Host statement of the 16-byte record format (no GPU involved), for callers that run their own

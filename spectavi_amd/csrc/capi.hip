@@ -859,6 +859,22 @@ int spv_l1k2_set_bound(int which) {
 
 int spv_l1k2_get_bound(void) { return l1k2_get_bound(); }
 
+int spv_l1k2_set_prune_form(int form) {
+  clear_error();
+  if (form != SPV_L1K2_PRUNE_FORM_DEFAULT && form != SPV_L1K2_PRUNE_FORM_NARROW && form != SPV_L1K2_PRUNE_FORM_WIDE)
+    return set_error(SPV_ERR_INVALID, "bound kernel form %d", form);
+  l1k2_set_prune_form(form);
+  return SPV_OK;
+}
+
+int spv_l1k2_get_prune_form(void) { return l1k2_get_prune_form(); }
+
+int spv_l1k2_prune_form_of(int xrows, int yrows, int dim) {
+  if (!l1k2_shape_ok(xrows, yrows, dim)) return -1;
+  const L1K2Plan p = l1k2_plan(xrows, yrows, dim);
+  return p.dim_pad >= 0 && p.path == kL1K2Bound ? p.form : -1;
+}
+
 int spv_l1k2_bound_table_of(int which, int8_t phi[256][4], int *p, int *m) {
   clear_error();
   if (!phi || !p || !m) return set_error(SPV_ERR_INVALID, "null output");

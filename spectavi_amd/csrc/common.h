@@ -119,6 +119,7 @@ struct L1K2Knobs {
   int prune_octet;   // SPECTAVI_L1K2_PRUNE_OCTET: most pairs a survivor pass takes eight lanes per pair for (-1: the measured crossover; 0: never)
   bool prune_stats;  // SPECTAVI_L1K2_PRUNE_STATS=1: the bound path prints its counters (synchronises)
   int bound;         // SPECTAVI_L1K2_BOUND: the bound table a process starts with (-1 default, 0 recipe, 1 tuned)
+  int prune_form;    // SPECTAVI_L1K2_PRUNE_FORM: the form of the bound kernel a process starts with (-1 default, 0 narrow, 1 wide)
 };
 const L1K2Knobs &l1k2_knobs();
 
@@ -143,6 +144,8 @@ struct L1K2Plan {
   size_t wide_lds;       // wide kernel: dynamic LDS bytes
   dim3 bound_grid;       // l1k2_prune_kernel: (blocks of 256 queries, slices)
   int bound;             // ... and the table it runs with (kL1K2BoundRecipe / kL1K2BoundTuned)
+  int form;              // ... and the form that runs (kL1K2FormNarrow / kL1K2FormWide)
+  dim3 bound_wide_grid;  // l1k2_prune_wide_kernel: (blocks of 512 queries, slices)
   unsigned work_grid;    // tile kernel over the bound path's work list: kWorkSub blocks for every workgroup there
   unsigned merge_grid;
   size_t thr_words;      // bound path: shared thresholds (an even number: the counters behind them are 64-bit)
@@ -167,6 +170,9 @@ const L1K2Bound &l1k2_bound();                               // the recipe; host
 const L1K2Bound &l1k2_bound_of(int which);                   // either table, each built once; a tuned table that fails its check is the recipe
 int l1k2_set_bound(int which);                               // -1 default (tuned under prune mode auto, the recipe under mode 1), 0, 1; returns the setting before
 int l1k2_get_bound();
+enum { kL1K2FormNarrow = 0, kL1K2FormWide = 1 };             // l1k2_prune_kernel (32-row tiles, 256 queries); l1k2_prune_wide_kernel (64, 512)
+int l1k2_set_prune_form(int form);                           // -1 default (wide where `auto` takes the path and the grid fills the chip), 0, 1; returns the setting before
+int l1k2_get_prune_form();
 int l1k2_set_prune(int mode);                                // -1 auto, 0 never, 1 wherever possible; returns the mode before
 int l1k2_get_prune();
 // The bound path's part of a plan whose slicing is done: its scratch, the next pieces of the plan's walk, and

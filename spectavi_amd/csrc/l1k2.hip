@@ -538,6 +538,8 @@ const L1K2Knobs &l1k2_knobs() {
     k.prune_stats = v && v[0] == '1';
     v = getenv("SPECTAVI_L1K2_BOUND");
     k.bound = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
+    v = getenv("SPECTAVI_L1K2_PRUNE_FORM");
+    k.prune_form = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
     return k;
   }();
   return knobs;

@@ -61,6 +61,13 @@
 // the first and the last MFMA of a tile), tests/test_l1k2_prune_staging_isa.py (the loads to LDS, no vmcnt wait
 // between them and the tile's MFMAs, counted lgkmcnt waits among the MFMAs) and
 // tests/test_l1k2_prune_chain_isa.py (the scalar-base form of the loads, the vector instructions at a tile's top).
+//
+// Two forms.  All of the above is l1k2_prune_kernel, the narrow form, which prune mode 1 runs and whose decisions per
+// 32-row tile and 256-query workgroup the case tables of the tests pin.  Where `auto` takes the path and the grid
+// fills the chip, l1k2_prune_plan chooses l1k2_prune_wide_kernel instead: 64-row tiles, 512 queries and 8 waves per
+// workgroup, one workgroup per CU, so that what a tile costs whatever survives is paid half as often per row.  Its
+// LDS and register budget stand at its head; tests/test_l1k2_prune_wide_isa.py checks them.  The two share the
+// survivor passes (drain_lanes, drain_octets); spv_l1k2_set_prune_form / SPECTAVI_L1K2_PRUNE_FORM force either.
 #include "common.h"
 #include "l1k2_bound_tuned.h"
 
@@ -97,6 +104,17 @@ constexpr uint32_t kMaxDist = 128 * 255;
 constexpr int kStatSlots = 16;                // survivor counters, spread to keep the atomics apart
 constexpr int kStatWords = kStatSlots * 4 * 2;
 constexpr int kWaitVm0 = 0x0F70;              // s_waitcnt vmcnt(0), the other counters left alone
+constexpr int kOctetPairsWide = 8;            // kOctetPairs of the wide form: 8 / 16 / 24 timed at 1M x 1M, DESIGN.md 4.1, "64-row tiles"
+
+// l1k2_prune_wide_kernel (see there): 64-row tiles, 8 waves.  What the narrow form counts in tiles keeps its number
+// of rows: the threshold cadence and the warm-up of the share rule.
+constexpr int kWideHalves = 2;                // MFMA row halves of a tile
+constexpr int kWideWaves = 8;
+constexpr int kWideThreads = 64 * kWideWaves;
+constexpr int kWideQPerBlock = kWideWaves * kQPerWave;
+constexpr int kWideTileRows = 32 * kWideHalves;
+constexpr int kWideThrEvery = 2;              // tiles between two publications of the thresholds: 128 rows, as every fourth narrow tile
+constexpr int kWideSkipTilesAlone = 2, kWideWarmTilesShared = kWarmTilesShared / 2, kWideWarmTilesAlone = kWarmTilesAlone / 2;
 
 // Phase stamps (-DSPV_L1K2_PHASE_STAMPS, never in the shipped library): every wave sums the shader cycles of each
 // phase of its tiles in scalar registers and lane 0 stores the sums once, when the wave ends; l1k2_prune_run
@@ -143,6 +161,93 @@ __global__ __launch_bounds__(kThreads) void l1k2_thr_init_kernel(uint32_t *thr, 
 __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
+}
+
+// ---- exact evaluation of the newest n <= 64 queued pairs of the current tile, one per lane; queue[w] is the wave's queue,
+// qslot its first query among the workgroup's top-2 slots k1s / k2s and raw rows qraw, xr the tile's raw rows, cnt
+// the queue's length.  Both rows
+// come from LDS in 16-byte pieces, each lane starting at a piece of its own so that the 64 rows,
+// which all begin on bank 0, are not read through the same four banks.
+template <int kRowBits>
+__device__ __forceinline__ void drain_lanes(int n, int &cnt, int lane, const uint16_t (*queue)[kQueue], int w, int qslot, const uint4 *qraw, const uint4 *xr,
+                                            unsigned long long *k1s, unsigned long long *k2s, uint32_t row0) {
+  wave_lds_fence();
+  const int base = cnt - n;
+  if (lane < n) {
+    const uint32_t e = queue[w][base + lane];
+    const int q6 = e >> kRowBits, i = e & ((1 << kRowBits) - 1);
+    const uint4 *qa = qraw + (qslot + q6) * 8, *xa = xr + i * 8;
+    const unsigned long long k2now = k2s[qslot + q6];
+    uint32_t d = 0;
+    // All 16 pieces are in flight before the first is used (the accumulators and the A buffers are dead
+    // here, and no register holds a staged tile): one LDS round trip for the rows.
+#pragma unroll
+    for (int h = 0; h < 8 / kDrainBatch; ++h) {
+      uint4 a[kDrainBatch], b[kDrainBatch];
+#pragma unroll
+      for (int k = 0; k < kDrainBatch; ++k) {
+        const int j = (kDrainBatch * h + k + lane) & 7;
+        a[k] = qa[j];
+        b[k] = xa[j];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < kDrainBatch; ++k) {
+        d = __builtin_amdgcn_sad_u8(a[k].x, b[k].x, d);
+        d = __builtin_amdgcn_sad_u8(a[k].y, b[k].y, d);
+        d = __builtin_amdgcn_sad_u8(a[k].z, b[k].z, d);
+        d = __builtin_amdgcn_sad_u8(a[k].w, b[k].w, d);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // a key that does not beat the query's second best of this moment never will (k2 only falls):
+    // nearly all survivors end here, and the two dependent atomics are left to the few that matter
+    const unsigned long long key = ((unsigned long long)d << 32) | (row0 + i);
+    if (key < k2now) {
+      const unsigned long long old = atomicMin(&k1s[qslot + q6], key);
+      atomicMin(&k2s[qslot + q6], old > key ? old : key);
+    }
+  }
+  cnt = base;
+  wave_lds_fence();
+}
+
+// ---- the same for few pairs, eight lanes per pair and eight pairs per round: a tile of the benchmark leaves a
+// handful of survivors, and one pair per lane pays 16 reads and 32 v_sad_u8 for them as for 64.  Lane 8 o + j
+// holds piece j of octet o's two rows (one ds_read_b128 each), four v_sad_u8 and three DPP adds give every lane
+// of the octet the distance, and the octet's first lane does the key compare and the two minima.  All lanes stay
+// active (octets past the last pair repeat it and store nothing): the DPP adds read their neighbours.
+// Bank conflicts: a ds_read_b128 lane group ({0-3, 12-15, 20-27} and so on) holds pieces 0-3 of two octets and
+// pieces 4-7 of two others; rows are 128 B and the bank row 256 B, so the two octets that share their pieces
+// collide exactly when their rows have the same parity.  Two pairs with rows of one parity cover each slot
+// twice whatever the map, so 2-way is the floor there; no group ever takes more than two cycles.
+template <int kRowBits>
+__device__ __forceinline__ void drain_octets(int n, int &cnt, int lane, const uint16_t (*queue)[kQueue], int w, int qslot, const uint4 *qraw, const uint4 *xr,
+                                             unsigned long long *k1s, unsigned long long *k2s, uint32_t row0) {
+  wave_lds_fence();
+  const int base = cnt - n;
+  const int oct = lane >> 3, piece = lane & 7;
+  for (int r = 0; r < n; r += 8) {
+    const int j = r + oct;
+    const uint32_t e = queue[w][base + min(j, n - 1)];
+    const int q6 = e >> kRowBits, i = e & ((1 << kRowBits) - 1);
+    const uint4 a = qraw[(qslot + q6) * 8 + piece], b = xr[i * 8 + piece];
+    const unsigned long long k2now = k2s[qslot + q6];
+    uint32_t d = __builtin_amdgcn_sad_u8(a.x, b.x, 0u);
+    d = __builtin_amdgcn_sad_u8(a.y, b.y, d);
+    d = __builtin_amdgcn_sad_u8(a.z, b.z, d);
+    d = __builtin_amdgcn_sad_u8(a.w, b.w, d);
+    d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+    d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+    d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x141, 0xF, 0xF, false);  // row_half_mirror: the other quad
+    const unsigned long long key = ((unsigned long long)d << 32) | (row0 + i);
+    if (piece == 0 && j < n && key < k2now) {
+      const unsigned long long old = atomicMin(&k1s[qslot + q6], key);
+      atomicMin(&k2s[qslot + q6], old > key ? old : key);
+    }
+  }
+  cnt = base;
+  wave_lds_fence();
 }
 
 __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
@@ -226,87 +331,14 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
         : "memory");
   };
 
-  // ---- exact evaluation of the newest n <= 64 queued pairs of the current tile, one per lane.  Both rows
-  // come from LDS in 16-byte pieces, each lane starting at a piece of its own so that the 64 rows,
-  // which all begin on bank 0, are not read through the same four banks.
+  // ---- the survivor passes (drain_lanes, drain_octets) over this wave's queue, queries and top-2 slots
   int cnt = 0;  // wave-uniform
   unsigned long long ph[kPhases] = {};  // wave-uniform cycle sums, all zero and dead without the stamps
   auto drain = [&](int n, const uint4 *xr, uint32_t row0) {
-    wave_lds_fence();
-    const int base = cnt - n;
-    if (lane < n) {
-      const uint32_t e = queue[w][base + lane];
-      const int q6 = e >> 5, i = e & 31;
-      const uint4 *qa = qraw + (qslot + q6) * 8, *xa = xr + i * 8;
-      const unsigned long long k2now = k2s[qslot + q6];
-      uint32_t d = 0;
-      // All 16 pieces are in flight before the first is used (the accumulators and the A buffers are dead
-      // here, and no register holds a staged tile): one LDS round trip for the rows.
-#pragma unroll
-      for (int h = 0; h < 8 / kDrainBatch; ++h) {
-        uint4 a[kDrainBatch], b[kDrainBatch];
-#pragma unroll
-        for (int k = 0; k < kDrainBatch; ++k) {
-          const int j = (kDrainBatch * h + k + lane) & 7;
-          a[k] = qa[j];
-          b[k] = xa[j];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < kDrainBatch; ++k) {
-          d = __builtin_amdgcn_sad_u8(a[k].x, b[k].x, d);
-          d = __builtin_amdgcn_sad_u8(a[k].y, b[k].y, d);
-          d = __builtin_amdgcn_sad_u8(a[k].z, b[k].z, d);
-          d = __builtin_amdgcn_sad_u8(a[k].w, b[k].w, d);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // a key that does not beat the query's second best of this moment never will (k2 only falls):
-      // nearly all survivors end here, and the two dependent atomics are left to the few that matter
-      const unsigned long long key = ((unsigned long long)d << 32) | (row0 + i);
-      if (key < k2now) {
-        const unsigned long long old = atomicMin(&k1s[qslot + q6], key);
-        atomicMin(&k2s[qslot + q6], old > key ? old : key);
-      }
-    }
-    cnt = base;
-    wave_lds_fence();
+    drain_lanes<5>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
   };
-
-  // ---- the same for few pairs, eight lanes per pair and eight pairs per round: a tile of the benchmark leaves a
-  // handful of survivors, and one pair per lane pays 16 reads and 32 v_sad_u8 for them as for 64.  Lane 8 o + j
-  // holds piece j of octet o's two rows (one ds_read_b128 each), four v_sad_u8 and three DPP adds give every lane
-  // of the octet the distance, and the octet's first lane does the key compare and the two minima.  All lanes stay
-  // active (octets past the last pair repeat it and store nothing): the DPP adds read their neighbours.
-  // Bank conflicts: a ds_read_b128 lane group ({0-3, 12-15, 20-27} and so on) holds pieces 0-3 of two octets and
-  // pieces 4-7 of two others; rows are 128 B and the bank row 256 B, so the two octets that share their pieces
-  // collide exactly when their rows have the same parity.  Two pairs with rows of one parity cover each slot
-  // twice whatever the map, so 2-way is the floor there; no group ever takes more than two cycles.
   auto drain_octets = [&](int n, const uint4 *xr, uint32_t row0) {
-    wave_lds_fence();
-    const int base = cnt - n;
-    const int oct = lane >> 3, piece = lane & 7;
-    for (int r = 0; r < n; r += 8) {
-      const int j = r + oct;
-      const uint32_t e = queue[w][base + min(j, n - 1)];
-      const int q6 = e >> 5, i = e & 31;
-      const uint4 a = qraw[(qslot + q6) * 8 + piece], b = xr[i * 8 + piece];
-      const unsigned long long k2now = k2s[qslot + q6];
-      uint32_t d = __builtin_amdgcn_sad_u8(a.x, b.x, 0u);
-      d = __builtin_amdgcn_sad_u8(a.y, b.y, d);
-      d = __builtin_amdgcn_sad_u8(a.z, b.z, d);
-      d = __builtin_amdgcn_sad_u8(a.w, b.w, d);
-      d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-      d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-      d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x141, 0xF, 0xF, false);  // row_half_mirror: the other quad
-      const unsigned long long key = ((unsigned long long)d << 32) | (row0 + i);
-      if (piece == 0 && j < n && key < k2now) {
-        const unsigned long long old = atomicMin(&k1s[qslot + q6], key);
-        atomicMin(&k2s[qslot + q6], old > key ? old : key);
-      }
-    }
-    cnt = base;
-    wave_lds_fence();
+    spv::drain_octets<5>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
   };
 
   // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b] = 128 m - p thr; what is
@@ -560,6 +592,393 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
   }
 }
 
+// The wide form: 64 database rows per loop iteration, so that what a tile costs whatever survives (the LDS round trips
+// of its top, queue and drain, the two fences, the vmcnt(0) and the barrier) is paid half as often per row.
+// grid = (blocks of 512 queries, slices), 8 waves of 64 queries each, one workgroup per CU; the feature tile is shared
+// by 8 waves instead of being staged twice per CU.  Per tile and wave the same five loads to LDS (512 threads stage
+// 64 rows), 64 MFMAs into four accumulators (row half h, column block b), a 64-bit survivor mask per lane, queue
+// entries query << 6 | row.  Thresholds, share rule and hand-over keep their cadence in rows (the kWide constants); a
+// leaving workgroup lists its two query blocks of 256.  What follows is the narrow kernel's text with those changes.
+// LDS 157704 of 163840 bytes: ftile 2 x 64 x 512, qraw 512 x 128, xraw 2 x 64 x 128, k1s / k2s 8192, queue 2048, bail 8.
+// Registers: B 128, accumulators 64, A 12, lane offsets 5 and the rest inside the 256 that 8 waves per CU allow, none
+// spilled; during a drain the accumulators are dead as in the narrow form.  To fit, the ragged tile's offsets and the
+// epilogue's addresses are made again from the thread index instead of being carried across the loop.
+// __launch_bounds__' second argument is waves per SIMD here: 512 threads are two per SIMD already.
+__global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
+    const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
+    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
+    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
+  // the narrow kernel's names, with this form's values
+  constexpr int H = kWideHalves, kThreads = kWideThreads, kWaves = kWideWaves, kQPerBlock = kWideQPerBlock;
+  constexpr int kTileRows = kWideTileRows, kFtileV4 = kTileRows * kLdsRowV4, kXrawV4 = kTileRows * 8, kThrEvery = kWideThrEvery;
+  constexpr int kSkipTilesAlone = kWideSkipTilesAlone, kWarmTilesShared = kWideWarmTilesShared, kWarmTilesAlone = kWideWarmTilesAlone;
+  // 512-byte alignment: the A-operand read folds its swizzle into the address with one XOR
+  __shared__ __attribute__((aligned(512))) uint4 ftile[2][kFtileV4];
+  __shared__ unsigned long long k1s[kQPerBlock], k2s[kQPerBlock];
+  __shared__ uint4 qraw[kQPerBlock * 8];            // the workgroup's query rows as they are
+  __shared__ uint4 xraw[2][kXrawV4];                // the tile's database rows as they are
+  __shared__ uint16_t queue[kWaves][kQueue];        // survivors: query of the wave << 6 | row of the tile
+  __shared__ int bail[2];                           // set in tile tl & 1: the workgroup gives the bound up
+  // 157704 bytes in all: one workgroup per CU
+
+  const int t = threadIdx.x;
+  const int w = t >> 6, lane = t & 63, c = lane & 31, g = lane >> 5;
+  const int s = blockIdx.y;
+  const int row_begin = s * slice_rows;
+  const int row_end = min(M, row_begin + slice_rows);
+  const int qbase = blockIdx.x * kQPerBlock + w * kQPerWave;  // this wave's first query
+  const int qslot = w * kQPerWave;                            // and its first top-2 slot
+
+  k1s[t] = ~0ull;
+  k2s[t] = ~0ull;
+  if (t < 2) bail[t] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int e = t + i * kThreads;
+    qraw[e] = y[(size_t)min((int)blockIdx.x * kQPerBlock + (e >> 3), N - 1) * 8 + (e & 7)];
+  }
+
+  // ---- staging of the database tiles, from global memory straight into LDS (global_load_lds_dwordx4): no
+  // registers carry the tile and no ds_write stores it.  A wave's instruction lands its 64 x 16 B one after the
+  // other from the base in M0, so the LDS image is lane-linear and unpadded, and the swizzle that keeps the
+  // A-operand reads off each other's banks is made on the source side: the lane that lands on piece j of row r
+  // fetches piece j ^ (r & 15), and piece q of row r is read back from slot q ^ (r & 15).  EXEC must be full at
+  // these loads, so rows past the end of a ragged last tile are not predicated off but clamped to the last
+  // row: the tile then holds copies of it, which the `valid` mask keeps out of the queue.
+  // The loads are one asm statement, not __builtin_amdgcn_global_load_lds: the compiler, knowing of a load to
+  // LDS in flight, waits for vmcnt(0) before the first LDS read that may alias it (the A operand of this very
+  // tile, in the other buffer) and at every workgroup fence (each drain), and turns every counted lgkmcnt wait
+  // of the MFMA run into lgkmcnt(0).  Unknown to it, they count on vmcnt only, behind its own loads at most,
+  // which can only make one of its waits longer; nothing but the s_waitcnt vmcnt(0) ahead of the tile's
+  // barrier makes the data visible.  M0 is the compiler's: it is put back in the same statement.
+  typedef __attribute__((address_space(3))) void *lds_ptr;
+  const uint32_t lds_f = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&ftile[0][w * 64]));
+  const uint32_t lds_r = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&xraw[0][w * 64]));
+  // Addresses.  The tile's first feature row and first raw row are two wave-uniform 64-bit pointers, which the
+  // scalar unit advances by one tile per iteration (at 4M rows the feature offset passes 2^31), and each load
+  // adds the lane's byte offset within the tile (global_load_lds_dwordx4 vOff, s[base:base+1]).  The five
+  // offsets are the same for every full tile and stay in five registers; only a ragged tile, the last of a
+  // slice, computes them again with the row clamp, under a wave-uniform branch around that arithmetic alone
+  // (no full tile follows a ragged one, so they are overwritten in place).
+  uint32_t voff[5];
+  auto lane_offsets = [&](int nrows, int t) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = t + i * kThreads, r = e >> 5;
+      voff[i] = (uint32_t)(min(r, nrows - 1) * kFeatV4 + ((e & 31) ^ (r & 15))) * 16u;
+    }
+    voff[4] = (uint32_t)(min(t >> 3, nrows - 1) * 8 + (t & 7)) * 16u;
+  };
+  lane_offsets(kTileRows, t);
+  auto stage_issue = [&](const uint4 *ftile0, const uint4 *xtile0, int nrows, int b) {
+    if (__builtin_expect(nrows < kTileRows, 0)) {
+      // from the thread index alone, behind a move that the compiler cannot see through: else it keeps every row and
+      // piece number of the five loads in a register of its own across the loop, for a path that runs once a slice
+      int tt = t;
+      asm volatile("" : "+v"(tt));
+      lane_offsets(nrows, tt);
+    }
+    const uint32_t f0 = lds_f + b * (kFtileV4 * 16), r0 = lds_r + b * (kXrawV4 * 16);
+    uint32_t m0_kept;
+    // s_nop 2: with the two s_mov ahead of it, five states between whatever wrote a base register and its first use
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %11\n\t"
+        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %11\n\t"
+        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %11\n\t"
+        "s_mov_b32 m0, %9\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %11\n\t"
+        "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %12\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(m0_kept)
+        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "s"(f0), "s"(f0 + kThreads * 16u),
+          "s"(f0 + kThreads * 32u), "s"(f0 + kThreads * 48u), "s"(r0), "s"(ftile0), "s"(xtile0)
+        : "memory");
+  };
+
+  // ---- the survivor passes (drain_lanes, drain_octets) over this wave's queue, queries and top-2 slots
+  int cnt = 0;  // wave-uniform
+  unsigned long long ph[kPhases] = {};  // wave-uniform cycle sums, all zero and dead without the stamps
+  auto drain = [&](int n, const uint4 *xr, uint32_t row0) {
+    drain_lanes<6>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
+  };
+  auto drain_octets = [&](int n, const uint4 *xr, uint32_t row0) {
+    spv::drain_octets<6>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
+  };
+
+  // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b] = 128 m - p thr; what is
+  // kept is ntq[b] = -tq[b], the value that the tile's accumulators start from.  seen[b] is the
+  // shared threshold read last.  Only atomicMin ever writes thr[], so a later read is never above an earlier
+  // one and simply replaces it (and any value ever read there is a valid bound).  The two loads are issued
+  // a tile ahead of the refresh that uses them, behind that tile's stage loads, and have landed by the
+  // vmcnt(0) before its barrier: no tile waits for them.  Lanes past the last query read the last
+  // query's threshold, whose features they also carry.
+  int ntq[2];
+  uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+  auto thr_load = [&]() {
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+      seen[b] = __hip_atomic_load(&thr[min(qbase + 32 * b + c, N - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  auto refresh = [&](bool shared) {
+    uint32_t loc[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      loc[b] = (uint32_t)(k2s[qslot + 32 * b + c] >> 32);
+      // thr = "none yet" keeps every pair: sum >= 128 m - p 32640 always
+      ntq[b] = p * (int)min(min(loc[b], seen[b]), kMaxDist) - m128;
+    }
+    if (shared && g == 0) {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int qi = qbase + 32 * b + c;
+        if (qi < N && loc[b] < seen[b]) atomicMin(&thr[qi], loc[b]);
+      }
+    }
+  };
+
+  const int ntiles = (row_end - row_begin + kTileRows - 1) / kTileRows;
+  if (ntiles > 0) {
+    stage_issue(fx + (size_t)row_begin * kFeatV4, x + (size_t)row_begin * 8, min(kTileRows, row_end - row_begin), 0);
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+  }
+  __syncthreads();
+  // the tile that the loop stages next
+  const uint4 *fnext = fx + ((size_t)row_begin + kTileRows) * kFeatV4, *xnext = x + ((size_t)row_begin + kTileRows) * 8;
+
+  unsigned long long n_bound = 0, n_surv = 0;  // wave-uniform statistics
+  bool gave_up = false;                        // workgroup-uniform
+  int warm = kWarmTilesAlone, skip_tiles = kSkipTilesAlone;
+  int recent = 0;  // survivors of the last tiles, each tile weighing 7/8 of the one after it: 8 x the running share
+  int tl = 0;
+  // bail[] of the tile before, read right behind its barrier.  The index carries a zero that the compiler cannot
+  // see through: a value it knows to be wave-uniform is moved to a scalar register where it is loaded, which
+  // waits for it there; this one stays in its vector register until the tile's top asks for it.
+  int bailed = 0, zero_v = 0;
+  asm volatile("" : "+v"(zero_v));
+  {
+    // ---- this wave's queries as the B operand
+    v4i bq[2][16];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const uint4 *f = fy + (size_t)min(qbase + 32 * b + c, N - 1) * kFeatV4;
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + g]);
+    }
+    thr_load();
+    // The B operand is complete before the loop is entered.  Without this wait the compiler, which cannot
+    // prove on the back edge that these loads have landed, guards every MFMA of every tile with a vmcnt
+    // wait, and the last of them wait for the prefetch of the next tile.
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+
+    for (; tl < ntiles; ++tl) {
+      const unsigned long long t_top = stamp();
+      const unsigned long long drained = ph[kPhDrain];
+      const int row0 = row_begin + tl * kTileRows;
+      const bool has_next = tl + 1 < ntiles;
+      // this lane's A-operand slot at k-step 0 in this tile's buffer: row c, piece g ^ (c & 15)
+      const int a0 = (tl & 1) * kFtileV4 + c * kLdsRowV4 + (g ^ (c & 15));
+      // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair.  Each
+      // ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same of the upper half) holds 16
+      // distinct c mod 16 at one g, hence 16 distinct 16-byte slots of the 256-byte bank row: no conflict.
+      // Piece (2 ks + g) ^ (c & 15) = (g ^ (c & 15)) ^ 2 ks; the row and the buffer lie above those bits.
+      // The first two reads are the tile's first instructions: the stage issue and the thresholds run in their
+      // latency (the memory clobber of the loads keeps them ahead).
+      // k-step 16 h + ks is k-step ks of row half h, 32 rows further on
+      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, ftile[0][(a0 + (ks >> 4) * (32 * kLdsRowV4)) ^ (2 * (ks & 15))]); };
+      v4i a3[3];
+      a3[0] = lda(0);
+      a3[1] = lda(1);
+      // every wave passed the barrier of tile tl - 1 after its last read of these buffers
+      if (has_next) {
+        stage_issue(fnext, xnext, min(kTileRows, row_end - row0 - kTileRows), (tl + 1) & 1);
+        fnext += kFtileV4;
+        xnext += kXrawV4;
+      }
+      const bool shared = (tl & (kThrEvery - 1)) == 0;  // the shared thresholds move slowly: every 128 rows is enough
+      const int nrows = min(kTileRows, row_end - row0);
+      refresh(shared);
+      if (tl == 0 && __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
+        warm = kWarmTilesShared;
+        skip_tiles = 0;
+      }
+      if ((tl & (kThrEvery - 1)) == kThrEvery - 1) thr_load();  // for the next tile; they land behind this tile's work
+      // The workgroup leaves after the tile whose flag was raised, before it bounds a pair of this one.  The loads
+      // and the thresholds just issued are harmless: every published value is a valid bound, the exit path
+      // publishes anyway, and it waits for the loads.  The flag arrived with the k2s[] that the thresholds were
+      // made from; pinning them here keeps that one wait ahead of the branch (sunk below it, the reads would be
+      // pending on the way out of the loop and the compiler would wait for them at every tile's top).
+      asm volatile("" ::"v"(ntq[0]), "v"(ntq[1]));
+      if (__builtin_amdgcn_readfirstlane(bailed)) break;
+
+      // The accumulators start at minus the lane's threshold, so that a register ends as sum - threshold and its
+      // sign bit says "ruled out" (the difference cannot overflow: make_bound).  The 32 moves stand where the
+      // wave waits for its first A reads anyway, and take a subtraction per register out of the compare.
+      // Row half h of the tile (rows 32 h .. 32 h + 31) has its own pair of accumulators; the A reads run on across
+      // the boundary between the halves.
+      v16i acc[H][2];
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+#pragma unroll
+          for (int v = 0; v < 16; ++v) acc[h][b][v] = ntq[b];
+        }
+      }
+      const unsigned long long t_mfma = stamp();
+#pragma unroll
+      for (int ks = 0; ks < 16 * H; ++ks) {
+        if (ks + 2 < 16 * H) a3[(ks + 2) % 3] = lda(ks + 2);
+        acc[ks >> 4][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[0][ks & 15], acc[ks >> 4][0], 0, 0, 0);
+        acc[ks >> 4][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[1][ks & 15], acc[ks >> 4][1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+
+      // One bit per accumulator register: bit 31 - n of `skip[h]` says that pair n = 16 b + v of this lane and row
+      // half is ruled out (sum < threshold: the register's sign).  Register v of a lane is row
+      // 32 h + 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are copies of the
+      // slice's last row and must never be taken for neighbours.  `live` holds half 0 in its top 32 bits.
+      const unsigned long long t_cmp = stamp();
+      uint32_t skip[H] = {};
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+#pragma unroll
+          for (int v = 0; v < 16; ++v) skip[h] = __builtin_amdgcn_alignbit(skip[h], (uint32_t)acc[h][b][v], 31);
+        }
+      }
+      unsigned long long live = ~((unsigned long long)skip[0] << 32 | skip[1]);
+      if (nrows < kTileRows) {
+        unsigned long long valid = 0;
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+#pragma unroll
+          for (int v = 0; v < 16; ++v)
+            if (32 * h + 8 * (v >> 2) + 4 * g + (v & 3) < nrows) valid |= 0x80008000ull << (32 * (H - 1 - h)) >> v;
+        }
+        live &= valid;
+      }
+      // compaction: every round each lane with survivors left appends its first one to the wave's queue
+      int tile_surv = 0;
+      for (;;) {
+        const bool has = live != 0;
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(has);
+        if (mask == 0ull) break;
+        const int n = __clzll(live | 1ull);  // the lane's first pair: row half n / 32, column block n / 16 % 2, register n % 16
+        const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (has) {
+          queue[w][pos] = (uint16_t)(((32 * ((n >> 4) & 1) + c) << 6) | (32 * (n >> 5) + 8 * ((n >> 2) & 3) + 4 * g + (n & 3)));
+          live &= ~(0x8000000000000000ull >> n);
+        }
+        const int add = __popcll(mask);
+        cnt += add;
+        tile_surv += add;
+        if (cnt >= 64) {
+          const unsigned long long d0 = stamp();
+          drain(64, xraw[tl & 1], (uint32_t)row0);
+          ph[kPhDrain] += stamp() - d0;
+        }
+      }
+      // the tile's raw rows are overwritten during the next tile: nothing stays queued
+      if (cnt > 0) {
+        const unsigned long long d0 = stamp();
+        if (cnt <= octet_max)
+          drain_octets(cnt, xraw[tl & 1], (uint32_t)row0);
+        else
+          drain(cnt, xraw[tl & 1], (uint32_t)row0);
+        ph[kPhDrain] += stamp() - d0;
+      }
+      n_bound += (unsigned long long)nrows * kQPerWave;
+      n_surv += tile_surv;
+
+      // Above the break-even share a survivor pass costs more than the exact loop saves.  A wave that
+      // sees that raises the flag of this tile; after the barrier the whole workgroup reads the same flag
+      // (the next tile uses the other one, and a flag is never lowered), puts itself on the work list of
+      // l1k2_tile_kernel, which then computes this (query block, slice) from scratch, and leaves.
+      recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
+      const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
+      if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
+      const unsigned long long t_wait = stamp();
+      // the next tile and the thresholds have landed: a whole tile after their loads were issued
+      __builtin_amdgcn_s_waitcnt(kWaitVm0);
+      const unsigned long long t_bar = stamp();
+      __syncthreads();
+      const unsigned long long t_end = stamp();
+      ph[kPhStage] += t_mfma - t_top;
+      ph[kPhMfma] += t_cmp - t_mfma;
+      ph[kPhCompact] += (t_wait - t_cmp) - (ph[kPhDrain] - drained);
+      ph[kPhVmWait] += t_bar - t_wait;
+      ph[kPhBarrier] += t_end - t_bar;
+      ph[kPhLoop] += t_end - t_top;
+      // The flag is asked for here and looked at behind the next tile's first LDS wait: no round trip of its own.
+      bailed = bail[(tl & 1) + zero_v];
+    }
+    gave_up = __builtin_amdgcn_readfirstlane(bailed) != 0;  // whether it was seen at a tile's top or the slice ended with it
+  }
+  // a wave must not end with a load into its workgroup's LDS in flight
+  if (gave_up) __builtin_amdgcn_s_waitcnt(kWaitVm0);
+  // What follows the loop works from a copy of the thread index that the compiler cannot see through: made from t
+  // itself, its LDS addresses and the wave's number are held in registers across the loop, which has none to spare.
+  int te = t;
+  asm volatile("" : "+v"(te));
+  const int we = te >> 6;
+#ifdef SPV_L1K2_PHASE_STAMPS
+  if (lane == 0) {
+    unsigned long long *out = stamps_out + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kWaves + w) * (kPhases + 1);
+#pragma unroll
+    for (int k = 0; k < kPhases; ++k) out[k] = ph[k];
+    out[kPhases] = (unsigned long long)tl;  // tiles this wave ran
+  }
+#endif
+  if (gave_up) {
+    // what this workgroup has found still bounds its queries' second best from above: hand it on;
+    // the exact kernel merges into the partial pair, which starts as "none"
+    const int qo = blockIdx.x * kQPerBlock + te;
+    if (qo < N) {
+      const uint32_t loc = (uint32_t)(k2s[te] >> 32);
+      if (loc < __hip_atomic_load(&thr[qo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qo], loc);
+      uint64_t *dst = part + ((size_t)qo * S + s) * 2;
+      dst[0] = ~0ull;
+      dst[1] = ~0ull;
+    }
+    // the work list is in query blocks of 256 (l1k2_tile_kernel<32, 2, 128>): two of them, unless the second has no query
+    if (te == 0) {
+      const uint32_t first = 2 * blockIdx.x, nblk = min(2u, (uint32_t)((N + 255) / 256) - first);
+      const uint32_t slot = atomicAdd(&work[0], nblk);
+      work[2 + 2 * slot] = first;
+      work[3 + 2 * slot] = blockIdx.y;
+      if (nblk > 1) {
+        work[4 + 2 * slot] = first + 1;
+        work[5 + 2 * slot] = blockIdx.y;
+      }
+    }
+    if ((te & 63) == 0) {
+      unsigned long long *st = stats + ((blockIdx.x + we) % kStatSlots) * 4;
+      atomicAdd(&st[0], n_bound);
+      atomicAdd(&st[1], n_surv);
+      atomicAdd(&st[2], (unsigned long long)(row_end - row_begin) * kQPerWave);
+    }
+    return;
+  }
+  __syncthreads();
+
+  const int qi = blockIdx.x * kQPerBlock + te;
+  if (qi < N) {
+    const unsigned long long a1 = k1s[te], a2 = k2s[te];
+    uint64_t *dst = part + ((size_t)qi * S + s) * 2;
+    dst[0] = a1;
+    dst[1] = a2;
+    const uint32_t loc = (uint32_t)(a2 >> 32);
+    if (loc < __hip_atomic_load(&thr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qi], loc);
+  }
+  if ((te & 63) == 0) {
+    unsigned long long *st = stats + ((blockIdx.x + we) % kStatSlots) * 4;
+    atomicAdd(&st[0], n_bound);
+    atomicAdd(&st[1], n_surv);
+  }
+}
+
 // -1 auto, 0 off, 1 forced: SPECTAVI_L1K2_PRUNE until l1k2_set_prune is called
 std::atomic<int> &prune_mode() {
   static std::atomic<int> mode{l1k2_knobs().prune};
@@ -611,6 +1030,12 @@ L1K2Bound make_bound(const int8_t phi[256][4], int p_lo, int p_hi) {
   return b;
 }
 
+// -1 default, 0 narrow, 1 wide: SPECTAVI_L1K2_PRUNE_FORM until l1k2_set_prune_form is called
+std::atomic<int> &form_choice() {
+  static std::atomic<int> which{l1k2_knobs().prune_form};
+  return which;
+}
+
 L1K2Bound make_recipe() {
   int8_t phi[256][4];
   const double pi = 3.14159265358979323846;
@@ -650,6 +1075,8 @@ int l1k2_set_prune(int mode) { return prune_mode().exchange(mode); }
 int l1k2_get_prune() { return prune_mode().load(); }
 int l1k2_set_bound(int which) { return bound_choice().exchange(which); }
 int l1k2_get_bound() { return bound_choice().load(); }
+int l1k2_set_prune_form(int form) { return form_choice().exchange(form); }
+int l1k2_get_prune_form() { return form_choice().load(); }
 
 namespace {
 // where the counters of the calling thread's last l1k2_run lie (null: it took the tile kernels)
@@ -691,6 +1118,8 @@ int l1k2_prune_last_stats(unsigned long long out[3]) { return read_stats(t_last_
 //    against 62.0 ms, profiles/r08_prune_breakeven_knobs.jsonl); the rule was left as it is, its cost on inputs
 //    that do not pay has not grown (profiles/r08_prune_breakeven.jsonl).
 constexpr int kPruneMinX = 262144, kPruneMinSlice = 32768;
+// The wide form holds a CU with one workgroup: it is taken where there is at least this many of them (four per CU).
+constexpr unsigned kWideMinGroups = 1024;
 
 void l1k2_prune_plan(int xrows, int yrows, int dim, WsWalk *w, L1K2Plan *p) {
   p->off_feat_x = p->off_feat_y = p->off_thr = p->off_stats = p->off_work = w->end();
@@ -716,6 +1145,12 @@ void l1k2_prune_plan(int xrows, int yrows, int dim, WsWalk *w, L1K2Plan *p) {
   if (wanted && l1k2_bound_of(p->bound).ok) {
     p->path = kL1K2Bound;
     p->bound_grid = dim3(qgroups, (unsigned)p->slices);
+    // The form: as set, else the wide one where `auto` took the path and its grid fills the chip.  Mode 1 stays narrow:
+    // the case tables of the tests pin what l1k2_prune_kernel decides per 32-row tile and 256-query workgroup.
+    const unsigned wgroups = (unsigned)((yrows + kWideQPerBlock - 1) / kWideQPerBlock);
+    const int form = l1k2_get_prune_form();
+    p->form = form >= 0 ? form : mode != 1 && (unsigned long long)wgroups * p->slices >= kWideMinGroups ? kL1K2FormWide : kL1K2FormNarrow;
+    p->bound_wide_grid = dim3(wgroups, (unsigned)p->slices);
   }
 }
 
@@ -745,7 +1180,10 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   // wait for each other.  At 1M x 1M (four pairs per wave and tile on average) 8, 16 and 24 were timed against each other
   // on one build: DESIGN.md 4.1, "The wave's chain per tile", has the three numbers.
   const int octet = l1k2_knobs().prune_octet;
-  const int octet_max = octet < 0 ? kOctetPairs : std::min(64, octet);
+  const bool wide = p.form == kL1K2FormWide;
+  const int octet_max = octet < 0 ? (wide ? kOctetPairsWide : kOctetPairs) : std::min(64, octet);
+  const dim3 grid = wide ? p.bound_wide_grid : p.bound_grid;
+  const int waves = wide ? kWideWaves : kWaves;
   const size_t xw = (size_t)xrows * 32, yw = (size_t)yrows * 32;
   auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + kThreads - 1) / kThreads, 8192)); };
   hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
@@ -755,14 +1193,18 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(p.init_words), dim3(kThreads), 0, stream, thr, p.thr_words,
                      p.init_words);
 #ifdef SPV_L1K2_PHASE_STAMPS
-  const size_t nstamp = (size_t)p.bound_grid.x * p.bound_grid.y * kWaves * (kPhases + 1);
+  const size_t nstamp = (size_t)grid.x * grid.y * waves * (kPhases + 1);
   unsigned long long *d_stamps = nullptr;
   SPV_HIP_CHECK(hipMalloc(&d_stamps, nstamp * 8));
   SPV_HIP_CHECK(hipMemsetAsync(d_stamps, 0, nstamp * 8, stream));
 #endif
-  hipLaunchKernelGGL(l1k2_prune_kernel, p.bound_grid, dim3(kThreads), 0, stream, reinterpret_cast<const uint4 *>(d_x),
-                     reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, 128 * b.m, b.p,
-                     max_share, octet_max, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part) SPV_STAMP_ARG);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(waves * 64), 0, stream, reinterpret_cast<const uint4 *>(d_x),
+                       reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, 128 * b.m, b.p,
+                       max_share, octet_max, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part) SPV_STAMP_ARG);
+  };
+  if (wide) launch(l1k2_prune_wide_kernel);
+  else launch(l1k2_prune_kernel);
   SPV_HIP_CHECK(hipGetLastError());
 #ifdef SPV_L1K2_PHASE_STAMPS
   {

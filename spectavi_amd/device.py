@@ -178,6 +178,29 @@ def l1k2_get_bound():
     return int(clib.spv_l1k2_get_bound())
 
 
+def l1k2_set_prune_form(form):
+    """Which form of the bound kernel l1k2() runs where it takes the bound path (spv_l1k2_set_prune_form): "default"
+    (the wide one where prune mode "auto" takes the path and its grid fills the chip, else the narrow one),
+    0 / "narrow" (256 queries over 32-row tiles), 1 / "wide" (512 queries over 64-row tiles).
+    The results do not depend on it."""
+    if isinstance(form, str):
+        form = {"default": -1, "narrow": 0, "wide": 1}.get(form)
+    if isinstance(form, bool) or not isinstance(form, int) or form not in (-1, 0, 1):
+        raise ValueError("bound kernel form must be 'default', 'narrow' (0) or 'wide' (1)")
+    check(clib.spv_l1k2_set_prune_form(form))
+
+
+def l1k2_get_prune_form():
+    """The bound kernel form setting in force: -1 (default), 0 (narrow) or 1 (wide)."""
+    return int(clib.spv_l1k2_get_prune_form())
+
+
+def l1k2_prune_form_of(xrows, yrows, dim=128):
+    """The form l1k2() would run for this shape under the settings in force (spv_l1k2_prune_form_of; host only):
+    0 (narrow), 1 (wide), or -1 where it would not take the bound path."""
+    return int(clib.spv_l1k2_prune_form_of(xrows, yrows, dim))
+
+
 def l1k2_bound_table(which=0):
     """(phi int64 [256, 4], p, m) of the recipe (0) or the tuned (1) table (spv_l1k2_bound_table_of; host only):
     p |a - b| >= m - phi[a] . phi[b] for all bytes a, b."""
