@@ -120,7 +120,9 @@ constexpr int kWideSkipTilesAlone = 2, kWideWarmTilesShared = kWarmTilesShared /
 // phase of its tiles in scalar registers and lane 0 stores the sums once, when the wave ends; l1k2_prune_run
 // prints their totals.  Such a build is for attribution only and is never the one that is timed: a stamp waits
 // for lgkmcnt(0) and pins the schedule around it.
-enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPhLoop, kPhases };
+// The wide form has two barriers per tile: kPhBarrier is the one that ends a tile, kPhMidBarrier the one between its
+// MFMA run and its compare (the narrow form leaves it zero).
+enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPhLoop, kPhMidBarrier, kPhases };
 #ifdef SPV_L1K2_PHASE_STAMPS
 #define SPV_STAMP_PARAM , unsigned long long *stamps_out
 #define SPV_STAMP_ARG , d_stamps
@@ -670,7 +672,7 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
     voff[4] = (uint32_t)(min(t >> 3, nrows - 1) * 8 + (t & 7)) * 16u;
   };
   lane_offsets(kTileRows, t);
-  auto stage_issue = [&](const uint4 *ftile0, const uint4 *xtile0, int nrows, int b) {
+  auto ragged_offsets = [&](int nrows) {
     if (__builtin_expect(nrows < kTileRows, 0)) {
       // from the thread index alone, behind a move that the compiler cannot see through: else it keeps every row and
       // piece number of the five loads in a register of its own across the loop, for a path that runs once a slice
@@ -678,6 +680,39 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       asm volatile("" : "+v"(tt));
       lane_offsets(nrows, tt);
     }
+  };
+  // The five loads of a tile come in two statements as well, for the waves that issue its features and its raw rows in
+  // different half-steps (see the loop).  stage_raw takes the offset that stage_feat's ragged_offsets left: the raw
+  // rows of a tile are issued after its features, and nothing follows a ragged tile.
+  auto stage_feat = [&](const uint4 *ftile0, int nrows, int b) {
+    ragged_offsets(nrows);
+    const uint32_t f0 = lds_f + b * (kFtileV4 * 16);
+    uint32_t m0_kept;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %5\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
+        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %9\n\t"
+        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %9\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(m0_kept)
+        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(f0), "s"(f0 + kThreads * 16u), "s"(f0 + kThreads * 32u),
+          "s"(f0 + kThreads * 48u), "s"(ftile0)
+        : "memory");
+  };
+  auto stage_raw = [&](const uint4 *xtile0, int b) {
+    const uint32_t r0 = lds_r + b * (kXrawV4 * 16);
+    uint32_t m0_kept;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(m0_kept)
+        : "v"(voff[4]), "s"(r0), "s"(xtile0)
+        : "memory");
+  };
+  auto stage_issue = [&](const uint4 *ftile0, const uint4 *xtile0, int nrows, int b) {
+    ragged_offsets(nrows);
     const uint32_t f0 = lds_f + b * (kFtileV4 * 16), r0 = lds_r + b * (kXrawV4 * 16);
     uint32_t m0_kept;
     // s_nop 2: with the two s_mov ahead of it, five states between whatever wrote a base register and its first use
@@ -770,8 +805,29 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
     // wait, and the last of them wait for the prefetch of the next tile.
     __builtin_amdgcn_s_waitcnt(kWaitVm0);
 
+    // ---- Two half-steps per tile, waves 4-7 half a tile behind waves 0-3.  A SIMD holds waves w and w + 4.  M(t) is
+    // the top of tile t and its 64 MFMAs (it reads ftile[t & 1]), C(t) its compare, compaction and drains (xraw[t & 1]);
+    // a barrier ends each, B_h the one that ends half-step h.  The leading waves run M(t) in half-step 2t and C(t) in
+    // 2t + 1, the trailing waves M(t) in 2t + 1 and C(t) in 2t + 2: on every SIMD one wave's chain runs under the
+    // other's MFMAs, where in lock-step both had the pipe or neither.  The trailing waves get there by one barrier ahead
+    // of their loop (B_0); the leading waves' barrier behind the loop answers the last of the trailing waves' (B_2n).
+    // Every wave passes 2n + 1 of them for n tiles.
+    // Buffers.  Tile t + 2 replaces tile t.  ftile[b] with tile t is read in half-steps 2t and 2t + 1: loads into it are
+    // issued behind B_2t+1 and waited for ahead of B_2t+3.  xraw[b] with tile t is read in 2t + 1 and 2t + 2: issued
+    // behind B_2t+2, waited for ahead of B_2t+4.  The trailing waves issue all five loads of tile t + 1 at the top of
+    // M(t) (behind B_2t) and wait ahead of their mid-tile barrier B_2t+1; the leading waves issue its features at the
+    // top of M(t) (behind B_2t-1), its raw rows at the top of C(t) (behind B_2t), and wait at their mid-tile barriers:
+    // B_2t for the features, B_2t+2 for the raw rows.
+    // Leaving.  The flag of tile t is complete at B_2t+2 and both halves read it right behind that barrier.  The
+    // trailing waves are then at the top of tile t + 1 and leave before they bound a pair of it, as every wave did with
+    // one barrier per tile.  The leading waves have run M(t + 1) already: they drop its accumulators (no compare, no
+    // queue entry, no statistics) and leave too.  Both have passed 2t + 3 barriers.
+    const bool trail = __builtin_amdgcn_readfirstlane(w) >= kWaves / 2;  // wave-uniform
+    if (trail) __syncthreads();                                           // B_0
+
+    unsigned long long t_last = 0;  // stamps: the end of the tile before, so that the loop's back edge is counted too
     for (; tl < ntiles; ++tl) {
-      const unsigned long long t_top = stamp();
+      const unsigned long long t_now = stamp(), t_top = tl ? t_last : t_now;
       const unsigned long long drained = ph[kPhDrain];
       const int row0 = row_begin + tl * kTileRows;
       const bool has_next = tl + 1 < ntiles;
@@ -788,11 +844,17 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       v4i a3[3];
       a3[0] = lda(0);
       a3[1] = lda(1);
-      // every wave passed the barrier of tile tl - 1 after its last read of these buffers
+      // every wave has read the last of tile tl - 1's features; only the trailing waves are behind the barrier after
+      // which nobody reads its raw rows (the leading waves issue theirs behind the mid-tile barrier)
       if (has_next) {
-        stage_issue(fnext, xnext, min(kTileRows, row_end - row0 - kTileRows), (tl + 1) & 1);
+        const int nnext = min(kTileRows, row_end - row0 - kTileRows);
+        if (trail) {
+          stage_issue(fnext, xnext, nnext, (tl + 1) & 1);
+          xnext += kXrawV4;
+        } else {
+          stage_feat(fnext, nnext, (tl + 1) & 1);
+        }
         fnext += kFtileV4;
-        xnext += kXrawV4;
       }
       const bool shared = (tl & (kThrEvery - 1)) == 0;  // the shared thresholds move slowly: every 128 rows is enough
       const int nrows = min(kTileRows, row_end - row0);
@@ -801,14 +863,18 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
         warm = kWarmTilesShared;
         skip_tiles = 0;
       }
-      if ((tl & (kThrEvery - 1)) == kThrEvery - 1) thr_load();  // for the next tile; they land behind this tile's work
-      // The workgroup leaves after the tile whose flag was raised, before it bounds a pair of this one.  The loads
+      // The trailing waves leave after the tile whose flag was raised, before they bound a pair of this one (a leading
+      // wave gets here with `bailed` zero: it looks at the flag behind the mid-tile barrier).  The loads
       // and the thresholds just issued are harmless: every published value is a valid bound, the exit path
       // publishes anyway, and it waits for the loads.  The flag arrived with the k2s[] that the thresholds were
       // made from; pinning them here keeps that one wait ahead of the branch (sunk below it, the reads would be
       // pending on the way out of the loop and the compiler would wait for them at every tile's top).
       asm volatile("" ::"v"(ntq[0]), "v"(ntq[1]));
       if (__builtin_amdgcn_readfirstlane(bailed)) break;
+      // for the next tile; they land behind this tile's MFMAs.  Behind the branch: on the way out of the loop no load that
+      // the compiler knows of is pending, so it asks for none at the loop's end, where a leading wave has the next tile's
+      // raw rows in flight.
+      if ((tl & (kThrEvery - 1)) == kThrEvery - 1) thr_load();
 
       // The accumulators start at minus the lane's threshold, so that a register ends as sum - threshold and its
       // sign bit says "ruled out" (the difference cannot overflow: make_bound).  The 32 moves stand where the
@@ -837,7 +903,22 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       // half is ruled out (sum < threshold: the register's sign).  Register v of a lane is row
       // 32 h + 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are copies of the
       // slice's last row and must never be taken for neighbours.  `live` holds half 0 in its top 32 bits.
+      // Ahead of it the mid-tile barrier (B_2tl for the leading waves, B_2tl+1 for the trailing ones), and ahead of that
+      // the wave's one wait for global memory: everything it has in flight, see "Buffers" above.
+      const unsigned long long t_wait = stamp();
+      __builtin_amdgcn_s_waitcnt(kWaitVm0);
+      const unsigned long long t_bar = stamp();
+      __syncthreads();
       const unsigned long long t_cmp = stamp();
+      if (!trail) {
+        // the flag of tile tl - 1 (its slot is all zero at tile 0), asked for here and looked at behind the sign fold;
+        // the raw rows of tile tl + 1 go where the trailing waves have just finished C(tl - 1)
+        bailed = bail[((tl + 1) & 1) + zero_v];
+        if (has_next) {
+          stage_raw(xnext, (tl + 1) & 1);
+          xnext += kXrawV4;
+        }
+      }
       uint32_t skip[H] = {};
 #pragma unroll
       for (int h = 0; h < H; ++h) {
@@ -848,6 +929,8 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
         }
       }
       unsigned long long live = ~((unsigned long long)skip[0] << 32 | skip[1]);
+      // a leading wave drops the tile whose MFMAs it ran while the flag was being raised, and leaves
+      if (__builtin_amdgcn_readfirstlane(bailed)) break;
       if (nrows < kTileRows) {
         unsigned long long valid = 0;
 #pragma unroll
@@ -899,22 +982,29 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
       const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
       if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
-      const unsigned long long t_wait = stamp();
-      // the next tile and the thresholds have landed: a whole tile after their loads were issued
-      __builtin_amdgcn_s_waitcnt(kWaitVm0);
-      const unsigned long long t_bar = stamp();
-      __syncthreads();
+      const unsigned long long t_bar2 = stamp();
+      __syncthreads();  // B_2tl+1 for the leading waves, B_2tl+2 for the trailing ones
       const unsigned long long t_end = stamp();
       ph[kPhStage] += t_mfma - t_top;
-      ph[kPhMfma] += t_cmp - t_mfma;
-      ph[kPhCompact] += (t_wait - t_cmp) - (ph[kPhDrain] - drained);
+      ph[kPhMfma] += t_wait - t_mfma;
       ph[kPhVmWait] += t_bar - t_wait;
-      ph[kPhBarrier] += t_end - t_bar;
+      ph[kPhMidBarrier] += t_cmp - t_bar;
+      ph[kPhCompact] += (t_bar2 - t_cmp) - (ph[kPhDrain] - drained);
+      ph[kPhBarrier] += t_end - t_bar2;
       ph[kPhLoop] += t_end - t_top;
-      // The flag is asked for here and looked at behind the next tile's first LDS wait: no round trip of its own.
-      bailed = bail[(tl & 1) + zero_v];
+      t_last = t_end;
+      // A trailing wave asks for this tile's flag here, complete at the barrier it has just passed, and looks at it
+      // behind the next tile's first LDS wait: no round trip of its own.
+      if (trail) bailed = bail[(tl & 1) + zero_v];
     }
-    gave_up = __builtin_amdgcn_readfirstlane(bailed) != 0;  // whether it was seen at a tile's top or the slice ended with it
+    // B_2n, which the trailing waves passed as the last of their loop, and behind it the last tile's flag.  A leading
+    // wave that left the loop with the flag up has passed as many barriers as the trailing waves that left at the top
+    // of the same tile: it takes none here.
+    if (!trail && !__builtin_amdgcn_readfirstlane(bailed)) {
+      __syncthreads();
+      bailed = bail[((tl + 1) & 1) + zero_v];
+    }
+    gave_up = __builtin_amdgcn_readfirstlane(bailed) != 0;  // whether it was seen inside the loop or the slice ended with it
   }
   // a wave must not end with a load into its workgroup's LDS in flight
   if (gave_up) __builtin_amdgcn_s_waitcnt(kWaitVm0);
@@ -928,7 +1018,9 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
     unsigned long long *out = stamps_out + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kWaves + w) * (kPhases + 1);
 #pragma unroll
     for (int k = 0; k < kPhases; ++k) out[k] = ph[k];
-    out[kPhases] = (unsigned long long)tl;  // tiles this wave ran
+    // tiles this wave ran and, above them, the SIMD it ran on (HW_ID bits 5:4): the half-steps count on waves w and
+    // w + 4 sharing one
+    out[kPhases] = (unsigned long long)tl | (unsigned long long)(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3) << 32;
   }
 #endif
   if (gave_up) {
@@ -961,7 +1053,7 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
     }
     return;
   }
-  __syncthreads();
+  // no barrier here: k1s[te] and k2s[te] are this wave's own queries'
 
   const int qi = blockIdx.x * kQPerBlock + te;
   if (qi < N) {
@@ -1209,18 +1301,30 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
 #ifdef SPV_L1K2_PHASE_STAMPS
   {
     static const char *const names[kPhases] = {"stage issue + refresh", "MFMA run", "compare + compaction", "drains",
-                                               "vmcnt(0) wait", "barrier wait", "whole tile"};
+                                               "vmcnt(0) wait", "barrier wait", "whole tile", "mid-tile barrier wait"};
     std::vector<unsigned long long> h(nstamp);
     SPV_HIP_CHECK(hipStreamSynchronize(stream));
     SPV_HIP_CHECK(hipMemcpy(h.data(), d_stamps, nstamp * 8, hipMemcpyDeviceToHost));
     SPV_HIP_CHECK(hipFree(d_stamps));
-    unsigned long long sum[kPhases + 1] = {};
-    for (size_t i = 0; i < nstamp; ++i) sum[i % (kPhases + 1)] += h[i];
-    const double tiles = (double)std::max(1ull, sum[kPhases]);
-    fprintf(stderr, "l1k2_prune phase stamps, %d x %d: %llu wave-tiles\n", xrows, yrows, sum[kPhases]);
-    for (int k = 0; k < kPhases; ++k)
-      fprintf(stderr, "  %-24s %14llu cycles  %8.1f per wave-tile  %5.1f %%\n", names[k], sum[k], sum[k] / tiles,
-              100.0 * sum[k] / (double)std::max(1ull, sum[kPhLoop]));
+    // the wide form per half of its workgroup: waves 0-3 lead, waves 4-7 trail by half a tile; a wave's last word holds
+    // its tiles and, above them, the SIMD it ran on
+    const int groups = wide ? 2 : 1;
+    // (a workgroup's first wave starts on any SIMD; what the half-steps count on is that waves w and w + 4 share one)
+    unsigned long long sum[2][kPhases + 1] = {}, apart = 0;
+    for (size_t i = 0; i < nstamp; ++i) {
+      const size_t k = i % (kPhases + 1), w = i / (kPhases + 1) % waves;
+      sum[w * groups / waves][k] += k < kPhases ? h[i] : h[i] & 0xFFFFFFFFull;
+      if (k == kPhases && wide && w < 4 && (h[i] >> 32) != (h[i + 4 * (kPhases + 1)] >> 32)) ++apart;
+    }
+    for (int g = 0; g < groups; ++g) {
+      const double tiles = (double)std::max(1ull, sum[g][kPhases]);
+      fprintf(stderr, "l1k2_prune phase stamps, %d x %d, waves %d-%d: %llu wave-tiles\n", xrows, yrows, g * waves / groups,
+              (g + 1) * waves / groups - 1, sum[g][kPhases]);
+      for (int k = 0; k < kPhases; ++k)
+        fprintf(stderr, "  %-24s %14llu cycles  %8.1f per wave-tile  %5.1f %%\n", names[k], sum[g][k], sum[g][k] / tiles,
+                100.0 * sum[g][k] / (double)std::max(1ull, sum[g][kPhLoop]));
+    }
+    if (wide) fprintf(stderr, "  waves w < 4 not on the SIMD of wave w + 4: %llu of %zu\n", apart, nstamp / (kPhases + 1) / 2);
   }
 #endif
   if (l1k2_knobs().prune_stats) {  // debugging aid: synchronises
