@@ -121,8 +121,9 @@ constexpr int kWideSkipTilesAlone = 2, kWideWarmTilesShared = kWarmTilesShared /
 // prints their totals.  Such a build is for attribution only and is never the one that is timed: a stamp waits
 // for lgkmcnt(0) and pins the schedule around it.
 // The wide form has two barriers per tile: kPhBarrier is the one that ends a tile, kPhMidBarrier the one between its
-// MFMA run and its compare (the narrow form leaves it zero).
-enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPhLoop, kPhMidBarrier, kPhases };
+// MFMA run and its compare, and kPhArm is the arming of the next tile's accumulators at the end of its compare, which
+// the narrow form does in its top, kPhStage (the narrow form leaves both zero).
+enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPhLoop, kPhMidBarrier, kPhArm, kPhases };
 #ifdef SPV_L1K2_PHASE_STAMPS
 #define SPV_STAMP_PARAM , unsigned long long *stamps_out
 #define SPV_STAMP_ARG , d_stamps
@@ -603,8 +604,12 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
 // leaving workgroup lists its two query blocks of 256.  What follows is the narrow kernel's text with those changes.
 // LDS 157704 of 163840 bytes: ftile 2 x 64 x 512, qraw 512 x 128, xraw 2 x 64 x 128, k1s / k2s 8192, queue 2048, bail 8.
 // Registers: B 128, accumulators 64, A 12, lane offsets 5 and the rest inside the 256 that 8 waves per CU allow, none
-// spilled; during a drain the accumulators are dead as in the narrow form.  To fit, the ragged tile's offsets and the
-// epilogue's addresses are made again from the thread index instead of being carried across the loop.
+// spilled.  The accumulators are declared ahead of the tile loop and armed (set to minus the lane's thresholds) at the end
+// of the tile before, see "Arming" below; between a tile's sign fold and that point, the drains among it, they are dead as
+// in the narrow form, which is what lets a drain's 64 registers of row pieces fit.  To fit, the ragged tile's offsets and
+// the epilogue's addresses are made again from the thread index instead of being carried across the loop.
+// A tile's top is the first two A reads, the stage issue, the trailing waves' look at the flag and every second tile the
+// two threshold loads; the first MFMA accumulates in place.  tests/test_l1k2_prune_arm_isa.py holds that in the assembly.
 // __launch_bounds__' second argument is waves per SIMD here: 512 threads are two per SIMD already.
 __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
     const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
@@ -822,6 +827,31 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
     // trailing waves are then at the top of tile t + 1 and leave before they bound a pair of it, as every wave did with
     // one barrier per tile.  The leading waves have run M(t + 1) already: they drop its accumulators (no compare, no
     // queue entry, no statistics) and leave too.  Both have passed 2t + 3 barriers.
+    // Arming.  The accumulators live across the loop: a tile's MFMAs accumulate in place into registers that the end of
+    // the tile before set to minus the lane's threshold (see the accumulators' comment in the narrow kernel).  arm() is
+    // refresh, whose k2s[] only this wave's own drains write and whose seen[] landed at a mid-tile vmcnt(0), and the 64
+    // moves; it needs no barrier, so it stands where the wave would wait for the end-of-tile barrier while the other wave
+    // of its SIMD runs its MFMAs, and a tile's top is the first A reads, the stage issue and the flag test alone.
+    v16i acc[H][2];
+    auto arm = [&](bool shared) {
+      refresh(shared);
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+#pragma unroll
+          for (int v = 0; v < 16; ++v) acc[h][b][v] = ntq[b];
+          // made here: left to itself the compiler sinks the moves below the barrier that follows, into the next tile's top
+          asm volatile("" : "+v"(acc[h][b]));
+        }
+      }
+    };
+    arm(true);  // tile 0
+    // thresholds inherited from other slices: the share rule is judged sooner
+    if (__builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
+      warm = kWarmTilesShared;
+      skip_tiles = 0;
+    }
     const bool trail = __builtin_amdgcn_readfirstlane(w) >= kWaves / 2;  // wave-uniform
     if (trail) __syncthreads();                                           // B_0
 
@@ -832,15 +862,19 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       const int row0 = row_begin + tl * kTileRows;
       const bool has_next = tl + 1 < ntiles;
       // this lane's A-operand slot at k-step 0 in this tile's buffer: row c, piece g ^ (c & 15)
-      const int a0 = (tl & 1) * kFtileV4 + c * kLdsRowV4 + (g ^ (c & 15));
+      // (in bytes, so that each read's address is one XOR of it: with a shift behind the XOR the compiler makes the
+      // second read's address in the register that the read then fills, and waits ahead of both for the flag read)
+      const int a0 = ((tl & 1) * kFtileV4 + c * kLdsRowV4 + (g ^ (c & 15))) * 16;
       // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair.  Each
       // ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same of the upper half) holds 16
       // distinct c mod 16 at one g, hence 16 distinct 16-byte slots of the 256-byte bank row: no conflict.
       // Piece (2 ks + g) ^ (c & 15) = (g ^ (c & 15)) ^ 2 ks; the row and the buffer lie above those bits.
-      // The first two reads are the tile's first instructions: the stage issue and the thresholds run in their
+      // The first two reads are the tile's first instructions: the stage issue and the flag test run in their
       // latency (the memory clobber of the loads keeps them ahead).
       // k-step 16 h + ks is k-step ks of row half h, 32 rows further on
-      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, ftile[0][(a0 + (ks >> 4) * (32 * kLdsRowV4)) ^ (2 * (ks & 15))]); };
+      auto lda = [&](int ks) {
+        return __builtin_bit_cast(v4i, *(const uint4 *)((const char *)&ftile[0][0] + ((a0 ^ (32 * (ks & 15))) + (ks >> 4) * (32 * kLdsRowV4 * 16))));
+      };
       v4i a3[3];
       a3[0] = lda(0);
       a3[1] = lda(1);
@@ -856,40 +890,22 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
         }
         fnext += kFtileV4;
       }
-      const bool shared = (tl & (kThrEvery - 1)) == 0;  // the shared thresholds move slowly: every 128 rows is enough
       const int nrows = min(kTileRows, row_end - row0);
-      refresh(shared);
-      if (tl == 0 && __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
-        warm = kWarmTilesShared;
-        skip_tiles = 0;
-      }
       // The trailing waves leave after the tile whose flag was raised, before they bound a pair of this one (a leading
-      // wave gets here with `bailed` zero: it looks at the flag behind the mid-tile barrier).  The loads
-      // and the thresholds just issued are harmless: every published value is a valid bound, the exit path
-      // publishes anyway, and it waits for the loads.  The flag arrived with the k2s[] that the thresholds were
-      // made from; pinning them here keeps that one wait ahead of the branch (sunk below it, the reads would be
-      // pending on the way out of the loop and the compiler would wait for them at every tile's top).
-      asm volatile("" ::"v"(ntq[0]), "v"(ntq[1]));
+      // wave gets here with `bailed` zero: it looks at the flag behind the mid-tile barrier).  The loads just issued
+      // and the thresholds published at the end of the tile before are harmless: every published value is a valid
+      // bound, the exit path publishes anyway, and it waits for the loads.  The flag was asked for ahead of the two A
+      // reads and is looked at under a counted wait, with them still in flight; the armed accumulators are dropped.
       if (__builtin_amdgcn_readfirstlane(bailed)) break;
       // for the next tile; they land behind this tile's MFMAs.  Behind the branch: on the way out of the loop no load that
       // the compiler knows of is pending, so it asks for none at the loop's end, where a leading wave has the next tile's
       // raw rows in flight.
       if ((tl & (kThrEvery - 1)) == kThrEvery - 1) thr_load();
 
-      // The accumulators start at minus the lane's threshold, so that a register ends as sum - threshold and its
-      // sign bit says "ruled out" (the difference cannot overflow: make_bound).  The 32 moves stand where the
-      // wave waits for its first A reads anyway, and take a subtraction per register out of the compare.
+      // The accumulators were armed at minus the lane's threshold (arm, ahead of the loop), so that a register ends
+      // as sum - threshold and its sign bit says "ruled out" (the difference cannot overflow: make_bound).
       // Row half h of the tile (rows 32 h .. 32 h + 31) has its own pair of accumulators; the A reads run on across
       // the boundary between the halves.
-      v16i acc[H][2];
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-#pragma unroll
-          for (int v = 0; v < 16; ++v) acc[h][b][v] = ntq[b];
-        }
-      }
       const unsigned long long t_mfma = stamp();
 #pragma unroll
       for (int ks = 0; ks < 16 * H; ++ks) {
@@ -982,6 +998,12 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
       const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
       if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
+      // The next tile's accumulators, from the second best that this tile's drains left and the shared thresholds that
+      // landed at its mid-tile wait.  Armed behind the last tile too, where nobody reads them and nothing is published:
+      // under `if (has_next)` the accumulators of the path not taken stay live across the drains, which need their
+      // registers for the rows' pieces, and 50 registers spill.
+      const unsigned long long t_arm = stamp();
+      arm(has_next && ((tl + 1) & (kThrEvery - 1)) == 0);  // the shared thresholds move slowly: every 128 rows is enough
       const unsigned long long t_bar2 = stamp();
       __syncthreads();  // B_2tl+1 for the leading waves, B_2tl+2 for the trailing ones
       const unsigned long long t_end = stamp();
@@ -989,7 +1011,8 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       ph[kPhMfma] += t_wait - t_mfma;
       ph[kPhVmWait] += t_bar - t_wait;
       ph[kPhMidBarrier] += t_cmp - t_bar;
-      ph[kPhCompact] += (t_bar2 - t_cmp) - (ph[kPhDrain] - drained);
+      ph[kPhCompact] += (t_arm - t_cmp) - (ph[kPhDrain] - drained);
+      ph[kPhArm] += t_bar2 - t_arm;
       ph[kPhBarrier] += t_end - t_bar2;
       ph[kPhLoop] += t_end - t_top;
       t_last = t_end;
@@ -1300,8 +1323,10 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   SPV_HIP_CHECK(hipGetLastError());
 #ifdef SPV_L1K2_PHASE_STAMPS
   {
-    static const char *const names[kPhases] = {"stage issue + refresh", "MFMA run", "compare + compaction", "drains",
-                                               "vmcnt(0) wait", "barrier wait", "whole tile", "mid-tile barrier wait"};
+    // the narrow form's top holds its refresh and accumulator set-up as well, and its arming line is zero
+    static const char *const names[kPhases] = {"top: reads, stage issue", "MFMA run", "compare + compaction", "drains",
+                                               "vmcnt(0) wait", "barrier wait", "whole tile", "mid-tile barrier wait",
+                                               "arming the next tile"};
     std::vector<unsigned long long> h(nstamp);
     SPV_HIP_CHECK(hipStreamSynchronize(stream));
     SPV_HIP_CHECK(hipMemcpy(h.data(), d_stamps, nstamp * 8, hipMemcpyDeviceToHost));
