@@ -154,7 +154,7 @@ void spv_release_cached_memory(void);
 const char *spv_version(void);
 
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
- * "l1k2_tile", "l1k2_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
+ * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
  * "ann_merge", "ann_rerank", "cascade_project",
  * "cascade_buckets", "cascade_probe_refine", "dlt", "rectify") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
@@ -411,6 +411,14 @@ void sift_filter_batch_destroy(void *sfb);
 int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
                           uint64_t *idx, int32_t *dist);
 
+/* The L1 2-NN of many (query set, database set) pairs in one call: spv_l1k2_batch_device (section 3, which
+ * states the contract) through host pointers.  desc uint8[seg_off[nseg], dim], idx uint64[out_rows,2], dist
+ * int32[out_rows,2], out_rows = the query-set rows summed over pairs.  One device: the first one selected by
+ * spv_set_device / spv_set_devices (sharding over the device list is not implemented for this form).  An
+ * addition: the reference has no such symbol. */
+int spv_nn_bruteforcel1k2_batch(const uint8_t *desc, const long long *seg_off, int nseg, int dim,
+                                const int32_t *pairs, int npairs, uint64_t *idx, int32_t *dist);
+
 /* nn_bruteforce (is_int = 0: float32 rows, float32 dist) / nn_bruteforcei (is_int = 1: int32 rows,
  * int32 dist) with caller-allocated idx uint64[yrows,k], dist [yrows,k]. */
 int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
@@ -549,6 +557,46 @@ int spv_l1k2_plan(int xrows, int yrows, int dim, int out[5]);
 int spv_l1k2_device(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,
                     uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes,
                     void *stream);
+
+/* The exact L1 2-NN of a collection of descriptor-set pairs, one main launch for all of them (l1k2_batch.hip):
+ * what a multi-view front-end runs between "SIFT for N images" and "geometry per image pair".
+ *   desc     uint8[total_rows, dim]: the tables of nseg descriptor sets back to back.
+ *   seg_off  host long long[nseg + 1], non-decreasing, seg_off[0] = 0, seg_off[nseg] = total_rows < 2^31; set s is
+ *            rows [seg_off[s], seg_off[s + 1]) and may be empty.
+ *   pairs    host int32[npairs, 2] = (query set, database set), in any order, repeats allowed, a set may be
+ *            paired with itself (no self-exclusion: a row then finds itself at distance 0, as
+ *            nn_bruteforcel1k2(x, x) does).
+ *   idx      uint64[out_rows, 2], dist int32[out_rows, 2]; out_rows = the query-set row counts summed over pairs.
+ *            Pair p owns the rows from the sum over the pairs before it, in query-row order; idx is the row
+ *            number inside the database set; missing neighbours are ((size_t)-1, INT_MAX).
+ * Per pair the rows are bit for bit what spv_l1k2_device(database set, query set) writes: the two smallest
+ * (dist, idx) in lexicographic order, whatever way the call cuts the work.  Limits: dim a positive multiple of
+ * 16 and <= 256, the widths of the tile kernels (widths without a kernel of their own are zero-padded once, for
+ * the whole of desc, into the workspace; dim > 256 is SPV_ERR_INVALID in this form), nseg >= 0, npairs >= 0, set
+ * numbers in [0, nseg), d_desc and d_ws 16-byte aligned, d_idx 8-byte, d_dist 4-byte.  Outside them
+ * SPV_ERR_INVALID, nothing launched, no output touched.  One device.  Very large single pairs remain the job of
+ * spv_l1k2_device (its bound path from 512k rows on is not taken here).
+ *
+ * spv_l1k2_batch_plan: host only, touches no device.  out = {kernel row width in bytes, queries per lane, work
+ * items, out_rows, largest slice count of any pair, workspace bytes}; items may be NULL, otherwise int32[items_cap, 5]
+ * receives the first min(work items, items_cap) work items, one workgroup each, as (pair, first query row within
+ * the query set, query rows, first database row within the database set, database rows): exactly the list the
+ * device call launches, in its order.  The SPECTAVI_L1K2_Q / SPECTAVI_L1K2_BLOCKS overrides are applied.
+ * SPV_ERR_INVALID leaves out and items untouched.  spv_l1k2_batch_workspace_bytes: out[5] (0 for arguments the
+ * plan rejects): 16 bytes per out row, 32 per work item, the padded desc if any; it does not grow with the slice count.
+ *
+ * spv_l1k2_batch_device: seg_off and pairs are read before the call returns.  The call may wait for the upload
+ * of its small work table, which is queued on `stream`; it never waits for its kernels, and everything else is
+ * asynchronous on `stream`.  Kernel names for spv_profile_read: "l1k2_batch" (the main kernel, one launch per
+ * call), "l1k2_batch_merge" (keys to idx / dist).  spv_ratio_test and spv_ratio_test_device apply to the
+ * concatenated output as it stands: their matches are (out row, row within the database set). */
+int spv_l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs,
+                        long long out[6], int32_t *items, long long items_cap);
+size_t spv_l1k2_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, const int32_t *pairs,
+                                      int npairs);
+int spv_l1k2_batch_device(const uint8_t *d_desc, const long long *seg_off, int nseg, int dim,
+                          const int32_t *pairs, int npairs, uint64_t *d_idx, int32_t *d_dist, void *d_ws,
+                          size_t ws_bytes, void *stream);
 
 /* The query loop sharded over the GPUs of one node with everything resident (the loop
  * the reference shards over OpenMP threads, src/BruteForceNnL1K2.h:92-93): one process, rank r =

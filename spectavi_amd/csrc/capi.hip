@@ -243,6 +243,32 @@ int host_l1k2(const uint8_t *x, const uint8_t *y, int xrows, int yrows, int dim,
   });
 }
 
+// The many-pairs L1 2-NN through host pointers, on the first selected device (no sharding): the whole of desc up,
+// one l1k2_batch_run, both results back.
+int host_l1k2_batch(const uint8_t *desc, const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs,
+                    uint64_t *idx, int32_t *dist) {
+  L1K2BatchPlan p;
+  SPV_TRY(l1k2_batch_plan(seg_off, nseg, dim, pairs, npairs, &p));
+  if (p.out_rows == 0) return SPV_OK;
+  if (!desc || !idx || !dist) return set_error(SPV_ERR_INVALID, "null pointer");
+  const int dev = device_list()[0];
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
+  const size_t xb = (size_t)p.total_rows * dim;
+  const size_t ib = (size_t)p.out_rows * 2 * sizeof(uint64_t), db = (size_t)p.out_rows * 2 * sizeof(int32_t);
+  HostPrefault touch_idx(idx, ib, {{desc, xb}});
+  HostPrefault touch_dist(dist, db, {{desc, xb}});
+  DevBuf dx, di, dd, ws;
+  SPV_TRY(alloc_all({{&dx, xb}, {&di, ib}, {&dd, db}, {&ws, p.total_bytes}}));
+  SPV_TRY(dx.copy_in(desc, xb, st));
+  SPV_TRY(l1k2_batch_run(dx.as<uint8_t>(), seg_off, nseg, dim, pairs, npairs, di.as<uint64_t>(), dd.as<int32_t>(), ws.p,
+                         p.total_bytes, st));
+  touch_idx.wait();
+  touch_dist.wait();
+  SPV_TRY(dd.copy_out(dist, db, st));
+  return download(dev, idx, di.p, ib, st);
+}
+
 // Exact p-norm k-NN through host pointers, on the first selected device (no sharding).
 int host_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                     uint64_t *idx, void *dist) {
@@ -1088,6 +1114,11 @@ int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yro
   return host_api([&] { return host_l1k2(x, y, xrows, yrows, dim, idx, dist); });
 }
 
+int spv_nn_bruteforcel1k2_batch(const uint8_t *desc, const long long *seg_off, int nseg, int dim, const int32_t *pairs,
+                                int npairs, uint64_t *idx, int32_t *dist) {
+  return host_api([&] { return host_l1k2_batch(desc, seg_off, nseg, dim, pairs, npairs, idx, dist); });
+}
+
 int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                       uint64_t *idx, void *dist) {
   return host_api([&] { return host_bruteforce(x, y, is_int, xrows, yrows, dim, k, p, idx, dist); });
@@ -1372,6 +1403,43 @@ int spv_l1k2_device(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows
                     uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, void *stream) {
   return api([&] { return l1k2_run(d_x, d_y, xrows, yrows, dim, d_idx, d_dist, d_ws, ws_bytes,
                                    static_cast<hipStream_t>(stream)); });
+}
+
+int spv_l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs, long long out[6],
+                        int32_t *items, long long items_cap) {
+  return api([&] {
+    if (!out || (items && items_cap < 0)) return set_error(SPV_ERR_INVALID, "null output or negative items_cap");
+    L1K2BatchPlan p;
+    SPV_TRY(l1k2_batch_plan(seg_off, nseg, dim, pairs, npairs, &p));
+    const long long n = (long long)p.items.size();
+    out[0] = p.dim_pad;
+    out[1] = p.q;
+    out[2] = n;
+    out[3] = p.out_rows;
+    out[4] = p.max_slices;
+    out[5] = (long long)p.total_bytes;
+    for (long long e = 0; items && e < std::min(n, items_cap); ++e) {
+      const L1K2BatchItem &it = p.items[(size_t)e];
+      const int32_t row[5] = {it.pair, it.y0, it.yrows, it.x0, it.xrows};
+      std::copy(row, row + 5, items + 5 * e);
+    }
+    return (int)SPV_OK;
+  });
+}
+
+size_t spv_l1k2_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs) {
+  L1K2BatchPlan p;
+  const int st = guard([&] { return l1k2_batch_plan(seg_off, nseg, dim, pairs, npairs, &p); });
+  if (st != SPV_OK) clear_error();
+  return st == SPV_OK ? p.total_bytes : 0;
+}
+
+int spv_l1k2_batch_device(const uint8_t *d_desc, const long long *seg_off, int nseg, int dim, const int32_t *pairs,
+                          int npairs, uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, void *stream) {
+  return api([&] {
+    return l1k2_batch_run(d_desc, seg_off, nseg, dim, pairs, npairs, d_idx, d_dist, d_ws, ws_bytes,
+                          static_cast<hipStream_t>(stream));
+  });
 }
 
 size_t spv_bruteforce_workspace_bytes(int xrows, int yrows, int dim, int k) {

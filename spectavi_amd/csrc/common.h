@@ -159,6 +159,32 @@ L1K2Plan l1k2_plan(int xrows, int yrows, int dim);  // host only
 int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int dim,
              uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
 
+// l1k2.hip's pad_rows_kernel on `stream`: rows of dim bytes -> rows of dim_pad bytes, zero filled (both multiples of 16)
+void l1k2_pad_rows(const uint8_t *d_src, uint8_t *d_dst, size_t rows, int dim, int dim_pad, hipStream_t stream);
+
+// ---- L1 2-NN of many descriptor-set pairs in one launch (l1k2_batch.hip) ---------------
+// One workgroup's share of a collection: 256 q queries of one pair's query set against one slice of its database set.
+struct L1K2BatchItem {
+  int32_t pair, y0, yrows, x0, xrows;  // pair; first query row within the query set, query rows; first database row within the database set, database rows
+};
+// Everything l1k2_batch_run launches for a collection under the SPECTAVI_L1K2_Q / SPECTAVI_L1K2_BLOCKS knobs.
+struct L1K2BatchPlan {
+  int dim_pad;      // kernel row width in bytes (>= dim, zero padded)
+  int q;            // queries per lane, one value for the whole call
+  bool padded;      // pad_rows_kernel copies the whole of desc to dim_pad first
+  int max_slices;   // largest number of database slices of any pair
+  long long total_rows, out_rows;
+  std::vector<long long> out_off;    // [npairs + 1]: pair p owns out rows [out_off[p], out_off[p + 1])
+  std::vector<L1K2BatchItem> items;  // the grid, longest item first
+  // workspace: byte offsets, in this order.  The out rows' pairs of 64-bit keys, the device form of `items`, the
+  // padded copy of desc (empty unless `padded`).
+  size_t off_keys, off_items, off_pad, total_bytes;
+};
+// SPV_ERR_INVALID (message set, *p untouched) outside the limits of include/spectavi_amd.h; host only
+int l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs, L1K2BatchPlan *p);
+int l1k2_batch_run(const uint8_t *d_desc, const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs,
+                   uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
 // ---- matrix-core lower bound for the L1 2-NN at dim 128 (l1k2_prune.hip) -------------
 struct L1K2Bound {
   int8_t phi[256][4];  // features of a byte value

@@ -227,6 +227,78 @@ def l1k2_plan(xrows, yrows, dim):
     return dict(dim_pad=out[0], q=out[1], slices=out[2], slice_rows=out[3], wide=bool(out[4]))
 
 
+def _batch_args(seg_off, pairs, total_rows, dim):
+    """seg_off -> int64[nseg + 1], pairs -> int32[npairs, 2], out_off int64[npairs + 1]; ValueError for anything
+    spv_l1k2_batch_device would reject or that does not describe a table of total_rows rows."""
+    seg = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
+    if seg.size < 1 or seg[0] != 0 or np.any(np.diff(seg) < 0):
+        raise ValueError("seg_off must start at 0 and never decrease")
+    if total_rows is not None and int(seg[-1]) != int(total_rows):
+        raise ValueError("seg_off ends at %d, desc has %d rows" % (int(seg[-1]), int(total_rows)))
+    if int(seg[-1]) >= 2 ** 31:
+        raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    if dim <= 0 or dim % 16 != 0:
+        raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
+    if dim > 256:
+        raise ValueError("the many-pairs form takes dim <= 256 (dim=%d)" % dim)
+    prs = np.asarray(pairs)
+    if prs.size == 0:
+        prs = np.zeros((0, 2), np.int32)
+    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
+        raise ValueError("pairs must be integers of shape [npairs, 2]")
+    nseg = seg.size - 1
+    if prs.size and (int(prs.min()) < 0 or int(prs.max()) >= nseg):
+        raise ValueError("pairs name sets outside [0, %d)" % nseg)
+    prs = np.ascontiguousarray(prs, dtype=np.int32)
+    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]], dtype=np.int64)]).astype(np.int64)
+    return seg, prs, out_off
+
+
+def l1k2_batch_plan(seg_off, pairs, dim, want_items=False):
+    """The launch plan l1k2_batch() follows for a collection (spv_l1k2_batch_plan; host only, no device
+    touched): dict of dim_pad (kernel row width), q (queries per lane), items (work items = workgroups),
+    out_rows, max_slices (largest number of database slices of any pair), workspace_bytes and out_off
+    (int64[npairs + 1]: pair p owns out rows [out_off[p], out_off[p + 1])).  With want_items also the work
+    items themselves, int32[items, 5] = (pair, first query row within the query set, query rows, first
+    database row within the database set, database rows), in launch order."""
+    seg, prs, out_off = _batch_args(seg_off, pairs, None, dim)
+    out = (ct.c_longlong * 6)()
+    check(clib.spv_l1k2_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out, None, 0))
+    plan = dict(dim_pad=int(out[0]), q=int(out[1]), items=int(out[2]), out_rows=int(out[3]), max_slices=int(out[4]),
+                workspace_bytes=int(out[5]), out_off=out_off)
+    if want_items:
+        items = np.empty((plan["items"], 5), np.int32)
+        check(clib.spv_l1k2_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out,
+                                       items.ctypes.data, len(items)))
+        return plan, items
+    return plan
+
+
+def l1k2_batch(desc, seg_off, pairs, workspace=None):
+    """Exact L1 2-NN of many descriptor-set pairs on device, one main launch for all of them: desc uint8
+    [total_rows, D] (CUDA tensor) holds the sets back to back, set s = rows seg_off[s]:seg_off[s + 1];
+    pairs [npairs, 2] = (query set, database set).  Returns (idx int64 [out_rows, 2] -- the ABI's size_t
+    bits, -1 = no neighbour; the row number inside the database set --, dist int32 [out_rows, 2], out_off
+    int64 ndarray [npairs + 1]): pair p owns rows out_off[p]:out_off[p + 1], each bit for bit
+    l1k2(database set, query set).  ratio_test() applies to the concatenated output as it stands: its
+    matches are (out row, row within the database set).  Asynchronous on the current stream but for the
+    upload of the work table."""
+    _need(desc, torch.uint8, "desc")
+    if desc.dim() != 2:
+        raise ValueError("desc must be [total_rows, dim]")
+    total, dim = desc.shape
+    seg, prs, out_off = _batch_args(seg_off, pairs, total, dim)
+    out_rows = int(out_off[-1])
+    idx = torch.empty((out_rows, 2), dtype=torch.int64, device=desc.device)
+    dist = torch.empty((out_rows, 2), dtype=torch.int32, device=desc.device)
+    nbytes = clib.spv_l1k2_batch_workspace_bytes(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs))
+    with _on_device_of(desc) as stream:
+        ws = (workspace or _default_ws).get(nbytes, desc.device)
+        check(clib.spv_l1k2_batch_device(desc.data_ptr(), seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs),
+                                         idx.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+    return idx, dist, out_off
+
+
 def cascade_plan(xrows, yrows, dim, m, n, g):
     """The launch plan cascade() follows for this shape under the SPECTAVI_CASCADE_* environment of the
     moment (spv_cascade_plan; host only, no device touched): dict of family, pa, pb, gmax_q, probe_kind,

@@ -47,6 +47,48 @@ def nn_bruteforcel1k2(x, y, nthreads=1):
     return nn_idx.asarray(), nn_dist.asarray()
 
 
+def nn_bruteforcel1k2_batch(tables, pairs=None):
+    """
+    nn_bruteforcel1k2 for many pairs of descriptor tables in one call (an addition: the reference has no
+    such function).  `tables` is a list of uint8 arrays [rows_i, dim], one width for all; `pairs` a list
+    of (query table, database table) numbers, by default every i < j as (query j, database i).
+
+    Returns a list with one (nn_idx uint64 [rows, 2], nn_dist int32 [rows, 2]) per pair, each what
+    nn_bruteforcel1k2(tables[database], tables[query]) returns.  The arrays of the list are views of one
+    concatenated result, to which spv_ratio_test applies as it stands: its matches are (row of the
+    concatenated output, row within the database table).
+    """
+    tables = [np.ascontiguousarray(t) for t in tables]
+    if not tables:
+        raise ValueError("no tables")
+    dim = tables[0].shape[1] if tables[0].ndim == 2 else -1
+    if any(t.ndim != 2 or t.dtype != np.uint8 or t.shape[1] != dim for t in tables):
+        raise ValueError("tables must be uint8 arrays [rows, dim] of one width")
+    if dim <= 0 or dim % 16 != 0:
+        raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
+    if dim > 256:
+        raise ValueError("the many-pairs form takes dim <= 256 (dim=%d)" % dim)
+    n = len(tables)
+    if pairs is None:
+        pairs = [(j, i) for i in range(n) for j in range(i + 1, n)]
+    prs = np.asarray(pairs)
+    if prs.size == 0:
+        prs = np.zeros((0, 2), np.int32)
+    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
+        raise ValueError("pairs must be integers of shape [npairs, 2]")
+    if prs.size and (prs.min() < 0 or prs.max() >= n):
+        raise ValueError("pairs name tables outside [0, %d)" % n)
+    prs = np.ascontiguousarray(prs, dtype=np.int32)
+    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    desc = np.concatenate(tables) if seg[-1] else np.zeros((0, dim), np.uint8)
+    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
+    idx = np.empty((int(out_off[-1]), 2), np.uint64)
+    dist = np.empty((int(out_off[-1]), 2), np.int32)
+    check(clib.spv_nn_bruteforcel1k2_batch(desc.ctypes.data, seg.ctypes.data, n, dim, prs.ctypes.data, len(prs),
+                                           idx.ctypes.data, dist.ctypes.data))
+    return [(idx[a:b], dist[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
+
+
 # ==================================================================================
 # brute-force p-norm k-NN     (reference spectavi/feature.py:204-289)
 # ==================================================================================
