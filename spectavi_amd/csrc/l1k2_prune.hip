@@ -16,7 +16,7 @@
 // The kernel.  grid = (blocks of 256 queries, database slices); 4 waves, each owning 64 queries whose
 // 512 feature bytes stay in VGPRs as the B operand (2 column blocks x 16 k-steps x 4 dwords).  Database
 // feature tiles (32 rows x 512 B) stream through LDS, double buffered, one barrier per tile, loaded from
-// global memory straight into LDS (global_load_lds_dwordx4; see stage_issue), each load addressed by a scalar
+// global memory straight into LDS (global_load_lds_dwordx4; see Stage), each load addressed by a scalar
 // base that moves on by one tile per iteration plus a tile-invariant lane offset.  Per tile and wave: 32 MFMAs
 // whose accumulators start at minus the lane's threshold 128 m - p thr (the C layout puts one query on each
 // lane), so that the sign bit of each accumulator register says "ruled out"; the 32 signs are folded into one bit
@@ -57,17 +57,26 @@
 // buffers, 5 the lane offsets of the stage loads and 10 what a ragged tile makes them from again, where 10 held
 // the five 64-bit addresses; no register carries the staged tile, which is what lets the 64 of a drain's 16
 // pieces fit), no scratch; LDS 78856 of the 81920 bytes that two workgroups per CU allow.  The ISA is checked
-// after every change by tests/test_l1k2_prune_isa.py (registers, spills, scratch, LDS, and no vmcnt wait between
-// the first and the last MFMA of a tile), tests/test_l1k2_prune_staging_isa.py (the loads to LDS, no vmcnt wait
-// between them and the tile's MFMAs, counted lgkmcnt waits among the MFMAs) and
-// tests/test_l1k2_prune_chain_isa.py (the scalar-base form of the loads, the vector instructions at a tile's top).
+// after every change, without a GPU, by six modules that compile this file with the Makefile's flags:
+// tests/test_l1k2_prune_isa.py (registers, spills, scratch, LDS, and no vmcnt wait between the first and the last MFMA of
+// a tile), tests/test_l1k2_prune_staging_isa.py (the loads to LDS, no vmcnt wait between them and the tile's MFMAs,
+// counted lgkmcnt waits among the MFMAs), tests/test_l1k2_prune_chain_isa.py (the scalar-base form of the loads, the
+// vector instructions at a tile's top), and for the wide form tests/test_l1k2_prune_wide_isa.py (its budgets),
+// tests/test_l1k2_prune_stagger_isa.py (its half-steps) and tests/test_l1k2_prune_arm_isa.py (its arming; that module
+// also pins the narrow kernel's instruction stream, register numbers aside).
 //
 // Two forms.  All of the above is l1k2_prune_kernel, the narrow form, which prune mode 1 runs and whose decisions per
 // 32-row tile and 256-query workgroup the case tables of the tests pin.  Where `auto` takes the path and the grid
 // fills the chip, l1k2_prune_plan chooses l1k2_prune_wide_kernel instead: 64-row tiles, 512 queries and 8 waves per
 // workgroup, one workgroup per CU, so that what a tile costs whatever survives is paid half as often per row.  Its
-// LDS and register budget stand at its head; tests/test_l1k2_prune_wide_isa.py checks them.  The two share the
-// survivor passes (drain_lanes, drain_octets); spv_l1k2_set_prune_form / SPECTAVI_L1K2_PRUNE_FORM force either.
+// LDS and register budget stand at its head.  PruneForm holds every number in which the two differ; what they do alike
+// is written once, ahead of them: the LDS arrays, the prologue, the staging (Stage), the thresholds, the sign fold, the
+// `valid` mask and the compaction, the share rule, the epilogues and the survivor passes (drain_lanes, drain_octets).  A
+// kernel binds those to its own state with one-line lambdas where a piece is called from several places; the tile loops
+// differ in structure and are two.  Two short pieces stand in both kernels as they were, the B-operand load and the choice
+// between the two drains at the end of a tile: moved into a function, either changes the narrow kernel's schedule ahead of
+// its loop, which tests/test_l1k2_prune_arm_isa.py holds fixed.  spv_l1k2_set_prune_form / SPECTAVI_L1K2_PRUNE_FORM force
+// either form.
 #include "common.h"
 #include "l1k2_bound_tuned.h"
 
@@ -83,38 +92,45 @@ namespace {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+constexpr int kAuxThreads = 256;              // the feature and threshold-init kernels
 constexpr int kQPerWave = 64;                 // two MFMA column blocks of 32
-constexpr int kQPerBlock = kWaves * kQPerWave;
-constexpr int kTileRows = 32;                 // MFMA rows
 constexpr int kFeatV4 = 32;                   // 512 feature bytes per row = 32 x 16 B
 constexpr int kLdsRowV4 = kFeatV4;            // no pad: a wave's direct-to-LDS load lands 64 x 16 B in a row
 constexpr int kQueue = 128;                   // < 64 queued, then <= 64 appended in one round
 constexpr int kDrainBatch = 8;                // 16-byte pieces of each of a survivor's two rows requested at once
-constexpr int kOctetPairs = 8;                // up to here the end-of-tile drain takes eight lanes per pair (drain_octets), see l1k2_prune_run
-constexpr int kFtileV4 = kTileRows * kLdsRowV4;
-constexpr int kXrawV4 = kTileRows * 8;
-constexpr int kSkipTilesAlone = 3;            // tiles left out of the running share while a workgroup has no thresholds at all
-constexpr int kWarmTilesShared = 8;           // ... at the break-even share, with thresholds inherited from other slices
-constexpr int kWarmTilesAlone = 256;          // ... and without: its own thresholds take thousands of rows to settle
 constexpr int kShareUnit = 1024;              // the break-even survivor share is passed in 1/1024
 constexpr int kBreakEvenShare = 164;          // 16 %, see l1k2_prune_plan and profiles/r07_prune_breakeven.jsonl
 constexpr uint32_t kMaxDist = 128 * 255;
 constexpr int kStatSlots = 16;                // survivor counters, spread to keep the atomics apart
 constexpr int kStatWords = kStatSlots * 4 * 2;
 constexpr int kWaitVm0 = 0x0F70;              // s_waitcnt vmcnt(0), the other counters left alone
-constexpr int kOctetPairsWide = 8;            // kOctetPairs of the wide form: 8 / 16 / 24 timed at 1M x 1M, DESIGN.md 4.1, "64-row tiles"
 
-// l1k2_prune_wide_kernel (see there): 64-row tiles, 8 waves.  What the narrow form counts in tiles keeps its number
-// of rows: the threshold cadence and the warm-up of the share rule.
-constexpr int kWideHalves = 2;                // MFMA row halves of a tile
-constexpr int kWideWaves = 8;
-constexpr int kWideThreads = 64 * kWideWaves;
-constexpr int kWideQPerBlock = kWideWaves * kQPerWave;
-constexpr int kWideTileRows = 32 * kWideHalves;
-constexpr int kWideThrEvery = 2;              // tiles between two publications of the thresholds: 128 rows, as every fourth narrow tile
-constexpr int kWideSkipTilesAlone = 2, kWideWarmTilesShared = kWarmTilesShared / 2, kWideWarmTilesAlone = kWarmTilesAlone / 2;
+// A form of the bound kernel: H MFMA row halves of 32 rows per tile, four waves of 64 queries per half.  Narrow (H = 1)
+// is l1k2_prune_kernel, Wide (H = 2) l1k2_prune_wide_kernel; the kernels, the plan and the launch take every number
+// that depends on the form from here.  What the narrow form counts in tiles keeps its number of rows in the wide form:
+// the threshold cadence and the warm-up of the share rule (kSkipTilesAlone is no plain halving: 2 against 3).
+template <int H_>
+struct PruneForm {
+  static_assert(H_ == 1 || H_ == 2, "a 32- or a 64-bit survivor mask per lane");
+  static constexpr int H = H_;
+  static constexpr int kWaves = 4 * H;
+  static constexpr int kThreads = 64 * kWaves;
+  static constexpr int kQPerBlock = kWaves * kQPerWave;
+  static constexpr int kTileRows = 32 * H;                 // MFMA rows
+  static constexpr int kFtileV4 = kTileRows * kLdsRowV4;   // a feature tile in LDS
+  static constexpr int kXrawV4 = kTileRows * 8;            // and its raw rows
+  static constexpr int kRowBits = 4 + H;                   // a queue entry is query of the wave << kRowBits | row of the tile
+  static constexpr int kThrEvery = 4 / H;                  // tiles between two publications of the thresholds: 128 rows
+  static constexpr int kSkipTilesAlone = H == 1 ? 3 : 2;   // tiles left out of the running share while a workgroup has no thresholds at all
+  static constexpr int kWarmTilesShared = 8 / H;           // ... at the break-even share, with thresholds inherited from other slices
+  static constexpr int kWarmTilesAlone = 256 / H;          // ... and without: its own thresholds take thousands of rows to settle
+  // up to here the end-of-tile drain takes eight lanes per pair (drain_octets), see l1k2_prune_run; for the wide form 8 / 16 / 24
+  // were timed at 1M x 1M, DESIGN.md 4.1, "64-row tiles"
+  static constexpr int kOctetPairs = 8;
+  static constexpr bool kRaggedFromCopy = H > 1;           // see Stage::ragged_offsets
+};
+using Narrow = PruneForm<1>;
+using Wide = PruneForm<2>;
 
 // Phase stamps (-DSPV_L1K2_PHASE_STAMPS, never in the shipped library): every wave sums the shader cycles of each
 // phase of its tiles in scalar registers and lane 0 stores the sums once, when the wave ends; l1k2_prune_run
@@ -142,21 +158,21 @@ __device__ __forceinline__ unsigned long long stamp() { return 0; }
 
 struct FeatTable { uint32_t w[256]; };        // phi(a) packed little-endian, one dword per byte value
 
-__global__ __launch_bounds__(kThreads) void l1k2_feature_kernel(const uint32_t *__restrict__ src,
+__global__ __launch_bounds__(kAuxThreads) void l1k2_feature_kernel(const uint32_t *__restrict__ src,
                                                                 uint4 *__restrict__ dst, size_t words,
                                                                 FeatTable tab) {
   __shared__ uint32_t t[256];
   t[threadIdx.x] = tab.w[threadIdx.x];
   __syncthreads();
-  for (size_t e = blockIdx.x * (size_t)kThreads + threadIdx.x; e < words; e += (size_t)gridDim.x * kThreads) {
+  for (size_t e = blockIdx.x * (size_t)kAuxThreads + threadIdx.x; e < words; e += (size_t)gridDim.x * kAuxThreads) {
     const uint32_t v = src[e];
     dst[e] = make_uint4(t[v & 255], t[(v >> 8) & 255], t[(v >> 16) & 255], t[v >> 24]);
   }
 }
 
 // thresholds "none yet"; the counters and the work-list length behind them zero
-__global__ __launch_bounds__(kThreads) void l1k2_thr_init_kernel(uint32_t *thr, size_t nthr, size_t n) {
-  for (size_t e = blockIdx.x * (size_t)kThreads + threadIdx.x; e < n; e += (size_t)gridDim.x * kThreads)
+__global__ __launch_bounds__(kAuxThreads) void l1k2_thr_init_kernel(uint32_t *thr, size_t nthr, size_t n) {
+  for (size_t e = blockIdx.x * (size_t)kAuxThreads + threadIdx.x; e < n; e += (size_t)gridDim.x * kAuxThreads)
     thr[e] = e < nthr ? 0xFFFFFFFFu : 0u;
 }
 
@@ -253,71 +269,98 @@ __device__ __forceinline__ void drain_octets(int n, int &cnt, int lane, const ui
   wave_lds_fence();
 }
 
-__global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
-    const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
-    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
-    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
-  // 512-byte alignment: the A-operand read folds its swizzle into the address with one XOR
-  __shared__ __attribute__((aligned(512))) uint4 ftile[2][kFtileV4];
-  __shared__ unsigned long long k1s[kQPerBlock], k2s[kQPerBlock];
-  __shared__ uint4 qraw[kQPerBlock * 8];            // the workgroup's query rows as they are
-  __shared__ uint4 xraw[2][kXrawV4];                // the tile's database rows as they are
-  __shared__ uint16_t queue[kWaves][kQueue];        // survivors: query of the wave << 5 | row of the tile
-  __shared__ int bail[2];                           // set in tile tl & 1: the workgroup gives the bound up
-  // 78856 bytes in all: two workgroups per CU
+// ======== What the two forms share, each piece once.  A kernel below shows the order of its phases, its barriers and
+// what is particular to its form; everything else it takes from here, templated on its PruneForm F.
 
-  const int t = threadIdx.x;
-  const int w = t >> 6, lane = t & 63, c = lane & 31, g = lane >> 5;
-  const int s = blockIdx.y;
-  const int row_begin = s * slice_rows;
-  const int row_end = min(M, row_begin + slice_rows);
-  const int qbase = blockIdx.x * kQPerBlock + w * kQPerWave;  // this wave's first query
-  const int qslot = w * kQPerWave;                            // and its first top-2 slot
+// ---- LDS of a workgroup, one set of arrays per form (a kernel's LDS is what it names of them).
+// 78856 bytes in all for the narrow form, two workgroups per CU; 157704 for the wide form, one.
+// 512-byte alignment: the A-operand read folds its swizzle into the address with one XOR
+template <class F> __shared__ __attribute__((aligned(512))) uint4 lds_ftile[2][F::kFtileV4];  // the feature tiles, double buffered
+template <class F> __shared__ unsigned long long lds_k1s[F::kQPerBlock];                      // the top-2 keys of the workgroup's queries
+template <class F> __shared__ unsigned long long lds_k2s[F::kQPerBlock];
+template <class F> __shared__ uint4 lds_qraw[F::kQPerBlock * 8];                              // the workgroup's query rows as they are
+template <class F> __shared__ uint4 lds_xraw[2][F::kXrawV4];                                  // the tile's database rows as they are
+template <class F> __shared__ uint16_t lds_queue[F::kWaves][kQueue];                          // survivors: query of the wave << kRowBits | row of the tile
+template <class F> __shared__ int lds_bail[2];                                                // set in tile tl & 1: the workgroup gives the bound up
 
-  k1s[t] = ~0ull;
-  k2s[t] = ~0ull;
-  if (t < 2) bail[t] = 0;
+// ---- a thread's place: wave w of the workgroup and its lane; in the MFMA's C layout the lane holds column c (a query) of
+// either column block and the rows of group g
+template <class F>
+struct Place {
+  int t, w, lane, c, g;
+  int qbase;  // this wave's first query
+  int qslot;  // and its first top-2 slot
+  __device__ __forceinline__ explicit Place(int t)
+      : t(t), w(t >> 6), lane(t & 63), c(lane & 31), g(lane >> 5), qbase(blockIdx.x * F::kQPerBlock + w * kQPerWave), qslot(w * kQPerWave) {}
+};
+
+// ---- prologue: no key yet, no flag, and the workgroup's query rows (rows past the last query are copies of it)
+template <class F>
+__device__ __forceinline__ void prologue(int t, const uint4 *__restrict__ y, int N) {
+  lds_k1s<F>[t] = ~0ull;
+  lds_k2s<F>[t] = ~0ull;
+  if (t < 2) lds_bail<F>[t] = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const int e = t + i * kThreads;
-    qraw[e] = y[(size_t)min((int)blockIdx.x * kQPerBlock + (e >> 3), N - 1) * 8 + (e & 7)];
+    const int e = t + i * F::kThreads;
+    lds_qraw<F>[e] = y[(size_t)min((int)blockIdx.x * F::kQPerBlock + (e >> 3), N - 1) * 8 + (e & 7)];
   }
+}
 
-  // ---- staging of the database tiles, from global memory straight into LDS (global_load_lds_dwordx4): no
-  // registers carry the tile and no ds_write stores it.  A wave's instruction lands its 64 x 16 B one after the
-  // other from the base in M0, so the LDS image is lane-linear and unpadded, and the swizzle that keeps the
-  // A-operand reads off each other's banks is made on the source side: the lane that lands on piece j of row r
-  // fetches piece j ^ (r & 15), and piece q of row r is read back from slot q ^ (r & 15).  EXEC must be full at
-  // these loads, so rows past the end of a ragged last tile are not predicated off but clamped to the last
-  // row: the tile then holds copies of it, which the `valid` mask keeps out of the queue.
-  // The loads are one asm statement, not __builtin_amdgcn_global_load_lds: the compiler, knowing of a load to
-  // LDS in flight, waits for vmcnt(0) before the first LDS read that may alias it (the A operand of this very
-  // tile, in the other buffer) and at every workgroup fence (each drain), and turns every counted lgkmcnt wait
-  // of the MFMA run into lgkmcnt(0).  Unknown to it, they count on vmcnt only, behind its own loads at most,
-  // which can only make one of its waits longer; nothing but the s_waitcnt vmcnt(0) ahead of the tile's
-  // barrier makes the data visible.  M0 is the compiler's: it is put back in the same statement.
-  typedef __attribute__((address_space(3))) void *lds_ptr;
-  const uint32_t lds_f = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&ftile[0][w * 64]));
-  const uint32_t lds_r = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&xraw[0][w * 64]));
-  // Addresses.  The tile's first feature row and first raw row are two wave-uniform 64-bit pointers, which the
-  // scalar unit advances by one tile per iteration (at 4M rows the feature offset passes 2^31), and each load
-  // adds the lane's byte offset within the tile (global_load_lds_dwordx4 vOff, s[base:base+1]).  The five
-  // offsets are the same for every full tile and stay in five registers; only a ragged tile, the last of a
-  // slice, computes them again with the row clamp, under a wave-uniform branch around that arithmetic alone
-  // (no full tile follows a ragged one, so they are overwritten in place).
+// ---- staging of the database tiles, from global memory straight into LDS (global_load_lds_dwordx4): no
+// registers carry the tile and no ds_write stores it.  A wave's instruction lands its 64 x 16 B one after the
+// other from the base in M0, so the LDS image is lane-linear and unpadded, and the swizzle that keeps the
+// A-operand reads off each other's banks is made on the source side: the lane that lands on piece j of row r
+// fetches piece j ^ (r & 15), and piece q of row r is read back from slot q ^ (r & 15).  EXEC must be full at
+// these loads, so rows past the end of a ragged last tile are not predicated off but clamped to the last
+// row: the tile then holds copies of it, which the `valid` mask keeps out of the queue.
+// The loads are one asm statement, not __builtin_amdgcn_global_load_lds: the compiler, knowing of a load to
+// LDS in flight, waits for vmcnt(0) before the first LDS read that may alias it (the A operand of this very
+// tile, in the other buffer) and at every workgroup fence (each drain), and turns every counted lgkmcnt wait
+// of the MFMA run into lgkmcnt(0).  Unknown to it, they count on vmcnt only, behind its own loads at most,
+// which can only make one of its waits longer; nothing but the s_waitcnt vmcnt(0) ahead of the tile's
+// barrier makes the data visible.  M0 is the compiler's: it is put back in the same statement.
+// Addresses.  The tile's first feature row and first raw row are two wave-uniform 64-bit pointers, which the
+// scalar unit advances by one tile per iteration (at 4M rows the feature offset passes 2^31), and each load
+// adds the lane's byte offset within the tile (global_load_lds_dwordx4 vOff, s[base:base+1]).  The five
+// offsets are the same for every full tile and stay in five registers; only a ragged tile, the last of a
+// slice, computes them again with the row clamp, under a wave-uniform branch around that arithmetic alone
+// (no full tile follows a ragged one, so they are overwritten in place).
+// A tile is F::kThreads x 16 B four times over for the features and once for the raw rows: five loads per thread.
+template <class F>
+struct Stage {
+  uint32_t lds_f, lds_r;  // where this wave's first feature load and its raw load land in buffer 0
   uint32_t voff[5];
-  auto lane_offsets = [&](int nrows) {
+  int t;
+
+  __device__ __forceinline__ Stage(const Place<F> &at) : t(at.t) {
+    typedef __attribute__((address_space(3))) void *lds_ptr;
+    lds_f = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&lds_ftile<F>[0][at.w * 64]));
+    lds_r = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&lds_xraw<F>[0][at.w * 64]));
+    lane_offsets(F::kTileRows, t);
+  }
+  __device__ __forceinline__ void lane_offsets(int nrows, int t) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int e = t + i * kThreads, r = e >> 5;
+      const int e = t + i * F::kThreads, r = e >> 5;
       voff[i] = (uint32_t)(min(r, nrows - 1) * kFeatV4 + ((e & 31) ^ (r & 15))) * 16u;
     }
     voff[4] = (uint32_t)(min(t >> 3, nrows - 1) * 8 + (t & 7)) * 16u;
-  };
-  lane_offsets(kTileRows);
-  auto stage_issue = [&](const uint4 *ftile0, const uint4 *xtile0, int nrows, int b) {
-    if (__builtin_expect(nrows < kTileRows, 0)) lane_offsets(nrows);
-    const uint32_t f0 = lds_f + b * (kFtileV4 * 16), r0 = lds_r + b * (kXrawV4 * 16);
+  }
+  __device__ __forceinline__ void ragged_offsets(int nrows) {
+    if (__builtin_expect(nrows < F::kTileRows, 0)) {
+      // F::kRaggedFromCopy: from the thread index alone, behind a move that the compiler cannot see through: else it keeps
+      // every row and piece number of the five loads in a register of its own across the loop, for a path that runs once a
+      // slice.  The wide form has no such registers to spare; the narrow form has, and is kept as it was.
+      int tt = t;
+      if constexpr (F::kRaggedFromCopy) asm volatile("" : "+v"(tt));
+      lane_offsets(nrows, tt);
+    }
+  }
+  // all five loads of a tile of nrows rows at (ftile0, xtile0) into buffer b
+  __device__ __forceinline__ void all(const uint4 *ftile0, const uint4 *xtile0, int nrows, int b) {
+    ragged_offsets(nrows);
+    const uint32_t f0 = lds_f + b * (F::kFtileV4 * 16), r0 = lds_r + b * (F::kXrawV4 * 16);
     uint32_t m0_kept;
     // s_nop 2: with the two s_mov ahead of it, five states between whatever wrote a base register and its first use
     asm volatile(
@@ -329,65 +372,269 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
         "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %12\n\t"
         "s_mov_b32 m0, %0"
         : "=&s"(m0_kept)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "s"(f0), "s"(f0 + 4096u), "s"(f0 + 8192u),
-          "s"(f0 + 12288u), "s"(r0), "s"(ftile0), "s"(xtile0)
+        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "s"(f0), "s"(f0 + F::kThreads * 16u),
+          "s"(f0 + F::kThreads * 32u), "s"(f0 + F::kThreads * 48u), "s"(r0), "s"(ftile0), "s"(xtile0)
         : "memory");
-  };
+  }
+  // The five loads in two statements as well, for waves that issue a tile's features and its raw rows at different
+  // times (the wide form's leading waves).  The two in a row are not all(): each saves and restores M0.  raw() takes
+  // the offset that feat()'s ragged_offsets left: the raw rows of a tile are issued after its features, and nothing
+  // follows a ragged tile.
+  __device__ __forceinline__ void feat(const uint4 *ftile0, int nrows, int b) {
+    ragged_offsets(nrows);
+    const uint32_t f0 = lds_f + b * (F::kFtileV4 * 16);
+    uint32_t m0_kept;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %5\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
+        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %9\n\t"
+        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %9\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(m0_kept)
+        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(f0), "s"(f0 + F::kThreads * 16u), "s"(f0 + F::kThreads * 32u),
+          "s"(f0 + F::kThreads * 48u), "s"(ftile0)
+        : "memory");
+  }
+  __device__ __forceinline__ void raw(const uint4 *xtile0, int b) {
+    const uint32_t r0 = lds_r + b * (F::kXrawV4 * 16);
+    uint32_t m0_kept;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(m0_kept)
+        : "v"(voff[4]), "s"(r0), "s"(xtile0)
+        : "memory");
+  }
+};
 
-  // ---- the survivor passes (drain_lanes, drain_octets) over this wave's queue, queries and top-2 slots
-  int cnt = 0;  // wave-uniform
-  unsigned long long ph[kPhases] = {};  // wave-uniform cycle sums, all zero and dead without the stamps
-  auto drain = [&](int n, const uint4 *xr, uint32_t row0) {
-    drain_lanes<5>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
-  };
-  auto drain_octets = [&](int n, const uint4 *xr, uint32_t row0) {
-    spv::drain_octets<5>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
-  };
-
-  // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b] = 128 m - p thr; what is
-  // kept is ntq[b] = -tq[b], the value that the tile's accumulators start from.  seen[b] is the
-  // shared threshold read last.  Only atomicMin ever writes thr[], so a later read is never above an earlier
-  // one and simply replaces it (and any value ever read there is a valid bound).  The two loads are issued
-  // a tile ahead of the refresh that uses them, behind that tile's stage loads, and have landed by the
-  // vmcnt(0) before its barrier: no tile waits for them.  Lanes past the last query read the last
-  // query's threshold, whose features they also carry.
-  int ntq[2];
-  uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-  auto thr_load = [&]() {
+// ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b] = 128 m - p thr; what is
+// kept is ntq[b] = -tq[b], the value that the tile's accumulators start from.  seen[b] is the
+// shared threshold read last.  Only atomicMin ever writes thr[], so a later read is never above an earlier
+// one and simply replaces it (and any value ever read there is a valid bound).  The two loads are issued
+// a tile ahead of the refresh that uses them, behind that tile's stage loads, and have landed by the
+// vmcnt(0) before its barrier: no tile waits for them.  Lanes past the last query read the last
+// query's threshold, whose features they also carry.
+template <class F>
+__device__ __forceinline__ void load_thresholds(uint32_t (&seen)[2], const uint32_t *thr, const Place<F> &at, int N) {
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
-      seen[b] = __hip_atomic_load(&thr[min(qbase + 32 * b + c, N - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto refresh = [&](bool shared) {
-    uint32_t loc[2];
+  for (int b = 0; b < 2; ++b)
+    seen[b] = __hip_atomic_load(&thr[min(at.qbase + 32 * b + at.c, N - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ntq[] from the wave's own second best and seen[]; `shared`: the own second best is published where it is lower
+template <class F>
+__device__ __forceinline__ void refresh_thresholds(int (&ntq)[2], const uint32_t (&seen)[2], bool shared, uint32_t *thr, const Place<F> &at, int N, int p,
+                                                   int m128) {
+  uint32_t loc[2];
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    loc[b] = (uint32_t)(lds_k2s<F>[at.qslot + 32 * b + at.c] >> 32);
+    // thr = "none yet" keeps every pair: sum >= 128 m - p 32640 always
+    ntq[b] = p * (int)min(min(loc[b], seen[b]), kMaxDist) - m128;
+  }
+  if (shared && at.g == 0) {
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      loc[b] = (uint32_t)(k2s[qslot + 32 * b + c] >> 32);
-      // thr = "none yet" keeps every pair: sum >= 128 m - p 32640 always
-      ntq[b] = p * (int)min(min(loc[b], seen[b]), kMaxDist) - m128;
+      const int qi = at.qbase + 32 * b + at.c;
+      if (qi < N && loc[b] < seen[b]) atomicMin(&thr[qi], loc[b]);
     }
-    if (shared && g == 0) {
+  }
+}
+// whether any lane of the wave has a threshold from another slice
+__device__ __forceinline__ bool any_inherited(const uint32_t (&seen)[2]) {
+  return __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull;
+}
+
+// ---- compare and compaction.  A lane's pairs of a tile are numbered n = 32 h + 16 b + v: row half h, column block b,
+// accumulator register v, which is row 32 h + 8 (v / 4) + 4 g + v % 4 of the tile; `live` has 32 H bits, pair n at bit
+// 32 H - 1 - n (row half 0 on top).
+template <int H>
+using Live = std::conditional_t<H == 1, uint32_t, unsigned long long>;
+__device__ __forceinline__ int first_pair(uint32_t live) { return __clz(live | 1u); }
+__device__ __forceinline__ int first_pair(unsigned long long live) { return __clzll(live | 1ull); }
+
+// One bit per accumulator register: the register's sign says that the pair is ruled out (sum < threshold).
+template <int H>
+__device__ __forceinline__ Live<H> fold_signs(const v16i (&acc)[H][2]) {
+  Live<H> skip = 0;
 #pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int qi = qbase + 32 * b + c;
-        if (qi < N && loc[b] < seen[b]) atomicMin(&thr[qi], loc[b]);
+  for (int h = 0; h < H; ++h) {
+    uint32_t sk = 0;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) sk = __builtin_amdgcn_alignbit(sk, (uint32_t)acc[h][b][v], 31);
+    }
+    if constexpr (H == 1) skip = sk;
+    else skip = skip << 32 | sk;
+  }
+  return ~skip;
+}
+
+// Rows past the end of a ragged last tile are copies of the slice's last row and must never be taken for neighbours.
+template <int H>
+__device__ __forceinline__ Live<H> valid_pairs(int nrows, int g) {
+  Live<H> valid = 0;
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v)
+      if (32 * h + 8 * (v >> 2) + 4 * g + (v & 3) < nrows) valid |= (Live<H>)0x80008000u << (32 * (H - 1 - h)) >> v;
+  }
+  return valid;
+}
+
+// Compaction: every round each lane with survivors left appends its first one to the wave's queue (cnt entries so far),
+// and 64 queued pairs are drained at once.  Returns the tile's survivors; drain_cycles is for the stamps.
+// drain(n, xr, row0) is the kernel's: drain_lanes over its wave's queue.  xraw[buf] is named at the call, not once ahead
+// of the loop: the drains' address arithmetic is hoisted out of the tile loop only in this form.
+template <class F, class Drain>
+__device__ __forceinline__ int compact(Live<F::H> live, int &cnt, const Place<F> &at, int buf, uint32_t row0, unsigned long long &drain_cycles,
+                                       Drain &drain) {
+  int tile_surv = 0;
+  for (;;) {
+    const bool has = live != 0;
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(has);
+    if (mask == 0ull) break;
+    const int n = first_pair(live);
+    const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (has) {
+      lds_queue<F>[at.w][pos] =
+          (uint16_t)(((32 * ((n >> 4) & 1) + at.c) << F::kRowBits) | (32 * (n >> 5) + 8 * ((n >> 2) & 3) + 4 * at.g + (n & 3)));
+      live &= ~((Live<F::H>)1 << (32 * F::H - 1) >> n);
+    }
+    const int add = __popcll(mask);
+    cnt += add;
+    tile_surv += add;
+    if (cnt >= 64) {
+      const unsigned long long d0 = stamp();
+      drain(64, lds_xraw<F>[buf], row0);
+      drain_cycles += stamp() - d0;
+    }
+  }
+  return tile_surv;
+}
+
+// ---- the share rule.  Above the break-even share a survivor pass costs more than the exact loop saves.  A wave that
+// sees that raises the flag of this tile; after the barrier the whole workgroup reads the same flag
+// (the next tile uses the other one, and a flag is never lowered), puts itself on the work list of
+// l1k2_tile_kernel, which then computes this (query block, slice) from scratch, and leaves.
+// recent: survivors of the last tiles, each tile weighing 7/8 of the one after it: 8 x the running share.  The first
+// skip_tiles tiles are left out of it; up to tile `warm` only a share of 3/4 counts (F::kSkipTilesAlone and
+// F::kWarmTilesAlone, or 0 and F::kWarmTilesShared where thresholds were inherited from other slices).  The tile counters
+// are never negative and are compared unsigned, which is what the compiler made of them when the rule stood in the kernel.
+template <class F>
+__device__ __forceinline__ int judge_share(int recent, uint32_t warm, uint32_t skip_tiles, uint32_t tl, int tile_surv, int max_share, int lane) {
+  recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
+  const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
+  if (lane == 0 && recent * (kShareUnit / 8) > limit * (F::kTileRows * kQPerWave)) lds_bail<F>[tl & 1] = 1;
+  return recent;
+}
+
+// ---- the epilogues, for thread t of the workgroup and its query, in slice s
+// Hand-over.  What this workgroup has found still bounds its queries' second best from above: hand it on;
+// the exact kernel merges into the partial pair, which starts as "none".  The work list is in query blocks of 256
+// (l1k2_tile_kernel<32, 2, 128>): F::kQPerBlock / 256 entries, clipped at the last block that holds a query (the
+// workgroup's first block always does).
+template <class F>
+__device__ __forceinline__ void hand_over(int t, int s, int N, int S, uint32_t *thr, uint32_t *work, uint64_t *__restrict__ part) {
+  const int qo = blockIdx.x * F::kQPerBlock + t;
+  if (qo < N) {
+    const uint32_t loc = (uint32_t)(lds_k2s<F>[t] >> 32);
+    if (loc < __hip_atomic_load(&thr[qo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qo], loc);
+    uint64_t *dst = part + ((size_t)qo * S + s) * 2;
+    dst[0] = ~0ull;
+    dst[1] = ~0ull;
+  }
+  if (t == 0) {
+    constexpr uint32_t kBlocks = F::kQPerBlock / 256;
+    const uint32_t first = kBlocks * blockIdx.x, nblk = 1 + min(kBlocks - 1, (uint32_t)((N + 255) / 256) - first - 1);
+    const uint32_t slot = atomicAdd(&work[0], nblk);
+#pragma unroll
+    for (uint32_t i = 0; i < kBlocks; ++i) {
+      if (i < nblk) {
+        work[2 + 2 * (slot + i)] = first + i;
+        work[3 + 2 * (slot + i)] = blockIdx.y;
       }
     }
-  };
+  }
+}
 
-  const int ntiles = (row_end - row_begin + kTileRows - 1) / kTileRows;
+// Result: the query's two keys of this slice, and its second best for the slices still running.
+template <class F>
+__device__ __forceinline__ void write_result(int t, int s, int N, int S, uint32_t *thr, uint64_t *__restrict__ part) {
+  const int qi = blockIdx.x * F::kQPerBlock + t;
+  if (qi < N) {
+    const unsigned long long a1 = lds_k1s<F>[t], a2 = lds_k2s<F>[t];
+    uint64_t *dst = part + ((size_t)qi * S + s) * 2;
+    dst[0] = a1;
+    dst[1] = a2;
+    const uint32_t loc = (uint32_t)(a2 >> 32);
+    if (loc < __hip_atomic_load(&thr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qi], loc);
+  }
+}
+
+// Statistics of wave w, by one of its lanes: pairs bounded and survivors.  Returns the wave's counters; the third counts
+// the pairs that a workgroup handing over leaves to the exact kernel.
+__device__ __forceinline__ unsigned long long *add_stats(unsigned long long *stats, int w, unsigned long long n_bound, unsigned long long n_surv) {
+  unsigned long long *st = stats + ((blockIdx.x + w) % kStatSlots) * 4;
+  atomicAdd(&st[0], n_bound);
+  atomicAdd(&st[1], n_surv);
+  return st;
+}
+
+#ifdef SPV_L1K2_PHASE_STAMPS
+// a wave's cycle sums and, behind them, a word of the form's own (the tiles it ran, at the least)
+template <class F>
+__device__ __forceinline__ void store_stamps(unsigned long long *stamps_out, int w, const unsigned long long (&ph)[kPhases], unsigned long long last) {
+  unsigned long long *out = stamps_out + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * F::kWaves + w) * (kPhases + 1);
+#pragma unroll
+  for (int k = 0; k < kPhases; ++k) out[k] = ph[k];
+  out[kPhases] = last;
+}
+#endif
+
+// ======== The narrow form: one barrier per tile, every wave in step; a tile's thresholds and accumulators are made at its top.
+__global__ __launch_bounds__(Narrow::kThreads, 2) void l1k2_prune_kernel(
+    const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
+    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
+    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
+  using F = Narrow;
+  const Place<F> at(threadIdx.x);
+  const int s = blockIdx.y;
+  const int row_begin = s * slice_rows;
+  const int row_end = min(M, row_begin + slice_rows);
+
+  prologue<F>(at.t, y, N);
+  Stage<F> stage(at);
+  int cnt = 0;  // the length of the wave's queue, wave-uniform
+  unsigned long long ph[kPhases] = {};  // wave-uniform cycle sums, all zero and dead without the stamps
+  // the survivor passes over this wave's queue, queries and top-2 slots
+  auto drain = [&](int n, const uint4 *xr, uint32_t row0) {
+    drain_lanes<F::kRowBits>(n, cnt, at.lane, lds_queue<F>, at.w, at.qslot, lds_qraw<F>, xr, lds_k1s<F>, lds_k2s<F>, row0);
+  };
+  auto drain_octets = [&](int n, const uint4 *xr, uint32_t row0) {
+    spv::drain_octets<F::kRowBits>(n, cnt, at.lane, lds_queue<F>, at.w, at.qslot, lds_qraw<F>, xr, lds_k1s<F>, lds_k2s<F>, row0);
+  };
+  int ntq[2];
+  uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+  auto thr_load = [&]() { load_thresholds(seen, thr, at, N); };
+  auto refresh = [&](bool shared) { refresh_thresholds(ntq, seen, shared, thr, at, N, p, m128); };
+
+  const int ntiles = (row_end - row_begin + F::kTileRows - 1) / F::kTileRows;
   if (ntiles > 0) {
-    stage_issue(fx + (size_t)row_begin * kFeatV4, x + (size_t)row_begin * 8, min(kTileRows, row_end - row_begin), 0);
+    stage.all(fx + (size_t)row_begin * kFeatV4, x + (size_t)row_begin * 8, min(F::kTileRows, row_end - row_begin), 0);
     __builtin_amdgcn_s_waitcnt(kWaitVm0);
   }
   __syncthreads();
   // the tile that the loop stages next
-  const uint4 *fnext = fx + ((size_t)row_begin + kTileRows) * kFeatV4, *xnext = x + ((size_t)row_begin + kTileRows) * 8;
+  const uint4 *fnext = fx + ((size_t)row_begin + F::kTileRows) * kFeatV4, *xnext = x + ((size_t)row_begin + F::kTileRows) * 8;
 
   unsigned long long n_bound = 0, n_surv = 0;  // wave-uniform statistics
   bool gave_up = false;                        // workgroup-uniform
-  int warm = kWarmTilesAlone, skip_tiles = kSkipTilesAlone;
-  int recent = 0;  // survivors of the last tiles, each tile weighing 7/8 of the one after it: 8 x the running share
+  int warm = F::kWarmTilesAlone, skip_tiles = F::kSkipTilesAlone, recent = 0;  // see judge_share
   int tl = 0;
   // bail[] of the tile before, read right behind its barrier.  The index carries a zero that the compiler cannot
   // see through: a value it knows to be wave-uniform is moved to a scalar register where it is loaded, which
@@ -395,13 +642,13 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
   int bailed = 0, zero_v = 0;
   asm volatile("" : "+v"(zero_v));
   {
-    // ---- this wave's queries as the B operand
     v4i bq[2][16];
+    // ---- this wave's queries as the B operand: 2 column blocks x 16 k-steps x 4 dwords
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      const uint4 *f = fy + (size_t)min(qbase + 32 * b + c, N - 1) * kFeatV4;
+      const uint4 *f = fy + (size_t)min(at.qbase + 32 * b + at.c, N - 1) * kFeatV4;
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + g]);
+      for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + at.g]);
     }
     thr_load();
     // The B operand is complete before the loop is entered.  Without this wait the compiler, which cannot
@@ -412,34 +659,34 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
     for (; tl < ntiles; ++tl) {
       const unsigned long long t_top = stamp();
       const unsigned long long drained = ph[kPhDrain];
-      const int row0 = row_begin + tl * kTileRows;
+      const int row0 = row_begin + tl * F::kTileRows;
       const bool has_next = tl + 1 < ntiles;
       // this lane's A-operand slot at k-step 0 in this tile's buffer: row c, piece g ^ (c & 15)
-      const int a0 = (tl & 1) * kFtileV4 + c * kLdsRowV4 + (g ^ (c & 15));
+      const int a0 = (tl & 1) * F::kFtileV4 + at.c * kLdsRowV4 + (at.g ^ (at.c & 15));
       // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair.  Each
       // ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same of the upper half) holds 16
       // distinct c mod 16 at one g, hence 16 distinct 16-byte slots of the 256-byte bank row: no conflict.
       // Piece (2 ks + g) ^ (c & 15) = (g ^ (c & 15)) ^ 2 ks; the row and the buffer lie above those bits.
       // The first two reads are the tile's first instructions: the stage issue and the thresholds run in their
       // latency (the memory clobber of the loads keeps them ahead).
-      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, ftile[0][a0 ^ (2 * ks)]); };
+      auto lda = [&](int ks) { return __builtin_bit_cast(v4i, lds_ftile<F>[0][a0 ^ (2 * ks)]); };
       v4i a3[3];
       a3[0] = lda(0);
       a3[1] = lda(1);
       // every wave passed the barrier of tile tl - 1 after its last read of these buffers
       if (has_next) {
-        stage_issue(fnext, xnext, min(kTileRows, row_end - row0 - kTileRows), (tl + 1) & 1);
-        fnext += kFtileV4;
-        xnext += kXrawV4;
+        stage.all(fnext, xnext, min(F::kTileRows, row_end - row0 - F::kTileRows), (tl + 1) & 1);
+        fnext += F::kFtileV4;
+        xnext += F::kXrawV4;
       }
-      const bool shared = (tl & 3) == 0;  // the shared thresholds move slowly: every fourth tile is enough
-      const int nrows = min(kTileRows, row_end - row0);
+      const bool shared = (tl & (F::kThrEvery - 1)) == 0;  // the shared thresholds move slowly: every fourth tile is enough
+      const int nrows = min(F::kTileRows, row_end - row0);
       refresh(shared);
-      if (tl == 0 && __builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
-        warm = kWarmTilesShared;
+      if (tl == 0 && any_inherited(seen)) {
+        warm = F::kWarmTilesShared;
         skip_tiles = 0;
       }
-      if ((tl & 3) == 3) thr_load();  // for the next tile; they land behind this tile's work
+      if ((tl & (F::kThrEvery - 1)) == F::kThrEvery - 1) thr_load();  // for the next tile; they land behind this tile's work
       // The workgroup leaves after the tile whose flag was raised, before it bounds a pair of this one.  The loads
       // and the thresholds just issued are harmless: every published value is a valid bound, the exit path
       // publishes anyway, and it waits for the loads.  The flag arrived with the k2s[] that the thresholds were
@@ -451,81 +698,37 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       // The accumulators start at minus the lane's threshold, so that a register ends as sum - threshold and its
       // sign bit says "ruled out" (the difference cannot overflow: make_bound).  The 32 moves stand where the
       // wave waits for its first A reads anyway, and take a subtraction per register out of the compare.
-      v16i acc[2];
+      v16i acc[1][2];
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
 #pragma unroll
-        for (int v = 0; v < 16; ++v) acc[b][v] = ntq[b];
+        for (int v = 0; v < 16; ++v) acc[0][b][v] = ntq[b];
       }
       const unsigned long long t_mfma = stamp();
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
         if (ks + 2 < 16) a3[(ks + 2) % 3] = lda(ks + 2);
-        acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[0][ks], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[1][ks], acc[1], 0, 0, 0);
+        acc[0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[0][ks], acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[1][ks], acc[0][1], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
 
-      // One bit per accumulator register: bit 31 - n of `skip` says that pair n = 16 b + v of this lane is
-      // ruled out (sum < threshold: the register's sign).  Register v of a lane is row
-      // 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are copies of the
-      // slice's last row and must never be taken for neighbours.
       const unsigned long long t_cmp = stamp();
-      uint32_t skip = 0;
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) skip = __builtin_amdgcn_alignbit(skip, (uint32_t)acc[b][v], 31);
-      }
-      uint32_t live = ~skip;
-      if (nrows < kTileRows) {
-        uint32_t valid = 0;
-#pragma unroll
-        for (int v = 0; v < 16; ++v)
-          if (8 * (v >> 2) + 4 * g + (v & 3) < nrows) valid |= 0x80008000u >> v;
-        live &= valid;
-      }
-      // compaction: every round each lane with survivors left appends its first one to the wave's queue
-      int tile_surv = 0;
-      for (;;) {
-        const bool has = live != 0;
-        const unsigned long long mask = __builtin_amdgcn_ballot_w64(has);
-        if (mask == 0ull) break;
-        const int n = __clz(live | 1u);
-        const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (has) {
-          queue[w][pos] = (uint16_t)(((32 * (n >> 4) + c) << 5) | (8 * ((n >> 2) & 3) + 4 * g + (n & 3)));
-          live &= ~(0x80000000u >> n);
-        }
-        const int add = __popcll(mask);
-        cnt += add;
-        tile_surv += add;
-        if (cnt >= 64) {
-          const unsigned long long d0 = stamp();
-          drain(64, xraw[tl & 1], (uint32_t)row0);
-          ph[kPhDrain] += stamp() - d0;
-        }
-      }
+      Live<F::H> live = fold_signs<F::H>(acc);
+      if (nrows < F::kTileRows) live &= valid_pairs<F::H>(nrows, at.g);
+      const int tile_surv = compact(live, cnt, at, tl & 1, (uint32_t)row0, ph[kPhDrain], drain);
       // the tile's raw rows are overwritten during the next tile: nothing stays queued
       if (cnt > 0) {
         const unsigned long long d0 = stamp();
         if (cnt <= octet_max)
-          drain_octets(cnt, xraw[tl & 1], (uint32_t)row0);
+          drain_octets(cnt, lds_xraw<F>[tl & 1], (uint32_t)row0);
         else
-          drain(cnt, xraw[tl & 1], (uint32_t)row0);
+          drain(cnt, lds_xraw<F>[tl & 1], (uint32_t)row0);
         ph[kPhDrain] += stamp() - d0;
       }
       n_bound += (unsigned long long)nrows * kQPerWave;
       n_surv += tile_surv;
-
-      // Above the break-even share a survivor pass costs more than the exact loop saves.  A wave that
-      // sees that raises the flag of this tile; after the barrier the whole workgroup reads the same flag
-      // (the next tile uses the other one, and a flag is never lowered), puts itself on the work list of
-      // l1k2_tile_kernel, which then computes this (query block, slice) from scratch, and leaves.
-      recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
-      const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
-      if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
+      recent = judge_share<F>(recent, warm, skip_tiles, tl, tile_surv, max_share, at.lane);
       const unsigned long long t_wait = stamp();
       // the next tile and the thresholds have landed: a whole tile after their loads were issued
       __builtin_amdgcn_s_waitcnt(kWaitVm0);
@@ -539,69 +742,34 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
       ph[kPhBarrier] += t_end - t_bar;
       ph[kPhLoop] += t_end - t_top;
       // The flag is asked for here and looked at behind the next tile's first LDS wait: no round trip of its own.
-      bailed = bail[(tl & 1) + zero_v];
+      bailed = lds_bail<F>[(tl & 1) + zero_v];
     }
     gave_up = __builtin_amdgcn_readfirstlane(bailed) != 0;  // whether it was seen at a tile's top or the slice ended with it
   }
   // a wave must not end with a load into its workgroup's LDS in flight
   if (gave_up) __builtin_amdgcn_s_waitcnt(kWaitVm0);
 #ifdef SPV_L1K2_PHASE_STAMPS
-  if (lane == 0) {
-    unsigned long long *out = stamps_out + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kWaves + w) * (kPhases + 1);
-#pragma unroll
-    for (int k = 0; k < kPhases; ++k) out[k] = ph[k];
-    out[kPhases] = (unsigned long long)tl;  // tiles this wave ran
-  }
+  if (at.lane == 0) store_stamps<F>(stamps_out, at.w, ph, (unsigned long long)tl);
 #endif
   if (gave_up) {
-    // what this workgroup has found still bounds its queries' second best from above: hand it on;
-    // the exact kernel merges into the partial pair, which starts as "none"
-    const int qo = blockIdx.x * kQPerBlock + t;
-    if (qo < N) {
-      const uint32_t loc = (uint32_t)(k2s[t] >> 32);
-      if (loc < __hip_atomic_load(&thr[qo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qo], loc);
-      uint64_t *dst = part + ((size_t)qo * S + s) * 2;
-      dst[0] = ~0ull;
-      dst[1] = ~0ull;
-    }
-    if (t == 0) {
-      const uint32_t slot = atomicAdd(&work[0], 1u);
-      work[2 + 2 * slot] = blockIdx.x;
-      work[3 + 2 * slot] = blockIdx.y;
-    }
-    if (lane == 0) {
-      unsigned long long *st = stats + ((blockIdx.x + w) % kStatSlots) * 4;
-      atomicAdd(&st[0], n_bound);
-      atomicAdd(&st[1], n_surv);
-      atomicAdd(&st[2], (unsigned long long)(row_end - row_begin) * kQPerWave);
-    }
+    hand_over<F>(at.t, s, N, S, thr, work, part);
+    if (at.lane == 0) atomicAdd(&add_stats(stats, at.w, n_bound, n_surv)[2], (unsigned long long)(row_end - row_begin) * kQPerWave);
     return;
   }
   __syncthreads();
-
-  const int qi = blockIdx.x * kQPerBlock + t;
-  if (qi < N) {
-    const unsigned long long a1 = k1s[t], a2 = k2s[t];
-    uint64_t *dst = part + ((size_t)qi * S + s) * 2;
-    dst[0] = a1;
-    dst[1] = a2;
-    const uint32_t loc = (uint32_t)(a2 >> 32);
-    if (loc < __hip_atomic_load(&thr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qi], loc);
-  }
-  if (lane == 0) {
-    unsigned long long *st = stats + ((blockIdx.x + w) % kStatSlots) * 4;
-    atomicAdd(&st[0], n_bound);
-    atomicAdd(&st[1], n_surv);
-  }
+  write_result<F>(at.t, s, N, S, thr, part);
+  if (at.lane == 0) add_stats(stats, at.w, n_bound, n_surv);
 }
 
-// The wide form: 64 database rows per loop iteration, so that what a tile costs whatever survives (the LDS round trips
-// of its top, queue and drain, the two fences, the vmcnt(0) and the barrier) is paid half as often per row.
+// ======== The wide form: 64 database rows per loop iteration, so that what a tile costs whatever survives (the LDS round
+// trips of its top, queue and drain, the two fences, the vmcnt(0) and the barrier) is paid half as often per row.
 // grid = (blocks of 512 queries, slices), 8 waves of 64 queries each, one workgroup per CU; the feature tile is shared
 // by 8 waves instead of being staged twice per CU.  Per tile and wave the same five loads to LDS (512 threads stage
 // 64 rows), 64 MFMAs into four accumulators (row half h, column block b), a 64-bit survivor mask per lane, queue
-// entries query << 6 | row.  Thresholds, share rule and hand-over keep their cadence in rows (the kWide constants); a
-// leaving workgroup lists its two query blocks of 256.  What follows is the narrow kernel's text with those changes.
+// entries query << 6 | row.  Thresholds, share rule and hand-over keep their cadence in rows (PruneForm); a
+// leaving workgroup lists its two query blocks of 256.  The shared pieces above are the narrow kernel's too; what
+// stands here is the wide form's own: two barriers per tile and the half-tile stagger (below, with Buffers and Leaving),
+// the arming of a tile at the end of the one before (Arming), and what its register budget asks of the source.
 // LDS 157704 of 163840 bytes: ftile 2 x 64 x 512, qraw 512 x 128, xraw 2 x 64 x 128, k1s / k2s 8192, queue 2048, bail 8.
 // Registers: B 128, accumulators 64, A 12, lane offsets 5 and the rest inside the 256 that 8 waves per CU allow, none
 // spilled.  The accumulators are declared ahead of the tile loop and armed (set to minus the lane's thresholds) at the end
@@ -609,206 +777,62 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_prune_kernel(
 // in the narrow form, which is what lets a drain's 64 registers of row pieces fit.  To fit, the ragged tile's offsets and
 // the epilogue's addresses are made again from the thread index instead of being carried across the loop.
 // A tile's top is the first two A reads, the stage issue, the trailing waves' look at the flag and every second tile the
-// two threshold loads; the first MFMA accumulates in place.  tests/test_l1k2_prune_arm_isa.py holds that in the assembly.
+// two threshold loads; the first MFMA accumulates in place.  tests/test_l1k2_prune_arm_isa.py holds that in the assembly,
+// tests/test_l1k2_prune_stagger_isa.py the half-steps.
 // __launch_bounds__' second argument is waves per SIMD here: 512 threads are two per SIMD already.
-__global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
+__global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
     const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
     const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
     unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
-  // the narrow kernel's names, with this form's values
-  constexpr int H = kWideHalves, kThreads = kWideThreads, kWaves = kWideWaves, kQPerBlock = kWideQPerBlock;
-  constexpr int kTileRows = kWideTileRows, kFtileV4 = kTileRows * kLdsRowV4, kXrawV4 = kTileRows * 8, kThrEvery = kWideThrEvery;
-  constexpr int kSkipTilesAlone = kWideSkipTilesAlone, kWarmTilesShared = kWideWarmTilesShared, kWarmTilesAlone = kWideWarmTilesAlone;
-  // 512-byte alignment: the A-operand read folds its swizzle into the address with one XOR
-  __shared__ __attribute__((aligned(512))) uint4 ftile[2][kFtileV4];
-  __shared__ unsigned long long k1s[kQPerBlock], k2s[kQPerBlock];
-  __shared__ uint4 qraw[kQPerBlock * 8];            // the workgroup's query rows as they are
-  __shared__ uint4 xraw[2][kXrawV4];                // the tile's database rows as they are
-  __shared__ uint16_t queue[kWaves][kQueue];        // survivors: query of the wave << 6 | row of the tile
-  __shared__ int bail[2];                           // set in tile tl & 1: the workgroup gives the bound up
-  // 157704 bytes in all: one workgroup per CU
-
-  const int t = threadIdx.x;
-  const int w = t >> 6, lane = t & 63, c = lane & 31, g = lane >> 5;
+  using F = Wide;
+  constexpr int H = F::H;
+  const Place<F> at(threadIdx.x);
   const int s = blockIdx.y;
   const int row_begin = s * slice_rows;
   const int row_end = min(M, row_begin + slice_rows);
-  const int qbase = blockIdx.x * kQPerBlock + w * kQPerWave;  // this wave's first query
-  const int qslot = w * kQPerWave;                            // and its first top-2 slot
 
-  k1s[t] = ~0ull;
-  k2s[t] = ~0ull;
-  if (t < 2) bail[t] = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int e = t + i * kThreads;
-    qraw[e] = y[(size_t)min((int)blockIdx.x * kQPerBlock + (e >> 3), N - 1) * 8 + (e & 7)];
-  }
-
-  // ---- staging of the database tiles, from global memory straight into LDS (global_load_lds_dwordx4): no
-  // registers carry the tile and no ds_write stores it.  A wave's instruction lands its 64 x 16 B one after the
-  // other from the base in M0, so the LDS image is lane-linear and unpadded, and the swizzle that keeps the
-  // A-operand reads off each other's banks is made on the source side: the lane that lands on piece j of row r
-  // fetches piece j ^ (r & 15), and piece q of row r is read back from slot q ^ (r & 15).  EXEC must be full at
-  // these loads, so rows past the end of a ragged last tile are not predicated off but clamped to the last
-  // row: the tile then holds copies of it, which the `valid` mask keeps out of the queue.
-  // The loads are one asm statement, not __builtin_amdgcn_global_load_lds: the compiler, knowing of a load to
-  // LDS in flight, waits for vmcnt(0) before the first LDS read that may alias it (the A operand of this very
-  // tile, in the other buffer) and at every workgroup fence (each drain), and turns every counted lgkmcnt wait
-  // of the MFMA run into lgkmcnt(0).  Unknown to it, they count on vmcnt only, behind its own loads at most,
-  // which can only make one of its waits longer; nothing but the s_waitcnt vmcnt(0) ahead of the tile's
-  // barrier makes the data visible.  M0 is the compiler's: it is put back in the same statement.
-  typedef __attribute__((address_space(3))) void *lds_ptr;
-  const uint32_t lds_f = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&ftile[0][w * 64]));
-  const uint32_t lds_r = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr)(&xraw[0][w * 64]));
-  // Addresses.  The tile's first feature row and first raw row are two wave-uniform 64-bit pointers, which the
-  // scalar unit advances by one tile per iteration (at 4M rows the feature offset passes 2^31), and each load
-  // adds the lane's byte offset within the tile (global_load_lds_dwordx4 vOff, s[base:base+1]).  The five
-  // offsets are the same for every full tile and stay in five registers; only a ragged tile, the last of a
-  // slice, computes them again with the row clamp, under a wave-uniform branch around that arithmetic alone
-  // (no full tile follows a ragged one, so they are overwritten in place).
-  uint32_t voff[5];
-  auto lane_offsets = [&](int nrows, int t) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = t + i * kThreads, r = e >> 5;
-      voff[i] = (uint32_t)(min(r, nrows - 1) * kFeatV4 + ((e & 31) ^ (r & 15))) * 16u;
-    }
-    voff[4] = (uint32_t)(min(t >> 3, nrows - 1) * 8 + (t & 7)) * 16u;
-  };
-  lane_offsets(kTileRows, t);
-  auto ragged_offsets = [&](int nrows) {
-    if (__builtin_expect(nrows < kTileRows, 0)) {
-      // from the thread index alone, behind a move that the compiler cannot see through: else it keeps every row and
-      // piece number of the five loads in a register of its own across the loop, for a path that runs once a slice
-      int tt = t;
-      asm volatile("" : "+v"(tt));
-      lane_offsets(nrows, tt);
-    }
-  };
-  // The five loads of a tile come in two statements as well, for the waves that issue its features and its raw rows in
-  // different half-steps (see the loop).  stage_raw takes the offset that stage_feat's ragged_offsets left: the raw
-  // rows of a tile are issued after its features, and nothing follows a ragged tile.
-  auto stage_feat = [&](const uint4 *ftile0, int nrows, int b) {
-    ragged_offsets(nrows);
-    const uint32_t f0 = lds_f + b * (kFtileV4 * 16);
-    uint32_t m0_kept;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %5\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
-        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
-        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %9\n\t"
-        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %9\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(m0_kept)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(f0), "s"(f0 + kThreads * 16u), "s"(f0 + kThreads * 32u),
-          "s"(f0 + kThreads * 48u), "s"(ftile0)
-        : "memory");
-  };
-  auto stage_raw = [&](const uint4 *xtile0, int b) {
-    const uint32_t r0 = lds_r + b * (kXrawV4 * 16);
-    uint32_t m0_kept;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(m0_kept)
-        : "v"(voff[4]), "s"(r0), "s"(xtile0)
-        : "memory");
-  };
-  auto stage_issue = [&](const uint4 *ftile0, const uint4 *xtile0, int nrows, int b) {
-    ragged_offsets(nrows);
-    const uint32_t f0 = lds_f + b * (kFtileV4 * 16), r0 = lds_r + b * (kXrawV4 * 16);
-    uint32_t m0_kept;
-    // s_nop 2: with the two s_mov ahead of it, five states between whatever wrote a base register and its first use
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %6\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %11\n\t"
-        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %11\n\t"
-        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %11\n\t"
-        "s_mov_b32 m0, %9\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %11\n\t"
-        "s_mov_b32 m0, %10\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %12\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(m0_kept)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "s"(f0), "s"(f0 + kThreads * 16u),
-          "s"(f0 + kThreads * 32u), "s"(f0 + kThreads * 48u), "s"(r0), "s"(ftile0), "s"(xtile0)
-        : "memory");
-  };
-
-  // ---- the survivor passes (drain_lanes, drain_octets) over this wave's queue, queries and top-2 slots
-  int cnt = 0;  // wave-uniform
+  prologue<F>(at.t, y, N);
+  Stage<F> stage(at);
+  int cnt = 0;  // the length of the wave's queue, wave-uniform
   unsigned long long ph[kPhases] = {};  // wave-uniform cycle sums, all zero and dead without the stamps
+  // the survivor passes over this wave's queue, queries and top-2 slots
   auto drain = [&](int n, const uint4 *xr, uint32_t row0) {
-    drain_lanes<6>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
+    drain_lanes<F::kRowBits>(n, cnt, at.lane, lds_queue<F>, at.w, at.qslot, lds_qraw<F>, xr, lds_k1s<F>, lds_k2s<F>, row0);
   };
   auto drain_octets = [&](int n, const uint4 *xr, uint32_t row0) {
-    spv::drain_octets<6>(n, cnt, lane, queue, w, qslot, qraw, xr, k1s, k2s, row0);
+    spv::drain_octets<F::kRowBits>(n, cnt, at.lane, lds_queue<F>, at.w, at.qslot, lds_qraw<F>, xr, lds_k1s<F>, lds_k2s<F>, row0);
   };
-
-  // ---- the lane's thresholds: a pair of query 32 b + c survives iff its sum >= tq[b] = 128 m - p thr; what is
-  // kept is ntq[b] = -tq[b], the value that the tile's accumulators start from.  seen[b] is the
-  // shared threshold read last.  Only atomicMin ever writes thr[], so a later read is never above an earlier
-  // one and simply replaces it (and any value ever read there is a valid bound).  The two loads are issued
-  // a tile ahead of the refresh that uses them, behind that tile's stage loads, and have landed by the
-  // vmcnt(0) before its barrier: no tile waits for them.  Lanes past the last query read the last
-  // query's threshold, whose features they also carry.
   int ntq[2];
   uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-  auto thr_load = [&]() {
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-      seen[b] = __hip_atomic_load(&thr[min(qbase + 32 * b + c, N - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto refresh = [&](bool shared) {
-    uint32_t loc[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      loc[b] = (uint32_t)(k2s[qslot + 32 * b + c] >> 32);
-      // thr = "none yet" keeps every pair: sum >= 128 m - p 32640 always
-      ntq[b] = p * (int)min(min(loc[b], seen[b]), kMaxDist) - m128;
-    }
-    if (shared && g == 0) {
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int qi = qbase + 32 * b + c;
-        if (qi < N && loc[b] < seen[b]) atomicMin(&thr[qi], loc[b]);
-      }
-    }
-  };
+  auto thr_load = [&]() { load_thresholds(seen, thr, at, N); };
+  auto refresh = [&](bool shared) { refresh_thresholds(ntq, seen, shared, thr, at, N, p, m128); };
 
-  const int ntiles = (row_end - row_begin + kTileRows - 1) / kTileRows;
+  const int ntiles = (row_end - row_begin + F::kTileRows - 1) / F::kTileRows;
   if (ntiles > 0) {
-    stage_issue(fx + (size_t)row_begin * kFeatV4, x + (size_t)row_begin * 8, min(kTileRows, row_end - row_begin), 0);
+    stage.all(fx + (size_t)row_begin * kFeatV4, x + (size_t)row_begin * 8, min(F::kTileRows, row_end - row_begin), 0);
     __builtin_amdgcn_s_waitcnt(kWaitVm0);
   }
   __syncthreads();
   // the tile that the loop stages next
-  const uint4 *fnext = fx + ((size_t)row_begin + kTileRows) * kFeatV4, *xnext = x + ((size_t)row_begin + kTileRows) * 8;
+  const uint4 *fnext = fx + ((size_t)row_begin + F::kTileRows) * kFeatV4, *xnext = x + ((size_t)row_begin + F::kTileRows) * 8;
 
   unsigned long long n_bound = 0, n_surv = 0;  // wave-uniform statistics
   bool gave_up = false;                        // workgroup-uniform
-  int warm = kWarmTilesAlone, skip_tiles = kSkipTilesAlone;
-  int recent = 0;  // survivors of the last tiles, each tile weighing 7/8 of the one after it: 8 x the running share
+  int warm = F::kWarmTilesAlone, skip_tiles = F::kSkipTilesAlone, recent = 0;  // see judge_share
   int tl = 0;
-  // bail[] of the tile before, read right behind its barrier.  The index carries a zero that the compiler cannot
-  // see through: a value it knows to be wave-uniform is moved to a scalar register where it is loaded, which
-  // waits for it there; this one stays in its vector register until the tile's top asks for it.
-  int bailed = 0, zero_v = 0;
+  int bailed = 0, zero_v = 0;  // as in the narrow kernel
   asm volatile("" : "+v"(zero_v));
   {
-    // ---- this wave's queries as the B operand
     v4i bq[2][16];
+    // ---- this wave's queries as the B operand: 2 column blocks x 16 k-steps x 4 dwords
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      const uint4 *f = fy + (size_t)min(qbase + 32 * b + c, N - 1) * kFeatV4;
+      const uint4 *f = fy + (size_t)min(at.qbase + 32 * b + at.c, N - 1) * kFeatV4;
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + g]);
+      for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + at.g]);
     }
     thr_load();
-    // The B operand is complete before the loop is entered.  Without this wait the compiler, which cannot
-    // prove on the back edge that these loads have landed, guards every MFMA of every tile with a vmcnt
-    // wait, and the last of them wait for the prefetch of the next tile.
-    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);  // the B operand is complete before the loop is entered, as in the narrow kernel
 
     // ---- Two half-steps per tile, waves 4-7 half a tile behind waves 0-3.  A SIMD holds waves w and w + 4.  M(t) is
     // the top of tile t and its 64 MFMAs (it reads ftile[t & 1]), C(t) its compare, compaction and drains (xraw[t & 1]);
@@ -847,33 +871,28 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       }
     };
     arm(true);  // tile 0
-    // thresholds inherited from other slices: the share rule is judged sooner
-    if (__builtin_amdgcn_ballot_w64(min(seen[0], seen[1]) != 0xFFFFFFFFu) != 0ull) {
-      warm = kWarmTilesShared;
+    if (any_inherited(seen)) {
+      warm = F::kWarmTilesShared;
       skip_tiles = 0;
     }
-    const bool trail = __builtin_amdgcn_readfirstlane(w) >= kWaves / 2;  // wave-uniform
-    if (trail) __syncthreads();                                           // B_0
+    const bool trail = __builtin_amdgcn_readfirstlane(at.w) >= F::kWaves / 2;  // wave-uniform
+    if (trail) __syncthreads();                                                 // B_0
 
     unsigned long long t_last = 0;  // stamps: the end of the tile before, so that the loop's back edge is counted too
     for (; tl < ntiles; ++tl) {
       const unsigned long long t_now = stamp(), t_top = tl ? t_last : t_now;
       const unsigned long long drained = ph[kPhDrain];
-      const int row0 = row_begin + tl * kTileRows;
+      const int row0 = row_begin + tl * F::kTileRows;
       const bool has_next = tl + 1 < ntiles;
-      // this lane's A-operand slot at k-step 0 in this tile's buffer: row c, piece g ^ (c & 15)
+      // this lane's A-operand slot at k-step 0 in this tile's buffer, as in the narrow kernel, which has the bank argument
       // (in bytes, so that each read's address is one XOR of it: with a shift behind the XOR the compiler makes the
       // second read's address in the register that the read then fills, and waits ahead of both for the flag read)
-      const int a0 = ((tl & 1) * kFtileV4 + c * kLdsRowV4 + (g ^ (c & 15))) * 16;
-      // the A operand is read two k-steps ahead of its use: a read is in flight behind every MFMA pair.  Each
-      // ds_read_b128 lane group ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same of the upper half) holds 16
-      // distinct c mod 16 at one g, hence 16 distinct 16-byte slots of the 256-byte bank row: no conflict.
-      // Piece (2 ks + g) ^ (c & 15) = (g ^ (c & 15)) ^ 2 ks; the row and the buffer lie above those bits.
+      const int a0 = ((tl & 1) * F::kFtileV4 + at.c * kLdsRowV4 + (at.g ^ (at.c & 15))) * 16;
       // The first two reads are the tile's first instructions: the stage issue and the flag test run in their
       // latency (the memory clobber of the loads keeps them ahead).
       // k-step 16 h + ks is k-step ks of row half h, 32 rows further on
       auto lda = [&](int ks) {
-        return __builtin_bit_cast(v4i, *(const uint4 *)((const char *)&ftile[0][0] + ((a0 ^ (32 * (ks & 15))) + (ks >> 4) * (32 * kLdsRowV4 * 16))));
+        return __builtin_bit_cast(v4i, *(const uint4 *)((const char *)&lds_ftile<F>[0][0] + ((a0 ^ (32 * (ks & 15))) + (ks >> 4) * (32 * kLdsRowV4 * 16))));
       };
       v4i a3[3];
       a3[0] = lda(0);
@@ -881,16 +900,16 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       // every wave has read the last of tile tl - 1's features; only the trailing waves are behind the barrier after
       // which nobody reads its raw rows (the leading waves issue theirs behind the mid-tile barrier)
       if (has_next) {
-        const int nnext = min(kTileRows, row_end - row0 - kTileRows);
+        const int nnext = min(F::kTileRows, row_end - row0 - F::kTileRows);
         if (trail) {
-          stage_issue(fnext, xnext, nnext, (tl + 1) & 1);
-          xnext += kXrawV4;
+          stage.all(fnext, xnext, nnext, (tl + 1) & 1);
+          xnext += F::kXrawV4;
         } else {
-          stage_feat(fnext, nnext, (tl + 1) & 1);
+          stage.feat(fnext, nnext, (tl + 1) & 1);
         }
-        fnext += kFtileV4;
+        fnext += F::kFtileV4;
       }
-      const int nrows = min(kTileRows, row_end - row0);
+      const int nrows = min(F::kTileRows, row_end - row0);
       // The trailing waves leave after the tile whose flag was raised, before they bound a pair of this one (a leading
       // wave gets here with `bailed` zero: it looks at the flag behind the mid-tile barrier).  The loads just issued
       // and the thresholds published at the end of the tile before are harmless: every published value is a valid
@@ -900,12 +919,10 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       // for the next tile; they land behind this tile's MFMAs.  Behind the branch: on the way out of the loop no load that
       // the compiler knows of is pending, so it asks for none at the loop's end, where a leading wave has the next tile's
       // raw rows in flight.
-      if ((tl & (kThrEvery - 1)) == kThrEvery - 1) thr_load();
+      if ((tl & (F::kThrEvery - 1)) == F::kThrEvery - 1) thr_load();
 
-      // The accumulators were armed at minus the lane's threshold (arm, ahead of the loop), so that a register ends
-      // as sum - threshold and its sign bit says "ruled out" (the difference cannot overflow: make_bound).
-      // Row half h of the tile (rows 32 h .. 32 h + 31) has its own pair of accumulators; the A reads run on across
-      // the boundary between the halves.
+      // Row half h of the tile (rows 32 h .. 32 h + 31) has its own pair of accumulators, armed at the end of the tile
+      // before; the A reads run on across the boundary between the halves.
       const unsigned long long t_mfma = stamp();
 #pragma unroll
       for (int ks = 0; ks < 16 * H; ++ks) {
@@ -915,12 +932,8 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
         __builtin_amdgcn_sched_barrier(0);
       }
 
-      // One bit per accumulator register: bit 31 - n of `skip[h]` says that pair n = 16 b + v of this lane and row
-      // half is ruled out (sum < threshold: the register's sign).  Register v of a lane is row
-      // 32 h + 8 (v / 4) + 4 g + v % 4 of the tile; rows past the end of a ragged last tile are copies of the
-      // slice's last row and must never be taken for neighbours.  `live` holds half 0 in its top 32 bits.
-      // Ahead of it the mid-tile barrier (B_2tl for the leading waves, B_2tl+1 for the trailing ones), and ahead of that
-      // the wave's one wait for global memory: everything it has in flight, see "Buffers" above.
+      // The mid-tile barrier (B_2tl for the leading waves, B_2tl+1 for the trailing ones), and ahead of it the wave's one
+      // wait for global memory: everything it has in flight, see "Buffers" above.
       const unsigned long long t_wait = stamp();
       __builtin_amdgcn_s_waitcnt(kWaitVm0);
       const unsigned long long t_bar = stamp();
@@ -929,81 +942,35 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       if (!trail) {
         // the flag of tile tl - 1 (its slot is all zero at tile 0), asked for here and looked at behind the sign fold;
         // the raw rows of tile tl + 1 go where the trailing waves have just finished C(tl - 1)
-        bailed = bail[((tl + 1) & 1) + zero_v];
+        bailed = lds_bail<F>[((tl + 1) & 1) + zero_v];
         if (has_next) {
-          stage_raw(xnext, (tl + 1) & 1);
-          xnext += kXrawV4;
+          stage.raw(xnext, (tl + 1) & 1);
+          xnext += F::kXrawV4;
         }
       }
-      uint32_t skip[H] = {};
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-#pragma unroll
-          for (int v = 0; v < 16; ++v) skip[h] = __builtin_amdgcn_alignbit(skip[h], (uint32_t)acc[h][b][v], 31);
-        }
-      }
-      unsigned long long live = ~((unsigned long long)skip[0] << 32 | skip[1]);
+      Live<H> live = fold_signs<H>(acc);
       // a leading wave drops the tile whose MFMAs it ran while the flag was being raised, and leaves
       if (__builtin_amdgcn_readfirstlane(bailed)) break;
-      if (nrows < kTileRows) {
-        unsigned long long valid = 0;
-#pragma unroll
-        for (int h = 0; h < H; ++h) {
-#pragma unroll
-          for (int v = 0; v < 16; ++v)
-            if (32 * h + 8 * (v >> 2) + 4 * g + (v & 3) < nrows) valid |= 0x80008000ull << (32 * (H - 1 - h)) >> v;
-        }
-        live &= valid;
-      }
-      // compaction: every round each lane with survivors left appends its first one to the wave's queue
-      int tile_surv = 0;
-      for (;;) {
-        const bool has = live != 0;
-        const unsigned long long mask = __builtin_amdgcn_ballot_w64(has);
-        if (mask == 0ull) break;
-        const int n = __clzll(live | 1ull);  // the lane's first pair: row half n / 32, column block n / 16 % 2, register n % 16
-        const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (has) {
-          queue[w][pos] = (uint16_t)(((32 * ((n >> 4) & 1) + c) << 6) | (32 * (n >> 5) + 8 * ((n >> 2) & 3) + 4 * g + (n & 3)));
-          live &= ~(0x8000000000000000ull >> n);
-        }
-        const int add = __popcll(mask);
-        cnt += add;
-        tile_surv += add;
-        if (cnt >= 64) {
-          const unsigned long long d0 = stamp();
-          drain(64, xraw[tl & 1], (uint32_t)row0);
-          ph[kPhDrain] += stamp() - d0;
-        }
-      }
+      if (nrows < F::kTileRows) live &= valid_pairs<H>(nrows, at.g);
+      const int tile_surv = compact(live, cnt, at, tl & 1, (uint32_t)row0, ph[kPhDrain], drain);
       // the tile's raw rows are overwritten during the next tile: nothing stays queued
       if (cnt > 0) {
         const unsigned long long d0 = stamp();
         if (cnt <= octet_max)
-          drain_octets(cnt, xraw[tl & 1], (uint32_t)row0);
+          drain_octets(cnt, lds_xraw<F>[tl & 1], (uint32_t)row0);
         else
-          drain(cnt, xraw[tl & 1], (uint32_t)row0);
+          drain(cnt, lds_xraw<F>[tl & 1], (uint32_t)row0);
         ph[kPhDrain] += stamp() - d0;
       }
       n_bound += (unsigned long long)nrows * kQPerWave;
       n_surv += tile_surv;
-
-      // Above the break-even share a survivor pass costs more than the exact loop saves.  A wave that
-      // sees that raises the flag of this tile; after the barrier the whole workgroup reads the same flag
-      // (the next tile uses the other one, and a flag is never lowered), puts itself on the work list of
-      // l1k2_tile_kernel, which then computes this (query block, slice) from scratch, and leaves.
-      recent = tl <= skip_tiles ? 8 * tile_surv : recent + tile_surv - (recent >> 3);
-      const int limit = tl >= warm ? max_share : tl > skip_tiles ? max(max_share, kShareUnit * 3 / 4) : kShareUnit;
-      if (lane == 0 && recent * (kShareUnit / 8) > limit * (kTileRows * kQPerWave)) bail[tl & 1] = 1;
+      recent = judge_share<F>(recent, warm, skip_tiles, tl, tile_surv, max_share, at.lane);
       // The next tile's accumulators, from the second best that this tile's drains left and the shared thresholds that
       // landed at its mid-tile wait.  Armed behind the last tile too, where nobody reads them and nothing is published:
       // under `if (has_next)` the accumulators of the path not taken stay live across the drains, which need their
       // registers for the rows' pieces, and 50 registers spill.
       const unsigned long long t_arm = stamp();
-      arm(has_next && ((tl + 1) & (kThrEvery - 1)) == 0);  // the shared thresholds move slowly: every 128 rows is enough
+      arm(has_next && ((tl + 1) & (F::kThrEvery - 1)) == 0);  // the shared thresholds move slowly: every 128 rows is enough
       const unsigned long long t_bar2 = stamp();
       __syncthreads();  // B_2tl+1 for the leading waves, B_2tl+2 for the trailing ones
       const unsigned long long t_end = stamp();
@@ -1018,14 +985,14 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
       t_last = t_end;
       // A trailing wave asks for this tile's flag here, complete at the barrier it has just passed, and looks at it
       // behind the next tile's first LDS wait: no round trip of its own.
-      if (trail) bailed = bail[(tl & 1) + zero_v];
+      if (trail) bailed = lds_bail<F>[(tl & 1) + zero_v];
     }
     // B_2n, which the trailing waves passed as the last of their loop, and behind it the last tile's flag.  A leading
     // wave that left the loop with the flag up has passed as many barriers as the trailing waves that left at the top
     // of the same tile: it takes none here.
     if (!trail && !__builtin_amdgcn_readfirstlane(bailed)) {
       __syncthreads();
-      bailed = bail[((tl + 1) & 1) + zero_v];
+      bailed = lds_bail<F>[((tl + 1) & 1) + zero_v];
     }
     gave_up = __builtin_amdgcn_readfirstlane(bailed) != 0;  // whether it was seen inside the loop or the slice ended with it
   }
@@ -1033,65 +1000,23 @@ __global__ __launch_bounds__(kWideThreads, 2) void l1k2_prune_wide_kernel(
   if (gave_up) __builtin_amdgcn_s_waitcnt(kWaitVm0);
   // What follows the loop works from a copy of the thread index that the compiler cannot see through: made from t
   // itself, its LDS addresses and the wave's number are held in registers across the loop, which has none to spare.
-  int te = t;
+  int te = at.t;
   asm volatile("" : "+v"(te));
   const int we = te >> 6;
 #ifdef SPV_L1K2_PHASE_STAMPS
-  if (lane == 0) {
-    unsigned long long *out = stamps_out + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kWaves + w) * (kPhases + 1);
-#pragma unroll
-    for (int k = 0; k < kPhases; ++k) out[k] = ph[k];
-    // tiles this wave ran and, above them, the SIMD it ran on (HW_ID bits 5:4): the half-steps count on waves w and
-    // w + 4 sharing one
-    out[kPhases] = (unsigned long long)tl | (unsigned long long)(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3) << 32;
-  }
+  // behind the tiles this wave ran, the SIMD it ran on (HW_ID bits 5:4): the half-steps count on waves w and w + 4 sharing one
+  if (at.lane == 0)
+    store_stamps<F>(stamps_out, at.w, ph,
+                    (unsigned long long)tl | (unsigned long long)(__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3) << 32);
 #endif
   if (gave_up) {
-    // what this workgroup has found still bounds its queries' second best from above: hand it on;
-    // the exact kernel merges into the partial pair, which starts as "none"
-    const int qo = blockIdx.x * kQPerBlock + te;
-    if (qo < N) {
-      const uint32_t loc = (uint32_t)(k2s[te] >> 32);
-      if (loc < __hip_atomic_load(&thr[qo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qo], loc);
-      uint64_t *dst = part + ((size_t)qo * S + s) * 2;
-      dst[0] = ~0ull;
-      dst[1] = ~0ull;
-    }
-    // the work list is in query blocks of 256 (l1k2_tile_kernel<32, 2, 128>): two of them, unless the second has no query
-    if (te == 0) {
-      const uint32_t first = 2 * blockIdx.x, nblk = min(2u, (uint32_t)((N + 255) / 256) - first);
-      const uint32_t slot = atomicAdd(&work[0], nblk);
-      work[2 + 2 * slot] = first;
-      work[3 + 2 * slot] = blockIdx.y;
-      if (nblk > 1) {
-        work[4 + 2 * slot] = first + 1;
-        work[5 + 2 * slot] = blockIdx.y;
-      }
-    }
-    if ((te & 63) == 0) {
-      unsigned long long *st = stats + ((blockIdx.x + we) % kStatSlots) * 4;
-      atomicAdd(&st[0], n_bound);
-      atomicAdd(&st[1], n_surv);
-      atomicAdd(&st[2], (unsigned long long)(row_end - row_begin) * kQPerWave);
-    }
+    hand_over<F>(te, s, N, S, thr, work, part);
+    if ((te & 63) == 0) atomicAdd(&add_stats(stats, we, n_bound, n_surv)[2], (unsigned long long)(row_end - row_begin) * kQPerWave);
     return;
   }
   // no barrier here: k1s[te] and k2s[te] are this wave's own queries'
-
-  const int qi = blockIdx.x * kQPerBlock + te;
-  if (qi < N) {
-    const unsigned long long a1 = k1s[te], a2 = k2s[te];
-    uint64_t *dst = part + ((size_t)qi * S + s) * 2;
-    dst[0] = a1;
-    dst[1] = a2;
-    const uint32_t loc = (uint32_t)(a2 >> 32);
-    if (loc < __hip_atomic_load(&thr[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&thr[qi], loc);
-  }
-  if ((te & 63) == 0) {
-    unsigned long long *st = stats + ((blockIdx.x + we) % kStatSlots) * 4;
-    atomicAdd(&st[0], n_bound);
-    atomicAdd(&st[1], n_surv);
-  }
+  write_result<F>(te, s, N, S, thr, part);
+  if ((te & 63) == 0) add_stats(stats, we, n_bound, n_surv);
 }
 
 // -1 auto, 0 off, 1 forced: SPECTAVI_L1K2_PRUNE until l1k2_set_prune is called
@@ -1238,11 +1163,11 @@ constexpr unsigned kWideMinGroups = 1024;
 
 void l1k2_prune_plan(int xrows, int yrows, int dim, WsWalk *w, L1K2Plan *p) {
   p->off_feat_x = p->off_feat_y = p->off_thr = p->off_stats = p->off_work = w->end();
-  if (dim != 128 || xrows < kTileRows || yrows < 1) return;  // no such path, no scratch
+  if (dim != 128 || xrows < Narrow::kTileRows || yrows < 1) return;  // no such path, no scratch
   // The scratch is a function of the shape alone, whether or not the path is switched on: the features, then
   // one block of dwords: thresholds (an even number: the counters are 64-bit), the counters, the work list
   // (its length, then one (query block, slice) pair for each workgroup there can be).
-  const unsigned qgroups = (unsigned)((yrows + kQPerBlock - 1) / kQPerBlock);
+  const unsigned qgroups = (unsigned)((yrows + Narrow::kQPerBlock - 1) / Narrow::kQPerBlock);
   p->thr_words = ((size_t)yrows + 1) / 2 * 2;
   p->init_words = p->thr_words + kStatWords + 2;
   p->off_feat_x = w->reserve((size_t)xrows * 512);
@@ -1262,7 +1187,7 @@ void l1k2_prune_plan(int xrows, int yrows, int dim, WsWalk *w, L1K2Plan *p) {
     p->bound_grid = dim3(qgroups, (unsigned)p->slices);
     // The form: as set, else the wide one where `auto` took the path and its grid fills the chip.  Mode 1 stays narrow:
     // the case tables of the tests pin what l1k2_prune_kernel decides per 32-row tile and 256-query workgroup.
-    const unsigned wgroups = (unsigned)((yrows + kWideQPerBlock - 1) / kWideQPerBlock);
+    const unsigned wgroups = (unsigned)((yrows + Wide::kQPerBlock - 1) / Wide::kQPerBlock);
     const int form = l1k2_get_prune_form();
     p->form = form >= 0 ? form : mode != 1 && (unsigned long long)wgroups * p->slices >= kWideMinGroups ? kL1K2FormWide : kL1K2FormNarrow;
     p->bound_wide_grid = dim3(wgroups, (unsigned)p->slices);
@@ -1296,16 +1221,16 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   // on one build: DESIGN.md 4.1, "The wave's chain per tile", has the three numbers.
   const int octet = l1k2_knobs().prune_octet;
   const bool wide = p.form == kL1K2FormWide;
-  const int octet_max = octet < 0 ? (wide ? kOctetPairsWide : kOctetPairs) : std::min(64, octet);
+  const int octet_max = octet < 0 ? (wide ? Wide::kOctetPairs : Narrow::kOctetPairs) : std::min(64, octet);
   const dim3 grid = wide ? p.bound_wide_grid : p.bound_grid;
-  const int waves = wide ? kWideWaves : kWaves;
+  const int waves = wide ? Wide::kWaves : Narrow::kWaves;
   const size_t xw = (size_t)xrows * 32, yw = (size_t)yrows * 32;
-  auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + kThreads - 1) / kThreads, 8192)); };
-  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
+  auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + kAuxThreads - 1) / kAuxThreads, 8192)); };
+  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
                      xw, tab);
-  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(yw), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_y), fy,
+  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(yw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_y), fy,
                      yw, tab);
-  hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(p.init_words), dim3(kThreads), 0, stream, thr, p.thr_words,
+  hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(p.init_words), dim3(kAuxThreads), 0, stream, thr, p.thr_words,
                      p.init_words);
 #ifdef SPV_L1K2_PHASE_STAMPS
   const size_t nstamp = (size_t)grid.x * grid.y * waves * (kPhases + 1);

@@ -18,8 +18,12 @@ from tests import test_l1k2_prune_stagger_isa as stagger
 
 KERNEL = stagger.KERNEL
 MFMA = narrow.MFMA
-# sha256 of "\n".join(narrow._body(asm)) at the parent commit (1fd098f), the Makefile's flags: l1k2_prune_kernel is not touched
-NARROW_BODY_SHA256 = "a5d39ba742be869d310787f572a4c3405bea092a0e2ec0a671edf6a80deb9b7d"
+# sha256 of "\n".join(narrow._register_blind(narrow._body(asm))) for l1k2_prune.hip of commit 340aded, the parent of the
+# change that moved what the two kernels share into common functions, compiled with the Makefile's flags as the `asm`
+# fixture does (git show 340aded:spectavi_amd/csrc/l1k2_prune.hip into a scratch copy of csrc, hipcc CXXFLAGS
+# --cuda-device-only -S).  Register-blind: a change of the source that leaves the instruction stream alone may still
+# let the allocator swap two register numbers.  The raw text at that commit hashed to a5d39ba7...b9b7d.
+NARROW_BODY_SHA256 = "7afb1bd7784a4665677bbb9155e57bb52aa407da3ce5cdf9ccd318a5e247dd6b"
 
 asm = narrow.asm     # the module-scoped fixture: one compilation of l1k2_prune.hip for this module
 loop = stagger.loop  # the wide kernel's tile loop
@@ -69,12 +73,7 @@ def test_the_arming_stands_between_the_two_barriers(parts):
 
 
 def test_registers(asm):
-    before = narrow.KERNEL
-    narrow.KERNEL = KERNEL
-    try:
-        md = narrow._metadata(asm)
-    finally:
-        narrow.KERNEL = before
+    md = narrow._metadata(asm, KERNEL)
     assert md["vgpr_count"] <= 256, md
     assert md["vgpr_spill_count"] == 0, md
     assert md["sgpr_spill_count"] == 0, md
@@ -84,4 +83,6 @@ def test_registers(asm):
 def test_the_narrow_kernel_is_the_parent_s(asm):
     body = narrow._body(asm)
     assert re.match(r"s_|v_", body[0]), body[0]
-    assert hashlib.sha256("\n".join(body).encode()).hexdigest() == NARROW_BODY_SHA256, len(body)
+    blind = narrow._register_blind(body)
+    assert not any(re.search(r"\b[vsa]\d", l) for l in blind), "a register operand was left in"
+    assert hashlib.sha256("\n".join(blind).encode()).hexdigest() == NARROW_BODY_SHA256, len(body)

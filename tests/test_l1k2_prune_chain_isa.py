@@ -8,7 +8,7 @@ that is held here: the scalar-base form of the five loads, and fewer vector inst
 the kernel had before (counted with the same function on the assembly of that commit)."""
 import re
 
-from tests.test_l1k2_prune_isa import KERNEL, MFMA, asm  # noqa: F401  (asm is the module's fixture)
+from tests.test_l1k2_prune_isa import KERNEL, _longest_mfma_run, asm  # noqa: F401  (asm is the module's fixture)
 
 DMA = "global_load_lds_dwordx4"
 # vector instructions, MFMAs aside, between the loop head and the tile's first MFMA in the assembly of commit
@@ -28,14 +28,9 @@ def tile_top(lines):
     """(index of the loop head's label, index of the first MFMA of the tile's run of 32).  The loop head is the
     first label between the barrier ahead of the loop and the loop's five stage loads that a branch behind the
     run jumps back to (a later one is where a block that was laid out behind the loop comes back in)."""
-    idx = [i for i, l in enumerate(lines) if l.startswith(MFMA)]
-    runs = [[idx[0]]]
-    for a, b in zip(idx, idx[1:]):
-        if any(re.match(r"s_(c?branch|barrier|endpgm|setpc)", l) for l in lines[a:b]):
-            runs.append([])
-        runs[-1].append(b)
-    run = max(runs, key=len)
-    assert len(run) == 32, len(run)
+    first_mfma, last_mfma, count = _longest_mfma_run(lines)
+    assert count == 32, count
+    run = [first_mfma, last_mfma]
     labels = {l[:-1]: i for i, l in enumerate(lines) if l.endswith(":")}
     dma = [i for i, l in enumerate(lines) if l.startswith(DMA) and i < run[0]][-5:]
     back = [labels[m.group(1)] for l in lines[run[-1]:] for m in [re.match(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", l)]

@@ -40,36 +40,26 @@ def asm(tmp_path_factory):
     return out.read_text()
 
 
-def _metadata(asm):
+def _metadata(asm, kernel=KERNEL):
     """The .amdhsa metadata entry of the kernel as {key: int}."""
     entries = asm[asm.index("amdhsa.kernels:"):].split("  - .agpr_count:")
-    mine = [e for e in entries if re.search(r"\.name:\s+\S*%s" % KERNEL, e)]
-    assert len(mine) == 1, "expected one metadata entry for %s, found %d" % (KERNEL, len(mine))
+    mine = [e for e in entries if re.search(r"\.name:\s+\S*%s" % kernel, e)]
+    assert len(mine) == 1, "expected one metadata entry for %s, found %d" % (kernel, len(mine))
     return {k: int(v) for k, v in re.findall(r"^\s+\.(\w+):\s+(\d+)\s*$", mine[0], re.M)}
 
 
-def _body(asm):
+def _body(asm, kernel=KERNEL):
     """The instructions of the kernel, comments stripped."""
-    start = re.search(r"^_Z\w*%s\w*:" % KERNEL, asm, re.M)
-    assert start, "no label for %s" % KERNEL
+    start = re.search(r"^_Z\w*%s\w*:" % kernel, asm, re.M)
+    assert start, "no label for %s" % kernel
     end = asm.index(".end_amdhsa_kernel", start.end())
     lines = [l.split(";")[0].strip() for l in asm[start.end():end].splitlines()]
     return [l for l in lines if l and not l.startswith(".")]
 
 
-def test_register_and_lds_budget(asm):
-    md = _metadata(asm)
-    assert md["vgpr_count"] <= 256, md
-    assert md["vgpr_spill_count"] == 0, md
-    assert md["sgpr_spill_count"] == 0, md
-    assert md["private_segment_fixed_size"] == 0, md
-    assert md["group_segment_fixed_size"] <= 81920, md
-
-
-def test_no_vector_memory_wait_inside_a_tiles_mfmas(asm):
-    """In the longest run of MFMAs (the 32 of a tile; a run ends at a branch or a label, which _body drops, so
-    runs are told apart by the branches between them) no s_waitcnt between the first and the last names vmcnt."""
-    body = _body(asm)
+def _longest_mfma_run(body):
+    """(index of the first, index of the last, count) of the longest run of MFMAs in `body`.  A run ends at a branch,
+    a barrier or the program's end (labels are dropped by _body, so runs are told apart by the branches between them)."""
     runs, cur = [], None
     for i, l in enumerate(body):
         if l.startswith(MFMA):
@@ -82,8 +72,28 @@ def test_no_vector_memory_wait_inside_a_tiles_mfmas(asm):
             cur = None
     if cur is not None:
         runs.append(cur)
-    assert runs, "no %s in %s" % (MFMA, KERNEL)
-    first, last, count = max(runs, key=lambda r: r[2])
+    assert runs, "no %s in the kernel" % MFMA
+    return tuple(max(runs, key=lambda r: r[2]))
+
+
+def _register_blind(lines):
+    """The lines with every register operand (v12, s[4:5], a3: single registers and ranges) replaced by one placeholder."""
+    return [re.sub(r"\b[vsa](\d+|\[\d+:\d+\])", "R", l) for l in lines]
+
+
+def test_register_and_lds_budget(asm):
+    md = _metadata(asm)
+    assert md["vgpr_count"] <= 256, md
+    assert md["vgpr_spill_count"] == 0, md
+    assert md["sgpr_spill_count"] == 0, md
+    assert md["private_segment_fixed_size"] == 0, md
+    assert md["group_segment_fixed_size"] <= 81920, md
+
+
+def test_no_vector_memory_wait_inside_a_tiles_mfmas(asm):
+    """In the longest run of MFMAs (the 32 of a tile) no s_waitcnt between the first and the last names vmcnt."""
+    body = _body(asm)
+    first, last, count = _longest_mfma_run(body)
     assert count == 32, "the tile's MFMA run has %d instructions, expected 32" % count
     waits = [l for l in body[first:last + 1] if l.startswith("s_waitcnt") and "vmcnt" in l]
     assert not waits, "%d vmcnt waits inside the tile's MFMA run: %s" % (len(waits), waits)

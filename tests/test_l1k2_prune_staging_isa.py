@@ -7,22 +7,16 @@ counted lgkmcnt waits between the MFMA pairs by lgkmcnt(0).  Either would pass t
 more than the staging saves; this file keeps them from coming back unnoticed."""
 import re
 
-from tests.test_l1k2_prune_isa import MFMA, _body, asm  # noqa: F401  (asm is the module's fixture)
+from tests.test_l1k2_prune_isa import _body, _longest_mfma_run, asm  # noqa: F401  (asm is the module's fixture)
 
 DMA = "global_load_lds_dwordx4"
 
 
 def _tile_run(body):
     """(index of the first, index of the last) MFMA of the tile's run of 32."""
-    idx = [i for i, l in enumerate(body) if l.startswith(MFMA)]
-    runs = [[idx[0]]]
-    for a, b in zip(idx, idx[1:]):
-        if any(re.match(r"s_(c?branch|barrier|endpgm|setpc)", l) for l in body[a:b]):
-            runs.append([])
-        runs[-1].append(b)
-    run = max(runs, key=len)
-    assert len(run) == 32, len(run)
-    return run[0], run[-1]
+    first, last, count = _longest_mfma_run(body)
+    assert count == 32, count
+    return first, last
 
 
 def test_tiles_are_loaded_straight_into_lds(asm):

@@ -1,8 +1,6 @@
 """The register, LDS and wait budget of l1k2_prune_wide_kernel (512 threads, one workgroup per CU, 64-row tiles),
 read from the gfx950 assembly the Makefile's flags produce, with the parsing of tests/test_l1k2_prune_isa.py.
 No GPU is needed: the file is only compiled."""
-import re
-
 import pytest
 
 from tests import test_l1k2_prune_isa as narrow
@@ -16,12 +14,7 @@ asm = narrow.asm   # the module-scoped fixture: one compilation of l1k2_prune.hi
 @pytest.fixture(scope="module")
 def wide(asm):
     """(metadata, body) of the wide kernel, through the narrow test's parsers."""
-    before = narrow.KERNEL
-    narrow.KERNEL = KERNEL
-    try:
-        return narrow._metadata(asm), narrow._body(asm)
-    finally:
-        narrow.KERNEL = before
+    return narrow._metadata(asm, KERNEL), narrow._body(asm, KERNEL)
 
 
 def test_the_narrow_kernel_is_still_told_apart(asm):
@@ -43,20 +36,7 @@ def test_register_and_lds_budget(wide):
 def test_no_vector_memory_wait_inside_a_tiles_mfmas(wide):
     """The longest run of MFMAs is the 64 of a tile, and no s_waitcnt between its first and its last names vmcnt."""
     _, body = wide
-    runs, cur = [], None
-    for i, l in enumerate(body):
-        if l.startswith(MFMA):
-            if cur is None:
-                cur = [i, i, 0]
-            cur[1] = i
-            cur[2] += 1
-        elif cur is not None and re.match(r"s_(c?branch|barrier|endpgm|setpc)", l):
-            runs.append(cur)
-            cur = None
-    if cur is not None:
-        runs.append(cur)
-    assert runs, "no %s in %s" % (MFMA, KERNEL)
-    first, last, count = max(runs, key=lambda r: r[2])
+    first, last, count = narrow._longest_mfma_run(body)
     assert count == 64, "the tile's MFMA run has %d instructions, expected 64" % count
     waits = [l for l in body[first:last + 1] if l.startswith("s_waitcnt") and "vmcnt" in l]
     assert not waits, "%d vmcnt waits inside the tile's MFMA run: %s" % (len(waits), waits)
