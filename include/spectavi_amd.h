@@ -156,7 +156,8 @@ const char *spv_version(void);
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
  * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
  * "ann_merge", "ann_rerank", "cascade_project",
- * "cascade_buckets", "cascade_probe_refine", "dlt", "rectify") are bracketed by hipEvents recorded on the
+ * "cascade_buckets", "cascade_probe_refine", "dlt", "rectify", "ransac_batch_score", "ransac_batch_reduce",
+ * "gather_match_coords_batch") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
  * last reset. */
@@ -523,6 +524,61 @@ int spv_ransac_fit_device(const double *d_x0, const double *d_x1, int npt, doubl
                           int32_t *inlier_idx, int32_t *n_inliers, int32_t *best_try, int32_t *best_root,
                           int32_t *tries_run, void *stream);
 
+/* spv_ransac_fit_samples for every set of a collection of correspondence sets, in one call (ransac_batch.hip):
+ * what a multi-view front-end runs after the matches of its image pairs have become coordinates.
+ *   x0, x1   double[total, 3]: the homogeneous correspondences of npairs sets back to back (the device form:
+ *            on the caller's current device).
+ *   pair_off host long long[npairs + 1], pair_off[0] = 0, non-decreasing, pair_off[npairs] = total < 2^31; set p
+ *            is rows [pair_off[p], pair_off[p + 1]).  npairs <= 2^20.
+ *   required_percent_inliers ... singular_value_ratio_allowed: as in spv_ransac_fit, one value for all sets.
+ *   samples  host int32[npairs, maximum_tries, 7], row numbers inside the set; or, if NULL,
+ *   seeds    host unsigned long long[npairs]: set p evaluates the subsets spv_ransac_sample(seeds[p], rows of p,
+ *            maximum_tries) returns (an entry 0: the environment seed, else std::random_device).
+ * Host outputs, one row per set: success int32[npairs], essential double[npairs, 9], camera double[npairs, 12]
+ * (both rows untouched where no model was kept), inlier_percent double[npairs], n_inliers int32[npairs], and --
+ * NULL to skip -- best_try, best_root, tries_run int32[npairs].  inlier_idx host int32[total]: set p's list is
+ * inlier_idx[pair_off[p] .. pair_off[p] + n_inliers[p]), row numbers inside the set, ascending.  d_inlier_mask
+ * (device form, may be NULL) uint8[total]: 1 = inlier of its set's kept model, 0 elsewhere, every byte written.
+ *
+ * A set with fewer than 10 rows is skipped, not an error: success 0, inlier_percent 0, n_inliers 0, best_try =
+ * best_root = -1, tries_run 0; its samples are not read.  npairs = 0 and maximum_tries = 0 are valid.
+ * SPV_ERR_INVALID, nothing launched and no output touched: a NULL required pointer, a pair_off that does not
+ * follow the rules above, maximum_tries < 0 or > 7e8, a sample row outside its set.
+ *
+ * For every set, success, essential, camera, inlier_percent, n_inliers, the inlier list, best_try and best_root
+ * are bit for bit what spv_ransac_fit_samples returns for that set alone with the same subsets, whatever else the
+ * collection holds and however the call cuts the work.  tries_run -- the number of leading tries of the set that
+ * were evaluated -- depends on the cuts: best_try < tries_run <= maximum_tries for a set that succeeds,
+ * maximum_tries for one that runs and does not.
+ *
+ * The call works in rounds: every set that is still running contributes its next block of tries, and `stream`
+ * is synchronised once per round, however many sets there are.  Scratch comes from the library's cache
+ * (spv_release_cached_memory).  One device: the host form runs on the first selected device and touches none if
+ * no set has 10 rows or maximum_tries is 0.  Kernel names for spv_profile_read: "ransac_batch_score" (the
+ * segmented scorer and its second pass), "ransac_batch_reduce"; "seven_point" and "ransac_cameras" as elsewhere.
+ *
+ * spv_ransac_fit_batch_plan: host only, touches no device.  The first round of such a call on a device of
+ * compute_units compute units: out = {sets in the round, tries in the round, work items, row blocks of 256};
+ * items may be NULL, otherwise int32[items_cap, 5] receives the first min(work items, items_cap) work items, one
+ * workgroup each, as (set, first row in x0 / x1, rows <= 256, first candidate of the round, candidates; a try
+ * has 3 candidates).  An item never straddles two sets; a set's candidates are cut over several items while the
+ * round has fewer than 4 row blocks per compute unit. */
+int spv_ransac_fit_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
+                         double required_percent_inliers, double reprojection_error_allowed, int maximum_tries,
+                         int find_best_even_in_failure, double singular_value_ratio_allowed, const int32_t *samples,
+                         const unsigned long long *seeds, int32_t *success, double *essential, double *camera,
+                         double *inlier_percent, int32_t *inlier_idx, int32_t *n_inliers, int32_t *best_try,
+                         int32_t *best_root, int32_t *tries_run);
+int spv_ransac_fit_batch_device(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs,
+                                double required_percent_inliers, double reprojection_error_allowed, int maximum_tries,
+                                int find_best_even_in_failure, double singular_value_ratio_allowed,
+                                const int32_t *samples, const unsigned long long *seeds, int32_t *success,
+                                double *essential, double *camera, double *inlier_percent, int32_t *inlier_idx,
+                                int32_t *n_inliers, int32_t *best_try, int32_t *best_root, int32_t *tries_run,
+                                uint8_t *d_inlier_mask, void *stream);
+int spv_ransac_fit_batch_plan(const long long *pair_off, int npairs, int maximum_tries, int compute_units,
+                              long long out[4], int32_t *items, long long items_cap);
+
 /* The output shape of image_pair_rectification: out = {output_rows, output_cols, rnx}.  Host only;
  * SPV_ERR_INVALID (out untouched) for the arguments image_pair_rectification rejects. */
 int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]);
@@ -751,6 +807,23 @@ int spv_sift_split_device(const float *d_table, int rows, float *d_geom, uint8_t
 int spv_gather_match_coords_device(const float *d_geom_x, const float *d_geom_y,
                                    const int32_t *d_matches, const int32_t *d_count, int capacity,
                                    double *d_x0, double *d_x1, void *stream);
+
+/* The same for the matches of a spv_l1k2_batch_device + spv_ratio_test_device run, as per-pair coordinates.
+ *   d_geom   float32[total_rows, 4]: the geometry of all sets back to back, row for row the desc of the matching call
+ *   seg_off, nseg, pairs, npairs: host arrays, the very arguments of the matching call (same rules, SPV_ERR_INVALID
+ *            with nothing launched outside them)
+ *   d_matches int32[capacity, 2], d_count: as spv_ratio_test_device wrote them over the concatenated output: a
+ *            match is (out row, row within the database set), in ascending out-row order
+ *   d_x0, d_x1 double[capacity, 3]: rows [0, *d_count) are written, x0 = (x, y, 1) of row seg_off[db] + k of d_geom,
+ *            x1 = (x, y, 1) of row seg_off[q] + (out row - first out row of the pair), for the pair (q, db) that owns
+ *            the out row
+ *   d_pair_off device long long[npairs + 1]: where pair p's matches begin; d_pair_off[npairs] = *d_count.  Read
+ *            back, it is the pair_off of spv_ransac_fit_batch_device.
+ * Asynchronous on `stream` but for the upload of its small per-pair table, which stays with the calling thread
+ * until its next call.  Kernel name for spv_profile_read: "gather_match_coords_batch". */
+int spv_gather_match_coords_batch_device(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
+                                         int npairs, const int32_t *d_matches, const int32_t *d_count, int capacity,
+                                         double *d_x0, double *d_x1, long long *d_pair_off, void *stream);
 
 /* normalize_to_ubyte_and_multiple_16_dim (reference spectavi/feature.py:384-407) for a float32
  * input, bit for bit what numpy computes: per-column de-mean (numpy's row-ordered float32 sum),

@@ -97,6 +97,9 @@ PROTOTYPES = {
     "spv_ransac_fit": (i, [f64a, f64a, i, d, d, i, i, d, ull] + _fit_out),
     "spv_ransac_fit_samples": (i, [f64a, f64a, i, d, d, i32a, i, i, d] + _fit_out),
     "spv_ransac_fit_device": (i, [vp, vp, i, d, d, i, i, d, ull, vp] + _fit_out + [vp]),
+    "spv_ransac_fit_batch": (i, [vp, vp, vp, i, d, d, i, i, d] + [vp] * 11),
+    "spv_ransac_fit_batch_device": (i, [vp, vp, vp, i, d, d, i, i, d] + [vp] * 13),
+    "spv_ransac_fit_batch_plan": (i, [vp, i, i, i, pll, vp, ll]),
     "spv_rectify_shape": (i, [i, i, i, d, i32a]),
     "spv_rectify_fundamental": (i, [f64a, f64a, f64a]),
     "spv_dlt_triangulate": (i, _dlt),
@@ -134,6 +137,7 @@ PROTOTYPES = {
     "spv_sift_split": (i, [f32a, i, f32a, u8a]),
     "spv_sift_split_device": (i, [vp, i, vp, vp, vp]),
     "spv_gather_match_coords_device": (i, [vp] * 4 + [i] + [vp] * 3),
+    "spv_gather_match_coords_batch_device": (i, [vp, vp, i, vp, i, vp, vp, i, vp, vp, vp, vp]),
     "spv_normalize": (i, [f32a, i, i, vp, vp]),
     "spv_normalize_workspace_bytes": (sz, [i]),
     "spv_normalize_workspace_bytes_rows": (sz, [i, i]),

@@ -55,6 +55,67 @@ __global__ __launch_bounds__(kThreads) void gather_match_coords_kernel(
   x1[3 * (size_t)i + 2] = 1.0;
 }
 
+
+// The same for the matches of an l1k2_batch + ratio-test run: a match is (out row, row within the database
+// set), in ascending out-row order.  tab = out_off long long[npairs + 1] | first geometry row of the query set
+// long long[npairs] | ... of the database set long long[npairs].  Thread i < *count writes match i (its pair is
+// the last one whose out rows begin at or before the match's: empty pairs own no out row); thread p <= npairs
+// also writes pair_off[p], the first match whose out row is not below out_off[p].
+__global__ __launch_bounds__(kThreads) void gather_match_coords_batch_kernel(
+    const float *__restrict__ geom, const long long *__restrict__ tab, int npairs, const int *__restrict__ matches,
+    const int *__restrict__ count, int capacity, double *__restrict__ x0, double *__restrict__ x1,
+    long long *__restrict__ pair_off) {
+  const int n = npairs > 0 ? min(*count, capacity) : 0;  // without pairs there is no out row and no match
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i <= npairs) {
+    const long long want = tab[i];
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = lo + (hi - lo) / 2;
+      if ((long long)matches[2 * (size_t)mid] < want) lo = mid + 1; else hi = mid;
+    }
+    pair_off[i] = lo;
+  }
+  if (i >= n) return;
+  const int o = matches[2 * (size_t)i], k = matches[2 * (size_t)i + 1];
+  int lo = 0, hi = npairs;  // the first pair whose out rows begin beyond o
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (tab[mid] <= (long long)o) lo = mid + 1; else hi = mid;
+  }
+  const int p = lo - 1;  // >= 0: out_off[0] = 0 <= o
+  const long long q = tab[(size_t)npairs + 1 + p] + ((long long)o - tab[p]);
+  const long long d = tab[(size_t)2 * npairs + 1 + p] + k;
+  x0[3 * (size_t)i + 0] = (double)geom[4 * (size_t)d + 0];
+  x0[3 * (size_t)i + 1] = (double)geom[4 * (size_t)d + 1];
+  x0[3 * (size_t)i + 2] = 1.0;
+  x1[3 * (size_t)i + 0] = (double)geom[4 * (size_t)q + 0];
+  x1[3 * (size_t)i + 1] = (double)geom[4 * (size_t)q + 1];
+  x1[3 * (size_t)i + 2] = 1.0;
+}
+
+// The per-pair table of the batch gather lives with the calling thread between calls (the call has no workspace
+// argument and does not wait for its kernel): a grow-only device buffer and the event of the kernel that read it
+// last, which the next call of the thread waits for before it overwrites the table.
+struct GatherTable {
+  void *p = nullptr;
+  size_t cap = 0;
+  int dev = -1;
+  hipEvent_t ev = nullptr;
+  void drop() {
+    if (ev) {
+      (void)hipEventSynchronize(ev);
+      (void)hipEventDestroy(ev);
+      ev = nullptr;
+    }
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  ~GatherTable() { drop(); }
+};
+thread_local GatherTable g_gather_table;
+
 }  // namespace
 
 int sift_split_run(const float *d_table, int rows, float *d_geom, uint8_t *d_desc, hipStream_t stream) {
@@ -81,6 +142,54 @@ int gather_match_coords_run(const float *d_geom_x, const float *d_geom_y, const 
   hipLaunchKernelGGL(gather_match_coords_kernel, dim3(blocks), dim3(kThreads), 0, stream, d_geom_x,
                      d_geom_y, d_matches, d_count, d_x0, d_x1);
   SPV_HIP_CHECK(hipGetLastError());
+  return SPV_OK;
+}
+
+int gather_match_coords_batch_run(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
+                                  int npairs, const int *d_matches, const int *d_count, int capacity, double *d_x0,
+                                  double *d_x1, long long *d_pair_off, hipStream_t stream) {
+  // seg_off and pairs: the rules of l1k2_batch_plan
+  if (nseg < 0 || npairs < 0) return set_error(SPV_ERR_INVALID, "negative count (nseg=%d, npairs=%d)", nseg, npairs);
+  if (capacity < 0) return set_error(SPV_ERR_INVALID, "negative capacity");
+  if (!seg_off || (npairs > 0 && !pairs)) return set_error(SPV_ERR_INVALID, "null pointer");
+  if (seg_off[0] != 0) return set_error(SPV_ERR_INVALID, "seg_off[0] = %lld, must be 0", seg_off[0]);
+  for (int s = 0; s < nseg; ++s)
+    if (seg_off[s + 1] < seg_off[s]) return set_error(SPV_ERR_INVALID, "seg_off decreases at set %d", s);
+  if (seg_off[nseg] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld rows in all, must be below 2^31", seg_off[nseg]);
+  for (int i = 0; i < 2 * npairs; ++i)
+    if (pairs[i] < 0 || pairs[i] >= nseg) return set_error(SPV_ERR_INVALID, "pair %d names set %d of %d", i / 2, (int)pairs[i], nseg);
+  std::vector<long long> tab((size_t)3 * npairs + 1, 0);
+  for (int p = 0; p < npairs; ++p) {
+    const int q = pairs[2 * p], d = pairs[2 * p + 1];
+    tab[(size_t)p + 1] = tab[p] + (seg_off[q + 1] - seg_off[q]);
+    tab[(size_t)npairs + 1 + p] = seg_off[q];
+    tab[(size_t)2 * npairs + 1 + p] = seg_off[d];
+  }
+  if (tab[npairs] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld out rows, must be below 2^31", tab[npairs]);
+  if (!d_pair_off || !d_count || (capacity > 0 && (!d_geom || !d_matches || !d_x0 || !d_x1)))
+    return set_error(SPV_ERR_INVALID, "null device pointer");
+  GatherTable &t = g_gather_table;
+  const size_t bytes = tab.size() * sizeof(long long);
+  int dev = 0;
+  SPV_HIP_CHECK(hipGetDevice(&dev));
+  if (t.ev) SPV_HIP_CHECK(hipEventSynchronize(t.ev));  // the kernel that read the table last
+  if (t.dev != dev || t.cap < bytes) {
+    t.drop();
+    SPV_HIP_CHECK(hipMalloc(&t.p, bytes));
+    t.cap = bytes;
+    t.dev = dev;
+  }
+  if (!t.ev) SPV_HIP_CHECK(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+  // (pageable source: the copy has left `tab` when the call returns)
+  SPV_HIP_CHECK(hipMemcpyAsync(t.p, tab.data(), bytes, hipMemcpyHostToDevice, stream));
+  const long long threads = std::max<long long>(capacity, (long long)npairs + 1);
+  {
+    ProfScope prof("gather_match_coords_batch", stream);
+    hipLaunchKernelGGL(gather_match_coords_batch_kernel, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads),
+                       0, stream, d_geom, (const long long *)t.p, npairs, d_matches, d_count, capacity, d_x0, d_x1, d_pair_off);
+    SPV_HIP_CHECK(hipGetLastError());
+  }
+  SPV_HIP_CHECK(hipEventRecord(t.ev, stream));
   return SPV_OK;
 }
 

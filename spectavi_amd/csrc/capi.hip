@@ -269,6 +269,37 @@ int host_l1k2_batch(const uint8_t *desc, const long long *seg_off, int nseg, int
   return download(dev, idx, di.p, ib, st);
 }
 
+// The many-sets RANSAC through host pointers, on the first selected device: both arrays up, one
+// ransac_fit_batch_run.  A collection in which no set runs touches no device.
+int host_ransac_fit_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
+                          double required_percent, double max_error, int max_tries, int find_best, double ratio_allowed,
+                          const int32_t *samples, const unsigned long long *seeds, int32_t *success, double *essential,
+                          double *camera, double *inlier_percent, int32_t *inlier_idx, int32_t *n_inliers,
+                          int32_t *best_try, int32_t *best_root, int32_t *tries_run) {
+  SPV_TRY(ransac_batch_check(pair_off, npairs, max_tries, samples));
+  const long long total = pair_off[npairs];
+  if (total > 0 && (!x0 || !x1)) return set_error(SPV_ERR_INVALID, "null pointer");
+  std::vector<RansacBatchSlot> first;
+  ransac_batch_first_round(pair_off, npairs, max_tries, &first);
+  DevBuf dx, dxp;
+  hipStream_t st = hipStreamPerThread;
+  if (!first.empty()) {
+    if (!samples && !seeds) return set_error(SPV_ERR_INVALID, "neither samples nor seeds");
+    if (!success || !essential || !camera || !inlier_percent || !n_inliers || !inlier_idx)
+      return set_error(SPV_ERR_INVALID, "null pointer");
+    SPV_TRY(host_begin(device_list()[0], &st));
+    const size_t ib = (size_t)total * 3 * sizeof(double);
+    SPV_TRY(alloc_all({{&dx, ib}, {&dxp, ib}}));
+    SPV_TRY(dx.copy_in(x0, ib, st));
+    SPV_TRY(dxp.copy_in(x1, ib, st));
+    x0 = dx.as<double>();
+    x1 = dxp.as<double>();
+  }
+  return ransac_fit_batch_run(x0, x1, pair_off, npairs, required_percent, max_error, max_tries, find_best, ratio_allowed,
+                              samples, seeds, success, essential, camera, inlier_percent, inlier_idx, n_inliers, best_try,
+                              best_root, tries_run, nullptr, st);
+}
+
 // Exact p-norm k-NN through host pointers, on the first selected device (no sharding).
 int host_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                     uint64_t *idx, void *dist) {
@@ -601,6 +632,9 @@ int host_seven_point(const double *x, const double *xp, int n, int32_t *nroot, d
   return SPV_OK;
 }
 
+}  // namespace
+
+// (floyd_sample, ransac_seed and check_fit_args also serve ransac_batch.hip: common.h)
 // One 7-subset of [0, N) the way the reference draws it (floyd_sample, src/RansacFitter.h:120-132):
 // for r = N-7 .. N-1 a value v uniform on [1, r] is taken unless already present, else r.  (Row 0 is
 // therefore never drawn: the reference's range starts at 1.)  The reference seeds a fresh mt19937 from
@@ -630,6 +664,8 @@ int check_fit_args(const double *x0, const double *x1, int npt, int max_tries) {
   if (max_tries > 700000000) return set_error(SPV_ERR_INVALID, "maximum_tries above 7e8 (candidate ids are 32-bit: 3 per try)");
   return SPV_OK;
 }
+
+namespace {
 
 // samples != NULL: the 7-subsets of the tries, int32[max_tries,7]; otherwise drawn from `seed`.
 // inputs_on_device: x0 / x1 are device pointers (the caller's current device) and `st` the caller's stream.
@@ -1176,6 +1212,14 @@ int spv_gather_match_coords_device(const float *d_geom_x, const float *d_geom_y,
   return api([&] { return gather_match_coords_run(d_geom_x, d_geom_y, d_matches, d_count, capacity, d_x0, d_x1,
                                                   static_cast<hipStream_t>(stream)); });
 }
+int spv_gather_match_coords_batch_device(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
+                                         int npairs, const int32_t *d_matches, const int32_t *d_count, int capacity,
+                                         double *d_x0, double *d_x1, long long *d_pair_off, void *stream) {
+  return api([&] {
+    return gather_match_coords_batch_run(d_geom, seg_off, nseg, pairs, npairs, d_matches, d_count, capacity, d_x0, d_x1,
+                                         d_pair_off, static_cast<hipStream_t>(stream));
+  });
+}
 int spv_ratio_test(const uint64_t *idx, const void *dist, int dist_is_float, int yrows,
                    double min_ratio, int32_t *matches, int32_t *count) {
   return host_api([&] { return host_ratio(idx, dist, dist_is_float, yrows, min_ratio, matches, count); });
@@ -1337,6 +1381,56 @@ int spv_dlt_score_hypotheses_device_ws(const double *P0, const double *d_P1s, in
                                        void *stream) {
   return api([&] { return dlt_score_run(P0, d_P1s, nhyp, npt, d_x, d_xp, max_error, d_counts, d_mask, d_ws,
                                         ws_bytes, static_cast<hipStream_t>(stream)); });
+}
+int spv_ransac_fit_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
+                         double required_percent_inliers, double reprojection_error_allowed, int maximum_tries,
+                         int find_best_even_in_failure, double singular_value_ratio_allowed, const int32_t *samples,
+                         const unsigned long long *seeds, int32_t *success, double *essential, double *camera,
+                         double *inlier_percent, int32_t *inlier_idx, int32_t *n_inliers, int32_t *best_try,
+                         int32_t *best_root, int32_t *tries_run) {
+  return host_api([&] {
+    return host_ransac_fit_batch(x0, x1, pair_off, npairs, required_percent_inliers, reprojection_error_allowed,
+                                 maximum_tries, find_best_even_in_failure, singular_value_ratio_allowed, samples, seeds,
+                                 success, essential, camera, inlier_percent, inlier_idx, n_inliers, best_try, best_root,
+                                 tries_run);
+  });
+}
+int spv_ransac_fit_batch_device(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs,
+                                double required_percent_inliers, double reprojection_error_allowed, int maximum_tries,
+                                int find_best_even_in_failure, double singular_value_ratio_allowed,
+                                const int32_t *samples, const unsigned long long *seeds, int32_t *success,
+                                double *essential, double *camera, double *inlier_percent, int32_t *inlier_idx,
+                                int32_t *n_inliers, int32_t *best_try, int32_t *best_root, int32_t *tries_run,
+                                uint8_t *d_inlier_mask, void *stream) {
+  return api([&] {
+    return ransac_fit_batch_run(d_x0, d_x1, pair_off, npairs, required_percent_inliers, reprojection_error_allowed,
+                                maximum_tries, find_best_even_in_failure, singular_value_ratio_allowed, samples, seeds,
+                                success, essential, camera, inlier_percent, inlier_idx, n_inliers, best_try, best_root,
+                                tries_run, d_inlier_mask, static_cast<hipStream_t>(stream));
+  });
+}
+int spv_ransac_fit_batch_plan(const long long *pair_off, int npairs, int maximum_tries, int compute_units,
+                              long long out[4], int32_t *items, long long items_cap) {
+  return api([&] {
+    SPV_TRY(ransac_batch_check(pair_off, npairs, maximum_tries, nullptr));
+    if (compute_units < 1 || !out || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
+    std::vector<RansacBatchSlot> slots;
+    std::vector<RansacBatchItem> its;
+    ransac_batch_first_round(pair_off, npairs, maximum_tries, &slots);
+    ransac_batch_items(slots, pair_off, compute_units, &its);
+    long long tries = 0, blocks = 0;
+    for (const RansacBatchSlot &s : slots) {
+      tries += s.ncand / 3;
+      blocks += (s.npt + 255) / 256;
+    }
+    out[0] = (long long)slots.size();
+    out[1] = tries;
+    out[2] = (long long)its.size();
+    out[3] = blocks;
+    static_assert(sizeof(RansacBatchItem) == 5 * sizeof(int32_t), "items are int32[5]");
+    if (items) memcpy(items, its.data(), (size_t)std::min<long long>(items_cap, (long long)its.size()) * sizeof(RansacBatchItem));
+    return (int)SPV_OK;
+  });
 }
 int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]) {
   return api([&] {

@@ -10,6 +10,7 @@
 #include <functional>
 #include <mutex>
 #include <new>
+#include <random>
 #include <type_traits>
 #include <vector>
 
@@ -355,6 +356,10 @@ int ransac_process_run(const double *d_Fs, int nF, long long npt, const double *
                        hipStream_t stream, int score_rows_cap = 65535);  // grid rows of the scorer: a RANSAC batch, whose
                                                                           // candidates are nearly all gated, passes 2048
 
+// ... its first stage alone (gate, E, four cameras), any nF: d_cams double[nF,4,12], NaN for a gated candidate
+int ransac_cameras_run(const double *d_Fs, int nF, double ratio_allowed, double *d_cams, int *d_gated, int *d_live,
+                       int *d_nlive, hipStream_t stream);
+
 // ---- seven-point solver and the RANSAC loop around the candidate processing (ransac.hip) ----
 // d_x, d_xp double[n,7,2] euclidean; d_Fs double[n,3,9] (NaN in the slots of missing roots);
 // d_nroot int[n] and d_basis double[n,2,9] may be NULL
@@ -367,5 +372,50 @@ int ransac_fit_run(const double *d_x0, const double *d_x1, long long npt, double
                    const std::function<void(int, int, int *)> &next_samples, int *success, double *essential,
                    double *camera, int *n_inliers, unsigned char *inlier_mask, int *best_try, int *best_root,
                    int *tries_run, void *d_ws, size_t ws_bytes, int batch, hipStream_t stream);
+
+int seven_point_sampled_run(const double *d_x0, const double *d_x1, const int *d_samples, int n, double *d_Fs,
+                            hipStream_t stream);  // subsets as rows of d_x0 / d_x1 double[.,3]; d_Fs double[n,3,9]
+// The best model of a fit so far, device resident; the four ints are what the host reads after a batch.
+struct FitState {
+  int found;    // a model has been kept
+  int success;  // ... and it is above required_percent_inliers: stop
+  int count;    // its inliers
+  int cand;     // 3 * try + root
+  double F[9];
+  double P[12];
+};
+void floyd_sample(std::mt19937 &gen, int N, int *out);  // one 7-subset of [1, N), as the reference draws it
+uint32_t ransac_seed(uint64_t seed);                    // the generator's seed for a caller's seed (0: environment, else random)
+int check_fit_args(const double *x0, const double *x1, int npt, int max_tries);
+
+// ---- two-view RANSAC of many correspondence sets in one call (ransac_batch.hip) ----------
+// One workgroup's share of a round: rows [row0, row0 + rows) of the concatenated correspondences, all of one set,
+// against the candidates [cand0, cand0 + ncand) of the round, all of that set.
+struct RansacBatchItem {
+  int32_t set, row0, rows, cand0, ncand;
+};
+// One set's part of a round.
+struct RansacBatchSlot {
+  int32_t set, npt, cand0, ncand, cand_base;  // cand_base: 3 x the tries of the set that earlier rounds evaluated
+};
+// The work items of a round, a function of the slots and the compute units alone; host only.
+void ransac_batch_items(const std::vector<RansacBatchSlot> &slots, const long long *pair_off, int cus,
+                        std::vector<RansacBatchItem> *items);
+// The slots of the first round of a call (host only): every set of >= 10 rows, in order, while the round has room.
+void ransac_batch_first_round(const long long *pair_off, int npairs, int max_tries, std::vector<RansacBatchSlot> *slots);
+// SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
+int ransac_batch_check(const long long *pair_off, int npairs, int max_tries, const int32_t *samples);
+// Host results as in include/spectavi_amd.h; d_x0 / d_x1 on the current device.  Synchronises `stream` once a round.
+int ransac_fit_batch_run(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs,
+                         double required_percent, double max_error, int max_tries, int find_best, double ratio_allowed,
+                         const int32_t *samples, const unsigned long long *seeds, int32_t *success, double *essential,
+                         double *camera, double *inlier_percent, int32_t *inlier_idx, int32_t *n_inliers,
+                         int32_t *best_try, int32_t *best_root, int32_t *tries_run, unsigned char *d_inlier_mask,
+                         hipStream_t stream);
+
+// ---- the matches of an l1k2_batch + ratio-test run as per-pair coordinates (adapter.hip) ----
+int gather_match_coords_batch_run(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
+                                  int npairs, const int *d_matches, const int *d_count, int capacity, double *d_x0,
+                                  double *d_x1, long long *d_pair_off, hipStream_t stream);
 
 }  // namespace spv

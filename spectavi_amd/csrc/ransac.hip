@@ -286,15 +286,6 @@ __global__ __launch_bounds__(kFitThreads) void seven_point_kernel(const double *
 // above required (or find_best_even_in_failure) and above the best so far; the first one above
 // required ends the search.  One workgroup; state persists between batches.
 // ---------------------------------------------------------------------------------
-struct FitState {
-  int found;    // a model has been kept
-  int success;  // ... and it is above required_percent_inliers: stop
-  int count;    // its inliers
-  int cand;     // 3 * try + root
-  double F[9];
-  double P[12];
-};
-
 constexpr int kReduceThreads = 256;
 
 __global__ __launch_bounds__(kReduceThreads) void ransac_reduce_kernel(
@@ -350,6 +341,19 @@ int seven_point_run(const double *d_x, const double *d_xp, int n, double *d_Fs, 
   ProfScope prof("seven_point", stream);
   hipLaunchKernelGGL(seven_point_kernel<false>, dim3((n + kFitThreads - 1) / kFitThreads), dim3(kFitThreads), 0, stream,
                      d_x, d_xp, (const int *)nullptr, n, d_Fs, d_nroot, d_basis);
+  SPV_HIP_CHECK(hipGetLastError());
+  return SPV_OK;
+}
+
+// seven_point_kernel<true> on its own: d_samples int[n,7] rows of d_x0 / d_x1 double[.,3] (not checked here),
+// d_Fs double[n,3,9].
+int seven_point_sampled_run(const double *d_x0, const double *d_x1, const int *d_samples, int n, double *d_Fs,
+                            hipStream_t stream) {
+  if (n <= 0) return n < 0 ? set_error(SPV_ERR_INVALID, "negative count") : (int)SPV_OK;
+  if (!d_x0 || !d_x1 || !d_samples || !d_Fs) return set_error(SPV_ERR_INVALID, "null device pointer");
+  ProfScope prof("seven_point", stream);
+  hipLaunchKernelGGL(seven_point_kernel<true>, dim3((n + kFitThreads - 1) / kFitThreads), dim3(kFitThreads), 0, stream,
+                     d_x0, d_x1, d_samples, n, d_Fs, (int *)nullptr, (double *)nullptr);
   SPV_HIP_CHECK(hipGetLastError());
   return SPV_OK;
 }

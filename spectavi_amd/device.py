@@ -614,6 +614,131 @@ def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.
             'inlier_idx': idx[:n.value].copy(), 'best_try': bt.value, 'best_root': br.value, 'tries_run': ran.value}
 
 
+def _fit_batch_args(pair_off, total, maximum_tries, seeds, samples):
+    """pair_off -> int64[npairs + 1], samples -> int32[npairs, T, 7] or None, seeds -> uint64[npairs] or None,
+    maximum_tries; ValueError for anything spv_ransac_fit_batch_device would reject or that does not describe
+    arrays of `total` rows.  Touches no device."""
+    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("pair_off must start at 0 and never decrease")
+    if int(off[-1]) != int(total):
+        raise ValueError("pair_off ends at %d, the arrays have %d rows" % (int(off[-1]), int(total)))
+    if int(off[-1]) >= 2 ** 31:
+        raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    npairs = off.size - 1
+    if npairs > 2 ** 20:
+        raise ValueError("more than 2^20 sets per call")
+    npt = np.diff(off)
+    if samples is not None:
+        samples = np.asarray(samples)
+        if samples.dtype.kind not in "iu" and samples.size:
+            raise ValueError("samples must be integers")
+        if samples.ndim != 3 or samples.shape[0] != npairs or samples.shape[2] != 7:
+            raise ValueError("samples must be [npairs, ntries, 7]")
+        samples = np.ascontiguousarray(samples, dtype=np.int32)
+        maximum_tries = samples.shape[1]
+        runs = npt >= 10
+        if samples[runs].size and (int(samples[runs].min()) < 0 or
+                                   np.any(samples[runs].reshape(int(runs.sum()), -1).max(axis=1) >= npt[runs])):
+            raise ValueError("a sample row lies outside its set")
+    else:
+        seeds = np.zeros(npairs, np.uint64) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        if seeds.size != npairs:
+            raise ValueError("seeds must hold one value per set")
+    maximum_tries = int(maximum_tries)
+    if maximum_tries < 0 or maximum_tries > 700000000:
+        raise ValueError("maximum_tries must be in [0, 7e8]")
+    return off, samples, seeds, maximum_tries
+
+
+def _fit_batch_dicts(off, ok, F, P, pct, idx, n, bt, br, ran):
+    out = []
+    for p in range(off.size - 1):
+        found = bt[p] >= 0
+        out.append({'success': bool(ok[p]), 'essential': F[p].reshape(3, 3).copy() if found else None,
+                    'camera': P[p].reshape(3, 4).copy() if found else None, 'inlier_percent': float(pct[p]),
+                    'inlier_idx': idx[off[p]:off[p] + n[p]].copy(), 'best_try': int(bt[p]), 'best_root': int(br[p]),
+                    'tries_run': int(ran[p])})
+    return out
+
+
+def ransac_fit_batch_plan(pair_off, maximum_tries=500, compute_units=256, want_items=False):
+    """The first round of ransac_fit_batch() for a collection (spv_ransac_fit_batch_plan; host only, no device
+    touched): dict of sets and tries in the round, items (work items = workgroups of the scorer) and row_blocks
+    (blocks of 256 rows).  With want_items also the items, int32[items, 5] = (set, first row, rows, first
+    candidate of the round, candidates)."""
+    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("pair_off must start at 0 and never decrease")
+    out = (ct.c_longlong * 4)()
+    check(clib.spv_ransac_fit_batch_plan(off.ctypes.data, off.size - 1, int(maximum_tries), int(compute_units), out,
+                                         None, 0))
+    plan = dict(sets=int(out[0]), tries=int(out[1]), items=int(out[2]), row_blocks=int(out[3]))
+    if want_items:
+        items = np.empty((plan["items"], 5), np.int32)
+        check(clib.spv_ransac_fit_batch_plan(off.ctypes.data, off.size - 1, int(maximum_tries), int(compute_units), out,
+                                             items.ctypes.data, len(items)))
+        return plan, items
+    return plan
+
+
+def ransac_fit_batch(x0, x1, pair_off, required_percent_inliers=.9, reprojection_error_allowed=.5, maximum_tries=500,
+                     find_best_even_in_failure=True, singular_value_ratio_allowed=3e-2, seeds=None, samples=None,
+                     want_mask=False):
+    """`ransac_fit` for every set of a collection in one call (spv_ransac_fit_batch_device): x0, x1 CUDA float64
+    [total,3] hold the sets back to back, set p = rows pair_off[p]:pair_off[p + 1] (e.g. the output of
+    `match_coordinates_batch`).  samples int32 [npairs, ntries, 7] (row numbers inside the set; `maximum_tries` and
+    `seeds` are then ignored) or seeds [npairs] (0 = SPECTAVI_RANSAC_SEED / random) choose the subsets.  Returns a
+    list of `ransac_fit` dicts, each bit for bit the single call's but for tries_run; a set of fewer than 10 rows
+    is skipped (success False, no model, tries_run 0).  With want_mask also a CUDA uint8 [total] tensor: 1 = inlier
+    of its set's kept model.  Synchronises the current stream once per round of tries, however many sets."""
+    if not (x0.shape == x1.shape and x0.dim() == 2 and x0.shape[1] == 3):
+        raise ValueError("x0, x1 must be [total,3]")
+    total = x0.shape[0]
+    off, samples, seeds, maximum_tries = _fit_batch_args(pair_off, total, maximum_tries, seeds, samples)
+    _need(x0, torch.float64, "x0")
+    _need(x1, torch.float64, "x1")
+    npairs = off.size - 1
+    ok, n, bt, br, ran = (np.zeros(npairs, np.int32) for _ in range(5))
+    pct, F, P, idx = np.zeros(npairs), np.zeros((npairs, 9)), np.zeros((npairs, 12)), np.zeros(total, np.int32)
+    mask = torch.empty(total, dtype=torch.uint8, device=x0.device) if want_mask else None
+    with _on_device_of(x0, x1) as stream:
+        check(clib.spv_ransac_fit_batch_device(
+            x0.data_ptr(), x1.data_ptr(), off.ctypes.data, npairs, float(required_percent_inliers),
+            float(reprojection_error_allowed), maximum_tries, int(bool(find_best_even_in_failure)),
+            float(singular_value_ratio_allowed), samples.ctypes.data if samples is not None else None,
+            seeds.ctypes.data if samples is None else None, ok.ctypes.data, F.ctypes.data, P.ctypes.data,
+            pct.ctypes.data, idx.ctypes.data, n.ctypes.data, bt.ctypes.data, br.ctypes.data, ran.ctypes.data,
+            mask.data_ptr() if want_mask else None, stream))
+    fits = _fit_batch_dicts(off, ok, F, P, pct, idx, n, bt, br, ran)
+    return (fits, mask) if want_mask else fits
+
+
+def match_coordinates_batch(geom, seg_off, pairs, matches, count):
+    """`match_coordinates` for the matches of an `l1k2_batch` + `ratio_test` run: geom CUDA float32 [total_rows,4]
+    holds the geometry of all sets back to back (row for row the desc of the matching call), seg_off and pairs are
+    that call's.  Returns (x0 [cap,3], x1 [cap,3], pair_off int64 ndarray [npairs + 1]): rows
+    pair_off[p]:pair_off[p + 1] are pair p's matches, x0 from the database set, x1 from the query set -- the
+    arguments of `ransac_fit_batch`.  Reading pair_off back synchronises the current stream."""
+    if geom.dim() != 2 or geom.shape[1] != 4 or matches.dim() != 2 or matches.shape[1] != 2:
+        raise ValueError("geom must be [total_rows,4], matches [capacity,2]")
+    seg, prs, out_off = _batch_args(seg_off, pairs, geom.shape[0], 16)
+    if int(out_off[-1]) >= 2 ** 31:
+        raise ValueError("the pairs must own fewer than 2^31 out rows in all")
+    _need(geom, torch.float32, "geom")
+    _need(matches, torch.int32, "matches")
+    _need(count, torch.int32, "count")
+    cap = matches.shape[0]
+    x0 = torch.zeros((cap, 3), dtype=torch.float64, device=matches.device)
+    x1 = torch.zeros((cap, 3), dtype=torch.float64, device=matches.device)
+    pair_off = torch.zeros(len(prs) + 1, dtype=torch.int64, device=matches.device)
+    with _on_device_of(geom, matches, count) as stream:
+        check(clib.spv_gather_match_coords_batch_device(geom.data_ptr(), seg.ctypes.data, seg.size - 1, prs.ctypes.data,
+                                                        len(prs), matches.data_ptr(), count.data_ptr(), cap,
+                                                        x0.data_ptr(), x1.data_ptr(), pair_off.data_ptr(), stream))
+    return x0, x1, pair_off.cpu().numpy()
+
+
 def normalize(x, want_float=True, want_ubyte=False, workspace=None):
     """`normalize_to_ubyte_and_multiple_16_dim` (reference spectavi/feature.py:384-407) on a CUDA float32
     [rows, dim] table, bit-identical to the numpy function: returns the float32 [rows, dim16] table

@@ -303,6 +303,74 @@ def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.
             'tries_run': ran.value}
 
 
+_spv_ransac_fit_batch = clib.spv_ransac_fit_batch
+
+
+def ransac_fit_batch(x0s, x1s, required_percent_inliers=.9, reprojection_error_allowed=.5, maximum_tries=500,
+                     find_best_even_in_failure=True, singular_value_ratio_allowed=3e-2, seeds=None, samples=None):
+    """
+    `ransac_fit` for many correspondence sets in one call: x0s, x1s are lists of float64 [npt_p,3] arrays
+    (npt_p may be anything; a set of fewer than 10 rows is skipped: success False, no model, tries_run 0).
+    `samples`: a list of int32 [ntries,7] arrays, one per set, all of one ntries (`maximum_tries` and `seeds`
+    are then ignored), or `seeds`: one value per set (0 = SPECTAVI_RANSAC_SEED / random).
+
+    Returns a list of `ransac_fit` dicts, each bit for bit what `ransac_fit` returns for that set alone with
+    the same subsets, but for tries_run (the rounds of the call cut the tries differently).
+    """
+    if len(x0s) != len(x1s):
+        raise ValueError('x0s and x1s must hold one array per set each.')
+    a0 = [np.ascontiguousarray(x, dtype=np.float64) for x in x0s]
+    a1 = [np.ascontiguousarray(x, dtype=np.float64) for x in x1s]
+    for u, v in zip(a0, a1):
+        if not (u.ndim == 2 and u.shape == v.shape and u.shape[1] == 3):
+            raise TypeError('Coords must be homogenous [npt,3] pairs.')
+    npairs = len(a0)
+    off = np.concatenate([[0], np.cumsum([len(u) for u in a0])]).astype(np.int64)
+    total = int(off[-1])
+    if total >= 2 ** 31:
+        raise ValueError('the sets must hold fewer than 2^31 rows in all')
+    if npairs > 2 ** 20:
+        raise ValueError('more than 2^20 sets per call')
+    x0 = np.concatenate(a0) if total else np.zeros((0, 3))
+    x1 = np.concatenate(a1) if total else np.zeros((0, 3))
+    if samples is not None:
+        if len(samples) != npairs:
+            raise ValueError('samples must hold one [ntries,7] array per set.')
+        rows = [np.asarray(s) for s in samples]
+        ntries = rows[0].shape[0] if npairs else 0
+        for p, s in enumerate(rows):
+            if not (s.ndim == 2 and s.shape == (ntries, 7)):
+                raise ValueError('samples must be [ntries,7] arrays of one ntries.')
+            if len(a0[p]) >= 10 and s.size and (s.min() < 0 or s.max() >= len(a0[p])):
+                raise ValueError('a sample row lies outside its set')
+        samples = np.ascontiguousarray(np.stack(rows) if npairs else np.zeros((0, 0, 7)), dtype=np.int32)
+        maximum_tries = ntries
+    else:
+        seeds = np.zeros(npairs, np.uint64) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        if seeds.size != npairs:
+            raise ValueError('seeds must hold one value per set')
+    maximum_tries = int(maximum_tries)
+    if maximum_tries < 0 or maximum_tries > 700000000:
+        raise ValueError('maximum_tries must be in [0, 7e8]')
+    ok, n, bt, br, ran = (np.zeros(npairs, np.int32) for _ in range(5))
+    pct, F, P, idx = np.zeros(npairs), np.zeros((npairs, 9)), np.zeros((npairs, 12)), np.zeros(total, np.int32)
+    check(_spv_ransac_fit_batch(x0.ctypes.data, x1.ctypes.data, off.ctypes.data, npairs, float(required_percent_inliers),
+                                float(reprojection_error_allowed), maximum_tries, int(bool(find_best_even_in_failure)),
+                                float(singular_value_ratio_allowed),
+                                samples.ctypes.data if samples is not None else None,
+                                seeds.ctypes.data if samples is None else None, ok.ctypes.data, F.ctypes.data,
+                                P.ctypes.data, pct.ctypes.data, idx.ctypes.data, n.ctypes.data, bt.ctypes.data,
+                                br.ctypes.data, ran.ctypes.data))
+    out = []
+    for p in range(npairs):
+        found = bt[p] >= 0
+        out.append({'success': bool(ok[p]), 'essential': F[p].reshape(3, 3).copy() if found else None,
+                    'camera': P[p].reshape(3, 4).copy() if found else None, 'inlier_percent': float(pct[p]),
+                    'inlier_idx': idx[off[p]:off[p] + n[p]].copy(), 'best_try': int(bt[p]), 'best_root': int(br[p]),
+                    'tries_run': int(ran[p])})
+    return out
+
+
 # ==================================================================================
 # image_pair_rectification (reference spectavi/mvg.py:47-106)
 # ==================================================================================
