@@ -375,7 +375,8 @@ void fill_round(std::vector<SetRun> &run, int max_tries, std::vector<RansacBatch
     const SetRun &r = run[i];
     if (tries >= kRoundTries || (tries > 0 && solves >= kRoundSolves)) break;
     const long long per_try = 12ll * r.npt;
-    const long long by_work = tries == 0 ? INT_MAX : std::max<long long>((kRoundSolves - solves) / per_try, 1);
+    const long long by_work = tries == 0 ? INT_MAX : (kRoundSolves - solves) / per_try;  // the first set always runs
+    if (by_work < 1) break;  // not one more try of this set fits: it waits, and so do the sets behind it
     const int n = (int)std::min<long long>({(long long)r.step, (long long)(max_tries - r.done), (long long)(kRoundTries - tries), by_work});
     if (n <= 0) continue;
     slots->push_back(RansacBatchSlot{r.set, r.npt, 3 * tries, 3 * n, 3 * r.done});

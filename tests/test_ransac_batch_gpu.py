@@ -254,6 +254,76 @@ def test_gather_equals_the_per_pair_loop(matched, ratio, npairs):
     assert not x0[n:].any().item() and not x1[n:].any().item()
 
 
+def _gather_raw(geom, seg, pairs, m, c, cap, x0, x1, pair_off, stream):
+    """spv_gather_match_coords_batch_device into the caller's tensors on `stream`, without waiting for it."""
+    from spectavi_amd._lib import clib, check
+    seg = np.ascontiguousarray(seg, np.int64)
+    prs = np.ascontiguousarray(pairs, np.int32)
+    check(clib.spv_gather_match_coords_batch_device(geom.data_ptr(), seg.ctypes.data, len(seg) - 1, prs.ctypes.data, len(prs),
+                                                    m.data_ptr(), c.data_ptr(), cap, x0.data_ptr(), x1.data_ptr(),
+                                                    pair_off.data_ptr(), ct.c_void_p(stream.cuda_stream)))
+
+
+def test_gather_with_a_capacity_below_the_count(matched):
+    """matches[:cap] with cap inside a pair's matches, and cap = 0: the first cap matches are gathered, the pair is
+    cut short, later pairs are empty and no row at or beyond cap is written."""
+    import torch
+    from spectavi_amd import device as spv
+    desc, geom, seg, pairs = matched
+    idx, dist, _ = spv.l1k2_batch(desc, seg, pairs)
+    m, c = spv.ratio_test(idx, dist, 1.5)
+    loop = _per_pair_loop(desc, geom, seg, pairs, 1.5)
+    want_off = np.concatenate([[0], np.cumsum([len(a) for a, _ in loop])])
+    want0, want1 = np.concatenate([a for a, _ in loop]), np.concatenate([b for _, b in loop])
+    n = int(c.item())
+    assert n == want_off[-1] and want_off[4] - want_off[3] > 20
+    for cap in (int(want_off[3]) + 7, 0):
+        x0, x1, pair_off = spv.match_coordinates_batch(geom, seg, pairs, m[:cap], c)
+        assert pair_off[-1] == cap and np.array_equal(pair_off, np.minimum(want_off, cap))
+        assert x0.shape == (cap, 3) and x0.cpu().numpy().tobytes() == want0[:cap].tobytes()
+        assert x1.cpu().numpy().tobytes() == want1[:cap].tobytes()
+        # the same with room behind the capacity: rows from cap on stay as they were
+        big0, big1 = (torch.zeros((n, 3), dtype=torch.float64, device="cuda") for _ in range(2))
+        off = torch.full((len(pairs) + 1,), -1, dtype=torch.int64, device="cuda")
+        _gather_raw(geom, seg, pairs, m[:cap], c, cap, big0, big1, off, torch.cuda.current_stream())
+        torch.cuda.synchronize()
+        assert np.array_equal(off.cpu().numpy(), np.minimum(want_off, cap))
+        assert big0[:cap].cpu().numpy().tobytes() == want0[:cap].tobytes()
+        assert big1[:cap].cpu().numpy().tobytes() == want1[:cap].tobytes()
+        assert not big0[cap:].any().item() and not big1[cap:].any().item()
+
+
+def test_gather_table_regrows_between_calls_on_two_streams(matched):
+    """2 pairs, 8 pairs, 2 pairs, alternating between the current stream and a second one with no wait in between:
+    the calling thread's pair table grows for the second call, and each call waits for the kernel that read the
+    table last before it overwrites it.  Then 24 pairs and 2 again: more pairs than any other test of this
+    process has gathered, so the table grows here wherever in the suite this runs.  Each result is its per-pair
+    loop's."""
+    import torch
+    from spectavi_amd import device as spv
+    desc, geom, seg, pairs = matched
+    calls = []
+    for prs in (pairs[:2], pairs, pairs[3:5], np.tile(pairs, (3, 1)), pairs[5:7]):
+        idx, dist, _ = spv.l1k2_batch(desc, seg, prs)
+        m, c = spv.ratio_test(idx, dist, 1.5)
+        cap = m.shape[0]
+        outs = (torch.zeros((cap, 3), dtype=torch.float64, device="cuda"), torch.zeros((cap, 3), dtype=torch.float64, device="cuda"),
+                torch.full((len(prs) + 1,), -1, dtype=torch.int64, device="cuda"))
+        calls.append((prs, m, c, cap, outs, _per_pair_loop(desc, geom, seg, prs, 1.5)))
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()  # inputs and zeroed outputs are there for both streams
+    for k, (prs, m, c, cap, outs, _) in enumerate(calls):
+        _gather_raw(geom, seg, prs, m, c, cap, *outs, side if k % 2 else torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    for prs, m, c, cap, (x0, x1, pair_off), loop in calls:
+        want_off = np.concatenate([[0], np.cumsum([len(a) for a, _ in loop])])
+        n = int(want_off[-1])
+        assert n > 0 and n == int(c.item()) and np.array_equal(pair_off.cpu().numpy(), want_off), len(prs)
+        assert x0[:n].cpu().numpy().tobytes() == np.concatenate([a for a, _ in loop]).tobytes(), len(prs)
+        assert x1[:n].cpu().numpy().tobytes() == np.concatenate([b for _, b in loop]).tobytes(), len(prs)
+        assert not x0[n:].any().item() and not x1[n:].any().item()
+
+
 def test_matches_to_fits_end_to_end(matched):
     """l1k2_batch -> ratio_test -> match_coordinates_batch -> ransac_fit_batch against the per-pair loop."""
     from spectavi_amd import device as spv
