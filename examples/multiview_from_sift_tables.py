@@ -1,0 +1,134 @@
+"""Steps 2-4 of the reference's example pipeline for every image pair of a view set, one call per step.
+
+examples/essential_from_sift_tables.py runs matching, RANSAC and triangulation for ONE image pair, as the reference's
+example/ex01_essential_estimation.py does.  A multi-view front-end has N views and up to N (N - 1) / 2 pairs; this file
+runs all of them through the many-pairs forms of the same steps, with every intermediate resident in HBM:
+
+    l1k2_batch               exact L1 2-NN of every (query view, database view) pair
+    ratio_test               over the concatenated result
+    match_coordinates_batch  matches -> per-pair homogeneous coordinates and pair_off
+    ransac_fit_batch         one essential matrix and camera per pair, and the inlier mask over all rows
+    dlt_triangulate_batch    every pair's inliers triangulated with that pair's camera; pairs without a model skipped
+
+Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
+they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic:
+extracting them is not part of this library.
+
+    python examples/multiview_from_sift_tables.py [--images 6] [--points 2000]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_fraction=0.08, desc_noise=6.0):
+    """SIFT tables of one scene seen by n_views calibrated cameras (the first at [I|0]).  Every scene point appears
+    in every table, its descriptor perturbed by N(0, desc_noise) per component and view; in every view but the first
+    a `wrong_fraction` of them sits at an unrelated position (a descriptor match that is a geometric outlier), and
+    n_extra unrelated keypoints are added to each table.  Rows are shuffled per view.  Returns (tables, K)."""
+    rng = np.random.default_rng(seed)
+    n_extra = n_points // 2 if n_extra is None else n_extra
+    K = np.array([[1000.0, 0.0, 640.0], [0.0, 1000.0, 480.0], [0.0, 0.0, 1.0]])
+    X = np.c_[rng.uniform(-2.5, 2.5, n_points), rng.uniform(-1.8, 1.8, n_points), rng.uniform(4, 8, n_points)]
+
+    def descriptors(n):  # SIFT-like: non-negative, unit norm, stored as uint8(512 d) (src/Sift.h:118-121)
+        d = np.abs(rng.standard_normal((n, 128))) ** 2
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        return np.minimum(np.floor(512.0 * d), 255.0)
+
+    d_scene = descriptors(n_points)
+    tables = []
+    for v in range(n_views):
+        R, t = np.eye(3), np.zeros(3)
+        if v:
+            a = rng.standard_normal(3)
+            a /= np.linalg.norm(a)
+            th = rng.uniform(0.05, 0.25) * rng.choice([-1, 1])
+            S = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+            R = np.eye(3) + np.sin(th) * S + (1 - np.cos(th)) * (S @ S)
+            t = rng.standard_normal(3)
+            t /= np.linalg.norm(t)
+        Xc = X @ R.T + t
+        pix = ((Xc / Xc[:, 2:]) @ K.T)[:, :2]
+        if v:
+            wrong = rng.choice(n_points, int(round(wrong_fraction * n_points)), replace=False)
+            pix[wrong] = np.c_[rng.uniform(0, 1280, len(wrong)), rng.uniform(0, 960, len(wrong))]
+        desc = np.clip(np.round(d_scene + desc_noise * rng.standard_normal(d_scene.shape)), 0, 255)
+        pix = np.vstack([pix, np.c_[rng.uniform(0, 1280, n_extra), rng.uniform(0, 960, n_extra)]])
+        desc = np.vstack([desc, descriptors(n_extra)])
+        n = len(pix)
+        table = np.hstack([pix, rng.uniform(1, 8, (n, 1)), rng.uniform(-np.pi, np.pi, (n, 1)), desc]).astype(np.float32)
+        tables.append(table[rng.permutation(n)])
+    return tables, K
+
+
+def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, maximum_tries=2000, seed=1):
+    """SIFT tables (a list of float32 [n_v,132] arrays) -> one upload -> split -> exact L1 2-NN of all pairs -> ratio
+    test -> per-pair coordinates -> calibration -> one RANSAC fit per pair -> triangulation of every pair's inliers
+    with that pair's camera.  Returns a dict: pairs int32 [npairs,2] (query view, database view), pair_off (matches
+    per pair), fits (the `ransac_fit` dicts), out_off (points per pair), X (CUDA float64 [total,4], rows
+    out_off[p]:out_off[p + 1] are pair p's unit-norm homogeneous points) and rows (CUDA int32: the match each point
+    belongs to, numbered inside its pair)."""
+    import torch
+    from spectavi_amd import device as spv
+    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    table = torch.from_numpy(np.concatenate(tables)).cuda()
+    geom, desc = spv.split_sift_table(table)
+    nv = len(tables)
+    pairs = np.array([(q, d) for d in range(nv) for q in range(d + 1, nv)], np.int32).reshape(-1, 2)
+    idx, dist, _ = spv.l1k2_batch(desc, seg, pairs)
+    matches, count = spv.ratio_test(idx, dist, min_ratio)
+    p0, p1, pair_off = spv.match_coordinates_batch(geom, seg, pairs, matches, count)
+    n = int(pair_off[-1])
+    iKt = torch.from_numpy(np.linalg.inv(K).T.copy()).to(table.device)
+    x0 = (p0[:n] @ iKt).contiguous()
+    x1 = (p1[:n] @ iKt).contiguous()
+    fits, mask = spv.ransac_fit_batch(x0, x1, pair_off, required_percent_inliers=required_percent_inliers,
+                                      reprojection_error_allowed=3.35e-4, maximum_tries=maximum_tries,
+                                      find_best_even_in_failure=False, singular_value_ratio_allowed=1e-3,
+                                      seeds=np.arange(seed, seed + len(pairs), dtype=np.uint64), want_mask=True)
+    use = [f['best_try'] >= 0 for f in fits]            # a pair without a model owns no points
+    cameras = [f['camera'] for f in fits]               # None where there is none
+    X, rows, out_off = spv.dlt_triangulate_batch(x0, x1, pair_off, cameras, use=use, mask=mask, want_rows=True)
+    return {'pairs': pairs, 'pair_off': pair_off, 'fits': fits, 'out_off': out_off, 'X': X, 'rows': rows}
+
+
+def report(out):
+    fitted = 0
+    for p, (q, d) in enumerate(out['pairs'].tolist()):
+        f = out['fits'][p]
+        fitted += f['best_try'] >= 0
+        print("pair %d-%d: matches %d model %s inliers %d points %d" % (
+            d, q, out['pair_off'][p + 1] - out['pair_off'][p], "yes" if f['best_try'] >= 0 else "no",
+            len(f['inlier_idx']), out['out_off'][p + 1] - out['out_off'][p]))
+    print("pairs %d fitted %d inliers %d points %d" % (len(out['pairs']), fitted, sum(len(f['inlier_idx']) for f in out['fits']),
+                                                       out['out_off'][-1]))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--images", type=int, default=6, help="views of the scene")
+    ap.add_argument("--points", type=int, default=2000, help="scene points seen in every view")
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    import torch
+    tables, K = synthetic_sift_views(a.seed, a.images, a.points)
+    for rep in range(2):  # the second round is the warm one
+        torch.cuda.synchronize()
+        s = time.perf_counter()
+        out = multiview_pipeline(tables, K)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - s
+    report(out)
+    n = int(out['out_off'][-1])
+    E = out['X'][:n, :3] / out['X'][:n, 3:]
+    print("%d views, %.1f ms (warm); depth of the points: median %.2f" % (a.images, dt * 1e3, float(E[:, 2].median()) if n else 0.0))
+
+
+if __name__ == "__main__":
+    main()

@@ -156,7 +156,8 @@ const char *spv_version(void);
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
  * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
  * "ann_merge", "ann_rerank", "cascade_project",
- * "cascade_buckets", "cascade_probe_refine", "dlt", "rectify", "ransac_batch_score", "ransac_batch_reduce",
+ * "cascade_buckets", "cascade_probe_refine", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "ransac_batch_score",
+ * "ransac_batch_reduce",
  * "gather_match_coords_batch") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
@@ -579,6 +580,56 @@ int spv_ransac_fit_batch_device(const double *d_x0, const double *d_x1, const lo
 int spv_ransac_fit_batch_plan(const long long *pair_off, int npairs, int maximum_tries, int compute_units,
                               long long out[4], int32_t *items, long long items_cap);
 
+/* dlt_triangulate and dlt_reprojection_error for every set of a collection of correspondence sets, in one call
+ * (dlt_batch.hip), each set with its own camera pair: the step after spv_ransac_fit_batch -- the reference's
+ * RX = dlt_triangulate(P0, ransac['camera'], x0[idx], x1[idx]) for every image pair at once, with the fits' cameras
+ * as P1s and the fit's d_inlier_mask as the selection.  spv_dlt_triangulate_batch_device is in section 3.
+ *   x0, x1   double[total, 3]: the homogeneous correspondences of npairs sets back to back (the device form:
+ *            on the caller's current device).
+ *   pair_off host long long[npairs + 1]: the rules of spv_ransac_fit_batch.
+ *   P1s      host double[npairs, 12]: the second camera of every set.
+ *   P0s      host double[npairs, 12]: the first camera of every set; NULL: [I | 0] for every set, the frame the
+ *            cameras of spv_ransac_fit_batch are expressed in.
+ *   use      host int32[npairs], or NULL for all sets: a set with use[p] = 0 is skipped -- its cameras are not read
+ *            and it owns no out rows --, which is what a fit that kept no model becomes.
+ *   mask     uint8[total] (the device form: device memory), or NULL for all rows: a row is selected iff its byte
+ *            is non-zero and its set is used.
+ * The selected rows are written back to back, in ascending input-row order: out rows [0, min(count, capacity)) of
+ * X double[capacity, 4] (dlt_triangulate's unit-norm points), err double[capacity] (dlt_reprojection_error's values)
+ * and rows int32[capacity] (the row number inside its set, the numbering of spv_ransac_fit_batch's inlier_idx).
+ * Each of the three may be NULL, but not both X and err; nothing at or beyond min(count, capacity) is touched.
+ * out_off long long[npairs + 1] (may be NULL): the selected rows before every set, out_off[npairs] = *count (may be
+ * NULL) = the number of selected rows, also where it exceeds capacity -- the host form then returns
+ * SPV_ERR_OVERFLOW with the rows that fit written; the device form cannot know and returns SPV_OK.
+ *
+ * For every selected row, X is bit for bit what spv_dlt_triangulate_device writes for that row with its set's
+ * cameras and err what spv_dlt_reprojection_error_device writes, whatever else the collection holds and however the
+ * call cuts the work; rows with inf, NaN or w = 0 included.
+ *
+ * SPV_ERR_INVALID, nothing launched and no output touched: a NULL required pointer, a pair_off outside the rules,
+ * negative capacity.  npairs = 0, empty sets and a collection without a used set are valid: the host form then
+ * touches no device (the device form only sets d_out_off and d_count to zero).
+ *
+ * The device form is asynchronous on `stream` but for the upload of its small tables (the cameras and the work
+ * items); with a mask the out rows' places are counted on the device, without one the host computes them and
+ * nothing but the one kernel runs.  Scratch comes from the library's cache (spv_release_cached_memory) and goes
+ * back to it once the call's last kernel has ended.  One device: the host form runs on the first selected device.
+ * Kernel names for spv_profile_read: "dlt_batch" (the solve), "dlt_batch_scan" (count and scan, with a mask).
+ * Very large single sets remain the job of spv_dlt_triangulate_device, whose lanes stream their rows ahead of the
+ * solve.
+ *
+ * spv_dlt_triangulate_batch_plan: host only, touches no device.  out = {used sets, work items, rows of the used
+ * sets (the most a mask can select)}; items may be NULL, otherwise int32[items_cap, 4] receives the first
+ * min(work items, items_cap) work items, one workgroup's step each, in launch order, as (set, first row in x0 / x1,
+ * rows <= 256, out row of the first row where the call has no mask -- with a mask the device counts, and the call's
+ * own table holds -1).  An item never straddles two sets and a set that is not used owns none.  compute_units >= 1
+ * caps the grid (32 workgroups per unit, each walking items b, b + grid, ...) and does not change the items. */
+int spv_dlt_triangulate_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
+                              const double *P0s, const double *P1s, const int32_t *use, const uint8_t *mask, double *X,
+                              double *err, int32_t *rows, long long capacity, long long *out_off, long long *count);
+int spv_dlt_triangulate_batch_plan(const long long *pair_off, int npairs, const int32_t *use, int compute_units,
+                                   long long out[3], int32_t *items, long long items_cap);
+
 /* The output shape of image_pair_rectification: out = {output_rows, output_cols, rnx}.  Host only;
  * SPV_ERR_INVALID (out untouched) for the arguments image_pair_rectification rejects. */
 int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]);
@@ -777,6 +828,13 @@ int spv_dlt_triangulate_device(const double *P0, const double *P1, long long npt
 int spv_dlt_reprojection_error_device(const double *P0, const double *P1, long long npt,
                                       const double *d_x, const double *d_xp, double *d_dst,
                                       void *stream);
+/* Device form of spv_dlt_triangulate_batch (section 2, where the contract is): d_x0, d_x1, d_mask, d_X, d_err,
+ * d_rows, d_out_off long long[npairs + 1] and d_count long long[1] are device memory; pair_off, P0s, P1s and use
+ * are HOST pointers.  d_count holds the true count also above capacity. */
+int spv_dlt_triangulate_batch_device(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs,
+                                     const double *P0s, const double *P1s, const int32_t *use, const uint8_t *d_mask,
+                                     double *d_X, double *d_err, int32_t *d_rows, long long capacity,
+                                     long long *d_out_off, long long *d_count, void *stream);
 
 /* Ratio test + ordered match compaction, the step right after the NN path in the
  * reference's pipeline (example/ex01_essential_estimation.py:102-106): query q passes iff

@@ -46,7 +46,7 @@ def _preload_torch_hip_runtime():
 _preload_torch_hip_runtime()
 clib = ct.cdll.LoadLibrary(lib_path)
 
-SPV_OK, SPV_ERR_INVALID, SPV_ERR_HIP, SPV_ERR_NOMEM, SPV_ERR_INTERNAL = 0, 1, 2, 3, 4
+SPV_OK, SPV_ERR_INVALID, SPV_ERR_HIP, SPV_ERR_NOMEM, SPV_ERR_INTERNAL, SPV_ERR_OVERFLOW = 0, 1, 2, 3, 4, 5
 
 # every prototype of the C-ABI, once (spectavi_amd/_proto.py); nothing else declares one
 for _name, (_restype, _argtypes) in PROTOTYPES.items():

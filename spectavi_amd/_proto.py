@@ -100,6 +100,8 @@ PROTOTYPES = {
     "spv_ransac_fit_batch": (i, [vp, vp, vp, i, d, d, i, i, d] + [vp] * 11),
     "spv_ransac_fit_batch_device": (i, [vp, vp, vp, i, d, d, i, i, d] + [vp] * 13),
     "spv_ransac_fit_batch_plan": (i, [vp, i, i, i, pll, vp, ll]),
+    "spv_dlt_triangulate_batch": (i, [vp, vp, vp, i] + [vp] * 7 + [ll, vp, vp]),
+    "spv_dlt_triangulate_batch_plan": (i, [vp, i, vp, i, pll, vp, ll]),
     "spv_rectify_shape": (i, [i, i, i, d, i32a]),
     "spv_rectify_fundamental": (i, [f64a, f64a, f64a]),
     "spv_dlt_triangulate": (i, _dlt),
@@ -131,6 +133,7 @@ PROTOTYPES = {
     "spv_cascade_device": (i, [vp, vp] + [i] * 6 + [vp] * 5 + [sz, vp]),
     "spv_dlt_triangulate_device": (i, _dlt_device),
     "spv_dlt_reprojection_error_device": (i, _dlt_device),
+    "spv_dlt_triangulate_batch_device": (i, [vp, vp, vp, i] + [vp] * 7 + [ll, vp, vp, vp]),
     "spv_ratio_test": (i, [u64a, vp, i, i, d, i32a, pi32]),
     "spv_ratio_test_workspace_bytes": (sz, [i]),
     "spv_ratio_test_device": (i, [vp, vp, i, i, d, vp, vp, vp, sz, vp]),

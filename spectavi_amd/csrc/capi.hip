@@ -300,6 +300,48 @@ int host_ransac_fit_batch(const double *x0, const double *x1, const long long *p
                               best_root, tries_run, nullptr, st);
 }
 
+// The many-sets triangulation through host pointers, on the first selected device: both arrays and the mask up,
+// one dlt_batch_run, the offsets back, then as many result rows as were selected and fit.  A collection without a
+// row in a used set touches no device.
+int host_dlt_batch(const double *x0, const double *x1, const long long *pair_off, int npairs, const double *P0s,
+                   const double *P1s, const int32_t *use, const uint8_t *mask, double *X, double *err, int32_t *rows,
+                   long long capacity, long long *out_off, long long *count) {
+  SPV_TRY(dlt_batch_check(x0, x1, pair_off, npairs, P1s, X, err, capacity));
+  std::vector<DltBatchItem> items;
+  long long bound = 0;
+  dlt_batch_items(pair_off, npairs, use, mask != nullptr, &items, nullptr, &bound);
+  std::vector<long long> off((size_t)npairs + 2, 0);
+  if (!items.empty()) {
+    hipStream_t st;
+    SPV_TRY(host_begin(device_list()[0], &st));
+    const size_t total = (size_t)pair_off[npairs], ib = total * 3 * sizeof(double);
+    const size_t cap = (size_t)std::min(capacity, bound);  // no more rows than that are ever written
+    DevBuf dx, dxp, dm, dX, de, dr, doff;
+    SPV_TRY(alloc_all({{&dx, ib}, {&dxp, ib}, {&doff, off.size() * sizeof(long long)}}));
+    if (mask) SPV_TRY(dm.upload(mask, total, st));
+    if (X) SPV_TRY(dX.alloc(cap * 4 * sizeof(double)));
+    if (err) SPV_TRY(de.alloc(cap * sizeof(double)));
+    if (rows) SPV_TRY(dr.alloc(cap * sizeof(int32_t)));
+    SPV_TRY(dx.copy_in(x0, ib, st));
+    SPV_TRY(dxp.copy_in(x1, ib, st));
+    SPV_TRY(dlt_batch_run(dx.as<double>(), dxp.as<double>(), pair_off, npairs, P0s, P1s, use, mask ? dm.as<uint8_t>() : nullptr,
+                          X ? dX.as<double>() : nullptr, err ? de.as<double>() : nullptr, rows ? dr.as<int32_t>() : nullptr,
+                          (long long)cap, doff.as<long long>(), doff.as<long long>() + npairs + 1, st));
+    SPV_TRY(doff.copy_out(off.data(), off.size() * sizeof(long long), st));
+    SPV_HIP_CHECK(hipStreamSynchronize(st));
+    const size_t n = (size_t)std::min<long long>(off[(size_t)npairs + 1], (long long)cap);
+    if (X) SPV_TRY(dX.copy_out(X, n * 4 * sizeof(double), st));
+    if (err) SPV_TRY(de.copy_out(err, n * sizeof(double), st));
+    if (rows) SPV_TRY(dr.copy_out(rows, n * sizeof(int32_t), st));
+    SPV_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  if (out_off) memcpy(out_off, off.data(), ((size_t)npairs + 1) * sizeof(long long));
+  if (count) *count = off[(size_t)npairs + 1];
+  if (off[(size_t)npairs + 1] > capacity)
+    return set_error(SPV_ERR_OVERFLOW, "dlt_triangulate_batch: %lld rows do not fit a capacity of %lld", off[(size_t)npairs + 1], capacity);
+  return SPV_OK;
+}
+
 // Exact p-norm k-NN through host pointers, on the first selected device (no sharding).
 int host_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                     uint64_t *idx, void *dist) {
@@ -1432,6 +1474,28 @@ int spv_ransac_fit_batch_plan(const long long *pair_off, int npairs, int maximum
     return (int)SPV_OK;
   });
 }
+int spv_dlt_triangulate_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
+                              const double *P0s, const double *P1s, const int32_t *use, const uint8_t *mask, double *X,
+                              double *err, int32_t *rows, long long capacity, long long *out_off, long long *count) {
+  return host_api([&] {
+    return host_dlt_batch(x0, x1, pair_off, npairs, P0s, P1s, use, mask, X, err, rows, capacity, out_off, count);
+  });
+}
+int spv_dlt_triangulate_batch_plan(const long long *pair_off, int npairs, const int32_t *use, int compute_units,
+                                   long long out[3], int32_t *items, long long items_cap) {
+  return api([&] {
+    SPV_TRY(ransac_batch_check(pair_off, npairs, 0, nullptr));
+    if (compute_units < 1 || !out || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
+    std::vector<DltBatchItem> its;
+    long long used = 0, bound = 0;
+    dlt_batch_items(pair_off, npairs, use, false, &its, &used, &bound);
+    out[0] = used;
+    out[1] = (long long)its.size();
+    out[2] = bound;
+    if (items) memcpy(items, its.data(), (size_t)std::min<long long>(items_cap, (long long)its.size()) * sizeof(DltBatchItem));
+    return (int)SPV_OK;
+  });
+}
 int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]) {
   return api([&] {
     if (!out) return set_error(SPV_ERR_INVALID, "null output");
@@ -1710,6 +1774,15 @@ int spv_dlt_reprojection_error_device(const double *P0, const double *P1, long l
                                       const double *d_x, const double *d_xp, double *d_dst,
                                       void *stream) {
   return api([&] { return dlt_run(P0, P1, npt, d_x, d_xp, d_dst, true, static_cast<hipStream_t>(stream)); });
+}
+int spv_dlt_triangulate_batch_device(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs,
+                                     const double *P0s, const double *P1s, const int32_t *use, const uint8_t *d_mask,
+                                     double *d_X, double *d_err, int32_t *d_rows, long long capacity,
+                                     long long *d_out_off, long long *d_count, void *stream) {
+  return api([&] {
+    return dlt_batch_run(d_x0, d_x1, pair_off, npairs, P0s, P1s, use, d_mask, d_X, d_err, d_rows, capacity, d_out_off,
+                         d_count, static_cast<hipStream_t>(stream));
+  });
 }
 
 }  // extern "C"

@@ -413,6 +413,24 @@ int ransac_fit_batch_run(const double *d_x0, const double *d_x1, const long long
                          int32_t *best_try, int32_t *best_root, int32_t *tries_run, unsigned char *d_inlier_mask,
                          hipStream_t stream);
 
+// ---- DLT triangulation of many correspondence sets in one call (dlt_batch.hip) -----------
+// One workgroup's share of a collection: rows [row0, row0 + rows) of the concatenated correspondences, all of one
+// set; out: the out row of its first row where every row is selected (no mask), else -1 (the device counts).
+struct DltBatchItem {
+  int32_t set, row0, rows, out;
+};
+// The work items of a call, a function of pair_off and use alone (host only): every used set's rows in blocks of
+// 256, in order.  *bound (may be null): the rows of the used sets.
+void dlt_batch_items(const long long *pair_off, int npairs, const int32_t *use, bool masked,
+                     std::vector<DltBatchItem> *items, long long *used_sets, long long *bound);
+// SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
+int dlt_batch_check(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs, const double *P1s,
+                    const void *X, const void *err, long long capacity);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the call's tables.
+int dlt_batch_run(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs, const double *P0s,
+                  const double *P1s, const int32_t *use, const uint8_t *d_mask, double *d_X, double *d_err,
+                  int32_t *d_rows, long long capacity, long long *d_out_off, long long *d_count, hipStream_t stream);
+
 // ---- the matches of an l1k2_batch + ratio-test run as per-pair coordinates (adapter.hip) ----
 int gather_match_coords_batch_run(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
                                   int npairs, const int *d_matches, const int *d_count, int capacity, double *d_x0,

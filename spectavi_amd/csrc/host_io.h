@@ -44,6 +44,10 @@ struct DevBuf {
     SPV_TRY(alloc(bytes));
     return copy_in(src, bytes, st);
   }
+  // For a call that returns while its kernels are still queued on the caller's stream `st`: the buffer leaves
+  // this holder now and goes back to the cache once everything queued on `st` so far has ended (an event; a later
+  // alloc() or release_transfer_caches() collects it).  Nothing waits here unless the event cannot be made.
+  void release_after(hipStream_t st);
 };
 
 // Allocates each (buffer, bytes) in turn; stops at the first failure.

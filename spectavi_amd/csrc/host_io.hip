@@ -113,9 +113,38 @@ class PinnedPool {
 };
 PinnedPool g_pinned;
 
+// Buffers given up by DevBuf::release_after, each with the event behind its last use.
+struct Deferred {
+  int dev;
+  void *p;
+  size_t cap;
+  hipEvent_t ev;
+};
+std::mutex g_deferred_mu;
+std::vector<Deferred> g_deferred;
+
+// Those whose event has passed go back to the pool; wait: all of them, after their events.
+void collect_deferred(bool wait) {
+  std::lock_guard<std::mutex> lk(g_deferred_mu);
+  size_t keep = 0;
+  for (size_t i = 0; i < g_deferred.size(); ++i) {
+    const Deferred d = g_deferred[i];
+    if (wait) (void)hipEventSynchronize(d.ev);
+    if (!wait && hipEventQuery(d.ev) == hipErrorNotReady) {
+      (void)hipGetLastError();  // "not ready" is no error of the caller's
+      g_deferred[keep++] = d;
+      continue;
+    }
+    (void)hipEventDestroy(d.ev);
+    g_pool.release(d.dev, d.p, d.cap);
+  }
+  g_deferred.resize(keep);
+}
+
 }  // namespace
 
 void release_transfer_caches() {
+  collect_deferred(true);
   g_pool.clear();
   g_pinned.clear();
 }
@@ -126,8 +155,24 @@ DevBuf::~DevBuf() {
   g_pool.release(dev, p, cap);
 }
 
+void DevBuf::release_after(hipStream_t st) {
+  if (!p) return;
+  hipEvent_t ev = nullptr;
+  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, st) == hipSuccess) {
+    std::lock_guard<std::mutex> lk(g_deferred_mu);
+    g_deferred.push_back(Deferred{dev, p, cap, ev});
+  } else {
+    if (ev) (void)hipEventDestroy(ev);
+    (void)hipStreamSynchronize(st);
+    g_pool.release(dev, p, cap);
+  }
+  p = nullptr;
+  cap = 0;
+}
+
 int DevBuf::alloc(size_t bytes) {
   if (bytes == 0) bytes = 16;
+  collect_deferred(false);
   (void)hipGetDevice(&dev);
   p = g_pool.acquire(dev, bytes, &cap);
   if (p) return SPV_OK;

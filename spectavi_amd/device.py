@@ -714,6 +714,103 @@ def ransac_fit_batch(x0, x1, pair_off, required_percent_inliers=.9, reprojection
     return (fits, mask) if want_mask else fits
 
 
+def _dlt_batch_args(pair_off, total, P1s, P0s, use):
+    """pair_off -> int64[npairs + 1], P1s / P0s -> float64[npairs, 12] (P0s or None), use -> int32[npairs] or None;
+    ValueError for anything spv_dlt_triangulate_batch_device would reject or that does not describe arrays of `total`
+    rows.  A None entry of a P1s list is a skipped set.  Touches no device."""
+    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("pair_off must start at 0 and never decrease")
+    if total is not None and int(off[-1]) != int(total):
+        raise ValueError("pair_off ends at %d, the arrays have %d rows" % (int(off[-1]), int(total)))
+    if int(off[-1]) >= 2 ** 31:
+        raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    npairs = off.size - 1
+    if npairs > 2 ** 20:
+        raise ValueError("more than 2^20 sets per call")
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
+        if use.size != npairs:
+            raise ValueError("use must hold one value per set")
+    if not isinstance(P1s, np.ndarray) and any(P is None for P in P1s):
+        skip = np.array([P is None for P in P1s])
+        if len(skip) != npairs:
+            raise ValueError("P1s must hold one camera per set")
+        use = (~skip).astype(np.int32) if use is None else (use * ~skip).astype(np.int32)
+        P1s = [np.zeros((3, 4)) if P is None else P for P in P1s]
+
+    def cameras(Ps, name):
+        Ps = np.ascontiguousarray(Ps, dtype=np.float64).reshape(-1, 12) if npairs else np.zeros((0, 12))
+        if Ps.shape[0] != npairs:
+            raise ValueError("%s must hold one [3,4] camera per set" % name)
+        return Ps
+    return off, cameras(P1s, "P1s"), None if P0s is None else cameras(P0s, "P0s"), use
+
+
+def dlt_triangulate_batch_plan(pair_off, use=None, compute_units=256, want_items=False):
+    """The work items dlt_triangulate_batch() launches for a collection (spv_dlt_triangulate_batch_plan; host only,
+    no device touched): dict of sets (used sets), items (workgroup steps) and bound (rows of the used sets).  With
+    want_items also the items, int32[items, 4] = (set, first row, rows, out row of the first row without a mask)."""
+    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("pair_off must start at 0 and never decrease")
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
+        if use.size != off.size - 1:
+            raise ValueError("use must hold one value per set")
+    u = use.ctypes.data if use is not None else None
+    out = (ct.c_longlong * 3)()
+    check(clib.spv_dlt_triangulate_batch_plan(off.ctypes.data, off.size - 1, u, int(compute_units), out, None, 0))
+    plan = dict(sets=int(out[0]), items=int(out[1]), bound=int(out[2]))
+    if want_items:
+        items = np.empty((plan["items"], 4), np.int32)
+        check(clib.spv_dlt_triangulate_batch_plan(off.ctypes.data, off.size - 1, u, int(compute_units), out,
+                                                  items.ctypes.data, len(items)))
+        return plan, items
+    return plan
+
+
+def dlt_triangulate_batch(x0, x1, pair_off, P1s, P0s=None, use=None, mask=None, want_error=False, want_rows=False):
+    """`dlt_triangulate` (and `dlt_reprojection_error`) for every set of a collection in one call
+    (spv_dlt_triangulate_batch_device): x0, x1 CUDA float64 [total,3] hold the sets back to back, set p = rows
+    pair_off[p]:pair_off[p + 1], solved with the cameras P0s[p] (None: [I|0] for every set) and P1s[p] (host [3,4]
+    arrays); a set with use[p] == 0 (or a None entry of a P1s list) is skipped.  mask: CUDA uint8 [total], e.g. what
+    `ransac_fit_batch(want_mask=True)` returns; only rows with a non-zero byte are solved.  Returns X CUDA float64
+    [total,4] -- plus err float64 [total] with want_error, rows int32 [total] (row numbers inside the set) with
+    want_rows -- and out_off, an int64 ndarray [npairs + 1]: set p's results are out rows out_off[p]:out_off[p + 1],
+    in input order, each bit for bit the single call's; rows from out_off[-1] on are not written.  Asynchronous but
+    for the upload of the cameras; reading out_off back synchronises the current stream only when a mask is given
+    (without one the host computes it)."""
+    if not (x0.shape == x1.shape and x0.dim() == 2 and x0.shape[1] == 3):
+        raise ValueError("x0, x1 must be [total,3]")
+    total = x0.shape[0]
+    off, P1s, P0s, use = _dlt_batch_args(pair_off, total, P1s, P0s, use)
+    _need(x0, torch.float64, "x0")
+    _need(x1, torch.float64, "x1")
+    if mask is not None:
+        _need(mask, torch.uint8, "mask")
+        if mask.shape != (total,):
+            raise ValueError("mask must be [total]")
+    npairs = off.size - 1
+    X = torch.empty((total, 4), dtype=torch.float64, device=x0.device)
+    err = torch.empty(total, dtype=torch.float64, device=x0.device) if want_error else None
+    rows = torch.empty(total, dtype=torch.int32, device=x0.device) if want_rows else None
+    d_off = torch.empty(npairs + 1, dtype=torch.int64, device=x0.device) if mask is not None else None
+    with _on_device_of(x0, x1, mask) as stream:
+        check(clib.spv_dlt_triangulate_batch_device(
+            x0.data_ptr(), x1.data_ptr(), off.ctypes.data, npairs, P0s.ctypes.data if P0s is not None else None,
+            P1s.ctypes.data, use.ctypes.data if use is not None else None, mask.data_ptr() if mask is not None else None,
+            X.data_ptr(), err.data_ptr() if want_error else None, rows.data_ptr() if want_rows else None, total,
+            d_off.data_ptr() if mask is not None else None, None, stream))
+    if mask is not None:
+        out_off = d_off.cpu().numpy()
+    else:
+        sizes = np.diff(off) if use is None else np.diff(off) * (use != 0)
+        out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    out = (X,) + ((err,) if want_error else ()) + ((rows,) if want_rows else ())
+    return out + (out_off,)
+
+
 def match_coordinates_batch(geom, seg_off, pairs, matches, count):
     """`match_coordinates` for the matches of an `l1k2_batch` + `ratio_test` run: geom CUDA float32 [total_rows,4]
     holds the geometry of all sets back to back (row for row the desc of the matching call), seg_off and pairs are

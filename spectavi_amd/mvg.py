@@ -371,6 +371,84 @@ def ransac_fit_batch(x0s, x1s, required_percent_inliers=.9, reprojection_error_a
     return out
 
 
+_spv_dlt_triangulate_batch = clib.spv_dlt_triangulate_batch
+
+
+def dlt_triangulate_batch(P1s, x0s, x1s, P0s=None, masks=None, ret_error=False):
+    """
+    `dlt_triangulate` for many correspondence sets in one call, each with its own cameras: x0s, x1s are lists of
+    float64 [npt_p,3] arrays, P1s a list of [3,4] second cameras -- a None entry skips its set, which is what a
+    `ransac_fit_batch` row without a model becomes --, P0s a list of first cameras or None for [I|0] everywhere (the
+    frame `ransac_fit_batch`'s cameras are expressed in).  `masks`: a list of per-set row selections (anything
+    non-zero selects; a None entry selects the whole set), e.g. built from the fits' inlier_idx.
+
+    Returns a list with one float64 [n_p,4] array per set, the selected rows in input order ([0,4] for a skipped
+    set), each bit for bit what `dlt_triangulate` returns for those rows alone; with `ret_error` also the list of
+    [n_p,1] reprojection errors.
+    """
+    if not (len(x0s) == len(x1s) == len(P1s)):
+        raise ValueError('P1s, x0s and x1s must hold one entry per set each.')
+    a0 = [np.ascontiguousarray(x, dtype=np.float64) for x in x0s]
+    a1 = [np.ascontiguousarray(x, dtype=np.float64) for x in x1s]
+    for u, v in zip(a0, a1):
+        if not (u.ndim == 2 and u.shape == v.shape and u.shape[1] == 3):
+            raise TypeError('Coords must be homogenous [npt,3] pairs.')
+    npairs = len(a0)
+    off = np.concatenate([[0], np.cumsum([len(u) for u in a0])]).astype(np.int64)
+    total = int(off[-1])
+    if total >= 2 ** 31:
+        raise ValueError('the sets must hold fewer than 2^31 rows in all')
+    if npairs > 2 ** 20:
+        raise ValueError('more than 2^20 sets per call')
+    use = np.array([P is not None for P in P1s], dtype=np.int32)
+
+    def cameras(Ps, name):
+        out = np.zeros((npairs, 12))
+        for p, P in enumerate(Ps):
+            if P is None:
+                continue
+            P = np.asarray(P, dtype=np.float64)
+            if P.shape != (3, 4):
+                raise TypeError('%s must be camera matrices.' % name)
+            out[p] = P.reshape(12)
+        return out
+    c1 = cameras(P1s, 'P1s')
+    c0 = None
+    if P0s is not None:
+        if len(P0s) != npairs:
+            raise ValueError('P0s must hold one camera per set.')
+        if any(P is None for P, u in zip(P0s, use) if u):
+            raise TypeError('P0s must be camera matrices.')
+        c0 = cameras(P0s, 'P0s')
+    mask = None
+    if masks is not None:
+        if len(masks) != npairs:
+            raise ValueError('masks must hold one entry per set.')
+        mask = np.ones(total, np.uint8)
+        for p, m in enumerate(masks):
+            if m is None:
+                continue
+            m = np.asarray(m).reshape(-1)
+            if m.size != len(a0[p]):
+                raise ValueError('a mask must hold one value per row of its set')
+            mask[off[p]:off[p + 1]] = m != 0
+    x0 = np.concatenate(a0) if total else np.zeros((0, 3))
+    x1 = np.concatenate(a1) if total else np.zeros((0, 3))
+    X = np.empty((total, 4))
+    err = np.empty(total) if ret_error else None
+    out_off = np.zeros(npairs + 1, np.int64)
+    count = ct.c_longlong(0)
+    check(_spv_dlt_triangulate_batch(x0.ctypes.data, x1.ctypes.data, off.ctypes.data, npairs,
+                                     c0.ctypes.data if c0 is not None else None, c1.ctypes.data, use.ctypes.data,
+                                     mask.ctypes.data if mask is not None else None, X.ctypes.data,
+                                     err.ctypes.data if ret_error else None, None, total, out_off.ctypes.data,
+                                     ct.addressof(count)))
+    Xs = [X[out_off[p]:out_off[p + 1]].copy() for p in range(npairs)]
+    if ret_error:
+        return Xs, [err[out_off[p]:out_off[p + 1]].reshape(-1, 1).copy() for p in range(npairs)]
+    return Xs
+
+
 # ==================================================================================
 # image_pair_rectification (reference spectavi/mvg.py:47-106)
 # ==================================================================================
