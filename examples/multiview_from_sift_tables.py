@@ -11,8 +11,9 @@ runs all of them through the many-pairs forms of the same steps, with every inte
     dlt_triangulate_batch    every pair's inliers triangulated with that pair's camera; pairs without a model skipped
 
 Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
-they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic:
-extracting them is not part of this library.
+they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic
+here, so that the scene and the cameras are known; extracting them from images is the library's sift_batch, the step
+before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
     python examples/multiview_from_sift_tables.py [--images 6] [--points 2000]
 """

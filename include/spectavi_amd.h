@@ -780,6 +780,12 @@ int spv_sift_filter(const float *im, int wid, int hgt, NdArray *out);
  * number of rows; when it exceeds capacity the first capacity rows are written and the call
  * returns SPV_ERR_OVERFLOW. */
 int spv_sift_table(const float *im, int wid, int hgt, float *table, int capacity, int32_t *count);
+/* spv_sift_batch_device (below, where the contract is) through host pointers, on the first selected device: images,
+ * table float32[cap_off[nimg], 132] and counts int32[nimg] are host memory.  The workspace comes from the library's
+ * cache, never more than the cache keeps (or than the largest image needs), hence possibly several groups.  Returns
+ * SPV_ERR_OVERFLOW, with the rows that fit written and all counts set, if any count exceeds its capacity. */
+int spv_sift_tables(const float *images, const int32_t *sizes, int nimg, float *table, const long long *cap_off,
+                    int32_t *counts);
 
 /* Rows of the first table that sift_filter, spv_sift_filter and the batch form allocate before they
  * know the count (0: the default, max(1024, min(wid*hgt/16, 2^20))).  A longer result runs the
@@ -795,6 +801,49 @@ size_t spv_sift_workspace_bytes(int wid, int hgt);
  * "sift_detect", "sift_describe". */
 int spv_sift_device(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_bytes, float *d_table, int capacity,
                     int32_t *d_count, void *stream);
+
+/* sift_filter of many images in one chain of launches (sift.hip): the step before spv_l1k2_batch_device, "N images
+ * -> N tables, back to back".  The octaves are walked once for a group of images; every launch has the image as one
+ * more grid dimension, sized by the group's largest image at that octave, and the serial scans run one workgroup
+ * per image side by side.  The launch count of a group is that of its largest image alone.
+ *   sizes    host int32[nimg, 2] = (wid, hgt), each a size sift_filter takes (sides in [1, 8192]).
+ *   d_images float32: the images back to back in that order, each row-major [hgt, wid].
+ *   cap_off  host long long[nimg + 1], cap_off[0] = 0, non-decreasing, cap_off[nimg] < 2^31: image i owns rows
+ *            [cap_off[i], cap_off[i + 1]) of d_table float32[cap_off[nimg], 132]; that many rows are its capacity.
+ *   d_counts int32[nimg]: the true row count of every image, also where it exceeds the capacity.
+ * The rows [cap_off[i], cap_off[i] + min(count_i, capacity_i)) are written; nothing else in d_table is touched.  For
+ * every image the written rows and the count are bit for bit what spv_sift_device writes for that image alone,
+ * whatever else the call holds, wherever the image stands in it and however the call is cut into groups.
+ *
+ * spv_sift_batch_plan: host only, touches no device.  Every image has a slice of the workspace, laid out as
+ * spv_sift_device's workspace for its size.  The images are cut, in order, into groups that use the workspace one
+ * after another: a group is closed when the next image's slice would no longer fit into ws_bytes (0: as much as
+ * needed), or at 65535 images.  out = {groups, bytes with which only the 65535 cap closes a group, bytes of the
+ * largest slice (the least that works), total pixels}; groups may be NULL, otherwise int32[groups_cap, 2] receives
+ * (first image, images) of the first min(groups, groups_cap) groups.  SPV_ERR_INVALID, out and groups untouched: a
+ * size sift_filter rejects, nimg < 0, NULL sizes with nimg > 0, ws_bytes non-zero and below out[2].
+ * spv_sift_batch_workspace_bytes: out[1] (0 for arguments the plan rejects).
+ *
+ * spv_sift_batch_device follows the plan for the ws_bytes it is given, group after group on `stream` (stream order
+ * lets the groups share d_ws, 256-byte aligned).  sizes and cap_off are read before the call returns.  The call may
+ * wait for the upload of its small per-image table, which is queued on `stream`; it never waits for its kernels.
+ * nimg = 0 is valid and launches nothing.  SPV_ERR_INVALID, nothing launched and no output touched: what the plan
+ * rejects, a cap_off outside the rules, a NULL required pointer (d_table only where cap_off[nimg] > 0).  Kernel
+ * names for spv_profile_read: "sift_batch_pyramid", "sift_batch_detect", "sift_batch_describe".
+ *
+ * spv_sift_batch_pack_device: the regions as what the next steps take.  seg_off: host long long[nimg + 1], the rules
+ * of spv_l1k2_batch_device, each seg_off[i + 1] - seg_off[i] at most image i's capacity (the caller computes it from
+ * the counts it read back).  One kernel copies row cap_off[i] + r of d_table to row seg_off[i] + r of d_packed
+ * float32[total, 132], d_geom float32[total, 4] and d_desc uint8[total, 128] (4-byte aligned), the last two with the
+ * values spv_sift_split_device gives for the same rows; each may be NULL, not all three.  SPV_ERR_INVALID, outputs
+ * untouched, outside these rules.  Asynchronous but for the upload of the offsets.  Kernel name: "sift_batch_pack". */
+int spv_sift_batch_plan(const int32_t *sizes, int nimg, size_t ws_bytes, long long out[4], int32_t *groups,
+                        long long groups_cap);
+size_t spv_sift_batch_workspace_bytes(const int32_t *sizes, int nimg);
+int spv_sift_batch_device(const float *d_images, const int32_t *sizes, int nimg, void *d_ws, size_t ws_bytes,
+                          float *d_table, const long long *cap_off, int32_t *d_counts, void *stream);
+int spv_sift_batch_pack_device(const float *d_table, const long long *cap_off, const long long *seg_off, int nimg,
+                               float *d_packed, float *d_geom, uint8_t *d_desc, void *stream);
 
 /* Scratch bytes needed by spv_cascade_device. */
 size_t spv_cascade_workspace_bytes(int xrows, int yrows, int dim, int m, int n, int g);

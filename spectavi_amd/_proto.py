@@ -128,6 +128,11 @@ PROTOTYPES = {
     "spv_sift_set_first_capacity": (i, [i]),
     "spv_sift_workspace_bytes": (sz, [i, i]),
     "spv_sift_device": (i, [vp, i, i, vp, sz, vp, i, vp, vp]),
+    "spv_sift_tables": (i, [vp, vp, i, vp, vp, vp]),
+    "spv_sift_batch_plan": (i, [vp, i, sz, pll, vp, ll]),
+    "spv_sift_batch_workspace_bytes": (sz, [vp, i]),
+    "spv_sift_batch_device": (i, [vp, vp, i, vp, sz, vp, vp, vp, vp]),
+    "spv_sift_batch_pack_device": (i, [vp, vp, vp, i, vp, vp, vp, vp]),
     "spv_cascade_workspace_bytes": (sz, [i] * 6),
     "spv_cascade_plan": (i, [i] * 6 + [pi]),
     "spv_cascade_device": (i, [vp, vp] + [i] * 6 + [vp] * 5 + [sz, vp]),

@@ -456,6 +456,41 @@ int host_sift(const float *im, int wid, int hgt, NdArray *out, float *table, int
   return SPV_OK;
 }
 
+// spv_sift_batch_device through host pointers, on the first selected device.  The workspace is what runs all
+// images as one group, but no more than the buffer cache keeps (or than the largest image needs): the call
+// then runs as several groups.
+int host_sift_tables(const float *images, const int32_t *sizes, int nimg, float *table, const long long *cap_off,
+                     int32_t *counts) {
+  SiftBatchPlan plan;
+  SPV_TRY(sift_batch_plan(sizes, nimg, 0, &plan));
+  SPV_TRY(sift_batch_check_offsets(cap_off, nimg, "cap_off"));
+  if (nimg == 0) return SPV_OK;
+  if (!images || !counts || (cap_off[nimg] > 0 && !table)) return set_error(SPV_ERR_INVALID, "null pointer");
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t wsb = std::min(plan.all_bytes, std::max(plan.min_bytes, kDevicePoolCapBytes));
+  const size_t tb = (size_t)cap_off[nimg] * 132 * sizeof(float), cb = (size_t)nimg * sizeof(int32_t);
+  DevBuf dim, ws, dt, dc;
+  SPV_TRY(dim.upload(images, (size_t)plan.pixels * sizeof(float), st));
+  SPV_TRY(alloc_all({{&ws, wsb}, {&dc, cb}, {&dt, std::max<size_t>(tb, 1)}}));
+  SPV_TRY(sift_batch_run(dim.as<float>(), sizes, nimg, ws.p, wsb, dt.as<float>(), cap_off, dc.as<int32_t>(), st));
+  SPV_TRY(dc.copy_out(counts, cb, st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  int short_of = -1;
+  for (int i = 0; i < nimg; ++i) {
+    const long long cap = cap_off[i + 1] - cap_off[i], rows = std::min<long long>(counts[i], cap);
+    if (counts[i] > cap && short_of < 0) short_of = i;
+    if (rows > 0)
+      SPV_HIP_CHECK(hipMemcpyAsync(table + (size_t)cap_off[i] * 132, dt.as<float>() + (size_t)cap_off[i] * 132,
+                                 (size_t)rows * 132 * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  if (short_of >= 0)
+    return set_error(SPV_ERR_OVERFLOW, "sift: the %d rows of image %d do not fit its region of %lld", (int)counts[short_of],
+                     short_of, cap_off[short_of + 1] - cap_off[short_of]);
+  return SPV_OK;
+}
+
 struct SiftBatch {
   struct Item {
     const float *im;
@@ -1535,6 +1570,11 @@ int spv_sift_table(const float *im, int wid, int hgt, float *table, int capacity
   return host_api([&] { return host_sift(im, wid, hgt, nullptr, table, capacity, count); });
 }
 
+int spv_sift_tables(const float *images, const int32_t *sizes, int nimg, float *table, const long long *cap_off,
+                    int32_t *counts) {
+  return host_api([&] { return host_sift_tables(images, sizes, nimg, table, cap_off, counts); });
+}
+
 // ---- device-pointer variants --------------------------------------------------------
 size_t spv_l1k2_workspace_bytes(int xrows, int yrows, int dim) {
   if (!l1k2_shape_ok(xrows, yrows, dim)) return 0;
@@ -1670,6 +1710,48 @@ int spv_sift_device(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_b
                     int32_t *d_count, void *stream) {
   return api([&] {
     return sift_run(d_im, wid, hgt, d_ws, ws_bytes, d_table, capacity, d_count, static_cast<hipStream_t>(stream));
+  });
+}
+
+int spv_sift_batch_plan(const int32_t *sizes, int nimg, size_t ws_bytes, long long out[4], int32_t *groups,
+                        long long groups_cap) {
+  return api([&] {
+    if (!out || (groups && groups_cap < 0)) return set_error(SPV_ERR_INVALID, "null output or negative groups_cap");
+    SiftBatchPlan p;
+    SPV_TRY(sift_batch_plan(sizes, nimg, ws_bytes, &p));
+    const long long n = (long long)p.groups.size();
+    out[0] = n;
+    out[1] = (long long)p.all_bytes;
+    out[2] = (long long)p.min_bytes;
+    out[3] = p.pixels;
+    for (long long e = 0; groups && e < std::min(n, groups_cap); ++e) {
+      groups[2 * e] = p.groups[(size_t)e].first;
+      groups[2 * e + 1] = p.groups[(size_t)e].second;
+    }
+    return (int)SPV_OK;
+  });
+}
+
+size_t spv_sift_batch_workspace_bytes(const int32_t *sizes, int nimg) {
+  SiftBatchPlan p;
+  const int st = guard([&] { return sift_batch_plan(sizes, nimg, 0, &p); });
+  if (st != SPV_OK) clear_error();
+  return st == SPV_OK ? p.all_bytes : 0;
+}
+
+int spv_sift_batch_device(const float *d_images, const int32_t *sizes, int nimg, void *d_ws, size_t ws_bytes,
+                          float *d_table, const long long *cap_off, int32_t *d_counts, void *stream) {
+  return api([&] {
+    return sift_batch_run(d_images, sizes, nimg, d_ws, ws_bytes, d_table, cap_off, d_counts,
+                          static_cast<hipStream_t>(stream));
+  });
+}
+
+int spv_sift_batch_pack_device(const float *d_table, const long long *cap_off, const long long *seg_off, int nimg,
+                               float *d_packed, float *d_geom, uint8_t *d_desc, void *stream) {
+  return api([&] {
+    return sift_batch_pack_run(d_table, cap_off, seg_off, nimg, d_packed, d_geom, d_desc,
+                               static_cast<hipStream_t>(stream));
   });
 }
 

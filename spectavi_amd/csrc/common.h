@@ -302,6 +302,26 @@ size_t sift_workspace_bytes(int wid, int hgt);
 int sift_run(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_bytes, float *d_table, int capacity,
              int *d_count, hipStream_t stream);
 
+// ---- SIFT of many images in one chain of launches (sift.hip) ---------------------------
+constexpr int kSiftBatchMaxImages = 65535;  // the image is grid dimension y or z
+// How a call cuts its images, in order, into groups that share the workspace one after another.
+struct SiftBatchPlan {
+  std::vector<std::pair<int, int>> groups;  // (first image, images)
+  size_t all_bytes = 0;                     // workspace with which only kSiftBatchMaxImages closes a group
+  size_t min_bytes = 0;                     // the most demanding single image's slice
+  long long pixels = 0;
+};
+// sizes int32[nimg, 2] = (wid, hgt); ws_bytes = 0: as much as needed.  SPV_ERR_INVALID (message set, *p untouched)
+// for what include/spectavi_amd.h rejects; host only
+int sift_batch_plan(const int32_t *sizes, int nimg, size_t ws_bytes, SiftBatchPlan *p);
+// off[0] = 0, non-decreasing, off[nimg] < 2^31 (cap_off and seg_off); SPV_ERR_INVALID (message set) otherwise
+int sift_batch_check_offsets(const long long *off, int nimg, const char *what);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the images' records.
+int sift_batch_run(const float *d_images, const int32_t *sizes, int nimg, void *d_ws, size_t ws_bytes, float *d_table,
+                   const long long *cap_off, int32_t *d_counts, hipStream_t stream);
+int sift_batch_pack_run(const float *d_table, const long long *cap_off, const long long *seg_off, int nimg,
+                        float *d_packed, float *d_geom, uint8_t *d_desc, hipStream_t stream);
+
 // ---- ratio test + compaction (match.hip) ---------------------------------------------
 size_t ratio_workspace_bytes(int yrows);
 int ratio_run(const uint64_t *d_idx, const void *d_dist, int dist_is_float, int yrows,

@@ -56,6 +56,9 @@ inline int alloc_all(std::initializer_list<std::pair<DevBuf *, size_t>> bufs) {
   return SPV_OK;
 }
 
+// The most bytes the cache behind DevBuf keeps per device; a call that can run in pieces asks for no more at once.
+constexpr size_t kDevicePoolCapBytes = (size_t)4 << 30;
+
 // Empties the device buffer cache and the pinned staging cache (spv_release_cached_memory).
 void release_transfer_caches();
 

@@ -13,7 +13,7 @@ namespace {
 // release_transfer_caches() empties it.
 class DevicePool {
  public:
-  static constexpr size_t kPoolCapBytes = (size_t)4 << 30;
+  static constexpr size_t kPoolCapBytes = kDevicePoolCapBytes;
   void *acquire(int dev, size_t bytes, size_t *got) {
     std::lock_guard<std::mutex> lk(mu_);
     auto &fl = free_[dev];

@@ -9,7 +9,9 @@
 // Every float sum keeps vlfeat's order: a histogram bin is owned by one lane, which adds the window's
 // pixels in raster order; the pixels' terms are computed 64 at a time, one per lane, through LDS.
 // The DoG is never stored: D[s] = L[s+1] - L[s] is recomputed where it is read (same float result).
+// Many images run as one such chain (sift_batch_run): the same bodies, the image as one more grid dimension.
 #include "common.h"
+#include "host_io.h"
 
 #include <math.h>
 
@@ -147,8 +149,9 @@ __device__ __forceinline__ float up_x(const float *in, int w, int r, int X) {
   if (i < w - 1) return (in[(size_t)r * w + i] + in[(size_t)r * w + i + 1]) * 0.5f;
   return in[(size_t)r * w + w - 1];
 }
-__global__ __launch_bounds__(256) void sift_upsample_kernel(const float *__restrict__ in, int w, int h, float *__restrict__ out) {
-  const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y;
+// The kernels' bodies take their place in the grid as arguments: the single-image kernels and the batch
+// kernels (one more grid dimension: the image) run the same code, hence write the same bits.
+__device__ __forceinline__ void upsample_body(const float *__restrict__ in, int w, int h, float *__restrict__ out, int X, int Y) {
   if (X >= 2 * w) return;
   const int i = Y >> 1;
   float v;
@@ -157,17 +160,21 @@ __global__ __launch_bounds__(256) void sift_upsample_kernel(const float *__restr
   else v = up_x(in, w, h - 1, X);
   out[(size_t)Y * 2 * w + X] = v;
 }
+__global__ __launch_bounds__(256) void sift_upsample_kernel(const float *__restrict__ in, int w, int h, float *__restrict__ out) {
+  upsample_body(in, w, h, out, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
 
-__global__ __launch_bounds__(256) void sift_downsample_kernel(const float *__restrict__ in, int win, float *__restrict__ out, int w) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+__device__ __forceinline__ void downsample_body(const float *__restrict__ in, int win, float *__restrict__ out, int w, int x, int y) {
   if (x >= w) return;
   out[(size_t)y * w + x] = in[(size_t)(2 * y) * win + 2 * x];
+}
+__global__ __launch_bounds__(256) void sift_downsample_kernel(const float *__restrict__ in, int win, float *__restrict__ out, int w) {
+  downsample_body(in, win, out, w, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
 }
 
 // VERT: out[y][x] = sum_j in[clamp(y - W + j)][x] * t[2W - j]; else the same along x.
 template <bool VERT>
-__global__ __launch_bounds__(256) void sift_smooth_kernel(const float *__restrict__ in, float *__restrict__ out, int w, int h, Taps tp) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+__device__ __forceinline__ void smooth_body(const float *__restrict__ in, float *__restrict__ out, int w, int h, const Taps &tp, int x, int y) {
   if (x >= w) return;
   const int W = tp.W;
   float acc = 0.f;
@@ -184,6 +191,10 @@ __global__ __launch_bounds__(256) void sift_smooth_kernel(const float *__restric
     }
   }
   out[(size_t)y * w + x] = acc;
+}
+template <bool VERT>
+__global__ __launch_bounds__(256) void sift_smooth_kernel(const float *__restrict__ in, float *__restrict__ out, int w, int h, Taps tp) {
+  smooth_body<VERT>(in, out, w, h, tp, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
 }
 
 // ---- extrema --------------------------------------------------------------------------------
@@ -214,10 +225,9 @@ __device__ __forceinline__ bool is_extremum(const Octave &oc, int di, int y, int
 // One wave per DoG row (s in 0..2, y in 1..h-2).  WRITE = false: rowcnt[r] = extrema in the row;
 // WRITE = true: the row's extrema, packed x | y << 15 | s << 30, from offset rowoff[r], x ascending.
 template <bool WRITE>
-__global__ __launch_bounds__(256) void sift_extrema_kernel(Octave oc, int *__restrict__ rowcnt, const int *__restrict__ rowoff,
-                                    uint32_t *__restrict__ cand) {
+__device__ __forceinline__ void extrema_body(const Octave &oc, int *__restrict__ rowcnt, const int *__restrict__ rowoff,
+                                             uint32_t *__restrict__ cand, int r) {
   const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int rows = oc.h - 2;
   if (r >= 3 * rows) return;
   const int s = r / rows, y = 1 + r % rows;
@@ -234,15 +244,19 @@ __global__ __launch_bounds__(256) void sift_extrema_kernel(Octave oc, int *__res
   }
   if (!WRITE && lane == 0) rowcnt[r] = n;
 }
+template <bool WRITE>
+__global__ __launch_bounds__(256) void sift_extrema_kernel(Octave oc, int *__restrict__ rowcnt, const int *__restrict__ rowoff,
+                                    uint32_t *__restrict__ cand) {
+  extrema_body<WRITE>(oc, rowcnt, rowoff, cand, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+}
 
 // ---- scan ------------------------------------------------------------------------------------
 // One block: out[i] = base + sum(in[lo..i)) over i in [lo, hi).  [lo, hi) is range_in[0..1] or
 // [0, n); n is min(*n_dev, n) when n_dev is given.  base = *counter (0 without one).  Writes the
 // total to *total_out, {base, base + total} to range_out and base + total to *counter.
-__global__ __launch_bounds__(kScanThreads) void sift_scan_kernel(const int *__restrict__ in, int n,
-                                                                 const int *__restrict__ n_dev,
-                                                                 const int *__restrict__ range_in, int *out,
-                                                                 int *counter, int *total_out, int *range_out) {
+__device__ __forceinline__ void scan_body(const int *__restrict__ in, int n, const int *__restrict__ n_dev,
+                                          const int *__restrict__ range_in, int *out, int *counter, int *total_out,
+                                          int *range_out) {
   __shared__ int part[kScanThreads];
   __shared__ int carry_s;
   int lo = 0, hi = n;
@@ -291,6 +305,12 @@ __global__ __launch_bounds__(kScanThreads) void sift_scan_kernel(const int *__re
     if (counter) *counter = base + total;
   }
 }
+__global__ __launch_bounds__(kScanThreads) void sift_scan_kernel(const int *__restrict__ in, int n,
+                                                                 const int *__restrict__ n_dev,
+                                                                 const int *__restrict__ range_in, int *out,
+                                                                 int *counter, int *total_out, int *range_out) {
+  scan_body(in, n, n_dev, range_in, out, counter, total_out, range_out);
+}
 
 // ---- refinement ------------------------------------------------------------------------------
 struct KeyRec {
@@ -298,11 +318,13 @@ struct KeyRec {
   int s;
 };
 
-__global__ __launch_bounds__(256) void sift_refine_kernel(Octave oc, int o, double sigma0, const uint32_t *__restrict__ cand, const int *__restrict__ ncand,
-                                   int *__restrict__ flag, KeyRec *__restrict__ rec) {
+// lanes first, first + stride, ... of the image's share of the grid
+__device__ __forceinline__ void refine_body(const Octave &oc, int o, double sigma0, const uint32_t *__restrict__ cand,
+                                            const int *__restrict__ ncand, int *__restrict__ flag, KeyRec *__restrict__ rec,
+                                            int first, int stride) {
   const int n = *ncand;
   const int w = oc.w, h = oc.h;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+  for (int i = first; i < n; i += stride) {
     const uint32_t c = cand[i];
     int x = c & 0x7fff, y = (c >> 15) & 0x7fff;
     const int s = c >> 30, di = s + 1;
@@ -381,19 +403,27 @@ __global__ __launch_bounds__(256) void sift_refine_kernel(Octave oc, int o, doub
     }
   }
 }
+__global__ __launch_bounds__(256) void sift_refine_kernel(Octave oc, int o, double sigma0, const uint32_t *__restrict__ cand, const int *__restrict__ ncand,
+                                   int *__restrict__ flag, KeyRec *__restrict__ rec) {
+  refine_body(oc, o, sigma0, cand, ncand, flag, rec, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
 
+__device__ __forceinline__ void scatter_body(const int *__restrict__ ncand, const int *__restrict__ flag,
+                                             const int *__restrict__ off, const KeyRec *__restrict__ rec,
+                                             KeyRec *__restrict__ kp, int first, int stride) {
+  const int n = *ncand;
+  for (int i = first; i < n; i += stride)
+    if (flag[i]) kp[off[i]] = rec[i];
+}
 __global__ __launch_bounds__(256) void sift_scatter_kernel(const int *__restrict__ ncand, const int *__restrict__ flag,
                                     const int *__restrict__ off, const KeyRec *__restrict__ rec,
                                     KeyRec *__restrict__ kp) {
-  const int n = *ncand;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    if (flag[i]) kp[off[i]] = rec[i];
+  scatter_body(ncand, flag, off, rec, kp, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // ---- gradients -------------------------------------------------------------------------------
 // grad[(s * plane + i) * 2 + {0, 1}] = (mod, angle) of level s = 0..2 (level index s + 1).
-__global__ __launch_bounds__(256) void sift_gradient_kernel(Octave oc, float *__restrict__ grad) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, s = blockIdx.z;
+__device__ __forceinline__ void gradient_body(const Octave &oc, float *__restrict__ grad, int x, int y, int s) {
   const int w = oc.w, h = oc.h;
   if (x >= w) return;
   const float *src = oc.L + (size_t)(s + 1) * oc.plane;
@@ -409,7 +439,9 @@ __global__ __launch_bounds__(256) void sift_gradient_kernel(Octave oc, float *__
   g[0] = fast_sqrt_f(gx * gx + gy * gy);
   g[1] = mod2pi_f((float)((double)fast_atan2_f(gy, gx) + 2 * M_PI));
 }
-
+__global__ __launch_bounds__(256) void sift_gradient_kernel(Octave oc, float *__restrict__ grad) {
+  gradient_body(oc, grad, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y, blockIdx.z);
+}
 
 // ---- orientation ------------------------------------------------------------------------------
 // One 64-lane block per keypoint.  The window's pixels are taken 64 at a time in raster order, one
@@ -417,18 +449,18 @@ __global__ __launch_bounds__(256) void sift_gradient_kernel(Octave oc, float *__
 // differ, so each bin sees the pixels in raster order, as in vlfeat).
 constexpr int kSkip = -1000;  // no contribution (outside the circular window)
 
-__global__ __launch_bounds__(64) void sift_orientation_kernel(int o, int w, int h, size_t plane,
-                                                              const float *__restrict__ grad,
-                                                              const KeyRec *__restrict__ kp,
-                                                              const int *__restrict__ range,
-                                                              double *__restrict__ angles, int *__restrict__ nang) {
+// blocks block, block + nblocks, ... of the image's share of the grid
+__device__ __forceinline__ void orientation_body(int o, int w, int h, size_t plane, const float *__restrict__ grad,
+                                                 const KeyRec *__restrict__ kp, const int *__restrict__ range,
+                                                 double *__restrict__ angles, int *__restrict__ nang, int block,
+                                                 int nblocks) {
   __shared__ int sb[64];
   __shared__ double sv0[64], sv1[64];
   __shared__ double hist[36];
   const int lane = threadIdx.x;
   const int lo = range[0], hi = range[1];
   const double xper = ldexp(1.0, o);
-  for (int k = lo + blockIdx.x; k < hi; k += gridDim.x) {
+  for (int k = lo + block; k < hi; k += nblocks) {
     const KeyRec key = kp[k];
     const double x = key.x / xper, y = key.y / xper, sigma = key.sigma / xper;
     const int xi = (int)(x + 0.5), yi = (int)(y + 0.5);
@@ -508,6 +540,13 @@ __global__ __launch_bounds__(64) void sift_orientation_kernel(int o, int w, int 
     }
   }
 }
+__global__ __launch_bounds__(64) void sift_orientation_kernel(int o, int w, int h, size_t plane,
+                                                              const float *__restrict__ grad,
+                                                              const KeyRec *__restrict__ kp,
+                                                              const int *__restrict__ range,
+                                                              double *__restrict__ angles, int *__restrict__ nang) {
+  orientation_body(o, w, h, plane, grad, kp, range, angles, nang, blockIdx.x, gridDim.x);
+}
 
 // ---- descriptor --------------------------------------------------------------------------------
 // One 64-lane block per keypoint, its angles in turn; lane l owns bins l and l + 64.  Pixel terms
@@ -539,21 +578,18 @@ __device__ __forceinline__ float block_norm(float *sd, float a, float b, int lan
   return snorm;
 }
 
-__global__ __launch_bounds__(64) void sift_descriptor_kernel(int o, int w, int h, size_t plane,
-                                                             const float *__restrict__ grad,
-                                                             const KeyRec *__restrict__ kp,
-                                                             const int *__restrict__ range,
-                                                             const double *__restrict__ angles,
-                                                             const int *__restrict__ nang,
-                                                             const int *__restrict__ row0, float *__restrict__ table,
-                                                             int capacity) {
+__device__ __forceinline__ void descriptor_body(int o, int w, int h, size_t plane, const float *__restrict__ grad,
+                                                const KeyRec *__restrict__ kp, const int *__restrict__ range,
+                                                const double *__restrict__ angles, const int *__restrict__ nang,
+                                                const int *__restrict__ row0, float *__restrict__ table, int capacity,
+                                                int block, int nblocks) {
   __shared__ float swm[64], srx[64], sry[64], srt[64];
   __shared__ int sbin[64];  // bx + 8 | (by + 8) << 8 | bt << 16
   __shared__ float sd[128];
   const int lane = threadIdx.x;
   const int lo = range[0], hi = range[1];
   const double xper = ldexp(1.0, o);
-  for (int k = lo + blockIdx.x; k < hi; k += gridDim.x) {
+  for (int k = lo + block; k < hi; k += nblocks) {
     const KeyRec key = kp[k];
     const double x = key.x / xper, y = key.y / xper, sigma = key.sigma / xper;
     const int xi = (int)(x + 0.5), yi = (int)(y + 0.5);
@@ -638,8 +674,186 @@ __global__ __launch_bounds__(64) void sift_descriptor_kernel(int o, int w, int h
     }
   }
 }
+__global__ __launch_bounds__(64) void sift_descriptor_kernel(int o, int w, int h, size_t plane,
+                                                             const float *__restrict__ grad,
+                                                             const KeyRec *__restrict__ kp,
+                                                             const int *__restrict__ range,
+                                                             const double *__restrict__ angles,
+                                                             const int *__restrict__ nang,
+                                                             const int *__restrict__ row0, float *__restrict__ table,
+                                                             int capacity) {
+  descriptor_body(o, w, h, plane, grad, kp, range, angles, nang, row0, table, capacity, blockIdx.x, gridDim.x);
+}
 
 __global__ void sift_count_kernel(const int *__restrict__ ctr, int *__restrict__ count) { *count = ctr[C_NROW]; }
+
+// ---- many images in one chain of launches -----------------------------------------------------------
+// The host walks the octaves once for a group of images; every launch has the image as one more grid
+// dimension, its extent that of the group's largest image at that octave.  An image's record says where
+// its slice of the workspace lies (the pieces of sift_layout); whether the image takes part in octave o,
+// and with which w and h, is decided here from wid, hgt and noct.  Blocks outside their image's extent,
+// and all blocks of an image that sits out, return at once and together.
+struct SiftImg {
+  const float *im;
+  int *ctr;
+  float *L;
+  char *scratch;  // the smoothing temporary, the candidates and the gradients, each from its start
+  int *cflag, *coff;
+  KeyRec *crec;
+  int *rowcnt, *rowoff;
+  KeyRec *kp;
+  double *ang;
+  int *nang, *krow;
+  float *table;  // the image's region of the caller's table, `capacity` rows
+  int *count;
+  size_t N;
+  int wid, hgt, noct, capacity;
+};
+
+struct ImgOctave {
+  int w, h;
+  bool pyr, det;  // takes part in the pyramid; and in detection and description
+};
+__host__ __device__ __forceinline__ ImgOctave img_octave(int wid, int hgt, int noct, int o) {
+  ImgOctave q;
+  q.w = o < 0 ? 2 * wid : wid >> o;
+  q.h = o < 0 ? 2 * hgt : hgt >> o;
+  q.pyr = o < -1 + noct;
+  q.det = q.pyr && q.w >= 3 && q.h >= 3;
+  return q;
+}
+__device__ __forceinline__ ImgOctave img_octave(const SiftImg &r, int o) { return img_octave(r.wid, r.hgt, r.noct, o); }
+
+__global__ __launch_bounds__(256) void sift_batch_init_kernel(const SiftImg *__restrict__ imgs, int nimg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nimg) return;
+  for (int k = 0; k < C_COUNT; ++k) imgs[i].ctr[k] = 0;
+}
+
+// grid (columns / 256, rows, images) of the largest image
+__global__ __launch_bounds__(256) void sift_batch_upsample_kernel(const SiftImg *__restrict__ imgs) {
+  const SiftImg &r = imgs[blockIdx.z];
+  if ((int)blockIdx.y >= 2 * r.hgt) return;  // octave -1: every image takes part
+  upsample_body(r.im, r.wid, r.hgt, r.L, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+
+__global__ __launch_bounds__(256) void sift_batch_downsample_kernel(const SiftImg *__restrict__ imgs, int o) {
+  const SiftImg &r = imgs[blockIdx.z];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.pyr || (int)blockIdx.y >= q.h) return;
+  const int pw = img_octave(r, o - 1).w;
+  downsample_body(r.L + 3 * r.N, pw, r.L, q.w, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+
+// VERT: level `level` -> the temporary; else the temporary -> level `level`
+template <bool VERT>
+__global__ __launch_bounds__(256) void sift_batch_smooth_kernel(const SiftImg *__restrict__ imgs, int o, int level, Taps tp) {
+  const SiftImg &r = imgs[blockIdx.z];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.pyr || (int)blockIdx.y >= q.h) return;
+  float *lv = r.L + level * r.N, *tmp = reinterpret_cast<float *>(r.scratch);
+  smooth_body<VERT>(VERT ? lv : tmp, VERT ? tmp : lv, q.w, q.h, tp, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+
+// grid (DoG rows / 4, images)
+template <bool WRITE>
+__global__ __launch_bounds__(256) void sift_batch_extrema_kernel(const SiftImg *__restrict__ imgs, int o) {
+  const SiftImg &r = imgs[blockIdx.y];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.det) return;
+  extrema_body<WRITE>(Octave{r.L, r.N, q.w, q.h}, r.rowcnt, r.rowoff, reinterpret_cast<uint32_t *>(r.scratch),
+                      blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+}
+
+// One workgroup per image.  STAGE 0: the rows' extrema counts -> offsets and the candidate count; 1: the
+// candidates' flags -> keypoint offsets and the octave's keypoint range; 2: the keypoints' angle counts
+// -> table rows, after the rows of the image's earlier octaves.
+template <int STAGE>
+__global__ __launch_bounds__(kScanThreads) void sift_batch_scan_kernel(const SiftImg *__restrict__ imgs, int o) {
+  const SiftImg &r = imgs[blockIdx.x];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.det) return;  // the whole workgroup: no barrier is reached by part of it
+  if (STAGE == 0) scan_body(r.rowcnt, 3 * (q.h - 2), nullptr, nullptr, r.rowoff, nullptr, r.ctr + C_NCAND, nullptr);
+  if (STAGE == 1)
+    scan_body(r.cflag, (int)((size_t)q.w * q.h), r.ctr + C_NCAND, nullptr, r.coff, nullptr, nullptr, r.ctr + C_KP_LO);
+  if (STAGE == 2) scan_body(r.nang, 0, nullptr, r.ctr + C_KP_LO, r.krow, r.ctr + C_NROW, nullptr, nullptr);
+}
+
+// grid (the image's share of the persistent blocks, images)
+__global__ __launch_bounds__(256) void sift_batch_refine_kernel(const SiftImg *__restrict__ imgs, int o, double sigma0) {
+  const SiftImg &r = imgs[blockIdx.y];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.det) return;
+  refine_body(Octave{r.L, r.N, q.w, q.h}, o, sigma0, reinterpret_cast<const uint32_t *>(r.scratch), r.ctr + C_NCAND,
+              r.cflag, r.crec, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void sift_batch_scatter_kernel(const SiftImg *__restrict__ imgs, int o) {
+  const SiftImg &r = imgs[blockIdx.y];
+  if (!img_octave(r, o).det) return;
+  scatter_body(r.ctr + C_NCAND, r.cflag, r.coff, r.crec, r.kp, blockIdx.x * blockDim.x + threadIdx.x,
+               gridDim.x * blockDim.x);
+}
+
+// grid (columns / 256, rows, images); the three levels in turn
+__global__ __launch_bounds__(256) void sift_batch_gradient_kernel(const SiftImg *__restrict__ imgs, int o) {
+  const SiftImg &r = imgs[blockIdx.z];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.det || (int)blockIdx.y >= q.h) return;
+  const Octave oc{r.L, r.N, q.w, q.h};
+  for (int s = 0; s < 3; ++s)
+    gradient_body(oc, reinterpret_cast<float *>(r.scratch), blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y, s);
+}
+
+// grid (the image's share of the keypoint blocks, images)
+__global__ __launch_bounds__(64) void sift_batch_orientation_kernel(const SiftImg *__restrict__ imgs, int o) {
+  const SiftImg &r = imgs[blockIdx.y];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.det) return;
+  orientation_body(o, q.w, q.h, r.N, reinterpret_cast<const float *>(r.scratch), r.kp, r.ctr + C_KP_LO, r.ang, r.nang,
+                   blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64) void sift_batch_descriptor_kernel(const SiftImg *__restrict__ imgs, int o) {
+  const SiftImg &r = imgs[blockIdx.y];
+  const ImgOctave q = img_octave(r, o);
+  if (!q.det) return;
+  descriptor_body(o, q.w, q.h, r.N, reinterpret_cast<const float *>(r.scratch), r.kp, r.ctr + C_KP_LO, r.ang, r.nang,
+                  r.krow, r.table, r.capacity, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void sift_batch_count_kernel(const SiftImg *__restrict__ imgs, int nimg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nimg) *imgs[i].count = imgs[i].ctr[C_NROW];
+}
+
+// Rows cap_off[i] + r of the regions -> rows seg_off[i] + r of the packed outputs: 32 lanes per row, as
+// sift_split_kernel (adapter.hip) and with its values.  offs = cap_off[nimg] then seg_off[nimg + 1].
+__global__ __launch_bounds__(256) void sift_batch_pack_kernel(const long long *__restrict__ offs, int nimg,
+                                                              const float *__restrict__ table, float *__restrict__ packed,
+                                                              float *__restrict__ geom, uint8_t *__restrict__ desc) {
+  const long long *cap_off = offs, *seg_off = offs + nimg;
+  const long long gt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long row = gt >> 5;
+  const int j = (int)(gt & 31);
+  if (row >= seg_off[nimg]) return;
+  int lo = 0, hi = nimg - 1;  // the last image whose segment starts at or before row (empty segments skipped)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (seg_off[mid] <= row) lo = mid;
+    else hi = mid - 1;
+  }
+  const float *src = table + (size_t)(cap_off[lo] + (row - seg_off[lo])) * 132;
+  if (packed)
+    for (int c = j; c < 132; c += 32) packed[(size_t)row * 132 + c] = src[c];
+  if (geom && j < 4) geom[(size_t)row * 4 + j] = src[j];
+  if (desc) {
+    const float *d = src + 4 + 4 * j;
+    const uint32_t pk = ((uint32_t)(int)d[0] & 0xFFu) | (((uint32_t)(int)d[1] & 0xFFu) << 8) |
+                        (((uint32_t)(int)d[2] & 0xFFu) << 16) | (((uint32_t)(int)d[3] & 0xFFu) << 24);
+    reinterpret_cast<uint32_t *>(desc)[(size_t)row * 32 + j] = pk;
+  }
+}
 
 // ---- host side -----------------------------------------------------------------------------------
 
@@ -788,6 +1002,212 @@ int sift_run(const float *d_im, int wid, int hgt, void *d_ws, size_t ws_bytes, f
     SPV_HIP_CHECK(hipGetLastError());
   }
   sift_count_kernel<<<1, 1, 0, st>>>(ctr, d_count);
+  SPV_HIP_CHECK(hipGetLastError());
+  return SPV_OK;
+}
+
+// ---- many images in one chain of launches: host side ------------------------------------------------
+
+int sift_batch_plan(const int32_t *sizes, int nimg, size_t ws_bytes, SiftBatchPlan *p) {
+  if (nimg < 0) return set_error(SPV_ERR_INVALID, "negative image count");
+  if (nimg > 0 && !sizes) return set_error(SPV_ERR_INVALID, "null sizes");
+  SiftBatchPlan q;
+  std::vector<size_t> need((size_t)nimg);
+  for (int i = 0; i < nimg; ++i) {
+    SPV_TRY(sift_check(sizes[2 * i], sizes[2 * i + 1]));
+    need[i] = sift_layout(sizes[2 * i], sizes[2 * i + 1]).total;
+    q.min_bytes = std::max(q.min_bytes, need[i]);
+    q.pixels += (long long)sizes[2 * i] * sizes[2 * i + 1];
+  }
+  if (ws_bytes && ws_bytes < q.min_bytes)
+    return set_error(SPV_ERR_INVALID, "workspace %zu bytes, the largest image alone needs %zu", ws_bytes, q.min_bytes);
+  // the images in order; a group is closed when the next slice would not fit, or at kSiftBatchMaxImages
+  auto cut = [&](size_t cap, std::vector<std::pair<int, int>> *groups) {
+    size_t most = 0, sum = 0;
+    int first = 0;
+    for (int i = 0; i < nimg; ++i) {
+      if (i > first && ((cap && sum + need[i] > cap) || i - first == kSiftBatchMaxImages)) {
+        if (groups) groups->emplace_back(first, i - first);
+        first = i;
+        sum = 0;
+      }
+      sum += need[i];
+      most = std::max(most, sum);
+    }
+    if (nimg > 0 && groups) groups->emplace_back(first, nimg - first);
+    return most;
+  };
+  q.all_bytes = cut(0, nullptr);
+  cut(ws_bytes, &q.groups);
+  *p = std::move(q);
+  return SPV_OK;
+}
+
+int sift_batch_check_offsets(const long long *off, int nimg, const char *what) {
+  if (!off) return set_error(SPV_ERR_INVALID, "null %s", what);
+  if (off[0] != 0) return set_error(SPV_ERR_INVALID, "%s must start at 0", what);
+  for (int i = 0; i < nimg; ++i)
+    if (off[i + 1] < off[i]) return set_error(SPV_ERR_INVALID, "%s decreases at %d", what, i);
+  if (off[nimg] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%s ends at %lld rows: must be below 2^31", what, off[nimg]);
+  return SPV_OK;
+}
+
+namespace {
+
+constexpr int kPersistFloor = 32, kKeyFloor = 128;  // the least share of the persistent grids an image of a large group gets
+
+// One group: images [first, first + n), their slices one after another from d_ws; d_imgs holds their records.
+int sift_batch_group(const SiftImg *d_imgs, const int32_t *sizes, int n, hipStream_t st) {
+  const double sigmak = std::pow(2.0, 1.0 / 3), sigma0 = 1.6 * sigmak;
+  const double dsigma0 = sigma0 * std::sqrt(1.0 - 1.0 / (sigmak * sigmak));
+  Taps level_taps[5];
+  for (int s = 0; s < 5; ++s) level_taps[s] = make_taps(dsigma0 * std::pow(sigmak, s));
+  const double sa = sigma0 * std::pow(sigmak, -1), sb = 0.5 * 2.0;
+  const Taps first_taps = make_taps(std::sqrt(sa * sa - sb * sb));
+
+  sift_batch_init_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_imgs, n);
+  SPV_HIP_CHECK(hipGetLastError());
+  int O = 1;
+  for (int i = 0; i < n; ++i) O = std::max(O, sift_noctaves(sizes[2 * i], sizes[2 * i + 1]));
+  for (int o = -1; o < -1 + O; ++o) {
+    // the grid's extent: the widest and the tallest image that takes part (they need not be the same one)
+    int pw = 0, ph = 0, dw = 0, dh = 0;
+    size_t dplane = 0;
+    for (int i = 0; i < n; ++i) {
+      const ImgOctave q = img_octave(sizes[2 * i], sizes[2 * i + 1], sift_noctaves(sizes[2 * i], sizes[2 * i + 1]), o);
+      if (q.pyr) pw = std::max(pw, q.w), ph = std::max(ph, q.h);
+      if (q.det) dw = std::max(dw, q.w), dh = std::max(dh, q.h), dplane = std::max(dplane, (size_t)q.w * q.h);
+    }
+    const dim3 pgrid((pw + 255) / 256, ph, n);
+    auto smooth = [&](int from, int to, const Taps &t) -> int {
+      ProfScope ps("sift_batch_pyramid", st);
+      sift_batch_smooth_kernel<true><<<pgrid, 256, 0, st>>>(d_imgs, o, from, t);
+      sift_batch_smooth_kernel<false><<<pgrid, 256, 0, st>>>(d_imgs, o, to, t);
+      SPV_HIP_CHECK(hipGetLastError());
+      return SPV_OK;
+    };
+    {
+      ProfScope ps("sift_batch_pyramid", st);
+      if (o < 0) sift_batch_upsample_kernel<<<pgrid, 256, 0, st>>>(d_imgs);
+      else sift_batch_downsample_kernel<<<pgrid, 256, 0, st>>>(d_imgs, o);
+    }
+    SPV_HIP_CHECK(hipGetLastError());
+    if (o < 0) SPV_TRY(smooth(0, 0, first_taps));
+    for (int s = 0; s < 5; ++s) SPV_TRY(smooth(s, s + 1, level_taps[s]));
+    if (dplane == 0) continue;  // no image of the group has a DoG interior at this octave
+    const int rows = 3 * (dh - 2);
+    const dim3 egrid((rows + 3) / 4, n);
+    const dim3 rgrid((unsigned)std::min<size_t>((dplane + 255) / 256, std::max(kPersistBlocks / n, kPersistFloor)), n);
+    const dim3 kgrid(std::max(kKeyBlocks / n, kKeyFloor), n);
+    {
+      ProfScope ps("sift_batch_detect", st);
+      sift_batch_extrema_kernel<false><<<egrid, 256, 0, st>>>(d_imgs, o);
+      sift_batch_scan_kernel<0><<<n, kScanThreads, 0, st>>>(d_imgs, o);
+      sift_batch_extrema_kernel<true><<<egrid, 256, 0, st>>>(d_imgs, o);
+      sift_batch_refine_kernel<<<rgrid, 256, 0, st>>>(d_imgs, o, sigma0);
+      sift_batch_scan_kernel<1><<<n, kScanThreads, 0, st>>>(d_imgs, o);
+      sift_batch_scatter_kernel<<<rgrid, 256, 0, st>>>(d_imgs, o);
+    }
+    SPV_HIP_CHECK(hipGetLastError());
+    {
+      ProfScope ps("sift_batch_describe", st);
+      sift_batch_gradient_kernel<<<dim3((dw + 255) / 256, dh, n), 256, 0, st>>>(d_imgs, o);
+      sift_batch_orientation_kernel<<<kgrid, 64, 0, st>>>(d_imgs, o);
+      sift_batch_scan_kernel<2><<<n, kScanThreads, 0, st>>>(d_imgs, o);
+      sift_batch_descriptor_kernel<<<kgrid, 64, 0, st>>>(d_imgs, o);
+    }
+    SPV_HIP_CHECK(hipGetLastError());
+  }
+  sift_batch_count_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_imgs, n);
+  SPV_HIP_CHECK(hipGetLastError());
+  return SPV_OK;
+}
+
+// The scratch of a call that returns before its kernels: back to the cache behind them, on every way out.
+struct ReleaseAfter {
+  DevBuf &b;
+  hipStream_t st;
+  ~ReleaseAfter() { b.release_after(st); }
+};
+
+}  // namespace
+
+int sift_batch_run(const float *d_images, const int32_t *sizes, int nimg, void *d_ws, size_t ws_bytes, float *d_table,
+                   const long long *cap_off, int32_t *d_counts, hipStream_t st) {
+  SiftBatchPlan plan;
+  SPV_TRY(sift_batch_plan(sizes, nimg, ws_bytes, &plan));
+  SPV_TRY(sift_batch_check_offsets(cap_off, nimg, "cap_off"));
+  if (nimg == 0) return SPV_OK;
+  if (!d_images || !d_ws || !d_counts || (cap_off[nimg] > 0 && !d_table)) return set_error(SPV_ERR_INVALID, "null pointer");
+  if (ws_bytes < plan.min_bytes)
+    return set_error(SPV_ERR_INVALID, "workspace %zu bytes, the largest image alone needs %zu", ws_bytes, plan.min_bytes);
+  // the records of all images, one upload; every group's slices start over at d_ws, which stream order allows
+  std::vector<SiftImg> imgs((size_t)nimg);
+  size_t pix = 0;
+  int i = 0;
+  for (const auto &g : plan.groups) {
+    char *ws = static_cast<char *>(d_ws);
+    for (; i < g.first + g.second; ++i) {
+      const int wid = sizes[2 * i], hgt = sizes[2 * i + 1];
+      const SiftLayout l = sift_layout(wid, hgt);
+      char *scratch = ws + l.o_scratch;
+      imgs[i] = SiftImg{d_images + pix,
+                        reinterpret_cast<int *>(ws + l.o_ctr),
+                        reinterpret_cast<float *>(ws + l.o_L),
+                        scratch,
+                        reinterpret_cast<int *>(scratch + l.o_cflag),
+                        reinterpret_cast<int *>(scratch + l.o_coff),
+                        reinterpret_cast<KeyRec *>(scratch + l.o_crec),
+                        reinterpret_cast<int *>(ws + l.o_rowcnt),
+                        reinterpret_cast<int *>(ws + l.o_rowoff),
+                        reinterpret_cast<KeyRec *>(ws + l.o_kp),
+                        reinterpret_cast<double *>(ws + l.o_ang),
+                        reinterpret_cast<int *>(ws + l.o_nang),
+                        reinterpret_cast<int *>(ws + l.o_row),
+                        d_table + (size_t)cap_off[i] * 132,
+                        d_counts + i,
+                        l.N,
+                        wid,
+                        hgt,
+                        sift_noctaves(wid, hgt),
+                        (int)(cap_off[i + 1] - cap_off[i])};
+      pix += (size_t)wid * hgt;
+      ws += l.total;
+    }
+  }
+  DevBuf recs;
+  SPV_TRY(recs.alloc(imgs.size() * sizeof(SiftImg)));
+  ReleaseAfter release{recs, st};
+  // (pageable source: the copy has left `imgs` when the call returns)
+  SPV_HIP_CHECK(hipMemcpyAsync(recs.p, imgs.data(), imgs.size() * sizeof(SiftImg), hipMemcpyHostToDevice, st));
+  for (const auto &g : plan.groups)
+    SPV_TRY(sift_batch_group(recs.as<SiftImg>() + g.first, sizes + 2 * (size_t)g.first, g.second, st));
+  return SPV_OK;
+}
+
+int sift_batch_pack_run(const float *d_table, const long long *cap_off, const long long *seg_off, int nimg,
+                        float *d_packed, float *d_geom, uint8_t *d_desc, hipStream_t st) {
+  if (nimg < 0) return set_error(SPV_ERR_INVALID, "negative image count");
+  SPV_TRY(sift_batch_check_offsets(cap_off, nimg, "cap_off"));
+  SPV_TRY(sift_batch_check_offsets(seg_off, nimg, "seg_off"));
+  for (int i = 0; i < nimg; ++i)
+    if (seg_off[i + 1] - seg_off[i] > cap_off[i + 1] - cap_off[i])
+      return set_error(SPV_ERR_INVALID, "segment %d: %lld rows, its region holds %lld", i, seg_off[i + 1] - seg_off[i],
+                       cap_off[i + 1] - cap_off[i]);
+  if (!d_packed && !d_geom && !d_desc) return set_error(SPV_ERR_INVALID, "no output is wanted");
+  const long long total = seg_off[nimg];
+  if (total == 0) return SPV_OK;
+  if (!d_table) return set_error(SPV_ERR_INVALID, "null pointer");
+  std::vector<long long> offs(cap_off, cap_off + nimg);
+  offs.insert(offs.end(), seg_off, seg_off + nimg + 1);
+  DevBuf tab;
+  SPV_TRY(tab.alloc(offs.size() * sizeof(long long)));
+  ReleaseAfter release{tab, st};
+  // (pageable source: the copy has left `offs` when the call returns)
+  SPV_HIP_CHECK(hipMemcpyAsync(tab.p, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+  ProfScope ps("sift_batch_pack", st);
+  sift_batch_pack_kernel<<<(unsigned)((total * 32 + 255) / 256), 256, 0, st>>>(tab.as<long long>(), nimg, d_table, d_packed,
+                                                                               d_geom, d_desc);
   SPV_HIP_CHECK(hipGetLastError());
   return SPV_OK;
 }

@@ -939,3 +939,153 @@ def sift(im_tensor, workspace=None):
             return table[:n]
         cap = n
     raise AssertionError("unreachable: the second pass is sized to the true count")
+
+
+def _sift_sizes(sizes):
+    """sizes -> int32[nimg, 2] = (wid, hgt); ValueError for what spv_sift_batch_plan would reject."""
+    sz = np.asarray(sizes)
+    if sz.size == 0:
+        sz = np.zeros((0, 2), np.int32)
+    if sz.ndim != 2 or sz.shape[1] != 2 or sz.dtype.kind not in "iu":
+        raise ValueError("sizes must be integers of shape [nimg, 2] = (wid, hgt)")
+    if sz.size and (int(sz.min()) < 1 or int(sz.max()) > 8192):
+        raise ValueError("every image side must be in [1, 8192]")
+    return np.ascontiguousarray(sz, dtype=np.int32)
+
+
+def sift_batch_plan(sizes, ws_bytes=0, want_groups=False):
+    """How sift_batch_into() cuts a call into groups for a workspace of ws_bytes (0: as much as needed;
+    spv_sift_batch_plan, host only, no device touched): dict of groups, workspace_bytes (with which only the
+    65535-image cap closes a group), min_workspace_bytes (the largest image's slice, the least that works) and
+    pixels.  With want_groups also int32[groups, 2] = (first image, images)."""
+    sz = _sift_sizes(sizes)
+    out = (ct.c_longlong * 4)()
+    check(clib.spv_sift_batch_plan(sz.ctypes.data, len(sz), int(ws_bytes), out, None, 0))
+    plan = dict(groups=int(out[0]), workspace_bytes=int(out[1]), min_workspace_bytes=int(out[2]), pixels=int(out[3]))
+    if want_groups:
+        groups = np.empty((plan["groups"], 2), np.int32)
+        check(clib.spv_sift_batch_plan(sz.ctypes.data, len(sz), int(ws_bytes), out, groups.ctypes.data, len(groups)))
+        return plan, groups
+    return plan
+
+
+def _offsets(off, n, name):
+    off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+    if off.size != n + 1 or off[0] != 0 or np.any(np.diff(off) < 0) or int(off[-1]) >= 2 ** 31:
+        raise ValueError("%s must be [nimg + 1], start at 0, never decrease and end below 2^31" % name)
+    return off
+
+
+def sift_batch_into(images, sizes, table, cap_off, counts, workspace=None):
+    """vlfeat-exact SIFT of many images in one chain of launches (spv_sift_batch_device): images float32 CUDA
+    tensor holding the images back to back, image i row-major [hgt_i, wid_i] with sizes[i] = (wid_i, hgt_i);
+    image i owns rows cap_off[i]:cap_off[i + 1] of table (float32 [cap_off[-1], 132]), of which the first
+    min(n_i, capacity_i) are written, and counts (int32 [nimg]) receives the true row counts n_i.  workspace:
+    a Workspace, or a uint8 CUDA tensor whose size decides the groups (at least sift_batch_plan's
+    min_workspace_bytes).  Asynchronous on the current stream but for the upload of the per-image table."""
+    sz = _sift_sizes(sizes)
+    cap = _offsets(cap_off, len(sz), "cap_off")
+    _need(images, torch.float32, "images")
+    _need(table, torch.float32, "table")
+    _need(counts, torch.int32, "counts")
+    if images.numel() != int((sz[:, 0].astype(np.int64) * sz[:, 1]).sum()):
+        raise ValueError("images must hold exactly the pixels of sizes")
+    if table.dim() != 2 or table.shape[1] != 132 or table.shape[0] < int(cap[-1]) or counts.numel() < len(sz):
+        raise ValueError("table must be [cap_off[-1], 132] and counts hold one int32 per image")
+    with _on_device_of(images, table, counts) as stream:
+        if isinstance(workspace, torch.Tensor):
+            _need(workspace, torch.uint8, "workspace")
+            ws = workspace
+        else:
+            ws = (workspace or _default_ws).get(clib.spv_sift_batch_workspace_bytes(sz.ctypes.data, len(sz)), images.device)
+        check(clib.spv_sift_batch_device(images.data_ptr(), sz.ctypes.data, len(sz), ws.data_ptr(), ws.numel(),
+                                         table.data_ptr(), cap.ctypes.data, counts.data_ptr(), stream))
+
+
+def sift_batch_pack(table, cap_off, seg_off, want_packed=True, want_split=False):
+    """The regions of a sift_batch_into() table packed back to back (spv_sift_batch_pack_device): rows
+    cap_off[i]:cap_off[i] + (seg_off[i + 1] - seg_off[i]) go to rows seg_off[i]:seg_off[i + 1].  Returns the
+    wanted ones of (packed float32 [total, 132], geom float32 [total, 4], desc uint8 [total, 128]), geom and desc
+    as split_sift_table gives them."""
+    _need(table, torch.float32, "table")
+    seg = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
+    cap = _offsets(cap_off, seg.size - 1, "cap_off")
+    seg = _offsets(seg, seg.size - 1, "seg_off")
+    total = int(seg[-1])
+    packed = torch.empty((total, 132), dtype=torch.float32, device=table.device) if want_packed else None
+    geom = torch.empty((total, 4), dtype=torch.float32, device=table.device) if want_split else None
+    desc = torch.empty((total, 128), dtype=torch.uint8, device=table.device) if want_split else None
+    if not (want_packed or want_split):
+        raise ValueError("neither the packed table nor its split is wanted")
+    with _on_device_of(table) as stream:
+        if total == 0:   # nothing to copy (and an empty tensor has no address to give)
+            return ((packed,) if want_packed else ()) + ((geom, desc) if want_split else ())
+        check(clib.spv_sift_batch_pack_device(table.data_ptr(), cap.ctypes.data, seg.ctypes.data, seg.size - 1,
+                                              packed.data_ptr() if want_packed else None,
+                                              geom.data_ptr() if want_split else None,
+                                              desc.data_ptr() if want_split else None, stream))
+    return ((packed,) if want_packed else ()) + ((geom, desc) if want_split else ())
+
+
+def sift_batch(images, capacity=None, workspace=None, max_workspace_bytes=None, want_split=False):
+    """vlfeat-exact SIFT of a list of 2-D float32 CUDA tensors of any sizes, in one chain of launches.  Returns
+    (table float32 [total, 132], seg_off int64 ndarray [n + 1]): image i's table is rows seg_off[i]:seg_off[i + 1],
+    bit for bit sift(images[i]); with want_split (geom float32 [total, 4], desc uint8 [total, 128], seg_off)
+    instead, what l1k2_batch and match_coordinates_batch take.  capacity: rows reserved per image (an int, or
+    one per image; default sift()'s guess).  The counts are read back once; the images whose count exceeded
+    their capacity are run again, together, with exact capacities -- the same bits either way.
+    max_workspace_bytes caps the scratch (at least the largest image's need), at the price of several groups."""
+    n = len(images)
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dim() != 2:
+            raise TypeError("Only 2d images are supported.")
+    if n == 0:
+        raise ValueError("sift_batch needs at least one image")
+    sizes = _sift_sizes([(im.shape[1], im.shape[0]) for im in images])
+    if capacity is None:
+        caps = [max(1024, min(int(w) * int(h) // 16, 1 << 20)) for w, h in sizes]
+    else:
+        caps = [int(c) for c in np.broadcast_to(np.asarray(capacity, dtype=np.int64), (n,))]
+    dev = images[0].device
+
+    def run(which, caps):
+        """(table, cap_off, counts on the host) of images[which] with the capacities caps."""
+        flat = torch.cat([images[i].to(torch.float32).reshape(-1) for i in which])
+        cap_off = np.concatenate([[0], np.cumsum(caps, dtype=np.int64)]).astype(np.int64)
+        table = torch.empty((int(cap_off[-1]), 132), dtype=torch.float32, device=dev)
+        counts = torch.zeros(len(which), dtype=torch.int32, device=dev)
+        ws = workspace
+        if max_workspace_bytes is not None:
+            plan = sift_batch_plan(sizes[which])
+            nbytes = max(min(int(max_workspace_bytes), plan["workspace_bytes"]), plan["min_workspace_bytes"])
+            buf = workspace if isinstance(workspace, torch.Tensor) else (workspace or _default_ws).get(nbytes, dev)
+            ws = buf[:nbytes]
+        sift_batch_into(flat, sizes[which], table, cap_off, counts, ws)
+        return table, cap_off, counts.cpu().numpy().astype(np.int64)
+
+    every = list(range(n))
+    table, cap_off, counts = run(every, caps)
+    seg_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    short = [i for i in every if counts[i] > caps[i]]
+    if not short:
+        out = sift_batch_pack(table, cap_off, seg_off, want_packed=not want_split, want_split=want_split)
+        return out + (seg_off,)
+    # the complete regions packed, the short images again with exact capacities, each into its place
+    fit = counts.copy()
+    fit[short] = 0
+    part_off = np.concatenate([[0], np.cumsum(fit)]).astype(np.int64)
+    table2, cap_off2, counts2 = run(short, [int(counts[i]) for i in short])
+    assert np.array_equal(counts2, counts[short])
+    parts = sift_batch_pack(table, cap_off, part_off, want_packed=not want_split, want_split=want_split)
+    parts2 = sift_batch_pack(table2, cap_off2, cap_off2, want_packed=not want_split, want_split=want_split)
+    outs = []
+    for a, b in zip(parts, parts2):
+        o = torch.empty((int(seg_off[-1]),) + tuple(a.shape[1:]), dtype=a.dtype, device=dev)
+        for i in every:
+            if i in short:
+                k = short.index(i)
+                o[seg_off[i]:seg_off[i + 1]] = b[cap_off2[k]:cap_off2[k + 1]]
+            else:
+                o[seg_off[i]:seg_off[i + 1]] = a[part_off[i]:part_off[i + 1]]
+        outs.append(o)
+    return tuple(outs) + (seg_off,)
