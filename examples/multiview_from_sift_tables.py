@@ -4,7 +4,8 @@ examples/essential_from_sift_tables.py runs matching, RANSAC and triangulation f
 example/ex01_essential_estimation.py does.  A multi-view front-end has N views and up to N (N - 1) / 2 pairs; this file
 runs all of them through the many-pairs forms of the same steps, with every intermediate resident in HBM:
 
-    l1k2_batch               exact L1 2-NN of every (query view, database view) pair
+    l1k2_batch               exact L1 2-NN of every (query view, database view) pair; or, with --matcher cascade,
+    cascade_batch            the cascade hash + L1 refine of every pair, each view coded and bucket-sorted once
     ratio_test               over the concatenated result
     match_coordinates_batch  matches -> per-pair homogeneous coordinates and pair_off
     ransac_fit_batch         one essential matrix and camera per pair, and the inlier mask over all rows
@@ -15,7 +16,7 @@ they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 1
 here, so that the scene and the cameras are known; extracting them from images is the library's sift_batch, the step
 before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
-    python examples/multiview_from_sift_tables.py [--images 6] [--points 2000]
+    python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}]
 """
 import argparse
 import os
@@ -68,8 +69,11 @@ def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_f
     return tables, K
 
 
-def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, maximum_tries=2000, seed=1):
-    """SIFT tables (a list of float32 [n_v,132] arrays) -> one upload -> split -> exact L1 2-NN of all pairs -> ratio
+def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, maximum_tries=2000, seed=1,
+                       matcher='l1k2', hash_seed=0x5eed):
+    """SIFT tables (a list of float32 [n_v,132] arrays) -> one upload -> split -> exact L1 2-NN of all pairs (or,
+    matcher='cascade', the cascade hash of all pairs: descriptors normalised per view as the reference's front-end
+    does, m by its rule from the largest view, n = 2, g = 2, hyperplanes from hash_seed) -> ratio
     test -> per-pair coordinates -> calibration -> one RANSAC fit per pair -> triangulation of every pair's inliers
     with that pair's camera.  Returns a dict: pairs int32 [npairs,2] (query view, database view), pair_off (matches
     per pair), fits (the `ransac_fit` dicts), out_off (points per pair), X (CUDA float64 [total,4], rows
@@ -82,7 +86,16 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     geom, desc = spv.split_sift_table(table)
     nv = len(tables)
     pairs = np.array([(q, d) for d in range(nv) for q in range(d + 1, nv)], np.int32).reshape(-1, 2)
-    idx, dist, _ = spv.l1k2_batch(desc, seg, pairs)
+    if matcher == 'cascade':
+        from spectavi_amd import feature
+        m = feature.auto_hash_bit_rate(*[max(len(t) for t in tables)] * 2)
+        if m < 4:
+            raise ValueError("tables too small for the cascade hash (the front-end falls back to brute force)")
+        rows = torch.cat([spv.normalize(desc[a:b].to(torch.float32)) for a, b in zip(seg[:-1], seg[1:])])
+        hd = torch.from_numpy(feature.generate_hash_dict(hash_seed, rows.shape[1], m, 2)).to(table.device)
+        idx, dist, _ = spv.cascade_batch(rows, seg, pairs, hd, g=2)
+    else:
+        idx, dist, _ = spv.l1k2_batch(desc, seg, pairs)
     matches, count = spv.ratio_test(idx, dist, min_ratio)
     p0, p1, pair_off = spv.match_coordinates_batch(geom, seg, pairs, matches, count)
     n = int(pair_off[-1])
@@ -116,13 +129,14 @@ def main():
     ap.add_argument("--images", type=int, default=6, help="views of the scene")
     ap.add_argument("--points", type=int, default=2000, help="scene points seen in every view")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--matcher", default="l1k2", choices=["l1k2", "cascade"], help="exact brute force, or the cascade hash")
     a = ap.parse_args()
     import torch
     tables, K = synthetic_sift_views(a.seed, a.images, a.points)
     for rep in range(2):  # the second round is the warm one
         torch.cuda.synchronize()
         s = time.perf_counter()
-        out = multiview_pipeline(tables, K)
+        out = multiview_pipeline(tables, K, matcher=a.matcher)
         torch.cuda.synchronize()
         dt = time.perf_counter() - s
     report(out)

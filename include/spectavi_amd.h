@@ -156,7 +156,7 @@ const char *spv_version(void);
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
  * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
  * "ann_merge", "ann_rerank", "cascade_project",
- * "cascade_buckets", "cascade_probe_refine", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "ransac_batch_score",
+ * "cascade_buckets", "cascade_probe_refine", "cascade_batch_project", "cascade_batch_buckets", "cascade_batch_probe", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "ransac_batch_score",
  * "ransac_batch_reduce",
  * "gather_match_coords_batch") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
@@ -439,6 +439,15 @@ int spv_ann_l2(const float *x, const float *y, int xrows, int yrows, int dim, in
 int spv_nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, int dim, int m,
                           int n, int g, const float *dict, uint64_t *idx, float *dist,
                           int32_t *ncand);
+
+/* The cascade-hash 2-NN of many (query set, database set) pairs in one call: spv_cascade_batch_device (section 3,
+ * which states the contract) through host pointers.  rows float32[seg_off[nseg], dim], dict float32[n, dim, m],
+ * idx uint64[out_rows,2], dist float32[out_rows,2], ncand (may be NULL) int32[out_rows]; out_rows = the query-set
+ * rows summed over pairs.  One device: the first one selected by spv_set_device / spv_set_devices.  An addition:
+ * the reference has no such symbol. */
+int spv_nn_cascading_hash_batch(const float *rows, const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                                const int32_t *pairs, int npairs, const float *dict, uint64_t *idx, float *dist,
+                                int32_t *ncand);
 
 /* Fill dict[n*dim*m] exactly as the reference's generate_hash_dict would from
  * std::mt19937(seed) + std::normal_distribution<float>(0,1). */
@@ -868,6 +877,49 @@ int spv_cascade_device(const float *d_x, const float *d_y, int xrows, int yrows,
                        int m, int n, int g, const float *d_dict, uint64_t *d_idx,
                        float *d_dist, int32_t *d_ncand, void *d_ws, size_t ws_bytes,
                        void *stream);
+
+/* The cascade-hash 2-NN of a collection of (query set, database set) pairs in one chain of launches whose length
+ * depends neither on the number of pairs nor on the number of sets (cascade_batch.hip).  Every row of the
+ * collection is projected, sign-coded, imaged and bucket-sorted once, whatever number of pairs its set takes part in.
+ *   rows     float32[total_rows, dim]: the tables of nseg sets back to back.
+ *   seg_off  host long long[nseg + 1], non-decreasing, seg_off[0] = 0, seg_off[nseg] = total_rows < 2^31; set s is
+ *            rows [seg_off[s], seg_off[s + 1]) and may be empty (the seg_off of spv_l1k2_batch_device).
+ *   dict     float32[n, dim, m], one dictionary for the whole collection; g as for spv_cascade_device.
+ *   pairs    host int32[npairs, 2] = (query set, database set), in any order, repeats and self pairs allowed.
+ *   idx      uint64[out_rows, 2], dist float32[out_rows, 2], ncand (may be NULL) int32[out_rows]; out_rows = the
+ *            query-set row counts summed over pairs.  Pair p owns the rows from the sum over the pairs before it, in
+ *            query-row order; idx is the row number inside the database set; a missing neighbour is
+ *            ((size_t)-1, 2147483648.0f); an empty database set gives two of them and ncand 0.
+ * Per pair the rows are bit for bit what spv_cascade_device(database set, query set) writes: the same candidate
+ * set, its two smallest distinct (dist, idx) in lexicographic order, the same visited count.  Limits: dim a
+ * positive multiple of 16 and <= 256, m in [1,31], n >= 1, g in [0, min(m,16)], nseg >= 0, npairs >= 0, set numbers
+ * in [0, nseg), nseg * n <= 65535 (the scan kernels take the (set, table) as a grid row), at most 2^31 - 1 work
+ * items (64 query rows of one pair each), d_rows, d_dict and d_ws 16-byte aligned, d_idx 8-byte, d_dist and d_ncand
+ * 4-byte, ws_bytes at least the workspace bytes.  Outside them SPV_ERR_INVALID, nothing launched, no output
+ * touched.  One device.
+ *
+ * spv_cascade_batch_plan: host only, touches no device.  out = {work items, out_rows, bucket bits hb, workspace
+ * bytes}; items may be NULL, otherwise int32[items_cap, 3] receives the first min(work items, items_cap) work items,
+ * one workgroup of the probe each, as (pair, first query row within the query set, query rows): exactly the list
+ * the device call launches, in its order; together they cover every out row once.  hb = min(m, 22, max(12,
+ * ceil(log2(rows of the largest set)))), lowered until the nseg * n tables of 2^hb + 1 words fit 1 GiB; with hb < m
+ * the probe compares the full code of every bucket entry, so the results do not depend on hb.  SPV_ERR_INVALID
+ * leaves out and items untouched.  spv_cascade_batch_workspace_bytes: out[3] (0 for arguments the plan rejects).
+ *
+ * spv_cascade_batch_device: seg_off and pairs are read before the call returns.  The call may wait for the upload
+ * of its small tables (work items, seg_off), which is queued on `stream`; it never waits for its kernels, and
+ * everything else is asynchronous on `stream`.  Kernel names for spv_profile_read, one bracket per call each:
+ * "cascade_batch_project" (dictionary repack and the projection of all rows), "cascade_batch_buckets" (histogram,
+ * scan, fill), "cascade_batch_probe" (probe and refine of every out row).  spv_ratio_test and
+ * spv_ratio_test_device (dist_is_float = 1) apply to the concatenated output as it stands: their matches are (out
+ * row, row within the database set). */
+int spv_cascade_batch_plan(const long long *seg_off, int nseg, int dim, int m, int n, int g, const int32_t *pairs,
+                           int npairs, long long out[4], int32_t *items, long long items_cap);
+size_t spv_cascade_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                                         const int32_t *pairs, int npairs);
+int spv_cascade_batch_device(const float *d_rows, const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                             const int32_t *pairs, int npairs, const float *d_dict, uint64_t *d_idx, float *d_dist,
+                             int32_t *d_ncand, void *d_ws, size_t ws_bytes, void *stream);
 
 /* P0,P1 are HOST pointers (24 doubles, passed by value to the kernel);
  * d_x,d_xp double[npt,3]; d_dst double[npt,4] (triangulate) / double[npt] (error). */

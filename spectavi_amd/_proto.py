@@ -84,6 +84,7 @@ PROTOTYPES = {
     "spv_nn_bruteforce": (i, [vp, vp, i, i, i, i, i, f, vp, vp]),
     "spv_ann_l2": (i, [vp, vp, i, i, i, i, i, vp, vp]),
     "spv_nn_cascading_hash": (i, [f32a, f32a] + [i] * 6 + [f32a, u64a, f32a, vp]),
+    "spv_nn_cascading_hash_batch": (i, [vp, vp] + [i] * 5 + [vp, i] + [vp] * 4),
     "spv_generate_hash_dict": (i, [u32, i, i, i, f32a]),
     "spv_set_hash_seed": (None, [u32, i]),
     "spv_dlt_score_hypotheses": (i, [f64a, f64a, i, i, f64a, f64a, d, i32a, vp]),
@@ -136,6 +137,9 @@ PROTOTYPES = {
     "spv_cascade_workspace_bytes": (sz, [i] * 6),
     "spv_cascade_plan": (i, [i] * 6 + [pi]),
     "spv_cascade_device": (i, [vp, vp] + [i] * 6 + [vp] * 5 + [sz, vp]),
+    "spv_cascade_batch_plan": (i, [vp] + [i] * 5 + [vp, i, pll, vp, ll]),
+    "spv_cascade_batch_workspace_bytes": (sz, [vp] + [i] * 5 + [vp, i]),
+    "spv_cascade_batch_device": (i, [vp, vp] + [i] * 5 + [vp, i] + [vp] * 5 + [sz, vp]),
     "spv_dlt_triangulate_device": (i, _dlt_device),
     "spv_dlt_reprojection_error_device": (i, _dlt_device),
     "spv_dlt_triangulate_batch_device": (i, [vp, vp, vp, i] + [vp] * 7 + [ll, vp, vp, vp]),

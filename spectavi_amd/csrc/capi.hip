@@ -543,6 +543,33 @@ int host_cascade(const float *x, const float *y, int xrows, int yrows, int dim, 
   });
 }
 
+// The many-pairs cascade through host pointers, on the first selected device (no sharding): the whole of rows and
+// the dictionary up, one cascade_batch_run, the results back.
+int host_cascade_batch(const float *rows, const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                       const int32_t *pairs, int npairs, const float *dict, uint64_t *idx, float *dist, int32_t *ncand) {
+  CascadeBatchPlan p;
+  SPV_TRY(cascade_batch_plan(seg_off, nseg, dim, m, n, g, pairs, npairs, &p));
+  if (p.out_rows == 0) return SPV_OK;
+  if (!rows || !dict || !idx || !dist) return set_error(SPV_ERR_INVALID, "null pointer");
+  const int dev = device_list()[0];
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
+  const size_t xb = (size_t)p.total_rows * dim * sizeof(float), db = (size_t)n * dim * m * sizeof(float);
+  const size_t ib = (size_t)p.out_rows * 2 * sizeof(uint64_t), sb = (size_t)p.out_rows * 2 * sizeof(float);
+  const size_t nb = (size_t)p.out_rows * sizeof(int32_t);
+  HostPrefault touch_idx(idx, ib, {{rows, xb}});
+  DevBuf dx, dd, di, dds, dn, ws;
+  SPV_TRY(alloc_all({{&dx, xb}, {&dd, db}, {&di, ib}, {&dds, sb}, {&dn, nb}, {&ws, p.total_bytes}}));
+  SPV_TRY(dx.copy_in(rows, xb, st));
+  SPV_TRY(dd.copy_in(dict, db, st));
+  SPV_TRY(cascade_batch_run(dx.as<float>(), seg_off, nseg, dim, m, n, g, pairs, npairs, dd.as<float>(), di.as<uint64_t>(),
+                            dds.as<float>(), dn.as<int32_t>(), ws.p, p.total_bytes, st));
+  touch_idx.wait();
+  SPV_TRY(dds.copy_out(dist, sb, st));
+  if (ncand) SPV_TRY(dn.copy_out(ncand, nb, st));
+  return download(dev, idx, di.p, ib, st);
+}
+
 int host_dlt_one(int dev, const double *P0, const double *P1, int npt, const double *x,
                  const double *xp, double *dst, bool want_error) {
   if (npt < 0) return set_error(SPV_ERR_INVALID, "negative point count");
@@ -1248,6 +1275,12 @@ int spv_nn_cascading_hash(const float *x, const float *y, int xrows, int yrows, 
   return host_api([&] { return host_cascade(x, y, xrows, yrows, dim, m, n, g, dict, idx, dist, ncand); });
 }
 
+int spv_nn_cascading_hash_batch(const float *rows, const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                                const int32_t *pairs, int npairs, const float *dict, uint64_t *idx, float *dist,
+                                int32_t *ncand) {
+  return host_api([&] { return host_cascade_batch(rows, seg_off, nseg, dim, m, n, g, pairs, npairs, dict, idx, dist, ncand); });
+}
+
 int spv_generate_hash_dict(uint32_t seed, int dim, int m, int n, float *dict) {
   clear_error();
   if (dim <= 0 || m <= 0 || n <= 0 || !dict) return set_error(SPV_ERR_INVALID, "bad dict shape");
@@ -1771,6 +1804,43 @@ int spv_cascade_plan(int xrows, int yrows, int dim, int m, int n, int g, int out
                      p.ru,     p.wpe,   p.shift, p.full,  p.sorted,    p.qhist_fused};
   std::copy(v, v + 12, out);
   return SPV_OK;
+}
+
+int spv_cascade_batch_plan(const long long *seg_off, int nseg, int dim, int m, int n, int g, const int32_t *pairs,
+                           int npairs, long long out[4], int32_t *items, long long items_cap) {
+  return api([&] {
+    if (!out || (items && items_cap < 0)) return set_error(SPV_ERR_INVALID, "null output or negative items_cap");
+    CascadeBatchPlan p;
+    SPV_TRY(cascade_batch_plan(seg_off, nseg, dim, m, n, g, pairs, npairs, &p));
+    const long long cnt = (long long)p.items.size();
+    out[0] = cnt;
+    out[1] = p.out_rows;
+    out[2] = p.hb;
+    out[3] = (long long)p.total_bytes;
+    for (long long e = 0; items && e < std::min(cnt, items_cap); ++e) {
+      const CascadeBatchItem &it = p.items[(size_t)e];
+      const int32_t row[3] = {it.pair, it.y0, it.yrows};
+      std::copy(row, row + 3, items + 3 * e);
+    }
+    return (int)SPV_OK;
+  });
+}
+
+size_t spv_cascade_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                                         const int32_t *pairs, int npairs) {
+  CascadeBatchPlan p;
+  const int st = guard([&] { return cascade_batch_plan(seg_off, nseg, dim, m, n, g, pairs, npairs, &p); });
+  if (st != SPV_OK) clear_error();
+  return st == SPV_OK ? p.total_bytes : 0;
+}
+
+int spv_cascade_batch_device(const float *d_rows, const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                             const int32_t *pairs, int npairs, const float *d_dict, uint64_t *d_idx, float *d_dist,
+                             int32_t *d_ncand, void *d_ws, size_t ws_bytes, void *stream) {
+  return api([&] {
+    return cascade_batch_run(d_rows, seg_off, nseg, dim, m, n, g, pairs, npairs, d_dict, d_idx, d_dist, d_ncand, d_ws,
+                             ws_bytes, static_cast<hipStream_t>(stream));
+  });
 }
 
 int spv_l1k2_gathered_device(int ndev, const int *devices, const uint8_t *const *d_x, const uint8_t *const *d_y,

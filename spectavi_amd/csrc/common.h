@@ -281,6 +281,33 @@ int cascade_run(const float *d_x, const float *d_y, int xrows, int yrows, int di
                 int g, const float *d_dict, uint64_t *d_idx, float *d_dist, int32_t *d_ncand,
                 void *d_ws, size_t ws_bytes, hipStream_t stream);
 
+// ---- cascade hash of many set pairs in one chain of launches (cascade_batch.hip) --------
+constexpr int kCascadeBatchMaxDim = 256;        // the limit of the other many-pairs forms
+constexpr int kCascadeBatchMaxTables = 65535;   // nseg * n: the scan kernels take the (set, table) as blockIdx.y
+constexpr int kCascadeBatchItemRows = 64;       // query rows per work item
+// One workgroup's share of a collection: rows [y0, y0 + yrows) of one pair's query set.
+struct CascadeBatchItem {
+  int32_t pair, y0, yrows;
+};
+// Everything cascade_batch_run launches for a collection.
+struct CascadeBatchPlan {
+  CascadePlan proj;  // the projection of all rows in the query form: family, pa, pb, gmax_q, proj_rows, mc
+  int hb;            // bucket bits of every (set, table); hb < m: the probe compares full codes
+  long long total_rows, out_rows;
+  std::vector<long long> out_off;       // [npairs + 1]: pair p owns out rows [out_off[p], out_off[p + 1])
+  std::vector<CascadeBatchItem> items;  // the probe's grid, in pair order
+  // workspace: byte offsets, in this order.  The device form of `items` followed by seg_off as uint32, the repacked
+  // dictionary, the uint8 image, sign codes / masks / ranks / order [n][total_rows], the bucket offsets
+  // [nseg * n][2^hb + 1], the scan's segment sums.
+  size_t off_tables, off_dict, off_img, off_codes, off_masks, off_ranks, off_order, off_bstart, off_segsum, total_bytes;
+};
+// SPV_ERR_INVALID (message set, *p untouched) outside the limits of include/spectavi_amd.h; host only
+int cascade_batch_plan(const long long *seg_off, int nseg, int dim, int m, int n, int g, const int32_t *pairs,
+                       int npairs, CascadeBatchPlan *p);
+int cascade_batch_run(const float *d_rows, const long long *seg_off, int nseg, int dim, int m, int n, int g,
+                      const int32_t *pairs, int npairs, const float *d_dict, uint64_t *d_idx, float *d_dist,
+                      int32_t *d_ncand, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
 // ---- DLT (dlt.hip) ------------------------------------------------------------------
 int dlt_run(const double *P0, const double *P1, long long npt, const double *d_x,
             const double *d_xp, double *d_dst, bool want_error, hipStream_t stream);

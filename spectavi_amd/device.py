@@ -439,6 +439,70 @@ def cascade(x, y, hash_dict, g=2, workspace=None, want_ncand=False):
     return (idx, dist, ncand) if want_ncand else (idx, dist)
 
 
+def _cascade_batch_args(seg_off, pairs, total_rows, dim, m, n, g):
+    """_batch_args plus the cascade's own limits, as ValueError before any device work."""
+    seg, prs, out_off = _batch_args(seg_off, pairs, total_rows, dim)
+    if not 1 <= m <= 31:
+        raise ValueError("hash bit rate m must be in [1, 31]")
+    if n < 1 or not 0 <= g <= min(m, 16):
+        raise ValueError("need n >= 1 and 0 <= g <= min(m, 16)")
+    if (seg.size - 1) * n > 65535:
+        raise ValueError("the many-pairs cascade takes nseg * n <= 65535 (%d sets, %d tables)" % (seg.size - 1, n))
+    return seg, prs, out_off
+
+
+def cascade_batch_plan(seg_off, pairs, dim, m, n, g, want_items=False):
+    """The launch plan cascade_batch() follows for a collection (spv_cascade_batch_plan; host only, no device
+    touched): dict of items (work items = workgroups of the probe), out_rows, hb (bucket bits of every (set,
+    table)), workspace_bytes and out_off (int64[npairs + 1]: pair p owns out rows [out_off[p], out_off[p + 1])).
+    With want_items also the work items themselves, int32[items, 3] = (pair, first query row within the query
+    set, query rows), in launch order."""
+    seg, prs, out_off = _cascade_batch_args(seg_off, pairs, None, dim, m, n, g)
+    out = (ct.c_longlong * 4)()
+    args = (seg.ctypes.data, seg.size - 1, dim, m, n, g, prs.ctypes.data, len(prs), out)
+    check(clib.spv_cascade_batch_plan(*args, None, 0))
+    plan = dict(items=int(out[0]), out_rows=int(out[1]), hb=int(out[2]), workspace_bytes=int(out[3]), out_off=out_off)
+    if want_items:
+        items = np.empty((plan["items"], 3), np.int32)
+        check(clib.spv_cascade_batch_plan(*args, items.ctypes.data, len(items)))
+        return plan, items
+    return plan
+
+
+def cascade_batch(rows, seg_off, pairs, hash_dict, g=2, workspace=None, want_ncand=False):
+    """Cascade-hash 2-NN of many set pairs on device, in a chain of launches whose length depends neither on the
+    number of pairs nor on the number of sets: rows float32 [total_rows, D] (CUDA tensor) holds the sets back to
+    back, set s = rows seg_off[s]:seg_off[s + 1]; pairs [npairs, 2] = (query set, database set); hash_dict
+    float32 [n, D, m], one for the collection.  Every row is projected, coded and bucket-sorted once.  Returns
+    (idx int64 [out_rows, 2] -- the ABI's size_t bits, -1 = no neighbour; the row number inside the database
+    set --, dist float32 [out_rows, 2], out_off int64 ndarray [npairs + 1][, ncand int32 [out_rows]]): pair p owns
+    rows out_off[p]:out_off[p + 1], each bit for bit cascade(database set, query set, hash_dict, g).
+    ratio_test() applies to the concatenated output as it stands.  Asynchronous on the current stream but for
+    the upload of the small tables."""
+    _need(rows, torch.float32, "rows")
+    _need(hash_dict, torch.float32, "hash_dict")
+    if rows.dim() != 2 or hash_dict.dim() != 3:
+        raise ValueError("rows must be [total_rows, dim], hash_dict [n, dim, m]")
+    total, dim = rows.shape
+    n, ddim, m = hash_dict.shape
+    if ddim != dim:
+        raise ValueError("hash_dict is %d wide, rows %d" % (ddim, dim))
+    seg, prs, out_off = _cascade_batch_args(seg_off, pairs, total, dim, m, n, g)
+    out_rows = int(out_off[-1])
+    idx = torch.empty((out_rows, 2), dtype=torch.int64, device=rows.device)
+    dist = torch.empty((out_rows, 2), dtype=torch.float32, device=rows.device)
+    ncand = torch.empty((out_rows,), dtype=torch.int32, device=rows.device) if want_ncand else None
+    nbytes = clib.spv_cascade_batch_workspace_bytes(seg.ctypes.data, seg.size - 1, dim, m, n, g, prs.ctypes.data,
+                                                    len(prs))
+    with _on_device_of(rows, hash_dict) as stream:
+        ws = (workspace or _default_ws).get(nbytes, rows.device)
+        check(clib.spv_cascade_batch_device(rows.data_ptr(), seg.ctypes.data, seg.size - 1, dim, m, n, g,
+                                            prs.ctypes.data, len(prs), hash_dict.data_ptr(), idx.data_ptr(),
+                                            dist.data_ptr(), ncand.data_ptr() if want_ncand else None, ws.data_ptr(),
+                                            ws.numel(), stream))
+    return (idx, dist, out_off, ncand) if want_ncand else (idx, dist, out_off)
+
+
 def _dlt(fn, P0, P1, x, xp, cols):
     _need(x, torch.float64, "x")
     _need(xp, torch.float64, "xp")

@@ -339,6 +339,61 @@ def nn_cascading_hash_with_dict(x, y, hash_dict, g=2, return_ncand=False):
     return idx, dist
 
 
+def nn_cascading_hash_batch(tables, hash_dict, pairs=None, g=2, return_ncand=False):
+    """
+    nn_cascading_hash_with_dict for many pairs of tables in one call (an addition: the reference has no such
+    function).  `tables` is a list of float32 arrays [rows_i, dim], one width for all; `hash_dict` float32
+    [n, dim, m], one for the collection; `pairs` a list of (query table, database table) numbers, by default
+    every i < j as (query j, database i).  Every table is projected and bucket-sorted once, whatever number of
+    pairs it takes part in.
+
+    Returns a list with one (nn_idx uint64 [rows, 2], nn_dist float32 [rows, 2][, ncand int32 [rows]]) per pair,
+    each what nn_cascading_hash_with_dict(tables[database], tables[query], hash_dict, g) returns.  The arrays of
+    the list are views of one concatenated result, to which spv_ratio_test applies as it stands.
+    """
+    tables = [np.ascontiguousarray(t, dtype=np.float32) for t in tables]
+    hash_dict = np.ascontiguousarray(hash_dict, dtype=np.float32)
+    if not tables:
+        raise ValueError("no tables")
+    dim = tables[0].shape[1] if tables[0].ndim == 2 else -1
+    if any(t.ndim != 2 or t.shape[1] != dim for t in tables):
+        raise ValueError("tables must be float32 arrays [rows, dim] of one width")
+    if hash_dict.ndim != 3 or hash_dict.shape[1] != dim:
+        raise ValueError("hash_dict must be float32 [n, dim, m] of the tables' width")
+    if dim <= 0 or dim % 16 != 0:
+        raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
+    if dim > 256:
+        raise ValueError("the many-pairs form takes dim <= 256 (dim=%d)" % dim)
+    ntab, _, m = hash_dict.shape
+    if not 1 <= m <= 31:
+        raise ValueError("hash bit rate m must be in [1, 31]")
+    if ntab < 1 or not 0 <= g <= min(m, 16):
+        raise ValueError("need n >= 1 and 0 <= g <= min(m, 16)")
+    n = len(tables)
+    if pairs is None:
+        pairs = [(j, i) for i in range(n) for j in range(i + 1, n)]
+    prs = np.asarray(pairs)
+    if prs.size == 0:
+        prs = np.zeros((0, 2), np.int32)
+    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
+        raise ValueError("pairs must be integers of shape [npairs, 2]")
+    if prs.size and (prs.min() < 0 or prs.max() >= n):
+        raise ValueError("pairs name tables outside [0, %d)" % n)
+    prs = np.ascontiguousarray(prs, dtype=np.int32)
+    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    rows = np.concatenate(tables) if seg[-1] else np.zeros((0, dim), np.float32)
+    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
+    idx = np.empty((int(out_off[-1]), 2), np.uint64)
+    dist = np.empty((int(out_off[-1]), 2), np.float32)
+    ncand = np.zeros(int(out_off[-1]), np.int32)
+    check(clib.spv_nn_cascading_hash_batch(rows.ctypes.data, seg.ctypes.data, n, dim, m, ntab, g, prs.ctypes.data,
+                                           len(prs), hash_dict.ctypes.data, idx.ctypes.data, dist.ctypes.data,
+                                           ncand.ctypes.data if return_ncand else None))
+    if return_ncand:
+        return [(idx[a:b], dist[a:b], ncand[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
+    return [(idx[a:b], dist[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
+
+
 # ==================================================================================
 # normalization               (reference spectavi/feature.py:384-407)
 # ==================================================================================

@@ -33,6 +33,10 @@ BUNDLE_MAGICS = (b"__CLANG_OFFLOAD_BUNDLE__", b"CCOB")
 
 # Instantiations that no test can reach on purpose, printed beside the diff.
 NOTES = {
+    "cascade_kernels.h": [
+        "the projection and scan kernels cascade.hip and cascade_batch.hip share: both files compile their own copies of "
+        "the query-side instantiations, which show here once.",
+    ],
     "cascade.hip": [
         "probe_table_kernel<1, 8, 7, false, false> also serves the non-shift probe of power-of-two widths "
         "for images of 4 GiB and more (xrows * dim >= 2^32); that path is not exercised by any test "
@@ -66,9 +70,9 @@ def norm(name):
 
 
 def kernel_sources():
-    """kernel base name -> the .hip file that defines it (`__global__ ... void NAME(`)."""
+    """kernel base name -> the .hip file, or the shared header, that defines it (`__global__ ... void NAME(`)."""
     out = {}
-    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
         text = open(path).read()
         for m in re.finditer(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", text):
             out[m.group(1)] = os.path.basename(path)
@@ -136,7 +140,7 @@ def main():
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("--list", action="store_true", help="list the instantiations (no GPU needed)")
     g.add_argument("--trace", metavar="DIR", help="rocprofv3 --kernel-trace --output-format csv output directory")
-    ap.add_argument("--files", default="l1k2.hip,bruteforce.hip,cascade.hip,sift.hip",
+    ap.add_argument("--files", default="l1k2.hip,bruteforce.hip,cascade.hip,cascade_kernels.h,cascade_batch.hip,sift.hip",
                     help="source files to report (comma separated; 'all' for every file)")
     ap.add_argument("--strict", action="store_true", help="exit 1 if an instantiation never ran")
     a = ap.parse_args()
