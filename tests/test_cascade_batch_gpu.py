@@ -177,6 +177,42 @@ def test_ratio_test_applies_to_the_concatenated_output():
     assert np.array_equal(matches[:k].cpu().numpy(), np.stack([np.nonzero(keep)[0], hi[keep, 0]], 1))
 
 
+def test_a_non_default_stream_gives_the_default_stream_result():
+    import torch
+    from spectavi_amd import device
+    dim, m, n, g = cb.EDGES[3]
+    x, seg, d = cb.collection(cb.FEW_ROWS, dim, m, n, g)
+    want, _ = check_collection(x, seg, d, cb.FEW, g)   # on the default stream
+    dx, dd = torch.from_numpy(x).cuda(), torch.from_numpy(d).cuda()
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    assert side != torch.cuda.default_stream()
+    with torch.cuda.stream(side):
+        idx, dist, out_off, ncand = device.cascade_batch(dx, seg, cb.FEW, dd, g=g, workspace=device.Workspace(), want_ncand=True)
+    side.synchronize()
+    got = (idx.cpu().numpy().view(np.uint64), dist.cpu().numpy(), ncand.cpu().numpy(), out_off)
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b)
+
+
+def test_a_workspace_reused_by_a_smaller_collection():
+    """Large then small on one device.Workspace: the second call finds the order, ranks and segment sums of the first
+    in its workspace, which no call zeroes, and still matches its oracle."""
+    import torch
+    from spectavi_amd import device
+    ws = device.Workspace()
+    first = None
+    for rows, pairs in ((cb.NINE, [(8, 7), (7, 8), (6, 8), (8, 8)]), (cb.FEW_ROWS, cb.FEW)):
+        x, seg, d = cb.collection(rows, *cb.NINE_SHAPE)
+        idx, dist, out_off, ncand = device.cascade_batch(torch.from_numpy(x).cuda(), seg, pairs, torch.from_numpy(d).cuda(),
+                                                         g=cb.NINE_SHAPE[3], workspace=ws, want_ncand=True)
+        got = (idx.cpu().numpy().view(np.uint64), dist.cpu().numpy(), ncand.cpu().numpy(), out_off)
+        assert_pairs_equal(got, oracle_pairs(x, seg, d, pairs, cb.NINE_SHAPE[3]), seg, pairs, str(rows))
+        buf = ws.get(0, idx.device)
+        first = first or (buf.data_ptr(), buf.numel())
+    assert (buf.data_ptr(), buf.numel()) == first, "the smaller call ran on the larger call's buffer"
+
+
 def test_launch_count_does_not_depend_on_the_number_of_pairs():
     import torch
     from spectavi_amd import device

@@ -124,6 +124,31 @@ def test_cascade(m, n, g):
                  lambda ws: device.cascade(x, y, d, g=g, workspace=ws, want_ncand=True))
 
 
+@pytest.mark.parametrize("m,n,g", [(8, 2, 2), (24, 1, 2)])   # bucket bits = m: buckets copied; below m: filtered
+def test_cascade_batch(m, n, g):
+    import torch
+    from spectavi_amd import device
+    from spectavi_amd._lib import clib
+    from tests import cascade_batch_cases as cb
+    rows = [0, 70, 300, 33]   # the first set empty; more than one work item; less than one
+    x, seg, d = cb.collection(rows, 128, m, n, g)
+    prs = np.array(cb.BOOK, np.int32)
+    dx, dd = torch.from_numpy(x).cuda(), torch.from_numpy(d).cuda()
+    assert device.cascade_batch_plan(seg, cb.BOOK, 128, m, n, g)["hb"] == min(m, 12)
+
+    def call(ws):
+        idx, dist, _, ncand = device.cascade_batch(dx, seg, cb.BOOK, dd, g=g, workspace=ws, want_ncand=True)
+        return [idx, dist, ncand]
+
+    need = clib.spv_cascade_batch_workspace_bytes(seg.ctypes.data, len(rows), 128, m, n, g, prs.ctypes.data, len(prs))
+    check_bounds(need, call)
+    # order, ranks and the segment sums are not zeroed by the call: on a workspace of 0xA5 bytes it still is the oracle
+    from tests.test_cascade_batch_gpu import assert_pairs_equal, oracle_pairs
+    idx, dist, ncand = (t.cpu().numpy() for t in call(FixedWs(need)))
+    out_off = np.concatenate([[0], np.cumsum([rows[a] for a, _ in cb.BOOK])])
+    assert_pairs_equal((idx.view(np.uint64), dist, ncand, out_off), oracle_pairs(x, seg, d, cb.BOOK, g), seg, cb.BOOK, "0xA5")
+
+
 def test_sift():
     import torch
     from spectavi_amd import device
