@@ -1,4 +1,5 @@
-"""Steps 2-4 of the reference's example pipeline for every image pair of a view set, one call per step.
+"""Steps 2-4 (with --rectify also step 5) of the reference's example pipeline for every image pair of a view set, one
+call per step.
 
 examples/essential_from_sift_tables.py runs matching, RANSAC and triangulation for ONE image pair, as the reference's
 example/ex01_essential_estimation.py does.  A multi-view front-end has N views and up to N (N - 1) / 2 pairs; this file
@@ -10,13 +11,15 @@ runs all of them through the many-pairs forms of the same steps, with every inte
     match_coordinates_batch  matches -> per-pair homogeneous coordinates and pair_off
     ransac_fit_batch         one essential matrix and camera per pair, and the inlier mask over all rows
     dlt_triangulate_batch    every pair's inliers triangulated with that pair's camera; pairs without a model skipped
+    rectify_batch            (--rectify) every fitted pair's two images rectified, cropped on the device to the valid
+                             samples; the images are noise here, only the geometry is the pipeline's
 
 Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
 they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic
 here, so that the scene and the cameras are known; extracting them from images is the library's sift_batch, the step
 before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
-    python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}]
+    python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}] [--rectify]
 """
 import argparse
 import os
@@ -112,6 +115,17 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     return {'pairs': pairs, 'pair_off': pair_off, 'fits': fits, 'out_off': out_off, 'X': X, 'rows': rows}
 
 
+def rectify_pairs(out, K, images):
+    """Step 5 for every pair with a model: images is a list of CUDA tensors [960, 1280], one per view.  The fits'
+    cameras are calibrated and map the database view's coordinates, so the pixel cameras are K [I|0] for the
+    database view and K P for the query view, and a matcher's pair (query, database) is passed as (database, query).
+    Returns device.rectify_batch's (r0, r1, ri0, ri1, box, out_off)."""
+    from spectavi_amd import device as spv
+    P0 = K @ np.hstack([np.eye(3), np.zeros((3, 1))])
+    P1s = [None if f['best_try'] < 0 else K @ f['camera'] for f in out['fits']]
+    return spv.rectify_batch(images, None, out['pairs'][:, ::-1], P1s, [P0] * len(P1s))
+
+
 def report(out):
     fitted = 0
     for p, (q, d) in enumerate(out['pairs'].tolist()):
@@ -130,6 +144,7 @@ def main():
     ap.add_argument("--points", type=int, default=2000, help="scene points seen in every view")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--matcher", default="l1k2", choices=["l1k2", "cascade"], help="exact brute force, or the cascade hash")
+    ap.add_argument("--rectify", action="store_true", help="also rectify every fitted pair (step 5), on noise images")
     a = ap.parse_args()
     import torch
     tables, K = synthetic_sift_views(a.seed, a.images, a.points)
@@ -143,6 +158,16 @@ def main():
     n = int(out['out_off'][-1])
     E = out['X'][:n, :3] / out['X'][:n, 3:]
     print("%d views, %.1f ms (warm); depth of the points: median %.2f" % (a.images, dt * 1e3, float(E[:, 2].median()) if n else 0.0))
+    if a.rectify:
+        images = [torch.randint(0, 256, (960, 1280), dtype=torch.uint8, device="cuda") for _ in range(a.images)]
+        for rep in range(2):
+            torch.cuda.synchronize()
+            s = time.perf_counter()
+            r0, r1, ri0, ri1, box, off = rectify_pairs(out, K, images)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - s
+        print("rectified %d pairs, %.1f ms (warm); windows hold %d samples, %.2f of the whole frames" % (
+            int((off[1:] > off[:-1]).sum()), dt * 1e3, off[-1], off[-1] / max(1, sum(f['best_try'] >= 0 for f in out['fits'])) / (2240 * 1536)))
 
 
 if __name__ == "__main__":

@@ -156,7 +156,8 @@ const char *spv_version(void);
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
  * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
  * "ann_merge", "ann_rerank", "cascade_project",
- * "cascade_buckets", "cascade_probe_refine", "cascade_batch_project", "cascade_batch_buckets", "cascade_batch_probe", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "ransac_batch_score",
+ * "cascade_buckets", "cascade_probe_refine", "cascade_batch_project", "cascade_batch_buckets", "cascade_batch_probe", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "rectify_batch_bounds", "rectify_batch_box",
+ * "rectify_batch", "ransac_batch_score",
  * "ransac_batch_reduce",
  * "gather_match_coords_batch") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
@@ -646,6 +647,77 @@ int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]);
  * for a singular P0 P0^T, zero for cameras sharing a centre).  Host only. */
 int spv_rectify_fundamental(const double *P0, const double *P1, double *F);
 
+/* image_pair_rectification for every pair of a collection of image pairs, cropped on the device (rectify_batch.hip):
+ * the last step of a view set's pipeline in the form of the other many-pairs calls.  Two device steps -- the
+ * bounding box of every pair's valid samples, then the resampling of only that window of the four outputs, all pairs
+ * packed back to back -- with one host synchronisation between them however many pairs there are.  The device forms
+ * spv_rectify_batch_bounds_device and spv_rectify_batch_device are in section 3.
+ *   sizes    host int32[nimg, 2] = (wid, hgt) of every image.
+ *   images   the images back to back in that order, each [hgt, wid, nchan] (the device form: d_images, on the
+ *            caller's current device) -- for nchan = 1 exactly what spv_sift_batch_device takes.
+ *   dtype    SPV_RECTIFY_F64, SPV_RECTIFY_U8 or SPV_RECTIFY_F32 (float32 images, this call only): values are
+ *            copied as integers of their width, so NaN payloads and -0.0 pass through.  Images and outputs are
+ *            aligned to their element size.
+ *   nchan >= 1 and sampling_factor: one value each for the call.
+ *   pairs    host int32[npairs, 2] = (image 0, image 1) of every pair, numbers in [0, nimg).  Repeats are allowed
+ *            and an image may appear in many pairs; the two images of a pair have the same size.  The matcher's
+ *            pair (query set, database set) is passed here as (database, query): x0 -- the coordinates the cameras
+ *            of spv_ransac_fit_batch map with [I | 0] -- comes from the database view.
+ *   P0s      host double[npairs, 12], or NULL for [I | 0] for every pair; P1s host double[npairs, 12].
+ *   use      host int32[npairs], or NULL for all pairs: a pair with use[p] = 0 has its cameras unread, the box
+ *            (0, 0, 0, 0) and owns no output.
+ * F of every pair is spv_rectify_fundamental(P0, P1), computed on the host.  The uncropped frame of pair p is
+ * spv_rectify_shape(wid, hgt, nchan, sf) of its images; box[p] = (row_lo, row_hi, col_lo, col_hi), half-open, in
+ * that frame, is the pair's window.
+ *
+ * Bounds (spv_rectify_batch_bounds_device): d_box int32[npairs, 4] receives, for every pair, the bounding box of the
+ * samples with ri0 != -1 || ri1 != -1 under the sample rule of image_pair_rectification (section 1) -- what the
+ * front-end's crop_invalid keeps --, or (0, 0, 0, 0) where there is none: F all NaN or zero, rnx = 1, or a pair
+ * that is not used.  No image is read.  Every sample of every other pair is evaluated, in items of 16 frame rows of
+ * one pair (one workgroup's step each, over the capped grid of the resampling step); the partial results are
+ * combined with integer minima and maxima, so the result does not depend on their order.
+ *
+ * Plan (spv_rectify_batch_plan): host only, touches no device.  box: host int32[npairs, 4], or NULL for every used
+ * pair's whole frame (the entries of pairs that are not used are not read).  out = {used pairs, work items, total
+ * window samples}.  out_off long long[npairs + 1]: pair p owns samples [out_off[p], out_off[p + 1]) of the outputs,
+ * its window in row-major order, (row_hi - row_lo) * (col_hi - col_lo) samples.  items may be NULL, otherwise
+ * int32[items_cap, 4] receives the first min(work items, items_cap) work items, exactly the list the device call
+ * walks, in its order: (pair, image 0 or 1 of the pair, first row in the pair's frame, rows <= 8), one workgroup's
+ * step each -- pair by pair, the row blocks of image 0 then those of image 1.  Together they cover every window row
+ * of both images exactly once; an item never straddles two pairs and a window without a sample owns none.
+ * SPV_ERR_INVALID, outputs untouched: what spv_rectify_shape rejects for any image, image numbers outside
+ * [0, nimg), a pair of unequal sizes, a box outside its frame or with lo > hi, negative counts, more than 2^20
+ * pairs, a NULL required pointer.  npairs = 0 and a collection without a used pair are valid.
+ *
+ * Resample (spv_rectify_batch_device): box as for the plan, a HOST array.  d_r0, d_r1 hold
+ * dtype[out_off[npairs] * nchan], d_ri0, d_ri1 int32[out_off[npairs]].  Every element of every window is written
+ * exactly once, the padding columns [rnx, cols) included, and nothing else is touched.  For every pair the window
+ * is bit for bit the slice [row_lo:row_hi, col_lo:col_hi] of what spv_rectify_device writes for that pair alone
+ * with the same F (float32: of what it writes for the images widened to double, narrowed again), whatever else the
+ * collection contains and however the call cuts the work; the index is the flat index inside the pair's own image.
+ * Asynchronous on `stream` but for the upload of its small per-pair and item tables, which live in the library's
+ * cache (spv_release_cached_memory) and go back to it once the call's last kernel has ended.  One launch for the
+ * whole collection, its grid capped at 32 workgroups per compute unit, each walking items b, b + grid, ...
+ * Kernel names for spv_profile_read: "rectify_batch_bounds" (one launch per bounds call, followed by
+ * "rectify_batch_box", which turns the minima and maxima into boxes), "rectify_batch" (one launch per resample).
+ *
+ * spv_rectify_batch: the host-pointer form, on the first selected device.  crop != 0 runs the bounds step and reads
+ * the boxes back (the one synchronisation); crop = 0 takes whole frames.  rectified0/1: callee-allocated
+ * [out_off[npairs] * nchan, 1] of the dtype (the NdArray's item size must be the dtype's), rectified_idx0/1:
+ * int32[out_off[npairs], 1].  box int32[npairs, 4] and out_off long long[npairs + 1] are caller arrays the call
+ * fills.  A pair without a valid sample has an empty box and owns no output; that is no error.  No device is
+ * touched when no pair is used. */
+#define SPV_RECTIFY_F64 0
+#define SPV_RECTIFY_U8 1
+#define SPV_RECTIFY_F32 2
+int spv_rectify_batch(const void *images, int dtype, const int32_t *sizes, int nimg, int nchan, double sampling_factor,
+                      const int32_t *pairs, int npairs, const double *P0s, const double *P1s, const int32_t *use,
+                      int crop, NdArray *rectified0, NdArray *rectified1, NdArray *rectified_idx0,
+                      NdArray *rectified_idx1, int32_t *box, long long *out_off);
+int spv_rectify_batch_plan(const int32_t *sizes, int nimg, int nchan, double sampling_factor, const int32_t *pairs,
+                           int npairs, const int32_t *use, const int32_t *box, long long out[3], long long *out_off,
+                           int32_t *items, long long items_cap);
+
 int spv_dlt_triangulate(const double *P0, const double *P1, int npt, const double *x,
                         const double *xp, double *dst);
 int spv_dlt_reprojection_error(const double *P0, const double *P1, int npt, const double *x,
@@ -777,11 +849,20 @@ int spv_ann_l2_device(const float *d_x, const float *d_y, int xrows, int yrows, 
  * spv_rectify_fundamental): dtype SPV_RECTIFY_F64 (d_im0, d_im1, d_r0, d_r1 double, 8-byte aligned)
  * or SPV_RECTIFY_U8 (uint8_t: 8-bit images, values copied as bytes); d_ri0, d_ri1 int32.  Output
  * shapes from spv_rectify_shape; every element of the four outputs is written.  Asynchronous, no
- * host synchronisation.  Kernel name for spv_profile_read: "rectify". */
-#define SPV_RECTIFY_F64 0
-#define SPV_RECTIFY_U8 1
+ * host synchronisation.  Kernel name for spv_profile_read: "rectify".  (SPV_RECTIFY_F32 is spv_rectify_batch's
+ * alone.) */
 int spv_rectify_device(const double *F, const void *d_im0, const void *d_im1, int dtype, int wid, int hgt, int nchan,
                        double sf, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, void *stream);
+
+/* Device forms of spv_rectify_batch (section 2, where the contract is): d_images, d_box and the four outputs on the
+ * caller's current device; sizes, pairs, the cameras, use and box host arrays. */
+int spv_rectify_batch_bounds_device(const int32_t *sizes, int nimg, int nchan, double sampling_factor,
+                                    const int32_t *pairs, int npairs, const double *P0s, const double *P1s,
+                                    const int32_t *use, int32_t *d_box, void *stream);
+int spv_rectify_batch_device(const void *d_images, int dtype, const int32_t *sizes, int nimg, int nchan,
+                             double sampling_factor, const int32_t *pairs, int npairs, const double *P0s,
+                             const double *P1s, const int32_t *use, const int32_t *box, void *d_r0, void *d_r1,
+                             int32_t *d_ri0, int32_t *d_ri1, void *stream);
 
 /* sift_filter with a status.  out: float32 NdArray, allocated by the callee. */
 int spv_sift_filter(const float *im, int wid, int hgt, NdArray *out);

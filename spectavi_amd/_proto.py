@@ -103,6 +103,8 @@ PROTOTYPES = {
     "spv_ransac_fit_batch_plan": (i, [vp, i, i, i, pll, vp, ll]),
     "spv_dlt_triangulate_batch": (i, [vp, vp, vp, i] + [vp] * 7 + [ll, vp, vp]),
     "spv_dlt_triangulate_batch_plan": (i, [vp, i, vp, i, pll, vp, ll]),
+    "spv_rectify_batch": (i, [vp, i, vp, i, i, d, vp, i, vp, vp, vp, i] + [nd] * 4 + [vp, vp]),
+    "spv_rectify_batch_plan": (i, [vp, i, i, d, vp, i, vp, vp, pll, vp, vp, ll]),
     "spv_rectify_shape": (i, [i, i, i, d, i32a]),
     "spv_rectify_fundamental": (i, [f64a, f64a, f64a]),
     "spv_dlt_triangulate": (i, _dlt),
@@ -124,6 +126,8 @@ PROTOTYPES = {
     "spv_ann_l2_plan": (i, [i] * 6 + [pi]),
     "spv_ann_l2_device": (i, [vp, vp] + [i] * 6 + [vp] * 3 + [sz, vp]),
     "spv_rectify_device": (i, [f64a, vp, vp, i, i, i, i, d, vp, vp, vp, vp, vp]),
+    "spv_rectify_batch_bounds_device": (i, [vp, i, i, d, vp, i, vp, vp, vp, vp, vp]),
+    "spv_rectify_batch_device": (i, [vp, i, vp, i, i, d, vp, i] + [vp] * 9),
     "spv_sift_filter": (i, [vp, i, i, nd]),
     "spv_sift_table": (i, [f32a, i, i, f32a, i, pi32]),
     "spv_sift_set_first_capacity": (i, [i]),

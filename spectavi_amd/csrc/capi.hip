@@ -411,6 +411,54 @@ int host_rectify(const double *P0, const double *P1, const double *im0, const do
 
 int alloc_out(NdArray *arr, size_t rows, size_t cols, int itemsize, size_t depth);
 
+// The many-pairs rectification through host pointers, on the first selected device: the images up, with `crop` the
+// bounds step and its boxes back (the one synchronisation), the four flat outputs sized by the windows, one
+// rectify_batch_run, the outputs back.  A collection without a used pair touches no device.
+int host_rectify_batch(const void *images, int dtype, const int32_t *sizes, int nimg, int nchan, double sf,
+                       const int32_t *pairs, int npairs, const double *P0s, const double *P1s, const int32_t *use,
+                       int crop, NdArray *r0, NdArray *r1, NdArray *ri0, NdArray *ri1, int32_t *box,
+                       long long *out_off) {
+  if (dtype != SPV_RECTIFY_F64 && dtype != SPV_RECTIFY_U8 && dtype != SPV_RECTIFY_F32)
+    return set_error(SPV_ERR_INVALID, "dtype %d", dtype);
+  const int esize = dtype == SPV_RECTIFY_F64 ? 8 : dtype == SPV_RECTIFY_F32 ? 4 : 1;
+  RectifyBatchPlan pl;
+  SPV_TRY(rectify_batch_plan(sizes, nimg, nchan, sf, pairs, npairs, use, nullptr, &pl));
+  if (!r0 || !r1 || !ri0 || !ri1 || !out_off || (npairs > 0 && !box)) return set_error(SPV_ERR_INVALID, "null output");
+  if (pl.used > 0 && (!images || !P1s)) return set_error(SPV_ERR_INVALID, "null pointer");
+  hipStream_t st = nullptr;
+  DevBuf dim;
+  const int dev = device_list()[0];
+  if (pl.used > 0) {
+    SPV_TRY(host_begin(dev, &st));
+    SPV_TRY(dim.upload(images, (size_t)pl.img_off[nimg] * nchan * esize, st));
+    if (crop) {
+      DevBuf dbox;
+      const size_t bb = (size_t)npairs * 4 * sizeof(int32_t);
+      SPV_TRY(dbox.alloc(bb));
+      SPV_TRY(rectify_batch_bounds_run(sizes, nimg, nchan, sf, pairs, npairs, P0s, P1s, use, dbox.as<int32_t>(), st));
+      SPV_TRY(dbox.copy_out(box, bb, st));
+      SPV_HIP_CHECK(hipStreamSynchronize(st));
+      SPV_TRY(rectify_batch_plan(sizes, nimg, nchan, sf, pairs, npairs, use, box, &pl));
+    }
+  }
+  if (npairs > 0 && !(crop && pl.used > 0)) memcpy(box, pl.box.data(), (size_t)npairs * 4 * sizeof(int32_t));
+  memcpy(out_off, pl.out_off.data(), ((size_t)npairs + 1) * sizeof(long long));
+  const size_t total = (size_t)pl.out_off[npairs], vb = total * nchan * esize, xb = total * sizeof(int32_t);
+  SPV_TRY(alloc_out(r0, total * nchan, 1, esize, 0));
+  SPV_TRY(alloc_out(r1, total * nchan, 1, esize, 0));
+  SPV_TRY(alloc_out(ri0, total, 1, (int)sizeof(int32_t), 0));
+  SPV_TRY(alloc_out(ri1, total, 1, (int)sizeof(int32_t), 0));
+  if (total == 0) return SPV_OK;
+  DevBuf dr0, dr1, dx0, dx1;
+  SPV_TRY(alloc_all({{&dr0, vb}, {&dr1, vb}, {&dx0, xb}, {&dx1, xb}}));
+  SPV_TRY(rectify_batch_run(dim.p, dtype, sizes, nimg, nchan, sf, pairs, npairs, P0s, P1s, use, box, dr0.p, dr1.p,
+                            dx0.as<int32_t>(), dx1.as<int32_t>(), st));
+  SPV_TRY(dx0.copy_out(ri0->m_data, xb, st));
+  SPV_TRY(dx1.copy_out(ri1->m_data, xb, st));
+  SPV_TRY(download(dev, r0->m_data, dr0.p, vb, st));
+  return download(dev, r1->m_data, dr1.p, vb, st);
+}
+
 // First table size of the host forms that size the table to the result (0: the default guess).
 std::atomic<int> g_sift_first_rows{0};
 
@@ -1564,6 +1612,30 @@ int spv_dlt_triangulate_batch_plan(const long long *pair_off, int npairs, const 
     return (int)SPV_OK;
   });
 }
+int spv_rectify_batch(const void *images, int dtype, const int32_t *sizes, int nimg, int nchan, double sampling_factor,
+                      const int32_t *pairs, int npairs, const double *P0s, const double *P1s, const int32_t *use,
+                      int crop, NdArray *rectified0, NdArray *rectified1, NdArray *rectified_idx0,
+                      NdArray *rectified_idx1, int32_t *box, long long *out_off) {
+  return host_api([&] {
+    return host_rectify_batch(images, dtype, sizes, nimg, nchan, sampling_factor, pairs, npairs, P0s, P1s, use, crop,
+                              rectified0, rectified1, rectified_idx0, rectified_idx1, box, out_off);
+  });
+}
+int spv_rectify_batch_plan(const int32_t *sizes, int nimg, int nchan, double sampling_factor, const int32_t *pairs,
+                           int npairs, const int32_t *use, const int32_t *box, long long out[3], long long *out_off,
+                           int32_t *items, long long items_cap) {
+  return api([&] {
+    if (!out || !out_off || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
+    RectifyBatchPlan pl;
+    SPV_TRY(rectify_batch_plan(sizes, nimg, nchan, sampling_factor, pairs, npairs, use, box, &pl));
+    out[0] = pl.used;
+    out[1] = (long long)pl.items.size();
+    out[2] = pl.out_off[npairs];
+    memcpy(out_off, pl.out_off.data(), ((size_t)npairs + 1) * sizeof(long long));
+    if (items) memcpy(items, pl.items.data(), (size_t)std::min<long long>(items_cap, (long long)pl.items.size()) * sizeof(RectifyBatchItem));
+    return (int)SPV_OK;
+  });
+}
 int spv_rectify_shape(int wid, int hgt, int nchan, double sf, int out[3]) {
   return api([&] {
     if (!out) return set_error(SPV_ERR_INVALID, "null output");
@@ -1728,6 +1800,24 @@ int spv_rectify_device(const double *F, const void *d_im0, const void *d_im1, in
   return api([&] {
     return rectify_run(F, d_im0, d_im1, dtype, wid, hgt, nchan, sf, d_r0, d_r1, d_ri0, d_ri1,
                        static_cast<hipStream_t>(stream));
+  });
+}
+
+int spv_rectify_batch_bounds_device(const int32_t *sizes, int nimg, int nchan, double sampling_factor,
+                                    const int32_t *pairs, int npairs, const double *P0s, const double *P1s,
+                                    const int32_t *use, int32_t *d_box, void *stream) {
+  return api([&] {
+    return rectify_batch_bounds_run(sizes, nimg, nchan, sampling_factor, pairs, npairs, P0s, P1s, use, d_box,
+                                    static_cast<hipStream_t>(stream));
+  });
+}
+int spv_rectify_batch_device(const void *d_images, int dtype, const int32_t *sizes, int nimg, int nchan,
+                             double sampling_factor, const int32_t *pairs, int npairs, const double *P0s,
+                             const double *P1s, const int32_t *use, const int32_t *box, void *d_r0, void *d_r1,
+                             int32_t *d_ri0, int32_t *d_ri1, void *stream) {
+  return api([&] {
+    return rectify_batch_run(d_images, dtype, sizes, nimg, nchan, sampling_factor, pairs, npairs, P0s, P1s, use, box,
+                             d_r0, d_r1, d_ri0, d_ri1, static_cast<hipStream_t>(stream));
   });
 }
 

@@ -319,6 +319,36 @@ void rectify_fundamental(const double *P0, const double *P1, double *F);  // hos
 int rectify_run(const double *F, const void *d_im0, const void *d_im1, int dtype, int wid, int hgt, int nchan,
                 double sf, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, hipStream_t stream);
 
+// ---- epipolar rectification of many image pairs in one call (rectify_batch.hip) ---------
+constexpr int kRectifyBatchRows = 8;             // window rows per work item
+constexpr int kRectifyBatchGroupsPerCu = 32;     // the grid cap: workgroups per compute unit, each walking its items
+constexpr int kRectifyBatchMaxPairs = 1 << 20;   // the limit of the other many-pairs forms
+// One workgroup's share of a collection: rows [row0, row0 + rows) of pair `pair`'s uncropped frame, all inside its
+// window, in image `img` (0 or 1) of the pair.
+struct RectifyBatchItem {
+  int32_t pair, img, row0, rows;
+};
+// Everything rectify_batch_run launches for a collection, a function of the shapes, `use` and the boxes alone.
+struct RectifyBatchPlan {
+  long long used = 0;
+  std::vector<long long> img_off;       // [nimg + 1]: pixels before every image of the packed array
+  std::vector<int32_t> frame;           // [npairs, 3]: rectify_shape of every used pair (zero where not used)
+  std::vector<int32_t> box;             // [npairs, 4]: the window in force (zero where not used)
+  std::vector<long long> out_off;       // [npairs + 1]: pair p owns samples [out_off[p], out_off[p + 1])
+  std::vector<RectifyBatchItem> items;  // pair by pair, image 0's row blocks then image 1's
+};
+// box: host int32[npairs, 4] or null for whole frames.  SPV_ERR_INVALID (message set, *p untouched) for what
+// include/spectavi_amd.h rejects; host only
+int rectify_batch_plan(const int32_t *sizes, int nimg, int nchan, double sf, const int32_t *pairs, int npairs,
+                       const int32_t *use, const int32_t *box, RectifyBatchPlan *p);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the call's tables.
+int rectify_batch_bounds_run(const int32_t *sizes, int nimg, int nchan, double sf, const int32_t *pairs, int npairs,
+                             const double *P0s, const double *P1s, const int32_t *use, int32_t *d_box,
+                             hipStream_t stream);
+int rectify_batch_run(const void *d_images, int dtype, const int32_t *sizes, int nimg, int nchan, double sf,
+                      const int32_t *pairs, int npairs, const double *P0s, const double *P1s, const int32_t *use,
+                      const int32_t *box, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, hipStream_t stream);
+
 // ---- vlfeat-exact SIFT (sift.hip) ----------------------------------------------------
 constexpr int kSiftMaxSide = 8192;  // candidates pack x, y of octave -1 in 15 bits each; counts stay below 2^31
 int sift_check(int wid, int hgt);   // SPV_ERR_INVALID (message set) outside the header's limits

@@ -21,6 +21,7 @@
 //     through unchanged.
 
 #include "common.h"
+#include "rectify_device.h"
 
 #include <climits>
 #include <cmath>
@@ -51,31 +52,13 @@ __global__ __launch_bounds__(kThreads) void rectify_kernel(RectifyArgs a, const 
     const int row = (int)(rb / a.col_blocks);
     const int i = (int)(rb - (long long)row * a.col_blocks) * kThreads + (int)threadIdx.x;
     if (i >= a.cols) continue;
-    const double v = (double)(row - a.extra);
-    // image 0: l_j = F[0][j]*0 + F[1][j]*v + F[2][j]
-    double L0 = (a.F[0] * 0. + a.F[3] * v) + a.F[6];
-    double L1 = (a.F[1] * 0. + a.F[4] * v) + a.F[7];
-    double L2 = (a.F[2] * 0. + a.F[5] * v) + a.F[8];
-    if (img) {  // image 1: m = F (sx, sy, 1), the seed being sample 0 of the same image-0 row
-      const double sx = 0. + 0. * a.delta;
-      const double sy = ((-L2) - (L0 * sx)) / L1;
-      const double m0 = (a.F[0] * sx + a.F[1] * sy) + a.F[2];
-      const double m1 = (a.F[3] * sx + a.F[4] * sy) + a.F[5];
-      const double m2 = (a.F[6] * sx + a.F[7] * sy) + a.F[8];
-      L0 = m0;
-      L1 = m1;
-      L2 = m2;
-    }
+    double L0, L1, L2;  // the row's line in this image (rectify_device.h)
+    rectify_line(a.F, a.delta, (double)(row - a.extra), img, L0, L1, L2);
     const T *im = img ? im1 : im0;
     T *out = img ? r1 : r0;
     int *outi = img ? ri1 : ri0;
     const size_t o = (size_t)row * a.cols + i;
-    int idx = -1;
-    if (i < a.rnx) {
-      const double x = 0. + (double)i * a.delta;
-      const double y = ((-L2) - (L0 * x)) / L1;
-      if (x > -1. && x < (double)a.wid && y > -1. && y < (double)a.hgt) idx = (int)y * a.wid + (int)x;
-    }
+    const int idx = i < a.rnx ? rectify_sample(L0, L1, L2, a.delta, i, a.wid, a.hgt) : -1;
     outi[o] = idx;
     if (idx >= 0) {
       const T *src = im + (size_t)idx * a.nchan;

@@ -966,6 +966,173 @@ def image_pair_rectification(P0, P1, im0, im1, sampling_factor=1.2):
     return r0, r1, ri0, ri1
 
 
+_RECTIFY_BATCH_DTYPE = dict(_RECTIFY_DTYPE)
+_RECTIFY_BATCH_DTYPE[torch.float32] = 2  # SPV_RECTIFY_F32: the batch form alone
+
+
+def _rectify_batch_args(sizes, pairs, P1s, P0s, use, box=None):
+    """sizes -> int32[nimg, 2], pairs -> int32[npairs, 2], P1s / P0s -> float64[npairs, 12] (P0s or None), use ->
+    int32[npairs] or None, box -> int32[npairs, 4] or None.  A None entry of a P1s list is a pair that is not used.
+    ValueError where the counts disagree; the library checks the rest.  Touches no device."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1, 2)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    npairs = len(pairs)
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
+        if use.size != npairs:
+            raise ValueError("use must hold one value per pair")
+    if P1s is not None and not isinstance(P1s, np.ndarray) and any(P is None for P in P1s):
+        skip = np.array([P is None for P in P1s])
+        if len(skip) != npairs:
+            raise ValueError("P1s must hold one camera per pair")
+        use = (~skip).astype(np.int32) if use is None else (use * ~skip).astype(np.int32)
+        P1s = [np.zeros((3, 4)) if P is None else P for P in P1s]
+
+    def cameras(Ps, name):
+        Ps = np.ascontiguousarray(Ps, dtype=np.float64).reshape(-1, 12) if npairs else np.zeros((0, 12))
+        if Ps.shape[0] != npairs:
+            raise ValueError("%s must hold one [3,4] camera per pair" % name)
+        return Ps
+    if box is not None:
+        box = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 4)
+        if len(box) != npairs:
+            raise ValueError("box must hold one (row_lo, row_hi, col_lo, col_hi) per pair")
+    return (sizes, pairs, None if P1s is None else cameras(P1s, "P1s"), None if P0s is None else cameras(P0s, "P0s"),
+            use, box)
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def rectify_batch_plan(sizes, pairs, nchan=1, sampling_factor=1.2, use=None, box=None, want_items=False):
+    """What rectify_batch() writes and launches for a collection (spv_rectify_batch_plan; host only, no device
+    touched): dict of pairs (used pairs), items (workgroup steps), samples (window samples in all) and out_off, an
+    int64 ndarray [npairs + 1] -- pair p owns samples out_off[p]:out_off[p + 1] of the flat outputs, its window
+    box[p] = (row_lo, row_hi, col_lo, col_hi) in row-major order (box None: whole frames).  With want_items also the
+    items, int32[items, 4] = (pair, image 0 or 1, first frame row, rows <= 8)."""
+    sizes, pairs, _, _, use, box = _rectify_batch_args(sizes, pairs, None, None, use, box)
+    out = (ct.c_longlong * 3)()
+    out_off = np.zeros(len(pairs) + 1, np.int64)
+    args = (sizes.ctypes.data, len(sizes), int(nchan), float(sampling_factor), pairs.ctypes.data, len(pairs), _ptr(use),
+            _ptr(box), out, out_off.ctypes.data)
+    check(clib.spv_rectify_batch_plan(*args, None, 0))
+    plan = dict(pairs=int(out[0]), items=int(out[1]), samples=int(out[2]), out_off=out_off)
+    if want_items:
+        items = np.empty((plan["items"], 4), np.int32)
+        check(clib.spv_rectify_batch_plan(*args, items.ctypes.data, len(items)))
+        return plan, items
+    return plan
+
+
+def rectify_batch_bounds(sizes, pairs, P1s, P0s=None, use=None, nchan=1, sampling_factor=1.2, device=None):
+    """The window every pair of a collection rectifies into (spv_rectify_batch_bounds_device): a CUDA int32
+    [npairs, 4] tensor of (row_lo, row_hi, col_lo, col_hi), half-open, in each pair's uncropped frame -- the bounding
+    box of the samples valid in either image, what `mvg.image_pair_rectification(crop_invalid=True)` keeps --,
+    (0, 0, 0, 0) where a pair has none or is not used.  No image is read.  Asynchronous on the current stream of
+    `device` (default: the current device) but for the upload of the cameras."""
+    sizes, pairs, P1s, P0s, use, _ = _rectify_batch_args(sizes, pairs, P1s, P0s, use)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    d_box = torch.empty((len(pairs), 4), dtype=torch.int32, device=dev)
+    with _on_device_of(d_box) as stream:
+        check(clib.spv_rectify_batch_bounds_device(sizes.ctypes.data, len(sizes), int(nchan), float(sampling_factor),
+                                                   pairs.ctypes.data, len(pairs), _ptr(P0s), _ptr(P1s), _ptr(use),
+                                                   d_box.data_ptr(), stream))
+    return d_box
+
+
+def rectify_batch(images, sizes, pairs, P1s, P0s=None, use=None, sampling_factor=1.2, crop_invalid=True, box=None):
+    """`image_pair_rectification` for every pair of a collection in one call, cropped on the device
+    (spv_rectify_batch_bounds_device, spv_rectify_batch_device).  images: a list of CUDA tensors [hgt, wid] or
+    [hgt, wid, nchan] of one dtype (float64, float32 or uint8) and one nchan -- sizes may then be None --, or one
+    packed tensor holding the images back to back together with sizes = (wid, hgt) per image (gray images:
+    `sift_batch`'s layout; more channels: the packed tensor's last dimension is nchan).  pairs [npairs, 2] =
+    (image 0, image 1): a matcher's pair (query set, database set) is passed as (database, query).  P1s, P0s
+    (None: [I|0]) host [3,4] cameras per pair; a pair with use[p] == 0 (or a None entry of a P1s list) is skipped.
+
+    With crop_invalid every pair is written only inside the bounding box of its valid samples, which costs the
+    call's one synchronisation (the boxes come back to size the outputs); box, int32 [npairs, 4] on the host, gives
+    the windows instead, and with neither whole frames are written, both without a synchronisation.  Returns
+    (r0, r1, ri0, ri1, box, out_off): flat CUDA tensors (values of the images' dtype, [samples * nchan]; indices
+    int32 [samples]), box and out_off as ndarrays; pair p owns samples out_off[p]:out_off[p + 1], see
+    rectify_batch_view().  Every window is bit for bit the slice of what `image_pair_rectification` returns for the
+    pair alone; a pair without a valid sample has an empty box and no output."""
+    if isinstance(images, torch.Tensor):
+        if sizes is None:
+            raise ValueError("a packed tensor needs sizes")
+        packed = images
+        nchan = packed.shape[-1] if packed.dim() > 1 else 1
+    else:
+        from spectavi_amd import mvg
+        dims = [mvg.image_dims(tuple(im.shape)) for im in images]
+        if len({d[2] for d in dims}) > 1 or len({im.dtype for im in images}) > 1:
+            raise TypeError("the images must share one dtype and one number of channels")
+        nchan = dims[0][2] if dims else 1
+        if sizes is None:
+            sizes = [(d[1], d[0]) for d in dims]
+        packed = torch.cat([im.reshape(-1) for im in images]) if len(images) else torch.empty(0, device="cuda")
+    if packed.dtype not in _RECTIFY_BATCH_DTYPE:
+        raise TypeError("the images must be float64, float32 or uint8 tensors")
+    sizes, pairs, P1s, P0s, use, box = _rectify_batch_args(sizes, pairs, P1s, P0s, use, box)
+    sf = float(sampling_factor)
+    if box is None and crop_invalid:
+        d_box = rectify_batch_bounds(sizes, pairs, P1s, P0s, use, nchan, sf, device=packed.device)
+        box = d_box.cpu().numpy()  # the call's one synchronisation
+    plan = rectify_batch_plan(sizes, pairs, nchan, sf, use, box)
+    if box is None:  # whole frames (the plan has checked the pairs)
+        from spectavi_amd import mvg
+        box = np.zeros((len(pairs), 4), np.int32)
+        for p, (a, _) in enumerate(pairs):
+            if use is None or use[p]:
+                rows, cols, _ = mvg.rectification_shape(sizes[a, 0], sizes[a, 1], nchan, sf)
+                box[p] = (0, rows, 0, cols)
+    elif use is not None:
+        box = box * (use != 0)[:, None].astype(np.int32)
+    out_off, total = plan["out_off"], plan["samples"]
+    r0 = torch.empty(total * nchan, dtype=packed.dtype, device=packed.device)
+    r1 = torch.empty(total * nchan, dtype=packed.dtype, device=packed.device)
+    ri0 = torch.empty(total, dtype=torch.int32, device=packed.device)
+    ri1 = torch.empty(total, dtype=torch.int32, device=packed.device)
+    rectify_batch_into(packed, sizes, pairs, P1s, P0s, use, sf, box, nchan, r0, r1, ri0, ri1)
+    return r0, r1, ri0, ri1, box, out_off
+
+
+def rectify_batch_into(packed, sizes, pairs, P1s, P0s, use, sampling_factor, box, nchan, r0, r1, ri0, ri1):
+    """The resampling step of rectify_batch() into caller-allocated flat tensors (spv_rectify_batch_device): r0, r1
+    of the images' dtype with at least samples * nchan elements, ri0, ri1 int32 with at least samples, `samples` from
+    rectify_batch_plan().  Only the windows are written.  Asynchronous on the current stream."""
+    if not isinstance(packed, torch.Tensor) or packed.dtype not in _RECTIFY_BATCH_DTYPE:
+        raise TypeError("the images must be float64, float32 or uint8 tensors")
+    sizes, pairs, P1s, P0s, use, box = _rectify_batch_args(sizes, pairs, P1s, P0s, use, box)
+    _need(packed, packed.dtype, "images")
+    _need(r0, packed.dtype, "r0")
+    _need(r1, packed.dtype, "r1")
+    _need(ri0, torch.int32, "ri0")
+    _need(ri1, torch.int32, "ri1")
+    if int((sizes[:, 0].astype(np.int64) * sizes[:, 1]).sum()) * nchan != packed.numel():
+        raise ValueError("sizes do not describe the packed images")
+    if box is None:
+        samples = rectify_batch_plan(sizes, pairs, nchan, sampling_factor, use)["samples"]
+    else:  # (the library checks the boxes against the frames)
+        area = (box[:, 1] - box[:, 0]).astype(np.int64) * (box[:, 3] - box[:, 2])
+        samples = int(area.sum() if use is None else area[use != 0].sum())
+    if min(r0.numel(), r1.numel()) < samples * nchan or min(ri0.numel(), ri1.numel()) < samples:
+        raise ValueError("the outputs are too short for the %d samples of the windows" % samples)
+    with _on_device_of(packed, r0, r1, ri0, ri1) as stream:
+        check(clib.spv_rectify_batch_device(packed.data_ptr(), _RECTIFY_BATCH_DTYPE[packed.dtype],
+                                            sizes.ctypes.data, len(sizes), int(nchan), float(sampling_factor),
+                                            pairs.ctypes.data, len(pairs), _ptr(P0s), _ptr(P1s), _ptr(use), _ptr(box),
+                                            r0.data_ptr(), r1.data_ptr(), ri0.data_ptr(), ri1.data_ptr(), stream))
+
+
+def rectify_batch_view(flat, p, box, out_off, nchan=1):
+    """Pair p's window of a flat output of rectify_batch() as a view, nothing copied: [rows, cols] for ri0 / ri1
+    and for gray values, [rows, cols, nchan] for r0 / r1 when nchan (the images' channels) is given above 1."""
+    rows, cols = int(box[p][1] - box[p][0]), int(box[p][3] - box[p][2])
+    w = flat[int(out_off[p]) * nchan:int(out_off[p + 1]) * nchan]
+    return w.reshape(rows, cols) if nchan == 1 else w.reshape(rows, cols, nchan)
+
+
 def sift_into(im, table, count, workspace=None):
     """vlfeat-exact SIFT of im (float32 [H, W] CUDA tensor) into table (float32 [capacity, 132]): rows
     [0, min(n, capacity)) are written and count (int32 [1]) receives the true row count n.

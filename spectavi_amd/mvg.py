@@ -523,3 +523,79 @@ def image_pair_rectification(P0, P1, im0, im1, sampling_factor=1.2, crop_invalid
         ys, xs = slice(y.min(), y.max() + 1), slice(x.min(), x.max() + 1)
         r0, r1, ri0, ri1 = r0[ys, xs, ...], r1[ys, xs, ...], ri0[ys, xs], ri1[ys, xs]
     return r0, r1, ri0, ri1
+
+
+_spv_rectify_batch = clib.spv_rectify_batch
+_RECTIFY_BATCH_DTYPE = {np.dtype(np.float64): 0, np.dtype(np.uint8): 1, np.dtype(np.float32): 2}  # SPV_RECTIFY_*
+
+
+def image_pair_rectification_batch(ims, pairs, P1s, P0s=None, sampling_factor=1.2, crop_invalid=True):
+    """
+    `image_pair_rectification` for many image pairs in one call (spv_rectify_batch), cropped on the device.
+
+    ims : list of numpy images [hgt, wid] or [hgt, wid, nchan] of one dtype and one nchan; float32 and uint8
+    images keep their dtype, anything else is taken as float64.  pairs : [npairs, 2] = (image 0, image 1), numbers
+    into ims; the two images of a pair have the same size.  A matcher's pair (query set, database set) is passed as
+    (database, query).  P1s : list of [3,4] second cameras, a None entry skips its pair (what a `ransac_fit_batch`
+    row without a model becomes); P0s : list of first cameras or None for [I|0] everywhere.
+
+    Returns a list with one (r0, r1, ri0, ri1) per pair, each what `image_pair_rectification` returns for that pair
+    alone -- cropped to the bounding box of the valid samples with `crop_invalid`, on the device, so only the boxes
+    are written and brought back --, or None where a pair is skipped or, with `crop_invalid`, has no valid sample
+    (the single call raises ValueError there; the batch never does).
+    """
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    npairs = len(pairs)
+    if len(P1s) != npairs or (P0s is not None and len(P0s) != npairs):
+        raise ValueError('P1s (and P0s) must hold one entry per pair.')
+    ims = [np.asarray(im) for im in ims]
+    dtype = ims[0].dtype if ims and ims[0].dtype in _RECTIFY_BATCH_DTYPE else np.dtype(np.float64)
+    ims = [np.ascontiguousarray(im, dtype=dtype) for im in ims]
+    dims = [image_dims(im.shape) for im in ims]
+    if len({d[2] for d in dims}) > 1:
+        raise TypeError('Input images must have the same number of channels.')
+    nchan = dims[0][2] if dims else 1
+    for a, b in pairs:
+        if 0 <= a < len(ims) and 0 <= b < len(ims) and ims[a].shape != ims[b].shape:
+            raise TypeError("Input images must have same size.")
+    sizes = np.array([(d[1], d[0]) for d in dims], dtype=np.int32).reshape(-1, 2)
+    use = np.array([P is not None for P in P1s], dtype=np.int32)
+
+    def cameras(Ps, name):
+        out = np.zeros((npairs, 12))
+        for p, P in enumerate(Ps):
+            if P is None:
+                continue
+            P = np.asarray(P, dtype=np.float64)
+            if P.shape != (3, 4):
+                raise TypeError('%s must be camera matrices.' % name)
+            out[p] = P.reshape(12)
+        return out
+    c1 = cameras(P1s, 'P1s')
+    c0 = None
+    if P0s is not None:
+        if any(P is None for P, u in zip(P0s, use) if u):
+            raise TypeError('P0s must be camera matrices.')
+        c0 = cameras(P0s, 'P0s')
+    packed = np.concatenate([im.reshape(-1) for im in ims]) if ims else np.zeros(0, dtype)
+    r0, r1 = NdArray(dtype=dtype), NdArray(dtype=dtype)
+    ri0, ri1 = NdArray(dtype='int32'), NdArray(dtype='int32')
+    box = np.zeros((npairs, 4), np.int32)
+    out_off = np.zeros(npairs + 1, np.int64)
+    check(_spv_rectify_batch(packed.ctypes.data, _RECTIFY_BATCH_DTYPE[dtype], sizes.ctypes.data, len(sizes), nchan,
+                             float(sampling_factor), pairs.ctypes.data, npairs,
+                             c0.ctypes.data if c0 is not None else None, c1.ctypes.data, use.ctypes.data,
+                             1 if crop_invalid else 0, ct.byref(r0), ct.byref(r1), ct.byref(ri0), ct.byref(ri1),
+                             box.ctypes.data, out_off.ctypes.data))
+    r0, r1, ri0, ri1 = (a.asarray().reshape(-1) for a in (r0, r1, ri0, ri1))
+    out = []
+    for p in range(npairs):
+        rows, cols = int(box[p, 1] - box[p, 0]), int(box[p, 3] - box[p, 2])
+        if not use[p] or rows * cols == 0:
+            out.append(None)
+            continue
+        lo, hi = int(out_off[p]), int(out_off[p + 1])
+        vshape = (rows, cols) if nchan == 1 else (rows, cols, nchan)
+        out.append((r0[lo * nchan:hi * nchan].reshape(vshape), r1[lo * nchan:hi * nchan].reshape(vshape),
+                    ri0[lo:hi].reshape(rows, cols), ri1[lo:hi].reshape(rows, cols)))
+    return out
