@@ -6,6 +6,7 @@ example/ex01_essential_estimation.py does.  A multi-view front-end has N views a
 runs all of them through the many-pairs forms of the same steps, with every intermediate resident in HBM:
 
     l1k2_batch               exact L1 2-NN of every (query view, database view) pair; or, with --matcher cascade,
+    normalize_batch          every view's uint8 descriptors normalised per view, as the reference's front-end does, and
     cascade_batch            the cascade hash + L1 refine of every pair, each view coded and bucket-sorted once
     ratio_test               over the concatenated result
     match_coordinates_batch  matches -> per-pair homogeneous coordinates and pair_off
@@ -94,7 +95,7 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
         m = feature.auto_hash_bit_rate(*[max(len(t) for t in tables)] * 2)
         if m < 4:
             raise ValueError("tables too small for the cascade hash (the front-end falls back to brute force)")
-        rows = torch.cat([spv.normalize(desc[a:b].to(torch.float32)) for a, b in zip(seg[:-1], seg[1:])])
+        rows = spv.normalize_batch(desc, seg)
         hd = torch.from_numpy(feature.generate_hash_dict(hash_seed, rows.shape[1], m, 2)).to(table.device)
         idx, dist, _ = spv.cascade_batch(rows, seg, pairs, hd, g=2)
     else:

@@ -159,7 +159,7 @@ const char *spv_version(void);
  * "cascade_buckets", "cascade_probe_refine", "cascade_batch_project", "cascade_batch_buckets", "cascade_batch_probe", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "rectify_batch_bounds", "rectify_batch_box",
  * "rectify_batch", "ransac_batch_score",
  * "ransac_batch_reduce",
- * "gather_match_coords_batch") are bracketed by hipEvents recorded on the
+ * "gather_match_coords_batch", "normalize_batch_stats", "normalize_batch_finish", "normalize_batch") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
  * last reset. */
@@ -1078,6 +1078,53 @@ size_t spv_normalize_workspace_bytes(int dim);
 size_t spv_normalize_workspace_bytes_rows(int rows, int dim);
 int spv_normalize_device(const float *d_x, int rows, int dim, float *d_out_f32, uint8_t *d_out_u8,
                          void *d_ws, size_t ws_bytes, void *stream);
+
+/* spv_normalize_device for every table of a collection in one fixed chain of launches (normalize_batch.hip): the
+ * step between spv_sift_batch (or spv_sift_split) and spv_cascade_batch_device, whose rows are the normalised tables.
+ *   x        dtype[seg_off[nseg], dim]: the tables of nseg sets back to back; SPV_NORMALIZE_F32 float32, or
+ *            SPV_NORMALIZE_U8 uint8, whose values stand for their float32 conversions (no float copy is made).
+ *   seg_off  the seg_off of spv_l1k2_batch_device: host long long[nseg + 1], non-decreasing, seg_off[0] = 0,
+ *            seg_off[nseg] = total < 2^31; set s is rows [seg_off[s], seg_off[s + 1]) and may be empty.
+ *   out_f32  float32[total, dim16], out_u8 uint8[total, dim16], dim16 = roundup(dim, 16); either may be NULL, not both.
+ * For every set the rows [seg_off[s], seg_off[s + 1]) of both outputs are bit for bit what spv_normalize_device
+ * writes for that set alone (for SPV_NORMALIZE_U8: for that set's rows converted to float32), whatever else the
+ * collection holds, wherever the set stands in it and however the call cuts the work: the padding columns, and the
+ * NaN rows (and their uint8 image) of a constant column or a one-row set, which divide 0 by 0, included.  Every
+ * element of every non-empty set's rows is written exactly once; nothing else is touched.
+ * SPV_ERR_INVALID, nothing launched, no output touched: a seg_off outside the rules, nseg < 0, dim < 1 or
+ * dim > 2048, dim == 1 with any set of more than one row (the single call's refusal), an unknown dtype, a NULL
+ * required pointer (x, the workspace: only where total > 0), a workspace shorter than the size query's or not
+ * 16-byte aligned, a d_x or d_out_f32 not aligned to its element size.  nseg = 0 and all-empty collections are valid
+ * and launch nothing.  One device; asynchronous on `stream` but for the upload of its small item and segment
+ * tables, which the call waits for.  Very large single tables remain the job of spv_normalize_device (its folded
+ * column sums are not taken here).
+ *
+ * The launches (kernel names for spv_profile_read): "normalize_batch_stats", SPV_NORMALIZE_U8 only -- per work
+ * item (256 rows of one set) and column the integer sum, minimum and maximum; "normalize_batch_finish" -- per (set,
+ * 16-column block): where every integer column sum of the block is at most 2^24 it IS numpy's row-ordered float32
+ * sum (every prefix is an integer that float32 holds: any uint8 set of up to 65793 rows), so mean = float(S) /
+ * float(rows); every other block, and every float32 set, is walked in row order as spv_normalize_device does, its
+ * minimum and maximum taken on the way; "normalize_batch" -- the element-wise pass over the same work items.
+ * "normalize" does not tick.
+ *
+ * spv_normalize_batch_plan: host only, touches no device.  out = {non-empty sets, work items, workspace bytes, total
+ * rows}; items may be NULL, otherwise int32[items_cap, 3] receives the first min(work items, items_cap) work items as
+ * (set, first row within the set, rows): exactly the list the device call walks, in its order -- set by set, rows
+ * in order, every row once, no item in two sets.  compute_units >= 1 caps the grid (32 workgroups per compute
+ * unit, each walking items b, b + grid, ...) and does not change the items.  SPV_ERR_INVALID leaves out and items
+ * untouched.  spv_normalize_batch_workspace_bytes: out[2] (0 for arguments the plan rejects): 12 bytes per work
+ * item, 8 per set, the statistics float32[nseg, 2, dim], and for SPV_NORMALIZE_U8 4 bytes per work item and column,
+ * each piece rounded up to 256.
+ * spv_normalize_batch: host pointers, on the first selected device; touches none when total is 0. */
+#define SPV_NORMALIZE_F32 0
+#define SPV_NORMALIZE_U8 1
+int spv_normalize_batch_plan(const long long *seg_off, int nseg, int dim, int dtype, int compute_units,
+                             long long out[4], int32_t *items, long long items_cap);
+size_t spv_normalize_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, int dtype);
+int spv_normalize_batch_device(const void *d_x, int dtype, const long long *seg_off, int nseg, int dim,
+                               float *d_out_f32, uint8_t *d_out_u8, void *d_ws, size_t ws_bytes, void *stream);
+int spv_normalize_batch(const void *x, int dtype, const long long *seg_off, int nseg, int dim,
+                        float *out_f32, uint8_t *out_u8);
 
 /* Device form of spv_dlt_score_hypotheses: P0 is a HOST pointer (12 doubles), d_P1s
  * double[nhyp,12], d_counts int32[nhyp] (zeroed by the call), d_mask uint8[nhyp,npt] or NULL. */

@@ -158,6 +158,10 @@ PROTOTYPES = {
     "spv_normalize_workspace_bytes": (sz, [i]),
     "spv_normalize_workspace_bytes_rows": (sz, [i, i]),
     "spv_normalize_device": (i, [vp, i, i, vp, vp, vp, sz, vp]),
+    "spv_normalize_batch_plan": (i, [vp, i, i, i, i, pll, vp, ll]),
+    "spv_normalize_batch_workspace_bytes": (sz, [vp, i, i, i]),
+    "spv_normalize_batch_device": (i, [vp, i, vp, i, i, vp, vp, vp, sz, vp]),
+    "spv_normalize_batch": (i, [vp, i, vp, i, i, vp, vp]),
     "spv_dlt_score_hypotheses_device": (i, _score_device + [vp]),
     "spv_dlt_score_workspace_bytes": (sz, [i, ll]),
     "spv_dlt_score_hypotheses_device_ws": (i, _score_device + [vp, sz, vp]),

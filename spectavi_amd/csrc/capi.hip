@@ -936,6 +936,32 @@ int host_normalize(const float *x, int rows, int dim, float *out_f32, uint8_t *o
   return SPV_OK;
 }
 
+// The many-tables normalisation through host pointers, on the first selected device: the whole of x up, one
+// normalize_batch_run, the wanted tables back.  A collection without a row touches no device.
+int host_normalize_batch(const void *x, int dtype, const long long *seg_off, int nseg, int dim, float *out_f32,
+                         uint8_t *out_u8) {
+  NormalizeBatchPlan p;
+  SPV_TRY(normalize_batch_plan(seg_off, nseg, dim, dtype, &p));
+  if (!out_f32 && !out_u8) return set_error(SPV_ERR_INVALID, "neither the float32 nor the uint8 table is wanted");
+  if (p.total_rows == 0) return SPV_OK;
+  if (!x) return set_error(SPV_ERR_INVALID, "null pointer");
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t xb = (size_t)p.total_rows * dim * (dtype == SPV_NORMALIZE_U8 ? 1 : sizeof(float));
+  const size_t ub = (size_t)p.total_rows * ((dim + 15) / 16 * 16), fb = ub * sizeof(float);
+  DevBuf dx, df, du, ws;
+  SPV_TRY(dx.upload(x, xb, st));
+  if (out_f32) SPV_TRY(df.alloc(fb));
+  if (out_u8) SPV_TRY(du.alloc(ub));
+  SPV_TRY(ws.alloc(p.total_bytes));
+  SPV_TRY(normalize_batch_run(dx.p, dtype, seg_off, nseg, dim, out_f32 ? df.as<float>() : nullptr,
+                              out_u8 ? du.as<uint8_t>() : nullptr, ws.p, p.total_bytes, st));
+  if (out_f32) SPV_TRY(df.copy_out(out_f32, fb, st));
+  if (out_u8) SPV_TRY(du.copy_out(out_u8, ub, st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  return SPV_OK;
+}
+
 // Hyperplanes as the reference draws them (src/CascadingHashNn.h:86-100):
 // one std::mt19937 stream, std::normal_distribution<float>(0,1), table-major,
 // then dim (i), then bit (j).
@@ -1356,6 +1382,38 @@ size_t spv_normalize_workspace_bytes_rows(int rows, int dim) {
 int spv_normalize_device(const float *d_x, int rows, int dim, float *d_out_f32, uint8_t *d_out_u8,
                          void *d_ws, size_t ws_bytes, void *stream) {
   return api([&] { return normalize_run(d_x, rows, dim, d_out_f32, d_out_u8, d_ws, ws_bytes, static_cast<hipStream_t>(stream)); });
+}
+
+int spv_normalize_batch(const void *x, int dtype, const long long *seg_off, int nseg, int dim, float *out_f32,
+                        uint8_t *out_u8) {
+  return host_api([&] { return host_normalize_batch(x, dtype, seg_off, nseg, dim, out_f32, out_u8); });
+}
+int spv_normalize_batch_plan(const long long *seg_off, int nseg, int dim, int dtype, int compute_units, long long out[4],
+                             int32_t *items, long long items_cap) {
+  return api([&] {
+    if (compute_units < 1 || !out || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
+    NormalizeBatchPlan p;
+    SPV_TRY(normalize_batch_plan(seg_off, nseg, dim, dtype, &p));
+    out[0] = p.sets;
+    out[1] = (long long)p.items.size();
+    out[2] = (long long)p.total_bytes;
+    out[3] = p.total_rows;
+    if (items) memcpy(items, p.items.data(), (size_t)std::min<long long>(items_cap, (long long)p.items.size()) * sizeof(NormalizeBatchItem));
+    return (int)SPV_OK;
+  });
+}
+size_t spv_normalize_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, int dtype) {
+  NormalizeBatchPlan p;
+  const int st = guard([&] { return normalize_batch_plan(seg_off, nseg, dim, dtype, &p); });
+  if (st != SPV_OK) clear_error();
+  return st == SPV_OK ? p.total_bytes : 0;
+}
+int spv_normalize_batch_device(const void *d_x, int dtype, const long long *seg_off, int nseg, int dim, float *d_out_f32,
+                               uint8_t *d_out_u8, void *d_ws, size_t ws_bytes, void *stream) {
+  return api([&] {
+    return normalize_batch_run(d_x, dtype, seg_off, nseg, dim, d_out_f32, d_out_u8, d_ws, ws_bytes,
+                               static_cast<hipStream_t>(stream));
+  });
 }
 int spv_sift_split(const float *table, int rows, float *geom, uint8_t *desc) {
   return host_api([&] { return host_sift_split(table, rows, geom, desc); });

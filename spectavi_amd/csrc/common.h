@@ -398,6 +398,29 @@ size_t normalize_workspace_bytes_rows(int rows, int dim);
 int normalize_run(const float *d_x, int rows, int dim, float *d_out_f32, unsigned char *d_out_u8,
                   void *d_ws, size_t ws_bytes, hipStream_t stream);
 
+// ---- normalisation of many tables in one chain of launches (normalize_batch.hip) -------
+constexpr int kNormalizeBatchMaxDim = 2048;
+constexpr int kNormalizeBatchItemRows = 256;   // rows per work item
+constexpr int kNormalizeBatchGroupsPerCu = 32; // the grid cap: workgroups per compute unit, each walking its items
+// One workgroup's step: rows [row0, row0 + rows) of set `set`, row0 counted within the set.
+struct NormalizeBatchItem {
+  int32_t set, row0, rows;
+};
+// Everything normalize_batch_run launches for a collection, a function of seg_off, dim and dtype alone.
+struct NormalizeBatchPlan {
+  long long sets = 0, total_rows = 0;     // non-empty sets; rows in all
+  std::vector<NormalizeBatchItem> items;  // set by set, every set's rows in blocks of kNormalizeBatchItemRows, in order
+  // workspace: byte offsets, in this order.  The device form of `items`, seg_off as uint32[nseg + 1], the first
+  // item at or after every set int32[nseg + 1], (mean, norm) float[nseg][2][dim], and for uint8 input the items'
+  // partial statistics uint32[items][dim].
+  size_t off_items = 0, off_seg = 0, off_item0 = 0, off_stats = 0, off_part = 0, total_bytes = 0;
+};
+// SPV_ERR_INVALID (message set, *p untouched) for what include/spectavi_amd.h rejects; host only
+int normalize_batch_plan(const long long *seg_off, int nseg, int dim, int dtype, NormalizeBatchPlan *p);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the call's tables.
+int normalize_batch_run(const void *d_x, int dtype, const long long *seg_off, int nseg, int dim, float *d_out_f32,
+                        uint8_t *d_out_u8, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
 // ---- multi-device result gather over RCCL (gather.hip) -------------------------------
 struct GatherCtx;                    // communicator clique + one stream per rank, cached per device list
 std::mutex &gather_mutex();          // held by the caller around every use of a clique

@@ -918,6 +918,75 @@ def normalize(x, want_float=True, want_ubyte=False, workspace=None):
     return out if want_float else u8
 
 
+NORMALIZE_F32, NORMALIZE_U8 = 0, 1  # SPV_NORMALIZE_* of include/spectavi_amd.h
+
+
+def _normalize_batch_args(seg_off, total_rows, dim, dtype):
+    """seg_off -> int64[nseg + 1], dtype -> SPV_NORMALIZE_*; ValueError for anything spv_normalize_batch_device would
+    reject or that does not describe a table of total_rows rows (the seg_off rules of _batch_args).  Touches no device."""
+    seg = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
+    if seg.size < 1 or seg[0] != 0 or np.any(np.diff(seg) < 0):
+        raise ValueError("seg_off must start at 0 and never decrease")
+    if total_rows is not None and int(seg[-1]) != int(total_rows):
+        raise ValueError("seg_off ends at %d, x has %d rows" % (int(seg[-1]), int(total_rows)))
+    if int(seg[-1]) >= 2 ** 31:
+        raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    if not 1 <= int(dim) <= 2048:
+        raise ValueError("the many-tables form takes 1 <= dim <= 2048 (dim=%d)" % dim)
+    if dim == 1 and np.any(np.diff(seg) > 1):
+        raise ValueError("normalisation of a single-column table is not supported (dim=1)")
+    name = str(dtype)[6:] if isinstance(dtype, torch.dtype) else np.dtype(dtype).name
+    if name not in ("float32", "uint8"):
+        raise TypeError("dtype must be float32 or uint8")
+    return seg, NORMALIZE_U8 if name == "uint8" else NORMALIZE_F32
+
+
+def normalize_batch_plan(seg_off, dim, dtype, compute_units=256, want_items=False):
+    """The work items normalize_batch() walks for a collection (spv_normalize_batch_plan; host only, no device
+    touched): dict of sets (non-empty sets), items (workgroup steps), workspace_bytes and rows (in all).  dtype:
+    torch / numpy float32 or uint8.  With want_items also the items, int32[items, 3] = (set, first row within the
+    set, rows), in the order the device call walks them."""
+    seg, kind = _normalize_batch_args(seg_off, None, dim, dtype)
+    out = (ct.c_longlong * 4)()
+    check(clib.spv_normalize_batch_plan(seg.ctypes.data, seg.size - 1, int(dim), kind, int(compute_units), out, None, 0))
+    plan = dict(sets=int(out[0]), items=int(out[1]), workspace_bytes=int(out[2]), rows=int(out[3]))
+    if want_items:
+        items = np.empty((plan["items"], 3), np.int32)
+        check(clib.spv_normalize_batch_plan(seg.ctypes.data, seg.size - 1, int(dim), kind, int(compute_units), out,
+                                            items.ctypes.data, len(items)))
+        return plan, items
+    return plan
+
+
+def normalize_batch(x, seg_off, want_float=True, want_ubyte=False, workspace=None):
+    """`normalize` of every table of a collection in one fixed chain of launches (spv_normalize_batch_device): x CUDA
+    float32 or uint8 [total, dim] holds the tables back to back, set s = rows seg_off[s]:seg_off[s + 1] (empty sets
+    allowed); uint8 values stand for their float32 conversions, no float copy is made.  Returns what `normalize`
+    returns, for all rows: the float32 [total, dim16] table and / or its uint8 image, every set's rows bit for bit
+    `normalize` of that set alone.  Asynchronous on the current stream but for the upload of the work table."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("x must be a float32 or uint8 tensor")
+    _need(x, x.dtype, "x")
+    if x.dim() != 2:
+        raise ValueError("x must be [total_rows, dim]")
+    if not (want_float or want_ubyte):
+        raise ValueError("neither the float32 nor the uint8 table is wanted")
+    total, dim = x.shape
+    seg, kind = _normalize_batch_args(seg_off, total, dim, x.dtype)
+    dim16 = (dim + 15) // 16 * 16
+    out = torch.empty((total, dim16), dtype=torch.float32, device=x.device) if want_float else None
+    u8 = torch.empty((total, dim16), dtype=torch.uint8, device=x.device) if want_ubyte else None
+    nbytes = clib.spv_normalize_batch_workspace_bytes(seg.ctypes.data, seg.size - 1, dim, kind)
+    with _on_device_of(x) as stream:
+        ws = (workspace or _default_ws).get(nbytes, x.device)
+        check(clib.spv_normalize_batch_device(x.data_ptr(), kind, seg.ctypes.data, seg.size - 1, dim,
+                                              out.data_ptr() if want_float else None,
+                                              u8.data_ptr() if want_ubyte else None, ws.data_ptr(), ws.numel(), stream))
+    if want_float and want_ubyte:
+        return out, u8
+    return out if want_float else u8
+
+
 def seven_point(x, xp, want_basis=False):
     """Seven-point algorithm for n 7-subsets resident in HBM (reference src/FundamentalMatrixFitter.h:108-246):
     x, xp CUDA float64 [n,7,2] euclidean.  Returns (nroot int32 [n], Fs float64 [n,3,3,3], NaN in the slots of

@@ -489,6 +489,33 @@ def normalize_to_ubyte_and_multiple_16_dim_gpu(x, want_ubyte=False):
     return (out, u8) if want_ubyte else out
 
 
+def normalize_to_ubyte_and_multiple_16_dim_batch(tables, want_ubyte=False):
+    """`normalize_to_ubyte_and_multiple_16_dim_gpu` for many tables in one call (an addition: the reference
+    normalises table by table).  `tables` is a list of arrays [rows_i, dim], all float32 or all uint8 (whose values
+    stand for their float32 conversions), one width for all; empty tables are allowed.
+
+    Returns a list with one result per table, each what normalize_to_ubyte_and_multiple_16_dim_gpu(table,
+    want_ubyte) returns; the arrays of the list are views of one concatenated result."""
+    tables = [np.ascontiguousarray(t) for t in tables]
+    if not tables:
+        return []
+    dim = tables[0].shape[1] if tables[0].ndim == 2 else -1
+    dtype = tables[0].dtype
+    if dtype not in (np.float32, np.uint8) or any(t.ndim != 2 or t.dtype != dtype or t.shape[1] != dim for t in tables):
+        raise ValueError("tables must be arrays [rows, dim] of one width, all float32 or all uint8")
+    if not 1 <= dim <= 2048:
+        raise ValueError("the many-tables form takes 1 <= dim <= 2048 (dim=%d)" % dim)
+    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    x = np.concatenate(tables)
+    dim16 = (dim + 15) // 16 * 16
+    out = np.empty((int(seg[-1]), dim16), np.float32)
+    u8 = np.empty((int(seg[-1]), dim16), np.uint8) if want_ubyte else None
+    check(clib.spv_normalize_batch(x.ctypes.data, int(dtype == np.uint8), seg.ctypes.data, len(tables), dim,
+                                   out.ctypes.data, u8.ctypes.data if want_ubyte else None))
+    cut = list(zip(seg[:-1], seg[1:]))
+    return [(out[a:b], u8[a:b]) for a, b in cut] if want_ubyte else [out[a:b] for a, b in cut]
+
+
 # ==================================================================================
 # SIFT                        (reference spectavi/feature.py:17-148)
 # ==================================================================================
