@@ -138,6 +138,26 @@ int spv_l1k2_get_prune_form(void);
 int spv_l1k2_prune_form_of(int xrows, int yrows, int dim);
 /* spv_l1k2_bound_table for either table (which = RECIPE or TUNED). */
 int spv_l1k2_bound_table_of(int which, int8_t phi[256][4], int *p, int *m);
+/* The matrix format of the WIDE form's bound.  I8: the rank-4 int8 table, 64 v_mfma_i32_32x32x32_i8 per 64-row tile and
+ * wave.  FP6: the rank-5 e2m3 table of spv_l1k2_bound6_table, 40 v_mfma_scale_f32_32x32x64_f8f6f4 with unit scales, exact in
+ * f32 because every sum is a multiple of 1/64 below 2^24/64.  DEFAULT (also SPECTAVI_L1K2_PRUNE_MATRIX unset or "default";
+ * "i8" and "fp6" name the others): FP6 exactly where prune mode AUTO takes the path, the form is WIDE and the bound table
+ * setting is DEFAULT; I8 under prune mode ON and with a table named.  FP6 forces it onto every shape whose form is WIDE;
+ * the NARROW form is always I8.  Results are bit-identical either way, and neither spv_l1k2_plan nor
+ * spv_l1k2_workspace_bytes depends on it. */
+#define SPV_L1K2_PRUNE_MATRIX_DEFAULT (-1)
+#define SPV_L1K2_PRUNE_MATRIX_I8 0
+#define SPV_L1K2_PRUNE_MATRIX_FP6 1
+int spv_l1k2_set_prune_matrix(int matrix);
+/* The setting in force (the setter's last value, else SPECTAVI_L1K2_PRUNE_MATRIX, else DEFAULT). */
+int spv_l1k2_get_prune_matrix(void);
+/* The matrix format that spv_l1k2_device would run for this shape under the settings in force (host only, no GPU
+ * involved): I8 or FP6, or -1 where it would not take the bound path at all. */
+int spv_l1k2_prune_matrix_of(int xrows, int yrows, int dim);
+/* The FP6 bound's table (host only, no GPU involved): k = the five e2m3 features of every byte value as the integers k
+ * of the values k/8, and integers p, m in units of 1/64 with p |a-b| >= m - k(a).k(b) for all bytes a, b, m being the
+ * largest such. */
+int spv_l1k2_bound6_table(int8_t k[256][5], int *p, int *m);
 /* Host statement of the 16-byte record format (no GPU involved), for callers that run their own
  * collective on raw records.  pack: idx uint64[n,2] ((size_t)-1 = no neighbour), dist32 = int32 or
  * float32 [n,2] -> rec int32[n,4] = (idx0, idx1, d0 bits, d1 bits), -1 = no neighbour.

@@ -51,6 +51,10 @@ PROTOTYPES = {
     "spv_l1k2_get_prune_form": (i, []),
     "spv_l1k2_prune_form_of": (i, [i, i, i]),
     "spv_l1k2_bound_table_of": (i, [i, vp, pi, pi]),
+    "spv_l1k2_set_prune_matrix": (i, [i]),
+    "spv_l1k2_get_prune_matrix": (i, []),
+    "spv_l1k2_prune_matrix_of": (i, [i, i, i]),
+    "spv_l1k2_bound6_table": (i, [vp, pi, pi]),
     "spv_records_pack": (i, [pu64, vp, ll, pi32]),
     "spv_records_unpack": (i, [pi32, ll, i, ll, pu64, vp]),
     "spv_release_cached_memory": (None, []),

@@ -1127,6 +1127,33 @@ int spv_l1k2_bound_table_of(int which, int8_t phi[256][4], int *p, int *m) {
   return b.ok ? SPV_OK : set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
 }
 
+int spv_l1k2_set_prune_matrix(int matrix) {
+  clear_error();
+  if (matrix != SPV_L1K2_PRUNE_MATRIX_DEFAULT && matrix != SPV_L1K2_PRUNE_MATRIX_I8 && matrix != SPV_L1K2_PRUNE_MATRIX_FP6)
+    return set_error(SPV_ERR_INVALID, "bound matrix format %d", matrix);
+  l1k2_set_prune_matrix(matrix);
+  return SPV_OK;
+}
+
+int spv_l1k2_get_prune_matrix(void) { return l1k2_get_prune_matrix(); }
+
+int spv_l1k2_prune_matrix_of(int xrows, int yrows, int dim) {
+  if (!l1k2_shape_ok(xrows, yrows, dim)) return -1;
+  const L1K2Plan p = l1k2_plan(xrows, yrows, dim);
+  return p.dim_pad >= 0 && p.path == kL1K2Bound ? p.matrix : -1;
+}
+
+int spv_l1k2_bound6_table(int8_t k[256][5], int *p, int *m) {
+  clear_error();
+  if (!k || !p || !m) return set_error(SPV_ERR_INVALID, "null output");
+  const L1K2Bound6 &b = l1k2_bound6();
+  for (int a = 0; a < 256; ++a)
+    for (int f = 0; f < 5; ++f) k[a][f] = b.k[a][f];
+  *p = b.p;
+  *m = b.m;
+  return b.ok ? SPV_OK : set_error(SPV_ERR_INTERNAL, "the FP6 L1 bound table failed its own check");
+}
+
 void spv_release_cached_memory(void) { release_transfer_caches(); }
 
 void spv_profile_enable(int on) {

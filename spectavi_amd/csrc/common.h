@@ -121,6 +121,7 @@ struct L1K2Knobs {
   bool prune_stats;  // SPECTAVI_L1K2_PRUNE_STATS=1: the bound path prints its counters (synchronises)
   int bound;         // SPECTAVI_L1K2_BOUND: the bound table a process starts with (-1 default, 0 recipe, 1 tuned)
   int prune_form;    // SPECTAVI_L1K2_PRUNE_FORM: the form of the bound kernel a process starts with (-1 default, 0 narrow, 1 wide)
+  int prune_matrix;  // SPECTAVI_L1K2_PRUNE_MATRIX=default|i8|fp6: the matrix format of the wide form's bound a process starts with (-1, 0, 1)
 };
 const L1K2Knobs &l1k2_knobs();
 
@@ -146,6 +147,7 @@ struct L1K2Plan {
   dim3 bound_grid;       // l1k2_prune_kernel: (blocks of 256 queries, slices)
   int bound;             // ... and the table it runs with (kL1K2BoundRecipe / kL1K2BoundTuned)
   int form;              // ... and the form that runs (kL1K2FormNarrow / kL1K2FormWide)
+  int matrix;            // ... and its matrix format (kL1K2MatrixI8 / kL1K2MatrixFp6; FP6 runs its own table, l1k2_bound6, whatever `bound` says)
   dim3 bound_wide_grid;  // l1k2_prune_wide_kernel: (blocks of 512 queries, slices)
   unsigned work_grid;    // tile kernel over the bound path's work list: kWorkSub blocks for every workgroup there
   unsigned merge_grid;
@@ -200,6 +202,16 @@ int l1k2_get_bound();
 enum { kL1K2FormNarrow = 0, kL1K2FormWide = 1 };             // l1k2_prune_kernel (32-row tiles, 256 queries); l1k2_prune_wide_kernel (64, 512)
 int l1k2_set_prune_form(int form);                           // -1 default (wide where `auto` takes the path and the grid fills the chip), 0, 1; returns the setting before
 int l1k2_get_prune_form();
+// The rank-5 FP6 table of l1k2_bound_fp6.h: an entry is the integer k of the e2m3 value k/8, p and m are in units of 1/64.
+struct L1K2Bound6 {
+  int8_t k[256][5];
+  int p, m;            // p |a-b| >= m - k(a).k(b) for all bytes a, b
+  bool ok;             // on the e2m3 grid, the inequality on every byte pair, and every sum exact in f32
+};
+const L1K2Bound6 &l1k2_bound6();                             // host only, built once
+enum { kL1K2MatrixI8 = 0, kL1K2MatrixFp6 = 1 };              // l1k2_prune_wide_kernel; l1k2_prune_wide6_kernel
+int l1k2_set_prune_matrix(int matrix);                       // -1 default (FP6 where `auto` takes the path, the form is wide and the table the default one), 0, 1; returns the setting before
+int l1k2_get_prune_matrix();
 int l1k2_set_prune(int mode);                                // -1 auto, 0 never, 1 wherever possible; returns the mode before
 int l1k2_get_prune();
 // The bound path's part of a plan whose slicing is done: its scratch, the next pieces of the plan's walk, and

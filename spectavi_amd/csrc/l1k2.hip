@@ -451,6 +451,8 @@ const L1K2Knobs &l1k2_knobs() {
     k.bound = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
     v = getenv("SPECTAVI_L1K2_PRUNE_FORM");
     k.prune_form = (v && v[0] == '0') ? 0 : (v && v[0] == '1') ? 1 : -1;
+    v = getenv("SPECTAVI_L1K2_PRUNE_MATRIX");
+    k.prune_matrix = (v && (v[0] == 'i' || v[0] == '0')) ? 0 : (v && (v[0] == 'f' || v[0] == '1')) ? 1 : -1;
     return k;
   }();
   return knobs;

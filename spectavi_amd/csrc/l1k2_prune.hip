@@ -77,7 +77,22 @@
 // between the two drains at the end of a tile: moved into a function, either changes the narrow kernel's schedule ahead of
 // its loop, which tests/test_l1k2_prune_arm_isa.py holds fixed.  spv_l1k2_set_prune_form / SPECTAVI_L1K2_PRUNE_FORM force
 // either form.
+//
+// Two matrix formats of the wide form.  The int8 bound above costs a wave 64 MFMAs per 64-row tile, and 1e12 pairs x 512
+// MACs is a floor of the matrix pipe's own time whatever the schedule.  l1k2_prune_wide6_kernel does the same job with 40:
+// a rank-5 table of FP6 (e2m3) features (l1k2_bound_fp6.h; a feature is k/8, k on the e2m3 grid, so G, p and m are integers
+// in units of 1/64), K = 640 per pair in ten v_mfma_scale_f32_32x32x64_f8f6f4 with unit scales per row half and column
+// block.  Every value an accumulator ever holds is a multiple of 1/64 below 2^24/64 (make_bound6 refuses a table for which
+// it is not), so the f32 accumulation is exact and the bound stays the integer inequality above; the instruction was checked
+// bit for bit against an int64 GEMM first (tools/exp/mfma_fp6_exp.hip).  The tile loop is the wide form's, written once
+// (wide_body) over a matrix format X: MatI8 or MatFp6 hold the operand types, the A reads, the B load, the MFMA and the
+// armed value; geometry, protocol, share rule and hand-over are the same code.  The feature row keeps its 512 bytes (480
+// used, see l1k2_feature6_kernel), so Stage and the workspace do not move.  l1k2_prune_plan takes FP6 exactly where `auto`
+// takes the path, the form is wide and no table is named (the benchmark's shapes); prune mode 1 and a named table run the
+// int8 kernels, whose decisions the case tables of the tests pin.  spv_l1k2_set_prune_matrix / SPECTAVI_L1K2_PRUNE_MATRIX
+// force either, tests/test_l1k2_prune_fp6_isa.py holds the FP6 kernel's budgets (256 VGPRs, no spill, 40 MFMAs in one run).
 #include "common.h"
+#include "l1k2_bound_fp6.h"
 #include "l1k2_bound_tuned.h"
 
 #include <atomic>
@@ -91,6 +106,9 @@ namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+typedef int v2i __attribute__((ext_vector_type(2)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 
 constexpr int kAuxThreads = 256;              // the feature and threshold-init kernels
 constexpr int kQPerWave = 64;                 // two MFMA column blocks of 32
@@ -128,9 +146,14 @@ struct PruneForm {
   // were timed at 1M x 1M, DESIGN.md 4.1, "64-row tiles"
   static constexpr int kOctetPairs = 8;
   static constexpr bool kRaggedFromCopy = H > 1;           // see Stage::ragged_offsets
+  static constexpr bool kRefreshFromCopy = false;          // see `refresh` in wide_body
 };
 using Narrow = PruneForm<1>;
 using Wide = PruneForm<2>;
+// the wide form with the FP6 bound (l1k2_prune_wide6_kernel): every number of the form, and LDS arrays of its own
+struct Wide6 : PruneForm<2> {
+  static constexpr bool kRefreshFromCopy = true;
+};
 
 // Phase stamps (-DSPV_L1K2_PHASE_STAMPS, never in the shipped library): every wave sums the shader cycles of each
 // phase of its tiles in scalar registers and lane 0 stores the sums once, when the wave ends; l1k2_prune_run
@@ -143,6 +166,7 @@ enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPh
 #ifdef SPV_L1K2_PHASE_STAMPS
 #define SPV_STAMP_PARAM , unsigned long long *stamps_out
 #define SPV_STAMP_ARG , d_stamps
+#define SPV_STAMP_PASS , stamps_out
 __device__ __forceinline__ unsigned long long stamp() {
   unsigned long long v;
   __builtin_amdgcn_sched_barrier(0);
@@ -153,6 +177,7 @@ __device__ __forceinline__ unsigned long long stamp() {
 #else
 #define SPV_STAMP_PARAM
 #define SPV_STAMP_ARG
+#define SPV_STAMP_PASS
 __device__ __forceinline__ unsigned long long stamp() { return 0; }
 #endif
 
@@ -454,9 +479,13 @@ using Live = std::conditional_t<H == 1, uint32_t, unsigned long long>;
 __device__ __forceinline__ int first_pair(uint32_t live) { return __clz(live | 1u); }
 __device__ __forceinline__ int first_pair(unsigned long long live) { return __clzll(live | 1ull); }
 
-// One bit per accumulator register: the register's sign says that the pair is ruled out (sum < threshold).
-template <int H>
-__device__ __forceinline__ Live<H> fold_signs(const v16i (&acc)[H][2]) {
+// One bit per accumulator register: the register's sign says that the pair is ruled out (sum < threshold).  The
+// accumulators are int32 or, in the FP6 form, f32; an element is passed by value (a bit cast applied to the element
+// expression itself reads element 0 of the vector whatever the index).
+__device__ __forceinline__ uint32_t sign_word(int v) { return (uint32_t)v; }
+__device__ __forceinline__ uint32_t sign_word(float v) { return __builtin_bit_cast(uint32_t, v); }
+template <int H, class Acc>
+__device__ __forceinline__ Live<H> fold_signs(const Acc (&acc)[H][2]) {
   Live<H> skip = 0;
 #pragma unroll
   for (int h = 0; h < H; ++h) {
@@ -464,7 +493,7 @@ __device__ __forceinline__ Live<H> fold_signs(const v16i (&acc)[H][2]) {
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
 #pragma unroll
-      for (int v = 0; v < 16; ++v) sk = __builtin_amdgcn_alignbit(sk, (uint32_t)acc[h][b][v], 31);
+      for (int v = 0; v < 16; ++v) sk = __builtin_amdgcn_alignbit(sk, sign_word(acc[h][b][v]), 31);
     }
     if constexpr (H == 1) skip = sk;
     else skip = skip << 32 | sk;
@@ -761,6 +790,48 @@ __global__ __launch_bounds__(Narrow::kThreads, 2) void l1k2_prune_kernel(
   if (at.lane == 0) add_stats(stats, at.w, n_bound, n_surv);
 }
 
+// ======== The FP6 form of a feature row (l1k2_prune_wide6_kernel; it stands behind the narrow kernel, whose pinned
+// instruction stream names its function's number in every label).  A byte value has five e2m3 codes of 6 bits, and the map from
+// (dimension, component) to K is component-major: k-step s of 64 holds component s / 2 of dimensions 64 (s % 2) .. + 63, so
+// that lane half g's 32 values of a k-step are the codes of 32 consecutive bytes of the row, packed little-endian into 24
+// bytes: chunk u = 2 s + g, component u / 4, dimensions 32 (u % 4) .. + 31.  The row keeps its 512 bytes (Stage and the
+// workspace are the int8 form's): the first 16 bytes of chunk u are 16-byte piece u (bytes 0 .. 319), and the last 8 bytes of
+// chunk (s, g) lie behind them in 16-byte piece 20 + 2 (s / 2) + g, half s % 2 (bytes 320 .. 479), which a lane reads at a
+// constant offset from a 16-byte piece's address, see MatFp6::read_a.  Bytes 480 .. 511 are zero.
+struct FeatTable6 { uint32_t w[256]; };       // the five codes of a byte value, component j at bits 6 j .. 6 j + 5
+constexpr int kFeat6Chunks = 20;              // 24-byte chunks of a row
+constexpr int kFeat6Tail = 320;               // where the 8-byte pieces begin
+// byte of a row at which the last 8 bytes of k-step s, lane half g lie
+__host__ __device__ constexpr int feat6_tail(int s, int g) { return kFeat6Tail + 32 * (s >> 1) + 16 * g + 8 * (s & 1); }
+
+// One thread per (row, 16-byte piece of the row): pieces 0 .. 19 make a chunk each, 20 .. 29 nothing, 30 and 31 the zeros.
+__global__ __launch_bounds__(kAuxThreads) void l1k2_feature6_kernel(const uint4 *__restrict__ src, uint8_t *__restrict__ dst,
+                                                                    size_t rows, FeatTable6 tab) {
+  __shared__ uint32_t t[256];
+  t[threadIdx.x] = tab.w[threadIdx.x];
+  __syncthreads();
+  for (size_t e = blockIdx.x * (size_t)kAuxThreads + threadIdx.x; e < rows * 32; e += (size_t)gridDim.x * kAuxThreads) {
+    const size_t row = e >> 5;
+    const int u = (int)(e & 31);
+    uint8_t *out = dst + row * 512;
+    if (u >= 30) *reinterpret_cast<uint4 *>(out + 16 * u) = make_uint4(0, 0, 0, 0);
+    if (u >= kFeat6Chunks) continue;
+    const int shift = 6 * (u >> 2);
+    const uint4 in[2] = {src[row * 8 + 2 * (u & 3)], src[row * 8 + 2 * (u & 3) + 1]};
+    const uint32_t words[8] = {in[0].x, in[0].y, in[0].z, in[0].w, in[1].x, in[1].y, in[1].z, in[1].w};
+    uint32_t w[6] = {};
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const uint32_t c = (t[(words[i >> 2] >> (8 * (i & 3))) & 255] >> shift) & 63u;
+      const int bit = 6 * i;
+      w[bit >> 5] |= c << (bit & 31);
+      if ((bit & 31) > 26) w[(bit >> 5) + 1] |= c >> (32 - (bit & 31));
+    }
+    *reinterpret_cast<uint4 *>(out + 16 * u) = make_uint4(w[0], w[1], w[2], w[3]);
+    *reinterpret_cast<uint2 *>(out + feat6_tail(u >> 1, u & 1)) = make_uint2(w[4], w[5]);
+  }
+}
+
 // ======== The wide form: 64 database rows per loop iteration, so that what a tile costs whatever survives (the LDS round
 // trips of its top, queue and drain, the two fences, the vmcnt(0) and the barrier) is paid half as often per row.
 // grid = (blocks of 512 queries, slices), 8 waves of 64 queries each, one workgroup per CU; the feature tile is shared
@@ -779,12 +850,93 @@ __global__ __launch_bounds__(Narrow::kThreads, 2) void l1k2_prune_kernel(
 // A tile's top is the first two A reads, the stage issue, the trailing waves' look at the flag and every second tile the
 // two threshold loads; the first MFMA accumulates in place.  tests/test_l1k2_prune_arm_isa.py holds that in the assembly,
 // tests/test_l1k2_prune_stagger_isa.py the half-steps.
-// __launch_bounds__' second argument is waves per SIMD here: 512 threads are two per SIMD already.
-__global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
+// The tile loop is written once for both matrix formats, wide_body<F, X>: F = Wide and X = MatI8 is l1k2_prune_wide_kernel,
+// F = Wide6 and X = MatFp6 is l1k2_prune_wide6_kernel, the same geometry and protocol with 40 scaled FP6 MFMAs per tile.
+
+// ---- The matrix format of the wide form's bound: what a kernel's operands, accumulators and MFMAs are.
+// MatI8: the rank-4 int8 table, K = 512 per pair in 16 k-steps of 32 per row half, exact in int32.
+struct MatI8 {
+  static constexpr int kSteps = 16;
+  using Acc = v16i;
+  using Op = v4i;
+  struct Lane { int a0; };
+  // this lane's A-operand slot at k-step 0 in the tile's buffer, as in the narrow kernel, which has the bank argument
+  // (in bytes, so that each read's address is one XOR of it: with a shift behind the XOR the compiler makes the
+  // second read's address in the register that the read then fills, and waits ahead of both for the flag read)
+  template <class F>
+  static __device__ __forceinline__ Lane lane(const Place<F> &at, int buf) {
+    return {(buf * F::kFtileV4 + at.c * kLdsRowV4 + (at.g ^ (at.c & 15))) * 16};
+  }
+  // k-step 16 h + ks is k-step ks of row half h, 32 rows further on
+  template <class F>
+  static __device__ __forceinline__ Op read_a(const Lane &l, int ks) {
+    return __builtin_bit_cast(v4i, *(const uint4 *)((const char *)&lds_ftile<F>[0][0] + ((l.a0 ^ (32 * (ks & 15))) + (ks >> 4) * (32 * kLdsRowV4 * 16))));
+  }
+  // k-step ks of feature row f (row `row` of the query set) for lane half g
+  static __device__ __forceinline__ Op load_b(const uint4 *f, int row, int ks, int g) { return __builtin_bit_cast(v4i, f[2 * ks + g]); }
+  static __device__ __forceinline__ Acc mfma(const Op &a, const Op &b, const Acc &c) { return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ int armed(int ntq) { return ntq; }
+  static __device__ __forceinline__ void pin(Acc &, Acc &) {}
+};
+
+// MatFp6: the rank-5 e2m3 table (l1k2_bound_fp6.h), K = 640 per pair in 10 k-steps of 64 per row half:
+// v_mfma_scale_f32_32x32x64_f8f6f4 with both formats FP6 (cbsz = blgp = 2) and both scales 2^0 (byte 0x7F, the same in every
+// byte of the scale register whatever opsel picks).  A code is k/8, a product a multiple of 1/64, and every sum stays below
+// 2^24/64 in magnitude (make_bound6), so the f32 accumulation is exact integer arithmetic in units of 1/64
+// (profiles/l1k2_fp6_mfma_exp.txt has the instruction checked bit for bit against an int64 GEMM, ties on +0.0 among them): the
+// accumulators start at ntq/64 and the sign bit of (ntq + sum G)/64 says "ruled out", strictly, as in the int8 form.
+// An operand is the lane's 32 codes of a k-step in 6 registers, read as 16 + 8 bytes (see l1k2_feature6_kernel for the row).
+// Banks.  ds_read_b128: as in the int8 form, a lane group holds 16 distinct c mod 16 at one g, and piece u = 2 ks + g lies in
+// slot u ^ (c & 15) (the swizzle of Stage; 2 ks + g = 2 ks ^ g, so the address is one XOR of the lane's): for u < 16 these are
+// the 16 slots of the 256-byte bank row, for u = 16 .. 19 the XOR stays inside slots 16 .. 31, again 16 distinct slots mod 16:
+// no conflict.  ds_read_b64: the last 8 bytes of k-step s lie in 16-byte piece 16 + (2 t + g), t = 2 + s / 2, half s % 2: its
+// slot is 16 + ((2 t + g) ^ (c & 15)), the slot of piece 2 t + g plus 256 bytes, so the read takes the address that the
+// 16-byte read of k-step t has made, with 256 + 8 (s % 2) in its offset field: no address of its own and no register for
+// one, which the budget does not have (with an XOR of their own the ten addresses cost ten registers and two were
+// spilled).  A half wave (one g, c = 0 .. 31), 32 x 8 B being the bank row, asks for 16 slots at one half: rows c and
+// c + 16 share a slot, a 2-way conflict, two more LDS cycles for each of a wave's 20 such reads per tile.  Swapping the
+// halves in rows with bit 4 set would end it, and puts a lane-dependent bit 3 into the address: the ten registers again.
+struct MatFp6 {
+  static constexpr int kSteps = 10;
+  using Acc = v16f;
+  struct Op { v4i lo; v2i hi; };
+  using Lane = MatI8::Lane;
+  template <class F>
+  static __device__ __forceinline__ Lane lane(const Place<F> &at, int buf) { return MatI8::lane(at, buf); }
+  // k-step 10 h + ks is k-step ks of row half h, 32 rows further on
+  template <class F>
+  static __device__ __forceinline__ Op read_a(const Lane &l, int ks) {
+    const int h = ks / kSteps, s = ks % kSteps;
+    const char *base = (const char *)&lds_ftile<F>[0][0] + h * (32 * kLdsRowV4 * 16);
+    return {__builtin_bit_cast(v4i, *(const uint4 *)(base + (l.a0 ^ (32 * s)))),
+            __builtin_bit_cast(v2i, *(const uint2 *)(base + ((l.a0 ^ (32 * (2 + s / 2))) + (feat6_tail(s, 0) - 32 * (2 + s / 2)))))};
+  }
+  static __device__ __forceinline__ Op load_b(const uint4 *f, int row, int ks, int g) {
+    return {__builtin_bit_cast(v4i, f[2 * ks + g]), __builtin_bit_cast(v2i, *(const uint2 *)((const char *)f + feat6_tail(ks, g)))};
+  }
+  static __device__ __forceinline__ v8i regs(const Op &o) {  // the builtin takes 8 dwords and reads 6 of them for FP6
+    const v8i lo = __builtin_shufflevector(o.lo, o.lo, 0, 1, 2, 3, -1, -1, -1, -1);
+    const v8i hi = __builtin_shufflevector(o.hi, o.hi, 0, 1, -1, -1, -1, -1, -1, -1);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 8, 9, -1, -1);
+  }
+  static __device__ __forceinline__ Acc mfma(const Op &a, const Op &b, const Acc &c) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(regs(a), regs(b), c, 2, 2, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+  }
+  static __device__ __forceinline__ float armed(int ntq) { return (float)ntq * (1.0f / 64); }  // |ntq| < 2^24: exact
+  // A k-step's two accumulators, made where the source makes them.  Nothing but data orders an MFMA against the
+  // sched_barrier of its k-step, and left to itself instruction selection puts all 40 behind the 20 A reads, which then
+  // hold 120 registers at once and push the B operand out to scratch.
+  static __device__ __forceinline__ void pin(Acc &c0, Acc &c1) {
+    asm volatile("" : "+v"(c0));
+    asm volatile("" : "+v"(c1));
+  }
+};
+
+template <class F, class X>
+__device__ __forceinline__ void wide_body(
     const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
     const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
     unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
-  using F = Wide;
   constexpr int H = F::H;
   const Place<F> at(threadIdx.x);
   const int s = blockIdx.y;
@@ -805,7 +957,18 @@ __global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
   int ntq[2];
   uint32_t seen[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
   auto thr_load = [&]() { load_thresholds(seen, thr, at, N); };
-  auto refresh = [&](bool shared) { refresh_thresholds(ntq, seen, shared, thr, at, N, p, m128); };
+  // F::kRefreshFromCopy: the place made again from a copy of the thread index that the compiler cannot see through, else it
+  // carries the 64-bit address of the publication's atomicMin across the loop, for a path that runs once in a while.  The FP6
+  // form has no two registers to spare for it (they were spilled); the int8 form has, and is kept as it was.
+  auto refresh = [&](bool shared) {
+    if constexpr (F::kRefreshFromCopy) {
+      int tt = at.t;
+      asm volatile("" : "+v"(tt));
+      refresh_thresholds(ntq, seen, shared, thr, Place<F>(tt), N, p, m128);
+    } else {
+      refresh_thresholds(ntq, seen, shared, thr, at, N, p, m128);
+    }
+  };
 
   const int ntiles = (row_end - row_begin + F::kTileRows - 1) / F::kTileRows;
   if (ntiles > 0) {
@@ -823,19 +986,20 @@ __global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
   int bailed = 0, zero_v = 0;  // as in the narrow kernel
   asm volatile("" : "+v"(zero_v));
   {
-    v4i bq[2][16];
-    // ---- this wave's queries as the B operand: 2 column blocks x 16 k-steps x 4 dwords
+    typename X::Op bq[2][X::kSteps];
+    // ---- this wave's queries as the B operand: 2 column blocks x the format's k-steps (16 x 4 dwords, or 10 x 6)
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      const uint4 *f = fy + (size_t)min(at.qbase + 32 * b + at.c, N - 1) * kFeatV4;
+      const int row = min(at.qbase + 32 * b + at.c, N - 1);
+      const uint4 *f = fy + (size_t)row * kFeatV4;
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bq[b][ks] = __builtin_bit_cast(v4i, f[2 * ks + at.g]);
+      for (int ks = 0; ks < X::kSteps; ++ks) bq[b][ks] = X::load_b(f, row, ks, at.g);
     }
     thr_load();
     __builtin_amdgcn_s_waitcnt(kWaitVm0);  // the B operand is complete before the loop is entered, as in the narrow kernel
 
     // ---- Two half-steps per tile, waves 4-7 half a tile behind waves 0-3.  A SIMD holds waves w and w + 4.  M(t) is
-    // the top of tile t and its 64 MFMAs (it reads ftile[t & 1]), C(t) its compare, compaction and drains (xraw[t & 1]);
+    // the top of tile t and its MFMA run (it reads ftile[t & 1]), C(t) its compare, compaction and drains (xraw[t & 1]);
     // a barrier ends each, B_h the one that ends half-step h.  The leading waves run M(t) in half-step 2t and C(t) in
     // 2t + 1, the trailing waves M(t) in 2t + 1 and C(t) in 2t + 2: on every SIMD one wave's chain runs under the
     // other's MFMAs, where in lock-step both had the pipe or neither.  The trailing waves get there by one barrier ahead
@@ -856,7 +1020,7 @@ __global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
     // refresh, whose k2s[] only this wave's own drains write and whose seen[] landed at a mid-tile vmcnt(0), and the 64
     // moves; it needs no barrier, so it stands where the wave would wait for the end-of-tile barrier while the other wave
     // of its SIMD runs its MFMAs, and a tile's top is the first A reads, the stage issue and the flag test alone.
-    v16i acc[H][2];
+    typename X::Acc acc[H][2];
     auto arm = [&](bool shared) {
       refresh(shared);
 #pragma unroll
@@ -864,7 +1028,7 @@ __global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
 #pragma unroll
-          for (int v = 0; v < 16; ++v) acc[h][b][v] = ntq[b];
+          for (int v = 0; v < 16; ++v) acc[h][b][v] = X::armed(ntq[b]);
           // made here: left to itself the compiler sinks the moves below the barrier that follows, into the next tile's top
           asm volatile("" : "+v"(acc[h][b]));
         }
@@ -884,17 +1048,12 @@ __global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
       const unsigned long long drained = ph[kPhDrain];
       const int row0 = row_begin + tl * F::kTileRows;
       const bool has_next = tl + 1 < ntiles;
-      // this lane's A-operand slot at k-step 0 in this tile's buffer, as in the narrow kernel, which has the bank argument
-      // (in bytes, so that each read's address is one XOR of it: with a shift behind the XOR the compiler makes the
-      // second read's address in the register that the read then fills, and waits ahead of both for the flag read)
-      const int a0 = ((tl & 1) * F::kFtileV4 + at.c * kLdsRowV4 + (at.g ^ (at.c & 15))) * 16;
+      // this lane's A-operand addresses at k-step 0 in this tile's buffer (X::lane).
       // The first two reads are the tile's first instructions: the stage issue and the flag test run in their
       // latency (the memory clobber of the loads keeps them ahead).
-      // k-step 16 h + ks is k-step ks of row half h, 32 rows further on
-      auto lda = [&](int ks) {
-        return __builtin_bit_cast(v4i, *(const uint4 *)((const char *)&lds_ftile<F>[0][0] + ((a0 ^ (32 * (ks & 15))) + (ks >> 4) * (32 * kLdsRowV4 * 16))));
-      };
-      v4i a3[3];
+      const typename X::Lane a_at = X::template lane<F>(at, tl & 1);
+      auto lda = [&](int ks) { return X::template read_a<F>(a_at, ks); };
+      typename X::Op a3[3];
       a3[0] = lda(0);
       a3[1] = lda(1);
       // every wave has read the last of tile tl - 1's features; only the trailing waves are behind the barrier after
@@ -925,10 +1084,11 @@ __global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
       // before; the A reads run on across the boundary between the halves.
       const unsigned long long t_mfma = stamp();
 #pragma unroll
-      for (int ks = 0; ks < 16 * H; ++ks) {
-        if (ks + 2 < 16 * H) a3[(ks + 2) % 3] = lda(ks + 2);
-        acc[ks >> 4][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[0][ks & 15], acc[ks >> 4][0], 0, 0, 0);
-        acc[ks >> 4][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a3[ks % 3], bq[1][ks & 15], acc[ks >> 4][1], 0, 0, 0);
+      for (int ks = 0; ks < X::kSteps * H; ++ks) {
+        if (ks + 2 < X::kSteps * H) a3[(ks + 2) % 3] = lda(ks + 2);
+        acc[ks / X::kSteps][0] = X::mfma(a3[ks % 3], bq[0][ks % X::kSteps], acc[ks / X::kSteps][0]);
+        acc[ks / X::kSteps][1] = X::mfma(a3[ks % 3], bq[1][ks % X::kSteps], acc[ks / X::kSteps][1]);
+        X::pin(acc[ks / X::kSteps][0], acc[ks / X::kSteps][1]);
         __builtin_amdgcn_sched_barrier(0);
       }
 
@@ -1019,6 +1179,23 @@ __global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
   if ((te & 63) == 0) add_stats(stats, we, n_bound, n_surv);
 }
 
+// __launch_bounds__' second argument is waves per SIMD here: 512 threads are two per SIMD already.
+__global__ __launch_bounds__(Wide::kThreads, 2) void l1k2_prune_wide_kernel(
+    const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
+    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
+    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
+  wide_body<Wide, MatI8>(x, y, fx, fy, M, N, slice_rows, S, m128, p, max_share, octet_max, thr, stats, work, part SPV_STAMP_PASS);
+}
+
+// The FP6 form.  Registers: B 120 (2 x 10 x 6), accumulators 64, A 18 (3 x 6); LDS as the int8 form's.  m128 and p are the FP6
+// table's, in units of 1/64.
+__global__ __launch_bounds__(Wide6::kThreads, 2) void l1k2_prune_wide6_kernel(
+    const uint4 *__restrict__ x, const uint4 *__restrict__ y, const uint4 *__restrict__ fx,
+    const uint4 *__restrict__ fy, int M, int N, int slice_rows, int S, int m128, int p, int max_share, int octet_max, uint32_t *thr,
+    unsigned long long *stats, uint32_t *work, uint64_t *__restrict__ part SPV_STAMP_PARAM) {
+  wide_body<Wide6, MatFp6>(x, y, fx, fy, M, N, slice_rows, S, m128, p, max_share, octet_max, thr, stats, work, part SPV_STAMP_PASS);
+}
+
 // -1 auto, 0 off, 1 forced: SPECTAVI_L1K2_PRUNE until l1k2_set_prune is called
 std::atomic<int> &prune_mode() {
   static std::atomic<int> mode{l1k2_knobs().prune};
@@ -1076,6 +1253,72 @@ std::atomic<int> &form_choice() {
   return which;
 }
 
+// -1 default, 0 int8, 1 FP6: SPECTAVI_L1K2_PRUNE_MATRIX until l1k2_set_prune_matrix is called
+std::atomic<int> &matrix_choice() {
+  static std::atomic<int> which{l1k2_knobs().prune_matrix};
+  return which;
+}
+
+// make_bound for the FP6 table: the entries are the integers k of e2m3 values k/8, so G, p and m are integers in units of
+// 1/64 and the inequality is the same integer one.  Refused unless every entry is on the e2m3 grid (|k| in 0..15, 16..30
+// step 2, 32..60 step 4), the inequality holds on every byte pair, and 128 m, p 128 255 and the largest |sum G| of a
+// 128-byte pair stay below 2^24: then every value the f32 accumulators ever hold is a multiple of 1/64 below 2^24/64 in
+// magnitude, and their arithmetic is exact.
+L1K2Bound6 make_bound6(const int8_t k[256][5], int p_lo, int p_hi) {
+  L1K2Bound6 b{};
+  b.ok = true;
+  for (int a = 0; a < 256; ++a)
+    for (int f = 0; f < 5; ++f) {
+      const int v = b.k[a][f] = k[a][f], mag = std::abs(v);
+      if (mag > 60 || (mag >= 16 && mag % 2) || (mag >= 32 && mag % 4)) b.ok = false;
+    }
+  std::vector<int> Gv(256 * 256);
+  int(*G)[256] = reinterpret_cast<int(*)[256]>(Gv.data());
+  long long sumG = 0;
+  int maxG = 0;
+  for (int a = 0; a < 256; ++a)
+    for (int c = 0; c < 256; ++c) {
+      int g = 0;
+      for (int f = 0; f < 5; ++f) g += (int)b.k[a][f] * (int)b.k[c][f];
+      G[a][c] = g;
+      sumG += g;
+      maxG = std::max(maxG, std::abs(g));
+    }
+  // the slope whose bound is largest on average over all byte pairs, as in make_bound
+  double best = -1e300;
+  for (int p = p_lo; p < p_hi; ++p) {
+    int m = 0x7FFFFFFF;
+    for (int a = 0; a < 256; ++a)
+      for (int c = 0; c < 256; ++c) m = std::min(m, p * std::abs(a - c) + G[a][c]);
+    const double mean = (65536.0 * m - (double)sumG) / p;
+    if (mean > best) {
+      best = mean;
+      b.p = p;
+      b.m = m;
+    }
+  }
+  for (int a = 0; a < 256; ++a)
+    for (int c = 0; c < 256; ++c)
+      if ((long long)b.p * std::abs(a - c) < (long long)b.m - G[a][c]) b.ok = false;
+  if (128ll * std::abs(b.m) >= (1 << 24) || (long long)b.p * kMaxDist >= (1 << 24) || 128ll * maxG >= (1 << 24)) b.ok = false;
+  return b;
+}
+
+// a 6-bit e2m3 code: sign, two exponent bits, three mantissa bits; the value is k/8
+uint32_t e2m3_code(int k) {
+  const uint32_t mag = (uint32_t)std::abs(k);
+  return (k < 0 ? 32u : 0u) | (mag < 16 ? mag : mag < 32 ? mag / 2 + 8 : mag / 4 + 16);
+}
+
+FeatTable6 feat_table6(const L1K2Bound6 &b) {
+  FeatTable6 t;
+  for (int a = 0; a < 256; ++a) {
+    t.w[a] = 0;
+    for (int f = 0; f < 5; ++f) t.w[a] |= e2m3_code(b.k[a][f]) << (6 * f);
+  }
+  return t;
+}
+
 L1K2Bound make_recipe() {
   int8_t phi[256][4];
   const double pi = 3.14159265358979323846;
@@ -1111,12 +1354,20 @@ const L1K2Bound &l1k2_bound_of(int which) {
   return tuned.ok ? tuned : l1k2_bound();
 }
 
+// p is swept as tools/l1k2_bound_tune.py sweeps it for this table
+const L1K2Bound6 &l1k2_bound6() {
+  static const L1K2Bound6 b = make_bound6(kL1K2BoundFp6K, 8, 200);
+  return b;
+}
+
 int l1k2_set_prune(int mode) { return prune_mode().exchange(mode); }
 int l1k2_get_prune() { return prune_mode().load(); }
 int l1k2_set_bound(int which) { return bound_choice().exchange(which); }
 int l1k2_get_bound() { return bound_choice().load(); }
 int l1k2_set_prune_form(int form) { return form_choice().exchange(form); }
 int l1k2_get_prune_form() { return form_choice().load(); }
+int l1k2_set_prune_matrix(int matrix) { return matrix_choice().exchange(matrix); }
+int l1k2_get_prune_matrix() { return matrix_choice().load(); }
 
 namespace {
 // where the counters of the calling thread's last l1k2_run lie (null: it took the tile kernels)
@@ -1191,6 +1442,12 @@ void l1k2_prune_plan(int xrows, int yrows, int dim, WsWalk *w, L1K2Plan *p) {
     const int form = l1k2_get_prune_form();
     p->form = form >= 0 ? form : mode != 1 && (unsigned long long)wgroups * p->slices >= kWideMinGroups ? kL1K2FormWide : kL1K2FormNarrow;
     p->bound_wide_grid = dim3(wgroups, (unsigned)p->slices);
+    // The matrix format: as set where the form is wide, else FP6 exactly where `auto` took the path and nobody named a
+    // table.  Mode 1 and an explicit table stay int8: the case tables and model statistics of the tests are worked out
+    // from the int8 tables.  An FP6 table that fails its check leaves everything to the int8 kernel.
+    const int matrix = l1k2_get_prune_matrix();
+    const bool fp6 = matrix >= 0 ? matrix == kL1K2MatrixFp6 : mode != 1 && which < 0;
+    p->matrix = fp6 && p->form == kL1K2FormWide && l1k2_bound6().ok ? kL1K2MatrixFp6 : kL1K2MatrixI8;
   }
 }
 
@@ -1198,6 +1455,9 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
                    hipStream_t stream) {
   const L1K2Bound &b = l1k2_bound_of(p.bound);
   if (!b.ok) return set_error(SPV_ERR_INTERNAL, "the L1 bound table failed its own check");
+  const bool fp6 = p.matrix == kL1K2MatrixFp6;
+  const L1K2Bound6 &b6 = l1k2_bound6();
+  if (fp6 && !(b6.ok && p.form == kL1K2FormWide)) return set_error(SPV_ERR_INTERNAL, "the FP6 bound was planned where it cannot run");
   uint4 *fx = reinterpret_cast<uint4 *>(ws + p.off_feat_x);
   uint4 *fy = reinterpret_cast<uint4 *>(ws + p.off_feat_y);
   uint32_t *thr = reinterpret_cast<uint32_t *>(ws + p.off_thr);
@@ -1226,10 +1486,18 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
   const int waves = wide ? Wide::kWaves : Narrow::kWaves;
   const size_t xw = (size_t)xrows * 32, yw = (size_t)yrows * 32;
   auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + kAuxThreads - 1) / kAuxThreads, 8192)); };
-  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
-                     xw, tab);
-  hipLaunchKernelGGL(l1k2_feature_kernel, blocks(yw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_y), fy,
-                     yw, tab);
+  if (fp6) {
+    static const FeatTable6 tab6 = feat_table6(l1k2_bound6());
+    hipLaunchKernelGGL(l1k2_feature6_kernel, blocks(xw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint4 *>(d_x),
+                       reinterpret_cast<uint8_t *>(fx), (size_t)xrows, tab6);
+    hipLaunchKernelGGL(l1k2_feature6_kernel, blocks(yw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint4 *>(d_y),
+                       reinterpret_cast<uint8_t *>(fy), (size_t)yrows, tab6);
+  } else {
+    hipLaunchKernelGGL(l1k2_feature_kernel, blocks(xw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_x), fx,
+                       xw, tab);
+    hipLaunchKernelGGL(l1k2_feature_kernel, blocks(yw), dim3(kAuxThreads), 0, stream, reinterpret_cast<const uint32_t *>(d_y), fy,
+                       yw, tab);
+  }
   hipLaunchKernelGGL(l1k2_thr_init_kernel, blocks(p.init_words), dim3(kAuxThreads), 0, stream, thr, p.thr_words,
                      p.init_words);
 #ifdef SPV_L1K2_PHASE_STAMPS
@@ -1240,10 +1508,12 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
 #endif
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, grid, dim3(waves * 64), 0, stream, reinterpret_cast<const uint4 *>(d_x),
-                       reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, 128 * b.m, b.p,
+                       reinterpret_cast<const uint4 *>(d_y), fx, fy, xrows, yrows, p.slice_rows, p.slices, fp6 ? 128 * b6.m : 128 * b.m,
+                       fp6 ? b6.p : b.p,
                        max_share, octet_max, thr, stats, work, reinterpret_cast<uint64_t *>(ws + p.off_part) SPV_STAMP_ARG);
   };
-  if (wide) launch(l1k2_prune_wide_kernel);
+  if (fp6) launch(l1k2_prune_wide6_kernel);
+  else if (wide) launch(l1k2_prune_wide_kernel);
   else launch(l1k2_prune_kernel);
   SPV_HIP_CHECK(hipGetLastError());
 #ifdef SPV_L1K2_PHASE_STAMPS

@@ -211,6 +211,38 @@ def l1k2_bound_table(which=0):
     return phi.astype(np.int64), int(p.value), int(m.value)
 
 
+def l1k2_set_prune_matrix(matrix):
+    """The matrix format of the wide bound kernel (spv_l1k2_set_prune_matrix): "default" (FP6 where prune mode "auto"
+    takes the path, the form is wide and no bound table is named, else int8), 0 / "i8", 1 / "fp6" (every shape whose
+    form is wide).  The results do not depend on it."""
+    if isinstance(matrix, str):
+        matrix = {"default": -1, "i8": 0, "fp6": 1}.get(matrix)
+    if isinstance(matrix, bool) or not isinstance(matrix, int) or matrix not in (-1, 0, 1):
+        raise ValueError("bound matrix format must be 'default', 'i8' (0) or 'fp6' (1)")
+    check(clib.spv_l1k2_set_prune_matrix(matrix))
+
+
+def l1k2_get_prune_matrix():
+    """The matrix format setting in force: -1 (default), 0 (int8) or 1 (FP6)."""
+    return int(clib.spv_l1k2_get_prune_matrix())
+
+
+def l1k2_prune_matrix_of(xrows, yrows, dim=128):
+    """The matrix format l1k2() would run for this shape under the settings in force (spv_l1k2_prune_matrix_of; host
+    only): 0 (int8), 1 (FP6), or -1 where it would not take the bound path."""
+    return int(clib.spv_l1k2_prune_matrix_of(xrows, yrows, dim))
+
+
+def l1k2_bound6_table():
+    """(k int64 [256, 5], p, m) of the FP6 table (spv_l1k2_bound6_table; host only): the features are k / 8, and
+    p |a - b| >= m - k[a] . k[b] for all bytes a, b, in units of 1/64."""
+    import numpy as np
+    k = np.zeros((256, 5), np.int8)
+    p, m = ct.c_int(0), ct.c_int(0)
+    check(clib.spv_l1k2_bound6_table(k.ctypes.data, ct.byref(p), ct.byref(m)))
+    return k.astype(np.int64), int(p.value), int(m.value)
+
+
 def l1k2_prune_stats():
     """(pairs put to the bound, survivors, pairs of the exact fallback) of this thread's last l1k2()
     call; all zero if it ran the tile kernels.  Synchronises with that call."""
