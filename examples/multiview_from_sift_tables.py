@@ -14,6 +14,9 @@ runs all of them through the many-pairs forms of the same steps, with every inte
     dlt_triangulate_batch    every pair's inliers triangulated with that pair's camera; pairs without a model skipped
     rectify_batch            (--rectify) every fitted pair's two images rectified, cropped on the device to the valid
                              samples; the images are noise here, only the geometry is the pipeline's
+    epipolar_lines_batch     (--guided PIXELS) every fitted pair's model as one line per query keypoint, and
+    l1k2_guided_batch        the L1 2-NN again, only among the database keypoints within PIXELS of that line; the
+                             same ratio test then holds more matches than the blind one
 
 Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
 they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic
@@ -21,6 +24,7 @@ here, so that the scene and the cameras are known; extracting them from images i
 before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
     python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}] [--rectify]
+                                                  [--guided PIXELS]
 """
 import argparse
 import os
@@ -74,7 +78,7 @@ def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_f
 
 
 def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, maximum_tries=2000, seed=1,
-                       matcher='l1k2', hash_seed=0x5eed):
+                       matcher='l1k2', hash_seed=0x5eed, guided=None):
     """SIFT tables (a list of float32 [n_v,132] arrays) -> one upload -> split -> exact L1 2-NN of all pairs (or,
     matcher='cascade', the cascade hash of all pairs: descriptors normalised per view as the reference's front-end
     does, m by its rule from the largest view, n = 2, g = 2, hyperplanes from hash_seed) -> ratio
@@ -82,7 +86,9 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     with that pair's camera.  Returns a dict: pairs int32 [npairs,2] (query view, database view), pair_off (matches
     per pair), fits (the `ransac_fit` dicts), out_off (points per pair), X (CUDA float64 [total,4], rows
     out_off[p]:out_off[p + 1] are pair p's unit-norm homogeneous points) and rows (CUDA int32: the match each point
-    belongs to, numbered inside its pair)."""
+    belongs to, numbered inside its pair).  With guided (pixels) also guided_pair_off: the matches per pair of the
+    second pass, the same ratio test over the L1 2-NN inside a band of that half-width around each query's epipolar
+    line in the database view; a pair without a model has none."""
     import torch
     from spectavi_amd import device as spv
     seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
@@ -113,7 +119,18 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     use = [f['best_try'] >= 0 for f in fits]            # a pair without a model owns no points
     cameras = [f['camera'] for f in fits]               # None where there is none
     X, rows, out_off = spv.dlt_triangulate_batch(x0, x1, pair_off, cameras, use=use, mask=mask, want_rows=True)
-    return {'pairs': pairs, 'pair_off': pair_off, 'fits': fits, 'out_off': out_off, 'X': X, 'rows': rows}
+    out = {'pairs': pairs, 'pair_off': pair_off, 'fits': fits, 'out_off': out_off, 'X': X, 'rows': rows}
+    if guided is not None:
+        # x1^T E x0 = 0 with x0 the database view: a query pixel's line in the database view is (K^-T E K^-1)^T x
+        iK = np.linalg.inv(K)
+        G = np.stack([(iK.T @ np.asarray(f['essential']).reshape(3, 3) @ iK).T if u else np.zeros((3, 3))
+                      for f, u in zip(fits, use)])
+        lines = spv.epipolar_lines_batch(geom, seg, pairs, G, use=use)
+        gidx, gdist, goff = spv.l1k2_guided_batch(desc, geom, seg, pairs, lines, guided)
+        gm, gcount = spv.ratio_test(gidx, gdist, min_ratio)
+        qrows = gm[:int(gcount)].cpu().numpy()[:, 0]
+        out['guided_pair_off'] = np.searchsorted(qrows, goff).astype(np.int64)
+    return out
 
 
 def rectify_pairs(out, K, images):
@@ -135,6 +152,10 @@ def report(out):
         print("pair %d-%d: matches %d model %s inliers %d points %d" % (
             d, q, out['pair_off'][p + 1] - out['pair_off'][p], "yes" if f['best_try'] >= 0 else "no",
             len(f['inlier_idx']), out['out_off'][p + 1] - out['out_off'][p]))
+        if 'guided_pair_off' in out:
+            g = out['guided_pair_off']
+            print("pair %d-%d: guided pass holds %d matches against %d" % (d, q, g[p + 1] - g[p],
+                                                                          out['pair_off'][p + 1] - out['pair_off'][p]))
     print("pairs %d fitted %d inliers %d points %d" % (len(out['pairs']), fitted, sum(len(f['inlier_idx']) for f in out['fits']),
                                                        out['out_off'][-1]))
 
@@ -146,13 +167,15 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--matcher", default="l1k2", choices=["l1k2", "cascade"], help="exact brute force, or the cascade hash")
     ap.add_argument("--rectify", action="store_true", help="also rectify every fitted pair (step 5), on noise images")
+    ap.add_argument("--guided", type=float, default=None, metavar="PIXELS",
+                    help="match again inside a band of this half-width around the fitted epipolar lines")
     a = ap.parse_args()
     import torch
     tables, K = synthetic_sift_views(a.seed, a.images, a.points)
     for rep in range(2):  # the second round is the warm one
         torch.cuda.synchronize()
         s = time.perf_counter()
-        out = multiview_pipeline(tables, K, matcher=a.matcher)
+        out = multiview_pipeline(tables, K, matcher=a.matcher, guided=a.guided)
         torch.cuda.synchronize()
         dt = time.perf_counter() - s
     report(out)

@@ -174,7 +174,7 @@ void spv_release_cached_memory(void);
 const char *spv_version(void);
 
 /* Optional in-library kernel timing: when enabled, the hot kernels (names:
- * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
+ * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "l1k2_guided", "l1k2_guided_merge", "epipolar_lines", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
  * "ann_merge", "ann_rerank", "cascade_project",
  * "cascade_buckets", "cascade_probe_refine", "cascade_batch_project", "cascade_batch_buckets", "cascade_batch_probe", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "rectify_batch_bounds", "rectify_batch_box",
  * "rectify_batch", "ransac_batch_score",
@@ -441,6 +441,14 @@ int spv_nn_bruteforcel1k2(const uint8_t *x, const uint8_t *y, int xrows, int yro
  * addition: the reference has no such symbol. */
 int spv_nn_bruteforcel1k2_batch(const uint8_t *desc, const long long *seg_off, int nseg, int dim,
                                 const int32_t *pairs, int npairs, uint64_t *idx, int32_t *dist);
+
+/* spv_l1k2_guided_batch_device (section 3, which states the contract) through host pointers: desc
+ * uint8[seg_off[nseg], dim], geom float32[seg_off[nseg], 4], lines double[out_rows, 3], idx uint64[out_rows,2],
+ * dist int32[out_rows,2], ncand int32[out_rows] or NULL.  One device: the first one selected by spv_set_device /
+ * spv_set_devices.  An addition: the reference has no such symbol. */
+int spv_nn_bruteforcel1k2_guided_batch(const uint8_t *desc, const float *geom, const long long *seg_off, int nseg,
+                                       int dim, const int32_t *pairs, int npairs, const double *lines,
+                                       double max_dist, uint64_t *idx, int32_t *dist, int32_t *ncand);
 
 /* nn_bruteforce (is_int = 0: float32 rows, float32 dist) / nn_bruteforcei (is_int = 1: int32 rows,
  * int32 dist) with caller-allocated idx uint64[yrows,k], dist [yrows,k]. */
@@ -805,6 +813,58 @@ size_t spv_l1k2_batch_workspace_bytes(const long long *seg_off, int nseg, int di
 int spv_l1k2_batch_device(const uint8_t *d_desc, const long long *seg_off, int nseg, int dim,
                           const int32_t *pairs, int npairs, uint64_t *d_idx, int32_t *d_dist, void *d_ws,
                           size_t ws_bytes, void *stream);
+
+/* The guided pass of a multi-view front-end (l1k2_guided.hip): the exact L1 2-NN of spv_l1k2_batch_device, searched
+ * for every query only among the database keypoints within max_dist of that query's line -- its epipolar line
+ * once a model is fitted, or the scan line (0, 1, -v) of a rectified pair.  The two nearest rows inside the band
+ * are in general not the two nearest overall, so this is not a filter over spv_l1k2_batch_device's result.
+ *   desc, seg_off, pairs, idx, dist, out_rows
+ *            as for spv_l1k2_batch_device, rule for rule.
+ *   geom     float32[total_rows, 4]: row for row the geometry of desc, as spv_sift_split_device writes it; only
+ *            columns 0 and 1 (u, v) are read.
+ *   lines    double[out_rows, 3]: row r is the line (l0, l1, l2) of out row r in the database view's pixel
+ *            coordinates.
+ *   Candidates: row j of the pair's database set, keypoint (u_j, v_j), is a candidate of out row r iff
+ *            fabs(fma(l0, (double)u_j, fma(l1, (double)v_j, l2))) <= max_dist, in fp64 and in that operation
+ *            order.  A NaN anywhere makes the comparison false: a NaN line or a NaN keypoint yields no candidate.
+ *            Nothing is normalised inside: max_dist is in pixels when the lines have l0^2 + l1^2 = 1.
+ *   Result:  the two smallest (L1 distance, row within the database set) among the candidates, in lexicographic
+ *            order, ((size_t)-1, INT_MAX) where fewer than two candidates exist; bit for bit the same however the
+ *            call cuts the work.  ncand (may be NULL): int32[out_rows], the number of candidates of each out row.
+ * Limits: dim == 128 only in this form (any other width is SPV_ERR_INVALID); d_desc, d_geom and d_ws 16-byte
+ * aligned, d_idx and d_lines 8-byte, d_dist and d_ncand 4-byte; d_lines and d_geom may be NULL only when there are
+ * no out rows.  Outside them SPV_ERR_INVALID, nothing launched, no output touched.  One device.
+ *
+ * spv_l1k2_guided_batch_plan: host only, touches no device.  out = {work items, out_rows, largest slice count of
+ * any pair, workspace bytes}; items may be NULL, otherwise int32[items_cap, 5] receives the first min(work items,
+ * items_cap) work items, one workgroup each, as (pair, first query row within the query set, query rows, first
+ * database row within the database set, database rows), in launch order.  An item is up to 256 queries against one
+ * slice of the database set: a collection of at least 512 query blocks runs whole sets, a smaller one is cut into
+ * slices of at least 256 rows until it has 512 items.  SPV_ERR_INVALID leaves out and items untouched.
+ * spv_l1k2_guided_batch_workspace_bytes: out[3] (0 for arguments the plan rejects): 16 bytes per out row, 32 per
+ * work item.
+ *
+ * spv_l1k2_guided_batch_device: seg_off and pairs are read before the call returns.  The call may wait for the
+ * upload of its small work table, which is queued on `stream`; everything else is asynchronous on `stream`.
+ * Kernel names for spv_profile_read: "l1k2_guided" (the main kernel), "l1k2_guided_merge" (keys to idx / dist). */
+int spv_l1k2_guided_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs,
+                               long long out[4], int32_t *items, long long items_cap);
+size_t spv_l1k2_guided_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, const int32_t *pairs,
+                                             int npairs);
+int spv_l1k2_guided_batch_device(const uint8_t *d_desc, const float *d_geom, const long long *seg_off, int nseg,
+                                 int dim, const int32_t *pairs, int npairs, const double *d_lines, double max_dist,
+                                 uint64_t *d_idx, int32_t *d_dist, int32_t *d_ncand, void *d_ws, size_t ws_bytes,
+                                 void *stream);
+
+/* The lines of spv_l1k2_guided_batch_device from one 3x3 matrix per pair.  G is host double[npairs, 9], row major;
+ * G_p maps a pixel of the query view to its line in the database view: out row r of pair p, whose query keypoint
+ * is (u, v) (geom of the query set), gets l = G_p (u, v, 1)^T divided by hypot(l0, l1).  use is host int32[npairs]
+ * or NULL; three NaNs are written where use[p] == 0 or the norm is zero or not finite, so a pair without a model
+ * owns no candidates.  d_geom, seg_off, pairs and the out rows are those of spv_l1k2_guided_batch_device; d_lines is
+ * double[out_rows, 3].  G and use are read before the call returns; asynchronous on `stream`, no workspace.
+ * Kernel name for spv_profile_read: "epipolar_lines". */
+int spv_epipolar_lines_batch_device(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
+                                    int npairs, const double *G, const int32_t *use, double *d_lines, void *stream);
 
 /* The query loop sharded over the GPUs of one node with everything resident (the loop
  * the reference shards over OpenMP threads, src/BruteForceNnL1K2.h:92-93): one process, rank r =

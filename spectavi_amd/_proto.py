@@ -85,6 +85,7 @@ PROTOTYPES = {
     # ---- 2. host-pointer variants
     "spv_nn_bruteforcel1k2": (i, [vp, vp, i, i, i, vp, vp]),
     "spv_nn_bruteforcel1k2_batch": (i, [vp, vp, i, i, vp, i, vp, vp]),
+    "spv_nn_bruteforcel1k2_guided_batch": (i, [vp, vp, vp, i, i, vp, i, vp, d, vp, vp, vp]),
     "spv_nn_bruteforce": (i, [vp, vp, i, i, i, i, i, f, vp, vp]),
     "spv_ann_l2": (i, [vp, vp, i, i, i, i, i, vp, vp]),
     "spv_nn_cascading_hash": (i, [f32a, f32a] + [i] * 6 + [f32a, u64a, f32a, vp]),
@@ -120,7 +121,11 @@ PROTOTYPES = {
     "spv_l1k2_batch_plan": (i, [vp, i, i, vp, i, pll, vp, ll]),
     "spv_l1k2_batch_workspace_bytes": (sz, [vp, i, i, vp, i]),
     "spv_l1k2_batch_device": (i, [vp, vp, i, i, vp, i, vp, vp, vp, sz, vp]),
-    "spv_l1k2_gathered_device": (i, _ranks + [vp, vp, i]),
+    "spv_l1k2_guided_batch_plan": (i, [vp, i, i, vp, i, pll, vp, ll]),
+    "spv_l1k2_guided_batch_workspace_bytes": (sz, [vp, i, i, vp, i]),
+    "spv_l1k2_guided_batch_device": (i, [vp, vp, vp, i, i, vp, i, vp, d, vp, vp, vp, vp, sz, vp]),
+    "spv_epipolar_lines_batch_device": (i, [vp, vp, i, vp, i, vp, vp, vp, vp]),
+    "spv_l1k2_gathered_device":(i, _ranks + [vp, vp, i]),
     "spv_cascade_gathered_device": (i, _ranks + [i, i, i, vpp, vp, vp, vp, i]),
     "spv_dlt_gathered_device": (i, [i, pi, f64a, f64a, ll, vpp, vpp, vp, i, i]),
     "spv_shard_lo": (ll, [ll, i, i]),

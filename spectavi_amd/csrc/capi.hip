@@ -269,6 +269,33 @@ int host_l1k2_batch(const uint8_t *desc, const long long *seg_off, int nseg, int
   return download(dev, idx, di.p, ib, st);
 }
 
+// The guided many-pairs L1 2-NN through host pointers, on the first selected device: desc, geom and lines up, one
+// l1k2_guided_run, the results back.
+int host_l1k2_guided_batch(const uint8_t *desc, const float *geom, const long long *seg_off, int nseg, int dim,
+                           const int32_t *pairs, int npairs, const double *lines, double max_dist, uint64_t *idx,
+                           int32_t *dist, int32_t *ncand) {
+  L1K2GuidedPlan p;
+  SPV_TRY(l1k2_guided_plan(seg_off, nseg, dim, pairs, npairs, &p));
+  if (p.out_rows == 0) return SPV_OK;
+  if (!desc || !geom || !lines || !idx || !dist) return set_error(SPV_ERR_INVALID, "null pointer");
+  const int dev = device_list()[0];
+  hipStream_t st;
+  SPV_TRY(host_begin(dev, &st));
+  const size_t xb = (size_t)p.total_rows * dim, gb = (size_t)p.total_rows * 4 * sizeof(float);
+  const size_t lb = (size_t)p.out_rows * 3 * sizeof(double), nb = ncand ? (size_t)p.out_rows * sizeof(int32_t) : 0;
+  const size_t ib = (size_t)p.out_rows * 2 * sizeof(uint64_t), db = (size_t)p.out_rows * 2 * sizeof(int32_t);
+  DevBuf dx, dg, dl, di, dd, dn, ws;
+  SPV_TRY(alloc_all({{&dx, xb}, {&dg, gb}, {&dl, lb}, {&di, ib}, {&dd, db}, {&dn, nb}, {&ws, p.total_bytes}}));
+  SPV_TRY(dx.copy_in(desc, xb, st));
+  SPV_TRY(dg.copy_in(geom, gb, st));
+  SPV_TRY(dl.copy_in(lines, lb, st));
+  SPV_TRY(l1k2_guided_run(dx.as<uint8_t>(), dg.as<float>(), seg_off, nseg, dim, pairs, npairs, dl.as<double>(), max_dist,
+                          di.as<uint64_t>(), dd.as<int32_t>(), ncand ? dn.as<int32_t>() : nullptr, ws.p, p.total_bytes, st));
+  SPV_TRY(dd.copy_out(dist, db, st));
+  SPV_TRY(dn.copy_out(ncand, nb, st));
+  return download(dev, idx, di.p, ib, st);
+}
+
 // The many-sets RANSAC through host pointers, on the first selected device: both arrays up, one
 // ransac_fit_batch_run.  A collection in which no set runs touches no device.
 int host_ransac_fit_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
@@ -1360,6 +1387,14 @@ int spv_nn_bruteforcel1k2_batch(const uint8_t *desc, const long long *seg_off, i
   return host_api([&] { return host_l1k2_batch(desc, seg_off, nseg, dim, pairs, npairs, idx, dist); });
 }
 
+int spv_nn_bruteforcel1k2_guided_batch(const uint8_t *desc, const float *geom, const long long *seg_off, int nseg, int dim,
+                                       const int32_t *pairs, int npairs, const double *lines, double max_dist,
+                                       uint64_t *idx, int32_t *dist, int32_t *ncand) {
+  return host_api([&] {
+    return host_l1k2_guided_batch(desc, geom, seg_off, nseg, dim, pairs, npairs, lines, max_dist, idx, dist, ncand);
+  });
+}
+
 int spv_nn_bruteforce(const void *x, const void *y, int is_int, int xrows, int yrows, int dim, int k, float p,
                       uint64_t *idx, void *dist) {
   return host_api([&] { return host_bruteforce(x, y, is_int, xrows, yrows, dim, k, p, idx, dist); });
@@ -1827,6 +1862,51 @@ int spv_l1k2_batch_device(const uint8_t *d_desc, const long long *seg_off, int n
   return api([&] {
     return l1k2_batch_run(d_desc, seg_off, nseg, dim, pairs, npairs, d_idx, d_dist, d_ws, ws_bytes,
                           static_cast<hipStream_t>(stream));
+  });
+}
+
+int spv_l1k2_guided_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs,
+                               long long out[4], int32_t *items, long long items_cap) {
+  return api([&] {
+    if (!out || (items && items_cap < 0)) return set_error(SPV_ERR_INVALID, "null output or negative items_cap");
+    L1K2GuidedPlan p;
+    SPV_TRY(l1k2_guided_plan(seg_off, nseg, dim, pairs, npairs, &p));
+    const long long n = (long long)p.items.size();
+    out[0] = n;
+    out[1] = p.out_rows;
+    out[2] = p.max_slices;
+    out[3] = (long long)p.total_bytes;
+    for (long long e = 0; items && e < std::min(n, items_cap); ++e) {
+      const L1K2BatchItem &it = p.items[(size_t)e];
+      const int32_t row[5] = {it.pair, it.y0, it.yrows, it.x0, it.xrows};
+      std::copy(row, row + 5, items + 5 * e);
+    }
+    return (int)SPV_OK;
+  });
+}
+
+size_t spv_l1k2_guided_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, const int32_t *pairs,
+                                             int npairs) {
+  L1K2GuidedPlan p;
+  const int st = guard([&] { return l1k2_guided_plan(seg_off, nseg, dim, pairs, npairs, &p); });
+  if (st != SPV_OK) clear_error();
+  return st == SPV_OK ? p.total_bytes : 0;
+}
+
+int spv_l1k2_guided_batch_device(const uint8_t *d_desc, const float *d_geom, const long long *seg_off, int nseg, int dim,
+                                 const int32_t *pairs, int npairs, const double *d_lines, double max_dist,
+                                 uint64_t *d_idx, int32_t *d_dist, int32_t *d_ncand, void *d_ws, size_t ws_bytes,
+                                 void *stream) {
+  return api([&] {
+    return l1k2_guided_run(d_desc, d_geom, seg_off, nseg, dim, pairs, npairs, d_lines, max_dist, d_idx, d_dist, d_ncand,
+                           d_ws, ws_bytes, static_cast<hipStream_t>(stream));
+  });
+}
+
+int spv_epipolar_lines_batch_device(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
+                                    int npairs, const double *G, const int32_t *use, double *d_lines, void *stream) {
+  return api([&] {
+    return epipolar_lines_run(d_geom, seg_off, nseg, pairs, npairs, G, use, d_lines, static_cast<hipStream_t>(stream));
   });
 }
 

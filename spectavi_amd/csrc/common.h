@@ -188,6 +188,26 @@ int l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *
 int l1k2_batch_run(const uint8_t *d_desc, const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs,
                    uint64_t *d_idx, int32_t *d_dist, void *d_ws, size_t ws_bytes, hipStream_t stream);
 
+// ---- L1 2-NN inside a band around each query's line, many pairs (l1k2_guided.hip) -----
+// Everything l1k2_guided_run launches for a collection.  An item is 256 queries of one pair against one slice of
+// its database set.
+struct L1K2GuidedPlan {
+  int max_slices;   // largest number of database slices of any pair
+  long long total_rows, out_rows;
+  std::vector<long long> out_off;    // [npairs + 1]: pair p owns out rows [out_off[p], out_off[p + 1])
+  std::vector<L1K2BatchItem> items;  // the grid, longest item first
+  // workspace: byte offsets, in this order.  The out rows' pairs of 64-bit keys, the device form of `items`.
+  size_t off_keys, off_items, total_bytes;
+};
+// SPV_ERR_INVALID (message set, *p untouched) outside the limits of include/spectavi_amd.h; host only
+int l1k2_guided_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs, L1K2GuidedPlan *p);
+int l1k2_guided_run(const uint8_t *d_desc, const float *d_geom, const long long *seg_off, int nseg, int dim,
+                    const int32_t *pairs, int npairs, const double *d_lines, double max_dist, uint64_t *d_idx,
+                    int32_t *d_dist, int32_t *d_ncand, void *d_ws, size_t ws_bytes, hipStream_t stream);
+// G host double[npairs, 9], use host int32[npairs] or null; asynchronous on `stream`
+int epipolar_lines_run(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs, int npairs,
+                       const double *G, const int32_t *use, double *d_lines, hipStream_t stream);
+
 // ---- matrix-core lower bound for the L1 2-NN at dim 128 (l1k2_prune.hip) -------------
 struct L1K2Bound {
   int8_t phi[256][4];  // features of a byte value

@@ -331,6 +331,98 @@ def l1k2_batch(desc, seg_off, pairs, workspace=None):
     return idx, dist, out_off
 
 
+def l1k2_guided_batch_plan(seg_off, pairs, dim=128, want_items=False):
+    """The launch plan l1k2_guided_batch() follows for a collection (spv_l1k2_guided_batch_plan; host only, no
+    device touched): dict of items (work items = workgroups), out_rows, max_slices (largest number of database
+    slices of any pair), workspace_bytes and out_off (int64[npairs + 1]).  With want_items also the work items,
+    int32[items, 5] = (pair, first query row within the query set, query rows, first database row within the
+    database set, database rows), in launch order."""
+    seg, prs, out_off = _batch_args(seg_off, pairs, None, dim)
+    if dim != 128:
+        raise ValueError("the guided L1 2-NN takes dim 128 only (dim=%d)" % dim)
+    out = (ct.c_longlong * 4)()
+    check(clib.spv_l1k2_guided_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out, None, 0))
+    plan = dict(items=int(out[0]), out_rows=int(out[1]), max_slices=int(out[2]), workspace_bytes=int(out[3]),
+                out_off=out_off)
+    if want_items:
+        items = np.empty((plan["items"], 5), np.int32)
+        check(clib.spv_l1k2_guided_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out,
+                                              items.ctypes.data, len(items)))
+        return plan, items
+    return plan
+
+
+def _need_geom(geom, total):
+    if not isinstance(geom, torch.Tensor) or geom.dim() != 2 or geom.shape[1] != 4 or geom.dtype != torch.float32:
+        raise ValueError("geom must be a float32 tensor [total_rows, 4]")
+    if total is not None and geom.shape[0] != total:
+        raise ValueError("geom has %d rows, desc has %d" % (geom.shape[0], total))
+    _need(geom, torch.float32, "geom")
+
+
+def l1k2_guided_batch(desc, geom, seg_off, pairs, lines, max_dist, workspace=None, want_ncand=False):
+    """`l1k2_batch` searched only inside a band around each query's line (spv_l1k2_guided_batch_device): desc uint8
+    [total_rows, 128], seg_off and pairs as for `l1k2_batch`; geom float32 [total_rows, 4], row for row the geometry
+    of desc (`split_sift_table`), of which columns 0 and 1 (u, v) are read; lines float64 [out_rows, 3], row r the
+    line (l0, l1, l2) of out row r in the database view's pixels (`epipolar_lines_batch`, or (0, 1, -v) for a
+    rectified pair).  Database row j is a candidate of out row r iff |fma(l0, u_j, fma(l1, v_j, l2))| <= max_dist in
+    float64 (pixels, for unit-normal lines); a NaN line or keypoint has no candidates.  Returns (idx int64 [out_rows,
+    2], dist int32 [out_rows, 2][, ncand int32 [out_rows]], out_off): the two nearest candidates by (dist, row),
+    -1 / INT_MAX where fewer than two exist, and with want_ncand the number of candidates.  Asynchronous on the
+    current stream but for the upload of the work table."""
+    _need(desc, torch.uint8, "desc")
+    if desc.dim() != 2:
+        raise ValueError("desc must be [total_rows, dim]")
+    total, dim = desc.shape
+    seg, prs, out_off = _batch_args(seg_off, pairs, total, dim)
+    if dim != 128:
+        raise ValueError("the guided L1 2-NN takes dim 128 only (dim=%d)" % dim)
+    _need_geom(geom, total)
+    out_rows = int(out_off[-1])
+    if not isinstance(lines, torch.Tensor) or lines.dtype != torch.float64 or tuple(lines.shape) != (out_rows, 3):
+        raise ValueError("lines must be a float64 tensor [out_rows, 3] = [%d, 3]" % out_rows)
+    _need(lines, torch.float64, "lines")
+    idx = torch.empty((out_rows, 2), dtype=torch.int64, device=desc.device)
+    dist = torch.empty((out_rows, 2), dtype=torch.int32, device=desc.device)
+    ncand = torch.empty((out_rows,), dtype=torch.int32, device=desc.device) if want_ncand else None
+    nbytes = clib.spv_l1k2_guided_batch_workspace_bytes(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs))
+    with _on_device_of(desc, geom, lines) as stream:
+        ws = (workspace or _default_ws).get(nbytes, desc.device)
+        check(clib.spv_l1k2_guided_batch_device(
+            desc.data_ptr(), geom.data_ptr(), seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs),
+            lines.data_ptr(), float(max_dist), idx.data_ptr(), dist.data_ptr(),
+            ncand.data_ptr() if want_ncand else None, ws.data_ptr(), ws.numel(), stream))
+    return (idx, dist, ncand, out_off) if want_ncand else (idx, dist, out_off)
+
+
+def epipolar_lines_batch(geom, seg_off, pairs, G, use=None):
+    """The lines `l1k2_guided_batch` takes, from one 3x3 matrix per pair (spv_epipolar_lines_batch_device): geom
+    float32 [total_rows, 4], seg_off and pairs as for `l1k2_batch`; G [npairs, 3, 3] (or [npairs, 9]) host float64,
+    G[p] mapping a pixel of the query view to its line in the database view; use [npairs] or None.  Out row r of
+    pair p, query keypoint (u, v), gets G[p] (u, v, 1)^T / hypot(l0, l1); three NaNs where use[p] is 0 or the norm
+    is zero or not finite.  Returns lines, CUDA float64 [out_rows, 3].  Asynchronous on the current stream.
+
+    The convention of `ransac_fit_batch`: its 'essential' E is the seven-point solution with x1^T E x0 = 0
+    (`mvg.seven_point_algorithm`: xp^T F x = 0), x0 from the database set and x1 from the query set as
+    `match_coordinates_batch` returns them.  A query point's line in the database view is therefore E^T x1, and for
+    pixel coordinates with calibration K, G = (K^-T E K^-1)^T."""
+    _need_geom(geom, None)
+    seg, prs, out_off = _batch_args(seg_off, pairs, geom.shape[0], 16)
+    G = np.ascontiguousarray(G, dtype=np.float64).reshape(-1, 9) if np.size(G) else np.zeros((0, 9))
+    if len(G) != len(prs):
+        raise ValueError("G must hold one 3x3 matrix per pair (%d), got %d" % (len(prs), len(G)))
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use).astype(bool), dtype=np.int32).reshape(-1)
+        if len(use) != len(prs):
+            raise ValueError("use must hold one flag per pair")
+    lines = torch.empty((int(out_off[-1]), 3), dtype=torch.float64, device=geom.device)
+    with _on_device_of(geom) as stream:
+        check(clib.spv_epipolar_lines_batch_device(geom.data_ptr(), seg.ctypes.data, seg.size - 1, prs.ctypes.data,
+                                                   len(prs), G.ctypes.data, None if use is None else use.ctypes.data,
+                                                   lines.data_ptr(), stream))
+    return lines
+
+
 def cascade_plan(xrows, yrows, dim, m, n, g):
     """The launch plan cascade() follows for this shape under the SPECTAVI_CASCADE_* environment of the
     moment (spv_cascade_plan; host only, no device touched): dict of family, pa, pb, gmax_q, probe_kind,

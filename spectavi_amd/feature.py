@@ -89,6 +89,62 @@ def nn_bruteforcel1k2_batch(tables, pairs=None):
     return [(idx[a:b], dist[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
 
 
+def nn_bruteforcel1k2_guided_batch(tables, geoms, lines, max_dist, pairs=None):
+    """
+    nn_bruteforcel1k2_batch searched only inside a band around each query's line (an addition: the reference has
+    no such function; its BruteForceNnL1K2::find_neighbours<Filter> is the hook this fills).  `tables` is a list of
+    uint8 arrays [rows_i, 128]; `geoms` the matching list of float32 arrays [rows_i, 4] whose columns 0 and 1 are
+    the keypoints (u, v); `pairs` as for nn_bruteforcel1k2_batch; `lines` float64 [out_rows, 3], one line
+    (l0, l1, l2) in the database view's pixels per query row of every pair, pairs back to back, or a list with one
+    such array per pair.  Database row j is a candidate of a query iff |l0 u_j + l1 v_j + l2| <= max_dist.
+
+    Returns a list with one (nn_idx uint64 [rows, 2], nn_dist int32 [rows, 2], ncand int32 [rows]) per pair: the
+    two nearest candidates, ((size_t)-1, INT_MAX) where fewer than two exist, and the number of candidates.
+    """
+    tables = [np.ascontiguousarray(t) for t in tables]
+    geoms = [np.ascontiguousarray(g) for g in geoms]
+    if not tables:
+        raise ValueError("no tables")
+    if any(t.ndim != 2 or t.dtype != np.uint8 for t in tables):
+        raise ValueError("tables must be uint8 arrays [rows, dim] of one width")
+    dim = tables[0].shape[1]
+    if any(t.shape[1] != dim for t in tables):
+        raise ValueError("tables must be uint8 arrays [rows, dim] of one width")
+    if dim != 128:
+        raise ValueError("the guided L1 2-NN takes dim 128 only (dim=%d)" % dim)
+    if len(geoms) != len(tables) or any(g.ndim != 2 or g.dtype != np.float32 or g.shape != (len(t), 4)
+                                        for g, t in zip(geoms, tables)):
+        raise ValueError("geoms must be float32 arrays [rows, 4], one per table")
+    n = len(tables)
+    if pairs is None:
+        pairs = [(j, i) for i in range(n) for j in range(i + 1, n)]
+    prs = np.asarray(pairs)
+    if prs.size == 0:
+        prs = np.zeros((0, 2), np.int32)
+    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
+        raise ValueError("pairs must be integers of shape [npairs, 2]")
+    if prs.size and (prs.min() < 0 or prs.max() >= n):
+        raise ValueError("pairs name tables outside [0, %d)" % n)
+    prs = np.ascontiguousarray(prs, dtype=np.int32)
+    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    desc = np.concatenate(tables) if seg[-1] else np.zeros((0, dim), np.uint8)
+    geom = np.concatenate(geoms) if seg[-1] else np.zeros((0, 4), np.float32)
+    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
+    rows = int(out_off[-1])
+    if isinstance(lines, (list, tuple)):
+        lines = np.concatenate([np.asarray(l, np.float64).reshape(-1, 3) for l in lines]) if lines else np.zeros((0, 3))
+    lines = np.ascontiguousarray(lines)
+    if lines.dtype != np.float64 or lines.shape != (rows, 3):
+        raise ValueError("lines must be float64 [out_rows, 3] = [%d, 3]" % rows)
+    idx = np.empty((rows, 2), np.uint64)
+    dist = np.empty((rows, 2), np.int32)
+    ncand = np.empty((rows,), np.int32)
+    check(clib.spv_nn_bruteforcel1k2_guided_batch(desc.ctypes.data, geom.ctypes.data, seg.ctypes.data, n, dim,
+                                                  prs.ctypes.data, len(prs), lines.ctypes.data, float(max_dist),
+                                                  idx.ctypes.data, dist.ctypes.data, ncand.ctypes.data))
+    return [(idx[a:b], dist[a:b], ncand[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
+
+
 # ==================================================================================
 # brute-force p-norm k-NN     (reference spectavi/feature.py:204-289)
 # ==================================================================================
