@@ -17,6 +17,9 @@ runs all of them through the many-pairs forms of the same steps, with every inte
     epipolar_lines_batch     (--guided PIXELS) every fitted pair's model as one line per query keypoint, and
     l1k2_guided_batch        the L1 2-NN again, only among the database keypoints within PIXELS of that line; the
                              same ratio test then holds more matches than the blind one
+    tracks_batch             (--tracks) every pair's inlier matches linked into multi-view tracks: the connected
+                             components of the keypoint graph; with --guided the second pass's matches are then
+                             accumulated onto the same labels
 
 Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
 they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic
@@ -24,7 +27,7 @@ here, so that the scene and the cameras are known; extracting them from images i
 before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
     python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}] [--rectify]
-                                                  [--guided PIXELS]
+                                                  [--guided PIXELS] [--tracks]
 """
 import argparse
 import os
@@ -78,7 +81,7 @@ def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_f
 
 
 def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, maximum_tries=2000, seed=1,
-                       matcher='l1k2', hash_seed=0x5eed, guided=None):
+                       matcher='l1k2', hash_seed=0x5eed, guided=None, tracks=False):
     """SIFT tables (a list of float32 [n_v,132] arrays) -> one upload -> split -> exact L1 2-NN of all pairs (or,
     matcher='cascade', the cascade hash of all pairs: descriptors normalised per view as the reference's front-end
     does, m by its rule from the largest view, n = 2, g = 2, hyperplanes from hash_seed) -> ratio
@@ -88,7 +91,10 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     out_off[p]:out_off[p + 1] are pair p's unit-norm homogeneous points) and rows (CUDA int32: the match each point
     belongs to, numbered inside its pair).  With guided (pixels) also guided_pair_off: the matches per pair of the
     second pass, the same ratio test over the L1 2-NN inside a band of that half-width around each query's epipolar
-    line in the database view; a pair without a model has none."""
+    line in the database view; a pair without a model has none.  With tracks also tracks: `tracks_batch`'s (track_off,
+    members, flags, label, track) over every pair's inlier matches and, with guided, the second pass's matches
+    accumulated onto them; and track_inputs: the seg_off, matches, count and mask (and guided_matches, guided_count)
+    those calls read."""
     import torch
     from spectavi_amd import device as spv
     seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
@@ -120,6 +126,10 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     cameras = [f['camera'] for f in fits]               # None where there is none
     X, rows, out_off = spv.dlt_triangulate_batch(x0, x1, pair_off, cameras, use=use, mask=mask, want_rows=True)
     out = {'pairs': pairs, 'pair_off': pair_off, 'fits': fits, 'out_off': out_off, 'X': X, 'rows': rows}
+    if tracks:
+        # the mask has one entry per match: rows [0, n) of matches are the call's capacity
+        out['tracks'] = spv.tracks_batch(seg, pairs, matches[:n], count, mask=mask)
+        out['track_inputs'] = {'seg_off': seg, 'matches': matches[:n], 'count': count, 'mask': mask}
     if guided is not None:
         # x1^T E x0 = 0 with x0 the database view: a query pixel's line in the database view is (K^-T E K^-1)^T x
         iK = np.linalg.inv(K)
@@ -130,6 +140,9 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
         gm, gcount = spv.ratio_test(gidx, gdist, min_ratio)
         qrows = gm[:int(gcount)].cpu().numpy()[:, 0]
         out['guided_pair_off'] = np.searchsorted(qrows, goff).astype(np.int64)
+        if tracks:
+            out['tracks'] = spv.tracks_batch(seg, pairs, gm, gcount, label=out['tracks'][3])
+            out['track_inputs'].update(guided_matches=gm, guided_count=gcount)
     return out
 
 
@@ -158,6 +171,13 @@ def report(out):
                                                                           out['pair_off'][p + 1] - out['pair_off'][p]))
     print("pairs %d fitted %d inliers %d points %d" % (len(out['pairs']), fitted, sum(len(f['inlier_idx']) for f in out['fits']),
                                                        out['out_off'][-1]))
+    if 'tracks' in out:
+        track_off, members, flags = out['tracks'][:3]
+        nt, length = len(track_off) - 1, np.diff(track_off)
+        bad = int(flags.sum())
+        print("tracks %d members %d inconsistent %d (%.1f %%)" % (nt, track_off[-1], bad, 100.0 * bad / max(1, nt)))
+        hist = np.bincount(length) if nt else np.zeros(0, np.int64)
+        print("track length: " + ", ".join("%d x %d" % (c, l) for l, c in enumerate(hist.tolist()) if c))
 
 
 def main():
@@ -169,13 +189,14 @@ def main():
     ap.add_argument("--rectify", action="store_true", help="also rectify every fitted pair (step 5), on noise images")
     ap.add_argument("--guided", type=float, default=None, metavar="PIXELS",
                     help="match again inside a band of this half-width around the fitted epipolar lines")
+    ap.add_argument("--tracks", action="store_true", help="link every pair's inlier matches into multi-view tracks")
     a = ap.parse_args()
     import torch
     tables, K = synthetic_sift_views(a.seed, a.images, a.points)
     for rep in range(2):  # the second round is the warm one
         torch.cuda.synchronize()
         s = time.perf_counter()
-        out = multiview_pipeline(tables, K, matcher=a.matcher, guided=a.guided)
+        out = multiview_pipeline(tables, K, matcher=a.matcher, guided=a.guided, tracks=a.tracks)
         torch.cuda.synchronize()
         dt = time.perf_counter() - s
     report(out)

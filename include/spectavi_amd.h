@@ -179,7 +179,8 @@ const char *spv_version(void);
  * "cascade_buckets", "cascade_probe_refine", "cascade_batch_project", "cascade_batch_buckets", "cascade_batch_probe", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "rectify_batch_bounds", "rectify_batch_box",
  * "rectify_batch", "ransac_batch_score",
  * "ransac_batch_reduce",
- * "gather_match_coords_batch", "normalize_batch_stats", "normalize_batch_finish", "normalize_batch") are bracketed by hipEvents recorded on the
+ * "gather_match_coords_batch", "normalize_batch_stats", "normalize_batch_finish", "normalize_batch", "tracks_init", "tracks_hook",
+ * "tracks_flatten", "tracks_sizes", "tracks_scan", "tracks_place", "tracks_order", "tracks_flags") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
  * last reset. */
@@ -1144,6 +1145,56 @@ int spv_gather_match_coords_device(const float *d_geom_x, const float *d_geom_y,
 int spv_gather_match_coords_batch_device(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
                                          int npairs, const int32_t *d_matches, const int32_t *d_count, int capacity,
                                          double *d_x0, double *d_x1, long long *d_pair_off, void *stream);
+
+/* Multi-view tracks (tracks_batch.hip): the connected components of the keypoint graph whose nodes are the rows of
+ * the concatenated tables (global row g = seg_off[s] + r) and whose edges are the matches of all pairs, as
+ * spv_ratio_test_device writes them over a spv_l1k2_batch_device / spv_cascade_batch_device /
+ * spv_l1k2_guided_batch_device output.  The reference has no such step.
+ *   seg_off, nseg, pairs, npairs: host arrays, the very arguments of the matching call.
+ *   d_matches int32[capacity, 2], d_count: row i = (out row, row within the database set).  Its pair p is the one with
+ *            out_off[p] <= out row < out_off[p + 1] (out_off: the running sum of the query sets' rows; empty pairs own
+ *            nothing), pairs[p] = (q, db), and the edge joins seg_off[q] + (out row - out_off[p]) and seg_off[db] + the
+ *            database row.  Only rows [0, min(*d_count, capacity)) are read, in any order.  A row whose out row lies
+ *            outside [0, out_rows) or whose database row lies outside its set is skipped.  Duplicate edges, duplicate
+ *            pairs and self pairs are legal.
+ *   d_mask   uint8[capacity] or NULL: row i is an edge only where d_mask[i] != 0.
+ *   min_len  >= 2: a track is a component of at least min_len members.
+ * Outputs, all a function of the edge set alone (the same bits for any edge order and from run to run):
+ *   d_label  int32[total_rows]: the smallest global row of the node's component.
+ *   d_track  int32[total_rows]: the node's track number or -1; tracks are numbered in ascending order of their label.
+ *   d_track_off long long[B / 2 + 1]: track t owns members [d_track_off[t], d_track_off[t + 1]).
+ *   d_members int32[B, 2] = (set, row within the set), inside a track ascending by global row.
+ *   d_flags  uint8[B / 2]: bit 0 is set iff two members of the track lie in the same set; the other bits are 0.
+ *   d_counts int32[2] = (ntracks, nmembers).
+ * B = min(total_rows, 2 * capacity); with accumulate != 0, whose members this call's capacity does not bound,
+ * B = total_rows.  Entries [0, ntracks] of d_track_off, [0, nmembers) of d_members and [0, ntracks) of d_flags are
+ * written; nothing outside d_label, d_track, d_counts and these is.
+ * accumulate != 0: d_label is read first as an earlier call's result over the same seg_off and the new edges are added
+ * to its components; two calls that split an edge set give the bits of one call over the whole set.  An incoming
+ * entry outside [0, its own row] stands for "its own row": garbage may give meaningless tracks, never an access out
+ * of bounds or a loop without an end.
+ * SPV_ERR_INVALID, nothing launched: seg_off[0] != 0 or decreasing, total_rows >= 2^31, 2^31 out rows or more, a pair
+ * outside [0, nseg), nseg < 0, npairs < 0, capacity < 0, min_len < 2, a NULL required pointer, a workspace shorter
+ * than spv_tracks_batch_workspace_bytes(total_rows, capacity) (21 bytes a row and small change, every piece rounded
+ * up to 256; it does not depend on capacity) or not 16-byte aligned.  Asynchronous on `stream` but for the upload of
+ * its small per-pair table, which stays with the calling thread until its next call; no host synchronisation.
+ * d_label doubles as the parent array of the forest while the call runs.  Kernel names for spv_profile_read, one per
+ * phase that launches: "tracks_init", "tracks_hook" (agent-scope compare-and-swap from a root's self value, larger
+ * root under smaller; not launched without a possible edge), "tracks_flatten" (ceil(log2(total_rows) / 2) + 1
+ * launches of pointer jumping, which return at once after a round that changed nothing), "tracks_sizes",
+ * "tracks_scan", "tracks_place", "tracks_order" (a stable radix sort of (track, row) by track, 8 bits a pass, as many
+ * passes as the track count has bytes), "tracks_flags".
+ * spv_tracks_batch: host pointers, on the first selected device; matches int32[count, 2], every output sized as above
+ * with capacity = count; label is read only with accumulate != 0.  Touches no device when total_rows is 0. */
+size_t spv_tracks_batch_workspace_bytes(long long total_rows, int capacity);
+int spv_tracks_batch_device(const long long *seg_off, int nseg, const int32_t *pairs, int npairs,
+                            const int32_t *d_matches, const int32_t *d_count, int capacity, const uint8_t *d_mask,
+                            int min_len, int accumulate, int32_t *d_label, int32_t *d_track, long long *d_track_off,
+                            int32_t *d_members, uint8_t *d_flags, int32_t *d_counts, void *d_ws, size_t ws_bytes,
+                            void *stream);
+int spv_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const int32_t *matches,
+                     int count, const uint8_t *mask, int min_len, int accumulate, int32_t *label, int32_t *track,
+                     long long *track_off, int32_t *members, uint8_t *flags, int32_t *counts);
 
 /* normalize_to_ubyte_and_multiple_16_dim (reference spectavi/feature.py:384-407) for a float32
  * input, bit for bit what numpy computes: per-column de-mean (numpy's row-ordered float32 sum),

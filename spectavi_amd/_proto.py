@@ -163,6 +163,9 @@ PROTOTYPES = {
     "spv_sift_split_device": (i, [vp, i, vp, vp, vp]),
     "spv_gather_match_coords_device": (i, [vp] * 4 + [i] + [vp] * 3),
     "spv_gather_match_coords_batch_device": (i, [vp, vp, i, vp, i, vp, vp, i, vp, vp, vp, vp]),
+    "spv_tracks_batch_workspace_bytes": (sz, [ll, i]),
+    "spv_tracks_batch_device": (i, [vp, i, vp, i, vp, vp, i, vp, i, i] + [vp] * 7 + [sz, vp]),
+    "spv_tracks_batch": (i, [vp, i, vp, i, vp, i, vp, i, i] + [vp] * 6),
     "spv_normalize": (i, [f32a, i, i, vp, vp]),
     "spv_normalize_workspace_bytes": (sz, [i]),
     "spv_normalize_workspace_bytes_rows": (sz, [i, i]),

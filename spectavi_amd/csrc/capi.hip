@@ -296,6 +296,48 @@ int host_l1k2_guided_batch(const uint8_t *desc, const float *geom, const long lo
   return download(dev, idx, di.p, ib, st);
 }
 
+// The tracks of a collection through host pointers, on the first selected device: matches, mask and (continuing)
+// label up, one tracks_batch_run, the counts back, then as much of every output as the counts say.  A collection
+// without a row touches no device.
+int host_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const int32_t *matches, int count,
+                      const uint8_t *mask, int min_len, int accumulate, int32_t *label, int32_t *track, long long *track_off,
+                      int32_t *members, uint8_t *flags, int32_t *counts) {
+  SPV_TRY(tracks_batch_check(seg_off, nseg, pairs, npairs, count, min_len));
+  const long long n = seg_off[nseg];
+  const long long bound = tracks_batch_member_bound(n, count, accumulate);
+  if (!counts || !track_off || (n > 0 && (!label || !track)) || (count > 0 && !matches) || (bound > 0 && !members) ||
+      (bound > 1 && !flags))
+    return set_error(SPV_ERR_INVALID, "null pointer");
+  counts[0] = counts[1] = 0;
+  track_off[0] = 0;
+  if (n == 0) return SPV_OK;
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t mb = (size_t)count * 2 * sizeof(int32_t), kb = mask ? (size_t)count : 0, lb = (size_t)n * sizeof(int32_t);
+  const size_t wsb = tracks_batch_workspace_bytes(n, count);
+  const int32_t cnt = count;
+  DevBuf dm, dk, dc, dl, dt, doff, dmem, df, dn, ws;
+  SPV_TRY(alloc_all({{&dm, mb}, {&dk, kb}, {&dc, sizeof(int32_t)}, {&dl, lb}, {&dt, lb},
+                     {&doff, (size_t)(bound / 2 + 1) * sizeof(long long)}, {&dmem, (size_t)bound * 2 * sizeof(int32_t)},
+                     {&df, (size_t)(bound / 2)}, {&dn, 2 * sizeof(int32_t)}, {&ws, wsb}}));
+  SPV_TRY(dm.copy_in(matches, mb, st));
+  SPV_TRY(dk.copy_in(mask, kb, st));
+  SPV_TRY(dc.copy_in(&cnt, sizeof(int32_t), st));
+  if (accumulate) SPV_TRY(dl.copy_in(label, lb, st));
+  SPV_TRY(tracks_batch_run(seg_off, nseg, pairs, npairs, dm.as<int32_t>(), dc.as<int32_t>(), count,
+                           mask ? dk.as<uint8_t>() : nullptr, min_len, accumulate, dl.as<int32_t>(), dt.as<int32_t>(),
+                           doff.as<long long>(), dmem.as<int32_t>(), df.as<uint8_t>(), dn.as<int32_t>(), ws.p, wsb, st));
+  SPV_TRY(dn.copy_out(counts, 2 * sizeof(int32_t), st));
+  SPV_TRY(dl.copy_out(label, lb, st));
+  SPV_TRY(dt.copy_out(track, lb, st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  SPV_TRY(doff.copy_out(track_off, (size_t)(counts[0] + 1) * sizeof(long long), st));
+  SPV_TRY(dmem.copy_out(members, (size_t)counts[1] * 2 * sizeof(int32_t), st));
+  SPV_TRY(df.copy_out(flags, (size_t)counts[0], st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  return SPV_OK;
+}
+
 // The many-sets RANSAC through host pointers, on the first selected device: both arrays up, one
 // ransac_fit_batch_run.  A collection in which no set runs touches no device.
 int host_ransac_fit_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
@@ -1496,6 +1538,26 @@ int spv_gather_match_coords_batch_device(const float *d_geom, const long long *s
   return api([&] {
     return gather_match_coords_batch_run(d_geom, seg_off, nseg, pairs, npairs, d_matches, d_count, capacity, d_x0, d_x1,
                                          d_pair_off, static_cast<hipStream_t>(stream));
+  });
+}
+size_t spv_tracks_batch_workspace_bytes(long long total_rows, int capacity) {
+  return (total_rows < 0 || total_rows >= (1ll << 31) || capacity < 0) ? 0 : tracks_batch_workspace_bytes(total_rows, capacity);
+}
+int spv_tracks_batch_device(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const int32_t *d_matches,
+                            const int32_t *d_count, int capacity, const uint8_t *d_mask, int min_len, int accumulate,
+                            int32_t *d_label, int32_t *d_track, long long *d_track_off, int32_t *d_members,
+                            uint8_t *d_flags, int32_t *d_counts, void *d_ws, size_t ws_bytes, void *stream) {
+  return api([&] {
+    return tracks_batch_run(seg_off, nseg, pairs, npairs, d_matches, d_count, capacity, d_mask, min_len, accumulate, d_label,
+                            d_track, d_track_off, d_members, d_flags, d_counts, d_ws, ws_bytes, static_cast<hipStream_t>(stream));
+  });
+}
+int spv_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const int32_t *matches, int count,
+                     const uint8_t *mask, int min_len, int accumulate, int32_t *label, int32_t *track, long long *track_off,
+                     int32_t *members, uint8_t *flags, int32_t *counts) {
+  return host_api([&] {
+    return host_tracks_batch(seg_off, nseg, pairs, npairs, matches, count, mask, min_len, accumulate, label, track, track_off,
+                             members, flags, counts);
   });
 }
 int spv_ratio_test(const uint64_t *idx, const void *dist, int dist_is_float, int yrows,

@@ -568,4 +568,16 @@ int gather_match_coords_batch_run(const float *d_geom, const long long *seg_off,
                                   int npairs, const int *d_matches, const int *d_count, int capacity, double *d_x0,
                                   double *d_x1, long long *d_pair_off, hipStream_t stream);
 
+// ---- multi-view tracks from the matches of all pairs (tracks_batch.hip) --------------------
+// SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
+int tracks_batch_check(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, int capacity, int min_len);
+size_t tracks_batch_workspace_bytes(long long total_rows, int capacity);
+// B of include/spectavi_amd.h: the rows of members; track_off has B / 2 + 1 entries, flags B / 2
+long long tracks_batch_member_bound(long long total_rows, int capacity, int accumulate);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the call's table.
+int tracks_batch_run(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const int32_t *d_matches,
+                     const int32_t *d_count, int capacity, const uint8_t *d_mask, int min_len, int accumulate,
+                     int32_t *d_label, int32_t *d_track, long long *d_track_off, int32_t *d_members, uint8_t *d_flags,
+                     int32_t *d_counts, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
 }  // namespace spv

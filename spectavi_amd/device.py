@@ -1024,6 +1024,73 @@ def match_coordinates_batch(geom, seg_off, pairs, matches, count):
     return x0, x1, pair_off.cpu().numpy()
 
 
+def _tracks_batch_args(seg_off, pairs, capacity, min_len):
+    """seg_off -> int64[nseg + 1], pairs -> int32[npairs, 2]; ValueError for anything spv_tracks_batch_device would
+    reject, before any device is touched."""
+    seg, prs, out_off = _batch_args(seg_off, pairs, None, 16)
+    if int(out_off[-1]) >= 2 ** 31:
+        raise ValueError("the pairs must own fewer than 2^31 out rows in all")
+    if int(capacity) < 0:
+        raise ValueError("capacity must not be negative")
+    if int(min_len) != min_len or int(min_len) < 2:
+        raise ValueError("min_len must be an integer >= 2: a track has at least two members")
+    return seg, prs
+
+
+def tracks_batch(seg_off, pairs, matches, count, mask=None, min_len=2, label=None, workspace=None):
+    """Multi-view tracks on device: the connected components of the graph whose nodes are the rows of the
+    concatenated tables (global row seg_off[s] + r) and whose edges are the matches of all pairs.  seg_off and pairs
+    are the arguments of the `l1k2_batch` / `cascade_batch` / `l1k2_guided_batch` call, (matches, count) what
+    `ratio_test` returned over its output, in any order; mask (uint8 [capacity], e.g. `ransac_fit_batch(want_mask=
+    True)`'s) keeps row i only where it is not zero.  Rows out of range are skipped.
+
+    Returns (track_off int64 ndarray [ntracks + 1], members int32 [nmembers, 2] = (set, row within the set), flags
+    uint8 [ntracks], label int32 [total_rows], track int32 [total_rows]), the last four CUDA tensors: a track is a
+    component of at least min_len members, tracks are numbered in ascending order of their label (the smallest
+    global row), a track's members ascend by global row, bit 0 of flags marks a track with two members in one set,
+    track is -1 outside every track.  Every output is a function of the edge set alone, bit for bit.
+
+    Passing `label` (an earlier call's, over the same seg_off) continues from it -- the guided pass's matches on top
+    of the blind pass's: the tensor is updated in place and returned, and the result is that of one call over both
+    edge sets.  Reading the two counts back (and then the ntracks + 1 offsets they size) is where the call
+    synchronises with the current stream; the library call itself does not."""
+    if matches.dim() != 2 or matches.shape[1] != 2:
+        raise ValueError("matches must be [capacity, 2]")
+    cap = int(matches.shape[0])
+    seg, prs = _tracks_batch_args(seg_off, pairs, cap, min_len)
+    total = int(seg[-1])
+    _need(matches, torch.int32, "matches")
+    _need(count, torch.int32, "count")
+    if mask is not None:
+        _need(mask, torch.uint8, "mask")
+        if mask.numel() < cap:
+            raise ValueError("mask must have one entry per row of matches")
+    dev = matches.device
+    accumulate = label is not None
+    if accumulate:
+        _need(label, torch.int32, "label")
+        if label.dim() != 1 or label.numel() != total:
+            raise ValueError("label must be int32 [%d]" % total)
+    else:
+        label = torch.empty(total, dtype=torch.int32, device=dev)
+    bound = total if accumulate else min(total, 2 * cap)
+    track = torch.empty(total, dtype=torch.int32, device=dev)
+    track_off = torch.empty(bound // 2 + 1, dtype=torch.int64, device=dev)
+    members = torch.empty((bound, 2), dtype=torch.int32, device=dev)
+    flags = torch.empty(bound // 2, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    nbytes = clib.spv_tracks_batch_workspace_bytes(total, cap)
+    with _on_device_of(matches, count, mask, label) as stream:
+        ws = (workspace or _default_ws).get(nbytes, dev)
+        check(clib.spv_tracks_batch_device(seg.ctypes.data, seg.size - 1, prs.ctypes.data, len(prs), matches.data_ptr(),
+                                           count.data_ptr(), cap, mask.data_ptr() if mask is not None else None,
+                                           int(min_len), int(accumulate), label.data_ptr(), track.data_ptr(),
+                                           track_off.data_ptr(), members.data_ptr(), flags.data_ptr(), counts.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), stream))
+    nt, nm = counts.cpu().tolist()
+    return track_off[:nt + 1].cpu().numpy(), members[:nm], flags[:nt], label, track
+
+
 def normalize(x, want_float=True, want_ubyte=False, workspace=None):
     """`normalize_to_ubyte_and_multiple_16_dim` (reference spectavi/feature.py:384-407) on a CUDA float32
     [rows, dim] table, bit-identical to the numpy function: returns the float32 [rows, dim16] table

@@ -145,6 +145,64 @@ def nn_bruteforcel1k2_guided_batch(tables, geoms, lines, max_dist, pairs=None):
     return [(idx[a:b], dist[a:b], ncand[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
 
 
+def match_tracks_batch(sizes, pairs, matches, masks=None, min_len=2):
+    """
+    Multi-view tracks from the matches of many table pairs (an addition: the reference has no such function; its
+    pipeline stops at two views).  `sizes` holds the rows of every table, `pairs` is a list of (query table,
+    database table) numbers, `matches` a list with one integer array [k_p, 2] of (query row, database row) per pair,
+    `masks` None or a list with one array [k_p] per pair: a match counts only where its mask entry is not zero.
+    Matches whose rows lie outside their tables are skipped.
+
+    The keypoints are the nodes of a graph, the matches its edges; a track is a connected component of at least
+    `min_len` keypoints.  Returns (track_off int64 [ntracks + 1], members int32 [nmembers, 2] = (table, row), flags
+    uint8 [ntracks]): track t owns members[track_off[t]:track_off[t + 1]], ascending by table and row; tracks are
+    in ascending order of their first member; bit 0 of flags[t] is set iff the track holds two keypoints of one table.
+    """
+    sizes = np.asarray(sizes)
+    if sizes.ndim != 1 or (sizes.size and (sizes.dtype.kind not in "iu" or sizes.min() < 0)):
+        raise ValueError("sizes must be non-negative integers, one per table")
+    n = len(sizes)
+    seg = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+    if int(seg[-1]) >= 2 ** 31:
+        raise ValueError("the tables must hold fewer than 2^31 rows in all")
+    prs = np.asarray(pairs)
+    if prs.size == 0:
+        prs = np.zeros((0, 2), np.int32)
+    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
+        raise ValueError("pairs must be integers of shape [npairs, 2]")
+    if prs.size and (prs.min() < 0 or prs.max() >= n):
+        raise ValueError("pairs name tables outside [0, %d)" % n)
+    prs = np.ascontiguousarray(prs, dtype=np.int32)
+    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
+    if int(out_off[-1]) >= 2 ** 31:
+        raise ValueError("the pairs must own fewer than 2^31 out rows in all")
+    if int(min_len) != min_len or int(min_len) < 2:
+        raise ValueError("min_len must be an integer >= 2: a track has at least two members")
+    if len(matches) != len(prs) or (masks is not None and len(masks) != len(prs)):
+        raise ValueError("matches (and masks) must hold one array per pair")
+    rows, keep = [], []
+    for p in range(len(prs)):
+        m = np.asarray(matches[p]).reshape(-1, 2).astype(np.int64)
+        k = np.ones(len(m), bool) if masks is None else np.asarray(masks[p]).reshape(-1) != 0
+        if len(k) != len(m):
+            raise ValueError("mask %d has %d entries for %d matches" % (p, len(k), len(m)))
+        k = k & (m[:, 0] >= 0) & (m[:, 0] < out_off[p + 1] - out_off[p])   # a query row outside its table is no out row
+        m = m[k]
+        rows.append(np.stack([m[:, 0] + out_off[p], np.clip(m[:, 1], -1, 2 ** 31 - 1)], 1))
+    cat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 2)), dtype=np.int32)
+    if len(cat) >= 2 ** 31:
+        raise ValueError("fewer than 2^31 matches in all")
+    total, bound = int(seg[-1]), min(int(seg[-1]), 2 * len(cat))
+    label, track = np.empty(total, np.int32), np.empty(total, np.int32)
+    track_off, members = np.empty(bound // 2 + 1, np.int64), np.empty((bound, 2), np.int32)
+    flags, counts = np.empty(bound // 2, np.uint8), np.zeros(2, np.int32)
+    check(clib.spv_tracks_batch(seg.ctypes.data, n, prs.ctypes.data, len(prs), cat.ctypes.data, len(cat), None,
+                                int(min_len), 0, label.ctypes.data, track.ctypes.data, track_off.ctypes.data,
+                                members.ctypes.data, flags.ctypes.data, counts.ctypes.data))
+    nt, nm = int(counts[0]), int(counts[1])
+    return track_off[:nt + 1].copy(), members[:nm].copy(), flags[:nt].copy()
+
+
 # ==================================================================================
 # brute-force p-norm k-NN     (reference spectavi/feature.py:204-289)
 # ==================================================================================
