@@ -95,27 +95,8 @@ __global__ __launch_bounds__(kThreads) void gather_match_coords_batch_kernel(
   x1[3 * (size_t)i + 2] = 1.0;
 }
 
-// The per-pair table of the batch gather lives with the calling thread between calls (the call has no workspace
-// argument and does not wait for its kernel): a grow-only device buffer and the event of the kernel that read it
-// last, which the next call of the thread waits for before it overwrites the table.
-struct GatherTable {
-  void *p = nullptr;
-  size_t cap = 0;
-  int dev = -1;
-  hipEvent_t ev = nullptr;
-  void drop() {
-    if (ev) {
-      (void)hipEventSynchronize(ev);
-      (void)hipEventDestroy(ev);
-      ev = nullptr;
-    }
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  ~GatherTable() { drop(); }
-};
-thread_local GatherTable g_gather_table;
+// The per-pair table of the batch gather (pair_table, collection.h) lives with the calling thread between calls.
+thread_local DeviceTable g_gather_table;
 
 }  // namespace
 
@@ -149,40 +130,13 @@ int gather_match_coords_run(const float *d_geom_x, const float *d_geom_y, const 
 int gather_match_coords_batch_run(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs,
                                   int npairs, const int *d_matches, const int *d_count, int capacity, double *d_x0,
                                   double *d_x1, long long *d_pair_off, hipStream_t stream) {
-  // seg_off and pairs: the rules of l1k2_batch_plan
-  if (nseg < 0 || npairs < 0) return set_error(SPV_ERR_INVALID, "negative count (nseg=%d, npairs=%d)", nseg, npairs);
+  SPV_TRY(check_collection_out32(seg_off, nseg, pairs, npairs));
   if (capacity < 0) return set_error(SPV_ERR_INVALID, "negative capacity");
-  if (!seg_off || (npairs > 0 && !pairs)) return set_error(SPV_ERR_INVALID, "null pointer");
-  if (seg_off[0] != 0) return set_error(SPV_ERR_INVALID, "seg_off[0] = %lld, must be 0", seg_off[0]);
-  for (int s = 0; s < nseg; ++s)
-    if (seg_off[s + 1] < seg_off[s]) return set_error(SPV_ERR_INVALID, "seg_off decreases at set %d", s);
-  if (seg_off[nseg] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld rows in all, must be below 2^31", seg_off[nseg]);
-  for (int i = 0; i < 2 * npairs; ++i)
-    if (pairs[i] < 0 || pairs[i] >= nseg) return set_error(SPV_ERR_INVALID, "pair %d names set %d of %d", i / 2, (int)pairs[i], nseg);
-  std::vector<long long> tab((size_t)3 * npairs + 1, 0);
-  for (int p = 0; p < npairs; ++p) {
-    const int q = pairs[2 * p], d = pairs[2 * p + 1];
-    tab[(size_t)p + 1] = tab[p] + (seg_off[q + 1] - seg_off[q]);
-    tab[(size_t)npairs + 1 + p] = seg_off[q];
-    tab[(size_t)2 * npairs + 1 + p] = seg_off[d];
-  }
-  if (tab[npairs] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld out rows, must be below 2^31", tab[npairs]);
   if (!d_pair_off || !d_count || (capacity > 0 && (!d_geom || !d_matches || !d_x0 || !d_x1)))
     return set_error(SPV_ERR_INVALID, "null device pointer");
-  GatherTable &t = g_gather_table;
-  const size_t bytes = tab.size() * sizeof(long long);
-  int dev = 0;
-  SPV_HIP_CHECK(hipGetDevice(&dev));
-  if (t.ev) SPV_HIP_CHECK(hipEventSynchronize(t.ev));  // the kernel that read the table last
-  if (t.dev != dev || t.cap < bytes) {
-    t.drop();
-    SPV_HIP_CHECK(hipMalloc(&t.p, bytes));
-    t.cap = bytes;
-    t.dev = dev;
-  }
-  if (!t.ev) SPV_HIP_CHECK(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
-  // (pageable source: the copy has left `tab` when the call returns)
-  SPV_HIP_CHECK(hipMemcpyAsync(t.p, tab.data(), bytes, hipMemcpyHostToDevice, stream));
+  const std::vector<long long> tab = pair_table(seg_off, nseg, pairs, npairs);
+  DeviceTable &t = g_gather_table;
+  SPV_TRY(t.upload(tab.data(), ((size_t)3 * npairs + 1) * sizeof(long long), stream));
   const long long threads = std::max<long long>(capacity, (long long)npairs + 1);
   {
     ProfScope prof("gather_match_coords_batch", stream);
@@ -190,8 +144,7 @@ int gather_match_coords_batch_run(const float *d_geom, const long long *seg_off,
                        0, stream, d_geom, (const long long *)t.p, npairs, d_matches, d_count, capacity, d_x0, d_x1, d_pair_off);
     SPV_HIP_CHECK(hipGetLastError());
   }
-  SPV_HIP_CHECK(hipEventRecord(t.ev, stream));
-  return SPV_OK;
+  return t.record(stream);
 }
 
 }  // namespace spv

@@ -141,6 +141,24 @@ static int host_api(Fn fn) {
   return host_guard(fn);
 }
 
+// What a *_batch_plan entry hands out of its items: the first min(n, items_cap) of them, as rows of N int32 columns,
+// where the caller wants them (items_cap >= 0 is the entry's own rule).
+template <int N, typename Item>
+static void export_items(const std::vector<Item> &its, int32_t *items, long long items_cap) {
+  static_assert(sizeof(Item) == N * sizeof(int32_t), "an item is N int32 columns");
+  if (items) memcpy(items, its.data(), (size_t)std::min<long long>(items_cap, (long long)its.size()) * sizeof(Item));
+}
+
+// The body of a *_batch_workspace_bytes query: the bytes of the plan `make` fills, or 0 where it refuses the
+// arguments, with no error left behind.
+template <typename Plan, typename Base, typename Fn>
+static size_t plan_bytes(size_t Base::*bytes, Fn make) {
+  Plan p;
+  const int st = guard([&] { return make(&p); });
+  if (st != SPV_OK) clear_error();
+  return st == SPV_OK ? p.*bytes : 0;
+}
+
 int device_cu_count() {
   static std::atomic<int> cache[64];  // per device, 0 = not asked yet
   int dev = 0;
@@ -580,7 +598,7 @@ int host_sift_tables(const float *images, const int32_t *sizes, int nimg, float 
                      int32_t *counts) {
   SiftBatchPlan plan;
   SPV_TRY(sift_batch_plan(sizes, nimg, 0, &plan));
-  SPV_TRY(sift_batch_check_offsets(cap_off, nimg, "cap_off"));
+  SPV_TRY(check_offsets(cap_off, nimg, "cap_off"));
   if (nimg == 0) return SPV_OK;
   if (!images || !counts || (cap_off[nimg] > 0 && !table)) return set_error(SPV_ERR_INVALID, "null pointer");
   hipStream_t st;
@@ -1502,15 +1520,13 @@ int spv_normalize_batch_plan(const long long *seg_off, int nseg, int dim, int dt
     out[1] = (long long)p.items.size();
     out[2] = (long long)p.total_bytes;
     out[3] = p.total_rows;
-    if (items) memcpy(items, p.items.data(), (size_t)std::min<long long>(items_cap, (long long)p.items.size()) * sizeof(NormalizeBatchItem));
+    export_items<3>(p.items, items, items_cap);
     return (int)SPV_OK;
   });
 }
 size_t spv_normalize_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, int dtype) {
-  NormalizeBatchPlan p;
-  const int st = guard([&] { return normalize_batch_plan(seg_off, nseg, dim, dtype, &p); });
-  if (st != SPV_OK) clear_error();
-  return st == SPV_OK ? p.total_bytes : 0;
+  return plan_bytes<NormalizeBatchPlan>(&NormalizeBatchPlan::total_bytes,
+                                        [&](NormalizeBatchPlan *p) { return normalize_batch_plan(seg_off, nseg, dim, dtype, p); });
 }
 int spv_normalize_batch_device(const void *d_x, int dtype, const long long *seg_off, int nseg, int dim, float *d_out_f32,
                                uint8_t *d_out_u8, void *d_ws, size_t ws_bytes, void *stream) {
@@ -1767,8 +1783,7 @@ int spv_ransac_fit_batch_plan(const long long *pair_off, int npairs, int maximum
     out[1] = tries;
     out[2] = (long long)its.size();
     out[3] = blocks;
-    static_assert(sizeof(RansacBatchItem) == 5 * sizeof(int32_t), "items are int32[5]");
-    if (items) memcpy(items, its.data(), (size_t)std::min<long long>(items_cap, (long long)its.size()) * sizeof(RansacBatchItem));
+    export_items<5>(its, items, items_cap);
     return (int)SPV_OK;
   });
 }
@@ -1790,7 +1805,7 @@ int spv_dlt_triangulate_batch_plan(const long long *pair_off, int npairs, const 
     out[0] = used;
     out[1] = (long long)its.size();
     out[2] = bound;
-    if (items) memcpy(items, its.data(), (size_t)std::min<long long>(items_cap, (long long)its.size()) * sizeof(DltBatchItem));
+    export_items<4>(its, items, items_cap);
     return (int)SPV_OK;
   });
 }
@@ -1814,7 +1829,7 @@ int spv_rectify_batch_plan(const int32_t *sizes, int nimg, int nchan, double sam
     out[1] = (long long)pl.items.size();
     out[2] = pl.out_off[npairs];
     memcpy(out_off, pl.out_off.data(), ((size_t)npairs + 1) * sizeof(long long));
-    if (items) memcpy(items, pl.items.data(), (size_t)std::min<long long>(items_cap, (long long)pl.items.size()) * sizeof(RectifyBatchItem));
+    export_items<4>(pl.items, items, items_cap);
     return (int)SPV_OK;
   });
 }
@@ -1903,20 +1918,14 @@ int spv_l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32
     out[3] = p.out_rows;
     out[4] = p.max_slices;
     out[5] = (long long)p.total_bytes;
-    for (long long e = 0; items && e < std::min(n, items_cap); ++e) {
-      const L1K2BatchItem &it = p.items[(size_t)e];
-      const int32_t row[5] = {it.pair, it.y0, it.yrows, it.x0, it.xrows};
-      std::copy(row, row + 5, items + 5 * e);
-    }
+    export_items<5>(p.items, items, items_cap);
     return (int)SPV_OK;
   });
 }
 
 size_t spv_l1k2_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs) {
-  L1K2BatchPlan p;
-  const int st = guard([&] { return l1k2_batch_plan(seg_off, nseg, dim, pairs, npairs, &p); });
-  if (st != SPV_OK) clear_error();
-  return st == SPV_OK ? p.total_bytes : 0;
+  return plan_bytes<L1K2BatchPlan>(&L1K2BatchPlan::total_bytes,
+                                   [&](L1K2BatchPlan *p) { return l1k2_batch_plan(seg_off, nseg, dim, pairs, npairs, p); });
 }
 
 int spv_l1k2_batch_device(const uint8_t *d_desc, const long long *seg_off, int nseg, int dim, const int32_t *pairs,
@@ -1938,21 +1947,15 @@ int spv_l1k2_guided_batch_plan(const long long *seg_off, int nseg, int dim, cons
     out[1] = p.out_rows;
     out[2] = p.max_slices;
     out[3] = (long long)p.total_bytes;
-    for (long long e = 0; items && e < std::min(n, items_cap); ++e) {
-      const L1K2BatchItem &it = p.items[(size_t)e];
-      const int32_t row[5] = {it.pair, it.y0, it.yrows, it.x0, it.xrows};
-      std::copy(row, row + 5, items + 5 * e);
-    }
+    export_items<5>(p.items, items, items_cap);
     return (int)SPV_OK;
   });
 }
 
 size_t spv_l1k2_guided_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, const int32_t *pairs,
                                              int npairs) {
-  L1K2GuidedPlan p;
-  const int st = guard([&] { return l1k2_guided_plan(seg_off, nseg, dim, pairs, npairs, &p); });
-  if (st != SPV_OK) clear_error();
-  return st == SPV_OK ? p.total_bytes : 0;
+  return plan_bytes<L1K2GuidedPlan>(&L1K2GuidedPlan::total_bytes,
+                                    [&](L1K2GuidedPlan *p) { return l1k2_guided_plan(seg_off, nseg, dim, pairs, npairs, p); });
 }
 
 int spv_l1k2_guided_batch_device(const uint8_t *d_desc, const float *d_geom, const long long *seg_off, int nseg, int dim,
@@ -2074,19 +2077,13 @@ int spv_sift_batch_plan(const int32_t *sizes, int nimg, size_t ws_bytes, long lo
     out[1] = (long long)p.all_bytes;
     out[2] = (long long)p.min_bytes;
     out[3] = p.pixels;
-    for (long long e = 0; groups && e < std::min(n, groups_cap); ++e) {
-      groups[2 * e] = p.groups[(size_t)e].first;
-      groups[2 * e + 1] = p.groups[(size_t)e].second;
-    }
+    export_items<2>(p.groups, groups, groups_cap);
     return (int)SPV_OK;
   });
 }
 
 size_t spv_sift_batch_workspace_bytes(const int32_t *sizes, int nimg) {
-  SiftBatchPlan p;
-  const int st = guard([&] { return sift_batch_plan(sizes, nimg, 0, &p); });
-  if (st != SPV_OK) clear_error();
-  return st == SPV_OK ? p.all_bytes : 0;
+  return plan_bytes<SiftBatchPlan>(&SiftBatchPlan::all_bytes, [&](SiftBatchPlan *p) { return sift_batch_plan(sizes, nimg, 0, p); });
 }
 
 int spv_sift_batch_device(const float *d_images, const int32_t *sizes, int nimg, void *d_ws, size_t ws_bytes,
@@ -2134,21 +2131,16 @@ int spv_cascade_batch_plan(const long long *seg_off, int nseg, int dim, int m, i
     out[1] = p.out_rows;
     out[2] = p.hb;
     out[3] = (long long)p.total_bytes;
-    for (long long e = 0; items && e < std::min(cnt, items_cap); ++e) {
-      const CascadeBatchItem &it = p.items[(size_t)e];
-      const int32_t row[3] = {it.pair, it.y0, it.yrows};
-      std::copy(row, row + 3, items + 3 * e);
-    }
+    export_items<3>(p.items, items, items_cap);
     return (int)SPV_OK;
   });
 }
 
 size_t spv_cascade_batch_workspace_bytes(const long long *seg_off, int nseg, int dim, int m, int n, int g,
                                          const int32_t *pairs, int npairs) {
-  CascadeBatchPlan p;
-  const int st = guard([&] { return cascade_batch_plan(seg_off, nseg, dim, m, n, g, pairs, npairs, &p); });
-  if (st != SPV_OK) clear_error();
-  return st == SPV_OK ? p.total_bytes : 0;
+  return plan_bytes<CascadeBatchPlan>(&CascadeBatchPlan::total_bytes, [&](CascadeBatchPlan *p) {
+    return cascade_batch_plan(seg_off, nseg, dim, m, n, g, pairs, npairs, p);
+  });
 }
 
 int spv_cascade_batch_device(const float *d_rows, const long long *seg_off, int nseg, int dim, int m, int n, int g,

@@ -249,7 +249,8 @@ constexpr size_t kBatchBucketBytes = (size_t)1 << 30;
 
 int cascade_batch_plan(const long long *seg_off, int nseg, int dim, int m, int n, int g, const int32_t *pairs,
                        int npairs, CascadeBatchPlan *out) {
-  if (nseg < 0 || npairs < 0) return set_error(SPV_ERR_INVALID, "negative count (nseg=%d, npairs=%d)", nseg, npairs);
+  if (!seg_off && nseg == 0) seg_off = kNoSets;  // no sets: seg_off may be null
+  SPV_TRY(check_collection(seg_off, nseg, pairs, npairs));
   if (dim <= 0 || dim % 16 != 0)
     return set_error(SPV_ERR_INVALID, "Input matrix inner dimensions must be 16-byte aligned (dim=%d).", dim);
   if (dim > kCascadeBatchMaxDim)
@@ -262,26 +263,14 @@ int cascade_batch_plan(const long long *seg_off, int nseg, int dim, int m, int n
   if ((long long)nseg * n > kCascadeBatchMaxTables)
     return set_error(SPV_ERR_INVALID, "nseg * n = %lld bucket tables, more than the %d a scan launch takes",
                      (long long)nseg * n, kCascadeBatchMaxTables);
-  if ((nseg > 0 && !seg_off) || (npairs > 0 && !pairs)) return set_error(SPV_ERR_INVALID, "null pointer");
-  if (seg_off && seg_off[0] != 0) return set_error(SPV_ERR_INVALID, "seg_off[0] = %lld, must be 0", seg_off[0]);
-  for (int s = 0; s < nseg; ++s)
-    if (seg_off[s + 1] < seg_off[s]) return set_error(SPV_ERR_INVALID, "seg_off decreases at set %d", s);
   CascadeBatchPlan p{};
-  p.total_rows = nseg > 0 ? seg_off[nseg] : 0;
-  if (p.total_rows >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld rows in all, must be below 2^31", p.total_rows);
-  for (int i = 0; i < 2 * npairs; ++i)
-    if (pairs[i] < 0 || pairs[i] >= nseg)
-      return set_error(SPV_ERR_INVALID, "pair %d names set %d of %d", i / 2, (int)pairs[i], nseg);
+  p.total_rows = seg_off[nseg];
   auto rows = [&](int s) { return seg_off[s + 1] - seg_off[s]; };
 
-  p.out_off.assign((size_t)npairs + 1, 0);
-  long long count = 0;
-  for (int i = 0; i < npairs; ++i) {
-    const long long nq = rows(pairs[2 * i]);
-    p.out_off[i + 1] = p.out_off[i] + nq;
-    count += (nq + kCascadeBatchItemRows - 1) / kCascadeBatchItemRows;
-  }
+  p.out_off = pair_out_off(seg_off, pairs, npairs);
   p.out_rows = p.out_off[npairs];
+  long long count = 0;
+  for (int i = 0; i < npairs; ++i) count += (rows(pairs[2 * i]) + kCascadeBatchItemRows - 1) / kCascadeBatchItemRows;
   if (count > 0x7FFFFFFFll) return set_error(SPV_ERR_INVALID, "%lld work items, more than a grid takes", count);
   p.items.reserve((size_t)count);
   for (int i = 0; i < npairs; ++i) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/spectavi_amd.h"
+#include "collection.h"
 
 namespace spv {
 
@@ -165,23 +166,44 @@ int l1k2_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows, int d
 // l1k2.hip's pad_rows_kernel on `stream`: rows of dim bytes -> rows of dim_pad bytes, zero filled (both multiples of 16)
 void l1k2_pad_rows(const uint8_t *d_src, uint8_t *d_dst, size_t rows, int dim, int dim_pad, hipStream_t stream);
 
-// ---- L1 2-NN of many descriptor-set pairs in one launch (l1k2_batch.hip) ---------------
-// One workgroup's share of a collection: 256 q queries of one pair's query set against one slice of its database set.
+// ---- L1 2-NN of many descriptor-set pairs in one launch (l1k2_batch.hip, l1k2_guided.hip) ---------------
+// One workgroup's share of a collection: query rows of one pair's query set against one slice of its database set.
 struct L1K2BatchItem {
   int32_t pair, y0, yrows, x0, xrows;  // pair; first query row within the query set, query rows; first database row within the database set, database rows
 };
-// Everything l1k2_batch_run launches for a collection under the SPECTAVI_L1K2_Q / SPECTAVI_L1K2_BLOCKS knobs.
-struct L1K2BatchPlan {
-  int dim_pad;      // kernel row width in bytes (>= dim, zero padded)
-  int q;            // queries per lane, one value for the whole call
-  bool padded;      // pad_rows_kernel copies the whole of desc to dim_pad first
+// How l1k2_slice_plan cuts a collection into items, in plain numbers.  `whole` being the items with whole database
+// sets, every set is cut ceil(aim / whole) ways into slices of whole 64-row tiles, none (but a set's last) shorter
+// than floor_few rows while whole < fill, than floor_full from there on, and none longer than cap.
+struct L1K2SliceRule {
+  int qrows;  // query rows per item
+  long long aim, fill, floor_few, floor_full, cap;
+};
+// The part of a plan the two L1 forms share, and all of the guided form's.
+struct L1K2SlicePlan {
   int max_slices;   // largest number of database slices of any pair
   long long total_rows, out_rows;
   std::vector<long long> out_off;    // [npairs + 1]: pair p owns out rows [out_off[p], out_off[p + 1])
   std::vector<L1K2BatchItem> items;  // the grid, longest item first
-  // workspace: byte offsets, in this order.  The out rows' pairs of 64-bit keys, the device form of `items`, the
-  // padded copy of desc (empty unless `padded`).
-  size_t off_keys, off_items, off_pad, total_bytes;
+  // workspace: byte offsets, in this order.  The out rows' pairs of 64-bit keys, the device form of `items`.
+  size_t off_keys, off_items, total_bytes;
+};
+// Of a checked collection: all of *p but the workspace offsets.  SPV_ERR_INVALID for more items than a grid takes.
+int l1k2_slice_plan(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const L1K2SliceRule &rule,
+                    L1K2SlicePlan *p);
+// The plan's items as the kernels read them into d_items (the one wait of a run: the upload has ended on return)
+// and "none" into the out rows' keys d_keys; then, after the main kernel, keys -> idx, dist and their sentinels
+// under the ProfScope name `prof`.
+int l1k2_work_upload(const L1K2SlicePlan &p, const long long *seg_off, const int32_t *pairs, void *d_items,
+                     unsigned long long *d_keys, hipStream_t stream);
+int l1k2_keys_finish(const char *prof, const unsigned long long *d_keys, long long out_rows, uint64_t *d_idx,
+                     int32_t *d_dist, hipStream_t stream);
+// Everything l1k2_batch_run launches for a collection under the SPECTAVI_L1K2_Q / SPECTAVI_L1K2_BLOCKS knobs: an
+// item is 256 q queries.  The workspace ends with the padded copy of desc (empty unless `padded`).
+struct L1K2BatchPlan : L1K2SlicePlan {
+  int dim_pad;      // kernel row width in bytes (>= dim, zero padded)
+  int q;            // queries per lane, one value for the whole call
+  bool padded;      // pad_rows_kernel copies the whole of desc to dim_pad first
+  size_t off_pad;
 };
 // SPV_ERR_INVALID (message set, *p untouched) outside the limits of include/spectavi_amd.h; host only
 int l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs, L1K2BatchPlan *p);
@@ -191,14 +213,7 @@ int l1k2_batch_run(const uint8_t *d_desc, const long long *seg_off, int nseg, in
 // ---- L1 2-NN inside a band around each query's line, many pairs (l1k2_guided.hip) -----
 // Everything l1k2_guided_run launches for a collection.  An item is 256 queries of one pair against one slice of
 // its database set.
-struct L1K2GuidedPlan {
-  int max_slices;   // largest number of database slices of any pair
-  long long total_rows, out_rows;
-  std::vector<long long> out_off;    // [npairs + 1]: pair p owns out rows [out_off[p], out_off[p + 1])
-  std::vector<L1K2BatchItem> items;  // the grid, longest item first
-  // workspace: byte offsets, in this order.  The out rows' pairs of 64-bit keys, the device form of `items`.
-  size_t off_keys, off_items, total_bytes;
-};
+using L1K2GuidedPlan = L1K2SlicePlan;
 // SPV_ERR_INVALID (message set, *p untouched) outside the limits of include/spectavi_amd.h; host only
 int l1k2_guided_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs, L1K2GuidedPlan *p);
 int l1k2_guided_run(const uint8_t *d_desc, const float *d_geom, const long long *seg_off, int nseg, int dim,
@@ -403,8 +418,6 @@ struct SiftBatchPlan {
 // sizes int32[nimg, 2] = (wid, hgt); ws_bytes = 0: as much as needed.  SPV_ERR_INVALID (message set, *p untouched)
 // for what include/spectavi_amd.h rejects; host only
 int sift_batch_plan(const int32_t *sizes, int nimg, size_t ws_bytes, SiftBatchPlan *p);
-// off[0] = 0, non-decreasing, off[nimg] < 2^31 (cap_off and seg_off); SPV_ERR_INVALID (message set) otherwise
-int sift_batch_check_offsets(const long long *off, int nimg, const char *what);
 // Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the images' records.
 int sift_batch_run(const float *d_images, const int32_t *sizes, int nimg, void *d_ws, size_t ws_bytes, float *d_table,
                    const long long *cap_off, int32_t *d_counts, hipStream_t stream);

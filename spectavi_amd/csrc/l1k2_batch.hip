@@ -25,18 +25,12 @@
 namespace spv {
 namespace {
 
-// A work item as the kernel reads it: rows of desc, the out row of its first query, and the number of its first
-// database row inside the database set.
-struct alignas(32) BatchWork {
-  uint32_t x_row0, x_rows, y_row0, y_rows, out_lo, out_hi, x_local0, unused;
-};
-
-// grid = work items; block = 256 threads = 4 waves.  Thread t owns queries q * 256 + t of the item, q = 0..Q-1.
+// grid = work items (L1K2Work, l1k2_tile.h); block = 256 threads = 4 waves.  Thread t owns queries q * 256 + t of the item, q = 0..Q-1.
 // From the query load to the end of the tile loop this is a copy of l1k2_tile_kernel's body (l1k2.hip), whose code
 // must not move with this file's: a change to either is made in both.
 template <int D4, int Q>
 __global__ __launch_bounds__(kThreads, 3) void l1k2_batch_kernel(const uint4 *__restrict__ desc,
-                                                                const BatchWork *__restrict__ work,
+                                                                const L1K2Work *__restrict__ work,
                                                                 unsigned long long *keys) {
   constexpr int V4 = D4 / 4;                                   // 16-byte vectors per row
   constexpr int TILE_V4 = kTileRows * V4;                      // vectors per tile
@@ -44,7 +38,7 @@ __global__ __launch_bounds__(kThreads, 3) void l1k2_batch_kernel(const uint4 *__
   __shared__ uint4 tile[2][TILE_V4];
 
   const int t = threadIdx.x;
-  const BatchWork w = work[blockIdx.x];
+  const L1K2Work w = work[blockIdx.x];
   const uint4 *x = desc + (size_t)w.x_row0 * V4;
   const uint4 *y = desc + (size_t)w.y_row0 * V4;
   const int row_end = (int)w.x_rows, N = (int)w.y_rows;
@@ -163,10 +157,10 @@ __global__ __launch_bounds__(kThreads, 3) void l1k2_batch_kernel(const uint4 *__
   }
 }
 
-// keys (dist<<32 | idx, or "none") -> the ABI layout, one thread per key.
-__global__ __launch_bounds__(kThreads) void l1k2_batch_finish_kernel(const uint64_t *__restrict__ keys, size_t nkeys,
-                                                                     uint64_t *__restrict__ out_idx,
-                                                                     int32_t *__restrict__ out_dist) {
+// keys (dist<<32 | idx, or "none") -> the ABI layout, one thread per key: of this file's run and l1k2_guided.hip's.
+__global__ __launch_bounds__(kThreads) void l1k2_finish_kernel(const uint64_t *__restrict__ keys, size_t nkeys,
+                                                               uint64_t *__restrict__ out_idx,
+                                                               int32_t *__restrict__ out_dist) {
   for (size_t e = blockIdx.x * (size_t)kThreads + threadIdx.x; e < nkeys; e += (size_t)gridDim.x * kThreads) {
     const uint64_t k = keys[e];
     const bool none = k == kKey64None;
@@ -177,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void l1k2_batch_finish_kernel(const uint6
 
 struct BatchOperands {
   const uint4 *desc;
-  const BatchWork *work;
+  const L1K2Work *work;
   unsigned long long *keys;
   unsigned grid;
   hipStream_t stream;
@@ -205,23 +199,83 @@ constexpr int kBatchMaxSlice = 65536;  // 16-bit local index
 
 }  // namespace
 
+int l1k2_slice_plan(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const L1K2SliceRule &rule,
+                    L1K2SlicePlan *p) {
+  auto rows = [&](int s) { return seg_off[s + 1] - seg_off[s]; };
+  auto qblocks = [&](long long n) { return (n + rule.qrows - 1) / rule.qrows; };
+  p->total_rows = seg_off[nseg];
+  p->out_off = pair_out_off(seg_off, pairs, npairs);
+  p->out_rows = p->out_off[npairs];
+
+  // items with whole database sets; every set is then cut `cut` ways, no finer than the rule's floor
+  long long whole = 0;
+  for (int i = 0; i < npairs; ++i) whole += qblocks(rows(pairs[2 * i]));
+  const long long cut = whole > 0 ? std::max<long long>(1, (rule.aim + whole - 1) / whole) : 1;
+  const long long floor_rows = whole < rule.fill ? rule.floor_few : rule.floor_full;
+  auto slice_rows = [&](long long m) {
+    const long long r = ((m + cut - 1) / cut + kTileRows - 1) / kTileRows * kTileRows;
+    return std::min(std::max(r, floor_rows), rule.cap);
+  };
+  long long count = 0;
+  p->max_slices = 0;
+  for (int i = 0; i < npairs; ++i) {
+    const long long m = rows(pairs[2 * i + 1]), r = slice_rows(m);
+    const long long slices = std::max<long long>(1, (m + r - 1) / r);
+    count += qblocks(rows(pairs[2 * i])) * slices;
+    if (rows(pairs[2 * i]) > 0) p->max_slices = (int)std::max<long long>(p->max_slices, slices);
+  }
+  if (count > 0x7FFFFFFFll) return set_error(SPV_ERR_INVALID, "%lld work items, more than a grid takes", count);
+  p->items.clear();
+  p->items.reserve((size_t)count);
+  for (int i = 0; i < npairs; ++i) {
+    const long long n = rows(pairs[2 * i]), m = rows(pairs[2 * i + 1]), r = slice_rows(m);
+    for (long long y0 = 0; y0 < n; y0 += rule.qrows)
+      for (long long x0 = 0; x0 == 0 || x0 < m; x0 += r)  // an empty database set keeps one item
+        p->items.push_back({i, (int32_t)y0, (int32_t)std::min<long long>(rule.qrows, n - y0), (int32_t)x0,
+                            (int32_t)std::min(r, m - x0)});
+  }
+  // longest first: the last round of workgroups is the short items
+  std::stable_sort(p->items.begin(), p->items.end(), [](const L1K2BatchItem &a, const L1K2BatchItem &b) {
+    return (long long)a.yrows * a.xrows > (long long)b.yrows * b.xrows;
+  });
+  return SPV_OK;
+}
+
+int l1k2_work_upload(const L1K2SlicePlan &p, const long long *seg_off, const int32_t *pairs, void *d_items,
+                     unsigned long long *d_keys, hipStream_t stream) {
+  std::vector<L1K2Work> work(p.items.size());
+  for (size_t e = 0; e < work.size(); ++e) {
+    const L1K2BatchItem &it = p.items[e];
+    const long long xs = seg_off[pairs[2 * it.pair + 1]], ys = seg_off[pairs[2 * it.pair]];
+    const unsigned long long o = (unsigned long long)(p.out_off[it.pair] + it.y0);
+    work[e] = {(uint32_t)(xs + it.x0), (uint32_t)it.xrows, (uint32_t)(ys + it.y0), (uint32_t)it.yrows,
+               (uint32_t)o,            (uint32_t)(o >> 32), (uint32_t)it.x0,        0u};
+  }
+  // the one wait of the call: `work` is gone when it returns, so its upload must have ended
+  SPV_HIP_CHECK(hipMemcpyWithStream(d_items, work.data(), work.size() * sizeof(L1K2Work), hipMemcpyHostToDevice, stream));
+  SPV_HIP_CHECK(hipMemsetAsync(d_keys, 0xFF, (size_t)p.out_rows * 2 * sizeof(uint64_t), stream));  // kKey64None
+  return SPV_OK;
+}
+
+int l1k2_keys_finish(const char *prof, const unsigned long long *d_keys, long long out_rows, uint64_t *d_idx,
+                     int32_t *d_dist, hipStream_t stream) {
+  ProfScope prof_merge(prof, stream);
+  const size_t nkeys = (size_t)out_rows * 2;
+  hipLaunchKernelGGL(l1k2_finish_kernel, dim3((unsigned)std::min<size_t>((nkeys + kThreads - 1) / kThreads, 1u << 20)),
+                     dim3(kThreads), 0, stream, reinterpret_cast<const uint64_t *>(d_keys), nkeys, d_idx, d_dist);
+  SPV_HIP_CHECK(hipGetLastError());
+  return SPV_OK;
+}
+
 int l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs, L1K2BatchPlan *out) {
-  if (nseg < 0 || npairs < 0) return set_error(SPV_ERR_INVALID, "negative count (nseg=%d, npairs=%d)", nseg, npairs);
   if (dim <= 0 || dim % 16 != 0)
     return set_error(SPV_ERR_INVALID, "Input matrix inner dimensions must be 16-byte aligned (dim=%d).", dim);
   L1K2BatchPlan p{};
   p.dim_pad = first_at_least(TileWidths{}, dim);
   if (p.dim_pad == 0)
     return set_error(SPV_ERR_INVALID, "dim=%d > 256 is not supported by the many-pairs form of the L1 2-NN", dim);
-  if ((nseg > 0 && !seg_off) || (npairs > 0 && !pairs)) return set_error(SPV_ERR_INVALID, "null pointer");
-  if (seg_off && seg_off[0] != 0) return set_error(SPV_ERR_INVALID, "seg_off[0] = %lld, must be 0", seg_off[0]);
-  for (int s = 0; s < nseg; ++s)
-    if (seg_off[s + 1] < seg_off[s]) return set_error(SPV_ERR_INVALID, "seg_off decreases at set %d", s);
-  p.total_rows = nseg > 0 ? seg_off[nseg] : 0;
-  if (p.total_rows >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld rows in all, must be below 2^31", p.total_rows);
-  for (int i = 0; i < 2 * npairs; ++i)
-    if (pairs[i] < 0 || pairs[i] >= nseg)
-      return set_error(SPV_ERR_INVALID, "pair %d names set %d of %d", i / 2, (int)pairs[i], nseg);
+  if (!seg_off && nseg == 0) seg_off = kNoSets;  // no sets: seg_off may be null
+  SPV_TRY(check_collection(seg_off, nseg, pairs, npairs));
   p.padded = p.dim_pad != dim;
   auto rows = [&](int s) { return seg_off[s + 1] - seg_off[s]; };
   auto qblocks = [&](long long n, int q) { return (n + kThreads * q - 1) / (kThreads * q); };
@@ -239,44 +293,13 @@ int l1k2_batch_plan(const long long *seg_off, int nseg, int dim, const int32_t *
   if (knobs.q == 1 || knobs.q == 2 || knobs.q == 4) q = std::min(knobs.q, max_q_for(p.dim_pad));
   p.q = q;
 
-  // items with whole database sets; every set is then cut `cut` ways, no finer than the floor described above
-  long long whole = 0;
-  p.out_off.assign((size_t)npairs + 1, 0);
-  for (int i = 0; i < npairs; ++i) {
-    whole += qblocks(rows(pairs[2 * i]), q);
-    p.out_off[i + 1] = p.out_off[i] + rows(pairs[2 * i]);
-  }
-  p.out_rows = p.out_off[npairs];
-  const long long cut = whole > 0 ? std::max<long long>(1, (knobs.blocks + whole - 1) / whole) : 1;
-  const long long floor_rows = whole < kBatchFill ? kTileRows : kBatchTailRows;
-  auto slice_rows = [&](long long m) {
-    long long r = ((m + cut - 1) / cut + kTileRows - 1) / kTileRows * kTileRows;
-    return std::min<long long>(std::max(r, floor_rows), kBatchMaxSlice);
-  };
-  long long count = 0;
-  for (int i = 0; i < npairs; ++i) {
-    const long long m = rows(pairs[2 * i + 1]), r = slice_rows(m);
-    const long long slices = std::max<long long>(1, (m + r - 1) / r);
-    count += qblocks(rows(pairs[2 * i]), q) * slices;
-    if (rows(pairs[2 * i]) > 0) p.max_slices = (int)std::max<long long>(p.max_slices, slices);
-  }
-  if (count > 0x7FFFFFFFll) return set_error(SPV_ERR_INVALID, "%lld work items, more than a grid takes", count);
-  p.items.reserve((size_t)count);
-  for (int i = 0; i < npairs; ++i) {
-    const long long n = rows(pairs[2 * i]), m = rows(pairs[2 * i + 1]), r = slice_rows(m);
-    for (long long y0 = 0; y0 < n; y0 += kThreads * q)
-      for (long long x0 = 0; x0 == 0 || x0 < m; x0 += r)  // an empty database set keeps one item
-        p.items.push_back({i, (int32_t)y0, (int32_t)std::min<long long>(kThreads * q, n - y0), (int32_t)x0,
-                           (int32_t)std::min(r, m - x0)});
-  }
-  // longest first: the last round of workgroups is the short items
-  std::stable_sort(p.items.begin(), p.items.end(), [](const L1K2BatchItem &a, const L1K2BatchItem &b) {
-    return (long long)a.yrows * a.xrows > (long long)b.yrows * b.xrows;
-  });
+  // 256 q queries per item; sets cut SPECTAVI_L1K2_BLOCKS / whole ways, no finer than the floor described above
+  SPV_TRY(l1k2_slice_plan(seg_off, nseg, pairs, npairs,
+                          {kThreads * q, knobs.blocks, kBatchFill, kTileRows, kBatchTailRows, kBatchMaxSlice}, &p));
 
   WsWalk w;
   p.off_keys = w.reserve((size_t)p.out_rows * 2 * sizeof(uint64_t));
-  p.off_items = w.reserve(p.items.size() * sizeof(BatchWork));
+  p.off_items = w.reserve(p.items.size() * sizeof(L1K2Work));
   p.off_pad = w.reserve(p.padded ? (size_t)p.total_rows * p.dim_pad : 0);
   p.total_bytes = w.end();
   *out = std::move(p);
@@ -295,40 +318,23 @@ int l1k2_batch_run(const uint8_t *d_desc, const long long *seg_off, int nseg, in
     return set_error(SPV_ERR_INVALID, "output pointers must be aligned to their element size");
   if (ws_bytes < p.total_bytes) return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, p.total_bytes);
 
-  std::vector<BatchWork> work(p.items.size());
-  for (size_t e = 0; e < work.size(); ++e) {
-    const L1K2BatchItem &it = p.items[e];
-    const long long xs = seg_off[pairs[2 * it.pair + 1]], ys = seg_off[pairs[2 * it.pair]];
-    const unsigned long long o = (unsigned long long)(p.out_off[it.pair] + it.y0);
-    work[e] = {(uint32_t)(xs + it.x0), (uint32_t)it.xrows, (uint32_t)(ys + it.y0), (uint32_t)it.yrows,
-               (uint32_t)o,            (uint32_t)(o >> 32), (uint32_t)it.x0,        0u};
-  }
   uint8_t *ws = static_cast<uint8_t *>(d_ws);
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + p.off_keys);
-  // the one wait of the call: `work` is gone when it returns, so its upload must have ended
-  SPV_HIP_CHECK(hipMemcpyWithStream(ws + p.off_items, work.data(), work.size() * sizeof(BatchWork), hipMemcpyHostToDevice,
-                                    stream));
-  SPV_HIP_CHECK(hipMemsetAsync(keys, 0xFF, (size_t)p.out_rows * 2 * sizeof(uint64_t), stream));  // kKey64None
+  SPV_TRY(l1k2_work_upload(p, seg_off, pairs, ws + p.off_items, keys, stream));
   const uint8_t *kdesc = d_desc;
   if (p.padded) {
     l1k2_pad_rows(d_desc, ws + p.off_pad, (size_t)p.total_rows, dim, p.dim_pad, stream);
     kdesc = ws + p.off_pad;
   }
-  const BatchOperands o{reinterpret_cast<const uint4 *>(kdesc), reinterpret_cast<const BatchWork *>(ws + p.off_items), keys,
-                        (unsigned)work.size(), stream};
+  const BatchOperands o{reinterpret_cast<const uint4 *>(kdesc), reinterpret_cast<const L1K2Work *>(ws + p.off_items), keys,
+                        (unsigned)p.items.size(), stream};
   {
     ProfScope prof("l1k2_batch", stream);
     if (!pick(TileWidths{}, p.dim_pad, [&](auto W) { return launch_batch_q<decltype(W)::value / 4>(o, p.q); }))
       return set_error(SPV_ERR_INVALID, "internal: no kernel for dim_pad %d, q %d", p.dim_pad, p.q);
   }
   SPV_HIP_CHECK(hipGetLastError());
-
-  ProfScope prof_merge("l1k2_batch_merge", stream);
-  const size_t nkeys = (size_t)p.out_rows * 2;
-  hipLaunchKernelGGL(l1k2_batch_finish_kernel, dim3((unsigned)std::min<size_t>((nkeys + kThreads - 1) / kThreads, 1u << 20)),
-                     dim3(kThreads), 0, stream, reinterpret_cast<const uint64_t *>(keys), nkeys, d_idx, d_dist);
-  SPV_HIP_CHECK(hipGetLastError());
-  return SPV_OK;
+  return l1k2_keys_finish("l1k2_batch_merge", keys, p.out_rows, d_idx, d_dist, stream);
 }
 
 }  // namespace spv

@@ -45,12 +45,6 @@ constexpr int kQueue = 128;    // < 64 queued, then <= 64 appended in one round
 constexpr int kOctetMax = 16;  // most entries the end-of-tile drain takes eight lanes per pair for
 static_assert(kTileRows == 1 << kRowBits && kTileRows % 8 == 0, "a queue entry holds a tile row in kRowBits bits");
 
-// A work item as the kernel reads it: BatchWork of l1k2_batch.hip.  Rows of desc / geom, the out row of the first
-// query, and the number of the first database row inside the database set.
-struct alignas(32) GuidedWork {
-  uint32_t x_row0, x_rows, y_row0, y_rows, out_lo, out_hi, x_local0, unused;
-};
-
 // LDS accesses of one wave are executed in order; this keeps the compiler from moving them
 __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -131,7 +125,7 @@ __device__ __forceinline__ void drain_octets(int n, int &cnt, int lane, const ui
 // slots and the queue of queries 64 w .. 64 w + 63, so nothing but the tiles is shared between waves.
 __global__ __launch_bounds__(kThreads, 2) void l1k2_guided_kernel(const uint4 *__restrict__ desc,
                                                                  const float4 *__restrict__ geom,
-                                                                 const GuidedWork *__restrict__ work,
+                                                                 const L1K2Work *__restrict__ work,
                                                                  const double *__restrict__ lines, double max_dist,
                                                                  unsigned long long *keys, int *ncand) {
   constexpr int TILE_V4 = kTileRows * kRowV4;
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_guided_kernel(const uint4 *_
   __shared__ uint16_t s_queue[kWaves][kQueue];
 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const GuidedWork w = work[blockIdx.x];
+  const L1K2Work w = work[blockIdx.x];
   const uint4 *x = desc + (size_t)w.x_row0 * kRowV4;
   const float4 *xg = geom + w.x_row0;
   const int row_end = (int)w.x_rows, N = (int)w.y_rows;
@@ -263,18 +257,6 @@ __global__ __launch_bounds__(kThreads, 2) void l1k2_guided_kernel(const uint4 *_
   }
 }
 
-// keys (dist<<32 | idx, or "none") -> the ABI layout, one thread per key: l1k2_batch_finish_kernel's body.
-__global__ __launch_bounds__(kThreads) void l1k2_guided_finish_kernel(const uint64_t *__restrict__ keys, size_t nkeys,
-                                                                      uint64_t *__restrict__ out_idx,
-                                                                      int32_t *__restrict__ out_dist) {
-  for (size_t e = blockIdx.x * (size_t)kThreads + threadIdx.x; e < nkeys; e += (size_t)gridDim.x * kThreads) {
-    const uint64_t k = keys[e];
-    const bool none = k == kKey64None;
-    out_idx[e] = none ? ~0ull : (k & 0xFFFFFFFFull);
-    out_dist[e] = none ? 0x7FFFFFFF : (int32_t)(k >> 32);
-  }
-}
-
 // ---- lines: out row r of a pair, query keypoint (u, v), gets G (u, v, 1)^T over hypot(l0, l1), or three NaNs.
 // A launch takes the pairs of one chunk by value; blockIdx.y is the pair of the chunk.
 struct LinesPair {
@@ -313,71 +295,21 @@ __global__ __launch_bounds__(kThreads) void epipolar_lines_kernel(const float4 *
 constexpr long long kGuidedFill = 512;
 constexpr int kGuidedMinSlice = 256;
 
-// The rules on seg_off and pairs are l1k2_batch_plan's.
-int check_collection(const long long *seg_off, int nseg, const int32_t *pairs, int npairs) {
-  if (nseg < 0 || npairs < 0) return set_error(SPV_ERR_INVALID, "negative count (nseg=%d, npairs=%d)", nseg, npairs);
-  if (!seg_off || (npairs > 0 && !pairs)) return set_error(SPV_ERR_INVALID, "null pointer");
-  if (seg_off[0] != 0) return set_error(SPV_ERR_INVALID, "seg_off[0] = %lld, must be 0", seg_off[0]);
-  for (int s = 0; s < nseg; ++s)
-    if (seg_off[s + 1] < seg_off[s]) return set_error(SPV_ERR_INVALID, "seg_off decreases at set %d", s);
-  if (seg_off[nseg] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld rows in all, must be below 2^31", seg_off[nseg]);
-  for (int i = 0; i < 2 * npairs; ++i)
-    if (pairs[i] < 0 || pairs[i] >= nseg)
-      return set_error(SPV_ERR_INVALID, "pair %d names set %d of %d", i / 2, (int)pairs[i], nseg);
-  return SPV_OK;
-}
-
 }  // namespace
 
 int l1k2_guided_plan(const long long *seg_off, int nseg, int dim, const int32_t *pairs, int npairs, L1K2GuidedPlan *out) {
   if (dim != 128) return set_error(SPV_ERR_INVALID, "the guided L1 2-NN takes dim 128 only (dim=%d)", dim);
-  if (nseg == 0 && npairs == 0 && !seg_off) {  // nothing at all
-    *out = L1K2GuidedPlan{};
-    out->out_off.assign(1, 0);
-    return SPV_OK;
-  }
+  if (!seg_off && nseg == 0 && npairs == 0) seg_off = kNoSets;  // nothing at all: seg_off may be null
   SPV_TRY(check_collection(seg_off, nseg, pairs, npairs));
   L1K2GuidedPlan p{};
-  p.total_rows = seg_off[nseg];
-  auto rows = [&](int s) { return seg_off[s + 1] - seg_off[s]; };
-  auto qblocks = [&](long long n) { return (n + kThreads - 1) / kThreads; };
-
-  long long whole = 0;
-  p.out_off.assign((size_t)npairs + 1, 0);
-  for (int i = 0; i < npairs; ++i) {
-    whole += qblocks(rows(pairs[2 * i]));
-    p.out_off[i + 1] = p.out_off[i] + rows(pairs[2 * i]);
-  }
-  p.out_rows = p.out_off[npairs];
-  const long long cut = whole > 0 ? std::max<long long>(1, (kGuidedFill + whole - 1) / whole) : 1;
-  auto slice_rows = [&](long long m) {
-    const long long r = ((m + cut - 1) / cut + kTileRows - 1) / kTileRows * kTileRows;
-    return std::max<long long>(r, kGuidedMinSlice);
-  };
-  long long count = 0;
-  for (int i = 0; i < npairs; ++i) {
-    const long long m = rows(pairs[2 * i + 1]), r = slice_rows(m);
-    const long long slices = std::max<long long>(1, (m + r - 1) / r);
-    count += qblocks(rows(pairs[2 * i])) * slices;
-    if (rows(pairs[2 * i]) > 0) p.max_slices = (int)std::max<long long>(p.max_slices, slices);
-  }
-  if (count > 0x7FFFFFFFll) return set_error(SPV_ERR_INVALID, "%lld work items, more than a grid takes", count);
-  p.items.reserve((size_t)count);
-  for (int i = 0; i < npairs; ++i) {
-    const long long n = rows(pairs[2 * i]), m = rows(pairs[2 * i + 1]), r = slice_rows(m);
-    for (long long y0 = 0; y0 < n; y0 += kThreads)
-      for (long long x0 = 0; x0 == 0 || x0 < m; x0 += r)  // an empty database set keeps one item
-        p.items.push_back({i, (int32_t)y0, (int32_t)std::min<long long>(kThreads, n - y0), (int32_t)x0,
-                           (int32_t)std::min(r, m - x0)});
-  }
-  // longest first: the last round of workgroups is the short items
-  std::stable_sort(p.items.begin(), p.items.end(), [](const L1K2BatchItem &a, const L1K2BatchItem &b) {
-    return (long long)a.yrows * a.xrows > (long long)b.yrows * b.xrows;
-  });
+  // 256 queries per item; one floor whatever the item count; no cap, the row number in a key being 32 bits wide
+  SPV_TRY(l1k2_slice_plan(seg_off, nseg, pairs, npairs,
+                          {kThreads, kGuidedFill, 0, kGuidedMinSlice, kGuidedMinSlice, std::numeric_limits<long long>::max()},
+                          &p));
 
   WsWalk w;
   p.off_keys = w.reserve((size_t)p.out_rows * 2 * sizeof(uint64_t));
-  p.off_items = w.reserve(p.items.size() * sizeof(GuidedWork));
+  p.off_items = w.reserve(p.items.size() * sizeof(L1K2Work));
   p.total_bytes = w.end();
   *out = std::move(p);
   return SPV_OK;
@@ -398,35 +330,18 @@ int l1k2_guided_run(const uint8_t *d_desc, const float *d_geom, const long long 
     return set_error(SPV_ERR_INVALID, "lines and output pointers must be aligned to their element size");
   if (ws_bytes < p.total_bytes) return set_error(SPV_ERR_INVALID, "workspace too small: %zu < %zu", ws_bytes, p.total_bytes);
 
-  std::vector<GuidedWork> work(p.items.size());
-  for (size_t e = 0; e < work.size(); ++e) {
-    const L1K2BatchItem &it = p.items[e];
-    const long long xs = seg_off[pairs[2 * it.pair + 1]], ys = seg_off[pairs[2 * it.pair]];
-    const unsigned long long o = (unsigned long long)(p.out_off[it.pair] + it.y0);
-    work[e] = {(uint32_t)(xs + it.x0), (uint32_t)it.xrows, (uint32_t)(ys + it.y0), (uint32_t)it.yrows,
-               (uint32_t)o,            (uint32_t)(o >> 32), (uint32_t)it.x0,        0u};
-  }
   uint8_t *ws = static_cast<uint8_t *>(d_ws);
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + p.off_keys);
-  // the one wait of the call: `work` is gone when it returns, so its upload must have ended
-  SPV_HIP_CHECK(hipMemcpyWithStream(ws + p.off_items, work.data(), work.size() * sizeof(GuidedWork), hipMemcpyHostToDevice,
-                                    stream));
-  SPV_HIP_CHECK(hipMemsetAsync(keys, 0xFF, (size_t)p.out_rows * 2 * sizeof(uint64_t), stream));  // kKey64None
+  SPV_TRY(l1k2_work_upload(p, seg_off, pairs, ws + p.off_items, keys, stream));
   if (d_ncand) SPV_HIP_CHECK(hipMemsetAsync(d_ncand, 0, (size_t)p.out_rows * sizeof(int32_t), stream));
   {
     ProfScope prof("l1k2_guided", stream);
-    hipLaunchKernelGGL(l1k2_guided_kernel, dim3((unsigned)work.size()), dim3(kThreads), 0, stream,
+    hipLaunchKernelGGL(l1k2_guided_kernel, dim3((unsigned)p.items.size()), dim3(kThreads), 0, stream,
                        reinterpret_cast<const uint4 *>(d_desc), reinterpret_cast<const float4 *>(d_geom),
-                       reinterpret_cast<const GuidedWork *>(ws + p.off_items), d_lines, max_dist, keys, d_ncand);
+                       reinterpret_cast<const L1K2Work *>(ws + p.off_items), d_lines, max_dist, keys, d_ncand);
   }
   SPV_HIP_CHECK(hipGetLastError());
-
-  ProfScope prof_merge("l1k2_guided_merge", stream);
-  const size_t nkeys = (size_t)p.out_rows * 2;
-  hipLaunchKernelGGL(l1k2_guided_finish_kernel, dim3((unsigned)std::min<size_t>((nkeys + kThreads - 1) / kThreads, 1u << 20)),
-                     dim3(kThreads), 0, stream, reinterpret_cast<const uint64_t *>(keys), nkeys, d_idx, d_dist);
-  SPV_HIP_CHECK(hipGetLastError());
-  return SPV_OK;
+  return l1k2_keys_finish("l1k2_guided_merge", keys, p.out_rows, d_idx, d_dist, stream);
 }
 
 int epipolar_lines_run(const float *d_geom, const long long *seg_off, int nseg, const int32_t *pairs, int npairs,

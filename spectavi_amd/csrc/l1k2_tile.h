@@ -1,6 +1,7 @@
 // l1k2_tile.h -- the inline pieces of the L1 2-NN tile kernels that l1k2.hip and l1k2_batch.hip share: the packed
 // 32-bit key, its SAD chain, the lazy top-2, the 64-bit key of the partial results and the two-minimum protocol
-// on a pair of them in memory.  The design they serve is described at the top of l1k2.hip.
+// on a pair of them in memory; and the work record of l1k2_batch.hip and l1k2_guided.hip.  The design they serve is
+// described at the top of l1k2.hip.
 #pragma once
 
 #include "common.h"
@@ -12,6 +13,12 @@ constexpr int kThreads = 256;
 constexpr int kTileRows = 64;               // database rows per LDS tile
 constexpr uint32_t kKeyNone = 0xFFFFFFFFu;  // > any real key (dist <= 65280)
 constexpr uint64_t kKey64None = ~0ull;
+
+// A work item of the many-pairs forms as their kernels read it (l1k2_work_upload packs it): rows of desc (and geom),
+// the out row of its first query, and the number of its first database row inside the database set.
+struct alignas(32) L1K2Work {
+  uint32_t x_row0, x_rows, y_row0, y_rows, out_lo, out_hi, x_local0, unused;
+};
 
 __device__ __forceinline__ uint32_t sad_hi(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_sad_hi_u8(a, b, c);  // (SAD_U8(a,b) << 16) + c

@@ -254,7 +254,7 @@ int normalize_batch_plan(const long long *seg_off, int nseg, int dim, int dtype,
   // the finish kernel's grid is (sets, 16-column blocks) in one dimension; empty sets count, their workgroups leave at once
   if ((size_t)nseg * ((dim + kStatCols - 1) / kStatCols) > 0x7FFFFFFFull)
     return set_error(SPV_ERR_INVALID, "%d sets of %d columns, more than a grid takes", nseg, dim);
-  SPV_TRY(sift_batch_check_offsets(seg_off, nseg, "seg_off"));  // the rules of l1k2_batch_plan
+  SPV_TRY(check_offsets(seg_off, nseg, "seg_off"));
   NormalizeBatchPlan p;
   p.total_rows = seg_off[nseg];
   for (int s = 0; s < nseg; ++s) {

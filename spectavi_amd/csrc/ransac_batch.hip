@@ -406,13 +406,9 @@ void ransac_batch_first_round(const long long *pair_off, int npairs, int max_tri
 int ransac_batch_check(const long long *pair_off, int npairs, int max_tries, const int32_t *samples) {
   if (npairs < 0) return set_error(SPV_ERR_INVALID, "negative set count");
   if (npairs > (1 << 20)) return set_error(SPV_ERR_INVALID, "more than 2^20 sets per call");
-  if (!pair_off) return set_error(SPV_ERR_INVALID, "null pair_off");
   if (max_tries < 0) return set_error(SPV_ERR_INVALID, "negative maximum_tries");
   if (max_tries > 700000000) return set_error(SPV_ERR_INVALID, "maximum_tries above 7e8 (candidate ids are 32-bit: 3 per try)");
-  if (pair_off[0] != 0) return set_error(SPV_ERR_INVALID, "pair_off must start at 0");
-  for (int p = 0; p < npairs; ++p)
-    if (pair_off[p + 1] < pair_off[p]) return set_error(SPV_ERR_INVALID, "pair_off decreases at set %d", p);
-  if (pair_off[npairs] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "the sets must hold fewer than 2^31 rows in all");
+  SPV_TRY(check_offsets(pair_off, npairs, "pair_off"));
   if (!samples) return SPV_OK;
   for (int p = 0; p < npairs; ++p) {
     const long long npt = pair_off[p + 1] - pair_off[p];

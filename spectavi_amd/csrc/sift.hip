@@ -1043,15 +1043,6 @@ int sift_batch_plan(const int32_t *sizes, int nimg, size_t ws_bytes, SiftBatchPl
   return SPV_OK;
 }
 
-int sift_batch_check_offsets(const long long *off, int nimg, const char *what) {
-  if (!off) return set_error(SPV_ERR_INVALID, "null %s", what);
-  if (off[0] != 0) return set_error(SPV_ERR_INVALID, "%s must start at 0", what);
-  for (int i = 0; i < nimg; ++i)
-    if (off[i + 1] < off[i]) return set_error(SPV_ERR_INVALID, "%s decreases at %d", what, i);
-  if (off[nimg] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%s ends at %lld rows: must be below 2^31", what, off[nimg]);
-  return SPV_OK;
-}
-
 namespace {
 
 constexpr int kPersistFloor = 32, kKeyFloor = 128;  // the least share of the persistent grids an image of a large group gets
@@ -1136,7 +1127,7 @@ int sift_batch_run(const float *d_images, const int32_t *sizes, int nimg, void *
                    const long long *cap_off, int32_t *d_counts, hipStream_t st) {
   SiftBatchPlan plan;
   SPV_TRY(sift_batch_plan(sizes, nimg, ws_bytes, &plan));
-  SPV_TRY(sift_batch_check_offsets(cap_off, nimg, "cap_off"));
+  SPV_TRY(check_offsets(cap_off, nimg, "cap_off"));
   if (nimg == 0) return SPV_OK;
   if (!d_images || !d_ws || !d_counts || (cap_off[nimg] > 0 && !d_table)) return set_error(SPV_ERR_INVALID, "null pointer");
   if (ws_bytes < plan.min_bytes)
@@ -1188,8 +1179,8 @@ int sift_batch_run(const float *d_images, const int32_t *sizes, int nimg, void *
 int sift_batch_pack_run(const float *d_table, const long long *cap_off, const long long *seg_off, int nimg,
                         float *d_packed, float *d_geom, uint8_t *d_desc, hipStream_t st) {
   if (nimg < 0) return set_error(SPV_ERR_INVALID, "negative image count");
-  SPV_TRY(sift_batch_check_offsets(cap_off, nimg, "cap_off"));
-  SPV_TRY(sift_batch_check_offsets(seg_off, nimg, "seg_off"));
+  SPV_TRY(check_offsets(cap_off, nimg, "cap_off"));
+  SPV_TRY(check_offsets(seg_off, nimg, "seg_off"));
   for (int i = 0; i < nimg; ++i)
     if (seg_off[i + 1] - seg_off[i] > cap_off[i + 1] - cap_off[i])
       return set_error(SPV_ERR_INVALID, "segment %d: %lld rows, its region holds %lld", i, seg_off[i + 1] - seg_off[i],

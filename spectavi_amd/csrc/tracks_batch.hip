@@ -343,26 +343,8 @@ TracksLayout tracks_layout(void *base, long long n) {
   return l;
 }
 
-// The per-pair table lives with the calling thread between calls, as gather_match_coords_batch_run's does: a
-// grow-only device buffer and the event of the launch that read it last.
-struct TracksTable {
-  void *p = nullptr;
-  size_t cap = 0;
-  int dev = -1;
-  hipEvent_t ev = nullptr;
-  void drop() {
-    if (ev) {
-      (void)hipEventSynchronize(ev);
-      (void)hipEventDestroy(ev);
-      ev = nullptr;
-    }
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  ~TracksTable() { drop(); }
-};
-thread_local TracksTable g_tracks_table;
+// The per-pair table (pair_table, collection.h) lives with the calling thread between calls.
+thread_local DeviceTable g_tracks_table;
 
 unsigned grid_of(long long threads, int per) { return (unsigned)std::max<long long>(1, (threads + per - 1) / per); }
 
@@ -378,21 +360,9 @@ long long tracks_batch_member_bound(long long total_rows, int capacity, int accu
 }
 
 int tracks_batch_check(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, int capacity, int min_len) {
-  if (nseg < 0 || npairs < 0) return set_error(SPV_ERR_INVALID, "negative count (nseg=%d, npairs=%d)", nseg, npairs);
   if (capacity < 0) return set_error(SPV_ERR_INVALID, "negative capacity");
   if (min_len < 2) return set_error(SPV_ERR_INVALID, "min_len = %d, a track has at least 2 members", min_len);
-  if (!seg_off || (npairs > 0 && !pairs)) return set_error(SPV_ERR_INVALID, "null pointer");
-  if (seg_off[0] != 0) return set_error(SPV_ERR_INVALID, "seg_off[0] = %lld, must be 0", seg_off[0]);
-  for (int s = 0; s < nseg; ++s)
-    if (seg_off[s + 1] < seg_off[s]) return set_error(SPV_ERR_INVALID, "seg_off decreases at set %d", s);
-  if (seg_off[nseg] >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld rows in all, must be below 2^31", seg_off[nseg]);
-  long long out_rows = 0;
-  for (int i = 0; i < 2 * npairs; ++i) {
-    if (pairs[i] < 0 || pairs[i] >= nseg) return set_error(SPV_ERR_INVALID, "pair %d names set %d of %d", i / 2, (int)pairs[i], nseg);
-    if (i % 2 == 0) out_rows += seg_off[pairs[i] + 1] - seg_off[pairs[i]];
-  }
-  if (out_rows >= (1ll << 31)) return set_error(SPV_ERR_INVALID, "%lld out rows, must be below 2^31", out_rows);
-  return SPV_OK;
+  return check_collection_out32(seg_off, nseg, pairs, npairs);
 }
 
 int tracks_batch_run(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const int32_t *d_matches,
@@ -417,29 +387,9 @@ int tracks_batch_run(const long long *seg_off, int nseg, const int32_t *pairs, i
   if (!d_ws || ws_bytes < l.bytes) return set_error(SPV_ERR_INVALID, "workspace too small");
   if (reinterpret_cast<uintptr_t>(d_ws) & 15) return set_error(SPV_ERR_INVALID, "workspace must be aligned to 16 bytes");
 
-  std::vector<long long> tab((size_t)4 * npairs + 1 + nseg + 1, 0);
-  for (int p = 0; p < npairs; ++p) {
-    const int q = pairs[2 * p], d = pairs[2 * p + 1];
-    tab[(size_t)p + 1] = tab[p] + (seg_off[q + 1] - seg_off[q]);
-    tab[(size_t)npairs + 1 + p] = seg_off[q];
-    tab[(size_t)2 * npairs + 1 + p] = seg_off[d];
-    tab[(size_t)3 * npairs + 1 + p] = seg_off[d + 1] - seg_off[d];
-  }
-  std::copy(seg_off, seg_off + nseg + 1, tab.begin() + (size_t)4 * npairs + 1);
-  TracksTable &tt = g_tracks_table;
-  const size_t bytes = tab.size() * sizeof(long long);
-  int dev = 0;
-  SPV_HIP_CHECK(hipGetDevice(&dev));
-  if (tt.ev) SPV_HIP_CHECK(hipEventSynchronize(tt.ev));  // the launch that read the table last
-  if (tt.dev != dev || tt.cap < bytes) {
-    tt.drop();
-    SPV_HIP_CHECK(hipMalloc(&tt.p, bytes));
-    tt.cap = bytes;
-    tt.dev = dev;
-  }
-  if (!tt.ev) SPV_HIP_CHECK(hipEventCreateWithFlags(&tt.ev, hipEventDisableTiming));
-  // (pageable source: the copy has left `tab` when the call returns)
-  SPV_HIP_CHECK(hipMemcpyAsync(tt.p, tab.data(), bytes, hipMemcpyHostToDevice, stream));
+  const std::vector<long long> tab = pair_table(seg_off, nseg, pairs, npairs);
+  DeviceTable &tt = g_tracks_table;
+  SPV_TRY(tt.upload(tab.data(), tab.size() * sizeof(long long), stream));
   const long long *dt = static_cast<const long long *>(tt.p);
   TracksTab t;
   t.out_off = dt;
@@ -502,8 +452,7 @@ int tracks_batch_run(const long long *seg_off, int nseg, const int32_t *pairs, i
                        d_members, d_flags);
   }
   SPV_HIP_CHECK(hipGetLastError());
-  SPV_HIP_CHECK(hipEventRecord(tt.ev, stream));
-  return SPV_OK;
+  return tt.record(stream);
 }
 
 }  // namespace spv

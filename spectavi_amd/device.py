@@ -259,16 +259,35 @@ def l1k2_plan(xrows, yrows, dim):
     return dict(dim_pad=out[0], q=out[1], slices=out[2], slice_rows=out[3], wide=bool(out[4]))
 
 
-def _batch_args(seg_off, pairs, total_rows, dim):
-    """seg_off -> int64[nseg + 1], pairs -> int32[npairs, 2], out_off int64[npairs + 1]; ValueError for anything
-    spv_l1k2_batch_device would reject or that does not describe a table of total_rows rows."""
+def _seg_offsets(seg_off, total_rows, name):
+    """seg_off -> int64[nseg + 1]; ValueError for what check_offsets (collection.h) would reject or that does not
+    describe a table `name` of total_rows rows (None: any)."""
     seg = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
     if seg.size < 1 or seg[0] != 0 or np.any(np.diff(seg) < 0):
         raise ValueError("seg_off must start at 0 and never decrease")
     if total_rows is not None and int(seg[-1]) != int(total_rows):
-        raise ValueError("seg_off ends at %d, desc has %d rows" % (int(seg[-1]), int(total_rows)))
+        raise ValueError("seg_off ends at %d, %s has %d rows" % (int(seg[-1]), name, int(total_rows)))
     if int(seg[-1]) >= 2 ** 31:
         raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    return seg
+
+
+def _plan_items(fn, args, n_out, cols, want_items, at=0, tail=()):
+    """The two calls of a plan entry fn(*args, out[n_out], *tail, items, items_cap): out as ints and, with
+    want_items, the out[at] items as int32[items, cols] (else None)."""
+    out = (ct.c_longlong * n_out)()
+    check(fn(*args, out, *tail, None, 0))
+    items = None
+    if want_items:
+        items = np.empty((int(out[at]), cols), np.int32)
+        check(fn(*args, out, *tail, items.ctypes.data, len(items)))
+    return [int(v) for v in out], items
+
+
+def _batch_args(seg_off, pairs, total_rows, dim):
+    """seg_off -> int64[nseg + 1], pairs -> int32[npairs, 2], out_off int64[npairs + 1]; ValueError for anything
+    spv_l1k2_batch_device would reject or that does not describe a table of total_rows rows."""
+    seg = _seg_offsets(seg_off, total_rows, "desc")
     if dim <= 0 or dim % 16 != 0:
         raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
     if dim > 256:
@@ -294,16 +313,11 @@ def l1k2_batch_plan(seg_off, pairs, dim, want_items=False):
     items themselves, int32[items, 5] = (pair, first query row within the query set, query rows, first
     database row within the database set, database rows), in launch order."""
     seg, prs, out_off = _batch_args(seg_off, pairs, None, dim)
-    out = (ct.c_longlong * 6)()
-    check(clib.spv_l1k2_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out, None, 0))
-    plan = dict(dim_pad=int(out[0]), q=int(out[1]), items=int(out[2]), out_rows=int(out[3]), max_slices=int(out[4]),
-                workspace_bytes=int(out[5]), out_off=out_off)
-    if want_items:
-        items = np.empty((plan["items"], 5), np.int32)
-        check(clib.spv_l1k2_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out,
-                                       items.ctypes.data, len(items)))
-        return plan, items
-    return plan
+    out, items = _plan_items(clib.spv_l1k2_batch_plan, (seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs)),
+                             6, 5, want_items, at=2)
+    plan = dict(dim_pad=out[0], q=out[1], items=out[2], out_rows=out[3], max_slices=out[4], workspace_bytes=out[5],
+                out_off=out_off)
+    return (plan, items) if want_items else plan
 
 
 def l1k2_batch(desc, seg_off, pairs, workspace=None):
@@ -340,16 +354,10 @@ def l1k2_guided_batch_plan(seg_off, pairs, dim=128, want_items=False):
     seg, prs, out_off = _batch_args(seg_off, pairs, None, dim)
     if dim != 128:
         raise ValueError("the guided L1 2-NN takes dim 128 only (dim=%d)" % dim)
-    out = (ct.c_longlong * 4)()
-    check(clib.spv_l1k2_guided_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out, None, 0))
-    plan = dict(items=int(out[0]), out_rows=int(out[1]), max_slices=int(out[2]), workspace_bytes=int(out[3]),
-                out_off=out_off)
-    if want_items:
-        items = np.empty((plan["items"], 5), np.int32)
-        check(clib.spv_l1k2_guided_batch_plan(seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs), out,
-                                              items.ctypes.data, len(items)))
-        return plan, items
-    return plan
+    out, items = _plan_items(clib.spv_l1k2_guided_batch_plan,
+                             (seg.ctypes.data, seg.size - 1, dim, prs.ctypes.data, len(prs)), 4, 5, want_items)
+    plan = dict(items=out[0], out_rows=out[1], max_slices=out[2], workspace_bytes=out[3], out_off=out_off)
+    return (plan, items) if want_items else plan
 
 
 def _need_geom(geom, total):
@@ -582,15 +590,10 @@ def cascade_batch_plan(seg_off, pairs, dim, m, n, g, want_items=False):
     With want_items also the work items themselves, int32[items, 3] = (pair, first query row within the query
     set, query rows), in launch order."""
     seg, prs, out_off = _cascade_batch_args(seg_off, pairs, None, dim, m, n, g)
-    out = (ct.c_longlong * 4)()
-    args = (seg.ctypes.data, seg.size - 1, dim, m, n, g, prs.ctypes.data, len(prs), out)
-    check(clib.spv_cascade_batch_plan(*args, None, 0))
-    plan = dict(items=int(out[0]), out_rows=int(out[1]), hb=int(out[2]), workspace_bytes=int(out[3]), out_off=out_off)
-    if want_items:
-        items = np.empty((plan["items"], 3), np.int32)
-        check(clib.spv_cascade_batch_plan(*args, items.ctypes.data, len(items)))
-        return plan, items
-    return plan
+    out, items = _plan_items(clib.spv_cascade_batch_plan,
+                             (seg.ctypes.data, seg.size - 1, dim, m, n, g, prs.ctypes.data, len(prs)), 4, 3, want_items)
+    plan = dict(items=out[0], out_rows=out[1], hb=out[2], workspace_bytes=out[3], out_off=out_off)
+    return (plan, items) if want_items else plan
 
 
 def cascade_batch(rows, seg_off, pairs, hash_dict, g=2, workspace=None, want_ncand=False):
@@ -858,16 +861,10 @@ def ransac_fit_batch_plan(pair_off, maximum_tries=500, compute_units=256, want_i
     off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
     if off.size < 1:
         raise ValueError("pair_off must start at 0 and never decrease")
-    out = (ct.c_longlong * 4)()
-    check(clib.spv_ransac_fit_batch_plan(off.ctypes.data, off.size - 1, int(maximum_tries), int(compute_units), out,
-                                         None, 0))
-    plan = dict(sets=int(out[0]), tries=int(out[1]), items=int(out[2]), row_blocks=int(out[3]))
-    if want_items:
-        items = np.empty((plan["items"], 5), np.int32)
-        check(clib.spv_ransac_fit_batch_plan(off.ctypes.data, off.size - 1, int(maximum_tries), int(compute_units), out,
-                                             items.ctypes.data, len(items)))
-        return plan, items
-    return plan
+    out, items = _plan_items(clib.spv_ransac_fit_batch_plan,
+                             (off.ctypes.data, off.size - 1, int(maximum_tries), int(compute_units)), 4, 5, want_items, at=2)
+    plan = dict(sets=out[0], tries=out[1], items=out[2], row_blocks=out[3])
+    return (plan, items) if want_items else plan
 
 
 def ransac_fit_batch(x0, x1, pair_off, required_percent_inliers=.9, reprojection_error_allowed=.5, maximum_tries=500,
@@ -947,15 +944,10 @@ def dlt_triangulate_batch_plan(pair_off, use=None, compute_units=256, want_items
         if use.size != off.size - 1:
             raise ValueError("use must hold one value per set")
     u = use.ctypes.data if use is not None else None
-    out = (ct.c_longlong * 3)()
-    check(clib.spv_dlt_triangulate_batch_plan(off.ctypes.data, off.size - 1, u, int(compute_units), out, None, 0))
-    plan = dict(sets=int(out[0]), items=int(out[1]), bound=int(out[2]))
-    if want_items:
-        items = np.empty((plan["items"], 4), np.int32)
-        check(clib.spv_dlt_triangulate_batch_plan(off.ctypes.data, off.size - 1, u, int(compute_units), out,
-                                                  items.ctypes.data, len(items)))
-        return plan, items
-    return plan
+    out, items = _plan_items(clib.spv_dlt_triangulate_batch_plan, (off.ctypes.data, off.size - 1, u, int(compute_units)),
+                             3, 4, want_items, at=1)
+    plan = dict(sets=out[0], items=out[1], bound=out[2])
+    return (plan, items) if want_items else plan
 
 
 def dlt_triangulate_batch(x0, x1, pair_off, P1s, P0s=None, use=None, mask=None, want_error=False, want_rows=False):
@@ -1114,14 +1106,8 @@ NORMALIZE_F32, NORMALIZE_U8 = 0, 1  # SPV_NORMALIZE_* of include/spectavi_amd.h
 
 def _normalize_batch_args(seg_off, total_rows, dim, dtype):
     """seg_off -> int64[nseg + 1], dtype -> SPV_NORMALIZE_*; ValueError for anything spv_normalize_batch_device would
-    reject or that does not describe a table of total_rows rows (the seg_off rules of _batch_args).  Touches no device."""
-    seg = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
-    if seg.size < 1 or seg[0] != 0 or np.any(np.diff(seg) < 0):
-        raise ValueError("seg_off must start at 0 and never decrease")
-    if total_rows is not None and int(seg[-1]) != int(total_rows):
-        raise ValueError("seg_off ends at %d, x has %d rows" % (int(seg[-1]), int(total_rows)))
-    if int(seg[-1]) >= 2 ** 31:
-        raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    reject or that does not describe a table of total_rows rows.  Touches no device."""
+    seg = _seg_offsets(seg_off, total_rows, "x")
     if not 1 <= int(dim) <= 2048:
         raise ValueError("the many-tables form takes 1 <= dim <= 2048 (dim=%d)" % dim)
     if dim == 1 and np.any(np.diff(seg) > 1):
@@ -1138,15 +1124,10 @@ def normalize_batch_plan(seg_off, dim, dtype, compute_units=256, want_items=Fals
     torch / numpy float32 or uint8.  With want_items also the items, int32[items, 3] = (set, first row within the
     set, rows), in the order the device call walks them."""
     seg, kind = _normalize_batch_args(seg_off, None, dim, dtype)
-    out = (ct.c_longlong * 4)()
-    check(clib.spv_normalize_batch_plan(seg.ctypes.data, seg.size - 1, int(dim), kind, int(compute_units), out, None, 0))
-    plan = dict(sets=int(out[0]), items=int(out[1]), workspace_bytes=int(out[2]), rows=int(out[3]))
-    if want_items:
-        items = np.empty((plan["items"], 3), np.int32)
-        check(clib.spv_normalize_batch_plan(seg.ctypes.data, seg.size - 1, int(dim), kind, int(compute_units), out,
-                                            items.ctypes.data, len(items)))
-        return plan, items
-    return plan
+    out, items = _plan_items(clib.spv_normalize_batch_plan, (seg.ctypes.data, seg.size - 1, int(dim), kind, int(compute_units)),
+                             4, 3, want_items, at=1)
+    plan = dict(sets=out[0], items=out[1], workspace_bytes=out[2], rows=out[3])
+    return (plan, items) if want_items else plan
 
 
 def normalize_batch(x, seg_off, want_float=True, want_ubyte=False, workspace=None):
@@ -1272,17 +1253,12 @@ def rectify_batch_plan(sizes, pairs, nchan=1, sampling_factor=1.2, use=None, box
     box[p] = (row_lo, row_hi, col_lo, col_hi) in row-major order (box None: whole frames).  With want_items also the
     items, int32[items, 4] = (pair, image 0 or 1, first frame row, rows <= 8)."""
     sizes, pairs, _, _, use, box = _rectify_batch_args(sizes, pairs, None, None, use, box)
-    out = (ct.c_longlong * 3)()
     out_off = np.zeros(len(pairs) + 1, np.int64)
     args = (sizes.ctypes.data, len(sizes), int(nchan), float(sampling_factor), pairs.ctypes.data, len(pairs), _ptr(use),
-            _ptr(box), out, out_off.ctypes.data)
-    check(clib.spv_rectify_batch_plan(*args, None, 0))
-    plan = dict(pairs=int(out[0]), items=int(out[1]), samples=int(out[2]), out_off=out_off)
-    if want_items:
-        items = np.empty((plan["items"], 4), np.int32)
-        check(clib.spv_rectify_batch_plan(*args, items.ctypes.data, len(items)))
-        return plan, items
-    return plan
+            _ptr(box))
+    out, items = _plan_items(clib.spv_rectify_batch_plan, args, 3, 4, want_items, at=1, tail=(out_off.ctypes.data,))
+    plan = dict(pairs=out[0], items=out[1], samples=out[2], out_off=out_off)
+    return (plan, items) if want_items else plan
 
 
 def rectify_batch_bounds(sizes, pairs, P1s, P0s=None, use=None, nchan=1, sampling_factor=1.2, device=None):
@@ -1450,14 +1426,9 @@ def sift_batch_plan(sizes, ws_bytes=0, want_groups=False):
     65535-image cap closes a group), min_workspace_bytes (the largest image's slice, the least that works) and
     pixels.  With want_groups also int32[groups, 2] = (first image, images)."""
     sz = _sift_sizes(sizes)
-    out = (ct.c_longlong * 4)()
-    check(clib.spv_sift_batch_plan(sz.ctypes.data, len(sz), int(ws_bytes), out, None, 0))
-    plan = dict(groups=int(out[0]), workspace_bytes=int(out[1]), min_workspace_bytes=int(out[2]), pixels=int(out[3]))
-    if want_groups:
-        groups = np.empty((plan["groups"], 2), np.int32)
-        check(clib.spv_sift_batch_plan(sz.ctypes.data, len(sz), int(ws_bytes), out, groups.ctypes.data, len(groups)))
-        return plan, groups
-    return plan
+    out, groups = _plan_items(clib.spv_sift_batch_plan, (sz.ctypes.data, len(sz), int(ws_bytes)), 4, 2, want_groups)
+    plan = dict(groups=out[0], workspace_bytes=out[1], min_workspace_bytes=out[2], pixels=out[3])
+    return (plan, groups) if want_groups else plan
 
 
 def _offsets(off, n, name):

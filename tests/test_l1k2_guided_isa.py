@@ -29,15 +29,25 @@ def _makefile_flags():
     return flags.replace("$(ARCH)", arch).split()
 
 
-@pytest.fixture(scope="module")
-def asm(tmp_path_factory):
+def _compile(tmp_path_factory, source):
     hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc is not installed")
-    out = tmp_path_factory.mktemp("isa") / "l1k2_guided.s"
-    subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-S", os.path.join(CSRC, "l1k2_guided.hip"),
+    out = tmp_path_factory.mktemp("isa") / (source + ".s")
+    subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-S", os.path.join(CSRC, source),
                                                  "-o", str(out)], check=True, cwd=CSRC)
     return out.read_text()
+
+
+@pytest.fixture(scope="module")
+def asm(tmp_path_factory):
+    return _compile(tmp_path_factory, "l1k2_guided.hip")
+
+
+@pytest.fixture(scope="module")
+def asm_batch(tmp_path_factory):
+    """l1k2_batch.hip, which holds the finish kernel of both many-pairs forms."""
+    return _compile(tmp_path_factory, "l1k2_batch.hip")
 
 
 def _metadata(asm, kernel):
@@ -57,8 +67,8 @@ def test_main_kernel_budget(asm):
     assert 2 * md["group_segment_fixed_size"] <= 160 * 1024, md
 
 
-@pytest.mark.parametrize("kernel", ["l1k2_guided_finish_kernel", "epipolar_lines_kernel"])
-def test_helper_kernels_use_no_scratch(asm, kernel):
-    md = _metadata(asm, kernel)
+@pytest.mark.parametrize("kernel", ["l1k2_finish_kernel", "epipolar_lines_kernel"])
+def test_helper_kernels_use_no_scratch(request, kernel):
+    md = _metadata(request.getfixturevalue("asm_batch" if kernel == "l1k2_finish_kernel" else "asm"), kernel)
     assert md["vgpr_spill_count"] == 0 and md["sgpr_spill_count"] == 0 and md["private_segment_fixed_size"] == 0, md
     assert md["group_segment_fixed_size"] == 0, md
