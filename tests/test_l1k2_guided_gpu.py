@@ -1,7 +1,9 @@
 """GPU: the guided many-pairs L1 2-NN (spv_l1k2_guided_batch_device, spv_nn_bruteforcel1k2_guided_batch) equals the
 numpy oracle of tests/l1k2_guided_cases.py in idx, dist and ncand, elementwise, on inputs whose candidate decision
 is exact under any evaluation order; and spv_epipolar_lines_batch_device equals numpy within the rounding of its
-operations.  tests/test_l1k2_guided_plan.py shows without a GPU that the collections get the items these cases are
+operations -- also past its caps: more pairs than one launch takes as kernel arguments (kLinesChunk = 32: the host loop
+of epipolar_lines_run takes three turns, one of them skipped for having no query row) and a query set longer than
+the 4096 x 256 rows one pass of the capped grid covers (the kernel's grid-stride loop).  tests/test_l1k2_guided_plan.py shows without a GPU that the collections get the items these cases are
 written for."""
 import functools
 import os
@@ -223,12 +225,36 @@ def test_host_form_equals_the_device_form():
     assert_equal(tuple(np.concatenate([r[k] for r in res]) for k in range(3)), want, "host form")
 
 
+def random_geoms(rng, rows):
+    return [np.c_[rng.uniform(0, 1280, n), rng.uniform(0, 960, n), rng.uniform(1, 8, (n, 2))].astype(np.float32) for n in rows]
+
+
+def check_lines(got, geom_q, G, used, what):
+    """The out rows `got` of one pair against numpy: three NaNs where the pair is not used or the norm is zero or not
+    finite, else G (u, v, 1)^T / hypot(l0, l1) within 16 eps sum_j |g_ij x_j| / n.  Returns the NaN rows."""
+    eps, rows = np.finfo(np.float64).eps, len(geom_q)
+    assert got.shape == (rows, 3), what
+    x = np.c_[geom_q[:, :2].astype(np.float64), np.ones(rows)]
+    l = x @ G.T
+    n = np.hypot(l[:, 0], l[:, 1])
+    nan = np.full(rows, not used) | ~(n > 0) | ~np.isfinite(n)
+    assert np.array_equal(np.isnan(got), np.repeat(nan[:, None], 3, axis=1)), "%s: the NaN rows" % what
+    # three products, two sums, a hypot and a division, each good to an ulp
+    ok = ~nan
+    bound = 16 * eps * (np.abs(x[:, None, :] * G[None, :, :]).sum(axis=2)) / np.where(ok, n, 1.0)[:, None]
+    diff = np.abs(got[ok] - l[ok] / n[ok, None])
+    if ok.any():
+        print("%s: worst |difference| / bound %.3f over %d rows" % (what, (diff / bound[ok]).max(), ok.sum()))
+    assert (diff <= bound[ok]).all(), what
+    return nan
+
+
 def test_epipolar_lines_against_numpy():
     import torch
     from spectavi_amd import device
     rng = np.random.default_rng(51)
     rows, pairs = [40, 0, 300, 7], [(2, 0), (0, 3), (3, 2)]
-    geoms = [np.c_[rng.uniform(0, 1280, n), rng.uniform(0, 960, n), rng.uniform(1, 8, (n, 2))].astype(np.float32) for n in rows]
+    geoms = random_geoms(rng, rows)
     G = rng.standard_normal((3, 3, 3))
     G[0, 0] = (1.0, -1.0, 3.0)       # with the keypoint below, l0 = l1 = 0 exactly for one row of pair 0
     G[0, 1] = (2.0, 0.5, -6.5)
@@ -237,24 +263,76 @@ def test_epipolar_lines_against_numpy():
     geom = torch.from_numpy(np.concatenate(geoms)).cuda()
     lines = device.epipolar_lines_batch(geom, gc.seg_of(rows), pairs, G, use=use).cpu().numpy()
     assert lines.shape == (sum(rows[q] for q, _ in pairs), 3) and lines.dtype == np.float64
-    eps, o = np.finfo(np.float64).eps, 0
+    o = 0
     for p, (q, _) in enumerate(pairs):
-        x = np.c_[geoms[q][:, :2].astype(np.float64), np.ones(rows[q])]
-        l = x @ G[p].T
-        n = np.hypot(l[:, 0], l[:, 1])
-        nan = np.full(rows[q], not use[p]) | ~(n > 0) | ~np.isfinite(n)
+        nan = check_lines(lines[o:o + rows[q]], geoms[q], G[p], use[p], "pair %d" % p)
         if p == 0:
             assert nan[17] and nan.sum() == 1
-        got = lines[o:o + rows[q]]
-        assert np.array_equal(np.isnan(got), np.repeat(nan[:, None], 3, axis=1)), "pair %d: the NaN rows" % p
-        # three products, two sums, a hypot and a division, each good to an ulp
-        ok = ~nan
-        bound = 16 * eps * (np.abs(x[:, None, :] * G[p][None, :, :]).sum(axis=2)) / np.where(ok, n, 1.0)[:, None]
-        assert (np.abs(got[ok] - l[ok] / n[ok, None]) <= bound[ok]).all(), "pair %d" % p
         o += rows[q]
     # without `use` every pair has a model
     lines = device.epipolar_lines_batch(geom, gc.seg_of(rows), pairs, G).cpu().numpy()
     assert np.isnan(lines).any(axis=1).sum() == 1
+
+
+LINES_CHUNK = 32          # kLinesChunk of l1k2_guided.hip: the pairs one launch takes as kernel arguments
+LINES_GRID = 4096 * 256   # rows of a set that one pass of the capped grid covers
+
+
+def test_epipolar_lines_across_chunks():
+    """70 pairs are three chunks of kernel arguments: out_row and G[9 * i] are carried from chunk to chunk and use[i] is
+    read beyond the first; the second chunk's query sets are all empty (most == 0, no launch), so the third chunk's
+    out rows start where the first one's end."""
+    import torch
+    from spectavi_amd import device
+    rng = np.random.default_rng(52)
+    rows = [40, 0, 300, 7, 257]
+    filled = [0, 2, 3, 4]
+    query = [filled[k] for k in rng.integers(0, 4, 32)] + [1] * 32 + [4, 0, 2, 3, 2, 4]
+    query[5] = 1                     # an empty query set inside a chunk that is launched
+    pairs = [(q, int(d)) for q, d in zip(query, rng.integers(0, 5, 70))]
+    npairs = len(pairs)
+    assert npairs > 2 * LINES_CHUNK and all(rows[q] == 0 for q, _ in pairs[LINES_CHUNK:2 * LINES_CHUNK])
+    assert all(rows[q] > 0 for q, _ in pairs[2 * LINES_CHUNK:])
+    geoms = random_geoms(rng, rows)
+    G = rng.standard_normal((npairs, 3, 3))
+    use = np.ones(npairs, np.int32)
+    use[[3, 40, 65, 69]] = 0
+    seg = gc.seg_of(rows)
+    out_off = device.l1k2_guided_batch_plan(seg, pairs)["out_off"]
+    assert np.array_equal(np.diff(out_off), [rows[q] for q, _ in pairs])
+    assert out_off[2 * LINES_CHUNK] == out_off[LINES_CHUNK] > 0 and out_off[-1] > out_off[2 * LINES_CHUNK]
+    geom = torch.from_numpy(np.concatenate(geoms)).cuda()
+    lines = device.epipolar_lines_batch(geom, seg, pairs, G, use=use).cpu().numpy()
+    assert lines.shape == (out_off[-1], 3)
+    for p, (q, _) in enumerate(pairs):
+        nan = check_lines(lines[out_off[p]:out_off[p + 1]], geoms[q], G[p], use[p], "pair %d" % p)
+        assert nan.all() == (not use[p]) or rows[q] == 0
+    # the last six pairs as a call of their own: the same bits
+    tail = slice(2 * LINES_CHUNK, npairs)
+    alone = device.epipolar_lines_batch(geom, seg, pairs[tail], G[tail], use=use[tail]).cpu().numpy()
+    assert alone.shape == (out_off[-1] - out_off[2 * LINES_CHUNK], 3)
+    assert np.array_equal(alone.view(np.int64), lines[out_off[2 * LINES_CHUNK]:].view(np.int64))
+
+
+def test_epipolar_lines_grid_stride():
+    """One query set of 4096 * 256 + 300 rows: grid.x is capped at 4096 workgroups of 256 lanes, so the last 300 rows
+    are the second turn of 300 lanes' loops."""
+    import torch
+    from spectavi_amd import device
+    rng = np.random.default_rng(53)
+    rows = [LINES_GRID + 300, 1]
+    assert rows[0] > LINES_GRID
+    geoms = random_geoms(rng, rows)
+    G = rng.standard_normal((1, 3, 3))
+    geom = torch.from_numpy(np.concatenate(geoms)).cuda()
+    lines = device.epipolar_lines_batch(geom, gc.seg_of(rows), [(0, 1)], G).cpu().numpy()
+    assert lines.shape == (rows[0], 3)
+    nan = check_lines(lines, geoms[0], G[0], True, "all rows")
+    assert not nan.any()
+    # the last 300 rows as the query set of a collection of their own: the same bits
+    last = torch.from_numpy(np.concatenate([geoms[0][LINES_GRID:], geoms[1]])).cuda()
+    alone = device.epipolar_lines_batch(last, gc.seg_of([300, 1]), [(0, 1)], G).cpu().numpy()
+    assert np.array_equal(alone.view(np.int64), lines[LINES_GRID:].view(np.int64))
 
 
 def test_the_point_of_it_all():
