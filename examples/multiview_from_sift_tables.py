@@ -20,6 +20,11 @@ runs all of them through the many-pairs forms of the same steps, with every inte
     tracks_batch             (--tracks) every pair's inlier matches linked into multi-view tracks: the connected
                              components of the keypoint graph; with --guided the second pass's matches are then
                              accumulated onto the same labels
+    triangulate_tracks       (--triangulate PIXELS, with --tracks) one 3-D point per track from all its observations,
+                             a residual per observation and a verdict per track.  The op takes one camera per view
+                             as given; here they are the synthetic scene's own pixel cameras K [R | t].  Estimating
+                             global cameras (chaining the pairwise fits, fixing their scales) is not part of the
+                             library
 
 Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
 they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic
@@ -27,7 +32,7 @@ here, so that the scene and the cameras are known; extracting them from images i
 before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
     python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}] [--rectify]
-                                                  [--guided PIXELS] [--tracks]
+                                                  [--guided PIXELS] [--tracks] [--triangulate PIXELS]
 """
 import argparse
 import os
@@ -39,11 +44,13 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_fraction=0.08, desc_noise=6.0):
+def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_fraction=0.08, desc_noise=6.0,
+                         return_cameras=False):
     """SIFT tables of one scene seen by n_views calibrated cameras (the first at [I|0]).  Every scene point appears
     in every table, its descriptor perturbed by N(0, desc_noise) per component and view; in every view but the first
     a `wrong_fraction` of them sits at an unrelated position (a descriptor match that is a geometric outlier), and
-    n_extra unrelated keypoints are added to each table.  Rows are shuffled per view.  Returns (tables, K)."""
+    n_extra unrelated keypoints are added to each table.  Rows are shuffled per view.  Returns (tables, K); with
+    return_cameras (tables, K, cameras), cameras float64 [n_views,3,4] the scene's pixel cameras K [R | t]."""
     rng = np.random.default_rng(seed)
     n_extra = n_points // 2 if n_extra is None else n_extra
     K = np.array([[1000.0, 0.0, 640.0], [0.0, 1000.0, 480.0], [0.0, 0.0, 1.0]])
@@ -55,7 +62,7 @@ def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_f
         return np.minimum(np.floor(512.0 * d), 255.0)
 
     d_scene = descriptors(n_points)
-    tables = []
+    tables, cameras = [], []
     for v in range(n_views):
         R, t = np.eye(3), np.zeros(3)
         if v:
@@ -66,6 +73,7 @@ def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_f
             R = np.eye(3) + np.sin(th) * S + (1 - np.cos(th)) * (S @ S)
             t = rng.standard_normal(3)
             t /= np.linalg.norm(t)
+        cameras.append(K @ np.c_[R, t])
         Xc = X @ R.T + t
         pix = ((Xc / Xc[:, 2:]) @ K.T)[:, :2]
         if v:
@@ -77,11 +85,13 @@ def synthetic_sift_views(seed=0, n_views=6, n_points=2000, n_extra=None, wrong_f
         n = len(pix)
         table = np.hstack([pix, rng.uniform(1, 8, (n, 1)), rng.uniform(-np.pi, np.pi, (n, 1)), desc]).astype(np.float32)
         tables.append(table[rng.permutation(n)])
+    if return_cameras:
+        return tables, K, np.array(cameras)
     return tables, K
 
 
 def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, maximum_tries=2000, seed=1,
-                       matcher='l1k2', hash_seed=0x5eed, guided=None, tracks=False):
+                       matcher='l1k2', hash_seed=0x5eed, guided=None, tracks=False, triangulate=None):
     """SIFT tables (a list of float32 [n_v,132] arrays) -> one upload -> split -> exact L1 2-NN of all pairs (or,
     matcher='cascade', the cascade hash of all pairs: descriptors normalised per view as the reference's front-end
     does, m by its rule from the largest view, n = 2, g = 2, hyperplanes from hash_seed) -> ratio
@@ -94,7 +104,9 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     line in the database view; a pair without a model has none.  With tracks also tracks: `tracks_batch`'s (track_off,
     members, flags, label, track) over every pair's inlier matches and, with guided, the second pass's matches
     accumulated onto them; and track_inputs: the seg_off, matches, count and mask (and guided_matches, guided_count)
-    those calls read."""
+    those calls read.  With triangulate (one pixel camera [3,4] per view, e.g. synthetic_sift_views' own: the library
+    does not estimate them) and tracks also track_points: `triangulate_tracks`' (X, err, ok, nused) of those tracks, ok
+    without a residual bound (cheirality alone; call `triangulate_tracks` with max_error for one)."""
     import torch
     from spectavi_amd import device as spv
     seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
@@ -143,6 +155,10 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
         if tracks:
             out['tracks'] = spv.tracks_batch(seg, pairs, gm, gcount, label=out['tracks'][3])
             out['track_inputs'].update(guided_matches=gm, guided_count=gcount)
+    if triangulate is not None and tracks:
+        track_off, members = out['tracks'][:2]
+        out['track_points'] = spv.triangulate_tracks(geom, seg, triangulate, track_off, members)
+        out['track_inputs']['geom'] = geom
     return out
 
 
@@ -180,6 +196,20 @@ def report(out):
         print("track length: " + ", ".join("%d x %d" % (c, l) for l, c in enumerate(hist.tolist()) if c))
 
 
+def report_track_points(out, cameras, max_error):
+    """The tracks triangulated again with a residual bound of max_error pixels: solved and ok counts and the median
+    residual of the ok tracks' observations."""
+    from spectavi_amd import device as spv
+    track_off, members = out['tracks'][:2]
+    X, err, ok, nused = spv.triangulate_tracks(out['track_inputs']['geom'], out['track_inputs']['seg_off'], cameras,
+                                               track_off, members, max_error=max_error)
+    ok, nused, err = ok.cpu().numpy() != 0, nused.cpu().numpy(), err.cpu().numpy()
+    of_ok = np.repeat(ok, np.diff(track_off))
+    med = float(np.nanmedian(err[of_ok])) if of_ok.any() else float('nan')
+    print("track points: solved %d of %d, ok %d within %.2f px, median residual of the ok tracks %.2e px" % (
+        int((nused >= 2).sum()), len(ok), int(ok.sum()), max_error, med))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--images", type=int, default=6, help="views of the scene")
@@ -190,16 +220,21 @@ def main():
     ap.add_argument("--guided", type=float, default=None, metavar="PIXELS",
                     help="match again inside a band of this half-width around the fitted epipolar lines")
     ap.add_argument("--tracks", action="store_true", help="link every pair's inlier matches into multi-view tracks")
+    ap.add_argument("--triangulate", type=float, default=None, metavar="PIXELS",
+                    help="with --tracks: one point per track from the scene's own cameras, ok within this residual")
     a = ap.parse_args()
     import torch
-    tables, K = synthetic_sift_views(a.seed, a.images, a.points)
+    tables, K, cameras = synthetic_sift_views(a.seed, a.images, a.points, return_cameras=True)
+    triangulate = cameras if (a.triangulate is not None and a.tracks) else None
     for rep in range(2):  # the second round is the warm one
         torch.cuda.synchronize()
         s = time.perf_counter()
-        out = multiview_pipeline(tables, K, matcher=a.matcher, guided=a.guided, tracks=a.tracks)
+        out = multiview_pipeline(tables, K, matcher=a.matcher, guided=a.guided, tracks=a.tracks, triangulate=triangulate)
         torch.cuda.synchronize()
         dt = time.perf_counter() - s
     report(out)
+    if triangulate is not None:
+        report_track_points(out, cameras, a.triangulate)
     n = int(out['out_off'][-1])
     E = out['X'][:n, :3] / out['X'][:n, 3:]
     print("%d views, %.1f ms (warm); depth of the points: median %.2f" % (a.images, dt * 1e3, float(E[:, 2].median()) if n else 0.0))

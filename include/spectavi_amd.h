@@ -180,7 +180,8 @@ const char *spv_version(void);
  * "rectify_batch", "ransac_batch_score",
  * "ransac_batch_reduce",
  * "gather_match_coords_batch", "normalize_batch_stats", "normalize_batch_finish", "normalize_batch", "tracks_init", "tracks_hook",
- * "tracks_flatten", "tracks_sizes", "tracks_scan", "tracks_place", "tracks_order", "tracks_flags") are bracketed by hipEvents recorded on the
+ * "tracks_flatten", "tracks_sizes", "tracks_scan", "tracks_place", "tracks_order", "tracks_flags",
+ * "tracks_triangulate", "tracks_triangulate_long") are bracketed by hipEvents recorded on the
  * stream they are launched on.  spv_profile_read synchronises with the
  * recorded events and returns launch count and summed milliseconds since the
  * last reset. */
@@ -1195,6 +1196,59 @@ int spv_tracks_batch_device(const long long *seg_off, int nseg, const int32_t *p
 int spv_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, int npairs, const int32_t *matches,
                      int count, const uint8_t *mask, int min_len, int accumulate, int32_t *label, int32_t *track,
                      long long *track_off, int32_t *members, uint8_t *flags, int32_t *counts);
+
+/* N-view DLT of every track (tracks_triangulate.hip): one 3-D point per track from all its observations, a residual
+ * per observation and a verdict per track, for a caller who has one camera per set (a calibrated rig, an earlier
+ * reconstruction, a pose graph of their own).  The cameras are taken as given: chaining pairwise fits into global
+ * cameras, bundle adjustment and resection are not part of the library.  The reference has no such step.
+ *   d_geom   float32[total_rows, 4]: x, y, sigma, angle of every row, as spv_sift_split_device writes them; only x
+ *            and y are read, widened to double.
+ *   seg_off, nseg: host, the seg_off of spv_l1k2_batch_device.
+ *   cams     host double[nseg, 12]: the row-major 3x4 camera P_s of every set, pixel or calibrated to match d_geom.
+ *   use_set  host int32[nseg] or NULL: a set with use_set[s] == 0 has no camera (its row of cams is not read).
+ *   track_off host long long[ntracks + 1], d_members int32[nmembers, 2] = (set, row within the set): as
+ *            spv_tracks_batch_device returns them; track t owns members [track_off[t], track_off[t + 1]).
+ * A member is usable when its set is in [0, nseg), its row inside that set and the set has a camera.  Nothing else
+ * is dereferenced: garbage members give unsolved tracks, never an access out of bounds.  Per track t:
+ *   matrix   usable observation i in set s with (u, v) = (double)d_geom[row][0..1] contributes the reference's two
+ *            DLT rows u P_s[2] - P_s[0], v P_s[2] - P_s[1] (src/DltTriangulator.h:38-54), in member order: A_t, 2m x 4.
+ *   d_X      double[ntracks, 4]: the unit right singular vector of A_t's smallest singular value, sign as
+ *            spv_dlt_triangulate_device gives it.  A_t is reduced to a 4x4 triangle by Givens rotations (never through
+ *            A^T A) and solved by the two-view solver.  A track with exactly two usable observations goes through the
+ *            two-view arithmetic itself: d_X is bit for bit spv_dlt_triangulate_batch_device's for the same two
+ *            observations (w = 1) with P0 = the first member's camera, P1 = the second's, and the two d_err add up to
+ *            its err exactly.  A track with fewer than 2 usable observations is not solved: its d_X row is all zeros.
+ *   d_err    double[nmembers] or NULL: |proj(P_s X) - (u, v)| of every usable observation of a solved track, NaN
+ *            everywhere else.
+ *   d_ok     uint8[ntracks] or NULL: 1 iff the track is solved, X is finite, every usable observation has
+ *            sign(det P[:, :3]) / |P[2, :3]|^2 * (P X)[2] / X[3] > 0 and err <= max_error (+inf: cheirality alone).
+ *   d_nused  int32[ntracks] or NULL: the usable observations.
+ * Outputs are aligned with the inputs; nothing is compacted.  A track's results depend on its own members, d_geom and
+ * the cameras alone: not on its neighbours, its place in the call or the form that solves it beyond the rounding
+ * of the reduction order (tracks of at most two usable observations: not at all).
+ * Two forms, chosen by a track's member count alone: the lane form (one lane per track, at most L members) and the
+ * wave form (one wave per track, the lanes' triangles combined in 6 butterfly steps); kernel names for
+ * spv_profile_read "tracks_triangulate" and "tracks_triangulate_long".  spv_tracks_triangulate_set_long(L): L >= 0,
+ * default 16, the fastest of 8, 16, 32, 64 measured on two inputs of a million tracks; 0 sends every track of 3 or more
+ * members to the wave form, a value no track reaches sends none.  spv_tracks_triangulate_get_long: the setting.
+ * spv_tracks_triangulate_plan: host only, touches no device.  out = {lane-form tracks, wave-form tracks, workgroups
+ * of the lane launch, longest track} under the current setting.
+ * SPV_ERR_INVALID, nothing launched: the rules of seg_off (spv_l1k2_batch_device); track_off[0] != 0, decreasing, or
+ * not ending at nmembers; nmembers >= 2^31; a negative count; a NULL required pointer (seg_off, track_off; cams where
+ * nseg > 0; d_members where nmembers > 0; d_geom where both total_rows and nmembers > 0; d_X where ntracks > 0); a
+ * NaN max_error; an output not aligned to its element size.  Asynchronous on `stream` but for the one upload of the
+ * call's tables (cameras, use_set, seg_off, track_off, the wave-form list).
+ * spv_tracks_triangulate: host pointers, on the first selected device; touches no device when ntracks is 0. */
+int spv_tracks_triangulate_set_long(int L);
+int spv_tracks_triangulate_get_long(void);
+int spv_tracks_triangulate_plan(const long long *track_off, int ntracks, long long out[4]);
+int spv_tracks_triangulate_device(const float *d_geom, const long long *seg_off, int nseg, const double *cams,
+                                  const int32_t *use_set, const long long *track_off, int ntracks,
+                                  const int32_t *d_members, long long nmembers, double max_error, double *d_X,
+                                  double *d_err, uint8_t *d_ok, int32_t *d_nused, void *stream);
+int spv_tracks_triangulate(const float *geom, const long long *seg_off, int nseg, const double *cams,
+                           const int32_t *use_set, const long long *track_off, int ntracks, const int32_t *members,
+                           long long nmembers, double max_error, double *X, double *err, uint8_t *ok, int32_t *nused);
 
 /* normalize_to_ubyte_and_multiple_16_dim (reference spectavi/feature.py:384-407) for a float32
  * input, bit for bit what numpy computes: per-column de-mean (numpy's row-ordered float32 sum),

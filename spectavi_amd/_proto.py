@@ -166,6 +166,11 @@ PROTOTYPES = {
     "spv_tracks_batch_workspace_bytes": (sz, [ll, i]),
     "spv_tracks_batch_device": (i, [vp, i, vp, i, vp, vp, i, vp, i, i] + [vp] * 7 + [sz, vp]),
     "spv_tracks_batch": (i, [vp, i, vp, i, vp, i, vp, i, i] + [vp] * 6),
+    "spv_tracks_triangulate_set_long": (i, [i]),
+    "spv_tracks_triangulate_get_long": (i, []),
+    "spv_tracks_triangulate_plan": (i, [vp, i, pll]),
+    "spv_tracks_triangulate_device": (i, [vp, vp, i, vp, vp, vp, i, vp, ll, d] + [vp] * 5),
+    "spv_tracks_triangulate": (i, [vp, vp, i, vp, vp, vp, i, vp, ll, d] + [vp] * 4),
     "spv_normalize": (i, [f32a, i, i, vp, vp]),
     "spv_normalize_workspace_bytes": (sz, [i]),
     "spv_normalize_workspace_bytes_rows": (sz, [i, i]),

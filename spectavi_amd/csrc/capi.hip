@@ -356,6 +356,33 @@ int host_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, 
   return SPV_OK;
 }
 
+// The N-view triangulation of tracks through host pointers, on the first selected device: geom and the members up,
+// one tracks_triangulate_run, the four results back.  A call without a track touches no device.
+int host_tracks_triangulate(const float *geom, const long long *seg_off, int nseg, const double *cams, const int32_t *use_set,
+                            const long long *track_off, int ntracks, const int32_t *members, long long nmembers,
+                            double max_error, double *X, double *err, uint8_t *ok, int32_t *nused) {
+  SPV_TRY(tracks_triangulate_check(geom, seg_off, nseg, cams, track_off, ntracks, members, nmembers, max_error, X, err, ok, nused));
+  if (ntracks == 0) return SPV_OK;
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t gb = (size_t)seg_off[nseg] * 4 * sizeof(float), mb = (size_t)nmembers * 2 * sizeof(int32_t);
+  const size_t nt = (size_t)ntracks, nm = (size_t)nmembers;
+  DevBuf dg, dm, dX, de, dk, dn;
+  SPV_TRY(alloc_all({{&dg, gb}, {&dm, mb}, {&dX, nt * 4 * sizeof(double)}, {&de, err ? nm * sizeof(double) : 0},
+                     {&dk, ok ? nt : 0}, {&dn, nused ? nt * sizeof(int32_t) : 0}}));
+  SPV_TRY(dg.copy_in(geom, gb, st));
+  SPV_TRY(dm.copy_in(members, mb, st));
+  SPV_TRY(tracks_triangulate_run(dg.as<float>(), seg_off, nseg, cams, use_set, track_off, ntracks, dm.as<int32_t>(), nmembers,
+                                 max_error, dX.as<double>(), err ? de.as<double>() : nullptr, ok ? dk.as<uint8_t>() : nullptr,
+                                 nused ? dn.as<int32_t>() : nullptr, st));
+  SPV_TRY(dX.copy_out(X, nt * 4 * sizeof(double), st));
+  if (err) SPV_TRY(de.copy_out(err, nm * sizeof(double), st));
+  if (ok) SPV_TRY(dk.copy_out(ok, nt, st));
+  if (nused) SPV_TRY(dn.copy_out(nused, nt * sizeof(int32_t), st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  return SPV_OK;
+}
+
 // The many-sets RANSAC through host pointers, on the first selected device: both arrays up, one
 // ransac_fit_batch_run.  A collection in which no set runs touches no device.
 int host_ransac_fit_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
@@ -1574,6 +1601,43 @@ int spv_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, i
   return host_api([&] {
     return host_tracks_batch(seg_off, nseg, pairs, npairs, matches, count, mask, min_len, accumulate, label, track, track_off,
                              members, flags, counts);
+  });
+}
+int spv_tracks_triangulate_set_long(int L) {
+  clear_error();
+  if (L < 0) return set_error(SPV_ERR_INVALID, "longest lane-form track %d", L);
+  tracks_triangulate_set_long(L);
+  return SPV_OK;
+}
+int spv_tracks_triangulate_get_long(void) { return tracks_triangulate_get_long(); }
+int spv_tracks_triangulate_plan(const long long *track_off, int ntracks, long long out[4]) {
+  return api([&] {
+    if (ntracks < 0 || !out) return set_error(SPV_ERR_INVALID, "bad arguments");
+    SPV_TRY(check_offsets(track_off, ntracks, "track_off"));
+    TracksTriangulatePlan pl;
+    tracks_triangulate_plan(track_off, ntracks, &pl);
+    out[0] = pl.lane_tracks;
+    out[1] = pl.wave_tracks;
+    out[2] = pl.lane_groups;
+    out[3] = pl.longest;
+    return (int)SPV_OK;
+  });
+}
+int spv_tracks_triangulate_device(const float *d_geom, const long long *seg_off, int nseg, const double *cams,
+                                  const int32_t *use_set, const long long *track_off, int ntracks, const int32_t *d_members,
+                                  long long nmembers, double max_error, double *d_X, double *d_err, uint8_t *d_ok,
+                                  int32_t *d_nused, void *stream) {
+  return api([&] {
+    return tracks_triangulate_run(d_geom, seg_off, nseg, cams, use_set, track_off, ntracks, d_members, nmembers, max_error, d_X,
+                                  d_err, d_ok, d_nused, static_cast<hipStream_t>(stream));
+  });
+}
+int spv_tracks_triangulate(const float *geom, const long long *seg_off, int nseg, const double *cams, const int32_t *use_set,
+                           const long long *track_off, int ntracks, const int32_t *members, long long nmembers,
+                           double max_error, double *X, double *err, uint8_t *ok, int32_t *nused) {
+  return host_api([&] {
+    return host_tracks_triangulate(geom, seg_off, nseg, cams, use_set, track_off, ntracks, members, nmembers, max_error, X, err,
+                                   ok, nused);
   });
 }
 int spv_ratio_test(const uint64_t *idx, const void *dist, int dist_is_float, int yrows,

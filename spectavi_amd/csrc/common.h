@@ -593,4 +593,25 @@ int tracks_batch_run(const long long *seg_off, int nseg, const int32_t *pairs, i
                      int32_t *d_label, int32_t *d_track, long long *d_track_off, int32_t *d_members, uint8_t *d_flags,
                      int32_t *d_counts, void *d_ws, size_t ws_bytes, hipStream_t stream);
 
+// ---- N-view DLT of every track (tracks_triangulate.hip) ------------------------------------
+// The longest track the lane form takes; 0: every track of 3 or more members takes the wave form.  The setter
+// returns the setting before.
+int tracks_triangulate_set_long(int L);
+int tracks_triangulate_get_long();
+// Which tracks take which form, a function of track_off and the setting alone (host only).
+struct TracksTriangulatePlan {
+  long long lane_tracks = 0, wave_tracks = 0, lane_groups = 0, longest = 0;
+  std::vector<int32_t> wave_list;  // the wave-form tracks, ascending
+};
+void tracks_triangulate_plan(const long long *track_off, int ntracks, TracksTriangulatePlan *plan);
+// SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
+int tracks_triangulate_check(const void *geom, const long long *seg_off, int nseg, const double *cams,
+                             const long long *track_off, int ntracks, const void *members, long long nmembers,
+                             double max_error, const void *X, const void *err, const void *ok, const void *nused);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the call's tables.
+int tracks_triangulate_run(const float *d_geom, const long long *seg_off, int nseg, const double *cams,
+                           const int32_t *use_set, const long long *track_off, int ntracks, const int32_t *d_members,
+                           long long nmembers, double max_error, double *d_X, double *d_err, uint8_t *d_ok,
+                           int32_t *d_nused, hipStream_t stream);
+
 }  // namespace spv

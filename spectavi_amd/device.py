@@ -1083,6 +1083,111 @@ def tracks_batch(seg_off, pairs, matches, count, mask=None, min_len=2, label=Non
     return track_off[:nt + 1].cpu().numpy(), members[:nm], flags[:nt], label, track
 
 
+def tracks_triangulate_set_long(L):
+    """The longest track `triangulate_tracks` solves with one lane (spv_tracks_triangulate_set_long; default 16, the
+    fastest of 8, 16, 32 and 64 measured): longer tracks take one wave each.  0 sends every track of 3 or more members to
+    the wave form, a value no track reaches sends none.  The results of a track with more than two usable observations
+    differ between the forms by rounding only."""
+    if int(L) != L or int(L) < 0:
+        raise ValueError("L must be an integer >= 0")
+    check(clib.spv_tracks_triangulate_set_long(int(min(int(L), 2 ** 31 - 1))))
+
+
+def tracks_triangulate_get_long():
+    """The setting of `tracks_triangulate_set_long`."""
+    return int(clib.spv_tracks_triangulate_get_long())
+
+
+def _track_offsets(track_off, nmembers):
+    off = np.ascontiguousarray(track_off, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("track_off must start at 0 and never decrease")
+    if int(off[-1]) >= 2 ** 31:
+        raise ValueError("the tracks must hold fewer than 2^31 members in all")
+    if nmembers is not None and int(off[-1]) != int(nmembers):
+        raise ValueError("track_off ends at %d, members has %d rows" % (int(off[-1]), int(nmembers)))
+    return off
+
+
+def triangulate_tracks_plan(track_off):
+    """Which form solves how many tracks under the current setting (spv_tracks_triangulate_plan; host only, no device
+    touched): dict of lane_tracks, wave_tracks, lane_groups (workgroups of the lane launch) and longest."""
+    off = _track_offsets(track_off, None)
+    out = (ct.c_longlong * 4)()
+    check(clib.spv_tracks_triangulate_plan(off.ctypes.data, off.size - 1, out))
+    return dict(lane_tracks=int(out[0]), wave_tracks=int(out[1]), lane_groups=int(out[2]), longest=int(out[3]))
+
+
+def _tracks_triangulate_args(geom_shape, seg_off, cameras, track_off, members_shape, max_error, use):
+    """seg_off -> int64[nseg + 1], cameras -> float64[nseg, 12], use -> int32[nseg] or None, track_off ->
+    int64[ntracks + 1], max_error -> float; ValueError for anything spv_tracks_triangulate_device would reject or that
+    does not describe geom [total_rows, 4] and members [nmembers, 2].  A None entry of a cameras list is a set
+    without a camera.  Touches no device."""
+    if len(geom_shape) != 2 or geom_shape[1] != 4:
+        raise ValueError("geom must be [total_rows, 4]")
+    if len(members_shape) != 2 or members_shape[1] != 2:
+        raise ValueError("members must be [nmembers, 2]")
+    seg = _seg_offsets(seg_off, geom_shape[0], "geom")
+    nseg = seg.size - 1
+    off = _track_offsets(track_off, members_shape[0])
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
+        if use.size != nseg:
+            raise ValueError("use must hold one value per set")
+    if not isinstance(cameras, np.ndarray) and any(P is None for P in cameras):
+        skip = np.array([P is None for P in cameras])
+        if len(skip) != nseg:
+            raise ValueError("cameras must hold one [3,4] camera per set")
+        use = (~skip).astype(np.int32) if use is None else (use * ~skip).astype(np.int32)
+        cameras = [np.zeros((3, 4)) if P is None else P for P in cameras]
+    try:
+        cams = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12) if nseg else np.zeros((0, 12))
+    except (TypeError, ValueError):
+        raise ValueError("cameras must hold one [3,4] camera per set")
+    if cams.shape[0] != nseg:
+        raise ValueError("cameras must hold one [3,4] camera per set")
+    max_error = float(max_error)
+    if max_error != max_error:
+        raise ValueError("max_error must not be NaN")
+    return seg, cams, use, off, max_error
+
+
+def triangulate_tracks(geom, seg_off, cameras, track_off, members, max_error=float("inf"), use=None, want_err=True):
+    """One 3-D point per track from all its observations (spv_tracks_triangulate_device): geom CUDA float32
+    [total_rows, 4] (x, y, sigma, angle of every set's rows back to back, as `sift_split` writes them), seg_off the
+    sets' offsets, cameras one host [3,4] camera per set ([nseg,3,4], or a list whose None entries are sets without
+    a camera), use an optional per-set switch, (track_off, members) what `tracks_batch` returned.  The cameras are
+    taken as given -- pixel cameras for pixel geom; estimating them is not part of the library.
+
+    Returns (X float64 [ntracks,4], err float64 [nmembers] or None without want_err, ok uint8 [ntracks], nused int32
+    [ntracks]) as CUDA tensors, aligned with the inputs.  An observation is usable when its set and row exist and the
+    set has a camera; X is the unit null vector of the track's 2m x 4 DLT matrix (sign as `dlt_triangulate`'s), all
+    zeros for a track with fewer than 2 usable observations; err the image-plane residual norm of every usable
+    observation of a solved track, NaN elsewhere; ok is 1 where the track is solved, X is finite, the point lies in
+    front of every usable observation's camera and every err <= max_error.  A track with exactly two usable
+    observations is bit for bit `dlt_triangulate_batch`'s answer for them.  Asynchronous but for the upload of the
+    cameras and offsets."""
+    if not isinstance(geom, torch.Tensor) or geom.dtype != torch.float32:
+        raise ValueError("geom must be a float32 tensor [total_rows, 4]")
+    if not isinstance(members, torch.Tensor) or members.dtype != torch.int32:
+        raise ValueError("members must be an int32 tensor [nmembers, 2]")
+    seg, cams, use, off, max_error = _tracks_triangulate_args(tuple(geom.shape), seg_off, cameras, track_off,
+                                                              tuple(members.shape), max_error, use)
+    _need(geom, torch.float32, "geom")
+    _need(members, torch.int32, "members")
+    nt, nm, dev = off.size - 1, int(members.shape[0]), geom.device
+    X = torch.empty((nt, 4), dtype=torch.float64, device=dev)
+    err = torch.empty(nm, dtype=torch.float64, device=dev) if want_err else None
+    ok = torch.empty(nt, dtype=torch.uint8, device=dev)
+    nused = torch.empty(nt, dtype=torch.int32, device=dev)
+    with _on_device_of(geom, members) as stream:
+        check(clib.spv_tracks_triangulate_device(
+            geom.data_ptr(), seg.ctypes.data, seg.size - 1, cams.ctypes.data, use.ctypes.data if use is not None else None,
+            off.ctypes.data, nt, members.data_ptr(), nm, max_error, X.data_ptr(), err.data_ptr() if want_err else None,
+            ok.data_ptr(), nused.data_ptr(), stream))
+    return X, err, ok, nused
+
+
 def normalize(x, want_float=True, want_ubyte=False, workspace=None):
     """`normalize_to_ubyte_and_multiple_16_dim` (reference spectavi/feature.py:384-407) on a CUDA float32
     [rows, dim] table, bit-identical to the numpy function: returns the float32 [rows, dim16] table

@@ -449,6 +449,79 @@ def dlt_triangulate_batch(P1s, x0s, x1s, P0s=None, masks=None, ret_error=False):
     return Xs
 
 
+def triangulate_tracks(coords, sizes, cameras, track_off, members, max_error=float('inf'), use=None):
+    """
+    One 3-D point per multi-view track from all its observations (an addition: the reference stops at two views).
+    `coords` is a list with one [n_v, >=2] array per view whose first two columns are the keypoints' x and y (they
+    are rounded to float32, the precision of a SIFT table), `sizes` the rows of every view as `match_tracks_batch`
+    takes them (None: the rows of coords), `cameras` one [3,4] camera per view -- a None entry is a view without a
+    camera --, `use` an optional per-view switch, (`track_off`, `members`) what `match_tracks_batch` returned.  The
+    cameras are taken as given: estimating them is not part of the library.
+
+    Returns numpy arrays (X float64 [ntracks,4], err float64 [nmembers], ok uint8 [ntracks], nused int32 [ntracks]).
+    A member is usable when its view and row exist and the view has a camera.  X is the unit null vector of the
+    track's 2m x 4 DLT matrix, sign as `dlt_triangulate` gives it, all zeros for a track with fewer than 2 usable
+    members; err is the image-plane residual of every usable member of a solved track, NaN elsewhere; ok is 1 where
+    the track is solved, X is finite, the point lies in front of every usable member's camera and every err <=
+    max_error; nused counts the usable members.
+    """
+    arrs = [np.asarray(c) for c in coords]
+    for a in arrs:
+        if a.ndim != 2 or a.shape[1] < 2:
+            raise ValueError('coords must hold one [n, >=2] array per view.')
+    if sizes is None:
+        sizes = [len(a) for a in arrs]
+    sizes = np.asarray(sizes)
+    if sizes.ndim != 1 or (sizes.size and (sizes.dtype.kind not in 'iu' or sizes.min() < 0)):
+        raise ValueError('sizes must be non-negative integers, one per view.')
+    nseg = len(sizes)
+    if len(arrs) != nseg or any(len(a) != n for a, n in zip(arrs, sizes)):
+        raise ValueError('coords must hold sizes[v] rows for every view.')
+    seg = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+    if int(seg[-1]) >= 2 ** 31:
+        raise ValueError('the views must hold fewer than 2^31 rows in all.')
+    if len(cameras) != nseg:
+        raise ValueError('cameras must hold one entry per view.')
+    usable = np.array([P is not None for P in cameras], dtype=np.int32)
+    if use is not None:
+        use = np.asarray(use).reshape(-1)
+        if use.size != nseg:
+            raise ValueError('use must hold one value per view.')
+        usable = (usable * (use != 0)).astype(np.int32)
+    cams = np.zeros((nseg, 12))
+    for v, P in enumerate(cameras):
+        if P is None:
+            continue
+        P = np.asarray(P, dtype=np.float64)
+        if P.shape != (3, 4):
+            raise ValueError('cameras must be [3,4] matrices.')
+        cams[v] = P.reshape(12)
+    off = np.ascontiguousarray(track_off, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError('track_off must start at 0 and never decrease.')
+    mem = np.asarray(members)
+    if mem.size == 0:
+        mem = np.zeros((0, 2), np.int32)
+    if mem.ndim != 2 or mem.shape[1] != 2 or mem.dtype.kind not in 'iu':
+        raise ValueError('members must be integers of shape [nmembers, 2].')
+    if int(off[-1]) != len(mem) or len(mem) >= 2 ** 31:
+        raise ValueError('track_off must end at the rows of members, fewer than 2^31.')
+    mem = np.ascontiguousarray(np.clip(mem, -1, 2 ** 31 - 1), dtype=np.int32)
+    max_error = float(max_error)
+    if max_error != max_error:
+        raise ValueError('max_error must not be NaN.')
+    geom = np.zeros((int(seg[-1]), 4), np.float32)
+    for v, a in enumerate(arrs):
+        geom[seg[v]:seg[v + 1], :2] = a[:, :2]
+    nt, nm = off.size - 1, len(mem)
+    X, err = np.zeros((nt, 4)), np.full(nm, np.nan)
+    ok, nused = np.zeros(nt, np.uint8), np.zeros(nt, np.int32)
+    check(clib.spv_tracks_triangulate(geom.ctypes.data, seg.ctypes.data, nseg, cams.ctypes.data, usable.ctypes.data,
+                                      off.ctypes.data, nt, mem.ctypes.data, nm, max_error, X.ctypes.data,
+                                      err.ctypes.data, ok.ctypes.data, nused.ctypes.data))
+    return X, err, ok, nused
+
+
 # ==================================================================================
 # image_pair_rectification (reference spectavi/mvg.py:47-106)
 # ==================================================================================
