@@ -1,0 +1,164 @@
+"""The argument rules of a collection -- many sets back to back in one table, and pairs of them -- stated once for
+the Python wrappers of spectavi_amd.device, .feature and .mvg, as csrc/collection.h states them for the C entries.
+Needs numpy alone; touches neither the library nor a device.  Every refusal is a ValueError unless the caller names
+another class."""
+import numpy as np
+
+MAX_SETS = 2 ** 20      # of spv_ransac_fit_batch and spv_dlt_triangulate_batch, which keep state per set
+
+
+def offsets_unchecked(off, name):
+    """off -> int64[n + 1] with at least the one entry that lets n be read; the rules of check_offsets (collection.h)
+    are left to the library, as the *_plan entries that take bare offsets do."""
+    off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("%s must start at 0 and never decrease" % name)
+    return off
+
+
+def offsets(off, name, rows=None, rows_of=None, count=None):
+    """off -> int64[n + 1] under check_offsets (collection.h): starts at 0, never decreases, ends below 2^31 -- and at
+    `rows`, the rows of the table `rows_of` (None: any); with `count`, n must be count."""
+    off = offsets_unchecked(off, name)
+    if count is not None and off.size != count + 1:
+        raise ValueError("%s must hold %d offsets" % (name, count + 1))
+    if off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("%s must start at 0 and never decrease" % name)
+    if rows is not None and int(off[-1]) != int(rows):
+        raise ValueError("%s ends at %d, %s has %d rows" % (name, int(off[-1]), rows_of, int(rows)))
+    if int(off[-1]) >= 2 ** 31:
+        raise ValueError("%s must end below 2^31: fewer than 2^31 rows in all" % name)
+    return off
+
+
+def offsets_of(sizes):
+    """int64[n + 1]: the offsets of sets of `sizes` rows back to back (no rule applied: see offsets)."""
+    return np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+
+
+def offsets_of_sizes(sizes, per):
+    """A list of row counts, one per `per` -> (n, int64[n + 1]) under the 2^31 rule of check_offsets (collection.h)."""
+    sizes = np.asarray(sizes)
+    if sizes.ndim != 1 or (sizes.size and (sizes.dtype.kind not in "iu" or sizes.min() < 0)):
+        raise ValueError("sizes must be non-negative integers, one per %s" % per)
+    return len(sizes), offsets(offsets_of(sizes), "the %ss' offsets" % per)
+
+
+def check_set_count(n):
+    """The 2^20 sets cap that spv_ransac_fit_batch and spv_dlt_triangulate_batch state."""
+    if n > MAX_SETS:
+        raise ValueError("more than 2^20 sets per call")
+
+
+def all_pairs(n):
+    """The default pair list: every i < j as (query j, database i)."""
+    return [(j, i) for i in range(n) for j in range(i + 1, n)]
+
+
+def pair_table(pairs, nseg, noun="sets"):
+    """pairs -> int32[npairs, 2] under the pair rule of check_collection (collection.h): integers, every entry in
+    [0, nseg); an empty list is [0, 2]."""
+    prs = np.asarray(pairs)
+    if prs.size == 0:
+        prs = np.zeros((0, 2), np.int32)
+    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
+        raise ValueError("pairs must be integers of shape [npairs, 2]")
+    if prs.size and (int(prs.min()) < 0 or int(prs.max()) >= nseg):
+        raise ValueError("pairs name %s outside [0, %d)" % (noun, nseg))
+    return np.ascontiguousarray(prs, dtype=np.int32)
+
+
+def out_offsets(seg, prs, below_2_31=False):
+    """int64[npairs + 1]: pair p owns the out rows [out_off[p], out_off[p + 1]), one per row of its query set
+    (pair_out_off of collection.h); below_2_31 is the rule check_collection_out32 adds."""
+    out_off = offsets_of(np.diff(seg)[prs[:, 0]])
+    if below_2_31 and int(out_off[-1]) >= 2 ** 31:
+        raise ValueError("the pairs must own fewer than 2^31 out rows in all")
+    return out_off
+
+
+def per_pair(out_off, *arrays):
+    """One tuple of views per pair: rows out_off[p]:out_off[p + 1] of every array."""
+    return [tuple(a[lo:hi] for a in arrays) for lo, hi in zip(out_off[:-1], out_off[1:])]
+
+
+def check_matcher_dim(dim):
+    """The row width rule of spv_l1k2_batch_device and spv_cascade_batch_device."""
+    if dim <= 0 or dim % 16 != 0:
+        raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
+    if dim > 256:
+        raise ValueError("the many-pairs form takes dim <= 256 (dim=%d)" % dim)
+
+
+def use_flags(use, n, per="set"):
+    """use -> int32[n] of 0 / 1 (anything non-zero is 1), or None: the `use` array of the C entries."""
+    if use is None:
+        return None
+    use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
+    if use.size != n:
+        raise ValueError("use must hold one value per %s" % per)
+    return use
+
+
+def packed_cameras(Ps, n, name, per="set"):
+    """Ps ([n, 3, 4], [n, 12] or a list of [3, 4]) -> float64[n, 12], as the C entries read cameras."""
+    cams = np.ascontiguousarray(Ps, dtype=np.float64).reshape(-1, 12) if n else np.zeros((0, 12))
+    if cams.shape[0] != n:
+        raise ValueError("%s must hold one [3,4] camera per %s" % (name, per))
+    return cams
+
+
+def none_cameras_skip(Ps, n, name, use, per="set"):
+    """A None entry of a camera list skips its set: (Ps with zeros there, `use` -- use_flags' -- with 0 there) for
+    packed_cameras and the C entry; both as they came where no entry is None."""
+    if not isinstance(Ps, np.ndarray) and any(P is None for P in Ps):
+        skip = np.array([P is None for P in Ps])
+        if len(skip) != n:
+            raise ValueError("%s must hold one [3,4] camera per %s" % (name, per))
+        use = (~skip).astype(np.int32) if use is None else (use * ~skip).astype(np.int32)
+        Ps = [np.zeros((3, 4)) if P is None else P for P in Ps]
+    return Ps, use
+
+
+def listed_cameras(Ps, n, name, exc, needed=None):
+    """A list of n [3, 4] cameras or None -> (float64[n, 12] with zeros at the None entries, int32[n]: 1 where there
+    is a camera).  `exc` is raised for an entry that is not [3, 4], and for a None entry where `needed` is not 0."""
+    have = np.array([P is not None for P in Ps], dtype=np.int32)
+    if needed is not None and any(u and not h for u, h in zip(needed, have)):
+        raise exc("%s must be [3,4] camera matrices." % name)
+    cams = np.zeros((n, 12))
+    for p, P in enumerate(Ps):
+        if P is None:
+            continue
+        P = np.asarray(P, dtype=np.float64)
+        if P.shape != (3, 4):
+            raise exc("%s must be [3,4] camera matrices." % name)
+        cams[p] = P.reshape(12)
+    return cams, have
+
+
+def seeds_and_tries(seeds, samples, maximum_tries, n):
+    """The subsets' arguments of spv_ransac_fit_batch: (seeds uint64[n] -- zeros by default, not looked at when
+    samples int32[n, ntries, 7] are given --, maximum_tries in [0, 7e8], which samples set to their ntries)."""
+    if samples is not None:
+        maximum_tries = samples.shape[1]
+    else:
+        seeds = np.zeros(n, np.uint64) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        if seeds.size != n:
+            raise ValueError("seeds must hold one value per set")
+    maximum_tries = int(maximum_tries)
+    if maximum_tries < 0 or maximum_tries > 700000000:
+        raise ValueError("maximum_tries must be in [0, 7e8]")
+    return seeds, maximum_tries
+
+
+def fit_dicts(off, ok, F, P, pct, idx, n, bt, br, ran):
+    """The per-set outputs of spv_ransac_fit_batch as one `ransac_fit` dict per set."""
+    out = []
+    for p in range(off.size - 1):
+        found = bt[p] >= 0
+        out.append({'success': bool(ok[p]), 'essential': F[p].reshape(3, 3).copy() if found else None,
+                    'camera': P[p].reshape(3, 4).copy() if found else None, 'inlier_percent': float(pct[p]),
+                    'inlier_idx': idx[off[p]:off[p] + n[p]].copy(), 'best_try': int(bt[p]), 'best_root': int(br[p]),
+                    'tries_run': int(ran[p])})
+    return out

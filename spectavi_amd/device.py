@@ -10,6 +10,7 @@ import ctypes as ct
 import numpy as np
 import torch
 
+from spectavi_amd import _collection as col
 from spectavi_amd._lib import clib, check
 
 
@@ -36,6 +37,10 @@ class _on_device_of:
 
     def __exit__(self, *exc):
         return self._ctx.__exit__(*exc)
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
 
 
 def _need(t, dtype, name):
@@ -259,19 +264,6 @@ def l1k2_plan(xrows, yrows, dim):
     return dict(dim_pad=out[0], q=out[1], slices=out[2], slice_rows=out[3], wide=bool(out[4]))
 
 
-def _seg_offsets(seg_off, total_rows, name):
-    """seg_off -> int64[nseg + 1]; ValueError for what check_offsets (collection.h) would reject or that does not
-    describe a table `name` of total_rows rows (None: any)."""
-    seg = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
-    if seg.size < 1 or seg[0] != 0 or np.any(np.diff(seg) < 0):
-        raise ValueError("seg_off must start at 0 and never decrease")
-    if total_rows is not None and int(seg[-1]) != int(total_rows):
-        raise ValueError("seg_off ends at %d, %s has %d rows" % (int(seg[-1]), name, int(total_rows)))
-    if int(seg[-1]) >= 2 ** 31:
-        raise ValueError("the sets must hold fewer than 2^31 rows in all")
-    return seg
-
-
 def _plan_items(fn, args, n_out, cols, want_items, at=0, tail=()):
     """The two calls of a plan entry fn(*args, out[n_out], *tail, items, items_cap): out as ints and, with
     want_items, the out[at] items as int32[items, cols] (else None)."""
@@ -284,25 +276,20 @@ def _plan_items(fn, args, n_out, cols, want_items, at=0, tail=()):
     return [int(v) for v in out], items
 
 
-def _batch_args(seg_off, pairs, total_rows, dim):
+def _collection_args(seg_off, pairs, total_rows, table, out32=False):
     """seg_off -> int64[nseg + 1], pairs -> int32[npairs, 2], out_off int64[npairs + 1]; ValueError for anything
-    spv_l1k2_batch_device would reject or that does not describe a table of total_rows rows."""
-    seg = _seg_offsets(seg_off, total_rows, "desc")
-    if dim <= 0 or dim % 16 != 0:
-        raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
-    if dim > 256:
-        raise ValueError("the many-pairs form takes dim <= 256 (dim=%d)" % dim)
-    prs = np.asarray(pairs)
-    if prs.size == 0:
-        prs = np.zeros((0, 2), np.int32)
-    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
-        raise ValueError("pairs must be integers of shape [npairs, 2]")
-    nseg = seg.size - 1
-    if prs.size and (int(prs.min()) < 0 or int(prs.max()) >= nseg):
-        raise ValueError("pairs name sets outside [0, %d)" % nseg)
-    prs = np.ascontiguousarray(prs, dtype=np.int32)
-    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]], dtype=np.int64)]).astype(np.int64)
-    return seg, prs, out_off
+    check_collection (collection.h; with out32, check_collection_out32) would reject or that does not describe a
+    `table` of total_rows rows (None: any)."""
+    seg = col.offsets(seg_off, "seg_off", total_rows, table)
+    prs = col.pair_table(pairs, seg.size - 1)
+    return seg, prs, col.out_offsets(seg, prs, out32)
+
+
+def _batch_args(seg_off, pairs, total_rows, dim):
+    """_collection_args of a matcher's descriptor table, whose rows are dim wide: the arguments of
+    spv_l1k2_batch_device."""
+    col.check_matcher_dim(dim)
+    return _collection_args(seg_off, pairs, total_rows, "desc")
 
 
 def l1k2_batch_plan(seg_off, pairs, dim, want_items=False):
@@ -415,19 +402,15 @@ def epipolar_lines_batch(geom, seg_off, pairs, G, use=None):
     `match_coordinates_batch` returns them.  A query point's line in the database view is therefore E^T x1, and for
     pixel coordinates with calibration K, G = (K^-T E K^-1)^T."""
     _need_geom(geom, None)
-    seg, prs, out_off = _batch_args(seg_off, pairs, geom.shape[0], 16)
+    seg, prs, out_off = _collection_args(seg_off, pairs, geom.shape[0], "geom")
     G = np.ascontiguousarray(G, dtype=np.float64).reshape(-1, 9) if np.size(G) else np.zeros((0, 9))
     if len(G) != len(prs):
         raise ValueError("G must hold one 3x3 matrix per pair (%d), got %d" % (len(prs), len(G)))
-    if use is not None:
-        use = np.ascontiguousarray(np.asarray(use).astype(bool), dtype=np.int32).reshape(-1)
-        if len(use) != len(prs):
-            raise ValueError("use must hold one flag per pair")
+    use = col.use_flags(use, len(prs), "pair")
     lines = torch.empty((int(out_off[-1]), 3), dtype=torch.float64, device=geom.device)
     with _on_device_of(geom) as stream:
         check(clib.spv_epipolar_lines_batch_device(geom.data_ptr(), seg.ctypes.data, seg.size - 1, prs.ctypes.data,
-                                                   len(prs), G.ctypes.data, None if use is None else use.ctypes.data,
-                                                   lines.data_ptr(), stream))
+                                                   len(prs), G.ctypes.data, _ptr(use), lines.data_ptr(), stream))
     return lines
 
 
@@ -809,16 +792,9 @@ def _fit_batch_args(pair_off, total, maximum_tries, seeds, samples):
     """pair_off -> int64[npairs + 1], samples -> int32[npairs, T, 7] or None, seeds -> uint64[npairs] or None,
     maximum_tries; ValueError for anything spv_ransac_fit_batch_device would reject or that does not describe
     arrays of `total` rows.  Touches no device."""
-    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
-    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
-        raise ValueError("pair_off must start at 0 and never decrease")
-    if int(off[-1]) != int(total):
-        raise ValueError("pair_off ends at %d, the arrays have %d rows" % (int(off[-1]), int(total)))
-    if int(off[-1]) >= 2 ** 31:
-        raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    off = col.offsets(pair_off, "pair_off", total, "x0")
     npairs = off.size - 1
-    if npairs > 2 ** 20:
-        raise ValueError("more than 2^20 sets per call")
+    col.check_set_count(npairs)
     npt = np.diff(off)
     if samples is not None:
         samples = np.asarray(samples)
@@ -827,30 +803,15 @@ def _fit_batch_args(pair_off, total, maximum_tries, seeds, samples):
         if samples.ndim != 3 or samples.shape[0] != npairs or samples.shape[2] != 7:
             raise ValueError("samples must be [npairs, ntries, 7]")
         samples = np.ascontiguousarray(samples, dtype=np.int32)
-        maximum_tries = samples.shape[1]
         runs = npt >= 10
         if samples[runs].size and (int(samples[runs].min()) < 0 or
                                    np.any(samples[runs].reshape(int(runs.sum()), -1).max(axis=1) >= npt[runs])):
             raise ValueError("a sample row lies outside its set")
-    else:
-        seeds = np.zeros(npairs, np.uint64) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
-        if seeds.size != npairs:
-            raise ValueError("seeds must hold one value per set")
-    maximum_tries = int(maximum_tries)
-    if maximum_tries < 0 or maximum_tries > 700000000:
-        raise ValueError("maximum_tries must be in [0, 7e8]")
+    seeds, maximum_tries = col.seeds_and_tries(seeds, samples, maximum_tries, npairs)
     return off, samples, seeds, maximum_tries
 
 
-def _fit_batch_dicts(off, ok, F, P, pct, idx, n, bt, br, ran):
-    out = []
-    for p in range(off.size - 1):
-        found = bt[p] >= 0
-        out.append({'success': bool(ok[p]), 'essential': F[p].reshape(3, 3).copy() if found else None,
-                    'camera': P[p].reshape(3, 4).copy() if found else None, 'inlier_percent': float(pct[p]),
-                    'inlier_idx': idx[off[p]:off[p] + n[p]].copy(), 'best_try': int(bt[p]), 'best_root': int(br[p]),
-                    'tries_run': int(ran[p])})
-    return out
+_fit_batch_dicts = col.fit_dicts   # the name tests/test_ransac_batch_rounds_gpu.py builds its rows with
 
 
 def ransac_fit_batch_plan(pair_off, maximum_tries=500, compute_units=256, want_items=False):
@@ -858,9 +819,7 @@ def ransac_fit_batch_plan(pair_off, maximum_tries=500, compute_units=256, want_i
     touched): dict of sets and tries in the round, items (work items = workgroups of the scorer) and row_blocks
     (blocks of 256 rows).  With want_items also the items, int32[items, 5] = (set, first row, rows, first
     candidate of the round, candidates)."""
-    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
-    if off.size < 1:
-        raise ValueError("pair_off must start at 0 and never decrease")
+    off = col.offsets_unchecked(pair_off, "pair_off")
     out, items = _plan_items(clib.spv_ransac_fit_batch_plan,
                              (off.ctypes.data, off.size - 1, int(maximum_tries), int(compute_units)), 4, 5, want_items, at=2)
     plan = dict(sets=out[0], tries=out[1], items=out[2], row_blocks=out[3])
@@ -891,11 +850,10 @@ def ransac_fit_batch(x0, x1, pair_off, required_percent_inliers=.9, reprojection
         check(clib.spv_ransac_fit_batch_device(
             x0.data_ptr(), x1.data_ptr(), off.ctypes.data, npairs, float(required_percent_inliers),
             float(reprojection_error_allowed), maximum_tries, int(bool(find_best_even_in_failure)),
-            float(singular_value_ratio_allowed), samples.ctypes.data if samples is not None else None,
-            seeds.ctypes.data if samples is None else None, ok.ctypes.data, F.ctypes.data, P.ctypes.data,
-            pct.ctypes.data, idx.ctypes.data, n.ctypes.data, bt.ctypes.data, br.ctypes.data, ran.ctypes.data,
-            mask.data_ptr() if want_mask else None, stream))
-    fits = _fit_batch_dicts(off, ok, F, P, pct, idx, n, bt, br, ran)
+            float(singular_value_ratio_allowed), _ptr(samples), seeds.ctypes.data if samples is None else None,
+            ok.ctypes.data, F.ctypes.data, P.ctypes.data, pct.ctypes.data, idx.ctypes.data, n.ctypes.data,
+            bt.ctypes.data, br.ctypes.data, ran.ctypes.data, mask.data_ptr() if want_mask else None, stream))
+    fits = col.fit_dicts(off, ok, F, P, pct, idx, n, bt, br, ran)
     return (fits, mask) if want_mask else fits
 
 
@@ -903,48 +861,20 @@ def _dlt_batch_args(pair_off, total, P1s, P0s, use):
     """pair_off -> int64[npairs + 1], P1s / P0s -> float64[npairs, 12] (P0s or None), use -> int32[npairs] or None;
     ValueError for anything spv_dlt_triangulate_batch_device would reject or that does not describe arrays of `total`
     rows.  A None entry of a P1s list is a skipped set.  Touches no device."""
-    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
-    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
-        raise ValueError("pair_off must start at 0 and never decrease")
-    if total is not None and int(off[-1]) != int(total):
-        raise ValueError("pair_off ends at %d, the arrays have %d rows" % (int(off[-1]), int(total)))
-    if int(off[-1]) >= 2 ** 31:
-        raise ValueError("the sets must hold fewer than 2^31 rows in all")
+    off = col.offsets(pair_off, "pair_off", total, "x0")
     npairs = off.size - 1
-    if npairs > 2 ** 20:
-        raise ValueError("more than 2^20 sets per call")
-    if use is not None:
-        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
-        if use.size != npairs:
-            raise ValueError("use must hold one value per set")
-    if not isinstance(P1s, np.ndarray) and any(P is None for P in P1s):
-        skip = np.array([P is None for P in P1s])
-        if len(skip) != npairs:
-            raise ValueError("P1s must hold one camera per set")
-        use = (~skip).astype(np.int32) if use is None else (use * ~skip).astype(np.int32)
-        P1s = [np.zeros((3, 4)) if P is None else P for P in P1s]
-
-    def cameras(Ps, name):
-        Ps = np.ascontiguousarray(Ps, dtype=np.float64).reshape(-1, 12) if npairs else np.zeros((0, 12))
-        if Ps.shape[0] != npairs:
-            raise ValueError("%s must hold one [3,4] camera per set" % name)
-        return Ps
-    return off, cameras(P1s, "P1s"), None if P0s is None else cameras(P0s, "P0s"), use
+    col.check_set_count(npairs)
+    P1s, use = col.none_cameras_skip(P1s, npairs, "P1s", col.use_flags(use, npairs))
+    return off, col.packed_cameras(P1s, npairs, "P1s"), None if P0s is None else col.packed_cameras(P0s, npairs, "P0s"), use
 
 
 def dlt_triangulate_batch_plan(pair_off, use=None, compute_units=256, want_items=False):
     """The work items dlt_triangulate_batch() launches for a collection (spv_dlt_triangulate_batch_plan; host only,
     no device touched): dict of sets (used sets), items (workgroup steps) and bound (rows of the used sets).  With
     want_items also the items, int32[items, 4] = (set, first row, rows, out row of the first row without a mask)."""
-    off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
-    if off.size < 1:
-        raise ValueError("pair_off must start at 0 and never decrease")
-    if use is not None:
-        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
-        if use.size != off.size - 1:
-            raise ValueError("use must hold one value per set")
-    u = use.ctypes.data if use is not None else None
-    out, items = _plan_items(clib.spv_dlt_triangulate_batch_plan, (off.ctypes.data, off.size - 1, u, int(compute_units)),
+    off = col.offsets_unchecked(pair_off, "pair_off")
+    use = col.use_flags(use, off.size - 1)
+    out, items = _plan_items(clib.spv_dlt_triangulate_batch_plan, (off.ctypes.data, off.size - 1, _ptr(use), int(compute_units)),
                              3, 4, want_items, at=1)
     plan = dict(sets=out[0], items=out[1], bound=out[2])
     return (plan, items) if want_items else plan
@@ -978,15 +908,14 @@ def dlt_triangulate_batch(x0, x1, pair_off, P1s, P0s=None, use=None, mask=None, 
     d_off = torch.empty(npairs + 1, dtype=torch.int64, device=x0.device) if mask is not None else None
     with _on_device_of(x0, x1, mask) as stream:
         check(clib.spv_dlt_triangulate_batch_device(
-            x0.data_ptr(), x1.data_ptr(), off.ctypes.data, npairs, P0s.ctypes.data if P0s is not None else None,
-            P1s.ctypes.data, use.ctypes.data if use is not None else None, mask.data_ptr() if mask is not None else None,
+            x0.data_ptr(), x1.data_ptr(), off.ctypes.data, npairs, _ptr(P0s), P1s.ctypes.data, _ptr(use),
+            mask.data_ptr() if mask is not None else None,
             X.data_ptr(), err.data_ptr() if want_error else None, rows.data_ptr() if want_rows else None, total,
             d_off.data_ptr() if mask is not None else None, None, stream))
     if mask is not None:
         out_off = d_off.cpu().numpy()
     else:
-        sizes = np.diff(off) if use is None else np.diff(off) * (use != 0)
-        out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        out_off = col.offsets_of(np.diff(off) if use is None else np.diff(off) * (use != 0))
     out = (X,) + ((err,) if want_error else ()) + ((rows,) if want_rows else ())
     return out + (out_off,)
 
@@ -999,9 +928,7 @@ def match_coordinates_batch(geom, seg_off, pairs, matches, count):
     arguments of `ransac_fit_batch`.  Reading pair_off back synchronises the current stream."""
     if geom.dim() != 2 or geom.shape[1] != 4 or matches.dim() != 2 or matches.shape[1] != 2:
         raise ValueError("geom must be [total_rows,4], matches [capacity,2]")
-    seg, prs, out_off = _batch_args(seg_off, pairs, geom.shape[0], 16)
-    if int(out_off[-1]) >= 2 ** 31:
-        raise ValueError("the pairs must own fewer than 2^31 out rows in all")
+    seg, prs, _ = _collection_args(seg_off, pairs, geom.shape[0], "geom", out32=True)
     _need(geom, torch.float32, "geom")
     _need(matches, torch.int32, "matches")
     _need(count, torch.int32, "count")
@@ -1019,9 +946,7 @@ def match_coordinates_batch(geom, seg_off, pairs, matches, count):
 def _tracks_batch_args(seg_off, pairs, capacity, min_len):
     """seg_off -> int64[nseg + 1], pairs -> int32[npairs, 2]; ValueError for anything spv_tracks_batch_device would
     reject, before any device is touched."""
-    seg, prs, out_off = _batch_args(seg_off, pairs, None, 16)
-    if int(out_off[-1]) >= 2 ** 31:
-        raise ValueError("the pairs must own fewer than 2^31 out rows in all")
+    seg, prs, _ = _collection_args(seg_off, pairs, None, None, out32=True)
     if int(capacity) < 0:
         raise ValueError("capacity must not be negative")
     if int(min_len) != min_len or int(min_len) < 2:
@@ -1098,21 +1023,10 @@ def tracks_triangulate_get_long():
     return int(clib.spv_tracks_triangulate_get_long())
 
 
-def _track_offsets(track_off, nmembers):
-    off = np.ascontiguousarray(track_off, dtype=np.int64).reshape(-1)
-    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
-        raise ValueError("track_off must start at 0 and never decrease")
-    if int(off[-1]) >= 2 ** 31:
-        raise ValueError("the tracks must hold fewer than 2^31 members in all")
-    if nmembers is not None and int(off[-1]) != int(nmembers):
-        raise ValueError("track_off ends at %d, members has %d rows" % (int(off[-1]), int(nmembers)))
-    return off
-
-
 def triangulate_tracks_plan(track_off):
     """Which form solves how many tracks under the current setting (spv_tracks_triangulate_plan; host only, no device
     touched): dict of lane_tracks, wave_tracks, lane_groups (workgroups of the lane launch) and longest."""
-    off = _track_offsets(track_off, None)
+    off = col.offsets(track_off, "track_off")
     out = (ct.c_longlong * 4)()
     check(clib.spv_tracks_triangulate_plan(off.ctypes.data, off.size - 1, out))
     return dict(lane_tracks=int(out[0]), wave_tracks=int(out[1]), lane_groups=int(out[2]), longest=int(out[3]))
@@ -1127,24 +1041,13 @@ def _tracks_triangulate_args(geom_shape, seg_off, cameras, track_off, members_sh
         raise ValueError("geom must be [total_rows, 4]")
     if len(members_shape) != 2 or members_shape[1] != 2:
         raise ValueError("members must be [nmembers, 2]")
-    seg = _seg_offsets(seg_off, geom_shape[0], "geom")
+    seg = col.offsets(seg_off, "seg_off", geom_shape[0], "geom")
     nseg = seg.size - 1
-    off = _track_offsets(track_off, members_shape[0])
-    if use is not None:
-        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
-        if use.size != nseg:
-            raise ValueError("use must hold one value per set")
-    if not isinstance(cameras, np.ndarray) and any(P is None for P in cameras):
-        skip = np.array([P is None for P in cameras])
-        if len(skip) != nseg:
-            raise ValueError("cameras must hold one [3,4] camera per set")
-        use = (~skip).astype(np.int32) if use is None else (use * ~skip).astype(np.int32)
-        cameras = [np.zeros((3, 4)) if P is None else P for P in cameras]
+    off = col.offsets(track_off, "track_off", members_shape[0], "members")
+    cameras, use = col.none_cameras_skip(cameras, nseg, "cameras", col.use_flags(use, nseg))
     try:
-        cams = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 12) if nseg else np.zeros((0, 12))
+        cams = col.packed_cameras(cameras, nseg, "cameras")
     except (TypeError, ValueError):
-        raise ValueError("cameras must hold one [3,4] camera per set")
-    if cams.shape[0] != nseg:
         raise ValueError("cameras must hold one [3,4] camera per set")
     max_error = float(max_error)
     if max_error != max_error:
@@ -1182,9 +1085,9 @@ def triangulate_tracks(geom, seg_off, cameras, track_off, members, max_error=flo
     nused = torch.empty(nt, dtype=torch.int32, device=dev)
     with _on_device_of(geom, members) as stream:
         check(clib.spv_tracks_triangulate_device(
-            geom.data_ptr(), seg.ctypes.data, seg.size - 1, cams.ctypes.data, use.ctypes.data if use is not None else None,
-            off.ctypes.data, nt, members.data_ptr(), nm, max_error, X.data_ptr(), err.data_ptr() if want_err else None,
-            ok.data_ptr(), nused.data_ptr(), stream))
+            geom.data_ptr(), seg.ctypes.data, seg.size - 1, cams.ctypes.data, _ptr(use), off.ctypes.data, nt,
+            members.data_ptr(), nm, max_error, X.data_ptr(), err.data_ptr() if want_err else None, ok.data_ptr(),
+            nused.data_ptr(), stream))
     return X, err, ok, nused
 
 
@@ -1212,7 +1115,7 @@ NORMALIZE_F32, NORMALIZE_U8 = 0, 1  # SPV_NORMALIZE_* of include/spectavi_amd.h
 def _normalize_batch_args(seg_off, total_rows, dim, dtype):
     """seg_off -> int64[nseg + 1], dtype -> SPV_NORMALIZE_*; ValueError for anything spv_normalize_batch_device would
     reject or that does not describe a table of total_rows rows.  Touches no device."""
-    seg = _seg_offsets(seg_off, total_rows, "x")
+    seg = col.offsets(seg_off, "seg_off", total_rows, "x")
     if not 1 <= int(dim) <= 2048:
         raise ValueError("the many-tables form takes 1 <= dim <= 2048 (dim=%d)" % dim)
     if dim == 1 and np.any(np.diff(seg) > 1):
@@ -1323,32 +1226,15 @@ def _rectify_batch_args(sizes, pairs, P1s, P0s, use, box=None):
     sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1, 2)
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
     npairs = len(pairs)
-    if use is not None:
-        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.int32).reshape(-1)
-        if use.size != npairs:
-            raise ValueError("use must hold one value per pair")
-    if P1s is not None and not isinstance(P1s, np.ndarray) and any(P is None for P in P1s):
-        skip = np.array([P is None for P in P1s])
-        if len(skip) != npairs:
-            raise ValueError("P1s must hold one camera per pair")
-        use = (~skip).astype(np.int32) if use is None else (use * ~skip).astype(np.int32)
-        P1s = [np.zeros((3, 4)) if P is None else P for P in P1s]
-
-    def cameras(Ps, name):
-        Ps = np.ascontiguousarray(Ps, dtype=np.float64).reshape(-1, 12) if npairs else np.zeros((0, 12))
-        if Ps.shape[0] != npairs:
-            raise ValueError("%s must hold one [3,4] camera per pair" % name)
-        return Ps
+    use = col.use_flags(use, npairs, "pair")
+    if P1s is not None:
+        P1s, use = col.none_cameras_skip(P1s, npairs, "P1s", use, "pair")
+        P1s = col.packed_cameras(P1s, npairs, "P1s", "pair")
     if box is not None:
         box = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 4)
         if len(box) != npairs:
             raise ValueError("box must hold one (row_lo, row_hi, col_lo, col_hi) per pair")
-    return (sizes, pairs, None if P1s is None else cameras(P1s, "P1s"), None if P0s is None else cameras(P0s, "P0s"),
-            use, box)
-
-
-def _ptr(a):
-    return a.ctypes.data if a is not None else None
+    return sizes, pairs, P1s, None if P0s is None else col.packed_cameras(P0s, npairs, "P0s", "pair"), use, box
 
 
 def rectify_batch_plan(sizes, pairs, nchan=1, sampling_factor=1.2, use=None, box=None, want_items=False):
@@ -1536,13 +1422,6 @@ def sift_batch_plan(sizes, ws_bytes=0, want_groups=False):
     return (plan, groups) if want_groups else plan
 
 
-def _offsets(off, n, name):
-    off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
-    if off.size != n + 1 or off[0] != 0 or np.any(np.diff(off) < 0) or int(off[-1]) >= 2 ** 31:
-        raise ValueError("%s must be [nimg + 1], start at 0, never decrease and end below 2^31" % name)
-    return off
-
-
 def sift_batch_into(images, sizes, table, cap_off, counts, workspace=None):
     """vlfeat-exact SIFT of many images in one chain of launches (spv_sift_batch_device): images float32 CUDA
     tensor holding the images back to back, image i row-major [hgt_i, wid_i] with sizes[i] = (wid_i, hgt_i);
@@ -1551,7 +1430,7 @@ def sift_batch_into(images, sizes, table, cap_off, counts, workspace=None):
     a Workspace, or a uint8 CUDA tensor whose size decides the groups (at least sift_batch_plan's
     min_workspace_bytes).  Asynchronous on the current stream but for the upload of the per-image table."""
     sz = _sift_sizes(sizes)
-    cap = _offsets(cap_off, len(sz), "cap_off")
+    cap = col.offsets(cap_off, "cap_off", count=len(sz))
     _need(images, torch.float32, "images")
     _need(table, torch.float32, "table")
     _need(counts, torch.int32, "counts")
@@ -1576,8 +1455,8 @@ def sift_batch_pack(table, cap_off, seg_off, want_packed=True, want_split=False)
     as split_sift_table gives them."""
     _need(table, torch.float32, "table")
     seg = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
-    cap = _offsets(cap_off, seg.size - 1, "cap_off")
-    seg = _offsets(seg, seg.size - 1, "seg_off")
+    cap = col.offsets(cap_off, "cap_off", count=seg.size - 1)
+    seg = col.offsets(seg, "seg_off")
     total = int(seg[-1])
     packed = torch.empty((total, 132), dtype=torch.float32, device=table.device) if want_packed else None
     geom = torch.empty((total, 4), dtype=torch.float32, device=table.device) if want_split else None
@@ -1618,7 +1497,7 @@ def sift_batch(images, capacity=None, workspace=None, max_workspace_bytes=None, 
     def run(which, caps):
         """(table, cap_off, counts on the host) of images[which] with the capacities caps."""
         flat = torch.cat([images[i].to(torch.float32).reshape(-1) for i in which])
-        cap_off = np.concatenate([[0], np.cumsum(caps, dtype=np.int64)]).astype(np.int64)
+        cap_off = col.offsets_of(caps)
         table = torch.empty((int(cap_off[-1]), 132), dtype=torch.float32, device=dev)
         counts = torch.zeros(len(which), dtype=torch.int32, device=dev)
         ws = workspace
@@ -1632,7 +1511,7 @@ def sift_batch(images, capacity=None, workspace=None, max_workspace_bytes=None, 
 
     every = list(range(n))
     table, cap_off, counts = run(every, caps)
-    seg_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    seg_off = col.offsets_of(counts)
     short = [i for i in every if counts[i] > caps[i]]
     if not short:
         out = sift_batch_pack(table, cap_off, seg_off, want_packed=not want_split, want_split=want_split)
@@ -1640,7 +1519,7 @@ def sift_batch(images, capacity=None, workspace=None, max_workspace_bytes=None, 
     # the complete regions packed, the short images again with exact capacities, each into its place
     fit = counts.copy()
     fit[short] = 0
-    part_off = np.concatenate([[0], np.cumsum(fit)]).astype(np.int64)
+    part_off = col.offsets_of(fit)
     table2, cap_off2, counts2 = run(short, [int(counts[i]) for i in short])
     assert np.array_equal(counts2, counts[short])
     parts = sift_batch_pack(table, cap_off, part_off, want_packed=not want_split, want_split=want_split)

@@ -10,6 +10,7 @@ import ctypes as ct
 
 import numpy as np
 
+from spectavi_amd import _collection as col
 from spectavi_amd._lib import clib, check
 from spectavi_amd.ndarray import NdArray
 
@@ -47,6 +48,25 @@ def nn_bruteforcel1k2(x, y, nthreads=1):
     return nn_idx.asarray(), nn_dist.asarray()
 
 
+def _table_width(tables, dtype, what):
+    """dim of a non-empty list of `dtype` arrays [rows_i, dim]; ValueError where they are not that."""
+    if not tables:
+        raise ValueError("no tables")
+    dim = tables[0].shape[1] if tables[0].ndim == 2 else -1
+    if any(t.ndim != 2 or t.dtype != dtype or t.shape[1] != dim for t in tables):
+        raise ValueError("tables must be %s arrays [rows, dim] of one width" % what)
+    return dim
+
+
+def _tables_and_pairs(tables, pairs):
+    """(n, seg_off int64[n + 1], pairs int32[npairs, 2] -- None: col.all_pairs --, out_off int64[npairs + 1]) of a
+    list of tables that a many-pairs matcher stores back to back."""
+    n = len(tables)
+    prs = col.pair_table(col.all_pairs(n) if pairs is None else pairs, n, "tables")
+    seg = col.offsets_of([len(t) for t in tables])
+    return n, seg, prs, col.out_offsets(seg, prs)
+
+
 def nn_bruteforcel1k2_batch(tables, pairs=None):
     """
     nn_bruteforcel1k2 for many pairs of descriptor tables in one call (an addition: the reference has no
@@ -59,34 +79,15 @@ def nn_bruteforcel1k2_batch(tables, pairs=None):
     concatenated output, row within the database table).
     """
     tables = [np.ascontiguousarray(t) for t in tables]
-    if not tables:
-        raise ValueError("no tables")
-    dim = tables[0].shape[1] if tables[0].ndim == 2 else -1
-    if any(t.ndim != 2 or t.dtype != np.uint8 or t.shape[1] != dim for t in tables):
-        raise ValueError("tables must be uint8 arrays [rows, dim] of one width")
-    if dim <= 0 or dim % 16 != 0:
-        raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
-    if dim > 256:
-        raise ValueError("the many-pairs form takes dim <= 256 (dim=%d)" % dim)
-    n = len(tables)
-    if pairs is None:
-        pairs = [(j, i) for i in range(n) for j in range(i + 1, n)]
-    prs = np.asarray(pairs)
-    if prs.size == 0:
-        prs = np.zeros((0, 2), np.int32)
-    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
-        raise ValueError("pairs must be integers of shape [npairs, 2]")
-    if prs.size and (prs.min() < 0 or prs.max() >= n):
-        raise ValueError("pairs name tables outside [0, %d)" % n)
-    prs = np.ascontiguousarray(prs, dtype=np.int32)
-    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    dim = _table_width(tables, np.uint8, "uint8")
+    col.check_matcher_dim(dim)
+    n, seg, prs, out_off = _tables_and_pairs(tables, pairs)
     desc = np.concatenate(tables) if seg[-1] else np.zeros((0, dim), np.uint8)
-    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
     idx = np.empty((int(out_off[-1]), 2), np.uint64)
     dist = np.empty((int(out_off[-1]), 2), np.int32)
     check(clib.spv_nn_bruteforcel1k2_batch(desc.ctypes.data, seg.ctypes.data, n, dim, prs.ctypes.data, len(prs),
                                            idx.ctypes.data, dist.ctypes.data))
-    return [(idx[a:b], dist[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
+    return col.per_pair(out_off, idx, dist)
 
 
 def nn_bruteforcel1k2_guided_batch(tables, geoms, lines, max_dist, pairs=None):
@@ -103,33 +104,15 @@ def nn_bruteforcel1k2_guided_batch(tables, geoms, lines, max_dist, pairs=None):
     """
     tables = [np.ascontiguousarray(t) for t in tables]
     geoms = [np.ascontiguousarray(g) for g in geoms]
-    if not tables:
-        raise ValueError("no tables")
-    if any(t.ndim != 2 or t.dtype != np.uint8 for t in tables):
-        raise ValueError("tables must be uint8 arrays [rows, dim] of one width")
-    dim = tables[0].shape[1]
-    if any(t.shape[1] != dim for t in tables):
-        raise ValueError("tables must be uint8 arrays [rows, dim] of one width")
+    dim = _table_width(tables, np.uint8, "uint8")
     if dim != 128:
         raise ValueError("the guided L1 2-NN takes dim 128 only (dim=%d)" % dim)
     if len(geoms) != len(tables) or any(g.ndim != 2 or g.dtype != np.float32 or g.shape != (len(t), 4)
                                         for g, t in zip(geoms, tables)):
         raise ValueError("geoms must be float32 arrays [rows, 4], one per table")
-    n = len(tables)
-    if pairs is None:
-        pairs = [(j, i) for i in range(n) for j in range(i + 1, n)]
-    prs = np.asarray(pairs)
-    if prs.size == 0:
-        prs = np.zeros((0, 2), np.int32)
-    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
-        raise ValueError("pairs must be integers of shape [npairs, 2]")
-    if prs.size and (prs.min() < 0 or prs.max() >= n):
-        raise ValueError("pairs name tables outside [0, %d)" % n)
-    prs = np.ascontiguousarray(prs, dtype=np.int32)
-    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    n, seg, prs, out_off = _tables_and_pairs(tables, pairs)
     desc = np.concatenate(tables) if seg[-1] else np.zeros((0, dim), np.uint8)
     geom = np.concatenate(geoms) if seg[-1] else np.zeros((0, 4), np.float32)
-    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
     rows = int(out_off[-1])
     if isinstance(lines, (list, tuple)):
         lines = np.concatenate([np.asarray(l, np.float64).reshape(-1, 3) for l in lines]) if lines else np.zeros((0, 3))
@@ -142,7 +125,7 @@ def nn_bruteforcel1k2_guided_batch(tables, geoms, lines, max_dist, pairs=None):
     check(clib.spv_nn_bruteforcel1k2_guided_batch(desc.ctypes.data, geom.ctypes.data, seg.ctypes.data, n, dim,
                                                   prs.ctypes.data, len(prs), lines.ctypes.data, float(max_dist),
                                                   idx.ctypes.data, dist.ctypes.data, ncand.ctypes.data))
-    return [(idx[a:b], dist[a:b], ncand[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
+    return col.per_pair(out_off, idx, dist, ncand)
 
 
 def match_tracks_batch(sizes, pairs, matches, masks=None, min_len=2):
@@ -158,24 +141,9 @@ def match_tracks_batch(sizes, pairs, matches, masks=None, min_len=2):
     uint8 [ntracks]): track t owns members[track_off[t]:track_off[t + 1]], ascending by table and row; tracks are
     in ascending order of their first member; bit 0 of flags[t] is set iff the track holds two keypoints of one table.
     """
-    sizes = np.asarray(sizes)
-    if sizes.ndim != 1 or (sizes.size and (sizes.dtype.kind not in "iu" or sizes.min() < 0)):
-        raise ValueError("sizes must be non-negative integers, one per table")
-    n = len(sizes)
-    seg = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
-    if int(seg[-1]) >= 2 ** 31:
-        raise ValueError("the tables must hold fewer than 2^31 rows in all")
-    prs = np.asarray(pairs)
-    if prs.size == 0:
-        prs = np.zeros((0, 2), np.int32)
-    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
-        raise ValueError("pairs must be integers of shape [npairs, 2]")
-    if prs.size and (prs.min() < 0 or prs.max() >= n):
-        raise ValueError("pairs name tables outside [0, %d)" % n)
-    prs = np.ascontiguousarray(prs, dtype=np.int32)
-    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
-    if int(out_off[-1]) >= 2 ** 31:
-        raise ValueError("the pairs must own fewer than 2^31 out rows in all")
+    n, seg = col.offsets_of_sizes(sizes, "table")
+    prs = col.pair_table(pairs, n, "tables")
+    out_off = col.out_offsets(seg, prs, below_2_31=True)
     if int(min_len) != min_len or int(min_len) < 2:
         raise ValueError("min_len must be an integer >= 2: a track has at least two members")
     if len(matches) != len(prs) or (masks is not None and len(masks) != len(prs)):
@@ -467,45 +435,24 @@ def nn_cascading_hash_batch(tables, hash_dict, pairs=None, g=2, return_ncand=Fal
     """
     tables = [np.ascontiguousarray(t, dtype=np.float32) for t in tables]
     hash_dict = np.ascontiguousarray(hash_dict, dtype=np.float32)
-    if not tables:
-        raise ValueError("no tables")
-    dim = tables[0].shape[1] if tables[0].ndim == 2 else -1
-    if any(t.ndim != 2 or t.shape[1] != dim for t in tables):
-        raise ValueError("tables must be float32 arrays [rows, dim] of one width")
+    dim = _table_width(tables, np.float32, "float32")
     if hash_dict.ndim != 3 or hash_dict.shape[1] != dim:
         raise ValueError("hash_dict must be float32 [n, dim, m] of the tables' width")
-    if dim <= 0 or dim % 16 != 0:
-        raise ValueError("Input matrix inner dimensions must be 16-byte aligned.")
-    if dim > 256:
-        raise ValueError("the many-pairs form takes dim <= 256 (dim=%d)" % dim)
+    col.check_matcher_dim(dim)
     ntab, _, m = hash_dict.shape
     if not 1 <= m <= 31:
         raise ValueError("hash bit rate m must be in [1, 31]")
     if ntab < 1 or not 0 <= g <= min(m, 16):
         raise ValueError("need n >= 1 and 0 <= g <= min(m, 16)")
-    n = len(tables)
-    if pairs is None:
-        pairs = [(j, i) for i in range(n) for j in range(i + 1, n)]
-    prs = np.asarray(pairs)
-    if prs.size == 0:
-        prs = np.zeros((0, 2), np.int32)
-    if prs.ndim != 2 or prs.shape[1] != 2 or prs.dtype.kind not in "iu":
-        raise ValueError("pairs must be integers of shape [npairs, 2]")
-    if prs.size and (prs.min() < 0 or prs.max() >= n):
-        raise ValueError("pairs name tables outside [0, %d)" % n)
-    prs = np.ascontiguousarray(prs, dtype=np.int32)
-    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    n, seg, prs, out_off = _tables_and_pairs(tables, pairs)
     rows = np.concatenate(tables) if seg[-1] else np.zeros((0, dim), np.float32)
-    out_off = np.concatenate([[0], np.cumsum(np.diff(seg)[prs[:, 0]])]).astype(np.int64)
     idx = np.empty((int(out_off[-1]), 2), np.uint64)
     dist = np.empty((int(out_off[-1]), 2), np.float32)
     ncand = np.zeros(int(out_off[-1]), np.int32)
     check(clib.spv_nn_cascading_hash_batch(rows.ctypes.data, seg.ctypes.data, n, dim, m, ntab, g, prs.ctypes.data,
                                            len(prs), hash_dict.ctypes.data, idx.ctypes.data, dist.ctypes.data,
                                            ncand.ctypes.data if return_ncand else None))
-    if return_ncand:
-        return [(idx[a:b], dist[a:b], ncand[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
-    return [(idx[a:b], dist[a:b]) for a, b in zip(out_off[:-1], out_off[1:])]
+    return col.per_pair(out_off, idx, dist, ncand) if return_ncand else col.per_pair(out_off, idx, dist)
 
 
 # ==================================================================================
@@ -619,15 +566,14 @@ def normalize_to_ubyte_and_multiple_16_dim_batch(tables, want_ubyte=False):
         raise ValueError("tables must be arrays [rows, dim] of one width, all float32 or all uint8")
     if not 1 <= dim <= 2048:
         raise ValueError("the many-tables form takes 1 <= dim <= 2048 (dim=%d)" % dim)
-    seg = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    seg = col.offsets_of([len(t) for t in tables])
     x = np.concatenate(tables)
     dim16 = (dim + 15) // 16 * 16
     out = np.empty((int(seg[-1]), dim16), np.float32)
     u8 = np.empty((int(seg[-1]), dim16), np.uint8) if want_ubyte else None
     check(clib.spv_normalize_batch(x.ctypes.data, int(dtype == np.uint8), seg.ctypes.data, len(tables), dim,
                                    out.ctypes.data, u8.ctypes.data if want_ubyte else None))
-    cut = list(zip(seg[:-1], seg[1:]))
-    return [(out[a:b], u8[a:b]) for a, b in cut] if want_ubyte else [out[a:b] for a, b in cut]
+    return col.per_pair(seg, out, u8) if want_ubyte else [o for o, in col.per_pair(seg, out)]
 
 
 # ==================================================================================

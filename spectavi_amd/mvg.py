@@ -10,6 +10,7 @@ import ctypes as ct
 
 import numpy as np
 
+from spectavi_amd import _collection as col
 from spectavi_amd._lib import clib, check
 from spectavi_amd.ndarray import NdArray
 
@@ -306,6 +307,22 @@ def ransac_fit(x0, x1, required_percent_inliers=.9, reprojection_error_allowed=.
 _spv_ransac_fit_batch = clib.spv_ransac_fit_batch
 
 
+def _coordinate_sets(x0s, x1s):
+    """Two lists of float64 [npt_p, 3] arrays, set for set of one shape (TypeError otherwise) -> (the sets of x0s, x0
+    and x1 [total, 3] with the sets back to back, npairs, off int64[npairs + 1], total) under the rules of
+    spv_ransac_fit_batch and spv_dlt_triangulate_batch."""
+    a0 = [np.ascontiguousarray(x, dtype=np.float64) for x in x0s]
+    a1 = [np.ascontiguousarray(x, dtype=np.float64) for x in x1s]
+    for u, v in zip(a0, a1):
+        if not (u.ndim == 2 and u.shape == v.shape and u.shape[1] == 3):
+            raise TypeError('Coords must be homogenous [npt,3] pairs.')
+    off = col.offsets(col.offsets_of([len(u) for u in a0]), "the sets' offsets")
+    col.check_set_count(len(a0))
+    total = int(off[-1])
+    return (a0, np.concatenate(a0) if total else np.zeros((0, 3)), np.concatenate(a1) if total else np.zeros((0, 3)),
+            len(a0), off, total)
+
+
 def ransac_fit_batch(x0s, x1s, required_percent_inliers=.9, reprojection_error_allowed=.5, maximum_tries=500,
                      find_best_even_in_failure=True, singular_value_ratio_allowed=3e-2, seeds=None, samples=None):
     """
@@ -319,20 +336,7 @@ def ransac_fit_batch(x0s, x1s, required_percent_inliers=.9, reprojection_error_a
     """
     if len(x0s) != len(x1s):
         raise ValueError('x0s and x1s must hold one array per set each.')
-    a0 = [np.ascontiguousarray(x, dtype=np.float64) for x in x0s]
-    a1 = [np.ascontiguousarray(x, dtype=np.float64) for x in x1s]
-    for u, v in zip(a0, a1):
-        if not (u.ndim == 2 and u.shape == v.shape and u.shape[1] == 3):
-            raise TypeError('Coords must be homogenous [npt,3] pairs.')
-    npairs = len(a0)
-    off = np.concatenate([[0], np.cumsum([len(u) for u in a0])]).astype(np.int64)
-    total = int(off[-1])
-    if total >= 2 ** 31:
-        raise ValueError('the sets must hold fewer than 2^31 rows in all')
-    if npairs > 2 ** 20:
-        raise ValueError('more than 2^20 sets per call')
-    x0 = np.concatenate(a0) if total else np.zeros((0, 3))
-    x1 = np.concatenate(a1) if total else np.zeros((0, 3))
+    a0, x0, x1, npairs, off, total = _coordinate_sets(x0s, x1s)
     if samples is not None:
         if len(samples) != npairs:
             raise ValueError('samples must hold one [ntries,7] array per set.')
@@ -344,14 +348,7 @@ def ransac_fit_batch(x0s, x1s, required_percent_inliers=.9, reprojection_error_a
             if len(a0[p]) >= 10 and s.size and (s.min() < 0 or s.max() >= len(a0[p])):
                 raise ValueError('a sample row lies outside its set')
         samples = np.ascontiguousarray(np.stack(rows) if npairs else np.zeros((0, 0, 7)), dtype=np.int32)
-        maximum_tries = ntries
-    else:
-        seeds = np.zeros(npairs, np.uint64) if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
-        if seeds.size != npairs:
-            raise ValueError('seeds must hold one value per set')
-    maximum_tries = int(maximum_tries)
-    if maximum_tries < 0 or maximum_tries > 700000000:
-        raise ValueError('maximum_tries must be in [0, 7e8]')
+    seeds, maximum_tries = col.seeds_and_tries(seeds, samples, maximum_tries, npairs)
     ok, n, bt, br, ran = (np.zeros(npairs, np.int32) for _ in range(5))
     pct, F, P, idx = np.zeros(npairs), np.zeros((npairs, 9)), np.zeros((npairs, 12)), np.zeros(total, np.int32)
     check(_spv_ransac_fit_batch(x0.ctypes.data, x1.ctypes.data, off.ctypes.data, npairs, float(required_percent_inliers),
@@ -361,14 +358,7 @@ def ransac_fit_batch(x0s, x1s, required_percent_inliers=.9, reprojection_error_a
                                 seeds.ctypes.data if samples is None else None, ok.ctypes.data, F.ctypes.data,
                                 P.ctypes.data, pct.ctypes.data, idx.ctypes.data, n.ctypes.data, bt.ctypes.data,
                                 br.ctypes.data, ran.ctypes.data))
-    out = []
-    for p in range(npairs):
-        found = bt[p] >= 0
-        out.append({'success': bool(ok[p]), 'essential': F[p].reshape(3, 3).copy() if found else None,
-                    'camera': P[p].reshape(3, 4).copy() if found else None, 'inlier_percent': float(pct[p]),
-                    'inlier_idx': idx[off[p]:off[p] + n[p]].copy(), 'best_try': int(bt[p]), 'best_root': int(br[p]),
-                    'tries_run': int(ran[p])})
-    return out
+    return col.fit_dicts(off, ok, F, P, pct, idx, n, bt, br, ran)
 
 
 _spv_dlt_triangulate_batch = clib.spv_dlt_triangulate_batch
@@ -388,38 +378,11 @@ def dlt_triangulate_batch(P1s, x0s, x1s, P0s=None, masks=None, ret_error=False):
     """
     if not (len(x0s) == len(x1s) == len(P1s)):
         raise ValueError('P1s, x0s and x1s must hold one entry per set each.')
-    a0 = [np.ascontiguousarray(x, dtype=np.float64) for x in x0s]
-    a1 = [np.ascontiguousarray(x, dtype=np.float64) for x in x1s]
-    for u, v in zip(a0, a1):
-        if not (u.ndim == 2 and u.shape == v.shape and u.shape[1] == 3):
-            raise TypeError('Coords must be homogenous [npt,3] pairs.')
-    npairs = len(a0)
-    off = np.concatenate([[0], np.cumsum([len(u) for u in a0])]).astype(np.int64)
-    total = int(off[-1])
-    if total >= 2 ** 31:
-        raise ValueError('the sets must hold fewer than 2^31 rows in all')
-    if npairs > 2 ** 20:
-        raise ValueError('more than 2^20 sets per call')
-    use = np.array([P is not None for P in P1s], dtype=np.int32)
-
-    def cameras(Ps, name):
-        out = np.zeros((npairs, 12))
-        for p, P in enumerate(Ps):
-            if P is None:
-                continue
-            P = np.asarray(P, dtype=np.float64)
-            if P.shape != (3, 4):
-                raise TypeError('%s must be camera matrices.' % name)
-            out[p] = P.reshape(12)
-        return out
-    c1 = cameras(P1s, 'P1s')
-    c0 = None
-    if P0s is not None:
-        if len(P0s) != npairs:
-            raise ValueError('P0s must hold one camera per set.')
-        if any(P is None for P, u in zip(P0s, use) if u):
-            raise TypeError('P0s must be camera matrices.')
-        c0 = cameras(P0s, 'P0s')
+    a0, x0, x1, npairs, off, total = _coordinate_sets(x0s, x1s)
+    c1, use = col.listed_cameras(P1s, npairs, 'P1s', TypeError)
+    if P0s is not None and len(P0s) != npairs:
+        raise ValueError('P0s must hold one camera per set.')
+    c0 = None if P0s is None else col.listed_cameras(P0s, npairs, 'P0s', TypeError, needed=use)[0]
     mask = None
     if masks is not None:
         if len(masks) != npairs:
@@ -432,8 +395,6 @@ def dlt_triangulate_batch(P1s, x0s, x1s, P0s=None, masks=None, ret_error=False):
             if m.size != len(a0[p]):
                 raise ValueError('a mask must hold one value per row of its set')
             mask[off[p]:off[p + 1]] = m != 0
-    x0 = np.concatenate(a0) if total else np.zeros((0, 3))
-    x1 = np.concatenate(a1) if total else np.zeros((0, 3))
     X = np.empty((total, 4))
     err = np.empty(total) if ret_error else None
     out_off = np.zeros(npairs + 1, np.int64)
@@ -471,41 +432,20 @@ def triangulate_tracks(coords, sizes, cameras, track_off, members, max_error=flo
             raise ValueError('coords must hold one [n, >=2] array per view.')
     if sizes is None:
         sizes = [len(a) for a in arrs]
-    sizes = np.asarray(sizes)
-    if sizes.ndim != 1 or (sizes.size and (sizes.dtype.kind not in 'iu' or sizes.min() < 0)):
-        raise ValueError('sizes must be non-negative integers, one per view.')
-    nseg = len(sizes)
-    if len(arrs) != nseg or any(len(a) != n for a, n in zip(arrs, sizes)):
+    nseg, seg = col.offsets_of_sizes(sizes, 'view')
+    if len(arrs) != nseg or any(len(a) != n for a, n in zip(arrs, np.diff(seg))):
         raise ValueError('coords must hold sizes[v] rows for every view.')
-    seg = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
-    if int(seg[-1]) >= 2 ** 31:
-        raise ValueError('the views must hold fewer than 2^31 rows in all.')
     if len(cameras) != nseg:
         raise ValueError('cameras must hold one entry per view.')
-    usable = np.array([P is not None for P in cameras], dtype=np.int32)
+    cams, usable = col.listed_cameras(cameras, nseg, 'cameras', ValueError)
     if use is not None:
-        use = np.asarray(use).reshape(-1)
-        if use.size != nseg:
-            raise ValueError('use must hold one value per view.')
-        usable = (usable * (use != 0)).astype(np.int32)
-    cams = np.zeros((nseg, 12))
-    for v, P in enumerate(cameras):
-        if P is None:
-            continue
-        P = np.asarray(P, dtype=np.float64)
-        if P.shape != (3, 4):
-            raise ValueError('cameras must be [3,4] matrices.')
-        cams[v] = P.reshape(12)
-    off = np.ascontiguousarray(track_off, dtype=np.int64).reshape(-1)
-    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
-        raise ValueError('track_off must start at 0 and never decrease.')
+        usable = usable * col.use_flags(use, nseg, 'view')
     mem = np.asarray(members)
     if mem.size == 0:
         mem = np.zeros((0, 2), np.int32)
     if mem.ndim != 2 or mem.shape[1] != 2 or mem.dtype.kind not in 'iu':
         raise ValueError('members must be integers of shape [nmembers, 2].')
-    if int(off[-1]) != len(mem) or len(mem) >= 2 ** 31:
-        raise ValueError('track_off must end at the rows of members, fewer than 2^31.')
+    off = col.offsets(track_off, 'track_off', len(mem), 'members')
     mem = np.ascontiguousarray(np.clip(mem, -1, 2 ** 31 - 1), dtype=np.int32)
     max_error = float(max_error)
     if max_error != max_error:
@@ -632,24 +572,8 @@ def image_pair_rectification_batch(ims, pairs, P1s, P0s=None, sampling_factor=1.
         if 0 <= a < len(ims) and 0 <= b < len(ims) and ims[a].shape != ims[b].shape:
             raise TypeError("Input images must have same size.")
     sizes = np.array([(d[1], d[0]) for d in dims], dtype=np.int32).reshape(-1, 2)
-    use = np.array([P is not None for P in P1s], dtype=np.int32)
-
-    def cameras(Ps, name):
-        out = np.zeros((npairs, 12))
-        for p, P in enumerate(Ps):
-            if P is None:
-                continue
-            P = np.asarray(P, dtype=np.float64)
-            if P.shape != (3, 4):
-                raise TypeError('%s must be camera matrices.' % name)
-            out[p] = P.reshape(12)
-        return out
-    c1 = cameras(P1s, 'P1s')
-    c0 = None
-    if P0s is not None:
-        if any(P is None for P, u in zip(P0s, use) if u):
-            raise TypeError('P0s must be camera matrices.')
-        c0 = cameras(P0s, 'P0s')
+    c1, use = col.listed_cameras(P1s, npairs, 'P1s', TypeError)
+    c0 = None if P0s is None else col.listed_cameras(P0s, npairs, 'P0s', TypeError, needed=use)[0]
     packed = np.concatenate([im.reshape(-1) for im in ims]) if ims else np.zeros(0, dtype)
     r0, r1 = NdArray(dtype=dtype), NdArray(dtype=dtype)
     ri0, ri1 = NdArray(dtype='int32'), NdArray(dtype='int32')

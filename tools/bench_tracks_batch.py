@@ -156,7 +156,7 @@ def main():
     matches, tmask = torch.from_numpy(m).cuda(), torch.from_numpy(mask).cuda()
     count = torch.tensor([len(m)], dtype=torch.int32).cuda()
     seg_t = torch.from_numpy(seg).cuda()
-    out_off_t = torch.from_numpy(np.concatenate([[0], np.cumsum(np.diff(seg)[pairs[:, 0]])]).astype(np.int64)).cuda()
+    out_off_t = torch.from_numpy(spv.l1k2_batch_plan(seg, pairs, 128)["out_off"]).cuda()   # the matcher's out rows per pair
     qbase_t, dbase_t = torch.from_numpy(seg[pairs[:, 0]]).cuda(), torch.from_numpy(seg[pairs[:, 1]]).cuda()
     calls = {"tracks_batch": lambda: spv.tracks_batch(seg, pairs, matches, count, mask=tmask),
              "torch": lambda: torch_form(seg_t, out_off_t, qbase_t, dbase_t, matches, count, tmask, n),
