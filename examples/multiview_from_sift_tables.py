@@ -22,9 +22,13 @@ runs all of them through the many-pairs forms of the same steps, with every inte
                              accumulated onto the same labels
     triangulate_tracks       (--triangulate PIXELS, with --tracks) one 3-D point per track from all its observations,
                              a residual per observation and a verdict per track.  The op takes one camera per view
-                             as given; here they are the synthetic scene's own pixel cameras K [R | t].  Estimating
-                             global cameras (chaining the pairwise fits, fixing their scales) is not part of the
-                             library
+                             as given; here they are the synthetic scene's own pixel cameras K [R | t]
+    resect_gather            (--resect PIXELS, with --tracks) the cameras estimated instead, incrementally: the fitted
+    resect_fit_batch         pair with the most inliers is registered as K [I | 0] and K camera, the tracks it sees are
+                             triangulated, every other view is resected from the points its keypoints belong to -- all
+                             of them in one call -- and the tracks are triangulated again over all registered views.
+                             Chaining the other pairwise fits and their scales, and bundle adjustment, are not part of
+                             the library
 
 Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
 they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic
@@ -32,7 +36,7 @@ here, so that the scene and the cameras are known; extracting them from images i
 before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
     python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}] [--rectify]
-                                                  [--guided PIXELS] [--tracks] [--triangulate PIXELS]
+                                                  [--guided PIXELS] [--tracks] [--triangulate PIXELS] [--resect PIXELS]
 """
 import argparse
 import os
@@ -104,8 +108,8 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     line in the database view; a pair without a model has none.  With tracks also tracks: `tracks_batch`'s (track_off,
     members, flags, label, track) over every pair's inlier matches and, with guided, the second pass's matches
     accumulated onto them; and track_inputs: the seg_off, matches, count and mask (and guided_matches, guided_count)
-    those calls read.  With triangulate (one pixel camera [3,4] per view, e.g. synthetic_sift_views' own: the library
-    does not estimate them) and tracks also track_points: `triangulate_tracks`' (X, err, ok, nused) of those tracks, ok
+    those calls read.  With triangulate (one pixel camera [3,4] per view, e.g. synthetic_sift_views' own, or what
+    resect_views below estimates) and tracks also track_points: `triangulate_tracks`' (X, err, ok, nused) of those tracks, ok
     without a residual bound (cheirality alone; call `triangulate_tracks` with max_error for one)."""
     import torch
     from spectavi_amd import device as spv
@@ -141,7 +145,7 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
     if tracks:
         # the mask has one entry per match: rows [0, n) of matches are the call's capacity
         out['tracks'] = spv.tracks_batch(seg, pairs, matches[:n], count, mask=mask)
-        out['track_inputs'] = {'seg_off': seg, 'matches': matches[:n], 'count': count, 'mask': mask}
+        out['track_inputs'] = {'seg_off': seg, 'matches': matches[:n], 'count': count, 'mask': mask, 'geom': geom}
     if guided is not None:
         # x1^T E x0 = 0 with x0 the database view: a query pixel's line in the database view is (K^-T E K^-1)^T x
         iK = np.linalg.inv(K)
@@ -160,6 +164,82 @@ def multiview_pipeline(tables, K, min_ratio=1.75, required_percent_inliers=0.6, 
         out['track_points'] = spv.triangulate_tracks(geom, seg, triangulate, track_off, members)
         out['track_inputs']['geom'] = geom
     return out
+
+
+def resect_views(out, K, max_error, required_percent_inliers=0.6, maximum_tries=500, seed=1):
+    """Incremental registration from the pipeline's tracks (multiview_pipeline(..., tracks=True)), every step on the
+    device: the fitted pair with the most inliers is the seed -- its database view K [I | 0], its query view K camera
+    --, the tracks are triangulated from those two views with a residual bound of max_error pixels, all other views
+    are resected in one call from the ok points their keypoints belong to, and the tracks are triangulated again over
+    every registered view.  Returns a dict: seed (database view, query view), cameras (one pixel camera [3,4] per
+    view, None where a view was not registered), views (the resected views), fits (their `resect_fit_batch` dicts),
+    view_off, x and Xw (their correspondences), track_off and points (`triangulate_tracks`' (X, err, ok, nused) of
+    the last step)."""
+    from spectavi_amd import device as spv
+    fits, pairs, ti = out['fits'], out['pairs'], out['track_inputs']
+    track_off, members, track = out['tracks'][0], out['tracks'][1], out['tracks'][4]
+    nv = len(ti['seg_off']) - 1
+    best = max(range(len(fits)), key=lambda p: len(fits[p]['inlier_idx']) if fits[p]['best_try'] >= 0 else -1)
+    if fits[best]['best_try'] < 0:
+        raise ValueError("no pair has a model to seed from")
+    q, d = (int(v) for v in pairs[best])
+    cameras = [None] * nv
+    cameras[d] = K @ np.hstack([np.eye(3), np.zeros((3, 1))])
+    cameras[q] = K @ fits[best]['camera']
+    X, _, ok, _ = spv.triangulate_tracks(ti['geom'], ti['seg_off'], cameras, track_off, members, max_error=max_error,
+                                         want_err=False)
+    views = [v for v in range(nv) if v not in (q, d)]
+    x, Xw, _, view_off = spv.resect_gather(ti['geom'], track, ti['seg_off'], views, X, ok)
+    n = int(view_off[-1])
+    res = spv.resect_fit_batch(x[:n], Xw[:n], view_off, required_percent_inliers=required_percent_inliers,
+                               max_error=max_error, maximum_tries=maximum_tries,
+                               seeds=np.arange(seed, seed + len(views), dtype=np.uint64))
+    for v, f in zip(views, res):
+        if f['success']:
+            cameras[v] = f['camera']
+    points = spv.triangulate_tracks(ti['geom'], ti['seg_off'], cameras, track_off, members, max_error=max_error)
+    return {'seed': (d, q), 'cameras': cameras, 'views': views, 'fits': res, 'view_off': view_off, 'x': x[:n], 'Xw': Xw[:n],
+            'points': points, 'track_off': track_off}
+
+
+def camera_parts(P, K):
+    """A pixel camera lambda K [R | t] -> (R, the camera centre)."""
+    M = np.linalg.inv(K) @ P
+    lam = np.cbrt(np.linalg.det(M[:, :3]))
+    return M[:, :3] / lam, -np.linalg.solve(M[:, :3], M[:, 3])
+
+
+def report_resection(reg, K, scene_cameras):
+    """Registered views, every resected camera's median reprojection residual over its inliers, and its agreement
+    with the scene's camera in the gauge of the seed pair (the seed's database view at [I | 0], lengths in units of
+    the seed's baseline): the angle between the rotations and the distance between the centres."""
+    d, q = reg['seed']
+    Rd, Cd = camera_parts(scene_cameras[d], K)
+    Cq_scene = Rd @ (camera_parts(scene_cameras[q], K)[1] - Cd)
+    scale = np.linalg.norm(camera_parts(reg['cameras'][q], K)[1]) / np.linalg.norm(Cq_scene)
+    print("registered %d of %d views; seed pair %d-%d" % (sum(c is not None for c in reg['cameras']), len(reg['cameras']), d, q))
+    x, Xw = reg['x'].cpu().numpy(), reg['Xw'].cpu().numpy()
+    for i, (v, f) in enumerate(zip(reg['views'], reg['fits'])):
+        lo, hi = reg['view_off'][i], reg['view_off'][i + 1]
+        if f['camera'] is None:
+            print("view %d: %d correspondences, no camera" % (v, hi - lo))
+            continue
+        idx = f['inlier_idx']
+        h = Xw[lo:hi][idx] @ f['camera'].T
+        res = np.hypot(h[:, 0] / h[:, 2] - x[lo:hi][idx, 0], h[:, 1] / h[:, 2] - x[lo:hi][idx, 1])
+        R, C = camera_parts(f['camera'], K)
+        Rs, Cs = camera_parts(scene_cameras[v], K)
+        Rs, Cs = Rs @ Rd.T, scale * (Rd @ (Cs - Cd))
+        angle = np.degrees(np.arccos(np.clip((np.trace(R @ Rs.T) - 1) / 2, -1, 1)))
+        print("view %d: %d correspondences, %d inliers (%s, try %d of %d run), median residual %.2e px, rotation off by "
+              "%.3f deg, centre off by %.2e baselines" % (v, hi - lo, len(idx), "success" if f['success'] else "best effort",
+                                                         f['best_try'], f['tries_run'], float(np.median(res)) if len(res) else
+                                                         float('nan'), angle, np.linalg.norm(C - Cs)))
+    X, err, ok, nused = reg['points']
+    ok, err = ok.cpu().numpy() != 0, err.cpu().numpy()
+    of_ok = np.repeat(ok, np.diff(reg['track_off']))
+    print("track points over the registered views: ok %d of %d, median residual of the ok tracks %.2e px" % (
+        int(ok.sum()), len(ok), float(np.nanmedian(err[of_ok])) if of_ok.any() else float('nan')))
 
 
 def rectify_pairs(out, K, images):
@@ -222,6 +302,8 @@ def main():
     ap.add_argument("--tracks", action="store_true", help="link every pair's inlier matches into multi-view tracks")
     ap.add_argument("--triangulate", type=float, default=None, metavar="PIXELS",
                     help="with --tracks: one point per track from the scene's own cameras, ok within this residual")
+    ap.add_argument("--resect", type=float, default=None, metavar="PIXELS",
+                    help="with --tracks: register every view from the best fitted pair on, inliers within this residual")
     a = ap.parse_args()
     import torch
     tables, K, cameras = synthetic_sift_views(a.seed, a.images, a.points, return_cameras=True)
@@ -235,6 +317,15 @@ def main():
     report(out)
     if triangulate is not None:
         report_track_points(out, cameras, a.triangulate)
+    if a.resect is not None and a.tracks:
+        for rep in range(2):
+            torch.cuda.synchronize()
+            s = time.perf_counter()
+            reg = resect_views(out, K, a.resect)
+            torch.cuda.synchronize()
+            dt_reg = time.perf_counter() - s
+        report_resection(reg, K, cameras)
+        print("seed, triangulation, resection of %d views, triangulation: %.1f ms (warm)" % (len(reg['views']), dt_reg * 1e3))
     n = int(out['out_off'][-1])
     E = out['X'][:n, :3] / out['X'][:n, 3:]
     print("%d views, %.1f ms (warm); depth of the points: median %.2f" % (a.images, dt * 1e3, float(E[:, 2].median()) if n else 0.0))

@@ -1199,8 +1199,9 @@ int spv_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, i
 
 /* N-view DLT of every track (tracks_triangulate.hip): one 3-D point per track from all its observations, a residual
  * per observation and a verdict per track, for a caller who has one camera per set (a calibrated rig, an earlier
- * reconstruction, a pose graph of their own).  The cameras are taken as given: chaining pairwise fits into global
- * cameras, bundle adjustment and resection are not part of the library.  The reference has no such step.
+ * reconstruction, a pose graph of their own, or spv_resect_fit_batch_device below for views that see points already
+ * triangulated).  The cameras are taken as given: chaining pairwise fits into global cameras and bundle adjustment
+ * are not part of the library.  The reference has no such step.
  *   d_geom   float32[total_rows, 4]: x, y, sigma, angle of every row, as spv_sift_split_device writes them; only x
  *            and y are read, widened to double.
  *   seg_off, nseg: host, the seg_off of spv_l1k2_batch_device.
@@ -1249,6 +1250,94 @@ int spv_tracks_triangulate_device(const float *d_geom, const long long *seg_off,
 int spv_tracks_triangulate(const float *geom, const long long *seg_off, int nseg, const double *cams,
                            const int32_t *use_set, const long long *track_off, int ntracks, const int32_t *members,
                            long long nmembers, double max_error, double *X, double *err, uint8_t *ok, int32_t *nused);
+
+/* RANSAC camera resection of many views (resect_batch.hip): the camera of every view that has none yet, from the 3-D
+ * points of the tracks the view observes.  With it the chain runs incremental structure from motion on the device:
+ * seed with one pair (spv_ransac_fit_batch: [I | 0] and `camera`), spv_tracks_triangulate_device with use_set = the
+ * registered views, resect all other views in one call, triangulate again.  Two ops, split the way
+ * spv_gather_match_coords_batch_device and spv_ransac_fit_batch_device are.  The reference has no such step.
+ *
+ * spv_resect_gather_device: the 2-D / 3-D correspondences of the listed views.
+ *   d_geom, seg_off, nseg: as in spv_tracks_triangulate_device.
+ *   d_track  int32[total_rows]: the track of every row, as spv_tracks_batch_device writes it.
+ *   views    host int32[nviews], each in [0, nseg): the sets to gather; repeats are legal, every listed view owns a
+ *            block of its own.  At most 2^20 views, and fewer than 2^31 rows in the listed views together.
+ *   d_X      double[ntracks, 4], d_ok uint8[ntracks] or NULL: spv_tracks_triangulate_device's outputs.
+ * Row r of view views[i] = set s is taken iff 0 <= d_track[seg_off[s] + r] < ntracks, d_ok is NULL or d_ok[track] != 0,
+ * and all four entries of d_X[track] are finite.  Nothing else is dereferenced: garbage track numbers give skipped
+ * rows, never an access out of bounds.  Taken rows are written back to back, view after view in the order of `views`,
+ * inside a view in ascending row order: d_x double[capacity, 3] = (u, v, 1) widened from float32, d_Xw
+ * double[capacity, 4] = the track's d_X row bit for bit, d_rows int32[capacity] (may be NULL) = the row within the view.
+ * d_view_off device long long[nviews + 1] and view_off, the same on the host (either may be NULL; a host view_off makes
+ * the call wait for its kernels): listed view i owns rows [view_off[i], view_off[i + 1]); both count all taken rows
+ * even beyond `capacity`, as spv_dlt_triangulate_batch_device does, and nothing at or beyond `capacity` is written.
+ * A flag / segmented scan / place chain over the listed views' rows in blocks of 256; the same bits from run to run;
+ * spv_profile_read name "resect_gather".  SPV_ERR_INVALID, nothing launched: the rules of seg_off; a negative count or
+ * capacity; a view outside [0, nseg); the limits above; a NULL required pointer (seg_off; views where nviews > 0;
+ * d_geom, d_track where the listed views have rows; d_X where they have rows and ntracks > 0; d_x, d_Xw where
+ * moreover capacity > 0); a pointer not aligned to its element size.
+ *
+ * spv_resect_fit_batch_device: one camera per set.  d_x double[total, 3] and d_Xw double[total, 4] hold the sets back
+ * to back, set p = rows [view_off[p], view_off[p + 1]) (host, the rules of spv_ransac_fit_batch's pair_off), in whatever
+ * units and scale the caller has, pixel or calibrated: nothing is normalised.  The pixel of a row is (u, v) =
+ * (x[0] / x[2], x[1] / x[2]) by IEEE division: a third column of 1 leaves the first two as they are.
+ *   subsets  samples host int32[nviews, maximum_tries, 6]: row numbers inside the set, each in [0, rows); duplicates
+ *            are legal and give a degenerate hypothesis.  NULL: seeds host unsigned long long[nviews], and set p uses
+ *            the first six columns of what spv_ransac_sample(seeds[p], rows, maximum_tries) returns (a set of 6 to 9
+ *            rows, which that sampler does not take, the first six of a shuffle of its rows by the same generator).
+ *            Sets of fewer than 6 rows are skipped: success 0, best_try -1, tries_run 0, camera row untouched.
+ *   hypothesis  of a try, whatever solves it: the six sampled rows give the 11 x 12 matrix A, row i contributing
+ *            [X_i^T, 0, -u_i X_i^T] and [0, X_i^T, -v_i X_i^T] in sample order, the sixth its u row only.  P is the
+ *            unit-norm null vector of A read as a row-major 3x4 matrix, its last non-zero entry positive.  (11 rows,
+ *            not the 12-row least-squares DLT: the null vector is then defined exactly, whatever a solver normalises
+ *            by.)  The kernel eliminates P's first two rows through one Givens QR of the X_i, takes P[2] as the
+ *            vector orthogonal to the three rows that remain (Householder, unpivoted) and solves the two triangles:
+ *            ||A p|| stays below 1e-15 sigma1(A) on subsets in general position.
+ *   verdict  a row is an inlier of P iff |proj(P Xw) - (u, v)| <= max_error and the depth term of
+ *            spv_tracks_triangulate_device's d_ok is positive: sign(det P[:, :3]) / |P[2, :3]|^2 (P Xw)[2] / Xw[3] > 0.
+ *            The kernel compares squares and multiplies by 1 / Xw[3]; NaNs compare false, a non-finite P counts 0.
+ *   rule     on try order: the first try with count / (double) rows >= required_percent_inliers (success 1); failing
+ *            that, with find_best_even_in_failure, the try with the most inliers -- at least one --, the earliest
+ *            among equals (success 0); otherwise no model.  The result does not depend on how tries are cut into
+ *            rounds and work items: counts are integer sums.
+ * Host outputs as spv_ransac_fit_batch_device's: success int32[nviews], camera double[nviews, 12] (written where a
+ * model was kept), inlier_percent double[nviews] = n_inliers / rows, n_inliers int32[nviews], best_try and tries_run
+ * int32[nviews] or NULL.  d_inlier_mask uint8[total] or NULL: the kept camera's verdict of every row, 0 where a set
+ * kept none.  d_try_cameras double[nviews, maximum_tries, 12] and d_try_inliers int32[nviews, maximum_tries] (device,
+ * either may be NULL) make the op checkable try by try; rows of skipped sets are NaN / 0.  With either of them no set
+ * leaves early: every try is evaluated and tries_run = maximum_tries.  Otherwise sets advance in rounds (256 tries of
+ * a set, then fourfold up to 4096; 32768 tries a round) and leave at their first success: tries_run lies in
+ * [best_try + 1, maximum_tries].  The call waits for `stream` once a round.
+ * Kernels, spv_profile_read names: "resect_solve" (one try per lane), "resect_score" (one workgroup per work item =
+ * at most 256 rows of one set and a range of its tries; a lane keeps its row in registers, a try's camera is
+ * workgroup-uniform; one ballot and popcount per wave and try), "resect_reduce" (per set over its tries in order).
+ * Work items are spv_ransac_fit_batch's: rows in blocks of 256, a set's tries cut into ranges of at least 48 while the
+ * round has fewer than 4 row blocks per compute unit.  spv_resect_fit_batch_plan: host only; the first round of such a
+ * call on a device of compute_units, out = {sets, tries, items, row blocks}, items int32[items_cap, 5] = (set, first
+ * row of the concatenated arrays, rows, first try of the round, tries) or NULL.
+ * SPV_ERR_INVALID, nothing launched: the rules of view_off; NaN max_error or required_percent_inliers; a negative
+ * count; more than 2^20 sets or 7e8 tries; a NULL required pointer; neither samples nor seeds while a set has >= 6
+ * rows and maximum_tries > 0; a sample out of range; a pointer not aligned to its element size.
+ * spv_resect_fit_batch: host pointers (inlier_mask, try_cameras, try_inliers on the host, each may be NULL), on the
+ * first selected device; touches no device when no set has 6 rows or maximum_tries is 0.
+ * Not part of the op: a refit of the winner on all its inliers, a calibrated P3P solver, bundle adjustment. */
+int spv_resect_gather_device(const float *d_geom, const int32_t *d_track, const long long *seg_off, int nseg,
+                             const int32_t *views, int nviews, const double *d_X, const uint8_t *d_ok, int ntracks,
+                             long long capacity, double *d_x, double *d_Xw, int32_t *d_rows, long long *d_view_off,
+                             long long *view_off, void *stream);
+int spv_resect_fit_batch_device(const double *d_x, const double *d_Xw, const long long *view_off, int nviews,
+                                double required_percent_inliers, double max_error, int maximum_tries,
+                                int find_best_even_in_failure, const int32_t *samples, const unsigned long long *seeds,
+                                int32_t *success, double *camera, double *inlier_percent, int32_t *n_inliers,
+                                int32_t *best_try, int32_t *tries_run, uint8_t *d_inlier_mask, double *d_try_cameras,
+                                int32_t *d_try_inliers, void *stream);
+int spv_resect_fit_batch(const double *x, const double *Xw, const long long *view_off, int nviews,
+                         double required_percent_inliers, double max_error, int maximum_tries,
+                         int find_best_even_in_failure, const int32_t *samples, const unsigned long long *seeds,
+                         int32_t *success, double *camera, double *inlier_percent, int32_t *n_inliers, int32_t *best_try,
+                         int32_t *tries_run, uint8_t *inlier_mask, double *try_cameras, int32_t *try_inliers);
+int spv_resect_fit_batch_plan(const long long *view_off, int nviews, int maximum_tries, int compute_units,
+                              long long out[4], int32_t *items, long long items_cap);
 
 /* normalize_to_ubyte_and_multiple_16_dim (reference spectavi/feature.py:384-407) for a float32
  * input, bit for bit what numpy computes: per-column de-mean (numpy's row-ordered float32 sum),

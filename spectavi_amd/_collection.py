@@ -152,6 +152,36 @@ def seeds_and_tries(seeds, samples, maximum_tries, n):
     return seeds, maximum_tries
 
 
+def sample_table(samples, npt, width, min_rows):
+    """samples -> int32[n, ntries, width] or None: the subsets of a many-sets fit whose sets have `npt` rows, row
+    numbers inside the set; the subsets of a set under min_rows rows -- a skipped set -- are not looked at."""
+    if samples is None:
+        return None
+    n = len(npt)
+    samples = np.asarray(samples)
+    if samples.dtype.kind not in "iu" and samples.size:
+        raise ValueError("samples must be integers")
+    if samples.ndim != 3 or samples.shape[0] != n or samples.shape[2] != width:
+        raise ValueError("samples must be [npairs, ntries, %d]" % width)
+    samples = np.ascontiguousarray(samples, dtype=np.int32)
+    runs = npt >= min_rows
+    if samples[runs].size and (int(samples[runs].min()) < 0 or
+                               np.any(samples[runs].reshape(int(runs.sum()), -1).max(axis=1) >= npt[runs])):
+        raise ValueError("a sample row lies outside its set")
+    return samples
+
+
+def resect_dicts(off, ok, P, pct, bt, ran, mask):
+    """The per-set outputs of spv_resect_fit_batch as one dict per set; inlier_idx from the mask uint8[total]."""
+    out = []
+    for p in range(off.size - 1):
+        found = bt[p] >= 0
+        idx = np.flatnonzero(mask[off[p]:off[p + 1]]).astype(np.int32) if found else np.zeros(0, np.int32)
+        out.append({'success': bool(ok[p]), 'camera': P[p].reshape(3, 4).copy() if found else None,
+                    'inlier_percent': float(pct[p]), 'inlier_idx': idx, 'best_try': int(bt[p]), 'tries_run': int(ran[p])})
+    return out
+
+
 def fit_dicts(off, ok, F, P, pct, idx, n, bt, br, ran):
     """The per-set outputs of spv_ransac_fit_batch as one `ransac_fit` dict per set."""
     out = []

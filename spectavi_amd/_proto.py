@@ -171,6 +171,10 @@ PROTOTYPES = {
     "spv_tracks_triangulate_plan": (i, [vp, i, pll]),
     "spv_tracks_triangulate_device": (i, [vp, vp, i, vp, vp, vp, i, vp, ll, d] + [vp] * 5),
     "spv_tracks_triangulate": (i, [vp, vp, i, vp, vp, vp, i, vp, ll, d] + [vp] * 4),
+    "spv_resect_gather_device": (i, [vp, vp, vp, i, vp, i, vp, vp, i, ll] + [vp] * 6),
+    "spv_resect_fit_batch_device": (i, [vp, vp, vp, i, d, d, i, i] + [vp] * 12),
+    "spv_resect_fit_batch": (i, [vp, vp, vp, i, d, d, i, i] + [vp] * 11),
+    "spv_resect_fit_batch_plan": (i, [vp, i, i, i, pll, vp, ll]),
     "spv_normalize": (i, [f32a, i, i, vp, vp]),
     "spv_normalize_workspace_bytes": (sz, [i]),
     "spv_normalize_workspace_bytes_rows": (sz, [i, i]),

@@ -414,6 +414,48 @@ int host_ransac_fit_batch(const double *x0, const double *x1, const long long *p
                               best_root, tries_run, nullptr, st);
 }
 
+// The many-views resection through host pointers, on the first selected device: both arrays up, one
+// resect_fit_batch_run, the mask and the per-try arrays back where they are wanted.  A collection in which no set
+// runs touches no device.
+int host_resect_fit_batch(const double *x, const double *Xw, const long long *view_off, int nviews, double required_percent,
+                          double max_error, int max_tries, int find_best, const int32_t *samples,
+                          const unsigned long long *seeds, int32_t *success, double *camera, double *inlier_percent,
+                          int32_t *n_inliers, int32_t *best_try, int32_t *tries_run, uint8_t *inlier_mask,
+                          double *try_cameras, int32_t *try_inliers) {
+  SPV_TRY(resect_check(view_off, nviews, required_percent, max_error, max_tries, samples));
+  const size_t total = (size_t)view_off[nviews], ntry = (size_t)nviews * (size_t)max_tries;
+  if (total > 0 && (!x || !Xw)) return set_error(SPV_ERR_INVALID, "null pointer");
+  std::vector<RansacBatchSlot> first;
+  resect_first_round(view_off, nviews, max_tries, &first);
+  if (first.empty()) {
+    if (inlier_mask) memset(inlier_mask, 0, total);
+    if (try_inliers) memset(try_inliers, 0, ntry * sizeof(int32_t));
+    if (try_cameras) memset(try_cameras, 0xFF, ntry * 12 * sizeof(double));
+    // (no set runs: the arrays are not read, every set reports what a skipped set reports)
+    return resect_fit_batch_run(x, Xw, view_off, nviews, required_percent, max_error, max_tries, find_best, samples,
+                                seeds, success, camera, inlier_percent, n_inliers, best_try, tries_run, nullptr, nullptr,
+                                nullptr, hipStreamPerThread);
+  }
+  if (!samples && !seeds) return set_error(SPV_ERR_INVALID, "neither samples nor seeds");
+  if (!success || !camera || !inlier_percent || !n_inliers) return set_error(SPV_ERR_INVALID, "null pointer");
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  DevBuf dx, dX, dm, dc, di;
+  SPV_TRY(alloc_all({{&dx, total * 3 * sizeof(double)}, {&dX, total * 4 * sizeof(double)}, {&dm, inlier_mask ? total : 0},
+                     {&dc, try_cameras ? ntry * 12 * sizeof(double) : 0}, {&di, try_inliers ? ntry * sizeof(int32_t) : 0}}));
+  SPV_TRY(dx.copy_in(x, total * 3 * sizeof(double), st));
+  SPV_TRY(dX.copy_in(Xw, total * 4 * sizeof(double), st));
+  SPV_TRY(resect_fit_batch_run(dx.as<double>(), dX.as<double>(), view_off, nviews, required_percent, max_error, max_tries,
+                               find_best, samples, seeds, success, camera, inlier_percent, n_inliers, best_try, tries_run,
+                               inlier_mask ? dm.as<uint8_t>() : nullptr, try_cameras ? dc.as<double>() : nullptr,
+                               try_inliers ? di.as<int32_t>() : nullptr, st));
+  if (inlier_mask) SPV_TRY(dm.copy_out(inlier_mask, total, st));
+  if (try_cameras) SPV_TRY(dc.copy_out(try_cameras, ntry * 12 * sizeof(double), st));
+  if (try_inliers) SPV_TRY(di.copy_out(try_inliers, ntry * sizeof(int32_t), st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  return SPV_OK;
+}
+
 // The many-sets triangulation through host pointers, on the first selected device: both arrays and the mask up,
 // one dlt_batch_run, the offsets back, then as many result rows as were selected and fit.  A collection without a
 // row in a used set touches no device.
@@ -1841,6 +1883,61 @@ int spv_ransac_fit_batch_plan(const long long *pair_off, int npairs, int maximum
     long long tries = 0, blocks = 0;
     for (const RansacBatchSlot &s : slots) {
       tries += s.ncand / 3;
+      blocks += (s.npt + 255) / 256;
+    }
+    out[0] = (long long)slots.size();
+    out[1] = tries;
+    out[2] = (long long)its.size();
+    out[3] = blocks;
+    export_items<5>(its, items, items_cap);
+    return (int)SPV_OK;
+  });
+}
+int spv_resect_gather_device(const float *d_geom, const int32_t *d_track, const long long *seg_off, int nseg,
+                             const int32_t *views, int nviews, const double *d_X, const uint8_t *d_ok, int ntracks,
+                             long long capacity, double *d_x, double *d_Xw, int32_t *d_rows, long long *d_view_off,
+                             long long *view_off, void *stream) {
+  return api([&] {
+    return resect_gather_run(d_geom, d_track, seg_off, nseg, views, nviews, d_X, d_ok, ntracks, capacity, d_x, d_Xw, d_rows,
+                             d_view_off, view_off, static_cast<hipStream_t>(stream));
+  });
+}
+int spv_resect_fit_batch(const double *x, const double *Xw, const long long *view_off, int nviews,
+                         double required_percent_inliers, double max_error, int maximum_tries,
+                         int find_best_even_in_failure, const int32_t *samples, const unsigned long long *seeds,
+                         int32_t *success, double *camera, double *inlier_percent, int32_t *n_inliers, int32_t *best_try,
+                         int32_t *tries_run, uint8_t *inlier_mask, double *try_cameras, int32_t *try_inliers) {
+  return host_api([&] {
+    return host_resect_fit_batch(x, Xw, view_off, nviews, required_percent_inliers, max_error, maximum_tries,
+                                 find_best_even_in_failure, samples, seeds, success, camera, inlier_percent, n_inliers,
+                                 best_try, tries_run, inlier_mask, try_cameras, try_inliers);
+  });
+}
+int spv_resect_fit_batch_device(const double *d_x, const double *d_Xw, const long long *view_off, int nviews,
+                                double required_percent_inliers, double max_error, int maximum_tries,
+                                int find_best_even_in_failure, const int32_t *samples, const unsigned long long *seeds,
+                                int32_t *success, double *camera, double *inlier_percent, int32_t *n_inliers,
+                                int32_t *best_try, int32_t *tries_run, uint8_t *d_inlier_mask, double *d_try_cameras,
+                                int32_t *d_try_inliers, void *stream) {
+  return api([&] {
+    return resect_fit_batch_run(d_x, d_Xw, view_off, nviews, required_percent_inliers, max_error, maximum_tries,
+                                find_best_even_in_failure, samples, seeds, success, camera, inlier_percent, n_inliers,
+                                best_try, tries_run, d_inlier_mask, d_try_cameras, d_try_inliers,
+                                static_cast<hipStream_t>(stream));
+  });
+}
+int spv_resect_fit_batch_plan(const long long *view_off, int nviews, int maximum_tries, int compute_units, long long out[4],
+                              int32_t *items, long long items_cap) {
+  return api([&] {
+    SPV_TRY(resect_check(view_off, nviews, 0.0, 0.0, maximum_tries, nullptr));
+    if (compute_units < 1 || !out || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
+    std::vector<RansacBatchSlot> slots;
+    std::vector<RansacBatchItem> its;
+    resect_first_round(view_off, nviews, maximum_tries, &slots);
+    ransac_batch_items(slots, view_off, compute_units, &its);
+    long long tries = 0, blocks = 0;
+    for (const RansacBatchSlot &s : slots) {
+      tries += s.ncand;
       blocks += (s.npt + 255) / 256;
     }
     out[0] = (long long)slots.size();

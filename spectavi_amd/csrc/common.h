@@ -543,6 +543,16 @@ struct RansacBatchItem {
 struct RansacBatchSlot {
   int32_t set, npt, cand0, ncand, cand_base;  // cand_base: 3 x the tries of the set that earlier rounds evaluated
 };
+// Row blocks of a set of npt rows: the scorers' workgroups take 256 rows each.
+inline size_t batch_row_blocks(long long npt) { return (size_t)((npt + 255) / 256); }
+// The rule that fills a round of a many-sets fit from its running sets, in order (host only).  A running set `r` (any
+// record with set, npt, done and step) brings its next min(step, what is left of max_tries) tries while the round
+// holds fewer than round_tries tries and less than round_work units of work, a try of a set costing work_per_row x npt;
+// the first set of a round always runs, and a set of which not one more try fits waits with the sets behind it.  A
+// slot counts candidates: per_try of them a try.  who (may be null): the slots' places in `run`.
+template <typename Run>
+void fill_batch_round(const std::vector<Run> &run, int max_tries, int round_tries, long long round_work,
+                      long long work_per_row, int per_try, std::vector<RansacBatchSlot> *slots, std::vector<int> *who);
 // The work items of a round, a function of the slots and the compute units alone; host only.
 void ransac_batch_items(const std::vector<RansacBatchSlot> &slots, const long long *pair_off, int cus,
                         std::vector<RansacBatchItem> *items);
@@ -613,5 +623,58 @@ int tracks_triangulate_run(const float *d_geom, const long long *seg_off, int ns
                            const int32_t *use_set, const long long *track_off, int ntracks, const int32_t *d_members,
                            long long nmembers, double max_error, double *d_X, double *d_err, uint8_t *d_ok,
                            int32_t *d_nused, hipStream_t stream);
+
+// ---- RANSAC camera resection of many views (resect_batch.hip) -------------------------------
+constexpr int kResectMinRows = 6;  // a hypothesis takes six rows: smaller sets are skipped
+// One workgroup's step of the gather: rows [row0, row0 + rows) of geom, all of the listed view `view` (an index into
+// views), the first of them row view_row0 of that view.
+struct ResectGatherItem {
+  int32_t view, row0, rows, view_row0;
+};
+// The work items of a gather, a function of seg_off and views alone (host only): every listed view's rows in blocks
+// of 256, in order.
+void resect_gather_items(const long long *seg_off, const int32_t *views, int nviews, std::vector<ResectGatherItem> *items);
+// SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
+int resect_gather_check(const void *geom, const void *track, const long long *seg_off, int nseg, const int32_t *views,
+                        int nviews, const void *X, int ntracks, long long capacity, const void *x, const void *Xw);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream` but for the upload of the call's tables, and
+// for the wait that a host view_off asks for.
+int resect_gather_run(const float *d_geom, const int32_t *d_track, const long long *seg_off, int nseg, const int32_t *views,
+                      int nviews, const double *d_X, const uint8_t *d_ok, int ntracks, long long capacity, double *d_x,
+                      double *d_Xw, int32_t *d_rows, long long *d_view_off, long long *view_off, hipStream_t stream);
+// The slots of the first round of a fit (host only): every set of >= 6 rows, in order, while the round has room; a
+// slot's cand0 / ncand / cand_base count tries.  Its work items are ransac_batch_items'.
+void resect_first_round(const long long *view_off, int nviews, int max_tries, std::vector<RansacBatchSlot> *slots);
+// SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
+int resect_check(const long long *view_off, int nviews, double required_percent, double max_error, int max_tries,
+                 const int32_t *samples);
+// Host results as in include/spectavi_amd.h; d_x / d_Xw on the current device.  Synchronises `stream` once a round.
+int resect_fit_batch_run(const double *d_x, const double *d_Xw, const long long *view_off, int nviews,
+                         double required_percent, double max_error, int max_tries, int find_best, const int32_t *samples,
+                         const unsigned long long *seeds, int32_t *success, double *camera, double *inlier_percent,
+                         int32_t *n_inliers, int32_t *best_try, int32_t *tries_run, unsigned char *d_inlier_mask,
+                         double *d_try_cameras, int32_t *d_try_inliers, hipStream_t stream);
+
+template <typename Run>
+void fill_batch_round(const std::vector<Run> &run, int max_tries, int round_tries, long long round_work,
+                      long long work_per_row, int per_try, std::vector<RansacBatchSlot> *slots, std::vector<int> *who) {
+  slots->clear();
+  if (who) who->clear();
+  int tries = 0;
+  long long work = 0;
+  for (size_t i = 0; i < run.size(); ++i) {
+    const Run &r = run[i];
+    if (tries >= round_tries || (tries > 0 && work >= round_work)) break;
+    const long long per = work_per_row * r.npt;
+    const long long by_work = tries == 0 ? 2147483647 : (round_work - work) / per;  // the first set always runs
+    if (by_work < 1) break;  // not one more try of this set fits: it waits, and so do the sets behind it
+    const int n = (int)std::min<long long>({(long long)r.step, (long long)(max_tries - r.done), (long long)(round_tries - tries), by_work});
+    if (n <= 0) continue;
+    slots->push_back(RansacBatchSlot{r.set, r.npt, per_try * tries, per_try * n, per_try * r.done});
+    if (who) who->push_back((int)i);
+    tries += n;
+    work += per * n;
+  }
+}
 
 }  // namespace spv

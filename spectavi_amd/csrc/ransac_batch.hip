@@ -339,7 +339,7 @@ int score_items(const BatchBufs &b, const RansacBatchItem *d_items, int nitems, 
   return SPV_OK;
 }
 
-size_t row_blocks(long long npt) { return (size_t)((npt + kDltThreads - 1) / kDltThreads); }
+size_t row_blocks(long long npt) { return batch_row_blocks(npt); }
 
 }  // namespace
 
@@ -367,23 +367,8 @@ struct SetRun {
   int set, npt, done, step, batch;
 };
 void fill_round(std::vector<SetRun> &run, int max_tries, std::vector<RansacBatchSlot> *slots, std::vector<int> *who) {
-  slots->clear();
-  if (who) who->clear();
-  int tries = 0;
-  long long solves = 0;
-  for (size_t i = 0; i < run.size(); ++i) {
-    const SetRun &r = run[i];
-    if (tries >= kRoundTries || (tries > 0 && solves >= kRoundSolves)) break;
-    const long long per_try = 12ll * r.npt;
-    const long long by_work = tries == 0 ? INT_MAX : (kRoundSolves - solves) / per_try;  // the first set always runs
-    if (by_work < 1) break;  // not one more try of this set fits: it waits, and so do the sets behind it
-    const int n = (int)std::min<long long>({(long long)r.step, (long long)(max_tries - r.done), (long long)(kRoundTries - tries), by_work});
-    if (n <= 0) continue;
-    slots->push_back(RansacBatchSlot{r.set, r.npt, 3 * tries, 3 * n, 3 * r.done});
-    if (who) who->push_back((int)i);
-    tries += n;
-    solves += per_try * n;
-  }
+  // a try is three candidates of four cameras each: 12 solves a row
+  fill_batch_round(run, max_tries, kRoundTries, kRoundSolves, 12, 3, slots, who);
 }
 std::vector<SetRun> running_sets(const long long *pair_off, int npairs, int max_tries) {
   std::vector<SetRun> run;

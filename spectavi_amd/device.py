@@ -795,18 +795,7 @@ def _fit_batch_args(pair_off, total, maximum_tries, seeds, samples):
     off = col.offsets(pair_off, "pair_off", total, "x0")
     npairs = off.size - 1
     col.check_set_count(npairs)
-    npt = np.diff(off)
-    if samples is not None:
-        samples = np.asarray(samples)
-        if samples.dtype.kind not in "iu" and samples.size:
-            raise ValueError("samples must be integers")
-        if samples.ndim != 3 or samples.shape[0] != npairs or samples.shape[2] != 7:
-            raise ValueError("samples must be [npairs, ntries, 7]")
-        samples = np.ascontiguousarray(samples, dtype=np.int32)
-        runs = npt >= 10
-        if samples[runs].size and (int(samples[runs].min()) < 0 or
-                                   np.any(samples[runs].reshape(int(runs.sum()), -1).max(axis=1) >= npt[runs])):
-            raise ValueError("a sample row lies outside its set")
+    samples = col.sample_table(samples, np.diff(off), 7, 10)
     seeds, maximum_tries = col.seeds_and_tries(seeds, samples, maximum_tries, npairs)
     return off, samples, seeds, maximum_tries
 
@@ -1060,7 +1049,8 @@ def triangulate_tracks(geom, seg_off, cameras, track_off, members, max_error=flo
     [total_rows, 4] (x, y, sigma, angle of every set's rows back to back, as `sift_split` writes them), seg_off the
     sets' offsets, cameras one host [3,4] camera per set ([nseg,3,4], or a list whose None entries are sets without
     a camera), use an optional per-set switch, (track_off, members) what `tracks_batch` returned.  The cameras are
-    taken as given -- pixel cameras for pixel geom; estimating them is not part of the library.
+    taken as given -- pixel cameras for pixel geom; `resect_fit_batch` estimates those of views that see points
+    already triangulated.
 
     Returns (X float64 [ntracks,4], err float64 [nmembers] or None without want_err, ok uint8 [ntracks], nused int32
     [ntracks]) as CUDA tensors, aligned with the inputs.  An observation is usable when its set and row exist and the
@@ -1089,6 +1079,135 @@ def triangulate_tracks(geom, seg_off, cameras, track_off, members, max_error=flo
             members.data_ptr(), nm, max_error, X.data_ptr(), err.data_ptr() if want_err else None, ok.data_ptr(),
             nused.data_ptr(), stream))
     return X, err, ok, nused
+
+
+def _resect_gather_args(geom_shape, seg_off, views, track_shape, X_shape, ok_shape, capacity):
+    """seg_off -> int64[nseg + 1], views -> int32[nviews] (each in [0, nseg)), capacity (None: the rows of the listed
+    views); ValueError for anything spv_resect_gather_device would reject or that does not describe geom [total_rows,
+    4], track [total_rows], X [ntracks, 4] and ok [ntracks].  Touches no device."""
+    if len(geom_shape) != 2 or geom_shape[1] != 4:
+        raise ValueError("geom must be [total_rows, 4]")
+    seg = col.offsets(seg_off, "seg_off", geom_shape[0], "geom")
+    nseg = seg.size - 1
+    if tuple(track_shape) != (geom_shape[0],):
+        raise ValueError("track must hold one entry per row of geom")
+    if len(X_shape) != 2 or X_shape[1] != 4:
+        raise ValueError("X must be [ntracks, 4]")
+    if ok_shape is not None and tuple(ok_shape) != (X_shape[0],):
+        raise ValueError("ok must hold one entry per track")
+    v = np.asarray(views)
+    if v.size == 0:
+        v = np.zeros(0, np.int32)
+    if v.ndim != 1 or v.dtype.kind not in "iu":
+        raise ValueError("views must be a list of set numbers")
+    if v.size and (int(v.min()) < 0 or int(v.max()) >= nseg):
+        raise ValueError("views name sets outside [0, %d)" % nseg)
+    col.check_set_count(v.size)
+    v = np.ascontiguousarray(v, dtype=np.int32)
+    rows = int(np.diff(seg)[v].sum())
+    if rows >= 2 ** 31:
+        raise ValueError("the listed views must have fewer than 2^31 rows in all")
+    capacity = rows if capacity is None else int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity must not be negative")
+    return seg, v, capacity
+
+
+def resect_gather(geom, track, seg_off, views, X, ok=None, capacity=None):
+    """The 2-D / 3-D correspondences of the listed views (spv_resect_gather_device): geom CUDA float32 [total_rows, 4]
+    and seg_off as for `triangulate_tracks`, track CUDA int32 [total_rows] what `tracks_batch` returned, (X, ok) what
+    `triangulate_tracks` returned, views the sets to resect (repeats are legal).  A row is taken when its track number
+    is in range, ok (if given) is not zero there and the track's X is finite.  Returns (x float64 [capacity, 3] =
+    (u, v, 1), Xw float64 [capacity, 4], rows int32 [capacity] = the row within its view, view_off int64 ndarray
+    [nviews + 1]): listed view i owns rows view_off[i]:view_off[i + 1], the arguments of `resect_fit_batch`.  capacity
+    defaults to the rows of the listed views; view_off counts every taken row even beyond it, and nothing beyond it
+    is written.  Reading view_off back synchronises the current stream."""
+    if not isinstance(geom, torch.Tensor) or geom.dtype != torch.float32:
+        raise ValueError("geom must be a float32 tensor [total_rows, 4]")
+    seg, v, capacity = _resect_gather_args(tuple(geom.shape), seg_off, views, tuple(track.shape), tuple(X.shape),
+                                           None if ok is None else tuple(ok.shape), capacity)
+    _need(geom, torch.float32, "geom")
+    _need(track, torch.int32, "track")
+    _need(X, torch.float64, "X")
+    if ok is not None:
+        _need(ok, torch.uint8, "ok")
+    dev = geom.device
+    x = torch.zeros((capacity, 3), dtype=torch.float64, device=dev)
+    Xw = torch.zeros((capacity, 4), dtype=torch.float64, device=dev)
+    rows = torch.zeros(capacity, dtype=torch.int32, device=dev)
+    view_off = np.zeros(v.size + 1, np.int64)
+    with _on_device_of(geom, track, X, ok) as stream:
+        check(clib.spv_resect_gather_device(
+            geom.data_ptr(), track.data_ptr(), seg.ctypes.data, seg.size - 1, v.ctypes.data, v.size, X.data_ptr(),
+            ok.data_ptr() if ok is not None else None, int(X.shape[0]), capacity, x.data_ptr(), Xw.data_ptr(),
+            rows.data_ptr(), None, view_off.ctypes.data, stream))
+    return x, Xw, rows, view_off
+
+
+def _resect_fit_args(view_off, total, max_error, required_percent_inliers, maximum_tries, seeds, samples):
+    """view_off -> int64[nviews + 1], samples -> int32[nviews, T, 6] or None, seeds -> uint64[nviews] or None,
+    maximum_tries, max_error and the share as floats; ValueError for anything spv_resect_fit_batch_device would reject
+    or that does not describe arrays of `total` rows.  Touches no device."""
+    off = col.offsets(view_off, "view_off", total, "x")
+    nviews = off.size - 1
+    col.check_set_count(nviews)
+    samples = col.sample_table(samples, np.diff(off), 6, 6)
+    seeds, maximum_tries = col.seeds_and_tries(seeds, samples, maximum_tries, nviews)
+    max_error, share = float(max_error), float(required_percent_inliers)
+    if max_error != max_error or share != share:
+        raise ValueError("max_error and required_percent_inliers must not be NaN")
+    return off, samples, seeds, maximum_tries, max_error, share
+
+
+def resect_fit_batch_plan(view_off, maximum_tries=500, compute_units=256, want_items=False):
+    """The first round of resect_fit_batch() for a collection (spv_resect_fit_batch_plan; host only, no device
+    touched): dict of sets and tries in the round, items (work items = workgroups of the scorer) and row_blocks
+    (blocks of 256 rows).  With want_items also the items, int32[items, 5] = (set, first row, rows, first try of the
+    round, tries)."""
+    off = col.offsets(view_off, "view_off")
+    out, items = _plan_items(clib.spv_resect_fit_batch_plan,
+                             (off.ctypes.data, off.size - 1, int(maximum_tries), int(compute_units)), 4, 5, want_items, at=2)
+    plan = dict(sets=out[0], tries=out[1], items=out[2], row_blocks=out[3])
+    return (plan, items) if want_items else plan
+
+
+def resect_fit_batch(x, Xw, view_off, required_percent_inliers=.9, max_error=2., maximum_tries=500,
+                     find_best_even_in_failure=False, samples=None, seeds=None, want_mask=False, want_tries=False):
+    """RANSAC camera resection of every set of a collection in one call (spv_resect_fit_batch_device): x CUDA float64
+    [total, 3] = (u, v, 1) and Xw CUDA float64 [total, 4] hold the sets back to back, set p = rows
+    view_off[p]:view_off[p + 1] (e.g. the output of `resect_gather`), in the caller's units -- max_error is in those of
+    x.  samples int32 [nviews, ntries, 6] (row numbers inside the set; `maximum_tries` and `seeds` are then ignored) or
+    seeds [nviews] (0 = SPECTAVI_RANSAC_SEED / random; the first six columns of `mvg.ransac_sample`) choose the subsets.
+    A try's camera is the unit null vector of the 11 x 12 matrix of its six rows; a row is an inlier when it reprojects
+    within max_error in front of the camera; the winner is the first try whose inlier share reaches
+    required_percent_inliers, else -- with find_best_even_in_failure -- the try with the most inliers.  Returns a list
+    of dicts (success, camera [3,4] or None, inlier_percent, inlier_idx, best_try, tries_run); a set of fewer than 6
+    rows is skipped.  With want_mask also a CUDA uint8 [total] tensor (1 = inlier of its set's kept camera), with
+    want_tries also the CUDA tensors try_cameras float64 [nviews, ntries, 12] and try_inliers int32 [nviews, ntries]
+    (every try is then evaluated).  Synchronises the current stream once per round of tries, however many sets; the
+    mask is computed and copied to the host (one byte a row) whether it is wanted or not: inlier_idx is read from it."""
+    if not (x.dim() == 2 and x.shape[1] == 3 and Xw.dim() == 2 and Xw.shape[1] == 4 and x.shape[0] == Xw.shape[0]):
+        raise ValueError("x must be [total,3] and Xw [total,4]")
+    total = x.shape[0]
+    off, samples, seeds, maximum_tries, max_error, share = _resect_fit_args(view_off, total, max_error, required_percent_inliers,
+                                                                           maximum_tries, seeds, samples)
+    _need(x, torch.float64, "x")
+    _need(Xw, torch.float64, "Xw")
+    nviews = off.size - 1
+    ok, n, bt, ran = (np.zeros(nviews, np.int32) for _ in range(4))
+    pct, P = np.zeros(nviews), np.zeros((nviews, 12))
+    mask = torch.empty(total, dtype=torch.uint8, device=x.device)
+    cams = torch.empty((nviews, maximum_tries, 12), dtype=torch.float64, device=x.device) if want_tries else None
+    inl = torch.empty((nviews, maximum_tries), dtype=torch.int32, device=x.device) if want_tries else None
+    with _on_device_of(x, Xw) as stream:
+        check(clib.spv_resect_fit_batch_device(
+            x.data_ptr(), Xw.data_ptr(), off.ctypes.data, nviews, share, max_error, maximum_tries,
+            int(bool(find_best_even_in_failure)), _ptr(samples), seeds.ctypes.data if samples is None else None,
+            ok.ctypes.data, P.ctypes.data, pct.ctypes.data, n.ctypes.data, bt.ctypes.data, ran.ctypes.data,
+            mask.data_ptr(), cams.data_ptr() if want_tries else None, inl.data_ptr() if want_tries else None, stream))
+    fits = col.resect_dicts(off, ok, P, pct, bt, ran, mask.cpu().numpy())
+    out = (fits,) + ((mask,) if want_mask else ()) + ((cams, inl) if want_tries else ())
+    return out if len(out) > 1 else fits
 
 
 def normalize(x, want_float=True, want_ubyte=False, workspace=None):

@@ -417,7 +417,7 @@ def triangulate_tracks(coords, sizes, cameras, track_off, members, max_error=flo
     are rounded to float32, the precision of a SIFT table), `sizes` the rows of every view as `match_tracks_batch`
     takes them (None: the rows of coords), `cameras` one [3,4] camera per view -- a None entry is a view without a
     camera --, `use` an optional per-view switch, (`track_off`, `members`) what `match_tracks_batch` returned.  The
-    cameras are taken as given: estimating them is not part of the library.
+    cameras are taken as given; `resect_batch` estimates those of views that see points already triangulated.
 
     Returns numpy arrays (X float64 [ntracks,4], err float64 [nmembers], ok uint8 [ntracks], nused int32 [ntracks]).
     A member is usable when its view and row exist and the view has a camera.  X is the unit null vector of the
@@ -460,6 +460,62 @@ def triangulate_tracks(coords, sizes, cameras, track_off, members, max_error=flo
                                       off.ctypes.data, nt, mem.ctypes.data, nm, max_error, X.ctypes.data,
                                       err.ctypes.data, ok.ctypes.data, nused.ctypes.data))
     return X, err, ok, nused
+
+
+def resect_batch(xs, Xws, required_percent_inliers=.9, max_error=2., maximum_tries=500, find_best_even_in_failure=False,
+                 seeds=None, samples=None, want_tries=False):
+    """
+    RANSAC camera resection of many views in one call (an addition: the reference stops at two views).  `xs` is a
+    list with one [n_v, >=2] array per view -- image points (u, v), a third column, if any, is the homogeneous
+    scale --, `Xws` the list of [n_v, 4] homogeneous 3-D points they observe, in whatever units the caller has;
+    `max_error` is in the units of xs.  `samples`: a list of int32 [ntries,6] arrays, one per view, all of one ntries
+    (`maximum_tries` and `seeds` are then ignored), or `seeds`: one value per view (0 = SPECTAVI_RANSAC_SEED /
+    random), the first six columns of `ransac_sample`.  A view of fewer than 6 rows is skipped.
+
+    Returns a list of dicts (success, camera [3,4] or None, inlier_percent, inlier_idx, best_try, tries_run): a try's
+    camera is the unit null vector of the 11 x 12 matrix of its six rows (the sixth with its u row only); a row is an
+    inlier when it reprojects within max_error in front of the camera; the winner is the first try whose inlier share
+    reaches required_percent_inliers, else -- with find_best_even_in_failure -- the try with the most inliers.  With
+    `want_tries` also (try_cameras [nviews, ntries, 12], try_inliers [nviews, ntries]), every try evaluated.
+    """
+    if len(xs) != len(Xws):
+        raise ValueError('xs and Xws must hold one array per view each.')
+    ax, aX = [], []
+    for u, X in zip(xs, Xws):
+        u, X = np.asarray(u, dtype=np.float64), np.ascontiguousarray(X, dtype=np.float64)
+        if not (u.ndim == 2 and u.shape[1] in (2, 3) and X.ndim == 2 and X.shape == (len(u), 4)):
+            raise TypeError('Coords must be [npt,2] or [npt,3] with [npt,4] points.')
+        ax.append(np.concatenate([u, np.ones((len(u), 1))], 1) if u.shape[1] == 2 else u)
+        aX.append(X)
+    nviews = len(ax)
+    off = col.offsets(col.offsets_of([len(u) for u in ax]), "the views' offsets")
+    col.check_set_count(nviews)
+    total = int(off[-1])
+    x = np.ascontiguousarray(np.concatenate(ax)) if total else np.zeros((0, 3))
+    Xw = np.ascontiguousarray(np.concatenate(aX)) if total else np.zeros((0, 4))
+    if samples is not None:
+        if len(samples) != nviews:
+            raise ValueError('samples must hold one [ntries,6] array per view.')
+        rows = [np.asarray(s) for s in samples]
+        if any(s.ndim != 2 or s.shape != rows[0].shape for s in rows):
+            raise ValueError('samples must be [ntries,6] arrays of one ntries.')
+        samples = col.sample_table(np.stack(rows) if nviews else np.zeros((0, 0, 6), np.int32), np.diff(off), 6, 6)
+    seeds, maximum_tries = col.seeds_and_tries(seeds, samples, maximum_tries, nviews)
+    max_error, share = float(max_error), float(required_percent_inliers)
+    if max_error != max_error or share != share:
+        raise ValueError('max_error and required_percent_inliers must not be NaN.')
+    ok, n, bt, ran = (np.zeros(nviews, np.int32) for _ in range(4))
+    pct, P, mask = np.zeros(nviews), np.zeros((nviews, 12)), np.zeros(total, np.uint8)
+    cams = np.empty((nviews, maximum_tries, 12)) if want_tries else None
+    inl = np.empty((nviews, maximum_tries), np.int32) if want_tries else None
+    check(clib.spv_resect_fit_batch(x.ctypes.data, Xw.ctypes.data, off.ctypes.data, nviews, share, max_error, maximum_tries,
+                                    int(bool(find_best_even_in_failure)),
+                                    samples.ctypes.data if samples is not None else None,
+                                    seeds.ctypes.data if samples is None else None, ok.ctypes.data, P.ctypes.data,
+                                    pct.ctypes.data, n.ctypes.data, bt.ctypes.data, ran.ctypes.data, mask.ctypes.data,
+                                    cams.ctypes.data if want_tries else None, inl.ctypes.data if want_tries else None))
+    fits = col.resect_dicts(off, ok, P, pct, bt, ran, mask)
+    return (fits, cams, inl) if want_tries else fits
 
 
 # ==================================================================================
