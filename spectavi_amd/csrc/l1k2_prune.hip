@@ -91,6 +91,9 @@
 // takes the path, the form is wide and no table is named (the benchmark's shapes); prune mode 1 and a named table run the
 // int8 kernels, whose decisions the case tables of the tests pin.  spv_l1k2_set_prune_matrix / SPECTAVI_L1K2_PRUNE_MATRIX
 // force either, tests/test_l1k2_prune_fp6_isa.py holds the FP6 kernel's budgets (256 VGPRs, no spill, 40 MFMAs in one run).
+// The two arm a tile's accumulators in different places: the int8 form at the end of the compare of the tile before, under
+// its partner's MFMA run, which is the longer half-step there; the FP6 form, whose shorter run made the compare the longer
+// half-step, in the tile's own top, ahead of its first MFMA (see "Arming" in wide_body; tests/test_l1k2_prune_fp6_rebalance_isa.py).
 #include "common.h"
 #include "l1k2_bound_fp6.h"
 #include "l1k2_bound_tuned.h"
@@ -147,12 +150,22 @@ struct PruneForm {
   static constexpr int kOctetPairs = 8;
   static constexpr bool kRaggedFromCopy = H > 1;           // see Stage::ragged_offsets
   static constexpr bool kRefreshFromCopy = false;          // see `refresh` in wide_body
+  // Where wide_body arms a tile's accumulators, see "Arming" there: at the end of the compare of the tile before (false) or
+  // in the tile's own top, ahead of its first MFMA (true); and, if in the top, whether the refresh of the thresholds goes
+  // there with the 64 moves (true) or stays at the end of the compare (false, the split form).
+  static constexpr bool kArmAtTop = false;
+  static constexpr bool kRefreshAtTop = false;
 };
 using Narrow = PruneForm<1>;
 using Wide = PruneForm<2>;
 // the wide form with the FP6 bound (l1k2_prune_wide6_kernel): every number of the form, and LDS arrays of its own
+#ifndef SPV_L1K2_FP6_ARM  // 0 end of compare, 1 top, 2 top with the refresh left at the end of compare; measurements only
+#define SPV_L1K2_FP6_ARM 1
+#endif
 struct Wide6 : PruneForm<2> {
   static constexpr bool kRefreshFromCopy = true;
+  static constexpr bool kArmAtTop = SPV_L1K2_FP6_ARM != 0;
+  static constexpr bool kRefreshAtTop = SPV_L1K2_FP6_ARM == 1;
 };
 
 // Phase stamps (-DSPV_L1K2_PHASE_STAMPS, never in the shipped library): every wave sums the shader cycles of each
@@ -161,8 +174,11 @@ struct Wide6 : PruneForm<2> {
 // for lgkmcnt(0) and pins the schedule around it.
 // The wide form has two barriers per tile: kPhBarrier is the one that ends a tile, kPhMidBarrier the one between its
 // MFMA run and its compare, and kPhArm is the arming of the next tile's accumulators at the end of its compare, which
-// the narrow form does in its top, kPhStage (the narrow form leaves both zero).
-enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPhLoop, kPhMidBarrier, kPhArm, kPhases };
+// the narrow form does in its top, kPhStage (the narrow form leaves both zero).  Where the wide form arms in the tile's own top
+// (F::kArmAtTop), kPhArm is counted there and lies inside kPhStage.  kPhIssue, the wide form's alone, is the issue of the
+// next tile's loads to LDS inside the top, five by a trailing wave and four by a leading one; the stamp ahead of it waits for
+// the tile's first two A reads, which the unstamped top leaves in flight across the issue.
+enum Phase { kPhStage, kPhMfma, kPhCompact, kPhDrain, kPhVmWait, kPhBarrier, kPhLoop, kPhMidBarrier, kPhArm, kPhIssue, kPhases };
 #ifdef SPV_L1K2_PHASE_STAMPS
 #define SPV_STAMP_PARAM , unsigned long long *stamps_out
 #define SPV_STAMP_ARG , d_stamps
@@ -852,6 +868,10 @@ __global__ __launch_bounds__(kAuxThreads) void l1k2_feature6_kernel(const uint4 
 // tests/test_l1k2_prune_stagger_isa.py the half-steps.
 // The tile loop is written once for both matrix formats, wide_body<F, X>: F = Wide and X = MatI8 is l1k2_prune_wide_kernel,
 // F = Wide6 and X = MatFp6 is l1k2_prune_wide6_kernel, the same geometry and protocol with 40 scaled FP6 MFMAs per tile.
+// One placement differs (PruneForm::kArmAtTop): with 40 MFMAs the compare is the longer half-step, and the FP6 form arms a
+// tile in the tile's own top, behind the flag test and ahead of the threshold loads and the first MFMA; its top is the int8
+// form's plus refresh and the 64 moves, and the end of its compare holds neither.  tests/test_l1k2_prune_fp6_rebalance_isa.py
+// holds that in the assembly.
 
 // ---- The matrix format of the wide form's bound: what a kernel's operands, accumulators and MFMAs are.
 // MatI8: the rank-4 int8 table, K = 512 per pair in 16 k-steps of 32 per row half, exact in int32.
@@ -1020,9 +1040,18 @@ __device__ __forceinline__ void wide_body(
     // refresh, whose k2s[] only this wave's own drains write and whose seen[] landed at a mid-tile vmcnt(0), and the 64
     // moves; it needs no barrier, so it stands where the wave would wait for the end-of-tile barrier while the other wave
     // of its SIMD runs its MFMAs, and a tile's top is the first A reads, the stage issue and the flag test alone.
+    // F::kArmAtTop (the FP6 form): the same refresh and moves stand in the tile's own top instead, behind the first A reads
+    // and the stage issue and ahead of the first MFMA, where the wave waits for its LDS reads anyway.  With 40 MFMAs where
+    // the int8 form has 64 the compare is the longer half-step on both wave groups, and what the arming costs there
+    // bounds the tile; in M the leading waves have slack.  The decisions are the same: between the end of C(t - 1) and
+    // the top of M(t) nobody writes this wave's k2s[], and seen[] is written again only by the thr_load that stands
+    // behind the arming.  A trailing wave that leaves at the top leaves ahead of it; the exit path publishes anyway.
+    // F::kRefreshAtTop false keeps refresh at the end of the compare and moves only the moves (ntq[] then lives across
+    // the barrier); it was timed and is the slower of the two.  Estimated before it ran, with a second lever that was not
+    // built: 3-7 % of the step.  Measured, best parent over worst branch at 1M x 1M: 1.024x and 1.028x on two GPUs
+    // ("FP6: arming back in M").
     typename X::Acc acc[H][2];
-    auto arm = [&](bool shared) {
-      refresh(shared);
+    auto set_acc = [&]() {
 #pragma unroll
       for (int h = 0; h < H; ++h) {
 #pragma unroll
@@ -1034,7 +1063,13 @@ __device__ __forceinline__ void wide_body(
         }
       }
     };
-    arm(true);  // tile 0
+    auto arm = [&](bool shared) {
+      refresh(shared);
+      set_acc();
+    };
+    // tile 0: armed here, or in its top with the rest (seen[] is complete either way: the vmcnt(0) above)
+    if constexpr (!F::kArmAtTop) arm(true);
+    else if constexpr (!F::kRefreshAtTop) refresh(true);
     if (any_inherited(seen)) {
       warm = F::kWarmTilesShared;
       skip_tiles = 0;
@@ -1058,6 +1093,7 @@ __device__ __forceinline__ void wide_body(
       a3[1] = lda(1);
       // every wave has read the last of tile tl - 1's features; only the trailing waves are behind the barrier after
       // which nobody reads its raw rows (the leading waves issue theirs behind the mid-tile barrier)
+      const unsigned long long t_iss0 = stamp();
       if (has_next) {
         const int nnext = min(F::kTileRows, row_end - row0 - F::kTileRows);
         if (trail) {
@@ -1068,6 +1104,7 @@ __device__ __forceinline__ void wide_body(
         }
         fnext += F::kFtileV4;
       }
+      const unsigned long long t_iss1 = stamp();
       const int nrows = min(F::kTileRows, row_end - row0);
       // The trailing waves leave after the tile whose flag was raised, before they bound a pair of this one (a leading
       // wave gets here with `bailed` zero: it looks at the flag behind the mid-tile barrier).  The loads just issued
@@ -1075,6 +1112,14 @@ __device__ __forceinline__ void wide_body(
       // bound, the exit path publishes anyway, and it waits for the loads.  The flag was asked for ahead of the two A
       // reads and is looked at under a counted wait, with them still in flight; the armed accumulators are dropped.
       if (__builtin_amdgcn_readfirstlane(bailed)) break;
+      // This tile's accumulators where the form arms in the top: ahead of the thr_load below, which writes seen[] again.
+      // The shared thresholds are published at tile 0 and every 128 rows, as at the end of the compare.
+      const unsigned long long t_arm0 = F::kArmAtTop ? stamp() : 0;
+      if constexpr (F::kArmAtTop) {
+        if constexpr (F::kRefreshAtTop) refresh((tl & (F::kThrEvery - 1)) == 0);
+        set_acc();
+      }
+      const unsigned long long t_arm1 = F::kArmAtTop ? stamp() : 0;
       // for the next tile; they land behind this tile's MFMAs.  Behind the branch: on the way out of the loop no load that
       // the compiler knows of is pending, so it asks for none at the loop's end, where a leading wave has the next tile's
       // raw rows in flight.
@@ -1100,7 +1145,8 @@ __device__ __forceinline__ void wide_body(
       __syncthreads();
       const unsigned long long t_cmp = stamp();
       if (!trail) {
-        // the flag of tile tl - 1 (its slot is all zero at tile 0), asked for here and looked at behind the sign fold;
+        // the flag of tile tl - 1 (its slot is all zero at tile 0), asked for here and, in the source, looked at behind the
+        // sign fold; the compiler waits for it ahead of the fold, and pinned behind it the FP6 step was 1-2 % slower;
         // the raw rows of tile tl + 1 go where the trailing waves have just finished C(tl - 1)
         bailed = lds_bail<F>[((tl + 1) & 1) + zero_v];
         if (has_next) {
@@ -1129,8 +1175,11 @@ __device__ __forceinline__ void wide_body(
       // landed at its mid-tile wait.  Armed behind the last tile too, where nobody reads them and nothing is published:
       // under `if (has_next)` the accumulators of the path not taken stay live across the drains, which need their
       // registers for the rows' pieces, and 50 registers spill.
+      // Where the form arms in the top, nothing of it stands here, or the refresh alone.
       const unsigned long long t_arm = stamp();
-      arm(has_next && ((tl + 1) & (F::kThrEvery - 1)) == 0);  // the shared thresholds move slowly: every 128 rows is enough
+      const bool share_next = has_next && ((tl + 1) & (F::kThrEvery - 1)) == 0;  // the shared thresholds move slowly: every 128 rows is enough
+      if constexpr (!F::kArmAtTop) arm(share_next);
+      else if constexpr (!F::kRefreshAtTop) refresh(share_next);
       const unsigned long long t_bar2 = stamp();
       __syncthreads();  // B_2tl+1 for the leading waves, B_2tl+2 for the trailing ones
       const unsigned long long t_end = stamp();
@@ -1139,8 +1188,9 @@ __device__ __forceinline__ void wide_body(
       ph[kPhVmWait] += t_bar - t_wait;
       ph[kPhMidBarrier] += t_cmp - t_bar;
       ph[kPhCompact] += (t_arm - t_cmp) - (ph[kPhDrain] - drained);
-      ph[kPhArm] += t_bar2 - t_arm;
+      ph[kPhArm] += (t_bar2 - t_arm) + (t_arm1 - t_arm0);  // the second part lies inside the top's count
       ph[kPhBarrier] += t_end - t_bar2;
+      ph[kPhIssue] += t_iss1 - t_iss0;
       ph[kPhLoop] += t_end - t_top;
       t_last = t_end;
       // A trailing wave asks for this tile's flag here, complete at the barrier it has just passed, and looks at it
@@ -1519,9 +1569,14 @@ int l1k2_prune_run(const uint8_t *d_x, const uint8_t *d_y, int xrows, int yrows,
 #ifdef SPV_L1K2_PHASE_STAMPS
   {
     // the narrow form's top holds its refresh and accumulator set-up as well, and its arming line is zero
-    static const char *const names[kPhases] = {"top: reads, stage issue", "MFMA run", "compare + compaction", "drains",
-                                               "vmcnt(0) wait", "barrier wait", "whole tile", "mid-tile barrier wait",
-                                               "arming the next tile"};
+    // and where the wide form armed: at the end of the compare (its own line of the tile), or inside the top, whose line
+    // then holds the arming's cycles as well
+    const char *const names[kPhases] = {"top: reads, stage issue", "MFMA run", "compare + compaction", "drains",
+                                        "vmcnt(0) wait", "barrier wait", "whole tile", "mid-tile barrier wait",
+                                        !(fp6 && Wide6::kArmAtTop) ? "arming (end of compare)"
+                                        : Wide6::kRefreshAtTop     ? "arming (inside the top)"
+                                                                   : "arming (moves in the top)",
+                                        "stage issue (in the top)"};
     std::vector<unsigned long long> h(nstamp);
     SPV_HIP_CHECK(hipStreamSynchronize(stream));
     SPV_HIP_CHECK(hipMemcpy(h.data(), d_stamps, nstamp * 8, hipMemcpyDeviceToHost));
