@@ -1224,6 +1224,13 @@ int spv_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, i
  *   d_ok     uint8[ntracks] or NULL: 1 iff the track is solved, X is finite, every usable observation has
  *            sign(det P[:, :3]) / |P[2, :3]|^2 * (P X)[2] / X[3] > 0 and err <= max_error (+inf: cheirality alone).
  *   d_nused  int32[ntracks] or NULL: the usable observations.
+ * Nothing is screened beyond "usable".  A usable observation whose (u, v) or whose camera holds a NaN or an infinity
+ * stays usable and counts in d_nused; its track has d_ok 0 and a d_X that is NaN or finite garbage, and no other track
+ * of the call notices.  A track whose A_t has rank 3 gets its null vector -- members of one set alone: that camera's
+ * centre, where every depth term is a rounding of 0 and d_ok and d_err are not determined --, one of rank 2 (the same
+ * observation over and over) some unit vector with ||A X|| <= 1e-13 sigma1.  All cameras times one power of two, or
+ * times -1, leave d_X, d_err, d_ok and d_nused the same bits while no intermediate leaves the double range (tested
+ * at 2^+-40); at 2^+-445 d_X, d_err and d_nused still meet the definition, d_ok does not (det P[:, :3] overflows).
  * Outputs are aligned with the inputs; nothing is compacted.  A track's results depend on its own members, d_geom and
  * the cameras alone: not on its neighbours, its place in the call or the form that solves it beyond the rounding
  * of the reduction order (tracks of at most two usable observations: not at all).
@@ -1296,6 +1303,12 @@ int spv_tracks_triangulate(const float *geom, const long long *seg_off, int nseg
  *   verdict  a row is an inlier of P iff |proj(P Xw) - (u, v)| <= max_error and the depth term of
  *            spv_tracks_triangulate_device's d_ok is positive: sign(det P[:, :3]) / |P[2, :3]|^2 (P Xw)[2] / Xw[3] > 0.
  *            The kernel compares squares and multiplies by 1 / Xw[3]; NaNs compare false, a non-finite P counts 0.
+ *            Rows are taken as they come.  A row with x[2] = 0, with a NaN, or with an all-zero Xw is an inlier of no
+ *            camera and spoils only the tries that sample it (their P is not finite, or finite garbage that is scored
+ *            like any other); Xw[3] = 0 makes the depth term +-inf, which passes where it is +inf.  A row of x times
+ *            +-2^k, all of Xw times one power of two (tested at 2^+-30): the same bits in every output; a negated Xw
+ *            row is the same point.  A degenerate subset (duplicates, coplanar or collinear points) gives a P that is
+ *            finite garbage or not finite, scored by the same verdict; a set of coplanar points may keep such a P.
  *   rule     on try order: the first try with count / (double) rows >= required_percent_inliers (success 1); failing
  *            that, with find_best_even_in_failure, the try with the most inliers -- at least one --, the earliest
  *            among equals (success 0); otherwise no model.  The result does not depend on how tries are cut into
