@@ -27,8 +27,10 @@ runs all of them through the many-pairs forms of the same steps, with every inte
     resect_fit_batch         pair with the most inliers is registered as K [I | 0] and K camera, the tracks it sees are
                              triangulated, every other view is resected from the points its keypoints belong to -- all
                              of them in one call -- and the tracks are triangulated again over all registered views.
-                             Chaining the other pairwise fits and their scales, and bundle adjustment, are not part of
-                             the library
+                             Chaining the other pairwise fits and their scales is not part of the library
+    bundle_adjust            (--bundle, with --resect) every registered camera as a pose K [R | t] (pose_from_camera),
+                             the two seed views fixed, and all other cameras and all ok track points refined together
+                             over all their observations under a Huber loss of the --resect width
 
 Only the small per-pair results (the fits, the offsets) come back on the way; the points stay on the device until
 they are asked for.  The SIFT tables (rows of 132 float32: x, y, sigma, angle, 128 descriptor values) are synthetic
@@ -37,6 +39,7 @@ before l1k2_batch, which examples/sift_tables_from_images.py shows.
 
     python examples/multiview_from_sift_tables.py [--images 6] [--points 2000] [--matcher {l1k2,cascade}] [--rectify]
                                                   [--guided PIXELS] [--tracks] [--triangulate PIXELS] [--resect PIXELS]
+                                                  [--bundle]
 """
 import argparse
 import os
@@ -242,6 +245,46 @@ def report_resection(reg, K, scene_cameras):
         int(ok.sum()), len(ok), float(np.nanmedian(err[of_ok])) if of_ok.any() else float('nan')))
 
 
+def bundle_views(out, reg, K, huber):
+    """Bundle adjustment of what resect_views registered: every camera goes through pose_from_camera, the two seed
+    views are held fixed, the ok track points of the last triangulation and all other cameras are refined together
+    (Huber width `huber` pixels).  Returns (cameras: one pixel camera K [R | t] per view or None, X, info) with
+    `bundle_adjust`'s X and info (want_err)."""
+    from spectavi_amd import device as spv
+    from spectavi_amd import mvg
+    ti, (track_off, members) = out['track_inputs'], out['tracks'][:2]
+    poses = []
+    for P in reg['cameras']:
+        if P is None:
+            poses.append(None)
+            continue
+        R, t = mvg.pose_from_camera(P, K)
+        poses.append(np.hstack([R, t[:, None]]))
+    fixed = [v in reg['seed'] for v in range(len(poses))]
+    X, _, ok, _ = reg['points']
+    P, Xo, info = spv.bundle_adjust(ti['geom'], ti['seg_off'], K, poses, track_off, members, X, use=ok, fixed=fixed, huber=huber,
+                                    want_err=True)
+    return [None if p is None else K @ P[v] for v, p in enumerate(poses)], Xo, info
+
+
+def report_cameras(label, cameras, reg, K, scene_cameras, err, of_track):
+    """report_resection's figures for a set of cameras: the median residual over the observations `of_track` selects,
+    and every non-seed view's rotation and centre offsets against the scene in the gauge of the seed pair."""
+    d, q = reg['seed']
+    Rd, Cd = camera_parts(scene_cameras[d], K)
+    Cq_scene = Rd @ (camera_parts(scene_cameras[q], K)[1] - Cd)
+    scale = np.linalg.norm(camera_parts(reg['cameras'][q], K)[1]) / np.linalg.norm(Cq_scene)
+    print("%s: median residual %.3e px over %d observations" % (label, float(np.nanmedian(err[of_track])), int(of_track.sum())))
+    for v in reg['views']:
+        if cameras[v] is None:
+            continue
+        R, C = camera_parts(cameras[v], K)
+        Rs, Cs = camera_parts(scene_cameras[v], K)
+        Rs, Cs = Rs @ Rd.T, scale * (Rd @ (Cs - Cd))
+        angle = np.degrees(np.arccos(np.clip((np.trace(R @ Rs.T) - 1) / 2, -1, 1)))
+        print("%s: view %d rotation off by %.4f deg, centre off by %.3e baselines" % (label, v, angle, np.linalg.norm(C - Cs)))
+
+
 def rectify_pairs(out, K, images):
     """Step 5 for every pair with a model: images is a list of CUDA tensors [960, 1280], one per view.  The fits'
     cameras are calibrated and map the database view's coordinates, so the pixel cameras are K [I|0] for the
@@ -304,6 +347,7 @@ def main():
                     help="with --tracks: one point per track from the scene's own cameras, ok within this residual")
     ap.add_argument("--resect", type=float, default=None, metavar="PIXELS",
                     help="with --tracks: register every view from the best fitted pair on, inliers within this residual")
+    ap.add_argument("--bundle", action="store_true", help="with --resect: bundle adjustment of the registered views")
     a = ap.parse_args()
     import torch
     tables, K, cameras = synthetic_sift_views(a.seed, a.images, a.points, return_cameras=True)
@@ -326,6 +370,20 @@ def main():
             dt_reg = time.perf_counter() - s
         report_resection(reg, K, cameras)
         print("seed, triangulation, resection of %d views, triangulation: %.1f ms (warm)" % (len(reg['views']), dt_reg * 1e3))
+        if a.bundle:
+            for rep in range(2):
+                torch.cuda.synchronize()
+                s = time.perf_counter()
+                cams, Xb, info = bundle_views(out, reg, K, a.resect)
+                torch.cuda.synchronize()
+                dt_ba = time.perf_counter() - s
+            active = info['active'].cpu().numpy() != 0
+            of_track = np.repeat(active, np.diff(reg['track_off']))
+            report_cameras("before the bundle", reg['cameras'], reg, K, cameras, reg['points'][1].cpu().numpy(), of_track)
+            report_cameras("after the bundle", cams, reg, K, cameras, info['err'].cpu().numpy(), of_track)
+            print("bundle adjustment: %d tracks, %d observations, %d steps (%d accepted, stop: %s), cost %.6e -> %.6e, "
+                  "%.1f ms (warm)" % (info['tracks'], info['observations'], info['steps'], info['accepted'], info['stop'],
+                                      info['first_cost'], info['last_cost'], dt_ba * 1e3))
     n = int(out['out_off'][-1])
     E = out['X'][:n, :3] / out['X'][:n, 3:]
     print("%d views, %.1f ms (warm); depth of the points: median %.2f" % (a.images, dt * 1e3, float(E[:, 2].median()) if n else 0.0))

@@ -1200,8 +1200,8 @@ int spv_tracks_batch(const long long *seg_off, int nseg, const int32_t *pairs, i
 /* N-view DLT of every track (tracks_triangulate.hip): one 3-D point per track from all its observations, a residual
  * per observation and a verdict per track, for a caller who has one camera per set (a calibrated rig, an earlier
  * reconstruction, a pose graph of their own, or spv_resect_fit_batch_device below for views that see points already
- * triangulated).  The cameras are taken as given: chaining pairwise fits into global cameras and bundle adjustment
- * are not part of the library.  The reference has no such step.
+ * triangulated).  The cameras are taken as given: chaining pairwise fits into global cameras is not part of the
+ * library; spv_bundle_adjust_device below refines cameras and points together.  The reference has no such step.
  *   d_geom   float32[total_rows, 4]: x, y, sigma, angle of every row, as spv_sift_split_device writes them; only x
  *            and y are read, widened to double.
  *   seg_off, nseg: host, the seg_off of spv_l1k2_batch_device.
@@ -1333,7 +1333,8 @@ int spv_tracks_triangulate(const float *geom, const long long *seg_off, int nseg
  * rows and maximum_tries > 0; a sample out of range; a pointer not aligned to its element size.
  * spv_resect_fit_batch: host pointers (inlier_mask, try_cameras, try_inliers on the host, each may be NULL), on the
  * first selected device; touches no device when no set has 6 rows or maximum_tries is 0.
- * Not part of the op: a refit of the winner on all its inliers, a calibrated P3P solver, bundle adjustment. */
+ * Not part of the op: a refit of the winner on all its inliers, a calibrated P3P solver.  The joint refinement of
+ * cameras and points is spv_bundle_adjust_device. */
 int spv_resect_gather_device(const float *d_geom, const int32_t *d_track, const long long *seg_off, int nseg,
                              const int32_t *views, int nviews, const double *d_X, const uint8_t *d_ok, int ntracks,
                              long long capacity, double *d_x, double *d_Xw, int32_t *d_rows, long long *d_view_off,
@@ -1351,6 +1352,90 @@ int spv_resect_fit_batch(const double *x, const double *Xw, const long long *vie
                          int32_t *tries_run, uint8_t *inlier_mask, double *try_cameras, int32_t *try_inliers);
 int spv_resect_fit_batch_plan(const long long *view_off, int nviews, int maximum_tries, int compute_units,
                               long long out[4], int32_t *items, long long items_cap);
+
+/* Bundle adjustment (bundle_adjust.hip): Levenberg-Marquardt refinement of all free cameras and all participating track
+ * points over all observations, by a matrix-free Schur complement and preconditioned conjugate gradients (Wu et al.,
+ * "Multicore Bundle Adjustment"; Agarwal et al., "Bundle Adjustment in the Large").  The reference has no such step;
+ * tests/bundle_model.py restates this text in numpy with dense normal equations.
+ *   d_geom, seg_off, nseg, track_off, ntracks, d_members, nmembers: as in spv_tracks_triangulate_device.
+ *   d_X      double[ntracks, 4], in and out: spv_tracks_triangulate_device's points.
+ *   d_use    uint8[ntracks] or NULL: e.g. spv_tracks_triangulate_device's d_ok.
+ *   K        host double[nseg, 9]: row-major, upper triangular, K[8] == 1, K[3] == K[6] == K[7] == 0, K[0] and K[4]
+ *            non-zero, all finite.  Held fixed.
+ *   poses    host double[nseg, 12], in and out: row-major [R | t].
+ *   mode     host int32[nseg]: 0 the set has no camera (its rows of K and poses are not read), 1 free, 2 fixed (read,
+ *            its observations count, never moved).
+ * Residual of an observation of the point X (Euclidean: d_X[:3] / d_X[3]) in set s: y = R X + t, (u, v) = (K0 y0/y2 +
+ * K1 y1/y2 + K2, K4 y1/y2 + K5), r = (u, v) - (double)d_geom[row][0..1].  Loss: rho(|r|) = r^2 / 2 for |r| <= huber,
+ * huber (|r| - huber / 2) beyond; huber = +inf is plain least squares.  Robustification is first order: the weight is
+ * w = min(1, huber / |r|), Jacobian rows and residual are scaled by sqrt(w) (J~, r~), there is no second-order
+ * correction, and the cost reported and compared is F = sum rho.
+ * Parameters: a free camera has six, R <- Exp(omega) R (Rodrigues) and t <- t + tau, linearised at omega = 0:
+ * dy/d omega = -[R X]x, dy/d tau = I, dy/dX = R; a point has its three Euclidean coordinates.  p (+) delta applies both.
+ * Who takes part: a member is usable under spv_tracks_triangulate_device's rule with "has a camera" = mode != 0;
+ * nothing else is dereferenced, garbage members give ignored observations and never an access out of bounds.  A track
+ * takes part iff d_use is NULL or non-zero there, its d_X row is finite with d_X[3] != 0 (and a finite quotient), it has
+ * at least 2 usable observations, and at the starting parameters every one of them has a finite residual and y2 > 0.
+ * A track that does not take part is left untouched bit for bit and contributes nothing; one that does has its d_X
+ * row written as (X, Y, Z, 1).  d_active uint8[ntracks] or NULL: which tracks took part.  A free camera with no
+ * observation among the participating tracks does not move: its row of poses comes back bit for bit, as do the rows
+ * of mode 2 and mode 0.
+ * Loop, with g = J~^T r~, H = J~^T J~ and D = diag(H), every entry clamped to [1e-6, 1e32]:
+ *   lambda = lambda0; linearise; F = cost
+ *   for step in 0 .. max_steps - 1:
+ *     if max |g| <= gtol: stop (gradient, reason 1)
+ *     solve (H + lambda D) delta = -g
+ *     F' = cost at p (+) delta; +inf if any participating observation has y2 <= 0 or a non-finite residual there
+ *     if F' < F: accept, lambda = max(lambda / 10, 1e-15), linearise again; if (F - F') / F <= ftol: stop (cost, 2)
+ *     else:      reject, lambda *= 10; if lambda > 1e15: stop (damping, 3)
+ *   (reason 0: max_steps ran out)
+ * Solve: the point blocks V_t + lambda D_t (3x3) are inverted in closed form per track; the reduced camera system
+ * S dc = b, S = (U + lambda Dc) - E (V + lambda Dp)^-1 E^T, b = -gc + E (V + lambda Dp)^-1 gp, is never formed:
+ * conjugate gradients from x0 = 0 apply S as (U + lambda Dc) dc - E (Vl^-1 (E^T dc)), preconditioned by the inverses of
+ * the 6x6 blocks U_s + lambda D_s (Cholesky, once per step), and stop at |r| <= cg_tol |b| (r the true recurrence
+ * residual), after cg_max iterations, or when p^T S p or r^T z is not positive; then dp = -Vl^-1 (gp + E^T dc).
+ * Outputs: poses on the host, d_X on the device, d_err double[nmembers] or NULL with spv_tracks_triangulate_device's
+ * meaning at the final parameters (|r| of every observation of a participating track, NaN elsewhere), trace host
+ * double[max_steps, 6] or NULL, row = (F before, F', lambda used, CG iterations, accepted 0/1, max |g| before), unused
+ * rows NaN, and info host double[7] = (steps run, steps accepted, stop reason, participating tracks, participating
+ * observations, first F, last F).
+ * Kernels: track-major ones take one lane per track of at most 16 members and one wave per longer track (the lanes'
+ * sums meet in an xor butterfly); view-major ones walk a stable counting sort of the participating observations by
+ * set, built once per call from scans, each camera's list cut into chunks of 1024 observations, one workgroup per
+ * chunk, the chunk partials added in chunk order.  The Jacobians are made again wherever they are needed, not stored
+ * (measured faster than streaming 144 bytes per observation twice per CG iteration, with the same bits).  There are no
+ * floating-point atomics and no order that depends on timing: the op returns the same bits from run to run.  CG scalars
+ * and a `done` flag stay on the device, a step's cg_max iterations are enqueued back to back and become no-ops once
+ * `done` is set; the call waits for `stream` twice before the loop (the view-major order, the first cost), once per
+ * step and once after the loop, to bring the poses back.  F and max |g| are summed over the tracks in two stages
+ * (partials of 2048 tracks, then the partials), in a fixed order.  spv_profile_read names: "bundle_mark", "bundle_sort", "bundle_linearise", "bundle_cam_sum",
+ * "bundle_gradient_max", "bundle_cost_sum", "bundle_point_blocks", "bundle_precondition", "bundle_cg_start",
+ * "bundle_cg_track", "bundle_cg_cam", "bundle_cg_step", "bundle_move", "bundle_cost", "bundle_commit", "bundle_finish".
+ * d_ws: spv_bundle_adjust_workspace_bytes(nseg, ntracks, nmembers) bytes, aligned to 256.
+ * spv_bundle_adjust_plan: host only, touches no device.  out = {lane-form tracks, wave-form tracks, view-major chunk
+ * size, chunks, longest track}; chunks counts those of the mode 1 sets (every set where mode is NULL) when every usable
+ * member of a track with two or more takes part, and is 0 where members (host int32[nmembers, 2]) is NULL, in which
+ * case seg_off, nseg and mode are not read.
+ * SPV_ERR_INVALID, nothing launched: the seg_off and track_off rules of spv_tracks_triangulate_device; nseg *
+ * ceil(nmembers / 256) >= 2^31; a mode outside {0, 1, 2}; a K row that breaks the shape above; an R with |R^T R - I|
+ * or |det R - 1| above 1e-6, or non-finite, in a set with mode != 0; a NaN or non-positive huber; a NaN or negative
+ * lambda0, ftol, gtol or cg_tol; a negative max_steps or cg_max; a NULL required pointer (as there, and K, poses, mode
+ * where nseg > 0, info); an output not aligned to its element size; a workspace that is missing, short or misaligned.
+ * spv_bundle_adjust: host pointers (X, use, err, active on the host), on the first selected device; touches no device
+ * when ntracks is 0 or no set has mode != 0. */
+int spv_bundle_adjust_plan(const long long *track_off, int ntracks, const int32_t *members, const long long *seg_off,
+                           int nseg, const int32_t *mode, long long out[5]);
+size_t spv_bundle_adjust_workspace_bytes(int nseg, int ntracks, long long nmembers);
+int spv_bundle_adjust_device(const float *d_geom, const long long *seg_off, int nseg, const double *K, double *poses,
+                             const int32_t *mode, const long long *track_off, int ntracks, const int32_t *d_members,
+                             long long nmembers, double *d_X, const uint8_t *d_use, double huber, int max_steps,
+                             double lambda0, double ftol, double gtol, double cg_tol, int cg_max, double *d_err,
+                             uint8_t *d_active, double *trace, double *info, void *d_ws, size_t ws_bytes, void *stream);
+int spv_bundle_adjust(const float *geom, const long long *seg_off, int nseg, const double *K, double *poses,
+                      const int32_t *mode, const long long *track_off, int ntracks, const int32_t *members,
+                      long long nmembers, double *X, const uint8_t *use, double huber, int max_steps, double lambda0,
+                      double ftol, double gtol, double cg_tol, int cg_max, double *err, uint8_t *active, double *trace,
+                      double *info);
 
 /* normalize_to_ubyte_and_multiple_16_dim (reference spectavi/feature.py:384-407) for a float32
  * input, bit for bit what numpy computes: per-column de-mean (numpy's row-ordered float32 sum),

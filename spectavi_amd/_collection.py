@@ -137,6 +137,62 @@ def listed_cameras(Ps, n, name, exc, needed=None):
     return cams, have
 
 
+BUNDLE_STOPS = ("max_steps", "gradient", "cost", "damping")   # spv_bundle_adjust_device's stop reasons, by number
+
+
+def bundle_cameras(K, poses, fixed, nseg, per="set"):
+    """The camera tables of spv_bundle_adjust_device: K one [3,3] or one per set -> float64[nseg, 9]; poses a list or
+    array of [3,4] = [R | t] whose None entries are sets without a camera -> float64[nseg, 12]; fixed (None, or one
+    switch per set) -> mode int32[nseg] of 0 no camera / 1 free / 2 fixed.  ValueError for what the library would
+    refuse in K or in a rotation, with its bound of 1e-6."""
+    if len(poses) != nseg:
+        raise ValueError("poses must hold one [3,4] pose or None per %s" % per)
+    P, have = listed_cameras(poses, nseg, "poses", ValueError)
+    fixed = np.zeros(nseg, bool) if fixed is None else np.asarray(fixed).reshape(-1) != 0
+    if fixed.size != nseg:
+        raise ValueError("fixed must hold one value per %s" % per)
+    mode = np.where(have == 0, 0, np.where(fixed, 2, 1)).astype(np.int32)
+    try:
+        K = np.asarray(K, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("K must be one [3,3] matrix, or one per %s" % per)
+    if K.shape == (3, 3):
+        K = np.broadcast_to(K, (nseg, 3, 3))
+    if K.shape != (nseg, 3, 3):
+        raise ValueError("K must be one [3,3] matrix, or one per %s" % per)
+    K = np.ascontiguousarray(K).reshape(nseg, 9)
+    for s in np.flatnonzero(mode):
+        k, R = K[s], P[s].reshape(3, 4)[:, :3]
+        if not (np.all(np.isfinite(k)) and k[8] == 1 and k[3] == 0 and k[6] == 0 and k[7] == 0 and k[0] != 0 and k[4] != 0):
+            raise ValueError("K must be finite and upper triangular with K[2,2] = 1 and non-zero focal lengths")
+        if not (np.all(np.isfinite(P[s])) and np.abs(R.T @ R - np.eye(3)).max() <= 1e-6
+                and abs(np.linalg.det(R) - 1) <= 1e-6):
+            raise ValueError("poses must be [R | t] with R a rotation (to 1e-6)")
+    return K, P, mode
+
+
+def bundle_options(huber, max_steps, lambda0, ftol, gtol, cg_tol, cg_max, mode):
+    """The scalar arguments of spv_bundle_adjust_device under its rules; cg_max None -> 6 * free cameras + 10."""
+    huber, lambda0, ftol, gtol, cg_tol = (float(v) for v in (huber, lambda0, ftol, gtol, cg_tol))
+    if not huber > 0:
+        raise ValueError("huber must be positive")
+    if not (lambda0 >= 0 and ftol >= 0 and gtol >= 0 and cg_tol >= 0):
+        raise ValueError("lambda0, ftol, gtol and cg_tol must be non-negative numbers")
+    cg_max = 6 * int(np.sum(mode == 1)) + 10 if cg_max is None else int(cg_max)
+    max_steps = int(max_steps)
+    if max_steps < 0 or cg_max < 0 or max_steps >= 2 ** 31 or cg_max >= 2 ** 31:
+        raise ValueError("max_steps and cg_max must be non-negative")
+    return huber, max_steps, lambda0, ftol, gtol, cg_tol, cg_max
+
+
+def bundle_info(info, trace):
+    """spv_bundle_adjust_device's info and trace as the wrappers return them."""
+    steps = int(info[0])
+    return {'steps': steps, 'accepted': int(info[1]), 'stop': BUNDLE_STOPS[int(info[2])], 'tracks': int(info[3]),
+            'observations': int(info[4]), 'first_cost': float(info[5]), 'last_cost': float(info[6]),
+            'trace': trace[:steps].copy()}
+
+
 def seeds_and_tries(seeds, samples, maximum_tries, n):
     """The subsets' arguments of spv_ransac_fit_batch: (seeds uint64[n] -- zeros by default, not looked at when
     samples int32[n, ntries, 7] are given --, maximum_tries in [0, 7e8], which samples set to their ntries)."""

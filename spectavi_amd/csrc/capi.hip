@@ -383,6 +383,41 @@ int host_tracks_triangulate(const float *geom, const long long *seg_off, int nse
   return SPV_OK;
 }
 
+// Bundle adjustment through host pointers, on the first selected device: geom, the members, X and use up, one
+// bundle_adjust_run in a workspace of its own, X, err and active back.  A call without a track or without a camera
+// touches no device.
+int host_bundle_adjust(const float *geom, const long long *seg_off, int nseg, const double *K, double *poses, const int32_t *mode,
+                       const long long *track_off, int ntracks, const int32_t *members, long long nmembers, double *X,
+                       const uint8_t *use, const BundleAdjustOptions &o, double *err, uint8_t *active, double *trace, double *info) {
+  SPV_TRY(bundle_adjust_check(geom, seg_off, nseg, K, poses, mode, track_off, ntracks, members, nmembers, X, o, err, trace, info));
+  if (!bundle_adjust_has_work(mode, nseg, ntracks)) {
+    bundle_adjust_idle(o, trace, info);
+    if (active) memset(active, 0, (size_t)ntracks);
+    if (err)
+      for (long long i = 0; i < nmembers; ++i) err[i] = __builtin_nan("");
+    return SPV_OK;
+  }
+  hipStream_t st;
+  SPV_TRY(host_begin(device_list()[0], &st));
+  const size_t gb = (size_t)seg_off[nseg] * 4 * sizeof(float), mb = (size_t)nmembers * 2 * sizeof(int32_t);
+  const size_t nt = (size_t)ntracks, nm = (size_t)nmembers, wsb = bundle_adjust_workspace_bytes(nseg, ntracks, nmembers);
+  DevBuf dg, dm, dX, du, de, da, ws;
+  SPV_TRY(alloc_all({{&dg, gb}, {&dm, mb}, {&dX, nt * 4 * sizeof(double)}, {&du, use ? nt : 0}, {&de, err ? nm * sizeof(double) : 0},
+                     {&da, active ? nt : 0}, {&ws, wsb}}));
+  SPV_TRY(dg.copy_in(geom, gb, st));
+  SPV_TRY(dm.copy_in(members, mb, st));
+  SPV_TRY(dX.copy_in(X, nt * 4 * sizeof(double), st));
+  if (use) SPV_TRY(du.copy_in(use, nt, st));
+  SPV_TRY(bundle_adjust_run(dg.as<float>(), seg_off, nseg, K, poses, mode, track_off, ntracks, dm.as<int32_t>(), nmembers,
+                            dX.as<double>(), use ? du.as<uint8_t>() : nullptr, o, err ? de.as<double>() : nullptr,
+                            active ? da.as<uint8_t>() : nullptr, trace, info, ws.p, wsb, st));
+  SPV_TRY(dX.copy_out(X, nt * 4 * sizeof(double), st));
+  if (err) SPV_TRY(de.copy_out(err, nm * sizeof(double), st));
+  if (active) SPV_TRY(da.copy_out(active, nt, st));
+  SPV_HIP_CHECK(hipStreamSynchronize(st));
+  return SPV_OK;
+}
+
 // The many-sets RANSAC through host pointers, on the first selected device: both arrays up, one
 // ransac_fit_batch_run.  A collection in which no set runs touches no device.
 int host_ransac_fit_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,
@@ -1680,6 +1715,46 @@ int spv_tracks_triangulate(const float *geom, const long long *seg_off, int nseg
   return host_api([&] {
     return host_tracks_triangulate(geom, seg_off, nseg, cams, use_set, track_off, ntracks, members, nmembers, max_error, X, err,
                                    ok, nused);
+  });
+}
+int spv_bundle_adjust_plan(const long long *track_off, int ntracks, const int32_t *members, const long long *seg_off, int nseg,
+                           const int32_t *mode, long long out[5]) {
+  return api([&] {
+    if (ntracks < 0 || nseg < 0 || !out) return set_error(SPV_ERR_INVALID, "bad arguments");
+    SPV_TRY(check_offsets(track_off, ntracks, "track_off"));
+    if (members) SPV_TRY(check_offsets(seg_off, nseg, "seg_off"));
+    BundleAdjustPlan pl;
+    bundle_adjust_plan(track_off, ntracks, members, seg_off, nseg, mode, &pl);
+    out[0] = pl.lane_tracks;
+    out[1] = pl.wave_tracks;
+    out[2] = pl.chunk;
+    out[3] = pl.chunks;
+    out[4] = pl.longest;
+    return (int)SPV_OK;
+  });
+}
+size_t spv_bundle_adjust_workspace_bytes(int nseg, int ntracks, long long nmembers) {
+  return (nseg < 0 || ntracks < 0 || nmembers < 0) ? 0 : bundle_adjust_workspace_bytes(nseg, ntracks, nmembers);
+}
+int spv_bundle_adjust_device(const float *d_geom, const long long *seg_off, int nseg, const double *K, double *poses,
+                             const int32_t *mode, const long long *track_off, int ntracks, const int32_t *d_members,
+                             long long nmembers, double *d_X, const uint8_t *d_use, double huber, int max_steps, double lambda0,
+                             double ftol, double gtol, double cg_tol, int cg_max, double *d_err, uint8_t *d_active, double *trace,
+                             double *info, void *d_ws, size_t ws_bytes, void *stream) {
+  return api([&] {
+    const BundleAdjustOptions o{huber, lambda0, ftol, gtol, cg_tol, max_steps, cg_max};
+    return bundle_adjust_run(d_geom, seg_off, nseg, K, poses, mode, track_off, ntracks, d_members, nmembers, d_X, d_use, o, d_err,
+                             d_active, trace, info, d_ws, ws_bytes, static_cast<hipStream_t>(stream));
+  });
+}
+int spv_bundle_adjust(const float *geom, const long long *seg_off, int nseg, const double *K, double *poses, const int32_t *mode,
+                      const long long *track_off, int ntracks, const int32_t *members, long long nmembers, double *X,
+                      const uint8_t *use, double huber, int max_steps, double lambda0, double ftol, double gtol, double cg_tol,
+                      int cg_max, double *err, uint8_t *active, double *trace, double *info) {
+  return host_api([&] {
+    const BundleAdjustOptions o{huber, lambda0, ftol, gtol, cg_tol, max_steps, cg_max};
+    return host_bundle_adjust(geom, seg_off, nseg, K, poses, mode, track_off, ntracks, members, nmembers, X, use, o, err, active,
+                              trace, info);
   });
 }
 int spv_ratio_test(const uint64_t *idx, const void *dist, int dist_is_float, int yrows,

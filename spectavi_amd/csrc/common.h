@@ -655,6 +655,33 @@ int resect_fit_batch_run(const double *d_x, const double *d_Xw, const long long 
                          int32_t *n_inliers, int32_t *best_try, int32_t *tries_run, unsigned char *d_inlier_mask,
                          double *d_try_cameras, int32_t *d_try_inliers, hipStream_t stream);
 
+// ---- Bundle adjustment of cameras and track points (bundle_adjust.hip) -----------------------
+struct BundleAdjustOptions {
+  double huber, lambda0, ftol, gtol, cg_tol;
+  int max_steps, cg_max;
+};
+// Which tracks take which form, the view-major chunk size and, where the host has the members, the chunks of the free
+// cameras when every usable member of a track of two or more takes part (host only).
+struct BundleAdjustPlan {
+  long long lane_tracks = 0, wave_tracks = 0, chunk = 0, chunks = 0, longest = 0;
+  std::vector<int32_t> wave_list;  // the wave-form tracks, ascending
+};
+void bundle_adjust_plan(const long long *track_off, int ntracks, const int32_t *members, const long long *seg_off, int nseg,
+                        const int32_t *mode, BundleAdjustPlan *plan);
+size_t bundle_adjust_workspace_bytes(int nseg, int ntracks, long long nmembers);
+// SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
+int bundle_adjust_check(const void *geom, const long long *seg_off, int nseg, const double *K, const double *poses,
+                        const int32_t *mode, const long long *track_off, int ntracks, const void *members, long long nmembers,
+                        const void *X, const BundleAdjustOptions &o, const void *err, const void *trace, const void *info);
+// Whether a checked call has a track and a camera; the trace and info of one that has not.
+bool bundle_adjust_has_work(const int32_t *mode, int nseg, int ntracks);
+void bundle_adjust_idle(const BundleAdjustOptions &o, double *trace, double *info);
+// Host and device outputs as in include/spectavi_amd.h.  Waits for `stream` twice before the loop and once per step.
+int bundle_adjust_run(const float *d_geom, const long long *seg_off, int nseg, const double *K, double *poses, const int32_t *mode,
+                      const long long *track_off, int ntracks, const int32_t *d_members, long long nmembers, double *d_X,
+                      const uint8_t *d_use, const BundleAdjustOptions &o, double *d_err, uint8_t *d_active, double *trace,
+                      double *info, void *d_ws, size_t ws_bytes, hipStream_t stream);
+
 template <typename Run>
 void fill_batch_round(const std::vector<Run> &run, int max_tries, int round_tries, long long round_work,
                       long long work_per_row, int per_try, std::vector<RansacBatchSlot> *slots, std::vector<int> *who) {

@@ -1081,6 +1081,83 @@ def triangulate_tracks(geom, seg_off, cameras, track_off, members, max_error=flo
     return X, err, ok, nused
 
 
+def bundle_adjust_plan(track_off, members=None, seg_off=None, mode=None):
+    """How bundle_adjust() lays a collection out (spv_bundle_adjust_plan; host only, no device touched): dict of
+    lane_tracks, wave_tracks, chunk (observations of a view-major chunk), chunks and longest.  chunks needs the host
+    members int32 [nmembers, 2] and seg_off, and counts the chunks of the free sets (mode 1; every set without mode)
+    when every usable member of a track with two or more takes part; it is 0 without members."""
+    off = col.offsets(track_off, "track_off")
+    mem = seg = md = None
+    if members is not None:
+        mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1, 2)
+        if len(mem) != off[-1]:
+            raise ValueError("track_off ends at %d, members has %d rows" % (off[-1], len(mem)))
+        seg = col.offsets(seg_off, "seg_off")
+        if mode is not None:
+            md = np.ascontiguousarray(mode, dtype=np.int32).reshape(-1)
+            if md.size != seg.size - 1:
+                raise ValueError("mode must hold one value per set")
+    out = (ct.c_longlong * 5)()
+    check(clib.spv_bundle_adjust_plan(off.ctypes.data, off.size - 1, _ptr(mem), _ptr(seg), 0 if seg is None else seg.size - 1,
+                                      _ptr(md), out))
+    return dict(lane_tracks=int(out[0]), wave_tracks=int(out[1]), chunk=int(out[2]), chunks=int(out[3]), longest=int(out[4]))
+
+
+def bundle_adjust(geom, seg_off, K, poses, track_off, members, X, use=None, fixed=None, huber=float("inf"), max_steps=50,
+                  lambda0=1e-4, ftol=1e-10, gtol=1e-10, cg_tol=1e-8, cg_max=None, want_err=False, workspace=None):
+    """Levenberg-Marquardt refinement of cameras and track points over all observations (spv_bundle_adjust_device):
+    geom, seg_off, (track_off, members) as `triangulate_tracks` takes them, X CUDA float64 [ntracks, 4] its points
+    (not modified: the refined points are returned), use an optional per-track switch (CUDA uint8, e.g. its ok), K
+    one [3,3] calibration or one per set (held fixed), poses one [3,4] = [R | t] per set, None for a set without a
+    camera, fixed an optional per-set switch: a fixed camera's observations count but it is never moved.  huber is
+    the width of the robust loss in pixels (inf: least squares); cg_max None means 6 * free cameras + 10.
+
+    Returns (poses ndarray [nseg,3,4] -- zeros for sets without a camera --, X CUDA float64 [ntracks,4] with (X, Y, Z,
+    1) in the rows of the tracks that took part and the input's bits elsewhere, info): info has steps, accepted,
+    stop ('max_steps', 'gradient', 'cost' or 'damping'), tracks, observations, first_cost, last_cost, trace
+    [steps, 6] = (F before, F', lambda, CG iterations, accepted, max |g|), active (CUDA uint8 [ntracks]) and, with
+    want_err, err (CUDA float64 [nmembers]: the residual norm of every participating observation, NaN elsewhere).
+    The same inputs give the same bits.  Waits for the stream once per step."""
+    if not isinstance(geom, torch.Tensor) or geom.dtype != torch.float32 or geom.dim() != 2 or geom.shape[1] != 4:
+        raise ValueError("geom must be a float32 tensor [total_rows, 4]")
+    if not isinstance(members, torch.Tensor) or members.dtype != torch.int32 or members.dim() != 2 or members.shape[1] != 2:
+        raise ValueError("members must be an int32 tensor [nmembers, 2]")
+    seg = col.offsets(seg_off, "seg_off", geom.shape[0], "geom")
+    nseg = seg.size - 1
+    off = col.offsets(track_off, "track_off", members.shape[0], "members")
+    nt, nm = off.size - 1, int(members.shape[0])
+    if not isinstance(X, torch.Tensor) or X.dtype != torch.float64 or tuple(X.shape) != (nt, 4):
+        raise ValueError("X must be a float64 tensor [ntracks, 4]")
+    if use is not None and (not isinstance(use, torch.Tensor) or use.dtype != torch.uint8 or tuple(use.shape) != (nt,)):
+        raise ValueError("use must be a uint8 tensor [ntracks]")
+    Ks, P, mode = col.bundle_cameras(K, poses, fixed, nseg)
+    huber, max_steps, lambda0, ftol, gtol, cg_tol, cg_max = col.bundle_options(huber, max_steps, lambda0, ftol, gtol,
+                                                                               cg_tol, cg_max, mode)
+    _need(geom, torch.float32, "geom")
+    _need(members, torch.int32, "members")
+    _need(X, torch.float64, "X")
+    if use is not None:
+        _need(use, torch.uint8, "use")
+    dev = geom.device
+    Xo = X.clone()
+    err = torch.empty(nm, dtype=torch.float64, device=dev) if want_err else None
+    active = torch.empty(nt, dtype=torch.uint8, device=dev)
+    trace, info = np.full((max_steps, 6), np.nan), np.zeros(7)
+    nbytes = clib.spv_bundle_adjust_workspace_bytes(nseg, nt, nm)
+    with _on_device_of(geom, members, X) as stream:
+        ws = (workspace or _default_ws).get(nbytes, dev)
+        check(clib.spv_bundle_adjust_device(
+            geom.data_ptr(), seg.ctypes.data, nseg, Ks.ctypes.data, P.ctypes.data, mode.ctypes.data, off.ctypes.data, nt,
+            members.data_ptr(), nm, Xo.data_ptr(), use.data_ptr() if use is not None else None, huber, max_steps, lambda0,
+            ftol, gtol, cg_tol, cg_max, err.data_ptr() if want_err else None, active.data_ptr(), trace.ctypes.data,
+            info.ctypes.data, ws.data_ptr(), ws.numel(), stream))
+    out = col.bundle_info(info, trace)
+    out['active'] = active
+    if want_err:
+        out['err'] = err
+    return P.reshape(nseg, 3, 4), Xo, out
+
+
 def _resect_gather_args(geom_shape, seg_off, views, track_shape, X_shape, ok_shape, capacity):
     """seg_off -> int64[nseg + 1], views -> int32[nviews] (each in [0, nseg)), capacity (None: the rows of the listed
     views); ValueError for anything spv_resect_gather_device would reject or that does not describe geom [total_rows,

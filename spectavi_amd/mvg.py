@@ -462,6 +462,90 @@ def triangulate_tracks(coords, sizes, cameras, track_off, members, max_error=flo
     return X, err, ok, nused
 
 
+def camera_from_pose(R, t, K):
+    """The 3x4 pixel camera K [R | t]."""
+    R, t, K = np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64).reshape(3), np.asarray(K, dtype=np.float64)
+    if R.shape != (3, 3) or K.shape != (3, 3):
+        raise ValueError('R and K must be [3,3].')
+    return K @ np.hstack([R, t[:, None]])
+
+
+def pose_from_camera(P, K):
+    """
+    A general 3x4 camera, e.g. one `resect_batch` returned, as the pose `bundle_adjust` takes: (R, t) with K [R | t]
+    nearest to P up to scale.  M = K^-1 P has its sign fixed by det M[:, :3] > 0 and its scale by |det M[:, :3]|^(1/3);
+    R is the rotation nearest to the scaled M[:, :3] (numpy SVD), t its scaled last column.
+    """
+    P, K = np.asarray(P, dtype=np.float64), np.asarray(K, dtype=np.float64)
+    if P.shape != (3, 4) or K.shape != (3, 3):
+        raise ValueError('P must be [3,4] and K [3,3].')
+    M = np.linalg.solve(K, P)
+    det = np.linalg.det(M[:, :3])
+    if not np.isfinite(det) or det == 0:
+        raise ValueError('P has no pose: K^-1 P[:, :3] is singular.')
+    M = M / (np.sign(det) * abs(det) ** (1. / 3))
+    U, _, Vt = np.linalg.svd(M[:, :3])
+    R = U @ np.diag([1., 1., np.linalg.det(U @ Vt)]) @ Vt
+    return R, M[:, 3].copy()
+
+
+def bundle_adjust(coords, sizes, K, poses, track_off, members, X, use=None, fixed=None, huber=float('inf'), max_steps=50,
+                  lambda0=1e-4, ftol=1e-10, gtol=1e-10, cg_tol=1e-8, cg_max=None):
+    """
+    Levenberg-Marquardt refinement of all free cameras and all participating track points over all observations (an
+    addition: the reference stops at two views).  `coords`, `sizes`, (`track_off`, `members`) as `triangulate_tracks`
+    takes them, `X` [ntracks,4] its points, `use` an optional per-track switch (e.g. its ok), `K` one [3,3]
+    calibration or one per view (held fixed), `poses` one [3,4] = [R | t] per view -- None for a view without a
+    camera; `pose_from_camera` makes one of a resected camera --, `fixed` an optional per-view switch.  `huber` is the
+    width of the robust loss in pixels; `cg_max` None means 6 * free cameras + 10.
+
+    Returns (poses [nviews,3,4], X [ntracks,4], info): a track takes part when it is switched on, its X row is finite
+    with X[3] != 0, it has two usable members or more and lies in front of all their cameras; its row comes back as
+    (X, Y, Z, 1), every other row as it came.  info has steps, accepted, stop, tracks, observations, first_cost,
+    last_cost, trace [steps, 6] = (F before, F', lambda, CG iterations, accepted, max |g|), active uint8 [ntracks]
+    and err [nmembers] (the residual norm of every participating member, NaN elsewhere).
+    """
+    arrs = [np.asarray(c) for c in coords]
+    for a in arrs:
+        if a.ndim != 2 or a.shape[1] < 2:
+            raise ValueError('coords must hold one [n, >=2] array per view.')
+    if sizes is None:
+        sizes = [len(a) for a in arrs]
+    nseg, seg = col.offsets_of_sizes(sizes, 'view')
+    if len(arrs) != nseg or any(len(a) != n for a, n in zip(arrs, np.diff(seg))):
+        raise ValueError('coords must hold sizes[v] rows for every view.')
+    Ks, P, mode = col.bundle_cameras(K, poses, fixed, nseg, 'view')
+    mem = np.asarray(members)
+    if mem.size == 0:
+        mem = np.zeros((0, 2), np.int32)
+    if mem.ndim != 2 or mem.shape[1] != 2 or mem.dtype.kind not in 'iu':
+        raise ValueError('members must be integers of shape [nmembers, 2].')
+    off = col.offsets(track_off, 'track_off', len(mem), 'members')
+    mem = np.ascontiguousarray(np.clip(mem, -1, 2 ** 31 - 1), dtype=np.int32)
+    nt, nm = off.size - 1, len(mem)
+    X = np.array(X, dtype=np.float64, order='C')
+    if X.shape != (nt, 4):
+        raise ValueError('X must be [ntracks, 4].')
+    if use is not None:
+        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8).reshape(-1)
+        if use.size != nt:
+            raise ValueError('use must hold one value per track.')
+    huber, max_steps, lambda0, ftol, gtol, cg_tol, cg_max = col.bundle_options(huber, max_steps, lambda0, ftol, gtol,
+                                                                               cg_tol, cg_max, mode)
+    geom = np.zeros((int(seg[-1]), 4), np.float32)
+    for v, a in enumerate(arrs):
+        geom[seg[v]:seg[v + 1], :2] = a[:, :2]
+    err, active = np.full(nm, np.nan), np.zeros(nt, np.uint8)
+    trace, info = np.full((max_steps, 6), np.nan), np.zeros(7)
+    check(clib.spv_bundle_adjust(geom.ctypes.data, seg.ctypes.data, nseg, Ks.ctypes.data, P.ctypes.data, mode.ctypes.data,
+                                 off.ctypes.data, nt, mem.ctypes.data, nm, X.ctypes.data,
+                                 use.ctypes.data if use is not None else None, huber, max_steps, lambda0, ftol, gtol, cg_tol,
+                                 cg_max, err.ctypes.data, active.ctypes.data, trace.ctypes.data, info.ctypes.data))
+    out = col.bundle_info(info, trace)
+    out['active'], out['err'] = active, err
+    return P.reshape(nseg, 3, 4), X, out
+
+
 def resect_batch(xs, Xws, required_percent_inliers=.9, max_error=2., maximum_tries=500, find_best_even_in_failure=False,
                  seeds=None, samples=None, want_tries=False):
     """
