@@ -149,6 +149,29 @@ static void export_items(const std::vector<Item> &its, int32_t *items, long long
   if (items) memcpy(items, its.data(), (size_t)std::min<long long>(items_cap, (long long)its.size()) * sizeof(Item));
 }
 
+// The body of a many-sets fit's *_fit_batch_plan entry behind its argument check: the first round's sets, tries
+// (per_try candidates each), work items and blocks of 256 rows.
+static int fit_batch_plan(void (*first_round)(const long long *, int, int, std::vector<RansacBatchSlot> *), int per_try,
+                          const long long *off, int nsets, int maximum_tries, int compute_units, long long out[4],
+                          int32_t *items, long long items_cap) {
+  if (compute_units < 1 || !out || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
+  std::vector<RansacBatchSlot> slots;
+  std::vector<RansacBatchItem> its;
+  first_round(off, nsets, maximum_tries, &slots);
+  ransac_batch_items(slots, off, compute_units, &its);
+  long long tries = 0, blocks = 0;
+  for (const RansacBatchSlot &s : slots) {
+    tries += s.ncand / per_try;
+    blocks += (s.npt + 255) / 256;
+  }
+  out[0] = (long long)slots.size();
+  out[1] = tries;
+  out[2] = (long long)its.size();
+  out[3] = blocks;
+  export_items<5>(its, items, items_cap);
+  return SPV_OK;
+}
+
 // The body of a *_batch_workspace_bytes query: the bytes of the plan `make` fills, or 0 where it refuses the
 // arguments, with no error left behind.
 template <typename Plan, typename Base, typename Fn>
@@ -1950,22 +1973,7 @@ int spv_ransac_fit_batch_plan(const long long *pair_off, int npairs, int maximum
                               long long out[4], int32_t *items, long long items_cap) {
   return api([&] {
     SPV_TRY(ransac_batch_check(pair_off, npairs, maximum_tries, nullptr));
-    if (compute_units < 1 || !out || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
-    std::vector<RansacBatchSlot> slots;
-    std::vector<RansacBatchItem> its;
-    ransac_batch_first_round(pair_off, npairs, maximum_tries, &slots);
-    ransac_batch_items(slots, pair_off, compute_units, &its);
-    long long tries = 0, blocks = 0;
-    for (const RansacBatchSlot &s : slots) {
-      tries += s.ncand / 3;
-      blocks += (s.npt + 255) / 256;
-    }
-    out[0] = (long long)slots.size();
-    out[1] = tries;
-    out[2] = (long long)its.size();
-    out[3] = blocks;
-    export_items<5>(its, items, items_cap);
-    return (int)SPV_OK;
+    return fit_batch_plan(ransac_batch_first_round, 3, pair_off, npairs, maximum_tries, compute_units, out, items, items_cap);
   });
 }
 int spv_resect_gather_device(const float *d_geom, const int32_t *d_track, const long long *seg_off, int nseg,
@@ -2005,22 +2013,7 @@ int spv_resect_fit_batch_plan(const long long *view_off, int nviews, int maximum
                               int32_t *items, long long items_cap) {
   return api([&] {
     SPV_TRY(resect_check(view_off, nviews, 0.0, 0.0, maximum_tries, nullptr));
-    if (compute_units < 1 || !out || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
-    std::vector<RansacBatchSlot> slots;
-    std::vector<RansacBatchItem> its;
-    resect_first_round(view_off, nviews, maximum_tries, &slots);
-    ransac_batch_items(slots, view_off, compute_units, &its);
-    long long tries = 0, blocks = 0;
-    for (const RansacBatchSlot &s : slots) {
-      tries += s.ncand;
-      blocks += (s.npt + 255) / 256;
-    }
-    out[0] = (long long)slots.size();
-    out[1] = tries;
-    out[2] = (long long)its.size();
-    out[3] = blocks;
-    export_items<5>(its, items, items_cap);
-    return (int)SPV_OK;
+    return fit_batch_plan(resect_first_round, 1, view_off, nviews, maximum_tries, compute_units, out, items, items_cap);
   });
 }
 int spv_dlt_triangulate_batch(const double *x0, const double *x1, const long long *pair_off, int npairs,

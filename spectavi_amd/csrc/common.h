@@ -511,6 +511,7 @@ int ransac_cameras_run(const double *d_Fs, int nF, double ratio_allowed, double 
 int seven_point_run(const double *d_x, const double *d_xp, int n, double *d_Fs, int *d_nroot, double *d_basis,
                     hipStream_t stream);
 int ransac_fit_batch_limit(long long npt);  // tries per batch for this many correspondences
+int ransac_first_step(long long npt, int batch);  // tries of a fit's first batch, of any set of a many-sets fit too
 size_t ransac_fit_workspace_bytes(int batch, long long npt);
 int ransac_fit_run(const double *d_x0, const double *d_x1, long long npt, double required_percent,
                    double max_error, int max_tries, int find_best, double ratio_allowed,
@@ -545,14 +546,7 @@ struct RansacBatchSlot {
 };
 // Row blocks of a set of npt rows: the scorers' workgroups take 256 rows each.
 inline size_t batch_row_blocks(long long npt) { return (size_t)((npt + 255) / 256); }
-// The rule that fills a round of a many-sets fit from its running sets, in order (host only).  A running set `r` (any
-// record with set, npt, done and step) brings its next min(step, what is left of max_tries) tries while the round
-// holds fewer than round_tries tries and less than round_work units of work, a try of a set costing work_per_row x npt;
-// the first set of a round always runs, and a set of which not one more try fits waits with the sets behind it.  A
-// slot counts candidates: per_try of them a try.  who (may be null): the slots' places in `run`.
-template <typename Run>
-void fill_batch_round(const std::vector<Run> &run, int max_tries, int round_tries, long long round_work,
-                      long long work_per_row, int per_try, std::vector<RansacBatchSlot> *slots, std::vector<int> *who);
+// (The rule that fills a round, the round driver and the argument check of a many-sets fit: fit_rounds.h.)
 // The work items of a round, a function of the slots and the compute units alone; host only.
 void ransac_batch_items(const std::vector<RansacBatchSlot> &slots, const long long *pair_off, int cus,
                         std::vector<RansacBatchItem> *items);
@@ -643,7 +637,8 @@ int resect_gather_run(const float *d_geom, const int32_t *d_track, const long lo
                       int nviews, const double *d_X, const uint8_t *d_ok, int ntracks, long long capacity, double *d_x,
                       double *d_Xw, int32_t *d_rows, long long *d_view_off, long long *view_off, hipStream_t stream);
 // The slots of the first round of a fit (host only): every set of >= 6 rows, in order, while the round has room; a
-// slot's cand0 / ncand / cand_base count tries.  Its work items are ransac_batch_items'.
+// slot's cand0 / ncand / cand_base count tries.  Its work items are ransac_batch_items'; the rule that fills a round,
+// the round driver, the heads and the argument check are the two-view fit's too (fit_rounds.h).
 void resect_first_round(const long long *view_off, int nviews, int max_tries, std::vector<RansacBatchSlot> *slots);
 // SPV_ERR_INVALID (message set) for what include/spectavi_amd.h rejects; touches no device, no output
 int resect_check(const long long *view_off, int nviews, double required_percent, double max_error, int max_tries,
@@ -681,27 +676,5 @@ int bundle_adjust_run(const float *d_geom, const long long *seg_off, int nseg, c
                       const long long *track_off, int ntracks, const int32_t *d_members, long long nmembers, double *d_X,
                       const uint8_t *d_use, const BundleAdjustOptions &o, double *d_err, uint8_t *d_active, double *trace,
                       double *info, void *d_ws, size_t ws_bytes, hipStream_t stream);
-
-template <typename Run>
-void fill_batch_round(const std::vector<Run> &run, int max_tries, int round_tries, long long round_work,
-                      long long work_per_row, int per_try, std::vector<RansacBatchSlot> *slots, std::vector<int> *who) {
-  slots->clear();
-  if (who) who->clear();
-  int tries = 0;
-  long long work = 0;
-  for (size_t i = 0; i < run.size(); ++i) {
-    const Run &r = run[i];
-    if (tries >= round_tries || (tries > 0 && work >= round_work)) break;
-    const long long per = work_per_row * r.npt;
-    const long long by_work = tries == 0 ? 2147483647 : (round_work - work) / per;  // the first set always runs
-    if (by_work < 1) break;  // not one more try of this set fits: it waits, and so do the sets behind it
-    const int n = (int)std::min<long long>({(long long)r.step, (long long)(max_tries - r.done), (long long)(round_tries - tries), by_work});
-    if (n <= 0) continue;
-    slots->push_back(RansacBatchSlot{r.set, r.npt, per_try * tries, per_try * n, per_try * r.done});
-    if (who) who->push_back((int)i);
-    tries += n;
-    work += per * n;
-  }
-}
 
 }  // namespace spv

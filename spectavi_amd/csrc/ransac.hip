@@ -13,8 +13,9 @@
 //                        missing roots are NaN, which the stages below treat as "no candidate")
 //   ransac_process_run   (dlt.hip) gate, E, four cameras and the (camera, correspondence) scoring
 //                        grid for all 3 x tries candidates at once -- this is where the time goes
-//   ransac_reduce_kernel the reference's best-model rule (:196-214) over the candidates IN ORDER,
-//                        carried from batch to batch in a small device-resident state
+//   ransac_reduce_kernel the reference's best-model rule (:196-214) over the candidates IN ORDER
+//                        (best_model_device.h, shared with the many-sets fits), carried from batch to
+//                        batch in a small device-resident state
 // The host loop only generates the 7-subsets, looks at 16 bytes of state after each batch (to stop
 // at the first success, as the reference's `if (_success) continue` does) and fetches the winner.
 //
@@ -25,6 +26,7 @@
 // for the restatement it is tested against) with every array in registers: loops fully unrolled, the
 // pivot exchange done with selects.  Products and sums are rounded separately (the library is built
 // with -ffp-contract=off), as in the reference's build.
+#include "best_model_device.h"
 #include "common.h"
 
 #include <math.h>
@@ -292,37 +294,12 @@ __global__ __launch_bounds__(kReduceThreads) void ransac_reduce_kernel(
     const int *__restrict__ ok, const int *__restrict__ count, const double *__restrict__ Fs,
     const double *__restrict__ best_P, int ncand, int cand_base, long long npt, double required_percent,
     int find_best, FitState *__restrict__ state) {
-  __shared__ unsigned int s_first;
-  __shared__ unsigned long long s_best;
-  if (threadIdx.x == 0) {
-    s_first = 0xFFFFFFFFu;
-    s_best = 0ull;
-  }
-  __syncthreads();
-  if (state->success) return;  // uniform: nothing after the first success is looked at
-  unsigned int first = 0xFFFFFFFFu;
-  unsigned long long best = 0ull;
-  for (int i = threadIdx.x; i < ncand; i += kReduceThreads) {
-    if (!ok[i]) continue;
-    const int c = count[i];
-    const double percent = (double)c / (double)npt;
-    if (percent > required_percent) first = min(first, (unsigned int)i);
-    // most inliers, the earliest among equals
-    if (find_best) best = max(best, ((unsigned long long)(unsigned int)c << 32) | (0xFFFFFFFFu - (unsigned int)i));
-  }
-  if (first != 0xFFFFFFFFu) atomicMin(&s_first, first);
-  if (best) atomicMax(&s_best, best);
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  int win = -1, success = 0;
-  if (s_first != 0xFFFFFFFFu) {
-    win = (int)s_first;
-    success = 1;
-  } else if (s_best) {
-    const int c = (int)(s_best >> 32);
-    if (c > (state->found ? state->count : 0)) win = (int)(0xFFFFFFFFu - (unsigned int)(s_best & 0xFFFFFFFFu));
-  }
-  if (win < 0) return;
+  int success;
+  // (state->success is uniform: nothing after the first success is looked at)
+  const int win = best_model<kReduceThreads>(
+      ncand, state->success != 0, (double)npt, state->found ? state->count : 0, find_best,
+      [=](int i) { return ok[i] ? count[i] : -1; }, [=](double share) { return share > required_percent; }, &success);
+  if (threadIdx.x != 0 || win < 0) return;
   state->found = 1;
   state->success = success;
   state->count = count[win];
@@ -363,6 +340,14 @@ int seven_point_sampled_run(const double *d_x0, const double *d_x1, const int *d
 int ransac_fit_batch_limit(long long npt) {
   const long long by_work = 2000000000ll / (12 * std::max<long long>(npt, 1));
   return (int)std::max<long long>(1, std::min<long long>(16383 / 3, by_work));
+}
+
+// Easy problems succeed within a few tries: a fit starts small -- 256 tries, fewer when a try is expensive (about
+// 1e8 (camera, correspondence) solves in the first batch, but at least 8 tries) -- and grows fourfold to the full
+// batch.  With a million correspondences a batch of 174 tries held some fifty models that pass the gate, each
+// scored in full, when the first of them already ended the search.
+int ransac_first_step(long long npt, int batch) {
+  return std::min(batch, (int)std::max<long long>(8, std::min<long long>(256, 100000000ll / (12 * std::max<long long>(npt, 1)))));
 }
 
 namespace {
@@ -425,11 +410,7 @@ int ransac_fit_run(const double *d_x0, const double *d_x1, long long npt, double
   head.found = head.success = head.count = 0;
   head.cand = -1;
   int done = 0;
-  // easy problems succeed within a few tries: start small -- 256 tries, fewer when a try is expensive
-  // (about 1e8 (camera, correspondence) solves in the first batch, but at least 8 tries) -- and grow
-  // fourfold to the full batch.  With a million correspondences a batch of 174 tries held some fifty
-  // models that pass the gate, each scored in full, when the first of them already ended the search.
-  int step = std::min(batch, (int)std::max<long long>(8, std::min<long long>(256, 100000000ll / (12 * std::max<long long>(npt, 1)))));
+  int step = ransac_first_step(npt, batch);  // then fourfold to the full batch
   auto draw = [&](int first, int n, int *dst) -> int {
     next_samples(first, n, dst);
     for (size_t i = 0; i < (size_t)n * 7; ++i)

@@ -4,12 +4,13 @@
 // hundreds of image pairs with a few hundred to a few thousand correspondences each, many of which never succeed
 // and run every try; one after another they are a chain of small launches and host waits on a chip that each of
 // them fills to a few percent.  Here the sets of a collection (rows [pair_off[p], pair_off[p + 1]) of one pair of
-// arrays) advance together, in rounds:
+// arrays) advance together, in rounds.  The rounds are fit_rounds.hip's, which resect_batch.hip shares: the running
+// sets, the rule that fills a round, the upload of its tables, the read-back of the heads, the one stream
+// synchronisation and which sets leave.  This file supplies (kTwoView): 7-subsets drawn by floyd_sample, three
+// candidates a try, sets of 10 rows and more, a round of at most kRoundTries tries and kRoundSolves solves at 12 a
+// row, ransac_fit_run's small-first growth per set (256 tries or fewer, then fourfold to the set's batch), each
+// try's set size as an extra table, and the kernels of a round:
 //
-//   every set that is still running contributes its next block of tries (ransac_fit_run's small-first growth
-//   per set: 256 tries or fewer, then fourfold), as long as the round has room (kRoundTries, kRoundSolves);
-//   one upload brings the round's tables: the 7-subsets as row numbers of the CONCATENATED arrays, each try's
-//   set size, the slots (one per set of the round) and the work items;
 //   seven_point_kernel<true> (ransac.hip) and essential_cameras_kernel (dlt.hip) run unchanged over all tries
 //   and all 3 x tries candidates of the round;
 //   ransac_batch_score_kernel   one workgroup per work item = (<= 256 rows of one set, a range of that set's
@@ -19,9 +20,8 @@
 //   ransac_batch_fallback_kernel the work list, one lane per entry, as dlt_score_fallback_kernel
 //   ransac_batch_select_kernel  select_camera_kernel with the candidate's own set size
 //   ransac_batch_reduce_kernel  ransac_reduce_kernel, one workgroup per set of the round over that set's
-//                               candidates in order, into that set's FitState; the four-int heads of the round's
-//                               sets go to one compact array
-//   one read-back of the heads and one stream synchronisation; sets that succeeded or ran out of tries leave.
+//                               candidates in order (best_model_device.h), into that set's FitState; the
+//                               four-int heads of the round's sets go to one compact array.
 //
 // A last pass scores the kept candidate of every set once more, with masks, through the same kernels.
 //
@@ -35,8 +35,10 @@
 // round and fewer than 4 workgroups per compute unit, every set's candidates are cut into ceil(4 CUs / B)
 // ranges (never below kMinPieceCands candidates a range, so that staging the rows stays a small part of an
 // item).  64 sets of 500 rows are 128 row blocks: uncut they would leave half of the chip idle.
+#include "best_model_device.h"
 #include "common.h"
 #include "dlt_device.h"
+#include "fit_rounds.h"
 #include "host_io.h"
 
 #include <limits.h>
@@ -50,10 +52,6 @@ constexpr long long kRoundSolves = 2000000000ll;    // (camera, correspondence) 
 constexpr int kMinPieceCands = 48;                  // candidates per work item when a set's candidates are cut
 constexpr int kMinSetRows = 10;                     // RansacFitter's constructor limit, here per set: smaller sets are skipped
 constexpr int kBatchReduceThreads = 256;
-
-struct Head {
-  int found, success, count, cand;
-};
 
 // The scorer.  mask4 (the last pass only, where a row meets one candidate): uint8[4, total], camera k of the
 // row's candidate at mask4[k total + row]; rows of gated candidates stay unwritten.
@@ -198,39 +196,16 @@ __global__ __launch_bounds__(kDltThreads) void ransac_batch_select_kernel(
 __global__ __launch_bounds__(kBatchReduceThreads) void ransac_batch_reduce_kernel(
     const RansacBatchSlot *__restrict__ slots, const int *__restrict__ ok, const int *__restrict__ count,
     const double *__restrict__ Fs, const double *__restrict__ best_P, double required_percent, int find_best,
-    FitState *__restrict__ states, Head *__restrict__ heads) {
-  __shared__ unsigned int s_first;
-  __shared__ unsigned long long s_best;
+    FitState *__restrict__ states, FitHead *__restrict__ heads) {
   const RansacBatchSlot sl = slots[blockIdx.x];
   FitState *state = states + sl.set;
-  if (threadIdx.x == 0) {
-    s_first = 0xFFFFFFFFu;
-    s_best = 0ull;
-  }
-  __syncthreads();
-  unsigned int first = 0xFFFFFFFFu;
-  unsigned long long best = 0ull;
-  const bool over = state->success != 0;  // uniform: nothing after the first success is looked at
-  for (int i = threadIdx.x; i < sl.ncand && !over; i += kBatchReduceThreads) {
-    if (!ok[sl.cand0 + i]) continue;
-    const int c = count[sl.cand0 + i];
-    const double percent = (double)c / (double)(long long)sl.npt;
-    if (percent > required_percent) first = min(first, (unsigned int)i);
-    // most inliers, the earliest among equals
-    if (find_best) best = max(best, ((unsigned long long)(unsigned int)c << 32) | (0xFFFFFFFFu - (unsigned int)i));
-  }
-  if (first != 0xFFFFFFFFu) atomicMin(&s_first, first);
-  if (best) atomicMax(&s_best, best);
-  __syncthreads();
+  int success;
+  // (state->success is uniform: nothing after the first success is looked at)
+  const int win = best_model<kBatchReduceThreads>(
+      sl.ncand, state->success != 0, (double)(long long)sl.npt, state->found ? state->count : 0, find_best,
+      [=](int i) { return ok[sl.cand0 + i] ? count[sl.cand0 + i] : -1; },
+      [=](double share) { return share > required_percent; }, &success);
   if (threadIdx.x != 0) return;
-  int win = -1, success = 0;
-  if (s_first != 0xFFFFFFFFu) {
-    win = (int)s_first;
-    success = 1;
-  } else if (s_best) {
-    const int c = (int)(s_best >> 32);
-    if (c > (state->found ? state->count : 0)) win = (int)(0xFFFFFFFFu - (unsigned int)(s_best & 0xFFFFFFFFu));
-  }
   if (win >= 0) {
     const size_t w = (size_t)sl.cand0 + win;
     state->found = 1;
@@ -240,7 +215,7 @@ __global__ __launch_bounds__(kBatchReduceThreads) void ransac_batch_reduce_kerne
     for (int i = 0; i < 9; ++i) state->F[i] = Fs[w * 9 + i];
     for (int i = 0; i < 12; ++i) state->P[i] = best_P[w * 12 + i];
   }
-  heads[blockIdx.x] = Head{state->found, state->success, state->count, state->cand};
+  heads[blockIdx.x] = FitHead{state->found, state->success, state->count, state->cand};
 }
 
 // The last pass's candidates: the kept F of every set, NaN (= gated) where a set kept none.
@@ -271,15 +246,11 @@ unsigned int batch_segment(unsigned long long pairs) {  // entries per shard of 
 }
 constexpr size_t kCountBytes = (size_t)kListShards * kCountStride * sizeof(unsigned int);
 
-int first_step(long long npt, int batch) {  // ransac_fit_run's first batch
-  return std::min(batch, (int)std::max<long long>(8, std::min<long long>(256, 100000000ll / (12 * std::max<long long>(npt, 1)))));
-}
-
 // Scratch of one call, carved once: the round buffers hold `tries` tries and `items` work items, the last pass
 // npairs candidates over `total` rows.
 struct BatchBufs {
   FitState *states;
-  Head *heads;
+  FitHead *heads;
   unsigned char *tables;  // a round's upload: samples, try_npt, slots, items (the last pass: set_npt, items)
   size_t tables_bytes;
   double *Fs, *cams, *best_P;
@@ -290,14 +261,13 @@ struct BatchBufs {
   unsigned char *mask4, *mask;
   size_t end;
 };
-BatchBufs carve(void *base, int npairs, long long total, int tries, size_t items, bool own_mask) {
+BatchBufs carve(void *base, int npairs, long long total, int tries, size_t tables_bytes, bool own_mask) {
   const size_t nc = (size_t)std::max(3 * tries, npairs);
   WsWalk w(base);
   BatchBufs b{};
   b.states = w.take<FitState>((size_t)npairs * sizeof(FitState));
-  b.heads = w.take<Head>((size_t)npairs * sizeof(Head));
-  b.tables_bytes = (size_t)tries * 8 * sizeof(int) + (size_t)npairs * (sizeof(RansacBatchSlot) + sizeof(int)) +
-                   items * sizeof(RansacBatchItem) + 64;
+  b.heads = w.take<FitHead>((size_t)npairs * sizeof(FitHead));
+  b.tables_bytes = tables_bytes;
   b.tables = w.take(b.tables_bytes);
   b.Fs = w.take<double>(nc * 9 * sizeof(double));
   b.cams = w.take<double>(nc * 48 * sizeof(double));
@@ -339,15 +309,13 @@ int score_items(const BatchBufs &b, const RansacBatchItem *d_items, int nitems, 
   return SPV_OK;
 }
 
-size_t row_blocks(long long npt) { return batch_row_blocks(npt); }
-
 }  // namespace
 
 void ransac_batch_items(const std::vector<RansacBatchSlot> &slots, const long long *pair_off, int cus,
                         std::vector<RansacBatchItem> *items) {
   items->clear();
   size_t blocks = 0;
-  for (const RansacBatchSlot &s : slots) blocks += row_blocks(s.npt);
+  for (const RansacBatchSlot &s : slots) blocks += batch_row_blocks(s.npt);
   if (blocks == 0) return;
   const size_t target = 4 * (size_t)std::max(cus, 1);
   const int pieces = (int)std::min<size_t>((target + blocks - 1) / blocks, 1u << 16);
@@ -362,48 +330,22 @@ void ransac_batch_items(const std::vector<RansacBatchSlot> &slots, const long lo
 }
 
 namespace {
-// The running sets of a call and the rule that fills a round from them.
-struct SetRun {
-  int set, npt, done, step, batch;
-};
-void fill_round(std::vector<SetRun> &run, int max_tries, std::vector<RansacBatchSlot> *slots, std::vector<int> *who) {
-  // a try is three candidates of four cameras each: 12 solves a row
-  fill_batch_round(run, max_tries, kRoundTries, kRoundSolves, 12, 3, slots, who);
+// What this fit gives the round driver (fit_rounds.h).  A set's steps are ransac_fit_run's: its first batch, then
+// fourfold up to its full batch.  A try is three candidates of four cameras each: 12 solves a row.
+void two_view_steps(long long npt, int max_tries, int *first, int *top) {
+  *top = std::min(ransac_fit_batch_limit(npt), max_tries);
+  *first = ransac_first_step(npt, *top);
 }
-std::vector<SetRun> running_sets(const long long *pair_off, int npairs, int max_tries) {
-  std::vector<SetRun> run;
-  if (max_tries <= 0) return run;
-  for (int p = 0; p < npairs; ++p) {
-    const long long npt = pair_off[p + 1] - pair_off[p];
-    if (npt < kMinSetRows) continue;
-    const int batch = std::min(ransac_fit_batch_limit(npt), max_tries);
-    run.push_back(SetRun{p, (int)npt, 0, first_step(npt, batch), batch});
-  }
-  return run;
-}
+const FitRoundsOp kTwoView{7, 3, kMinSetRows, kRoundTries, kRoundSolves, 12, two_view_steps, floyd_sample, true};
 }  // namespace
 
 void ransac_batch_first_round(const long long *pair_off, int npairs, int max_tries, std::vector<RansacBatchSlot> *slots) {
-  std::vector<SetRun> run = running_sets(pair_off, npairs, max_tries);
-  fill_round(run, max_tries, slots, nullptr);
+  FitRounds(kTwoView, pair_off, npairs, max_tries).fill_round(slots, nullptr);
 }
 
 int ransac_batch_check(const long long *pair_off, int npairs, int max_tries, const int32_t *samples) {
-  if (npairs < 0) return set_error(SPV_ERR_INVALID, "negative set count");
-  if (npairs > (1 << 20)) return set_error(SPV_ERR_INVALID, "more than 2^20 sets per call");
-  if (max_tries < 0) return set_error(SPV_ERR_INVALID, "negative maximum_tries");
-  if (max_tries > 700000000) return set_error(SPV_ERR_INVALID, "maximum_tries above 7e8 (candidate ids are 32-bit: 3 per try)");
-  SPV_TRY(check_offsets(pair_off, npairs, "pair_off"));
-  if (!samples) return SPV_OK;
-  for (int p = 0; p < npairs; ++p) {
-    const long long npt = pair_off[p + 1] - pair_off[p];
-    if (npt < kMinSetRows) continue;  // a skipped set's subsets are not read
-    const int32_t *s = samples + (size_t)p * max_tries * 7;
-    for (size_t i = 0; i < (size_t)max_tries * 7; ++i)
-      if (s[i] < 0 || s[i] >= npt)
-        return set_error(SPV_ERR_INVALID, "set %d: sample index %d outside [0, %lld)", p, s[i], npt);
-  }
-  return SPV_OK;
+  return fit_sets_check(pair_off, npairs, max_tries, samples, kTwoView.width, kTwoView.min_rows, "pair_off",
+                        "maximum_tries above 7e8 (candidate ids are 32-bit: 3 per try)");
 }
 
 int ransac_fit_batch_run(const double *d_x0, const double *d_x1, const long long *pair_off, int npairs,
@@ -417,141 +359,49 @@ int ransac_fit_batch_run(const double *d_x0, const double *d_x1, const long long
   if (npairs > 0 && (!success || !essential || !camera || !inlier_percent || !n_inliers))
     return set_error(SPV_ERR_INVALID, "null pointer");
   if (total > 0 && (!d_x0 || !d_x1 || !inlier_idx)) return set_error(SPV_ERR_INVALID, "null pointer");
-  std::vector<SetRun> run = running_sets(pair_off, npairs, max_tries);
-  if (!run.empty() && !samples && !seeds) return set_error(SPV_ERR_INVALID, "neither samples nor seeds");
-  for (int p = 0; p < npairs; ++p) {  // what a skipped set reports, and every set before its first round
-    success[p] = 0;
-    inlier_percent[p] = 0.0;
-    n_inliers[p] = 0;
-    if (best_try) best_try[p] = -1;
-    if (best_root) best_root[p] = -1;
-    if (tries_run) tries_run[p] = 0;
-  }
-  if (run.empty()) {
+  FitRounds rounds(kTwoView, pair_off, npairs, max_tries);
+  if (!rounds.empty() && !samples && !seeds) return set_error(SPV_ERR_INVALID, "neither samples nor seeds");
+  const FitOutputs out{success, inlier_percent, n_inliers, best_try, tries_run};
+  fit_outputs_clear(out, npairs);
+  for (int p = 0; p < npairs && best_root; ++p) best_root[p] = -1;
+  if (rounds.empty()) {
     if (d_inlier_mask && total > 0) SPV_HIP_CHECK(hipMemsetAsync(d_inlier_mask, 0, (size_t)total, stream));
     return SPV_OK;
   }
   const int cus = device_cu_count();
-  // the largest round: no set brings more than its batch, the round no more than kRoundTries
-  long long cap_tries = 0;
-  size_t all_blocks = 0;
-  for (const SetRun &r : run) {
-    cap_tries += r.batch;
-    all_blocks += row_blocks(r.npt);
-  }
-  for (int p = 0; p < npairs; ++p) all_blocks += pair_off[p + 1] - pair_off[p] < kMinSetRows ? 1 : 0;  // the last pass's items
-  const int round_cap = (int)std::min<long long>(cap_tries, kRoundTries);
-  const size_t items_cap = all_blocks + 4 * (size_t)cus + (size_t)npairs;
+  rounds.size_scratch(cus);
+  // (the last pass's tables: every set's size, and items that the rounds' cap covers)
+  const size_t tables_bytes = rounds.tables_bytes() + (size_t)npairs * sizeof(int);
   DevBuf ws;
-  const size_t ws_bytes = carve(nullptr, npairs, total, round_cap, items_cap, d_inlier_mask == nullptr).end;
+  const size_t ws_bytes = carve(nullptr, npairs, total, rounds.round_cap(), tables_bytes, d_inlier_mask == nullptr).end;
   SPV_TRY(ws.alloc(ws_bytes));
-  BatchBufs b = carve(ws.p, npairs, total, round_cap, items_cap, d_inlier_mask == nullptr);
+  BatchBufs b = carve(ws.p, npairs, total, rounds.round_cap(), tables_bytes, d_inlier_mask == nullptr);
   if (d_inlier_mask) b.mask = d_inlier_mask;
-  // (error paths below: nothing may still be queued on a caller's stream when the scratch goes back to the pool)
-  struct Drain {
-    hipStream_t st;
-    ~Drain() { (void)hipStreamSynchronize(st); }
-  } drain{stream};
+  StreamDrain drain{stream};
   SPV_HIP_CHECK(hipMemsetAsync(b.states, 0, (size_t)npairs * sizeof(FitState), stream));
 
-  std::vector<std::mt19937> gens;
-  if (!samples) {
-    gens.reserve(run.size());
-    for (const SetRun &r : run) gens.emplace_back(ransac_seed(seeds[r.set]));
-  }
-  std::vector<int> gen_of(run.size());
-  for (size_t i = 0; i < run.size(); ++i) gen_of[i] = (int)i;
-
-  std::vector<RansacBatchSlot> slots;
-  std::vector<RansacBatchItem> items;
-  std::vector<int> who;
-  std::vector<unsigned char> host;
-  std::vector<Head> heads((size_t)npairs);
-  std::vector<Head> last((size_t)npairs, Head{0, 0, 0, -1});  // per set
-  while (!run.empty()) {
-    fill_round(run, max_tries, &slots, &who);
-    ransac_batch_items(slots, pair_off, cus, &items);
-    int ntries = 0;
-    for (const RansacBatchSlot &s : slots) ntries += s.ncand / 3;
-    const int ncand = 3 * ntries;
-    // the round's tables, one upload: samples int[ntries,7] | try_npt int[ntries] | slots | items
-    const size_t off_npt = (size_t)ntries * 7 * sizeof(int), off_slots = off_npt + (size_t)ntries * sizeof(int);
-    const size_t off_items = round_up(off_slots + slots.size() * sizeof(RansacBatchSlot), 16);
-    const size_t bytes = off_items + items.size() * sizeof(RansacBatchItem);
-    if (ntries > round_cap || bytes > b.tables_bytes) return set_error(SPV_ERR_INTERNAL, "round of %d tries, %zu items outgrew its scratch", ntries, items.size());
-    host.resize(bytes);
-    int *h_samples = reinterpret_cast<int *>(host.data());
-    int *h_npt = reinterpret_cast<int *>(host.data() + off_npt);
-    for (size_t k = 0; k < slots.size(); ++k) {
-      const RansacBatchSlot &s = slots[k];
-      const SetRun &r = run[who[k]];
-      const int n = s.ncand / 3, t0 = s.cand0 / 3;
-      int *dst = h_samples + (size_t)t0 * 7;
-      if (samples) {
-        memcpy(dst, samples + ((size_t)s.set * max_tries + r.done) * 7, (size_t)n * 7 * sizeof(int));
-      } else {
-        std::mt19937 &gen = gens[gen_of[who[k]]];
-        for (int t = 0; t < n; ++t) floyd_sample(gen, s.npt, dst + 7 * (size_t)t);
-      }
-      const int row0 = (int)pair_off[s.set];
-      for (size_t i = 0; i < (size_t)n * 7; ++i) dst[i] += row0;  // rows of the concatenated arrays
-      for (int t = 0; t < n; ++t) h_npt[t0 + t] = s.npt;
-    }
-    if (!slots.empty()) memcpy(host.data() + off_slots, slots.data(), slots.size() * sizeof(RansacBatchSlot));
-    if (!items.empty()) memcpy(host.data() + off_items, items.data(), items.size() * sizeof(RansacBatchItem));
-    // (pageable source: the copy has left `host` when the call returns)
-    SPV_HIP_CHECK(hipMemcpyAsync(b.tables, host.data(), bytes, hipMemcpyHostToDevice, stream));
-    const int *d_samples = reinterpret_cast<const int *>(b.tables);
-    const int *d_npt = reinterpret_cast<const int *>(b.tables + off_npt);
-    const RansacBatchSlot *d_slots = reinterpret_cast<const RansacBatchSlot *>(b.tables + off_slots);
-    const RansacBatchItem *d_items = reinterpret_cast<const RansacBatchItem *>(b.tables + off_items);
-    SPV_TRY(seven_point_sampled_run(d_x0, d_x1, d_samples, ntries, b.Fs, stream));
+  SPV_TRY(rounds.run(samples, seeds, false, b.tables, b.heads, stream, [&](const FitRoundTables &t) -> int {
+    const int ncand = 3 * t.ntries;
+    SPV_TRY(seven_point_sampled_run(d_x0, d_x1, t.samples, t.ntries, b.Fs, stream));
     SPV_TRY(ransac_cameras_run(b.Fs, ncand, ratio_allowed, b.cams, b.gated, b.nlive + 1, b.nlive, stream));
-    SPV_TRY(score_items(b, d_items, (int)items.size(), d_x0, d_x1, max_error, ncand, nullptr, total, stream));
+    SPV_TRY(score_items(b, t.items, t.nitems, d_x0, d_x1, max_error, ncand, nullptr, total, stream));
     hipLaunchKernelGGL(ransac_batch_select_kernel, dim3((ncand + kDltThreads - 1) / kDltThreads), dim3(kDltThreads), 0,
-                       stream, (const int *)b.counts, (const int *)b.gated, (const double *)b.cams, ncand, d_npt, 3,
+                       stream, (const int *)b.counts, (const int *)b.gated, (const double *)b.cams, ncand, t.try_npt, 3,
                        required_percent, find_best, b.ok, b.count, b.best_cam, b.best_P);
     SPV_HIP_CHECK(hipGetLastError());
-    {
-      ProfScope prof("ransac_batch_reduce", stream);
-      hipLaunchKernelGGL(ransac_batch_reduce_kernel, dim3((unsigned)slots.size()), dim3(kBatchReduceThreads), 0, stream,
-                         d_slots, (const int *)b.ok, (const int *)b.count, (const double *)b.Fs,
-                         (const double *)b.best_P, required_percent, find_best, b.states, b.heads);
-      SPV_HIP_CHECK(hipGetLastError());
-    }
-    SPV_HIP_CHECK(hipMemcpyAsync(heads.data(), b.heads, slots.size() * sizeof(Head), hipMemcpyDeviceToHost, stream));
-    SPV_HIP_CHECK(hipStreamSynchronize(stream));
-    // sets that succeeded or ran out of tries leave
-    std::vector<char> leaves(run.size(), 0);
-    for (size_t k = 0; k < slots.size(); ++k) {
-      SetRun &r = run[who[k]];
-      const int n = slots[k].ncand / 3;
-      if (n == r.step) r.step = std::min(r.batch, r.step * 4);
-      r.done += n;
-      last[r.set] = heads[k];
-      if (tries_run) tries_run[r.set] = r.done;
-      if (heads[k].success || r.done >= max_tries) leaves[who[k]] = 1;
-    }
-    size_t keep = 0;
-    for (size_t i = 0; i < run.size(); ++i)
-      if (!leaves[i]) {
-        run[keep] = run[i];
-        gen_of[keep] = gen_of[i];
-        ++keep;
-      }
-    run.resize(keep);
-  }
-
+    ProfScope prof("ransac_batch_reduce", stream);
+    hipLaunchKernelGGL(ransac_batch_reduce_kernel, dim3((unsigned)t.nslots), dim3(kBatchReduceThreads), 0, stream, t.slots,
+                       (const int *)b.ok, (const int *)b.count, (const double *)b.Fs, (const double *)b.best_P,
+                       required_percent, find_best, b.states, b.heads);
+    SPV_HIP_CHECK(hipGetLastError());
+    return SPV_OK;
+  }, tries_run));
+  const std::vector<FitHead> &last = rounds.last();
+  fit_outputs_set(out, kTwoView, pair_off, last);
   int nfound = 0;
   for (int p = 0; p < npairs; ++p) {
-    const Head &h = last[p];
-    success[p] = h.success;
-    n_inliers[p] = h.found ? h.count : 0;
-    const long long npt = pair_off[p + 1] - pair_off[p];
-    inlier_percent[p] = npt >= kMinSetRows ? (double)n_inliers[p] / (double)npt : 0.0;
-    if (best_try) best_try[p] = h.found ? h.cand / 3 : -1;
-    if (best_root) best_root[p] = h.found ? h.cand % 3 : -1;
-    nfound += h.found ? 1 : 0;
+    if (best_root) best_root[p] = last[p].found ? last[p].cand % 3 : -1;
+    nfound += last[p].found ? 1 : 0;
   }
   if (nfound == 0) {
     if (d_inlier_mask && total > 0) SPV_HIP_CHECK(hipMemsetAsync(d_inlier_mask, 0, (size_t)total, stream));
@@ -559,7 +409,8 @@ int ransac_fit_batch_run(const double *d_x0, const double *d_x1, const long long
   }
   // the kept candidate of every set once more, this time with masks (same statements per (camera, correspondence),
   // hence the same best camera and the same count); the items cover every row, so every mask byte is written
-  slots.clear();
+  std::vector<RansacBatchSlot> slots;
+  std::vector<RansacBatchItem> items;
   for (int p = 0; p < npairs; ++p) {
     const long long npt = pair_off[p + 1] - pair_off[p];
     if (npt > 0) slots.push_back(RansacBatchSlot{p, (int)npt, p, 1, 0});
@@ -568,7 +419,7 @@ int ransac_fit_batch_run(const double *d_x0, const double *d_x1, const long long
   const size_t off_items = round_up((size_t)npairs * sizeof(int), 16);
   const size_t bytes = off_items + items.size() * sizeof(RansacBatchItem);
   if (bytes > b.tables_bytes) return set_error(SPV_ERR_INTERNAL, "last pass of %zu items outgrew its scratch", items.size());
-  host.assign(bytes, 0);
+  std::vector<unsigned char> host(bytes, 0);
   int *h_npt = reinterpret_cast<int *>(host.data());
   for (int p = 0; p < npairs; ++p) h_npt[p] = (int)std::max<long long>(pair_off[p + 1] - pair_off[p], 1);
   memcpy(host.data() + off_items, items.data(), items.size() * sizeof(RansacBatchItem));

@@ -12,8 +12,12 @@
 //   resect_gather_place_kernel   the flags again, a wave scan, the rows that fit the capacity
 //
 // resect_fit_batch: one camera per set of 2-D / 3-D correspondences.  The sets of a collection advance together in
-// rounds, as in ransac_batch.hip: every running set contributes its next block of tries (256, then fourfold up to
-// 4096) while the round has room; one upload brings the round's subsets, slots and work items;
+// the rounds of fit_rounds.hip, which ransac_batch.hip shares: the running sets, the rule that fills a round, the
+// upload of its subsets, slots and work items, the read-back of the heads, the one stream synchronisation and which
+// sets leave.  This file supplies (kResect): 6-subsets (spv_ransac_sample's first six columns, or the first six of a
+// shuffle for a set under 10 rows), one candidate a try, sets of 6 rows and more, a round of at most kRoundTries
+// tries and kRoundVerdicts verdicts at one a row, 256 tries a set and round, then fourfold up to 4096, no leaving on
+// success where per-try outputs are wanted, and the kernels of a round:
 //   resect_solve_kernel    one try per lane: the unit null vector of the try's 11 x 12 matrix (resect_device.h), and
 //                          the camera's factor of the depth term, 16 doubles a try
 //   resect_score_kernel    the hot path.  One workgroup per work item = (<= 256 rows of one set, a range of that
@@ -21,18 +25,19 @@
 //                          scalar loads, a verdict is 12 fma / mul for P X, one reciprocal with two Newton steps, five
 //                          more for the squared residual and two for the depth term; one ballot and one popcount per
 //                          wave and try, kept in the lane try % 64 and added to the try's counter 64 tries at a time
-//   resect_reduce_kernel   one workgroup per set of the round over that set's tries in order, into the set's state;
-//                          with the per-try outputs it also copies the round's cameras and counts to them
-//   one read-back of the four-int heads and one stream synchronisation; sets that succeeded or ran out of tries leave
-//   (with per-try outputs no set leaves early).
+//   resect_reduce_kernel   one workgroup per set of the round over that set's tries in order (best_model_device.h, a
+//                          share AT the required one succeeds), into the set's state and its four-int head; with
+//                          the per-try outputs it also copies the round's cameras and counts to them.
 // A last pass writes the kept camera's verdict of every row (resect_mask_kernel) with the scorer's very statements.
 //
 // The result does not depend on the cuts: a hypothesis is per try, a verdict per (try, row), counts are integer
 // sums, and the best-model rule is defined on try order.  Only tries_run depends on the rounds.  Work items come from
 // ransac_batch_items, the slice rule of the many-sets RANSAC.
+#include "best_model_device.h"
 #include "common.h"
 #include "device_util.h"
 #include "dlt_device.h"
+#include "fit_rounds.h"
 #include "host_io.h"
 #include "resect_device.h"
 
@@ -139,9 +144,6 @@ struct ResectState {
   int found, success, count, try_;
   double P[kCamStride];  // the kept try's 16 doubles
 };
-struct ResectHead {
-  int found, success, count, try_;
-};
 
 // A row as the scorer keeps it: (u, v) = (x0, x1) / x2 by IEEE division (a third column of 1 leaves them as they
 // are), the point and 1 / X3.
@@ -244,44 +246,24 @@ __global__ __launch_bounds__(kReduceThreads) void resect_reduce_kernel(const Ran
                                                                        const double *__restrict__ cams, double share,
                                                                        int find_best, int max_tries,
                                                                        ResectState *__restrict__ states,
-                                                                       ResectHead *__restrict__ heads,
+                                                                       FitHead *__restrict__ heads,
                                                                        double *__restrict__ try_cams,
                                                                        int32_t *__restrict__ try_inl) {
-  __shared__ unsigned int s_first;
-  __shared__ unsigned long long s_best;
   const RansacBatchSlot sl = slots[blockIdx.x];
   ResectState *state = states + sl.set;
-  if (threadIdx.x == 0) {
-    s_first = 0xFFFFFFFFu;
-    s_best = 0ull;
-  }
-  __syncthreads();
-  unsigned int first = 0xFFFFFFFFu;
-  unsigned long long best = 0ull;
-  const bool over = state->success != 0;  // uniform: nothing after the first success is looked at
-  for (int i = threadIdx.x; i < sl.ncand; i += kReduceThreads) {
-    const int c = counts[sl.cand0 + i];
-    const size_t at = (size_t)sl.set * max_tries + sl.cand_base + i;
-    if (try_inl) try_inl[at] = c;
-    if (try_cams)
-      for (int k = 0; k < 12; ++k) try_cams[at * 12 + k] = cams[(size_t)(sl.cand0 + i) * kCamStride + k];
-    if (over) continue;
-    if ((double)c / (double)sl.npt >= share) first = min(first, (unsigned int)i);
-    // most inliers (at least one), the earliest among equals
-    if (find_best && c > 0) best = max(best, ((unsigned long long)(unsigned int)c << 32) | (0xFFFFFFFFu - (unsigned int)i));
-  }
-  if (first != 0xFFFFFFFFu) atomicMin(&s_first, first);
-  if (best) atomicMax(&s_best, best);
-  __syncthreads();
+  if (try_inl || try_cams)  // every try of the slot, whether or not the set has already succeeded
+    for (int i = threadIdx.x; i < sl.ncand; i += kReduceThreads) {
+      const size_t at = (size_t)sl.set * max_tries + sl.cand_base + i;
+      if (try_inl) try_inl[at] = counts[sl.cand0 + i];
+      if (try_cams)
+        for (int k = 0; k < 12; ++k) try_cams[at * 12 + k] = cams[(size_t)(sl.cand0 + i) * kCamStride + k];
+    }
+  int success;
+  // (state->success is uniform: nothing after the first success is looked at; every try is eligible)
+  const int win = best_model<kReduceThreads>(
+      sl.ncand, state->success != 0, (double)sl.npt, state->found ? state->count : 0, find_best,
+      [=](int i) { return counts[sl.cand0 + i]; }, [=](double s) { return s >= share; }, &success);
   if (threadIdx.x != 0) return;
-  int win = -1, success = 0;
-  if (s_first != 0xFFFFFFFFu) {
-    win = (int)s_first;
-    success = 1;
-  } else if (s_best) {
-    const int c = (int)(s_best >> 32);
-    if (c > (state->found ? state->count : 0)) win = (int)(0xFFFFFFFFu - (unsigned int)(s_best & 0xFFFFFFFFu));
-  }
   if (win >= 0) {
     const size_t w = (size_t)sl.cand0 + win;
     state->found = 1;
@@ -290,7 +272,7 @@ __global__ __launch_bounds__(kReduceThreads) void resect_reduce_kernel(const Ran
     state->try_ = sl.cand_base + win;
     for (int k = 0; k < kCamStride; ++k) state->P[k] = cams[w * kCamStride + k];
   }
-  heads[blockIdx.x] = ResectHead{state->found, state->success, state->count, state->try_};
+  heads[blockIdx.x] = FitHead{state->found, state->success, state->count, state->try_};
 }
 
 // mask[row] = the verdict of the row under the camera its set kept; 0 where the set kept none.  One workgroup per
@@ -316,23 +298,6 @@ __global__ __launch_bounds__(kDltThreads) void resect_mask_kernel(const RansacBa
   mask[row] = inl ? 1 : 0;
 }
 
-// The running sets of a call and the rule that fills a round from them.
-struct SetRun {
-  int set, npt, done, step;
-};
-std::vector<SetRun> running_sets(const long long *view_off, int nviews, int max_tries) {
-  std::vector<SetRun> run;
-  if (max_tries <= 0) return run;
-  for (int p = 0; p < nviews; ++p) {
-    const long long npt = view_off[p + 1] - view_off[p];
-    if (npt >= kResectMinRows) run.push_back(SetRun{p, (int)npt, 0, std::min(kFirstStep, max_tries)});
-  }
-  return run;
-}
-void fill_round(const std::vector<SetRun> &run, int max_tries, std::vector<RansacBatchSlot> *slots, std::vector<int> *who) {
-  fill_batch_round(run, max_tries, kRoundTries, kRoundVerdicts, 1, 1, slots, who);  // a try is one candidate, a verdict a row
-}
-
 // One 6-subset of [0, N) for a set the many-sets sampler does not take (N < 10): the first six of a shuffle.
 void small_sample(std::mt19937 &gen, int N, int *out) {
   int idx[16];
@@ -344,21 +309,36 @@ void small_sample(std::mt19937 &gen, int N, int *out) {
   }
 }
 
+// What this fit gives the round driver (fit_rounds.h).  A set's steps: 256 tries, then fourfold up to 4096.  A
+// sample: spv_ransac_sample's rows, the first six columns, where that sampler takes the set.  A try is one candidate,
+// a verdict a row.
+void resect_steps(long long, int max_tries, int *first, int *top) {
+  *first = std::min(kFirstStep, max_tries);
+  *top = kLastStep;
+}
+void resect_sample(std::mt19937 &gen, int npt, int *out) {
+  int seven[7];
+  if (npt >= 10) floyd_sample(gen, npt, seven);
+  else small_sample(gen, npt, seven);
+  memcpy(out, seven, 6 * sizeof(int));
+}
+const FitRoundsOp kResect{6, 1, kResectMinRows, kRoundTries, kRoundVerdicts, 1, resect_steps, resect_sample, false};
+
 struct FitBufs {
   ResectState *states;
-  ResectHead *heads;
-  unsigned char *tables;  // a round's upload: samples int[tries, 6] | slots | items (the last pass: items)
+  FitHead *heads;
+  unsigned char *tables;  // a round's upload (fit_rounds.h); the last pass: items
   size_t tables_bytes;
   double *cams;
   int *counts;
   size_t end;
 };
-FitBufs carve(void *base, int nviews, int tries, size_t items) {
+FitBufs carve(void *base, int nviews, int tries, size_t tables_bytes) {
   WsWalk w(base);
   FitBufs b{};
   b.states = w.take<ResectState>((size_t)nviews * sizeof(ResectState));
-  b.heads = w.take<ResectHead>((size_t)nviews * sizeof(ResectHead));
-  b.tables_bytes = (size_t)tries * 6 * sizeof(int) + (size_t)nviews * sizeof(RansacBatchSlot) + items * sizeof(RansacBatchItem) + 64;
+  b.heads = w.take<FitHead>((size_t)nviews * sizeof(FitHead));
+  b.tables_bytes = tables_bytes;
   b.tables = w.take(b.tables_bytes);
   b.cams = w.take<double>((size_t)tries * kCamStride * sizeof(double));
   b.counts = w.take<int>(((size_t)tries + 64) * sizeof(int));
@@ -465,28 +445,15 @@ int resect_gather_run(const float *d_geom, const int32_t *d_track, const long lo
 
 // ---- fit: host side ----------------------------------------------------------------------------------------------
 void resect_first_round(const long long *view_off, int nviews, int max_tries, std::vector<RansacBatchSlot> *slots) {
-  fill_round(running_sets(view_off, nviews, max_tries), max_tries, slots, nullptr);
+  FitRounds(kResect, view_off, nviews, max_tries).fill_round(slots, nullptr);
 }
 
 int resect_check(const long long *view_off, int nviews, double required_percent, double max_error, int max_tries,
                  const int32_t *samples) {
-  if (nviews < 0) return set_error(SPV_ERR_INVALID, "negative set count");
-  if (nviews > (1 << 20)) return set_error(SPV_ERR_INVALID, "more than 2^20 sets per call");
-  if (max_tries < 0) return set_error(SPV_ERR_INVALID, "negative maximum_tries");
-  if (max_tries > 700000000) return set_error(SPV_ERR_INVALID, "maximum_tries above 7e8");
   if (max_error != max_error) return set_error(SPV_ERR_INVALID, "max_error is NaN");
   if (required_percent != required_percent) return set_error(SPV_ERR_INVALID, "required_percent_inliers is NaN");
-  SPV_TRY(check_offsets(view_off, nviews, "view_off"));
-  if (!samples) return SPV_OK;
-  for (int p = 0; p < nviews; ++p) {
-    const long long npt = view_off[p + 1] - view_off[p];
-    if (npt < kResectMinRows) continue;  // a skipped set's subsets are not read
-    const int32_t *s = samples + (size_t)p * max_tries * 6;
-    for (size_t i = 0; i < (size_t)max_tries * 6; ++i)
-      if (s[i] < 0 || s[i] >= npt)
-        return set_error(SPV_ERR_INVALID, "set %d: sample index %d outside [0, %lld)", p, s[i], npt);
-  }
-  return SPV_OK;
+  return fit_sets_check(view_off, nviews, max_tries, samples, kResect.width, kResect.min_rows, "view_off",
+                        "maximum_tries above 7e8");
 }
 
 int resect_fit_batch_run(const double *d_x, const double *d_Xw, const long long *view_off, int nviews,
@@ -501,148 +468,53 @@ int resect_fit_batch_run(const double *d_x, const double *d_Xw, const long long 
   if (((reinterpret_cast<uintptr_t>(d_x) | reinterpret_cast<uintptr_t>(d_Xw) | reinterpret_cast<uintptr_t>(d_try_cameras)) & 7) ||
       (reinterpret_cast<uintptr_t>(d_try_inliers) & 3))
     return set_error(SPV_ERR_INVALID, "pointers must be aligned to their element size");
-  std::vector<SetRun> run = running_sets(view_off, nviews, max_tries);
-  if (!run.empty() && !samples && !seeds) return set_error(SPV_ERR_INVALID, "neither samples nor seeds");
-  for (int p = 0; p < nviews; ++p) {  // what a skipped set reports, and every set before its first round
-    success[p] = 0;
-    inlier_percent[p] = 0.0;
-    n_inliers[p] = 0;
-    if (best_try) best_try[p] = -1;
-    if (tries_run) tries_run[p] = 0;
-  }
-  if (run.empty()) {
+  FitRounds rounds(kResect, view_off, nviews, max_tries);
+  if (!rounds.empty() && !samples && !seeds) return set_error(SPV_ERR_INVALID, "neither samples nor seeds");
+  const FitOutputs out{success, inlier_percent, n_inliers, best_try, tries_run};
+  fit_outputs_clear(out, nviews);
+  if (rounds.empty()) {
     if (d_inlier_mask && total > 0) SPV_HIP_CHECK(hipMemsetAsync(d_inlier_mask, 0, (size_t)total, stream));
     return SPV_OK;
   }
   const bool every_try = d_try_cameras || d_try_inliers;
-  const int cus = device_cu_count();
-  // the largest round: no set brings more than kLastStep tries, the round no more than kRoundTries
-  const long long cap_tries = (long long)run.size() * std::min(kLastStep, max_tries);
-  size_t all_blocks = 0;
-  for (int p = 0; p < nviews; ++p) all_blocks += batch_row_blocks(view_off[p + 1] - view_off[p]);
-  const int round_cap = (int)std::min<long long>(cap_tries, kRoundTries);
-  // (ransac_batch_items cuts a set's tries at most ceil(4 cus / blocks) ways)
-  const size_t items_cap = all_blocks + 4 * (size_t)cus + (size_t)nviews;
+  rounds.size_scratch(device_cu_count());
   DevBuf ws;
-  SPV_TRY(ws.alloc(carve(nullptr, nviews, round_cap, items_cap).end));
-  const FitBufs b = carve(ws.p, nviews, round_cap, items_cap);
-  // (error paths below: nothing may still be queued on a caller's stream when the scratch goes back to the pool)
-  struct Drain {
-    hipStream_t st;
-    ~Drain() { (void)hipStreamSynchronize(st); }
-  } drain{stream};
+  SPV_TRY(ws.alloc(carve(nullptr, nviews, rounds.round_cap(), rounds.tables_bytes()).end));
+  const FitBufs b = carve(ws.p, nviews, rounds.round_cap(), rounds.tables_bytes());
+  StreamDrain drain{stream};
   SPV_HIP_CHECK(hipMemsetAsync(b.states, 0, (size_t)nviews * sizeof(ResectState), stream));
   if (every_try) {  // the rows of skipped sets: NaN cameras, zero counts
     if (d_try_inliers) SPV_HIP_CHECK(hipMemsetAsync(d_try_inliers, 0, (size_t)nviews * max_tries * sizeof(int32_t), stream));
     if (d_try_cameras) SPV_HIP_CHECK(hipMemsetAsync(d_try_cameras, 0xFF, (size_t)nviews * max_tries * 12 * sizeof(double), stream));
   }
   const double me2 = max_error < 0 ? -1.0 : max_error * max_error;
-
-  std::vector<std::mt19937> gens;
-  if (!samples) {
-    gens.reserve(run.size());
-    for (const SetRun &r : run) gens.emplace_back(ransac_seed(seeds[r.set]));
-  }
-  std::vector<int> gen_of(run.size());
-  for (size_t i = 0; i < run.size(); ++i) gen_of[i] = (int)i;
-
-  std::vector<RansacBatchSlot> slots;
-  std::vector<RansacBatchItem> items;
-  std::vector<int> who;
-  std::vector<unsigned char> host;
-  std::vector<ResectHead> heads((size_t)nviews);
-  std::vector<ResectHead> last((size_t)nviews, ResectHead{0, 0, 0, -1});  // per set
-  while (!run.empty()) {
-    fill_round(run, max_tries, &slots, &who);
-    ransac_batch_items(slots, view_off, cus, &items);
-    int ntries = 0;
-    for (const RansacBatchSlot &s : slots) ntries += s.ncand;
-    // the round's tables, one upload: samples int[ntries, 6] | slots | items
-    const size_t off_slots = (size_t)ntries * 6 * sizeof(int);
-    const size_t off_items = round_up(off_slots + slots.size() * sizeof(RansacBatchSlot), 16);
-    const size_t bytes = off_items + items.size() * sizeof(RansacBatchItem);
-    if (ntries > round_cap || bytes > b.tables_bytes)
-      return set_error(SPV_ERR_INTERNAL, "round of %d tries, %zu items outgrew its scratch", ntries, items.size());
-    host.resize(bytes);
-    int *h_samples = reinterpret_cast<int *>(host.data());
-    for (size_t k = 0; k < slots.size(); ++k) {
-      const RansacBatchSlot &s = slots[k];
-      const SetRun &r = run[who[k]];
-      int *dst = h_samples + (size_t)s.cand0 * 6;
-      if (samples) {
-        memcpy(dst, samples + ((size_t)s.set * max_tries + r.done) * 6, (size_t)s.ncand * 6 * sizeof(int));
-      } else {
-        std::mt19937 &gen = gens[gen_of[who[k]]];
-        for (int t = 0; t < s.ncand; ++t) {
-          int seven[7];
-          if (s.npt >= 10) floyd_sample(gen, s.npt, seven);  // spv_ransac_sample's rows, the first six columns
-          else small_sample(gen, s.npt, seven);
-          memcpy(dst + 6 * (size_t)t, seven, 6 * sizeof(int));
-        }
-      }
-      const int row0 = (int)view_off[s.set];
-      for (size_t i = 0; i < (size_t)s.ncand * 6; ++i) dst[i] += row0;  // rows of the concatenated arrays
-    }
-    memcpy(host.data() + off_slots, slots.data(), slots.size() * sizeof(RansacBatchSlot));
-    memcpy(host.data() + off_items, items.data(), items.size() * sizeof(RansacBatchItem));
-    // (pageable source: the copy has left `host` when the call returns)
-    SPV_HIP_CHECK(hipMemcpyAsync(b.tables, host.data(), bytes, hipMemcpyHostToDevice, stream));
-    const int *d_samples = reinterpret_cast<const int *>(b.tables);
-    const RansacBatchSlot *d_slots = reinterpret_cast<const RansacBatchSlot *>(b.tables + off_slots);
-    const RansacBatchItem *d_items = reinterpret_cast<const RansacBatchItem *>(b.tables + off_items);
-    SPV_HIP_CHECK(hipMemsetAsync(b.counts, 0, (size_t)ntries * sizeof(int), stream));
+  // with per-try outputs no set leaves early
+  SPV_TRY(rounds.run(samples, seeds, every_try, b.tables, b.heads, stream, [&](const FitRoundTables &t) -> int {
+    SPV_HIP_CHECK(hipMemsetAsync(b.counts, 0, (size_t)t.ntries * sizeof(int), stream));
     {
       ProfScope prof("resect_solve", stream);
-      hipLaunchKernelGGL(resect_solve_kernel, dim3((unsigned)((ntries + kSolveThreads - 1) / kSolveThreads)), dim3(kSolveThreads),
-                         0, stream, d_samples, ntries, d_x, d_Xw, b.cams);
+      hipLaunchKernelGGL(resect_solve_kernel, dim3((unsigned)((t.ntries + kSolveThreads - 1) / kSolveThreads)),
+                         dim3(kSolveThreads), 0, stream, t.samples, t.ntries, d_x, d_Xw, b.cams);
       SPV_HIP_CHECK(hipGetLastError());
     }
     {
       ProfScope prof("resect_score", stream);
-      hipLaunchKernelGGL(resect_score_kernel, dim3((unsigned)items.size()), dim3(kDltThreads), 0, stream, d_items,
+      hipLaunchKernelGGL(resect_score_kernel, dim3((unsigned)t.nitems), dim3(kDltThreads), 0, stream, t.items,
                          (const double *)b.cams, d_x, d_Xw, me2, b.counts);
       SPV_HIP_CHECK(hipGetLastError());
     }
-    {
-      ProfScope prof("resect_reduce", stream);
-      hipLaunchKernelGGL(resect_reduce_kernel, dim3((unsigned)slots.size()), dim3(kReduceThreads), 0, stream, d_slots,
-                         (const int *)b.counts, (const double *)b.cams, required_percent, find_best, max_tries, b.states,
-                         b.heads, d_try_cameras, d_try_inliers);
-      SPV_HIP_CHECK(hipGetLastError());
-    }
-    SPV_HIP_CHECK(hipMemcpyAsync(heads.data(), b.heads, slots.size() * sizeof(ResectHead), hipMemcpyDeviceToHost, stream));
-    SPV_HIP_CHECK(hipStreamSynchronize(stream));
-    // sets that succeeded or ran out of tries leave
-    std::vector<char> leaves(run.size(), 0);
-    for (size_t k = 0; k < slots.size(); ++k) {
-      SetRun &r = run[who[k]];
-      if (slots[k].ncand == r.step) r.step = std::min(kLastStep, r.step * 4);
-      r.done += slots[k].ncand;
-      last[r.set] = heads[k];
-      if (tries_run) tries_run[r.set] = r.done;
-      if ((heads[k].success && !every_try) || r.done >= max_tries) leaves[who[k]] = 1;
-    }
-    size_t keep = 0;
-    for (size_t i = 0; i < run.size(); ++i)
-      if (!leaves[i]) {
-        run[keep] = run[i];
-        gen_of[keep] = gen_of[i];
-        ++keep;
-      }
-    run.resize(keep);
-  }
-
-  for (int p = 0; p < nviews; ++p) {
-    const ResectHead &h = last[p];
-    success[p] = h.success;
-    n_inliers[p] = h.found ? h.count : 0;
-    const long long npt = view_off[p + 1] - view_off[p];
-    inlier_percent[p] = npt >= kResectMinRows ? (double)n_inliers[p] / (double)npt : 0.0;
-    if (best_try) best_try[p] = h.found ? h.try_ : -1;
-  }
+    ProfScope prof("resect_reduce", stream);
+    hipLaunchKernelGGL(resect_reduce_kernel, dim3((unsigned)t.nslots), dim3(kReduceThreads), 0, stream, t.slots,
+                       (const int *)b.counts, (const double *)b.cams, required_percent, find_best, max_tries, b.states,
+                       b.heads, d_try_cameras, d_try_inliers);
+    SPV_HIP_CHECK(hipGetLastError());
+    return SPV_OK;
+  }, tries_run));
+  const std::vector<FitHead> &last = rounds.last();
+  fit_outputs_set(out, kResect, view_off, last);
   if (d_inlier_mask) {
     // the kept camera of every set over all its rows: the scorer's statements, hence the scorer's count
-    items.clear();  // one item per row block of every set, all under "try" 0
+    std::vector<RansacBatchItem> items;  // one item per row block of every set, all under "try" 0
     for (int p = 0; p < nviews; ++p)
       for (long long r = view_off[p]; r < view_off[p + 1]; r += kDltThreads)
         items.push_back(RansacBatchItem{p, (int32_t)r, (int32_t)std::min<long long>(kDltThreads, view_off[p + 1] - r), 0, 1});
