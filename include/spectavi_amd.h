@@ -177,7 +177,7 @@ const char *spv_version(void);
  * "l1k2_tile", "l1k2_merge", "l1k2_batch", "l1k2_batch_merge", "l1k2_guided", "l1k2_guided_merge", "epipolar_lines", "bruteforce", "bruteforce_merge", "ann_prep", "ann_coarse",
  * "ann_merge", "ann_rerank", "cascade_project",
  * "cascade_buckets", "cascade_probe_refine", "cascade_batch_project", "cascade_batch_buckets", "cascade_batch_probe", "dlt", "dlt_batch", "dlt_batch_scan", "rectify", "rectify_batch_bounds", "rectify_batch_box",
- * "rectify_batch", "ransac_batch_score",
+ * "rectify_batch", "stereo_batch", "stereo_keep_batch", "stereo_matches_count", "stereo_matches_fill", "ransac_batch_score",
  * "ransac_batch_reduce",
  * "gather_match_coords_batch", "normalize_batch_stats", "normalize_batch_finish", "normalize_batch", "tracks_init", "tracks_hook",
  * "tracks_flatten", "tracks_sizes", "tracks_scan", "tracks_place", "tracks_order", "tracks_flags",
@@ -945,6 +945,74 @@ int spv_rectify_batch_device(const void *d_images, int dtype, const int32_t *siz
                              double sampling_factor, const int32_t *pairs, int npairs, const double *P0s,
                              const double *P1s, const int32_t *use, const int32_t *box, void *d_r0, void *d_r1,
                              int32_t *d_ri0, int32_t *d_ri1, void *stream);
+
+/* Dense disparity of every rectified pair of a collection (stereo_batch.hip): block matching along the rows of the
+ * windows spv_rectify_batch_device wrote, by an integer sum of absolute differences on 8-bit gray values (nchan 1,
+ * SPV_RECTIFY_U8; nothing else has this step).  box: HOST int32[npairs, 4] = (row_lo, row_hi, col_lo, col_hi) per pair,
+ * rectify_batch's boxes; pair p's window has R = row_hi - row_lo rows and C = col_hi - col_lo columns and owns samples
+ * [out_off[p], out_off[p + 1]) of every flat array below, row-major, out_off the running sum of the areas R * C of ALL
+ * pairs (a pair that is not used keeps its window).  use: HOST int32[npairs] or NULL (every pair).
+ *
+ * 1. Cost and winner (spv_stereo_batch_device).  d_r0, d_r1 uint8 and d_ri0, d_ri1 int32, [samples]: rectify_batch's
+ * outputs.  radius r in 0..7; drange HOST int32[npairs, 2] = (d_lo, d_hi) per pair.  swap 0: image 0 (d_r0, d_ri0) is
+ * the reference, image 1 the other; swap 1: the roles are exchanged, drange is taken as given.  For the reference
+ * sample (y, x) and a disparity d the candidate is (y, x + d) of the other image and
+ *     cost(y, x, d) = sum over dy, dx in [-r, r] of |ref[y + dy, x + dx] - oth[y + dy, x + d + dx]|.
+ * d is admissible for (y, x) iff r <= y < R - r, r <= x < C - r and r <= x + d < C - r (both blocks inside the
+ * window), ri_ref[y, x] != -1, ri_oth[y, x + d] != -1 and d_lo <= d <= d_hi.  Only the two centres are tested for
+ * validity: an invalid sample inside a block counts with the value 0 rectification gave it.  Outputs, one per sample
+ * of every window, each element written exactly once:
+ *   d_disp   int32: the admissible d of smallest (cost, d), lexicographic -- among equal costs the smallest d --,
+ *            SPV_STEREO_NONE where no d is admissible
+ *   d_cost   uint16_t: that cost (at most 225 * 255 = 57375), 0xFFFF where none
+ *   d_cost2  uint16_t: the smallest cost over the admissible d' with |d' - disp| >= 2, 0xFFFF where there is none
+ * A pair with use[p] == 0 gets SPV_STEREO_NONE / 0xFFFF / 0xFFFF over its whole window; an empty box owns nothing.
+ * SPV_ERR_INVALID, nothing launched, outputs untouched: radius outside 0..7; d_lo > d_hi, |d_lo| or |d_hi| > 32767
+ * (of a used pair); a box with a negative entry or row_lo > row_hi or col_lo > col_hi (of any pair); npairs < 0 or
+ * above 2^20; 2^31 samples or more; a null pointer where there are samples.  Asynchronous on `stream`: the pair
+ * table is uploaded into a buffer the calling thread keeps between calls (one per value of swap), so a call waits
+ * only for the same thread's previous call of the same swap to have left the device.
+ * Kernel name for spv_profile_read: "stereo_batch" (one bracket per call: the kernel of the call's radius over the
+ * items, and the kernel that fills the windows of the pairs that are not used, where there are any).
+ *
+ * Plan (spv_stereo_batch_plan): host only.  out[3] = {used pairs, items, samples}; out_off long long[npairs + 1];
+ * items NULL or int32[items_cap, 4] = (pair, first window row, rows <= 4, first window column): an item is one
+ * workgroup step over a band of rows and a tile of at most 64 columns; the items of the used pairs with a non-empty
+ * window cover every (row, column) of those windows exactly once.  drange may be NULL (not checked then).
+ *
+ * 2. Keep mask (spv_stereo_keep_batch_device).  d_disp0, d_cost0, d_cost20: a swap = 0 result; d_disp1: the disp of
+ * a swap = 1 run or NULL; lr_tol >= 0; uniqueness in 0..100.  d_keep uint8[samples], every element written:
+ * keep[y, x] = 1 iff disp0[y, x] != SPV_STEREO_NONE; and, where d_disp1 is given, with x' = x + disp0[y, x]:
+ * 0 <= x' < C, disp1[y, x'] != SPV_STEREO_NONE and |disp0[y, x] + disp1[y, x']| <= lr_tol; and
+ * cost0 * 100 <= cost20 * (100 - uniqueness) in 32-bit unsigned arithmetic, 0xFFFF taking part as 65535.  Else 0.
+ * Kernel name: "stereo_keep_batch".
+ *
+ * 3. Correspondences (spv_stereo_matches_batch_device).  The kept samples of all pairs in order -- pair by pair,
+ * row-major inside a window -- compacted by scans (no atomic decides a position).  sizes HOST int32[nimg, 2] =
+ * (wid, hgt) and pairs HOST int32[npairs, 2] as spv_rectify_batch takes them (the two images of a pair may differ in
+ * width here).  Kept sample (y, x) with d = disp0[y, x] has the source pixels s0 = ri0[y, x], s1 = ri1[y, x + d]:
+ *   d_x0, d_x1  double[capacity, 3]: (s0 % wid0, s0 / wid0, 1.) and (s1 % wid1, s1 / wid1, 1.)
+ *   d_rows      int32[capacity]: the sample's number inside its window, y * C + x
+ *   d_pair_off  long long[npairs + 1]: pair p's matches are [pair_off[p], pair_off[p + 1])
+ * These are the x0, x1, pair_off of spv_dlt_triangulate_batch_device with pixel cameras.  Only the first `capacity`
+ * matches are written, nothing past them; d_pair_off always holds the true counts, so a call with capacity 0 (d_x0,
+ * d_x1, d_rows may be NULL then) counts.  d_keep must be 0 wherever disp0 is not an admissible disparity (what step 2
+ * writes); a kept sample whose candidate is outside its window is written with s1 = -1.  Asynchronous on `stream`,
+ * the scratch of the scan taken from the library's device cache.  Kernel names: "stereo_matches_count" (the counts of
+ * blocks of 1024 samples, their scan and pair_off), "stereo_matches_fill". */
+#define SPV_STEREO_NONE (-2147483647 - 1)
+int spv_stereo_batch_plan(const int32_t *box, int npairs, const int32_t *use, int radius, const int32_t *drange,
+                          long long out[3], long long *out_off, int32_t *items, long long items_cap);
+int spv_stereo_batch_device(const uint8_t *d_r0, const uint8_t *d_r1, const int32_t *d_ri0, const int32_t *d_ri1,
+                            const int32_t *box, int npairs, const int32_t *use, int radius, const int32_t *drange,
+                            int swap, int32_t *d_disp, void *d_cost, void *d_cost2, void *stream);
+int spv_stereo_keep_batch_device(const int32_t *box, int npairs, const int32_t *d_disp0, const void *d_cost0,
+                                 const void *d_cost20, const int32_t *d_disp1, int lr_tol, int uniqueness,
+                                 uint8_t *d_keep, void *stream);
+int spv_stereo_matches_batch_device(const int32_t *box, int npairs, const int32_t *sizes, int nimg,
+                                    const int32_t *pairs, const int32_t *d_disp0, const uint8_t *d_keep,
+                                    const int32_t *d_ri0, const int32_t *d_ri1, long long capacity, double *d_x0,
+                                    double *d_x1, int32_t *d_rows, long long *d_pair_off, void *stream);
 
 /* sift_filter with a status.  out: float32 NdArray, allocated by the callee. */
 int spv_sift_filter(const float *im, int wid, int hgt, NdArray *out);

@@ -2280,6 +2280,48 @@ int spv_rectify_batch_device(const void *d_images, int dtype, const int32_t *siz
   });
 }
 
+int spv_stereo_batch_plan(const int32_t *box, int npairs, const int32_t *use, int radius, const int32_t *drange,
+                          long long out[3], long long *out_off, int32_t *items, long long items_cap) {
+  return api([&] {
+    if (!out || !out_off || items_cap < 0) return set_error(SPV_ERR_INVALID, "bad arguments");
+    StereoBatchPlan pl;
+    SPV_TRY(stereo_batch_plan(box, npairs, use, radius, drange, &pl));
+    out[0] = pl.used;
+    out[1] = (long long)pl.items.size();
+    out[2] = pl.out_off[npairs];
+    memcpy(out_off, pl.out_off.data(), ((size_t)npairs + 1) * sizeof(long long));
+    export_items<4>(pl.items, items, items_cap);
+    return (int)SPV_OK;
+  });
+}
+int spv_stereo_batch_device(const uint8_t *d_r0, const uint8_t *d_r1, const int32_t *d_ri0, const int32_t *d_ri1,
+                            const int32_t *box, int npairs, const int32_t *use, int radius, const int32_t *drange,
+                            int swap, int32_t *d_disp, void *d_cost, void *d_cost2, void *stream) {
+  return api([&] {
+    return stereo_batch_run(d_r0, d_r1, d_ri0, d_ri1, box, npairs, use, radius, drange, swap, d_disp,
+                            static_cast<uint16_t *>(d_cost), static_cast<uint16_t *>(d_cost2),
+                            static_cast<hipStream_t>(stream));
+  });
+}
+int spv_stereo_keep_batch_device(const int32_t *box, int npairs, const int32_t *d_disp0, const void *d_cost0,
+                                 const void *d_cost20, const int32_t *d_disp1, int lr_tol, int uniqueness,
+                                 uint8_t *d_keep, void *stream) {
+  return api([&] {
+    return stereo_keep_batch_run(box, npairs, d_disp0, static_cast<const uint16_t *>(d_cost0),
+                                 static_cast<const uint16_t *>(d_cost20), d_disp1, lr_tol, uniqueness, d_keep,
+                                 static_cast<hipStream_t>(stream));
+  });
+}
+int spv_stereo_matches_batch_device(const int32_t *box, int npairs, const int32_t *sizes, int nimg,
+                                    const int32_t *pairs, const int32_t *d_disp0, const uint8_t *d_keep,
+                                    const int32_t *d_ri0, const int32_t *d_ri1, long long capacity, double *d_x0,
+                                    double *d_x1, int32_t *d_rows, long long *d_pair_off, void *stream) {
+  return api([&] {
+    return stereo_matches_batch_run(box, npairs, sizes, nimg, pairs, d_disp0, d_keep, d_ri0, d_ri1, capacity, d_x0,
+                                    d_x1, d_rows, d_pair_off, static_cast<hipStream_t>(stream));
+  });
+}
+
 size_t spv_sift_workspace_bytes(int wid, int hgt) {
   if (sift_check(wid, hgt) != SPV_OK) {
     clear_error();

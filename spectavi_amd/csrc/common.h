@@ -396,6 +396,36 @@ int rectify_batch_run(const void *d_images, int dtype, const int32_t *sizes, int
                       const int32_t *pairs, int npairs, const double *P0s, const double *P1s, const int32_t *use,
                       const int32_t *box, void *d_r0, void *d_r1, int32_t *d_ri0, int32_t *d_ri1, hipStream_t stream);
 
+// ---- dense SAD disparity of many rectified pairs (stereo_batch.hip) ---------------------
+constexpr int kStereoRows = 4;          // window rows per work item: one wave each
+constexpr int kStereoCols = 64;         // window columns per work item: one lane each
+constexpr int kStereoGroupsPerCu = 32;  // the grid cap: workgroups per compute unit, each walking its items
+// One workgroup's share of a collection: rows [row0, row0 + rows) and columns [col0, min(col0 + 64, C)) of pair
+// `pair`'s window.
+struct StereoBatchItem {
+  int32_t pair, row0, rows, col0;
+};
+// Everything stereo_batch_run launches for a collection, a function of the boxes and `use` alone.
+struct StereoBatchPlan {
+  long long used = 0;
+  std::vector<long long> out_off;      // [npairs + 1]: the running areas of all boxes
+  std::vector<StereoBatchItem> items;  // pair by pair, band by band, tile by tile: used pairs only
+};
+// SPV_ERR_INVALID (message set, *p untouched) for what include/spectavi_amd.h rejects; drange may be null; host only
+int stereo_batch_plan(const int32_t *box, int npairs, const int32_t *use, int radius, const int32_t *drange,
+                      StereoBatchPlan *p);
+// Device outputs as in include/spectavi_amd.h; asynchronous on `stream`.
+int stereo_batch_run(const uint8_t *d_r0, const uint8_t *d_r1, const int32_t *d_ri0, const int32_t *d_ri1,
+                     const int32_t *box, int npairs, const int32_t *use, int radius, const int32_t *drange, int swap,
+                     int32_t *d_disp, uint16_t *d_cost, uint16_t *d_cost2, hipStream_t stream);
+int stereo_keep_batch_run(const int32_t *box, int npairs, const int32_t *d_disp0, const uint16_t *d_cost0,
+                          const uint16_t *d_cost20, const int32_t *d_disp1, int lr_tol, int uniqueness, uint8_t *d_keep,
+                          hipStream_t stream);
+int stereo_matches_batch_run(const int32_t *box, int npairs, const int32_t *sizes, int nimg, const int32_t *pairs,
+                             const int32_t *d_disp0, const uint8_t *d_keep, const int32_t *d_ri0, const int32_t *d_ri1,
+                             long long capacity, double *d_x0, double *d_x1, int32_t *d_rows, long long *d_pair_off,
+                             hipStream_t stream);
+
 // ---- vlfeat-exact SIFT (sift.hip) ----------------------------------------------------
 constexpr int kSiftMaxSide = 8192;  // candidates pack x, y of octave -1 in 15 bits each; counts stay below 2^31
 int sift_check(int wid, int hgt);   // SPV_ERR_INVALID (message set) outside the header's limits

@@ -1556,6 +1556,168 @@ def rectify_batch_view(flat, p, box, out_off, nchan=1):
     return w.reshape(rows, cols) if nchan == 1 else w.reshape(rows, cols, nchan)
 
 
+STEREO_NONE = -2**31  # SPV_STEREO_NONE: the disparity of a sample that admits none
+
+
+def _stereo_batch_args(box, use=None, drange=None, radius=None):
+    """box -> int32[npairs, 4], use -> int32[npairs] or None, drange -> int32[npairs, 2] (one (d_lo, d_hi) for
+    every pair is broadcast) or None.  ValueError where the counts disagree or radius is outside 0..7; the library
+    checks the rest.  Touches no device."""
+    box = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 4)
+    npairs = len(box)
+    use = col.use_flags(use, npairs, "pair")
+    if drange is not None:
+        drange = np.asarray(drange, dtype=np.int32)
+        if drange.shape == (2,):
+            drange = np.tile(drange, (npairs, 1))
+        drange = np.ascontiguousarray(drange).reshape(-1, 2)
+        if len(drange) != npairs:
+            raise ValueError("drange must hold one (d_lo, d_hi), or one per pair")
+    if radius is not None and not 0 <= int(radius) <= 7:
+        raise ValueError("radius must be in 0..7")
+    return box, use, drange
+
+
+def _stereo_samples(box):
+    return int(((box[:, 1] - box[:, 0]).astype(np.int64) * (box[:, 3] - box[:, 2])).sum())
+
+
+def _need_samples(t, dtype, name, samples, exact=False):
+    """t: a contiguous CUDA tensor of `dtype` with at least `samples` elements (a caller-allocated output or a
+    per-sample result) or, with exact, with `samples` elements and no more: what rectify_batch() returns for gray
+    images.  The rectified values of images with more channels hold samples * nchan elements and are refused here,
+    since the library is given no channel count."""
+    _need(t, dtype, name)
+    if exact and t.numel() != samples:
+        raise ValueError("%s must hold exactly the %d samples of the windows, one element per sample (gray images, "
+                         "nchan == 1, only); it has %d elements" % (name, samples, t.numel()))
+    if t.numel() < samples:
+        raise ValueError("%s is too short for the %d samples of the windows" % (name, samples))
+
+
+def stereo_batch_plan(box, use=None, radius=0, drange=None, want_items=False):
+    """What stereo_batch() writes and launches for a collection of windows (spv_stereo_batch_plan; host only, no
+    device touched): dict of pairs (used pairs), items (workgroup steps), samples and out_off, an int64 ndarray
+    [npairs + 1] -- the running areas of all boxes.  With want_items also the items, int32[items, 4] = (pair, first
+    window row, rows <= 4, first window column of a tile of at most 64)."""
+    box, use, drange = _stereo_batch_args(box, use, drange)
+    out_off = np.zeros(len(box) + 1, np.int64)
+    args = (box.ctypes.data, len(box), _ptr(use), int(radius), _ptr(drange))
+    out, items = _plan_items(clib.spv_stereo_batch_plan, args, 3, 4, want_items, at=1, tail=(out_off.ctypes.data,))
+    plan = dict(pairs=out[0], items=out[1], samples=out[2], out_off=out_off)
+    return (plan, items) if want_items else plan
+
+
+def stereo_batch_into(r0, r1, ri0, ri1, box, use, radius, drange, swap, disp, cost, cost2):
+    """One direction of stereo_batch() into caller-allocated flat tensors (spv_stereo_batch_device): disp int32,
+    cost and cost2 uint16, at least `samples` elements each; r0, r1, ri0, ri1 exactly `samples`, which refuses the
+    rectified values of images with more than one channel.  Asynchronous on the current stream."""
+    box, use, drange = _stereo_batch_args(box, use, drange, radius)
+    if drange is None:
+        raise ValueError("drange is needed")
+    samples = _stereo_samples(box)
+    for t, dt, name in ((r0, torch.uint8, "r0"), (r1, torch.uint8, "r1"), (ri0, torch.int32, "ri0"), (ri1, torch.int32, "ri1")):
+        _need_samples(t, dt, name, samples, exact=True)
+    for t, dt, name in ((disp, torch.int32, "disp"), (cost, torch.uint16, "cost"), (cost2, torch.uint16, "cost2")):
+        _need_samples(t, dt, name, samples)
+    with _on_device_of(r0, r1, ri0, ri1, disp, cost, cost2) as stream:
+        check(clib.spv_stereo_batch_device(r0.data_ptr(), r1.data_ptr(), ri0.data_ptr(), ri1.data_ptr(), box.ctypes.data,
+                                           len(box), _ptr(use), int(radius), drange.ctypes.data, int(swap),
+                                           disp.data_ptr(), cost.data_ptr(), cost2.data_ptr(), stream))
+
+
+def stereo_batch(r0, r1, ri0, ri1, box, drange, radius=3, use=None, swap=0, both=False):
+    """Dense block-matching disparity of every rectified pair of a collection (spv_stereo_batch_device): r0, r1
+    (uint8) and ri0, ri1 (int32) the flat outputs of rectify_batch() for gray 8-bit images, box its boxes.  For the
+    reference sample (y, x) and every d of drange = (d_lo, d_hi) (one for all pairs, or [npairs, 2]) the cost is the
+    sum of absolute differences of the (2 radius + 1)^2 blocks around (y, x) and (y, x + d) of the other image; d is
+    admissible where both blocks are inside the window and both centres are valid samples.  Returns flat CUDA tensors
+    (disp int32, cost uint16, cost2 uint16): the admissible d of smallest (cost, d), STEREO_NONE where there is none;
+    its cost; the smallest cost at |d' - disp| >= 2 (0xFFFF where none).  rectify_batch_view() shows a pair's window
+    of any of them.  swap=1 exchanges the roles of the two images (drange as given).  both=True returns
+    (result of swap 0, result of swap 1 with the range (-d_hi, -d_lo)).  Asynchronous on the current stream; exactly
+    the integers of the numpy statement of the contract."""
+    box, use, drange = _stereo_batch_args(box, use, drange, radius)
+    if drange is None:
+        raise ValueError("drange is needed")
+    samples = _stereo_samples(box)
+    for t, dt, name in ((r0, torch.uint8, "r0"), (r1, torch.uint8, "r1"), (ri0, torch.int32, "ri0"), (ri1, torch.int32, "ri1")):
+        _need_samples(t, dt, name, samples, exact=True)  # (before anything is allocated from them)
+
+    def run(sw, rng):
+        out = (torch.empty(samples, dtype=torch.int32, device=r0.device),
+               torch.empty(samples, dtype=torch.uint16, device=r0.device),
+               torch.empty(samples, dtype=torch.uint16, device=r0.device))
+        stereo_batch_into(r0, r1, ri0, ri1, box, use, radius, rng, sw, *out)
+        return out
+    if not both:
+        return run(int(swap), drange)
+    return run(0, drange), run(1, np.ascontiguousarray(-drange[:, ::-1]))
+
+
+def stereo_keep_batch(box, disp0, cost0, cost20, disp1=None, lr_tol=1, uniqueness=10):
+    """Which samples of a stereo_batch() result to keep (spv_stereo_keep_batch_device): a flat uint8 CUDA tensor, 1
+    where disp0 is a disparity, the left-right check holds -- with disp1, the disp of the swap=1 run: the sample
+    x + disp0 of the same row has a disparity there and |disp0 + disp1| <= lr_tol -- and the best cost is unique:
+    cost0 * 100 <= cost20 * (100 - uniqueness).  Asynchronous on the current stream."""
+    box, _, _ = _stereo_batch_args(box)
+    if lr_tol < 0 or not 0 <= uniqueness <= 100:
+        raise ValueError("lr_tol must be >= 0 and uniqueness in 0..100")
+    samples = _stereo_samples(box)
+    _need_samples(disp0, torch.int32, "disp0", samples)
+    _need_samples(cost0, torch.uint16, "cost0", samples)
+    _need_samples(cost20, torch.uint16, "cost20", samples)
+    if disp1 is not None:
+        _need_samples(disp1, torch.int32, "disp1", samples)
+    kept = torch.empty(samples, dtype=torch.uint8, device=disp0.device)
+    with _on_device_of(disp0, cost0, cost20, disp1, kept) as stream:
+        check(clib.spv_stereo_keep_batch_device(box.ctypes.data, len(box), disp0.data_ptr(), cost0.data_ptr(),
+                                                cost20.data_ptr(), None if disp1 is None else disp1.data_ptr(),
+                                                int(lr_tol), int(uniqueness), kept.data_ptr(), stream))
+    return kept
+
+
+def stereo_matches_batch(box, sizes, pairs, disp0, keep, ri0, ri1, capacity=None):
+    """The kept samples of every pair as pixel correspondences (spv_stereo_matches_batch_device), pair by pair and
+    row-major inside a window: (x0, x1, rows, pair_off) with x0, x1 float64 CUDA [n, 3] = (column, row, 1) of the
+    source pixels in image 0 and image 1 of the pair (sizes, pairs as rectify_batch() takes them), rows int32 [n] the
+    sample's number inside its window, pair_off an int64 ndarray [npairs + 1] -- what dlt_triangulate_batch() takes,
+    with pixel cameras.  The call counts first and reads pair_off back to size the outputs: its one synchronisation.
+    With capacity the outputs hold that many rows, only the first capacity matches are written and pair_off still
+    reports the true counts."""
+    box, _, _ = _stereo_batch_args(box)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1, 2)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if len(pairs) != len(box):
+        raise ValueError("box and pairs must hold one entry per pair")
+    samples = _stereo_samples(box)
+    _need_samples(disp0, torch.int32, "disp0", samples)
+    _need_samples(keep, torch.uint8, "keep", samples)
+    _need_samples(ri0, torch.int32, "ri0", samples, exact=True)
+    _need_samples(ri1, torch.int32, "ri1", samples, exact=True)
+    d_off = torch.empty(len(box) + 1, dtype=torch.int64, device=disp0.device)
+
+    def call(cap, x0, x1, rows):
+        with _on_device_of(disp0, keep, ri0, ri1, d_off, x0, x1, rows) as stream:
+            check(clib.spv_stereo_matches_batch_device(box.ctypes.data, len(box), sizes.ctypes.data, len(sizes),
+                                                       pairs.ctypes.data, disp0.data_ptr(), keep.data_ptr(),
+                                                       ri0.data_ptr(), ri1.data_ptr(), int(cap),
+                                                       None if x0 is None else x0.data_ptr(),
+                                                       None if x1 is None else x1.data_ptr(),
+                                                       None if rows is None else rows.data_ptr(), d_off.data_ptr(), stream))
+    call(0, None, None, None)
+    pair_off = d_off.cpu().numpy()  # the call's one synchronisation
+    n = int(pair_off[-1]) if capacity is None else int(capacity)
+    if n < 0:
+        raise ValueError("negative capacity")
+    x0 = torch.empty((n, 3), dtype=torch.float64, device=disp0.device)
+    x1 = torch.empty((n, 3), dtype=torch.float64, device=disp0.device)
+    rows = torch.empty(n, dtype=torch.int32, device=disp0.device)
+    if n > 0:
+        call(n, x0, x1, rows)
+    return x0, x1, rows, pair_off
+
+
 def sift_into(im, table, count, workspace=None):
     """vlfeat-exact SIFT of im (float32 [H, W] CUDA tensor) into table (float32 [capacity, 132]): rows
     [0, min(n, capacity)) are written and count (int32 [1]) receives the true row count n.

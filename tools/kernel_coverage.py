@@ -140,7 +140,7 @@ def main():
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("--list", action="store_true", help="list the instantiations (no GPU needed)")
     g.add_argument("--trace", metavar="DIR", help="rocprofv3 --kernel-trace --output-format csv output directory")
-    ap.add_argument("--files", default="l1k2.hip,bruteforce.hip,cascade.hip,cascade_kernels.h,cascade_batch.hip,sift.hip,rectify_batch.hip,normalize_batch.hip,tracks_batch.hip,tracks_triangulate.hip,resect_batch.hip,bundle_adjust.hip",
+    ap.add_argument("--files", default="l1k2.hip,bruteforce.hip,cascade.hip,cascade_kernels.h,cascade_batch.hip,sift.hip,rectify_batch.hip,stereo_batch.hip,normalize_batch.hip,tracks_batch.hip,tracks_triangulate.hip,resect_batch.hip,bundle_adjust.hip",
                     help="source files to report (comma separated; 'all' for every file)")
     ap.add_argument("--strict", action="store_true", help="exit 1 if an instantiation never ran")
     a = ap.parse_args()
